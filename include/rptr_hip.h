@@ -273,10 +273,11 @@ typedef struct RptrSceneDesc {
 #define RPTR_HIP_ABI_VERSION 5
 /* RptrCreateInfo.flags */
 #define RPTR_CREATE_SET_HW_QUEUES 1u /* rptr_hip_create may set the HIP runtime's GPU_MAX_HW_QUEUES for the WHOLE host process (setenv) when the
-                                      * variable is unset or smaller than frames_in_flight + 2 -- effective only when the process has made no HIP
-                                      * call yet (the runtime reads the variable once). For hosts that own their process (bin/rptr_hip sets it);
-                                      * an embedded plugin leaves it clear and the library never edits its host's environment: it then notes on
-                                      * stderr, once, when the frame contexts outnumber the hardware queues (option "quiet" silences it). */
+                                      * variable is unset -- to 2, the most hardware queues the library asks for in one process (a card's queue
+                                      * slots are shared by every process on it; frame contexts beyond that share queues) -- effective only when
+                                      * the process has made no HIP call yet (the runtime reads the variable once). For hosts that own their
+                                      * process (bin/rptr_hip sets it); an embedded plugin leaves it clear and the library never edits its host's
+                                      * environment: it then notes on stderr, once, when the variable is below 2 (option "quiet" silences it). */
 typedef struct RptrCreateInfo {
     int32_t device_ordinal; /* hipSetDevice                                      */
     int32_t rank;
@@ -284,9 +285,9 @@ typedef struct RptrCreateInfo {
     int32_t stripe_rows;    /* 0 -> default 32                                   */
     void *stream;           /* hipStream_t to launch on, NULL -> backend-owned   */
     int32_t frames_in_flight; /* 0/1: frames run one after the other on `stream`; 2..16: that many frame contexts with
-                               * their own streams, see rptr_hip_render_async. Every context's stream wants a hardware
-                               * queue of its own: start the process with GPU_MAX_HW_QUEUES >= frames_in_flight + 1
-                               * (HIP runtime variable, default 4; streams that share a queue serialise).          */
+                               * their own streams, see rptr_hip_render_async. The HIP runtime maps the streams onto
+                               * GPU_MAX_HW_QUEUES hardware queues (default 4; streams that share a queue serialise);
+                               * the library asks for no more than 2 per process (RPTR_CREATE_SET_HW_QUEUES).       */
     int32_t abi_version;      /* RPTR_HIP_ABI_VERSION of the header the caller was compiled against: rptr_hip_create refuses any other
                                * value (a caller built against an older header would hand over structs whose former padding
                                * fields have since been given a meaning, e.g. RptrTextureDesc.mip_levels) */

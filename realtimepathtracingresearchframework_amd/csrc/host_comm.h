@@ -320,7 +320,7 @@ int comm_begin(rptr_hip *h, const float4 *&src, FrameCtx *&owner, int nb) {
                                        "after rptr_hip_wait");
     HIP_TRY(h, hipSetDevice(h->device));
     src = comm_source(h, owner, nb);
-    HIP_TRY(h, hipEventRecord(c->ev_src, h->stream)); // finish_frame made the backend's stream wait for the frame
+    HIP_TRY(h, hipEventRecord(c->ev_src, h->stream)); // the frame has ended (finish_frame waited for it); the caller's work on the stream comes first
     HIP_TRY(h, hipStreamWaitEvent(c->stream, c->ev_src, 0));
     comm_collect_timing(c, false);
     if (!c->timing_pending) HIP_TRY(h, hipEventRecord(c->ev_t0, c->stream));

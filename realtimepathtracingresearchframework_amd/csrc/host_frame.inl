@@ -110,9 +110,9 @@ static int finish_frame(rptr_hip *h, FrameCtx &c, RptrStats *out_stats, int whic
         }
         return RPTR_OK;
     }
-    // work queued on the backend's stream from here on (tile copies, read-backs) sees this frame; joining at collection
-    // time, not at submission, is what lets the next frame's dependency event pass while this frame still runs
-    if (h->ctx.size() > 1) HIP_TRY(h, hipStreamWaitEvent(h->stream, c.ev_end, 0));
+    // work queued on the backend's stream from here on (tile copies, read-backs) sees this frame: the host has waited for its end, so
+    // nothing needs to be queued there. (A join on the backend's stream would sit in a hardware queue that it may share with another frame
+    // context, behind that context's frame, and hold up the next frame's dependency event until that frame ends.)
     HIP_TRY(h, hipEventSynchronize(c.ev_end));
     c.synced = true;
     c.collected |= which < 0 ? all : (1u << which);
@@ -406,7 +406,10 @@ static int render_batch_impl(rptr_hip_t *h, const RptrCamera *camera, bool per_f
                 HIP_TRY(h, hipMemcpyAsync(scn.dynpos[gi], h->master.dynpos[gi], (size_t)h->geom_tris[gi] * 9 * sizeof(float), hipMemcpyDeviceToDevice,
                                           h->stream));
     }
-    if (multi) { // whatever the caller queued on the backend's stream (vertex updates, the copy above) comes first
+    // whatever the caller queued on the backend's stream (vertex updates, the copy above) comes first. When that stream has nothing
+    // unfinished there is nothing to wait for, and no event is recorded: an event on a stream that shares its hardware queue with another
+    // frame context completes only after that context's frame, and would serialise the frames in flight.
+    if (multi && hipStreamQuery(h->stream) != hipSuccess) {
         HIP_TRY(h, hipEventRecord(c.ev_dep, h->stream));
         HIP_TRY(h, hipStreamWaitEvent(c.stream, c.ev_dep, 0));
     }

@@ -99,15 +99,7 @@ int rptr_hip_create(const RptrCreateInfo *info, rptr_hip_t **out) {
         return fail(nullptr, RPTR_E_NO_DEVICE, "hipGetDeviceProperties failed");
     }
     h->num_cus = prop.multiProcessorCount;
-    if (info && info->stream) {
-        h->stream = (hipStream_t)info->stream;
-    } else {
-        if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
-            delete h;
-            return fail(nullptr, RPTR_E_HIP, "hipStreamCreate failed");
-        }
-        h->own_stream = true;
-    }
+    if (info && info->stream) h->stream = (hipStream_t)info->stream;
     {
         int fif = info ? info->frames_in_flight : 1;
         if (const char *s = getenv("RPTR_FRAMES_IN_FLIGHT")) fif = atoi(s);
@@ -124,9 +116,7 @@ int rptr_hip_create(const RptrCreateInfo *info, rptr_hip_t **out) {
             memset(&c.ps, 0, sizeof(c.ps));
             memset(&c.sq, 0, sizeof(c.sq));
             memset(&c.earlier_batches, 0, sizeof(c.earlier_batches));
-            if (fif == 1)
-                c.stream = h->stream;
-            else {
+            if (fif > 1) {
                 if (hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking) != hipSuccess) {
                     delete h;
                     return fail(nullptr, RPTR_E_HIP, "hipStreamCreate failed");
@@ -144,6 +134,17 @@ int rptr_hip_create(const RptrCreateInfo *info, rptr_hip_t **out) {
                 return fail(nullptr, RPTR_E_NOMEM, "hipHostMalloc failed");
             }
         }
+        // The backend's own stream is made AFTER the frame contexts' streams. The HIP runtime gives each new stream a hardware queue of its
+        // own until the process has GPU_MAX_HW_QUEUES of them and then shares queues: made first, the backend's stream -- which carries no
+        // frame work -- would take a queue and leave two frame contexts to share the other, and their frames could never overlap.
+        if (!h->stream) {
+            if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
+                delete h;
+                return fail(nullptr, RPTR_E_HIP, "hipStreamCreate failed");
+            }
+            h->own_stream = true;
+        }
+        if (fif == 1) h->ctx[0].stream = h->stream;
     }
     // defaults of RenderParams / LightSamplingConfig (librender/render_params.glsl.h:123-155)
     memset(&h->params, 0, sizeof(h->params));

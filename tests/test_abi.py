@@ -98,8 +98,9 @@ def test_options_are_part_of_the_c_abi_and_the_environment_only_overrides():
 def test_hardware_queues_are_the_hosts_unless_the_create_info_says_otherwise():
     """GPU_MAX_HW_QUEUES (one hardware queue per frame context's stream: DESIGN.md section 3) belongs to the host process. Loading the library
     changes nothing (round 5 set it from a load-time constructor: VERDICT r5 weak 11); a create WITHOUT RPTR_CREATE_SET_HW_QUEUES changes
-    nothing either; a create WITH the flag -- what bin/rptr_hip passes -- sets it before its first HIP call when nobody did, and leaves a
-    value the host chose alone. (The create itself may fail here for want of a GPU: the variable is set before the device is looked for.)"""
+    nothing either; a create WITH the flag -- what bin/rptr_hip passes -- sets it before its first HIP call when nobody did, to the two queues
+    a process on a shared GPU may hold however many frame contexts it has, and leaves a value the host chose alone. (The create itself may
+    fail here for want of a GPU: the variable is set before the device is looked for.)"""
     import subprocess
     import sys
     # (os.environ is a snapshot: ask the C library)
@@ -118,8 +119,8 @@ def test_hardware_queues_are_the_hosts_unless_the_create_info_says_otherwise():
         return subprocess.run([sys.executable, "-c", probe, str(flags)], env=dict(env, **extra), capture_output=True, text=True, check=True).stdout.split()
     assert run(0) == ["unset", "unset"]                                  # loading and creating: the host's environment is the host's
     out = run(abi.CREATE_SET_HW_QUEUES)
-    assert out[0] == "unset" and int(out[1]) >= 13, out                  # the process's first create, with the host's say-so
-    assert run(abi.CREATE_SET_HW_QUEUES, GPU_MAX_HW_QUEUES="6") == ["6", "6"]   # a value the host chose stays
+    assert out == ["unset", "2"], out                                   # the process's first create, with the host's say-so (11 contexts)
+    assert run(abi.CREATE_SET_HW_QUEUES, GPU_MAX_HW_QUEUES="1") == ["1", "1"]   # a value the host chose stays
 
 
 def test_no_cpu_fallback_create_fails_loudly_without_gpu():
@@ -142,18 +143,21 @@ def test_product_does_not_reference_the_oracle():
 
 
 ABI_REF = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "oracle", "_ref", "libabi_ref.so")
+ABI_REF_JSON = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_abi.json")
 
 
-@pytest.mark.skipif(not os.path.exists(ABI_REF), reason="oracle/_ref/libabi_ref.so is built from the reference tree (oracle/Makefile)")
 def test_boundary_structs_and_constants_against_the_references_headers():
     """pinned by oracle/_ref: the reference's dual-language headers (render_params.glsl.h, base_material.h.glsl, tri.h.glsl,
     sky_model.h.glsl, pathspace.h, sobol_data.h, bn_data.h, texture_channel_mask.h) compiled where they lie report sizes, member
-    offsets, default values and constants; the ctypes mirrors of include/rptr_hip.h, their defaults and the header's constants agree"""
+    offsets, default values and constants (stored in tests/golden/ref_abi.json; where oracle/_ref/libabi_ref.so was built, its live
+    report must equal the stored one); the ctypes mirrors of include/rptr_hip.h, their defaults and the header's constants agree"""
     import json
     import struct
-    L = C.CDLL(ABI_REF)
-    L.ref_abi_json.restype = C.c_char_p
-    ref = json.loads(L.ref_abi_json())
+    ref = json.load(open(ABI_REF_JSON))
+    if os.path.exists(ABI_REF):
+        L = C.CDLL(ABI_REF)
+        L.ref_abi_json.restype = C.c_char_p
+        assert json.loads(L.ref_abi_json()) == ref
     for cls, name in ((abi.RenderParams, "RenderParams"), (abi.LightSamplingConfig, "LightSamplingConfig"), (abi.BaseMaterial, "BaseMaterial"),
                       (abi.RenderRayQuery, "RenderRayQuery"), (abi.TriLightData, "TriLightData"), (abi.SkyModelParams, "SkyModelParams")):
         assert C.sizeof(cls) == ref["sizeof_" + name], name
@@ -176,7 +180,7 @@ def test_boundary_structs_and_constants_against_the_references_headers():
     m = abi.make_material(flags=0)
     assert np.float32(m.base_color[0]) == np.float32(ref["default_BaseMaterial_base_color_x"]) and m.transmission_color[0] == ref["default_BaseMaterial_transmission_color_x"]
     # constants of the header (through abi.py, which test_struct_sizes / the symbol tests hold against include/rptr_hip.h)
-    hdr = open(os.path.join(os.path.dirname(ABI_REF), "..", "..", "include", "rptr_hip.h")).read()
+    hdr = open(os.path.join(ROOT, "include", "rptr_hip.h")).read()
     def define(name):
         return eval(re.search(r"#define %s\s+(.+?)\s*(/\*|$)" % name, hdr, re.M).group(1).replace("u", "").replace("f", ""))
     assert define("RPTR_MAX_PATH_DEPTH") == abi.MAX_PATH_DEPTH == ref["MAX_PATH_DEPTH"]

@@ -1,7 +1,10 @@
 """Point sets behind rng_variant: the tables and the oracle's restatement of rendering/pointsets/{sobol,bn_rng,
 sample_order}.glsl.  The GLSL cannot be run here (GLM is absent: "parity unpinned" for the lookup code); the TABLES are pinned -- the
 Sobol matrices regenerated from the Joe-Kuo direction numbers and the tile inversion derived from them equal the reference's
-sobol_tables.h word by word (checked whenever /root/reference is there) and scipy's Sobol' engine point by point."""
+sobol_tables.h word by word (digests stored in tests/golden/ref_sobol.json; checked against the header itself whenever the reference
+tree is there) and scipy's Sobol' engine point by point."""
+import hashlib
+import json
 import os
 import re
 
@@ -12,6 +15,20 @@ import oracle_lib as O
 from realtimepathtracingresearchframework_amd import abi, pointsets, scenes
 
 REF_TABLE = "/root/reference/rendering/pointsets/sobol_tables.h"
+REF_SOBOL_JSON = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_sobol.json")
+
+
+def digest(words):
+    """word count + sha256 of a uint32 table (little-endian): what tests/golden/ref_sobol.json stores of the reference's tables"""
+    return {"n": int(words.size), "sha256": hashlib.sha256(np.ascontiguousarray(words, "<u4").tobytes()).hexdigest()}
+
+
+def parse_sobol_header(txt):
+    """sobol_tables.h -> (SobolMatrix words, SobolInversion_1_0 words)"""
+    i0, i1 = txt.index("SobolMatrix"), txt.index("SobolInversion_1_0")
+    ref_m = np.array([int(x, 16) for x in re.findall(r"0x([0-9a-fA-F]{8})U", txt[i0:i1])], dtype=np.uint32)
+    body = txt[txt.index("{", i1) + 1:txt.index("}", i1)]
+    return ref_m, np.array([int(x) for x in re.findall(r"\d+", body)], dtype=np.uint32)
 
 
 def lcg_next(s):
@@ -69,17 +86,15 @@ def test_sobol_matrices_against_scipy_engine():
         assert np.array_equal(mine, pts[:, d])
 
 
-@pytest.mark.skipif(not os.path.exists(REF_TABLE), reason="the reference tree is not on this machine")
 def test_sobol_table_equals_the_references_table():
-    txt = open(REF_TABLE).read()
-    i0, i1 = txt.index("SobolMatrix"), txt.index("SobolInversion_1_0")
-    ref_m = np.array([int(x, 16) for x in re.findall(r"0x([0-9a-fA-F]{8})U", txt[i0:i1])], dtype=np.uint32)
-    body = txt[txt.index("{", i1) + 1:txt.index("}", i1)]
-    ref_inv = np.array([int(x) for x in re.findall(r"\d+", body)], dtype=np.uint32)
+    stored = json.load(open(REF_SOBOL_JSON))["sobol_tables_h"]
+    if os.path.exists(REF_TABLE):
+        ref_m, ref_inv = parse_sobol_header(open(REF_TABLE).read())
+        assert {"matrix": digest(ref_m), "inversion": digest(ref_inv)} == stored
     t = pointsets.sobol_table()
-    assert ref_m.size == 1024 * 32 and ref_inv.size == 256 * 256
-    assert np.array_equal(t[:1024 * 32], ref_m)
-    assert np.array_equal(t[1024 * 32:], ref_inv)
+    assert stored["matrix"]["n"] == 1024 * 32 and stored["inversion"]["n"] == 256 * 256
+    assert digest(t[:1024 * 32]) == stored["matrix"]
+    assert digest(t[1024 * 32:]) == stored["inversion"]
 
 
 REF_TOOL = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "oracle", "_ref", "prepare_sobol")
@@ -94,19 +109,34 @@ def _run_ref_tool(bits, tile, dx, dy):
     return m, np.array([int(x) for x in re.findall(r"\d+", body)], dtype=np.uint32), txt
 
 
-@pytest.mark.skipif(not os.path.exists(REF_TOOL), reason="oracle/_ref/prepare_sobol is built from the reference tree (oracle/Makefile)")
+PREPARE_SOBOL_RUNS = ((32, 256, 0, 1), (32, 64, 0, 1), (32, 16, 1, 0), (32, 128, 0, 1))
+
+
+def prepare_sobol_outputs():
+    """what oracle/_ref/prepare_sobol prints for PREPARE_SOBOL_RUNS, as tests/golden/ref_sobol.json stores it"""
+    out = {}
+    for bits, tile, dx, dy in PREPARE_SOBOL_RUNS:
+        m, inv, txt = _run_ref_tool(bits, tile, dx, dy)
+        out["%d_%d_%d_%d" % (bits, tile, dx, dy)] = {"matrix": digest(m), "inversion": digest(inv), "zeros_1": "Zeros: 1" in txt}
+    return out
+
+
 def test_sobol_table_equals_the_output_of_the_references_generator():
-    """pinned by oracle/_ref: rendering/tools/prepare_sobol.cpp compiled unmodified prints the tables the shaders read; the package's
+    """pinned by oracle/_ref: rendering/tools/prepare_sobol.cpp compiled unmodified prints the tables the shaders read (digests stored in
+    tests/golden/ref_sobol.json; where oracle/_ref/prepare_sobol was built, its live output must equal them); the package's
     regenerated matrices and the derived tile inversion equal them word by word — for the shipped (32 bits, 256 tile, dims 0 / 1) table
     and for other tile sizes and dimension pairs of the same tool"""
-    m, inv, txt = _run_ref_tool(32, 256, 0, 1)
+    stored = json.load(open(REF_SOBOL_JSON))["prepare_sobol"]
+    if os.path.exists(REF_TOOL):
+        assert prepare_sobol_outputs() == stored
+    ref = stored["32_256_0_1"]
     t = pointsets.sobol_table()
-    assert m.size == 1024 * 32 and inv.size == 256 * 256 and "Zeros: 1" in txt
-    assert np.array_equal(t[:1024 * 32], m) and np.array_equal(t[1024 * 32:], inv)
+    assert ref["matrix"]["n"] == 1024 * 32 and ref["inversion"]["n"] == 256 * 256 and ref["zeros_1"]
+    assert digest(t[:1024 * 32]) == ref["matrix"] and digest(t[1024 * 32:]) == ref["inversion"]
     mine = pointsets.sobol_matrices()
-    for tile, dx, dy in ((64, 0, 1), (16, 1, 0), (128, 0, 1)):
-        _, inv, txt = _run_ref_tool(32, tile, dx, dy)
-        assert "Zeros: 1" in txt and np.array_equal(pointsets.sobol_tile_inversion(mine, tile=tile, dim_x=dx, dim_y=dy), inv)
+    for bits, tile, dx, dy in PREPARE_SOBOL_RUNS[1:]:
+        ref = stored["%d_%d_%d_%d" % (bits, tile, dx, dy)]
+        assert ref["zeros_1"] and digest(pointsets.sobol_tile_inversion(mine, tile=tile, dim_x=dx, dim_y=dy)) == ref["inversion"]
 
 
 def test_tile_inversion_is_the_inverse_of_the_first_two_dimensions():

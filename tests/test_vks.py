@@ -1,8 +1,11 @@
 """`.vks` / `.vkt` I/O against the reference's own reader: fixtures under tests/golden/vks were written
 by realtimepathtracingresearchframework_amd/vks.py and read back by ext/libvkr/src/vkr.c compiled unmodified
 (oracle/_ref/libvkr_ref.so; generator tests/golden/gen_vks_fixture.py). When that library is present (build container,
-and the GPU box, where the prebuilt .so travels) the comparison is also made live on freshly written scenes."""
+and the GPU box, where the prebuilt .so travels) the comparison is also made live on freshly written scenes; elsewhere the freshly
+written scenes are held against that reader's stored dumps of the very same bytes (tests/golden/vks/ref_reader_dumps.json, generator
+tests/golden/gen_ref_fixtures.py)."""
 import ctypes as C
+import hashlib
 import json
 import os
 import shutil
@@ -16,6 +19,7 @@ from realtimepathtracingresearchframework_amd import abi, scenes, vks
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
 REF_LIB = os.path.join(ROOT, "oracle", "_ref", "libvkr_ref.so")
+REF_DUMPS = os.path.join(GOLD, "vks", "ref_reader_dumps.json")
 
 
 def _bits(x):
@@ -202,26 +206,28 @@ def test_write_then_read_keeps_the_scene(tmp_path, name, version):
     assert abs(float(fa.mean()) - float(fb.mean())) < 0.05 * float(fa.mean()) + 0.01
 
 
+def write_lod_file(path):
+    """two_level_test with parameterized mesh 1 written as a coarser level of mesh 0"""
+    s = scenes.two_level_test()
+    assert len(s.pmeshes) >= 3
+    vks.write_vks(path, s, lod_groups=[[(0, 0.0), (1, 0.5)]])
+    return s
+
+
 def test_lod_groups_instance_the_base_level_only(tmp_path):
     """file version 4 LoD groups (vkr.h:261-270): meshes of a group share their instances' placement, the loader keeps the
     instances of a group's first (base) mesh only (scene.cpp:722-736) -- and the reference's reader sees the same groups"""
-    s = scenes.two_level_test()
-    n_pm = len(s.pmeshes)
-    assert n_pm >= 3
     path = str(tmp_path / "lod.vks")
-    vks.write_vks(path, s, lod_groups=[[(0, 0.0), (1, 0.5)]])          # parameterized mesh 1 is a coarser level of mesh 0
+    s = write_lod_file(path)
     v = vks.read_vks_header(path)
     assert v["numLodGroups"] == 2 and v["lodGroups"][1]["meshIds"] == [0, 1] and v["lodGroups"][1]["detailReduction"] == [0.0, 0.5]
     assert [m["lodGroup"] for m in v["meshes"]][:3] == [1, 1, 0]
     r = vks.read_vks(path)
     kept = [i for i in s.instances if i.pmesh != 1]
     assert len(r.instances) == len(kept) and all(a.pmesh == b.pmesh for a, b in zip(r.instances, kept))
-    if os.path.isfile(REF_LIB):
-        out = str(tmp_path / "dump.json")
-        assert _ref().ref_vkr_dump(path.encode(), out.encode()) == 0
-        ref = json.load(open(out))
-        _compare_with_dump(path, ref)
-        assert [g["detailReduction"] for g in ref["lodGroups"]][1] == _bits([0.0, 0.5]).tolist()
+    ref = _reference_dump(path, "lod_groups", tmp_path)
+    _compare_with_dump(path, ref)
+    assert [g["detailReduction"] for g in ref["lodGroups"]][1] == _bits([0.0, 0.5]).tolist()
     with pytest.raises(vks.VksError):
         vks.write_vks(str(tmp_path / "lod3.vks"), s, version=3, lod_groups=[[(0, 0.0), (1, 0.5)]])
 
@@ -241,16 +247,22 @@ def test_remove_first_lods_swaps_in_the_coarser_level(tmp_path):
     assert any(i.pmesh == 0 for i in base.instances) and all(np.array_equal(a.transform, b.transform) for a, b in zip(base.instances, lvl1.instances))
 
 
-def test_sixteen_bit_material_ids_and_index_buffers(tmp_path):
-    """a mesh whose material range exceeds 256 stores two bytes per triangle id (vkr.c:1127-1130); the reference's backend uploads
-    static_cast<uint8_t>(id) (render_vulkan.cpp:1114-1126), so does the reader. VKR_MESH_FLAGS_INDICES files carry a 12-byte-per-triangle
-    index buffer behind the ids (vkr.c:1131-1136): skipped, the vertex streams are unrolled. libvkr reads the same offsets."""
+def write_wide_ids_file(path):
+    """alpha_test with two-byte material ids on its first mesh that has them (ranges beyond 256) and index buffers on every mesh"""
     s = scenes.alpha_test()
     pm = next(i for i, p in enumerate(s.pmeshes) if p.tri_material_ids is not None)
     n = len(s.pmeshes[pm].tri_material_ids)
     wide = (np.asarray(s.pmeshes[pm].tri_material_ids, np.uint16) + np.uint16(256) * (np.arange(n) % 3).astype(np.uint16)).astype(np.uint16)
-    path = str(tmp_path / "wide.vks")
     vks.write_vks(path, s, wide_material_ids={pm: wide}, index_buffers=True)
+    return s, pm, wide
+
+
+def test_sixteen_bit_material_ids_and_index_buffers(tmp_path):
+    """a mesh whose material range exceeds 256 stores two bytes per triangle id (vkr.c:1127-1130); the reference's backend uploads
+    static_cast<uint8_t>(id) (render_vulkan.cpp:1114-1126), so does the reader. VKR_MESH_FLAGS_INDICES files carry a 12-byte-per-triangle
+    index buffer behind the ids (vkr.c:1131-1136): skipped, the vertex streams are unrolled. libvkr reads the same offsets."""
+    path = str(tmp_path / "wide.vks")
+    s, pm, wide = write_wide_ids_file(path)
     v = vks.read_vks_header(path)
     assert v["meshes"][pm]["materialIdSize"] == 2 and v["meshes"][pm]["numMaterialsInRange"] > 0x100
     assert all(m["flags"] & vks.MESH_FLAGS_INDICES and m["indexBufferOffset"] > m["materialIdBufferOffset"] for m in v["meshes"])
@@ -261,10 +273,7 @@ def test_sixteen_bit_material_ids_and_index_buffers(tmp_path):
     vks.write_vks(plain, s)
     q = vks.read_vks(plain)
     assert all(np.array_equal(a.qpos, b.qpos) for a, b in zip(r.geometries, q.geometries)) and len(r.instances) == len(q.instances)
-    if os.path.isfile(REF_LIB):
-        out = str(tmp_path / "dump.json")
-        assert _ref().ref_vkr_dump(path.encode(), out.encode()) == 0
-        _compare_with_dump(path, json.load(open(out)))
+    _compare_with_dump(path, _reference_dump(path, "wide_ids", tmp_path))
 
 
 def test_unrepresentable_scenes_are_refused(tmp_path):
@@ -296,44 +305,72 @@ def test_reader_errors(tmp_path):
     assert vks.read_vkt(str(tmp_path / "missing.vkt")) is None
 
 
-# ---------------------------------------------------------------- live against the reference's reader
-needs_ref = pytest.mark.skipif(not os.path.isfile(REF_LIB), reason="oracle/_ref/libvkr_ref.so not built (needs the reference checkout)")
-
-
+# ---------------------------------------------------------------- against the reference's reader (live where oracle/_ref was built)
 def _ref():
     lib = C.CDLL(REF_LIB)
     lib.ref_vkr_dump.argtypes = [C.c_char_p, C.c_char_p]
     return lib
 
 
-@needs_ref
+def tree_digest(path):
+    """sha256 over a written .vks file and its texture directory: a stored dump belongs to exactly these bytes"""
+    h = hashlib.sha256(open(path, "rb").read())
+    tdir = vks.texture_dir(path)
+    for f in (sorted(os.listdir(tdir)) if os.path.isdir(tdir) else []):
+        h.update(f.encode())
+        h.update(open(os.path.join(tdir, f), "rb").read())
+    return h.hexdigest()
+
+
+def live_dump(path, out):
+    """the reference reader's dump of `path` (None when it refuses the file); textureDir as its base name, as the stored dumps hold it"""
+    if _ref().ref_vkr_dump(path.encode(), out.encode()) != 0:
+        return None
+    d = json.load(open(out))
+    d["textureDir"] = os.path.basename(d["textureDir"].rstrip("/"))
+    return d
+
+
+def _reference_dump(path, key, tmp_path):
+    """what the reference's reader makes of `path`: its stored dump of the same bytes (tests/golden/vks/ref_reader_dumps.json) -- and,
+    where oracle/_ref/libvkr_ref.so was built, the live reader's, which must equal it"""
+    stored = json.load(open(REF_DUMPS))[key]
+    assert tree_digest(path) == stored["digest"], "%s: the writer's bytes changed; regenerate tests/golden (gen_ref_fixtures.py)" % key
+    if os.path.isfile(REF_LIB):
+        assert live_dump(path, str(tmp_path / "dump.json")) == stored["dump"], key
+    return stored["dump"]
+
+
 @pytest.mark.parametrize("name", ["cornell32", "textured_test", "two_level_test", "alpha_test"])
 @pytest.mark.parametrize("version", [3, 4])
 def test_written_files_are_read_identically_by_the_reference(tmp_path, name, version):
     s = getattr(scenes, name)()
     path = str(tmp_path / (name + ".vks"))
     vks.write_vks(path, s, version=version)
-    out = str(tmp_path / "dump.json")
-    assert _ref().ref_vkr_dump(path.encode(), out.encode()) == 0
-    _compare_with_dump(path, json.load(open(out)))
+    _compare_with_dump(path, _reference_dump(path, "%s_v%d" % (name, version), tmp_path))
 
 
-@needs_ref
-def test_reference_and_reader_reject_the_same_files(tmp_path):
+def reject_cases():
+    """a good file and four broken copies of it (tests/golden/vks/alpha_v4.vks)"""
     good = open(os.path.join(GOLD, "vks", "alpha_v4.vks"), "rb").read()
+    return {"magic": b"\1" + good[1:], "version": good[:4] + (7).to_bytes(4, "little") + good[8:], "truncated": good[:300],
+            "header_size": good[:16] + (999).to_bytes(8, "little") + good[24:], "good": good}
+
+
+def test_reference_and_reader_reject_the_same_files(tmp_path):
     shutil.copytree(os.path.join(GOLD, "vks", "alpha_v4_textures"), str(tmp_path / "t_textures"))
-    cases = {"magic": b"\1" + good[1:], "version": good[:4] + (7).to_bytes(4, "little") + good[8:], "truncated": good[:300],
-             "header_size": good[:16] + (999).to_bytes(8, "little") + good[24:], "good": good}
-    for tag, data in cases.items():
+    accepted = json.load(open(REF_DUMPS))["reference_accepts"]
+    for tag, data in reject_cases().items():
         p = str(tmp_path / "t.vks")
         open(p, "wb").write(data)
-        rc = _ref().ref_vkr_dump(p.encode(), str(tmp_path / "d.json").encode())
+        if os.path.isfile(REF_LIB):
+            assert (_ref().ref_vkr_dump(p.encode(), str(tmp_path / "d.json").encode()) == 0) == accepted[tag], tag
         try:
             vks.read_vks_header(p)
             mine_ok = True
         except vks.VksError:
             mine_ok = False
-        assert mine_ok == (rc == 0), tag
+        assert mine_ok == accepted[tag], tag
 
 
 def test_vkt_mip_levels_round_trip(tmp_path):
@@ -374,10 +411,8 @@ def test_vkt_mip_levels_round_trip(tmp_path):
     assert len(with_mips) >= 1 and len(with_mips[0].levels()) == len(tm) + 1
 
 
-@needs_ref
-def test_mip_mapped_vkt_files_are_read_by_the_reference(tmp_path):
-    """pinned by oracle/_ref: .vkt files written with several mip levels are accepted by the reference's own reader, which reports the
-    level count, the payload size and the payload offset the writer meant (vkr.c:248-300)"""
+def mip_mapped_scene():
+    """textured_test with every texture carrying its mip chain"""
     s = scenes.textured_test()
     for t in s.textures:
         lv, cur = [], np.asarray(t.rgba)
@@ -385,11 +420,15 @@ def test_mip_mapped_vkt_files_are_read_by_the_reference(tmp_path):
             cur = np.ascontiguousarray(cur[::2, ::2][:max(1, cur.shape[0] // 2), :max(1, cur.shape[1] // 2)])
             lv.append(cur)
         t.mips = lv or None
+    return s
+
+
+def test_mip_mapped_vkt_files_are_read_by_the_reference(tmp_path):
+    """pinned by oracle/_ref: .vkt files written with several mip levels are accepted by the reference's own reader, which reports the
+    level count, the payload size and the payload offset the writer meant (vkr.c:248-300)"""
     path = str(tmp_path / "m.vks")
-    vks.write_vks(path, s)
-    out = str(tmp_path / "dump.json")
-    assert _ref().ref_vkr_dump(path.encode(), out.encode()) == 0
-    ref = json.load(open(out))
+    vks.write_vks(path, mip_mapped_scene())
+    ref = _reference_dump(path, "mip_mapped", tmp_path)
     _compare_with_dump(path, ref)
     levels = [m["texBaseColor"]["numMipLevels"] for m in ref["materials"] if m["texBaseColor"]]
     assert max(levels) >= 4
