@@ -132,7 +132,18 @@ typedef struct RptrLightSamplingConfig {
     float min_radiance;
 } RptrLightSamplingConfig;
 
-/* librender/render_params.glsl.h:130-155 -- 80 bytes */
+/* librender/render_params.glsl.h:130-155 -- 80 bytes
+ * reprojection_mode (rendering/postprocess/reprojection.h): 0 REPROJECTION_MODE_NONE -- the running mean over every frame since the last
+ * reset; 1 REPROJECTION_MODE_DISCARD_HISTORY -- a frame shows its own samples only; 2 REPROJECTION_MODE_ACCUMULATE -- the real-time
+ * resolve of the reference's ENABLE_REALTIME_RESOLVE build (csrc/realtime_resolve.h): each render call of `spp` samples is one frame whose
+ * mean is folded into the previous frame's history REPROJECTED along the motion AOV (reprojection.glsl:43-367), so a moving camera keeps
+ * its history; the new-sample weight falls to 1 / spp_accumulation_window (>= 1), the accumulation image holds (history.rgb,
+ * 1 - new-sample weight), the frame shows history.rgb with its coverage alpha. reset_accumulation starts from this frame's mean. The
+ * history is what the previous mode-2 frame left (frames in flight: the frame resolved before it); a frame after one of another mode
+ * starts from its mean. Mode 2 returns RPTR_E_UNSUPPORTED with world_size > 1 (a stripe's edge pixels reproject into other ranks' rows),
+ * for launch sequences of several frames (rptr_hip_render_batch*_async with n_frames > 1) and with option "aovs" = 0 (no motion or
+ * normal + depth); option "taa" = 1 with mode 1, or with render_upscale_factor 2, does too. Modes 0 and 1 launch nothing new.
+ * (RPTR_HIP_ABI_VERSION stays: no layout changes, and mode 2 was accepted before -- as mode 0.) */
 typedef struct RptrRenderParams {
     int32_t batch_spp;
     int32_t max_path_depth;
@@ -480,7 +491,12 @@ int rptr_hip_set_stage_timing(rptr_hip_t *h, int level);
  *                                                        binned-RIS lights) 6.5 % faster per frame, whole frames within 2.3e-4 RMSE of
  *                                                        the oracle (IEEE: 1.4e-5; north_star's tolerance 1e-3), coverage and ray
  *                                                        counts unchanged; csrc/dmath.h. Traversal and camera rays are IEEE either way.
- *   rptr_hip_option_count / rptr_hip_option_name enumerate these keys. Experiments that were measured and not adopted stay reachable for
+ *   taa                      0         next frame        RenderBackendOptions::enable_taa: with reprojection_mode 2, a TAA pass on     RPTR_TAA
+ *                                                        the RGBA8 frame after the resolve (vulkan/processing/process_taa.comp:
+ *                                                        Lanczos history r = 5, weight 0.15, trimmed neighbourhood box), from the
+ *                                                        second frame after a reset on; render_upscale_factor 1 (see "Real-time
+ *                                                        resolve" at RptrRenderParams)
+ *   rptr_hip_option_count / rptr_hip_option_name enumerate these keys (22). Experiments that were measured and not adopted stay reachable for
  *   A/B runs under the key prefix "experimental." (and their environment variables), are not enumerated and carry no promise:
  *   experimental.rebraid, .tlas_collapse, .collapse, .presplit_density, .presplit_budget_pct, .host_ploc, .ploc_top, .ploc_leaf, .lds_top,
  *   .regroup_materials, .comm_self (profiles/r03_notes.md, r05_notes.md say what each lost by).

@@ -19,6 +19,8 @@ VARIANT_GLTF_TRANSMISSION = 2
 MESH_DYNAMIC, MESH_SUBTLY_DYNAMIC = 1, 2  # RptrMeshDesc.dynamic = Mesh::flags (librender/mesh.h:44-47)
 # RBO rng_variant (librender/render_params.glsl.h:34-37)
 RNG_VARIANT_UNIFORM, RNG_VARIANT_BN, RNG_VARIANT_SOBOL, RNG_VARIANT_Z_SBL = 0, 1, 2, 3
+# RenderParams.reprojection_mode (rendering/postprocess/reprojection.h); 2 = the real-time resolve, csrc/realtime_resolve.h
+REPROJECTION_MODE_NONE, REPROJECTION_MODE_DISCARD_HISTORY, REPROJECTION_MODE_ACCUMULATE = 0, 1, 2
 RNG_VARIANT_NAMES = ("UNIFORM", "BN", "SOBOL", "Z_SBL")
 SOBOL_TABLE_BYTES = (1024 * 32 + 256 * 256) * 4      # RPTR_SOBOL_TABLE_BYTES
 BN_TABLE_MIN_BYTES = (256 * 256 + 128 * 128 * 8) * 4  # RPTR_BN_TABLE_MIN_BYTES

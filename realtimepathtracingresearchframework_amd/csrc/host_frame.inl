@@ -253,6 +253,19 @@ static int check_render_arguments(rptr_hip_t *h, const RptrCamera *camera, bool 
     if (variant != RPTR_VARIANT_GLTF && variant != RPTR_VARIANT_SIMPLE && variant != RPTR_VARIANT_GLTF_TRANSMISSION)
         return fail(h, RPTR_E_INVALID, "unknown variant %d", variant);
     if (spp < 1) return fail(h, RPTR_E_INVALID, "spp must be >= 1");
+    // reprojection_mode 2 (realtime_resolve.h) covers one frame per call on one device with the AOV images
+    if (h->params.reprojection_mode == 2) {
+        if (h->world > 1)
+            return fail(h, RPTR_E_UNSUPPORTED, "reprojection_mode 2 needs world_size 1: the history of a stripe's edge pixels belongs to other ranks");
+        if (n_frames > 1) return fail(h, RPTR_E_UNSUPPORTED, "reprojection_mode 2 renders one frame per call: batches of %d frames are not supported", n_frames);
+        if (!h->aovs) return fail(h, RPTR_E_UNSUPPORTED, "reprojection_mode 2 reads the motion and normal + depth AOV images: option \"aovs\" is 0");
+        if (h->params.spp_accumulation_window < 1) return fail(h, RPTR_E_INVALID, "reprojection_mode 2 needs spp_accumulation_window >= 1");
+    }
+    if (h->opt.v[OPT_TAA] != 0 && h->params.reprojection_mode != 0) {
+        if (h->params.reprojection_mode != 2) return fail(h, RPTR_E_UNSUPPORTED, "option \"taa\" runs with reprojection_mode 2 only");
+        if (h->params.render_upscale_factor != 1)
+            return fail(h, RPTR_E_UNSUPPORTED, "option \"taa\" needs render_upscale_factor 1 (the frame buffer has the render resolution)");
+    }
     return RPTR_OK;
 }
 // the frame constants of a launch sequence (RpFrame: render / scene / lighting parameters, the camera basis of frame 0 and -- per_frame_cameras --
@@ -347,6 +360,22 @@ static int render_batch_impl(rptr_hip_t *h, const RptrCamera *camera, bool per_f
         h->frame_id = 0;
     }
     const uint32_t frame_id_before = h->frame_id;
+    // reprojection_mode 2: the images of realtime_resolve.h, made by the first frame that needs them
+    const bool realtime = h->params.reprojection_mode == 2 && h->local_rows > 0;
+    const bool taa = realtime && h->opt.v[OPT_TAA] != 0;
+    if (realtime) {
+        const size_t npix = (size_t)h->width * (size_t)h->local_rows;
+        int rc = RPTR_OK;
+        if (!h->rt.cur) {
+            if ((rc = dev_alloc(h, &h->rt.cur, npix, nullptr)) || (rc = dev_alloc(h, &h->rt.accum_other, npix, nullptr)) ||
+                (rc = dev_alloc(h, &h->rt.nd[0], npix, nullptr)) || (rc = dev_alloc(h, &h->rt.nd[1], npix, nullptr)))
+                return rc;
+            h->rt.chain = false;
+        }
+        if (taa && !h->rt.fb_pre) {
+            if ((rc = dev_alloc(h, &h->rt.fb_pre, npix, nullptr)) || (rc = dev_alloc(h, &h->rt.fb_other, npix, nullptr))) return rc;
+        }
+    }
     RpFrame f;
     fill_frame_constants(h, c, camera, per_frame_cameras, variant, spp, n_frames, reset_rest, f);
     size_t ev_cursor = 0;
@@ -490,7 +519,39 @@ static int render_batch_impl(rptr_hip_t *h, const RptrCamera *camera, bool per_f
             if (multi && h->last_resolved && h->last_resolved != c.ev_resolved) HIP_TRY(h, hipStreamWaitEvent(c.stream, h->last_resolved, 0));
             {
                 const size_t npix = (size_t)h->width * h->local_rows;
-                timed_kernel(c.stream, 4, rp_k_resolve, dim3(grid_for(h, npix)), dim3(256), f, c.ps, h->accum, h->fb, c.out_accum, c.out_fb);
+                if (!realtime)
+                    timed_kernel(c.stream, 4, rp_k_resolve, dim3(grid_for(h, npix)), dim3(256), f, c.ps, h->accum, h->fb, c.out_accum, c.out_fb);
+                else // the mean of this frame's samples (kernels_misc.h), then, after its last batch, the reprojection (and TAA) passes
+                    timed_kernel(c.stream, 4, rp_k_resolve, dim3(grid_for(h, npix)), dim3(256), f, c.ps, h->rt.cur, (uchar4 *)nullptr,
+                                 (float4 *)nullptr, (uchar4 *)nullptr);
+            }
+            if (realtime && remaining - batch == 0) {
+                // process_taa.cpp:92 reads frame_id after end_frame: this call's samples included
+                const bool taa_now = taa && frame_id_before + (uint32_t)spp > 1u;
+                RpReprojectArgs ra;
+                ra.cur = h->rt.cur;
+                ra.nd = c.aov[1];
+                ra.mj = c.aov[2];
+                ra.hist = h->accum;
+                ra.hist_nd = h->rt.nd[h->rt.parity];
+                ra.accum = h->rt.accum_other;
+                ra.out_nd = h->rt.nd[h->rt.parity ^ 1];
+                ra.fb = taa_now ? h->rt.fb_pre : h->fb;
+                ra.fb_keep = h->fb;
+                ra.out_accum = c.out_accum;
+                ra.out_fb = c.out_fb; // (with TAA, rp_k_taa overwrites it with the frame after the pass)
+                ra.min_sample_weight = 1.0f / float(h->params.spp_accumulation_window);
+                ra.sample_batch_size = spp;
+                ra.use_history = (f.frame_id > 0 && h->rt.chain) ? 1 : 0;
+                const dim3 tiles((unsigned)((h->width + RP_RT_TILE - 1) / RP_RT_TILE), (unsigned)((h->local_rows + RP_RT_TILE - 1) / RP_RT_TILE));
+                timed_kernel(c.stream, 4, rp_k_reproject, tiles, dim3(64), f, ra);
+                std::swap(h->accum, h->rt.accum_other);
+                h->rt.parity ^= 1;
+                if (taa_now) {
+                    timed_kernel(c.stream, 4, rp_k_taa, tiles, dim3(64), f, (const uchar4 *)h->rt.fb_pre, (const uchar4 *)h->fb, (const uint2 *)c.aov[2],
+                                 h->rt.fb_other, c.out_fb);
+                    std::swap(h->fb, h->rt.fb_other);
+                }
             }
             if (multi) { // (the resolve also kept a copy of the image this frame produced: the next frame's resolve overwrites the shared buffers)
                 HIP_TRY(h, hipEventRecord(c.ev_resolved, c.stream));
@@ -523,6 +584,7 @@ static int render_batch_impl(rptr_hip_t *h, const RptrCamera *camera, bool per_f
             c.batch_spp_after[k] = h->accumulated_spp;
         }
     }
+    h->rt.chain = realtime; // what this frame left is the next frame's history in mode 2 only
     HIP_TRY(h, hipEventRecord(c.ev_end, c.stream));
     HIP_TRY(h, hipGetLastError());
     if (h->freeze_frame) h->frame_id = frame_id_before; // end_frame, render_vulkan.cpp:2152-2154: the next frame repeats these samples

@@ -109,7 +109,7 @@ enum RpOpt : int {
     // supported: documented in include/rptr_hip.h "Options", enumerated by rptr_hip_option_count / rptr_hip_option_name
     OPT_FLATTEN, OPT_FLATTEN_MAX_TRIS, OPT_BVH_BUILDER, OPT_DEVICE_BUILD_MIN_TRIS, OPT_TRAVERSE_NODE_MIN, OPT_TRAVERSE_REFILL_MIN, OPT_SINGLE_INSTANCE, OPT_MAX_BATCH_FRAMES,
     OPT_MAX_BATCH_SPP, OPT_PATH_BUDGET_MB, OPT_BLOCKS_PER_CU, OPT_SIDE_CONNECT, OPT_AOVS, OPT_TAIL_BOUNCE, OPT_TAIL_THRESHOLD,
-    OPT_STAGE_TIMING, OPT_COMM_TRANSPORT, OPT_COMM_PRIORITY, OPT_QUIET, OPT_TRAVERSE_FETCH, OPT_FAST_MATH,
+    OPT_STAGE_TIMING, OPT_COMM_TRANSPORT, OPT_COMM_PRIORITY, OPT_QUIET, OPT_TRAVERSE_FETCH, OPT_FAST_MATH, OPT_TAA,
     OPT_PUBLIC_COUNT,
     // experiments that were measured and not adopted (profiles/r03_notes.md, r05_notes.md): reachable as "experimental.<key>" and through their
     // environment variables, not enumerated, no promise that they stay
@@ -142,6 +142,7 @@ static const RpOptDesc g_opt_desc[OPT_COUNT] = {
     {"quiet", "RPTR_QUIET", 0, 0, 1},
     {"traverse_fetch", "RPTR_TRAVERSE_FETCH", 0, 0, 4096},        // queue entries a traversal wave takes per pool at most (multiple of 64); 0: per scene, with the thresholds
     {"fast_math", "RPTR_FAST_MATH", 0, 0, 1},                     // the shading stages' division / square root: 0 IEEE (the oracle's bits), 1 the hardware's 1-ulp rcp / sqrt / rsq (dmath.h)
+    {"taa", "RPTR_TAA", 0, 0, 1},                                 // RenderBackendOptions::enable_taa: TAA pass on the RGBA8 frame in reprojection mode 2 (realtime_resolve.h)
     // ---- experimental.<key>
     {"rebraid", "RPTR_REBRAID", 0, 0, 64},                        // instance records per instance in the top level; 0 auto (4 from 16 instances on)
     {"tlas_collapse", "RPTR_TLAS_COLLAPSE", 0, 0, 2},             // rptr::COLLAPSE_* of the top level
@@ -328,6 +329,16 @@ struct rptr_hip {
     float scene_lo[3] = {0, 0, 0}, scene_hi[3] = {1, 1, 1};
     float4 *accum = nullptr;
     uchar4 *fb = nullptr;
+    // reprojection_mode 2 (realtime_resolve.h): the images that ping-pong with accum / fb, and the history normal + depth
+    struct RtResolve {
+        float4 *cur = nullptr;       // this frame's mean (rp_k_resolve writes it, rp_k_reproject reads it)
+        float4 *accum_other = nullptr; // the partner of `accum`: a frame reads the history in accum and writes here, then the two swap
+        uint2 *nd[2] = {nullptr, nullptr}; // normal + depth of the last mode-2 frame: nd[parity] is the history, nd[parity ^ 1] is written
+        int parity = 0;
+        uchar4 *fb_pre = nullptr;    // TAA: the frame before the pass
+        uchar4 *fb_other = nullptr;  // TAA: the partner of `fb` (the pass reads the history in fb and writes here, then they swap)
+        bool chain = false;          // the previously submitted frame ran the mode-2 resolve: its images are this frame's history
+    } rt;
     size_t path_capacity = 0;
     int persistent_blocks = 0;
     int extend_later_blocks = 0;     // grid of a closest-hit launch of bounce >= 1 (RP_EXTEND_LATER_WAVES)

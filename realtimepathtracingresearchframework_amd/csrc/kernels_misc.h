@@ -84,7 +84,7 @@ __global__ __launch_bounds__(256) void rp_k_resolve(RpFrame f, RpPathState ps, f
         if (rp_local_row_to_global(f, ly) >= f.height) continue;
         const uint32_t slot = rp_local_to_slot(f, lx, ly);
         float4 acc = accum[i];
-        uchar4 shown = fb[i];
+        uchar4 shown = fb ? fb[i] : make_uchar4(0, 0, 0, 0); // fb NULL (mode 2): only the mean is kept
         const int per_frame = f.batch_frames > 1 ? f.frame_spp : f.batch_spp;
         for (int k = 0; k < f.batch_frames; ++k) {
             for (int j = 0; j < per_frame; ++j) {
@@ -95,7 +95,8 @@ __global__ __launch_bounds__(256) void rp_k_resolve(RpFrame f, RpPathState ps, f
                 // all of its own samples -- the index inside the frame, which for a frame the backend splits into several internal launches
                 // (spp > max_batch_spp) continues where the previous launch stopped (sample_base - frame_id samples of this frame came before)
                 const uint32_t in_frame = (f.batch_frames > 1 ? 0u : f.sample_base - f.frame_id) + uint32_t(j);
-                const uint32_t sample_index = f.rp.reprojection_mode == 1 ? in_frame : rp_slot_frame(f, uint32_t(s)).sample_index;
+                // (REPROJECTION_MODE_ACCUMULATE, 2: the same mean of this frame's samples, which realtime_resolve.h rp_k_reproject folds in)
+                const uint32_t sample_index = f.rp.reprojection_mode == 1 || f.rp.reprojection_mode == 2 ? in_frame : rp_slot_frame(f, uint32_t(s)).sample_index;
                 if (sample_index == 0)
                     acc = c;
                 else {
@@ -108,18 +109,18 @@ __global__ __launch_bounds__(256) void rp_k_resolve(RpFrame f, RpPathState ps, f
             }
             float4 o = acc;
             o.w = fminf(o.w, 1.0f);
-            if (o.w >= 0.0f) {
+            if (fb && o.w >= 0.0f) {
                 o = rp_display_color(f, o, i, k);
                 shown = make_uchar4((unsigned char)(clamp1(o.x, 0.f, 1.f) * 255.0f + 0.5f), (unsigned char)(clamp1(o.y, 0.f, 1.f) * 255.0f + 0.5f),
                                     (unsigned char)(clamp1(o.z, 0.f, 1.f) * 255.0f + 0.5f), (unsigned char)(clamp1(o.w, 0.f, 1.f) * 255.0f + 0.5f));
             }
-            if (out_accum) {
+            if (out_accum && fb) {
                 out_accum[size_t(k) * f.out_stride + size_t(i)] = acc;
                 out_fb[size_t(k) * f.out_stride + size_t(i)] = shown;
             }
         }
         accum[i] = acc;
-        fb[i] = shown;
+        if (fb) fb[i] = shown;
     }
 }
 

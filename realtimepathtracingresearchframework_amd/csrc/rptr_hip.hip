@@ -9,6 +9,7 @@
 
 #include "bvh_build.h"
 #include "kernels_misc.h"
+#include "realtime_resolve.h"
 #include "launch.h"
 #include "lbvh.h"
 #include "ploc.h"
@@ -293,6 +294,7 @@ int rptr_hip_initialize(rptr_hip_t *h, int fb_width, int fb_height) {
         }
     h->output_ctx = -1;
     h->last_resolved = nullptr;
+    h->rt = decltype(h->rt)(); // (mode-2 images: allocated by the first frame that needs them, freed with the rest above)
     h->aov_ctx = 0;
     h->output_overwritten = h->aov_overwritten = false;
     if (h->aovs)

@@ -185,10 +185,8 @@ inline void apply_ini_object(const IniObject &o, HostConfig &c) {
         if (const IniObject *op = fl->child("reprojection")) { // REPROJECTION_MODE_NAMES (postprocess/reprojection.h)
             const std::string s = op->selected();
             if (s.find("DISCARD_HISTORY") != std::string::npos) c.params.reprojection_mode = 1;
-            else if (s.find("ACCUMULATE") != std::string::npos) {
-                c.params.reprojection_mode = 0;
-                c.notes.push_back("reprojection ACCUMULATE belongs to ENABLE_REALTIME_RESOLVE builds: NONE is used");
-            } else if (s.find("NONE") != std::string::npos) c.params.reprojection_mode = 0;
+            else if (s.find("ACCUMULATE") != std::string::npos) c.params.reprojection_mode = 2; // the real-time resolve (csrc/realtime_resolve.h)
+            else if (s.find("NONE") != std::string::npos) c.params.reprojection_mode = 0;
         }
         int upscale = c.params.render_upscale_factor == 2 ? 1 : 0, taa = c.params.enable_raster_taa != 0 ? 1 : 0, unjittered = c.params.enable_raster_taa < 0 ? 1 : 0;
         fl->get("use 2x upscaling", &upscale);

@@ -629,9 +629,11 @@ int main(int argc, char **argv) {
                 }
                 if (!rest.empty()) p.reset = true; // the geometry moves: the accumulation starts over
                 p.camera = cam;
-                if (fly_through) { // a moved camera restarts the accumulation (the application resets when the view changes)
+                if (fly_through) { // a moved camera restarts the accumulation (the application resets when the view changes) ...
                     p.camera = fly_camera(frame);
-                    p.reset = true;
+                    // ... unless the history is reprojected (REPROJECTION_MODE_ACCUMULATE, app.cpp:320-327); moving geometry still resets
+                    const int mode = active_key >= 0 ? frames[(size_t)active_key].params.reprojection_mode : base.params.reprojection_mode;
+                    if (mode != 2) p.reset = true;
                 }
                 p.key = active_key;
                 p.time = current_time;
@@ -667,6 +669,10 @@ int main(int argc, char **argv) {
         // ensure_hw_queues). One CSV row per frame as it is collected; render_time_ms is the frame's share of its sequence.
         if (frames_in_flight > 1 && rest.empty() && !freeze_frame) {
             frames_per_launch = std::min(frames_per_launch, std::max(1, 16 / std::max(1, batch_spp)));
+            // reprojection_mode 2 folds each frame into the one before it: one frame per launch sequence (include/rptr_hip.h)
+            bool realtime = base.params.reprojection_mode == 2;
+            for (const rptr::HostConfig &st : frames) realtime = realtime || st.params.reprojection_mode == 2;
+            if (realtime) frames_per_launch = 1;
             struct Pending {
                 rptr::RenderGroup::Sequence q;
                 int first;

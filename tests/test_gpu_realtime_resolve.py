@@ -1,0 +1,219 @@
+"""reprojection_mode 2 (REPROJECTION_MODE_ACCUMULATE) and the TAA pass on the GPU (csrc/realtime_resolve.h), against their numpy
+restatement (tests/realtime_resolve_ref.py) fed the library's own per-frame inputs: the frame means and AOV images of a mode-1 run of
+the same sequence (frame_offset / frame_id advance alike, so the random streams are the same), and the previous frame's stored images."""
+import math
+
+import numpy as np
+import pytest
+
+import realtime_resolve_ref as R
+from realtimepathtracingresearchframework_amd import abi, backend, scenes
+
+pytestmark = pytest.mark.gpu
+
+
+def _panned(cam, k, rate=0.003):
+    """the view yawed by rate * k radians about its up axis (a slow pan)"""
+    d = np.array(cam.dir[:], np.float64)
+    u = np.array(cam.up[:], np.float64)
+    r = np.cross(d, u)
+    r /= np.linalg.norm(r)
+    a = rate * k
+    nd = math.cos(a) * d + math.sin(a) * r
+    nd /= np.linalg.norm(nd)
+    c = abi.Camera()
+    c.pos[:] = cam.pos[:]
+    c.dir[:] = [float(v) for v in nd]
+    c.up[:] = cam.up[:]
+    c.fovy = cam.fovy
+    return c
+
+
+def _readback(r, W, H):
+    acc = np.zeros((H, W, 4), np.float32)
+    fb = np.zeros((H, W, 4), np.uint8)
+    nd = np.zeros((H, W, 4), np.float16)
+    mj = np.zeros((H, W, 4), np.float16)
+    r.readback_framebuffer(acc)
+    r.readback_framebuffer(fb)
+    r.readback_aov(1, nd)
+    r.readback_aov(2, mj)
+    return acc, fb, nd, mj
+
+
+def _sequence(scene, variant, W, H, mode, n, spp, options=None, resets=(0,), rate=0.003, frames_in_flight=1, asynchronous=False):
+    """n frames along the pan; per frame (accum, fb, nd, mj)"""
+    r = backend.RenderHip(options=options, frames_in_flight=frames_in_flight)
+    r.initialize(W, H)
+    r.set_scene(scene)
+    r.params.reprojection_mode = mode
+    cam = scene.camera_params()
+    out = []
+    cfg = lambda k: backend.RenderConfiguration(_panned(cam, k, rate), active_variant=variant, reset_accumulation=k in resets)
+    if not asynchronous:
+        for k in range(n):
+            r.render(cfg(k), spp=spp)
+            out.append(_readback(r, W, H))
+    else:  # two frames in flight: frame k + 1 is submitted before frame k is waited for
+        tickets = [r.render_async(cfg(0), spp=spp)]
+        for k in range(n):
+            if k + 1 < n:
+                tickets.append(r.render_async(cfg(k + 1), spp=spp))
+            r.wait(tickets[k])
+            out.append(_readback(r, W, H))
+    r.close()
+    return out
+
+
+CASES = [("lambert", lambda: scenes.grid(120, 60), abi.VARIANT_SIMPLE, 96, 64),
+         ("gltf", scenes.cornell32, abi.VARIANT_GLTF, 64, 64)]
+
+
+@pytest.mark.parametrize("name,make,variant,W,H", CASES, ids=[c[0] for c in CASES])
+def test_mode_two_matches_the_restatement_along_a_moving_camera(name, make, variant, W, H):
+    """8 frames of 2 spp along a slow pan: mode 1 gives each frame's mean and AOVs, mode 2 on the same sequence must store what the
+    restatement makes of them (1e-5 of the image's largest value) and show it within 1 LSB of RGBA8"""
+    s = make()
+    n, spp, window = 8, 2, 8
+    m1 = _sequence(s, variant, W, H, 1, n, spp)
+    m2 = _sequence(s, variant, W, H, 2, n, spp)
+    folded = 0
+    for k in range(n):
+        mean, _, nd, mj = m1[k]
+        acc2, fb2, nd2, mj2 = m2[k]
+        # the same samples in both runs (bit for bit: sky pixels carry NaN motion)
+        assert np.array_equal(nd.view(np.uint16), nd2.view(np.uint16)) and np.array_equal(mj.view(np.uint16), mj2.view(np.uint16)), k
+        if k == 0:
+            stored, shown = R.reproject(mean, nd, mj, None, None, spp, window, use_history=False)
+        else:
+            stored, shown, w = R.reproject(mean, nd, mj, m2[k - 1][0], m1[k - 1][2], spp, window, return_weight=True)
+            folded += int(np.count_nonzero(w < 1))
+        # every value within 1e-5 of the image's largest one. Both sides round every operation correctly, exp included: on the
+        # MI355X all frames of both cases agree bit for bit; the message counts the values that do not
+        scale = max(1.0, float(np.max(np.abs(stored))))
+        err = np.abs(acc2 - stored)
+        assert float(np.max(err)) <= 1e-5 * scale, (k, float(np.max(err)) / scale, int(np.count_nonzero(err > 1e-5 * scale)),
+                                                     int(np.count_nonzero(acc2.view(np.uint32) != stored.view(np.uint32))))
+        d = np.abs(fb2.astype(np.int32) - R.display(shown).astype(np.int32))
+        assert int(d.max()) <= 1, (k, int(d.max()), int(np.count_nonzero(d > 1)))
+    assert folded > 0.3 * (n - 1) * W * H   # the history is actually kept across the pan
+    # ... and mode 2 is not mode 0 / 1
+    assert not np.array_equal(m2[-1][0][..., :3], m1[-1][0][..., :3])
+
+
+def test_reprojection_lowers_the_error_of_a_panning_camera():
+    """a static scene, a slow pan, 16 frames of 1 spp: mode 2's last frame is closer to a 256-spp render of the last view than mode 0's,
+    which restarts the accumulation whenever the view moves"""
+    s = scenes.grid(120, 60)
+    W, H, n = 96, 64, 16
+    m2 = _sequence(s, abi.VARIANT_SIMPLE, W, H, 2, n, 1, rate=0.002)
+    m0 = _sequence(s, abi.VARIANT_SIMPLE, W, H, 0, n, 1, resets=tuple(range(n)), rate=0.002)
+    r = backend.RenderHip()
+    r.initialize(W, H)
+    r.set_scene(s)
+    r.render(backend.RenderConfiguration(_panned(s.camera_params(), n - 1, 0.002), active_variant=abi.VARIANT_SIMPLE, reset_accumulation=True), spp=256)
+    ref = np.zeros((H, W, 4), np.float32)
+    r.readback_framebuffer(ref)
+    r.close()
+    rmse = lambda img: float(np.sqrt(np.mean((img[..., :3] - ref[..., :3]) ** 2)))
+    e2, e0 = rmse(m2[-1][0]), rmse(m0[-1][0])
+    assert e2 < 0.8 * e0, (e2, e0)
+
+
+def test_frames_in_flight_are_bit_identical_to_the_synchronous_run():
+    """two frame contexts, frame k + 1 submitted before frame k is collected: the history still comes from the frame resolved before
+    (an event orders the resolves), every frame equals the synchronous run bit for bit"""
+    s = scenes.cornell32()
+    W, H, n = 64, 48, 6
+    sync = _sequence(s, abi.VARIANT_GLTF, W, H, 2, n, 2)
+    fif = _sequence(s, abi.VARIANT_GLTF, W, H, 2, n, 2, frames_in_flight=2, asynchronous=True)
+    for k in range(n):
+        assert np.array_equal(sync[k][0].view(np.uint32), fif[k][0].view(np.uint32)), k
+        assert np.array_equal(sync[k][1], fif[k][1]), k
+
+
+def test_reset_in_mode_two_is_mode_zeros_first_frame():
+    """reset_accumulation in mode 2 stores and shows the frame's mean: bit for bit what mode 0 shows after the same reset"""
+    s = scenes.cornell32()
+    W, H = 64, 48
+    a = _sequence(s, abi.VARIANT_GLTF, W, H, 2, 5, 2, resets=(0, 3))
+    b = _sequence(s, abi.VARIANT_GLTF, W, H, 0, 5, 2, resets=(0, 3))
+    for k in (0, 3):
+        assert np.array_equal(a[k][0].view(np.uint32), b[k][0].view(np.uint32)) and np.array_equal(a[k][1], b[k][1]), k
+    assert not np.array_equal(a[4][0], b[4][0])
+
+
+def test_taa_matches_the_restatement():
+    """option "taa" = 1 in mode 2: the RGBA8 frame after the pass equals the restatement fed the library's own pre-TAA frame (the same
+    sequence with "taa" = 0), its motion and its previous post-TAA frame, within 1 LSB; the first frame after the reset (frame_id 1 at 1
+    spp, process_taa.cpp:92) is left alone"""
+    s = scenes.grid(120, 60)
+    W, H, n = 96, 64, 6
+    pre = _sequence(s, abi.VARIANT_SIMPLE, W, H, 2, n, 1)
+    post = _sequence(s, abi.VARIANT_SIMPLE, W, H, 2, n, 1, options={"taa": 1})
+    for k in range(n):
+        assert np.array_equal(pre[k][0].view(np.uint32), post[k][0].view(np.uint32)), k   # the pass changes the RGBA8 frame only
+    assert np.array_equal(post[0][1], pre[0][1])
+    changed = 0
+    for k in range(1, n):
+        want = R.taa(pre[k][1], post[k - 1][1], post[k][3])
+        d = np.abs(post[k][1].astype(np.int32) - want.astype(np.int32))
+        assert int(d.max()) <= 1, (k, int(d.max()), int(np.count_nonzero(d > 1)))
+        changed += int(np.count_nonzero(post[k][1] != pre[k][1]))
+    assert changed > 0
+
+
+def test_taa_with_frames_in_flight_is_bit_identical_to_the_synchronous_run():
+    """option "taa" = 1 with two frame contexts and frame k + 1 submitted before frame k is collected: each context keeps the image
+    after the pass (the pass writes the context's copy), every frame equals the synchronous TAA run bit for bit"""
+    s = scenes.grid(120, 60)
+    W, H, n = 96, 64, 6
+    sync = _sequence(s, abi.VARIANT_SIMPLE, W, H, 2, n, 1, options={"taa": 1})
+    fif = _sequence(s, abi.VARIANT_SIMPLE, W, H, 2, n, 1, options={"taa": 1}, frames_in_flight=2, asynchronous=True)
+    for k in range(n):
+        assert np.array_equal(sync[k][0].view(np.uint32), fif[k][0].view(np.uint32)), k
+        assert np.array_equal(sync[k][1], fif[k][1]), k
+
+
+def _code(fn):
+    try:
+        fn()
+    except backend.BackendError as e:
+        return e.code
+    return 0
+
+
+def test_unsupported_combinations_are_refused():
+    s = scenes.cornell32()
+    W, H = 32, 32
+    cfg = backend.RenderConfiguration(s.camera_params(), active_variant=abi.VARIANT_GLTF, reset_accumulation=True)
+
+    def handle(**kw):
+        r = backend.RenderHip(**kw)
+        r.initialize(W, H)
+        r.set_scene(s)
+        r.params.reprojection_mode = 2
+        return r
+
+    def refused(r, fn, text):
+        assert _code(fn) == abi.RPTR_E_UNSUPPORTED
+        assert text in r._L.rptr_hip_last_error(r._h), r._L.rptr_hip_last_error(r._h)
+
+    r = handle(rank=0, world_size=2, stripe_rows=8)   # stripes of other ranks hold the neighbours
+    refused(r, lambda: r.render(cfg, spp=1), b"world_size")
+    r.close()
+    r = handle(frames_in_flight=2)                    # several frames in one launch sequence
+    refused(r, lambda: r.render_batch_async(cfg, spp=1, n_frames=2), b"batches of 2 frames")
+    r.close()
+    r = handle(options={"aovs": 0})                   # no motion, no normal + depth
+    refused(r, lambda: r.render(cfg, spp=1), b'"aovs" is 0')
+    r.close()
+    r = handle(options={"taa": 1})                    # TAA runs in mode 2 only ...
+    r.params.reprojection_mode = 1
+    refused(r, lambda: r.render(cfg, spp=1), b"reprojection_mode 2 only")
+    r.params.reprojection_mode = 2                    # ... at the render resolution
+    r.params.render_upscale_factor = 2
+    refused(r, lambda: r.render(cfg, spp=1), b"render_upscale_factor")
+    r.params.render_upscale_factor = 1
+    assert _code(lambda: r.render(cfg, spp=1)) == 0
+    r.close()
