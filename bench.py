@@ -14,10 +14,15 @@ Strong scaling: the frame is fixed, N GPUs share it.
 `python bench.py --gpus N` without a torch.distributed.run environment starts the
 N ranks itself (re-executes under `python -m torch.distributed.run`).
 
-Rank 0 prints ONE JSON line (contract in the task description) carrying
+A plain run sets up, warms up, times --steps frames, writes --dump-outputs and
+prints ONE JSON line (rank 0): metric / value / unit / ms_per_step / config, and
+`gather` at N > 1. Everything else takes runs of its own and comes with --full:
 `roofline` (dominant kernel = closest-hit traversal `rp_k_extend`; DESIGN.md section 6
-says what each figure is) and, at N=1, `cpu_baseline` (the CPU oracle timed on the
-same frame on the host cores).
+says what each figure is; with the exclusive stage passes, the sustained, static-camera
+and latency legs behind it), `boundary` (bin/rptr_hip on the same workload),
+`other_configs` (C3 - C5), at N=1 `cpu_baseline` (the CPU oracle timed on the same
+frame on the host cores), and at N > 1 the RCCL probe's informational stages. The
+timed region and `value` are the same either way.
 """
 import argparse
 import json
@@ -116,6 +121,10 @@ def parse_args():
                          "gather under a time-out before the real run commits to them)")
     ap.add_argument("--probe-timeout", type=float, default=150.0)
     ap.add_argument("--rccl-probe", action="store_true", help="(internal) run as the probe child of a rank")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the benchmark measures: roofline (exclusive stage passes, counted frames, "
+                         "sustained and static-camera legs, latency legs), boundary, other_configs, cpu_baseline, and at N > 1 the RCCL "
+                         "probe's peer-write and transport-timing stages. The --no-* switches and --sustained-seconds below trim a --full run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--fast-math", type=int, default=-1, choices=[-1, 0, 1],
                     help="library option fast_math (csrc/dmath.h): 1 = the shading stages' division / square root on the hardware's 1-ulp instructions; -1: the library's default (0, IEEE)")
@@ -188,6 +197,10 @@ def rccl_probe_child(args):
         r.comm_stats()   # waits for this rank's send
     dist.barrier()
     print("PROBE native 1", flush=True)
+    if not args.full:   # (stages 3 and 4 inform the line; the run does not depend on them)
+        r.close()
+        dist.destroy_process_group()
+        return
     # Stage 3, informational (nothing of the run depends on it): the peer-write transport for one process per GPU (--gather ipc) on THIS
     # node's devices -- the same two frames on a fresh handle, gathered through hipIpc-mapped stores into rank 0's frame, must equal the frame
     # RCCL just delivered, bit for bit. The line's gather.probe.ipc says whether remote stores over the node's fabric did that.
@@ -259,7 +272,7 @@ def run_rccl_probe(args, timeout_s, port_offset=1):
     env["MASTER_ADDR"] = "127.0.0.1" if os.environ.get("MASTER_ADDR", "127.0.0.1") in ("localhost", "127.0.0.1") else os.environ["MASTER_ADDR"]
     for k in ("TORCHELASTIC_RUN_ID", "TORCHELASTIC_USE_AGENT_STORE", "TORCHELASTIC_RESTART_COUNT", "TORCHELASTIC_MAX_RESTARTS"):
         env.pop(k, None)   # the child makes its own TCP store on MASTER_PORT + 1, it does not join the agent's
-    cmd = [sys.executable, os.path.abspath(__file__), "--rccl-probe"] + (["--same-device"] if args.same_device else [])
+    cmd = [sys.executable, os.path.abspath(__file__), "--rccl-probe"] + (["--same-device"] if args.same_device else []) + (["--full"] if args.full else [])
     t0 = time.time()
     p = subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, start_new_session=True)
     note = ""
@@ -636,7 +649,7 @@ def main():
         rl.close()
         return
     latency_in_children = world == 1 and args.emulate_world <= 1 and not args.profile_pass
-    if not args.profile_pass and not latency_in_children:
+    if args.full and not args.profile_pass and not latency_in_children:
         rl = latency_handle(1)
         latency["1"] = latency_of(rl, 1, n_lat)
         rl.close()
@@ -847,6 +860,53 @@ def main():
     if args.dump_outputs and rank == 0:   # (before anything else renders on this handle)
         dump_outputs(args.dump_outputs, last_frame(), acc["last_rays"])
 
+    def headline(elapsed, rays):
+        """the line's own fields, the same in a plain and a --full run: the timed region's rate (all ranks' rays over the slowest rank's
+        time at N > 1) and the configuration it ran"""
+        K = args.steps
+        bsdf = "diffuse-only" if variant == abi.VARIANT_SIMPLE else "glTF"
+        which = "configs[2]" if args.lights else "configs[1]"
+        if args.scene == "forest":
+            what = "C4: instanced forest, %d unique / %d instanced triangles, %d instances" % (scene.num_tris(), scene.num_instanced_tris(),
+                                                                                              len(scene.instances))
+        elif args.animate:
+            what = "C5: animated %d-triangle height field (dynamic mesh, device-side vertex animation + BVH refit every frame)" % scene.num_tris()
+        else:
+            what = "%s: procedural %d-triangle height field%s" % (which, scene.num_tris(),
+                                                                  " + 512 emissive triangles (binned-RIS NEE)" if args.lights else "")
+        return {
+            "metric": "Mrays/s", "value": round(rays / elapsed / 1e6, 3), "unit": "Mrays/s", "n_gpus": world, "steps": K, "warmup": args.warmup,
+            "ms_per_step": round(elapsed * 1e3 / K, 4), "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32",
+            "data": "synthetic",
+            "config": {"workload": "%s, %dx%d, %d spp, %s BSDF, sun+sky, max depth 9" % (what, W, H, spp, bsdf),
+                       "camera": "one view for all frames" if args.static_camera else "moves every frame (a camera per frame inside a launch sequence)",
+                       "frame_schedule": "stage launches", "fast_math": fast_math_in_force,
+                       "frames_in_flight": fif, "frames_per_launch_sequence": batch_frames, "flattened_instances": bool(flatten) and len(scene.instances) > 1,
+                       "parallelism": "tile%d" % world if args.emulate_world <= 1 else "rank 0 of an emulated tile%d split" % args.emulate_world, "stripe_rows": args.stripe_rows, "rays_per_step": rays // K,
+                       "scene_gen_s": round(t_scene, 2), "bvh_build_s": round(t_build, 2),
+                       "bvh": {"built_on": "device (csrc/ploc.h)" if bvh_on_device else "host (csrc/bvh_build.cpp)", "acceleration_structure_step_ms": round(bvh_step_ms, 1),
+                               "device_ms": round(bvh_device_ms, 2), "area_cost": round(bvh_area_cost, 1),
+                               "traversal_thresholds": {"node_min": trav_node_min or 10, "refill_min": trav_refill_min or 48,
+                                                        "pool_entries": int(os.environ.get("RPTR_TRAVERSE_FETCH", "0")) or (256 if trav_node_min else 384),
+                                                        "preset": "dense (area cost >= 24)" if trav_node_min else "default"}}},
+        }
+
+    if not args.full:
+        # a plain run ends here: the line's own fields (and the gather's, N > 1). Everything below renders or runs programs of its own.
+        if world > 1:
+            elapsed, ext_ms, gather_host_ms, _, rays, _ = combine_ranks(dist, elapsed, ext_ms, gather_host_ms, dict.fromkeys(SERIAL_KEYS, 0.0), rays, None)
+        if rank == 0:
+            out = headline(elapsed, rays)
+            if world > 1:   # (no one-frame latency: that leg is --full's)
+                out["gather"] = gather_report(gather_mode, gather_transport, probe, batch_frames, batched_gather, gather_gpu_ms, gather_host_ms, gathers_timed,
+                                              W * H * 16 - my_bytes, gather_note, None)
+            print(json.dumps(out), flush=True)
+        if world == 1:
+            r.close()
+        else:
+            dist.destroy_process_group()
+        return
+
     # untimed, one frame at a time, on a SECOND handle with one frame context (a traversal launch then asks for all the blocks a CU holds;
     # with 11 contexts each launch is sized to share the GPU with ten others): (1) events around every stage -> EXCLUSIVE launch durations
     # (nothing else on the GPU): what the roofline figures use; (2) instrumented frames: node / triangle visits of this rank's queries
@@ -949,7 +1009,6 @@ def main():
 
     K = args.steps
     ms_per_step = elapsed * 1e3 / K
-    mrays = rays / elapsed / 1e6
     # ---- roofline of the dominant kernel: rp_k_extend (closest-hit BVH4 traversal), rank 0's share.
     # All durations below are EXCLUSIVE: HIP events on the dispatch packets of frames rendered one at a time (nothing else on the GPU).
     primary = r.local_pixel_count() * spp  # the first launch computes its camera rays and its queue instead of reading them
@@ -1113,33 +1172,8 @@ def main():
     if refit_ms is not None:
         roofline["update_vertices_and_refit_ms"] = round(refit_ms, 4)
         roofline["bvh_policy"] = {"rebuild_budget": args.rebuild_budget, "device_rebuilds": r.bvh_rebuild_count()}
-    bsdf = "diffuse-only" if variant == abi.VARIANT_SIMPLE else "glTF"
-    which = "configs[2]" if args.lights else "configs[1]"
-    if args.scene == "forest":
-        what = "C4: instanced forest, %d unique / %d instanced triangles, %d instances" % (scene.num_tris(), scene.num_instanced_tris(),
-                                                                                          len(scene.instances))
-    elif args.animate:
-        what = "C5: animated %d-triangle height field (dynamic mesh, device-side vertex animation + BVH refit every frame)" % scene.num_tris()
-    else:
-        what = "%s: procedural %d-triangle height field%s" % (which, scene.num_tris(),
-                                                              " + 512 emissive triangles (binned-RIS NEE)" if args.lights else "")
-    out = {
-        "metric": "Mrays/s", "value": round(mrays, 3), "unit": "Mrays/s", "n_gpus": world, "steps": K, "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32",
-        "data": "synthetic",
-        "config": {"workload": "%s, %dx%d, %d spp, %s BSDF, sun+sky, max depth 9" % (what, W, H, spp, bsdf),
-                   "camera": "one view for all frames" if args.static_camera else "moves every frame (a camera per frame inside a launch sequence)",
-                   "frame_schedule": "stage launches", "fast_math": fast_math_in_force,
-                   "frames_in_flight": fif, "frames_per_launch_sequence": batch_frames, "flattened_instances": bool(flatten) and len(scene.instances) > 1,
-                   "parallelism": "tile%d" % world if args.emulate_world <= 1 else "rank 0 of an emulated tile%d split" % args.emulate_world, "stripe_rows": args.stripe_rows, "rays_per_step": rays // K,
-                   "scene_gen_s": round(t_scene, 2), "bvh_build_s": round(t_build, 2),
-                   "bvh": {"built_on": "device (csrc/ploc.h)" if bvh_on_device else "host (csrc/bvh_build.cpp)", "acceleration_structure_step_ms": round(bvh_step_ms, 1),
-                           "device_ms": round(bvh_device_ms, 2), "area_cost": round(bvh_area_cost, 1),
-                           "traversal_thresholds": {"node_min": trav_node_min or 10, "refill_min": trav_refill_min or 48,
-                                                    "pool_entries": int(os.environ.get("RPTR_TRAVERSE_FETCH", "0")) or (256 if trav_node_min else 384),
-                                                    "preset": "dense (area cost >= 24)" if trav_node_min else "default"}}},
-        "roofline": roofline,
-    }
+    out = headline(elapsed, rays)
+    out["roofline"] = roofline
     if world > 1:
         out["gather"] = gather_report(gather_mode, gather_transport, probe, batch_frames, batched_gather, gather_gpu_ms, gather_host_ms, gathers_timed,
                                       W * H * 16 - my_bytes, gather_note, latency_1_per_rank)
@@ -1180,7 +1214,7 @@ def main():
                 ("c4", ["--scene", "forest"]), ("c5", ["--animate", "--width", "3840", "--height", "2160", "--spp", "2"]))
         out["other_configs"] = {}
         for name, cfg_args in legs:
-            cmd = [sys.executable, os.path.abspath(__file__)] + cfg_args + ["--steps", "100", "--warmup", "4", "--no-cpu-baseline", "--no-boundary", "--no-other-configs",
+            cmd = [sys.executable, os.path.abspath(__file__)] + cfg_args + ["--full", "--steps", "100", "--warmup", "4", "--no-cpu-baseline", "--no-boundary", "--no-other-configs",
                                                                            "--sustained-seconds", "0.4"]   # (sustained + static-camera legs: C4's moving views cost 20 % more than its configuration's)
             t_leg = time.time()
             try:

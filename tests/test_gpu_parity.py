@@ -455,6 +455,29 @@ def test_bench_two_ranks_on_one_gpu_with_gloo(tmp_path):
     assert "cpu_baseline" not in d
 
 
+def test_bench_plain_run_prints_the_headline_only(tmp_path):
+    """`bench.py --gpus 1 --steps N --warmup W` without --full: set-up, warm-up, the timed steps, --dump-outputs and the line -- no roofline,
+    latency, boundary, other configurations or CPU baseline, which take runs of their own"""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "8", "--warmup", "2", "--grid", "100x50", "--width", "320",
+           "--height", "180", "--dump-outputs", str(tmp_path)]
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["metric"] == "Mrays/s" and d["unit"] == "Mrays/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["n_gpus"] == 1 and d["steps"] == 8 and d["warmup"] == 2 and d["ms_per_step"] > 0
+    assert abs(d["value"] - d["config"]["rays_per_step"] / (d["ms_per_step"] * 1e3)) < 1e-2 * d["value"]
+    assert not {"roofline", "boundary", "other_configs", "cpu_baseline", "gather"} & set(d)
+    img = np.load(str(tmp_path / "frame_rgba.npy"))
+    rays = np.load(str(tmp_path / "frame_rays.npy"))
+    assert img.shape == (180, 320, 4) and np.isfinite(img).all() and img[..., :3].max() > 0 and rays.shape == (2,) and rays[0] > 0
+
+
 def test_bench_gpus_n_starts_its_own_ranks():
     """`python bench.py --gpus 2` WITHOUT torch.distributed.run (the way a driver may call it): bench.py re-executes itself under
     torch.distributed.run, one JSON line comes back"""
@@ -464,7 +487,7 @@ def test_bench_gpus_n_starts_its_own_ranks():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--grid", "100x50", "--width", "320",
-           "--height", "180", "--dist-backend", "gloo", "--same-device"]
+           "--height", "180", "--dist-backend", "gloo", "--same-device", "--full"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -489,7 +512,7 @@ def test_bench_n_ranks_dry_run_probes_rccl_and_falls_back_without_hanging():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--grid", "100x50", "--width", "320",
-           "--height", "180", "--same-device", "--probe-timeout", "120"]
+           "--height", "180", "--same-device", "--probe-timeout", "120", "--full"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -530,7 +553,7 @@ def test_bench_n_ranks_with_the_ipc_gather_on_one_device():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "8", "--warmup", "2", "--grid", "100x50", "--width", "320",
-           "--height", "180", "--same-device", "--probe-timeout", "120", "--gather", "ipc", "--no-cpu-baseline"]
+           "--height", "180", "--same-device", "--probe-timeout", "120", "--gather", "ipc", "--no-cpu-baseline", "--full"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert p.returncode == 0, p.stderr[-3000:]
     d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])

@@ -2,7 +2,7 @@
 # A/B of library variants: tools/ab.sh <lib.so> [<lib.so> ...]  (bench.py, no CPU baseline), prints ms/frame + stage split
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 for lib in "$@"; do
-  RPTR_HIP_LIB=$lib python $R/bench.py --no-cpu-baseline --steps ${AB_STEPS:-100} --warmup 5 ${BENCH_ARGS:-} 2>/dev/null | python3 -c "
+  RPTR_HIP_LIB=$lib python $R/bench.py --full --no-cpu-baseline --steps ${AB_STEPS:-100} --warmup 5 ${BENCH_ARGS:-} 2>/dev/null | python3 -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

@@ -1,7 +1,7 @@
 #!/bin/bash
 # tools/fetch_sweep.sh: option traverse_fetch (pool size of a traversal wave) against the number of frames in flight
 for f in ${FETCHES:-0 384 512 768}; do
-RPTR_TRAVERSE_FETCH=$f python bench.py --no-cpu-baseline --no-probe --steps 100 --warmup 5 ${BENCH_ARGS:-} 2>/dev/null | python3 -c "
+RPTR_TRAVERSE_FETCH=$f python bench.py --full --no-cpu-baseline --no-probe --steps 100 --warmup 5 ${BENCH_ARGS:-} 2>/dev/null | python3 -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

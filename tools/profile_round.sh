@@ -14,20 +14,20 @@ bash tools/valu_issue.sh $TAG > $O/valu_issue_run.txt 2>&1
 bash tools/pmc_workloads.sh $TAG c2 c3 c3_two_level c4_flat c4_two_level c5 > $O/pmc_workloads.txt 2>&1
 bash tools/prof.sh ${TAG}_exclusive --profile-pass --steps 20 --warmup 2 > $O/prof_exclusive.txt 2>&1
 cp gpurun_out/prof_${TAG}_exclusive/*kernel_stats.csv $O/kernel_stats_exclusive_profile_pass.csv 2>/dev/null
-bash tools/prof.sh ${TAG}_pipelined --steps 200 > $O/prof_pipelined.txt 2>&1
+bash tools/prof.sh ${TAG}_pipelined --full --steps 200 > $O/prof_pipelined.txt 2>&1
 cp gpurun_out/prof_${TAG}_pipelined/*kernel_stats.csv $O/kernel_stats_pipelined_steps200.csv 2>/dev/null
 grep '^{' gpurun_out/prof_${TAG}_pipelined/bench.log | tail -1 > $O/bench_under_rocprof_steps200.json
-python3 bench.py > $O/bench_default.json 2> $O/bench_default.err
-python3 bench.py --lights --variant gltf --spp 8 > $O/bench_c3.json 2>/dev/null
-python3 bench.py --no-cpu-baseline --lights --variant gltf --spp 8 --flatten 0 > $O/bench_c3_two_level.json 2>/dev/null
-python3 bench.py --scene forest > $O/bench_c4.json 2>/dev/null
-RPTR_BVH_BUILDER=host python3 bench.py --no-cpu-baseline --scene forest > $O/bench_c4_host_built_tree.json 2>/dev/null
-python3 bench.py --no-cpu-baseline --scene forest --flatten 0 > $O/bench_c4_two_level.json 2>/dev/null
-python3 bench.py --animate --width 3840 --height 2160 --spp 2 > $O/bench_c5.json 2>/dev/null
-for n in 2 4 8; do python3 bench.py --no-cpu-baseline --emulate-world $n > $O/bench_emulated_world$n.json 2>/dev/null; done
+python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+python3 bench.py --full --lights --variant gltf --spp 8 > $O/bench_c3.json 2>/dev/null
+python3 bench.py --full --no-cpu-baseline --lights --variant gltf --spp 8 --flatten 0 > $O/bench_c3_two_level.json 2>/dev/null
+python3 bench.py --full --scene forest > $O/bench_c4.json 2>/dev/null
+RPTR_BVH_BUILDER=host python3 bench.py --full --no-cpu-baseline --scene forest > $O/bench_c4_host_built_tree.json 2>/dev/null
+python3 bench.py --full --no-cpu-baseline --scene forest --flatten 0 > $O/bench_c4_two_level.json 2>/dev/null
+python3 bench.py --full --animate --width 3840 --height 2160 --spp 2 > $O/bench_c5.json 2>/dev/null
+for n in 2 4 8; do python3 bench.py --full --no-cpu-baseline --emulate-world $n > $O/bench_emulated_world$n.json 2>/dev/null; done
 # the N > 1 path end to end on this box's one GPU (both ranks on cuda:0: the RCCL probe refuses, the run falls back and says so) with every rank
 # under rocprofv3: what tools/prof_ranks.sh <tag> 8 gives on a real node
-bash tools/prof_ranks.sh ${TAG}_ranks 2 --same-device > $O/prof_ranks_same_device.txt 2>&1
+bash tools/prof_ranks.sh ${TAG}_ranks 2 --same-device --full > $O/prof_ranks_same_device.txt 2>&1
 cp gpurun_out/${TAG}_ranks/bench_gpus2.json $O/bench_gpus2_same_device.json 2>/dev/null
 cp gpurun_out/${TAG}_ranks/hbm_gbs_per_rank.txt $O/hbm_gbs_per_rank_same_device.txt 2>/dev/null
 python3 - $O <<'PY'

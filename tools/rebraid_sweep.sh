@@ -1,6 +1,6 @@
 # tools/rebraid_sweep.sh: the two-level forest (C4 as instanced geometry) over re-braiding widths and collapse rules (diffuse BSDF, as profiles/*_c4_two_level)
 run() {
-  env "$@" timeout 600 python bench.py --scene forest --flatten 0 --steps 40 --warmup 4 --no-cpu-baseline --sustained-seconds 0 --static-camera 2>/dev/null | python -c "
+  env "$@" timeout 600 python bench.py --full --scene forest --flatten 0 --steps 40 --warmup 4 --no-cpu-baseline --sustained-seconds 0 --static-camera 2>/dev/null | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

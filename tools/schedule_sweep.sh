@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd $R
 run() { # label, bench args
-  python bench.py $2 --no-cpu-baseline --no-boundary --no-probe --steps ${STEPS:-80} --warmup 5 2>/dev/null | python3 -c "
+  python bench.py $2 --full --no-cpu-baseline --no-boundary --no-probe --steps ${STEPS:-80} --warmup 5 2>/dev/null | python3 -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):
