@@ -470,8 +470,9 @@ int rptr_hip_set_stage_timing(rptr_hip_t *h, int level);
  *   max_batch_spp            0         initialize        sample slots in flight per frame context; 0: min(16, what the budget      RPTR_MAX_BATCH_SPP
  *                                                        holds)
  *   path_budget_mb           6144      initialize        path state per frame context                                              RPTR_PATH_BUDGET_MB
- *   blocks_per_cu            0         initialize        persistent traversal blocks per CU; 0: occupancy, shared between the      RPTR_BLOCKS_PER_CU
- *                                                        frame contexts
+ *   blocks_per_cu            0         initialize        persistent traversal blocks per CU; 0: occupancy for a frame alone on     RPTR_BLOCKS_PER_CU
+ *                                                        the GPU, about 12 / n per CU for a frame submitted while n - 1 others
+ *                                                        are in flight (n at most the hardware queues, GPU_MAX_HW_QUEUES)
  *   side_connect             -1        initialize        shadow rays of bounce b on a side stream beside the closest-hit rays of   RPTR_SIDE_CONNECT
  *                                                        b + 1; -1: with one frame context, and with two for a frame submitted
  *                                                        while no other is in flight (a synchronous loop); off with more
@@ -503,7 +504,11 @@ int rptr_hip_set_stage_timing(rptr_hip_t *h, int level);
  *   Read-only through rptr_hip_get_option: "bvh_rebuild_failures" -- device-side rebuilds of dynamic meshes that could not start (no memory for
  *   their work space); such a mesh is refitted on its old topology, the frame is rendered, the next refit tries again; "sample_slots" -- the
  *   sample slots a frame context holds once rptr_hip_initialize has sized the path state ("max_batch_spp", or what "path_budget_mb" allows:
- *   16 up to ~2.9 Mpixel per rank, 12 at 1440p, 5 at 4K): a launch sequence of n frames of s samples needs n * s <= sample_slots. */
+ *   16 up to ~2.9 Mpixel per rank, 12 at 1440p, 5 at 4K): a launch sequence of n frames of s samples needs n * s <= sample_slots. The
+ *   persistent closest-hit grids, in blocks (0 before rptr_hip_initialize): "traversal_resident_blocks" -- the blocks that fit on the device
+ *   at once; "traversal_grid_alone" -- the grid of a frame alone on the GPU; "traversal_grid_shared" -- that of a frame beside the most
+ *   others that can run at once; "traversal_concurrency" -- that most, min(frame contexts, hardware queues); "traversal_stack_blocks" --
+ *   the grid the stack scratch of a frame context holds; "last_traversal_grid" -- the first grid of the last submitted frame. */
 int rptr_hip_set_option(rptr_hip_t *h, const char *key, int64_t value);
 int rptr_hip_get_option(const rptr_hip_t *h, const char *key, int64_t *out_value);
 int rptr_hip_option_count(void);

@@ -81,6 +81,21 @@ int rptr_hip_get_option(const rptr_hip_t *h, const char *key, int64_t *out_value
         *out_value = (int64_t)h->max_batch_spp;                  // the path state -- "max_batch_spp" or what the budget allows; 0 before initialize)
         return RPTR_OK;
     }
+    if (h && key && out_value) { // (read-only: the persistent traversal grids initialize sized, in blocks of RP_TRAVERSE_BLOCK threads; 0 before it)
+        const struct { const char *key; int64_t v; } grids[] = {
+            {"traversal_resident_blocks", (int64_t)h->num_cus * h->resident_per_cu[0]}, // first closest-hit kernel: blocks that fit at once
+            {"traversal_grid_alone", h->resident_per_cu[0] ? traversal_grid(h, 0, 1) : 0},  // ... its grid in a frame alone on the GPU
+            {"traversal_grid_shared", h->resident_per_cu[0] ? traversal_grid(h, 0, h->max_concurrency) : 0}, // ... beside the most frames
+            {"traversal_stack_blocks", h->ctx.empty() ? 0 : (int64_t)(h->ctx[0].gstack_threads / RP_TRAVERSE_BLOCK)}, // the stack scratch
+            {"traversal_concurrency", h->max_concurrency}, // frames that can run side by side: min(frame contexts, hardware queues)
+            {"last_traversal_grid", h->last_grids[0]},     // the first closest-hit grid of the last submitted frame
+        };
+        for (const auto &g : grids)
+            if (!strcmp(key, g.key)) {
+                *out_value = g.v;
+                return RPTR_OK;
+            }
+    }
     const int k = find_option(key);
     if (k < 0 || !out_value) return fail(nullptr, RPTR_E_INVALID, "rptr_hip_get_option: unknown option \"%s\" or NULL result", key ? key : "(null)");
     *out_value = h ? h->opt.v[k] : effective_default_options().v[k];

@@ -414,16 +414,22 @@ static int render_batch_impl(rptr_hip_t *h, const RptrCamera *camera, bool per_f
     // the general instantiation of the path stages: a table point set, or a screen jitter (raster TAA) -- the shipped path carries neither
     const bool table_rng_later = h->rng_variant != RPTR_RNG_VARIANT_UNIFORM || h->params.enable_raster_taa != 0;
     const bool table_rng = table_rng_later;
-    bool side = c.side != nullptr, alone = h->ctx.size() == 1;
-    if (h->ctx.size() == 2) {
-        alone = true;
-        for (FrameCtx &o : h->ctx)
-            if (&o != &c && o.pending && !o.synced && hipEventQuery(o.ev_end) != hipSuccess) alone = false; // another frame is in flight: it fills the GPU
-    }
+    // the frames of this handle that will share the GPU with this one: those still in flight on the device (up to the most that can run
+    // side by side). A frame alone gets the full grids (and, when the library chose side streams, its side stream); counted frames are
+    // launched as frames side by side are.
+    int concurrency = 1;
+    for (FrameCtx &o : h->ctx)
+        if (concurrency < h->max_concurrency && &o != &c && o.pending && !o.synced && hipEventQuery(o.ev_end) != hipSuccess) ++concurrency;
+    const bool alone = concurrency == 1;
+    bool side = c.side != nullptr;
     if (side && h->side_only_alone && !alone) side = false;
-    const bool full = alone && h->alone_blocks[0] > 0 && !count_traversal;
-    const int blocks_first = full ? h->alone_blocks[0] : h->persistent_blocks, blocks_later = full ? h->alone_blocks[1] : h->extend_later_blocks;
-    const int blocks_connect[2] = {full ? h->alone_blocks[2] : h->connect_blocks[0], full ? h->alone_blocks[3] : h->connect_blocks[1]};
+    if (count_traversal) concurrency = h->max_concurrency;
+    const int blocks_first = traversal_grid(h, 0, concurrency), blocks_later = traversal_grid(h, 1, concurrency);
+    const int blocks_connect[2] = {traversal_grid(h, 2, concurrency), traversal_grid(h, 3, concurrency)};
+    h->last_grids[0] = blocks_first;
+    h->last_grids[1] = blocks_later;
+    h->last_grids[2] = blocks_connect[0];
+    h->last_grids[3] = blocks_connect[1];
 
     SceneCopy &scn = h->ctx_scene.empty() ? h->master : h->ctx_scene[(size_t)(&c - h->ctx.data())];
     const bool follow = !h->ctx_scene.empty() && scn.version != h->refit_version;

@@ -340,9 +340,14 @@ struct rptr_hip {
         bool chain = false;          // the previously submitted frame ran the mode-2 resolve: its images are this frame's history
     } rt;
     size_t path_capacity = 0;
-    int persistent_blocks = 0;
+    // persistent traversal grids (traversal_grid below): [0] first / [1] later closest-hit, shadow rays [2] two-level / [3] one instance record
+    int resident_per_cu[4] = {0, 0, 0, 0}; // blocks per CU of each kernel that fit at once (its occupancy, at most 8)
+    int fixed_per_cu = 0;            // option "blocks_per_cu" as initialize read it (> 0: every launch gets this many per CU)
+    int hw_queues = 4;               // hardware queues of the process (GPU_MAX_HW_QUEUES when the handle was created; the runtime's default 4)
+    int max_concurrency = 1;         // frames of this handle that can run side by side: min(frame contexts, hw_queues)
+    int last_grids[4] = {0, 0, 0, 0}; // the grids of the last submitted frame (read-only options "last_grid_*")
+    int persistent_blocks = 0;       // the grids of max_concurrency frames side by side: ray queries and counted frames
     int extend_later_blocks = 0;     // grid of a closest-hit launch of bounce >= 1 (RP_EXTEND_LATER_WAVES)
-    int alone_blocks[4] = {0, 0, 0, 0}; // two frame contexts: the grids (first / later closest-hit, shadow rays [two-level, one record]) of a frame that is alone on the GPU
     int connect_blocks[2] = {0, 0};  // grid of a stand-alone shadow-ray launch, [single instance record ? 1 : 0] (RP_CONNECT_WAVES)
 
     // options (environment, read once)
@@ -398,20 +403,23 @@ static bool hip_was_initialised_before_us() {
 
 // may_set: RptrCreateInfo.flags & RPTR_CREATE_SET_HW_QUEUES -- the host lets this create edit the process's environment: when the variable
 // is unset (or was set by an earlier create of this library) it becomes kHwQueueLimit. Without it the library only reads the variable and
-// says (once, on stderr) when the frame contexts get fewer queues than that.
-static void ensure_hw_queues(int frames_in_flight, bool may_set) {
+// says (once, on stderr) when the frame contexts get fewer queues than that. Returns the queues the process has (what sizes the traversal
+// grids of frames side by side: no more of them run at once).
+static int ensure_hw_queues(int frames_in_flight, bool may_set) {
     static bool first_create = true;
     if (const char *s = getenv("RPTR_FRAMES_IN_FLIGHT")) frames_in_flight = atoi(s);
     // + the caller's stream + the communication stream, up to the limit
     const int want = std::min(std::max(1, std::min(frames_in_flight, 16)) + 2, kHwQueueLimit);
     const char *e = getenv("GPU_MAX_HW_QUEUES");
     const int have = e ? atoi(e) : 4;
+    int queues = std::max(1, have);
     if (may_set && first_create && (!e || g_hw_queues_set_by_library)) {
         // The setenv comes BEFORE any HIP call of this create: the first one makes the runtime read the variable.
         char buf[16];
         snprintf(buf, sizeof buf, "%d", kHwQueueLimit);
         setenv("GPU_MAX_HW_QUEUES", buf, 1);
         g_hw_queues_set_by_library = true;
+        queues = kHwQueueLimit;
         if (have != kHwQueueLimit && hip_was_initialised_before_us() && effective_default_options().v[OPT_QUIET] == 0)
             fprintf(stderr, "rptr_hip: RPTR_CREATE_SET_HW_QUEUES came too late -- the process already uses HIP with GPU_MAX_HW_QUEUES=%d, not %d "
                             "hardware queues\n", have, kHwQueueLimit);
@@ -424,6 +432,7 @@ static void ensure_hw_queues(int frames_in_flight, bool may_set) {
         warned = true;
     }
     first_create = false;
+    return queues;
 }
 
 #define HIP_TRY(h, expr)                                                                                   \
@@ -499,6 +508,18 @@ hipEvent_t next_event(FrameCtx &c, size_t &cursor) {
         c.ev_pool.push_back(e);
     }
     return c.ev_pool[cursor++];
+}
+
+// grid of a persistent traversal launch (kind: the index of resident_per_cu) of a frame that runs beside concurrency - 1 others of its
+// handle. A frame alone gets every block that fits; frames side by side share the CUs: each asks for about 12 / n blocks per CU, a
+// little more than its share, so that a frame whose neighbour ends early still fills the GPU (measured, profiles/r01_notes.md: 3
+// contexts 5 -> 4 blocks 1.50 -> 1.49 ms per full frame; 11 contexts 5 -> 1 blocks 0.30 -> 0.25 ms per 1/8 frame). The kernels pull their
+// work from a cursor: the grid changes no image and no ray count.
+int traversal_grid(const rptr_hip *h, int kind, int concurrency) {
+    if (h->fixed_per_cu > 0) return h->num_cus * h->fixed_per_cu;
+    const int occ = h->resident_per_cu[kind];
+    const int n = std::max(1, std::min(concurrency, h->max_concurrency));
+    return h->num_cus * (n == 1 ? occ : std::max(1, std::min(occ, (12 + n / 2) / n)));
 }
 
 int grid_for(const rptr_hip *h, size_t n, int per_cu = 8) {

@@ -69,7 +69,7 @@ int rptr_hip_create(const RptrCreateInfo *info, rptr_hip_t **out) {
         return fail(nullptr, RPTR_E_INVALID, "rptr_hip_create: RptrCreateInfo.abi_version is %d, this library implements version %d of include/rptr_hip.h "
                                              "(set abi_version = RPTR_HIP_ABI_VERSION; struct fields that used to be padding carry meaning now)",
                     info->abi_version, RPTR_HIP_ABI_VERSION);
-    ensure_hw_queues(info ? info->frames_in_flight : 1, info && (info->flags & RPTR_CREATE_SET_HW_QUEUES) != 0u);
+    const int hw_queues = ensure_hw_queues(info ? info->frames_in_flight : 1, info && (info->flags & RPTR_CREATE_SET_HW_QUEUES) != 0u);
     int n_dev = 0;
     hipError_t e = hipGetDeviceCount(&n_dev);
     if (e != hipSuccess || n_dev <= 0)
@@ -100,6 +100,7 @@ int rptr_hip_create(const RptrCreateInfo *info, rptr_hip_t **out) {
         return fail(nullptr, RPTR_E_NO_DEVICE, "hipGetDeviceProperties failed");
     }
     h->num_cus = prop.multiProcessorCount;
+    h->hw_queues = hw_queues;
     if (info && info->stream) h->stream = (hipStream_t)info->stream;
     {
         int fif = info ? info->frames_in_flight : 1;
@@ -246,7 +247,9 @@ int rptr_hip_initialize(rptr_hip_t *h, int fb_width, int fb_height) {
     h->max_batch_frames = (int)h->opt.v[OPT_MAX_BATCH_FRAMES];
     h->aovs = h->opt.v[OPT_AOVS] != 0;
     // (auto: handles with one or two frame contexts have side streams; a frame uses its context's when no other frame of the handle is in
-    // flight at its submission -- the synchronous loop of a host that holds the reference's two swap buffers, rptr_hip_render)
+    // flight at its submission -- the synchronous loop of a host that holds the reference's two swap buffers, rptr_hip_render. Not with
+    // more: their side streams would share hardware queues with other contexts' streams, and a frame queued behind a side stream's
+    // barrier on such a queue waits for the whole frame that forked it)
     h->side_connect = h->opt.v[OPT_SIDE_CONNECT] >= 0 ? (int)h->opt.v[OPT_SIDE_CONNECT] : (h->ctx.size() <= 2 ? 1 : 0);
     h->side_only_alone = h->opt.v[OPT_SIDE_CONNECT] < 0 && h->ctx.size() > 1;
     for (FrameCtx &c : h->ctx) {
@@ -303,41 +306,29 @@ int rptr_hip_initialize(rptr_hip_t *h, int fb_width, int fb_height) {
                 if ((rc = dev_alloc(h, &c.aov[k], npix_local, nullptr))) return rc;
                 HIP_TRY(h, hipMemsetAsync(c.aov[k], 0, npix_local * sizeof(uint2), h->stream));
             }
-    // persistent traversal kernels: as many blocks as are co-resident
-    int occ = 0;
-    HIP_TRY(h, rp_extend_blocks_per_cu(&occ));
-    occ = std::max(1, std::min(occ, 8));
-    // (handles with TWO frame contexts -- the reference's swap buffers -- keep the full-size grids as well: a frame submitted while no other
-    // is in flight, the synchronous loop, is launched like a frame of a one-context handle; side_only_alone above)
-    const bool keep_alone = h->ctx.size() == 2 && h->opt.v[OPT_BLOCKS_PER_CU] <= 0;
-    h->alone_blocks[0] = keep_alone ? h->num_cus * occ : 0;
-    // frames in flight share the CUs: with n contexts a traversal launch asks for about 12 / n blocks per CU instead of all that
-    // fit, so that the kernels of the other frames find room next to it (measured, profiles/r01_notes.md: 3 contexts 5 -> 4 blocks
-    // 1.50 -> 1.49 ms per full frame; 11 contexts 5 -> 1 blocks 0.30 -> 0.25 ms per 1/8 frame)
-    if (h->ctx.size() > 1) occ = std::max(1, std::min(occ, (int)((12 + h->ctx.size() / 2) / h->ctx.size())));
-    if (h->opt.v[OPT_BLOCKS_PER_CU] > 0) occ = (int)h->opt.v[OPT_BLOCKS_PER_CU];
-    h->persistent_blocks = h->num_cus * occ;
-    // the shadow-ray kernels may be compiled for more waves per SIMD than the closest-hit kernels (RP_CONNECT_WAVES): their launches get the
-    // blocks THEY can have resident (the same cap with frames in flight)
-    for (int sg = 0; sg < 2; ++sg) { // [0]: two-level scenes, [1]: scenes with one instance record (the instantiation compiled for six waves)
-        int occ_c = 0;
-        HIP_TRY(h, rp_connect_blocks_per_cu(sg, &occ_c));
-        occ_c = std::max(1, std::min(occ_c, 8));
-        h->alone_blocks[2 + sg] = keep_alone ? h->num_cus * occ_c : 0;
-        if (h->ctx.size() > 1) occ_c = std::max(1, std::min(occ_c, (int)((12 + h->ctx.size() / 2) / h->ctx.size())));
-        if (h->opt.v[OPT_BLOCKS_PER_CU] > 0) occ_c = (int)h->opt.v[OPT_BLOCKS_PER_CU];
-        h->connect_blocks[sg] = h->num_cus * occ_c;
-    }
-    int occ_l = 0;
-    HIP_TRY(h, rp_extend_later_blocks_per_cu(&occ_l));
-    occ_l = std::max(1, std::min(occ_l, 8));
-    h->alone_blocks[1] = keep_alone ? h->num_cus * occ_l : 0;
-    if (h->ctx.size() > 1) occ_l = std::max(1, std::min(occ_l, (int)((12 + h->ctx.size() / 2) / h->ctx.size())));
-    if (h->opt.v[OPT_BLOCKS_PER_CU] > 0) occ_l = (int)h->opt.v[OPT_BLOCKS_PER_CU];
-    h->extend_later_blocks = h->num_cus * occ_l;
+    // persistent traversal kernels: the blocks that fit per CU, and the grids of a frame alone / beside others (traversal_grid). The
+    // shadow-ray kernels may be compiled for more waves per SIMD than the closest-hit kernels (RP_CONNECT_WAVES): their launches get the
+    // blocks THEY can have resident.
+    int occ[4] = {0, 0, 0, 0};
+    HIP_TRY(h, rp_extend_blocks_per_cu(&occ[0]));
+    HIP_TRY(h, rp_extend_later_blocks_per_cu(&occ[1]));
+    HIP_TRY(h, rp_connect_blocks_per_cu(0, &occ[2])); // two-level scenes
+    HIP_TRY(h, rp_connect_blocks_per_cu(1, &occ[3])); // scenes with one instance record (the instantiation compiled for six waves)
+    for (int k = 0; k < 4; ++k) h->resident_per_cu[k] = std::max(1, std::min(occ[k], 8));
+    h->fixed_per_cu = (int)std::max<int64_t>(0, h->opt.v[OPT_BLOCKS_PER_CU]);
+    // frames of the handle in flight at once share the GPU, but no more of them run side by side than the process has hardware queues
+    // (streams that share a queue serialise): a frame's launches are sized at its submission for the frames then in flight
+    // (render_batch_impl); these are the grids of the most that can be
+    h->max_concurrency = std::max(1, std::min((int)h->ctx.size(), h->hw_queues));
+    h->persistent_blocks = traversal_grid(h, 0, h->max_concurrency);
+    h->extend_later_blocks = traversal_grid(h, 1, h->max_concurrency);
+    h->connect_blocks[0] = traversal_grid(h, 2, h->max_concurrency);
+    h->connect_blocks[1] = traversal_grid(h, 3, h->max_concurrency);
     h->tail_blocks = h->num_cus; // one block per CU (the tail kernel's LDS: two traversal stacks + the shade buffers)
-    const size_t stack_threads = (size_t)std::max(std::max(std::max(h->persistent_blocks, h->extend_later_blocks), std::max(h->connect_blocks[0], h->connect_blocks[1])),
-                                                  std::max(std::max(h->alone_blocks[0], h->alone_blocks[1]), std::max(h->alone_blocks[2], h->alone_blocks[3]))) * RP_TRAVERSE_BLOCK;
+    // the stack scratch holds the largest grid: that of a frame alone on the GPU (8 blocks per CU: 268 MB per stack on 256 CUs)
+    int stack_blocks = 0;
+    for (int k = 0; k < 4; ++k) stack_blocks = std::max(stack_blocks, traversal_grid(h, k, 1));
+    const size_t stack_threads = (size_t)stack_blocks * RP_TRAVERSE_BLOCK;
     for (FrameCtx &c : h->ctx) {
         c.gstack_threads = stack_threads;
         if ((rc = dev_alloc(h, &c.gstack, stack_threads * RPTR_BVH_STACK_DEPTH, nullptr))) return rc;
