@@ -1316,6 +1316,28 @@ void orc_simple_probe(const float base_color[3], const float n3[3], const float 
     weight3[0] = w.x; weight3[1] = w.y; weight3[2] = w.z;
     f3[0] = f.x; f3[1] = f.y; f3[2] = f.z;
 }
+// triangle-light solid angle and direction sample (tri.glsl:58-152) as rp_finish_tri_light_sample takes them: v9 = the three vertices
+// relative to the shading point, normalised here; u2 = the direction sample -> out9: solid angle, half-angle tangent, triangle parameters
+// (3), sampled direction (3), 1 / solid angle
+void orc_tri_light_probe(const float *v9, const float *u2, int n, float *out9) {
+    for (int i = 0; i < n; ++i) {
+        const float *v = v9 + 9 * i;
+        const vec3 d0 = normalize(vec3(v[0], v[1], v[2])), d1 = normalize(vec3(v[3], v[4], v[5])), d2 = normalize(vec3(v[6], v[7], v[8]));
+        vec3 tp;
+        const float tan_half = half_triangle_solid_angle_tan(d0, d1, d2, tp);
+        const float omega = 2.0f * fast_positive_atan(tan_half);
+        const vec3 dir = sample_solid_angle_polygon(d0, d1, d2, omega, tp, vec2(u2[2 * i], u2[2 * i + 1]));
+        const float o[9] = {omega, tan_half, tp.x, tp.y, tp.z, dir.x, dir.y, dir.z, 1.0f / omega};
+        memcpy(out9 + 9 * i, o, sizeof o);
+    }
+}
+// sample_sun_dir_pdf (sun.glsl:17-20) and nee_mis_heuristic(1, f, 1, g) (nee_interface.glsl:11-15) element by element
+void orc_sun_pdf(const float *cos_radius, int n, float *out) {
+    for (int i = 0; i < n; ++i) out[i] = sample_sun_dir_pdf(cos_radius[i]);
+}
+void orc_nee_mis(const float *pdf_f, const float *pdf_g, int n, float *out) {
+    for (int i = 0; i < n; ++i) out[i] = nee_mis_heuristic(1.0f, pdf_f[i], 1.0f, pdf_g[i]);
+}
 void orc_linear_to_srgb(const float *x, int n, float *out) {
     for (int i = 0; i < n; ++i) out[i] = linear_to_srgb(x[i]);
 }

@@ -414,6 +414,8 @@ struct SimpleMaterial {
 //   1 x 1 textures = one bilinear tap of level 0.
 // Mip levels: RptrTextureDesc.mip_levels levels stored back to back, level l = max(1, w >> l) x max(1, h >> l)
 // (vulkan/resource_utils.cpp:86-100); the reference uploads the levels its .vkt files hold and generates none.
+// Texel indices: floor(uv * size - 0.5) clamped to +-2^30 before the conversion to int (a NaN to -2^30), as csrc/dshade.h: the conversion
+// of a float beyond the int range is undefined in C++ (x86 gives INT_MIN, the GPU saturates) and index + 1 would overflow.
 struct TextureTable {
     const RptrTextureDesc *textures = nullptr;
     uint32_t num_textures = 0;
@@ -450,6 +452,7 @@ static inline vec4 fetch_texel(const TextureTable &tt, const RptrTextureDesc &t,
     if (t.srgb) return vec4(tt.srgb_lut[c[0]], tt.srgb_lut[c[1]], tt.srgb_lut[c[2]], float(c[3]) / 255.0f);
     return vec4(float(c[0]) / 255.0f, float(c[1]) / 255.0f, float(c[2]) / 255.0f, float(c[3]) / 255.0f);
 }
+static inline int texel_floor(float x0) { return int(fminf(fmaxf(x0, -1073741824.0f), 1073741824.0f)); }
 static inline int wrap_repeat(int i, int n) {
     i %= n;
     return i < 0 ? i + n : i;
@@ -460,8 +463,9 @@ static inline vec4 texture_bilinear(const TextureTable &tt, const RptrTextureDes
     const float x = uv.x * float(w) - 0.5f, y = uv.y * float(h) - 0.5f;
     const float x0 = floorf(x), y0 = floorf(y);
     const float fx = x - x0, fy = y - y0;
-    const int ix0 = wrap_repeat(int(x0), w), ix1 = wrap_repeat(int(x0) + 1, w);
-    const int iy0 = wrap_repeat(int(y0), h), iy1 = wrap_repeat(int(y0) + 1, h);
+    const int jx = texel_floor(x0), jy = texel_floor(y0);
+    const int ix0 = wrap_repeat(jx, w), ix1 = wrap_repeat(jx + 1, w);
+    const int iy0 = wrap_repeat(jy, h), iy1 = wrap_repeat(jy + 1, h);
     const vec4 c00 = fetch_texel(tt, t, v, ix0, iy0), c10 = fetch_texel(tt, t, v, ix1, iy0), c01 = fetch_texel(tt, t, v, ix0, iy1),
                c11 = fetch_texel(tt, t, v, ix1, iy1);
     const float gx = 1.0f - fx, gy = 1.0f - fy;
@@ -814,6 +818,8 @@ static inline vec3 sample_simple_brdf(const SimpleMaterial &mat, const vec3 n, c
 // MEGAKERNEL_MATERIALS switches on, :10-13; the RT-pipeline hit groups of vulkan/CMakeLists.txt:35-40 build it). Three components:
 // diffuse, GGX reflection, GGX transmission -- through a ONESIDED surface a refraction (w_h = -ior w_i - w_o, angle compression),
 // through a two-sided one the "thin" double reflection w_i = reflect(reflect(-w_o, w_h), n).
+// Known, as in the reference: the angle compression's denominator i.h ior + o.h cancels as ior -> 1 (i.h -> -o.h); at ior = 1 + 2^-23
+// the sample weights are not finite (csrc/dshade.h says the same).
 struct GLTFTransMaterial { // :15-35
     vec3 base_color;
     float metallic;

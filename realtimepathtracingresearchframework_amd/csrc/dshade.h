@@ -10,6 +10,7 @@
 //     values (no texture units on this path yet -> normal_map must be -1);
 //   * pow(x,5) is ((x*x)*(x*x))*x and pow(x,1.5) is x*sqrt(x).
 #pragma once
+#include <cmath>
 #include "../../include/rptr_bvh.h"
 #include "../../include/rptr_hip.h"
 #include "dmath.h"
@@ -582,6 +583,17 @@ struct RpMaterial { // GLTFMaterial (gltf_bsdf.glsl:15-35) / SimpleMaterial (sim
 //   rp_texture_lod(uv, lod): the two nearest levels blended by the fraction of the clamped lod
 //   rp_texture_grad(uv, ddx, ddy): eta = min(rho_max / rho_min, 12), N = ceil(eta) taps along the larger derivative at log2(rho_max / eta)
 // Levels are stored back to back, level l = max(1, w >> l) x max(1, h >> l) (RptrTextureDesc.mip_levels).
+// Texel indices: floor(uv * size - 0.5) is clamped to +-2^30 before it becomes an int (a NaN to -2^30), then wrapped. C++ leaves the
+// conversion of a float beyond the int range undefined -- v_cvt_i32_f32 saturates (NaN: 0), x86 returns INT_MIN -- and the index + 1 of
+// the second tap would overflow; beyond 2^30 texels a float holds no texel position any more (its ulp is 128 texels). The weights of a
+// NaN or infinite coordinate are NaN whatever the indices. oracle/oshade.h does the same.
+// RpScene::srgb_lut, computed on the host: the IEC 61966-2-1 decode of an 8-bit code (what a VK_FORMAT_*_SRGB fetch returns before filtering)
+static inline void rp_srgb_decode_lut(float lut[256]) {
+    for (int i = 0; i < 256; ++i) {
+        const float c = float(i) / 255.0f;
+        lut[i] = c <= 0.04045f ? c / 12.92f : std::pow((c + 0.055f) / 1.055f, 2.4f);
+    }
+}
 struct RpTexCoord { // HitPoint::uv + HitPoint::duvdxy
     V2 uv, ddx, ddy;
 };
@@ -604,6 +616,7 @@ RP_DEV float4 rp_texel(const RpScene &sc, const RpTexture &t, const RpMipView &v
     if (t.srgb) return make_float4(sc.srgb_lut[c.x], sc.srgb_lut[c.y], sc.srgb_lut[c.z], rp_fdiv(float(c.w), 255.0f));
     return make_float4(rp_fdiv(float(c.x), 255.0f), rp_fdiv(float(c.y), 255.0f), rp_fdiv(float(c.z), 255.0f), rp_fdiv(float(c.w), 255.0f));
 }
+RP_DEV int rp_texel_floor(float x0) { return int(fminf(fmaxf(x0, -1073741824.0f), 1073741824.0f)); }
 RP_DEV int rp_wrap_repeat(int i, int n) {
     if ((n & (n - 1)) == 0) return i & (n - 1); // power-of-two sizes (the usual case): no integer division (~30 instructions each, 4 per tap)
     i %= n;
@@ -613,8 +626,9 @@ RP_DEV float4 rp_texture_bilinear(const RpScene &sc, const RpTexture &t, const R
     const float x = uv.x * float(mv.w) - 0.5f, y = uv.y * float(mv.h) - 0.5f;
     const float x0 = floorf(x), y0 = floorf(y);
     const float fx = x - x0, fy = y - y0;
-    const int ix0 = rp_wrap_repeat(int(x0), mv.w), ix1 = rp_wrap_repeat(int(x0) + 1, mv.w);
-    const int iy0 = rp_wrap_repeat(int(y0), mv.h), iy1 = rp_wrap_repeat(int(y0) + 1, mv.h);
+    const int jx = rp_texel_floor(x0), jy = rp_texel_floor(y0);
+    const int ix0 = rp_wrap_repeat(jx, mv.w), ix1 = rp_wrap_repeat(jx + 1, mv.w);
+    const int iy0 = rp_wrap_repeat(jy, mv.h), iy1 = rp_wrap_repeat(jy + 1, mv.h);
     const float4 c00 = rp_texel(sc, t, mv, ix0, iy0), c10 = rp_texel(sc, t, mv, ix1, iy0), c01 = rp_texel(sc, t, mv, ix0, iy1), c11 = rp_texel(sc, t, mv, ix1, iy1);
     const float gx = 1.0f - fx, gy = 1.0f - fy;
     const float4 top = make_float4(c00.x * gx + c10.x * fx, c00.y * gx + c10.y * fx, c00.z * gx + c10.z * fx, c00.w * gx + c10.w * fx);
@@ -914,9 +928,10 @@ RP_DEV RpLobes rp_gltf_component_sampler(const RpMaterial &m, float o_dot_h_x, f
     float weight_sum = 0.0f;
     weight_sum += c.w0;
     weight_sum += c.w1;
+    // IEEE division in both builds: a denormal sum (a black metal at |o.h| -> 1) makes v_rcp_f32 return inf
     if (weight_sum > 0.0f) {
-        c.w0 = rp_fdiv(c.w0, weight_sum);
-        c.w1 = rp_fdiv(c.w1, weight_sum);
+        c.w0 = c.w0 / weight_sum;
+        c.w1 = c.w1 / weight_sum;
     } else
         c.w0 = 1.0f;
     return c;
@@ -1001,6 +1016,8 @@ RP_DEV V3 rp_sample_gltf_brdf(const RpMaterial &m, V3 n, V3 w_o, V3 &w_i, float 
 // ------------------------------------------------------------------ glTF BSDF with the transmission lobe
 // gltf_bsdf.glsl built with GLTF_SUPPORT_TRANSMISSION + GLTF_SUPPORT_TRANSMISSION_ROUGHNESS (RPTR_VARIANT_GLTF_TRANSMISSION): three
 // components -- diffuse, GGX reflection, GGX transmission (refraction through ONESIDED surfaces, thin double reflection otherwise)
+// Known, as in the reference: the angle compression 2 o.h / (i.h ior + o.h) of refraction cancels in its denominator as ior -> 1
+// (i.h -> -o.h). At ior = 1 + 2^-23 it gives non-finite sample weights in both builds (tests/test_gpu_shade_functions.py reports them).
 RP_DEV V3 rp_refract3(V3 I, V3 N, float eta) { // GLSL refract
     const float d = dot3(N, I);
     const float k = 1.0f - (eta * eta) * (1.0f - d * d);
@@ -1067,10 +1084,11 @@ RP_DEV RpLobes3 rp_gltf_t_component_sampler(const RpMaterial &m, float ior, floa
     weight_sum += c.w0;
     weight_sum += c.w1;
     weight_sum += c.w2;
+    // IEEE division in both builds: a denormal sum (a black metal at |o.h| -> 1) makes v_rcp_f32 return inf
     if (weight_sum > 0.0f) {
-        c.w0 = rp_fdiv(c.w0, weight_sum);
-        c.w1 = rp_fdiv(c.w1, weight_sum);
-        c.w2 = rp_fdiv(c.w2, weight_sum);
+        c.w0 = c.w0 / weight_sum;
+        c.w1 = c.w1 / weight_sum;
+        c.w2 = c.w2 / weight_sum;
     } else
         c.w0 = 1.0f;
     return c;
@@ -1403,7 +1421,9 @@ RP_DEV V3 rp_sample_sun_dir(V3 sun_dir, float cos_radius, V2 s) { // rendering/l
     return mul(fr, v3(sinTheta * cosf(phi), sinTheta * sinf(phi), cosTheta));
 }
 RP_DEV float rp_sun_dir_pdf(float cos_radius) { return rp_frcp(2.0f * RP_PI * (1.0f - cos_radius)); } // sun.glsl:17-20
-RP_DEV float rp_nee_mis(float pdf_f, float pdf_g) { return rp_fdiv(pdf_f, pdf_f + pdf_g); }                 // nee_interface.glsl:11-15 (n=1)
+// nee_interface.glsl:11-15 (n=1). IEEE division in both builds: a * rcp(b) gives inf / NaN for denormal pdfs and 0 for sums above 2^126
+// (v_rcp_f32 flushes), where the quotient is 0.5 (tests/test_gpu_shade_functions.py test_sun_and_mis)
+RP_DEV float rp_nee_mis(float pdf_f, float pdf_g) { return pdf_f / (pdf_f + pdf_g); }
 
 // rendering/lights/sky_model_arhosek/sky_model.glsl:40-59
 RP_DEV V3 rp_skymodel_radiance(const RptrSkyModelParams &st, V3 sun_dir, V3 view_dir) {

@@ -68,11 +68,8 @@ static int scene_upload_textures(rptr_hip *h, const RptrSceneDesc *s, RpTexture 
         }
         if ((rc = dev_alloc(h, &d_textures, std::max<size_t>(1, tex.size()), &h->scene_allocs))) return rc;
         if (!tex.empty()) HIP_TRY(h, hipMemcpy(d_textures, tex.data(), tex.size() * sizeof(RpTexture), hipMemcpyHostToDevice));
-        float lut[256]; // IEC 61966-2-1 decode of an 8-bit code (what a VK_FORMAT_*_SRGB fetch returns before filtering)
-        for (int i = 0; i < 256; ++i) {
-            const float c = float(i) / 255.0f;
-            lut[i] = c <= 0.04045f ? c / 12.92f : std::pow((c + 0.055f) / 1.055f, 2.4f);
-        }
+        float lut[256];
+        rp_srgb_decode_lut(lut);
         if ((rc = dev_alloc(h, &d_srgb_lut, 256, &h->scene_allocs))) return rc;
         HIP_TRY(h, hipMemcpy(d_srgb_lut, lut, sizeof(lut), hipMemcpyHostToDevice));
     }
