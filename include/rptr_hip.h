@@ -611,10 +611,44 @@ int rptr_hip_trace_device(rptr_hip_t *h, const RptrRenderRayQuery *device_querie
 /* RenderBackend::enable_ray_queries(max_queries, max_queries_per_pixel) (render_backend.h:101, render_vulkan.cpp:430-455): the library
  * owns a device buffer of max(max_queries, width x height x max_queries_per_pixel) RptrRenderRayQuery records and one of as many float4
  * results and returns their device addresses (≙ ray_query_buffer / ray_result_buffer; they stay valid until the next call that asks for
- * more, or rptr_hip_destroy). RenderBackend::render_ray_queries(num_queries, ...) = rptr_hip_render_ray_queries: traces the first
- * num_queries records of that buffer on the backend's stream. */
+ * more, or rptr_hip_destroy). RenderBackend::render_ray_queries(num_queries, ...) with the RQ_CLOSEST program = rptr_hip_render_ray_queries:
+ * traces the first num_queries records of that buffer on the backend's stream (with a path-tracing variant: rptr_hip_render_radiance_queries
+ * below). */
 int rptr_hip_enable_ray_queries(rptr_hip_t *h, int max_queries, int max_queries_per_pixel, void **out_device_queries, void **out_device_results);
 int rptr_hip_render_ray_queries(rptr_hip_t *h, int num_queries);
+/* ---- render_ray_queries with a path-tracing variant: radiance along the query rays
+ * (RenderBackend::render_ray_queries(num_queries, params, variant_idx) with a megakernel variant: pt_megakernel.glsl:276-302, 327-334
+ * ENABLE_RAYQUERIES, accumulate.glsl:31-42, render_vulkan.cpp:2961-3059). For query q and sample s < samples_per_query the path tracer's
+ * main_spp runs with its first ray replaced by the record's (origin, dir as given, t_min 0, t_max); out4[q] = (radiance.rgb, alpha) is what
+ * a frame's pixel is: bounces, next-event estimation, Russian roulette, alpha test, emitters, the sky on a miss (also when t_max ends the
+ * first ray before a surface; alpha is then 0). `variant` is an RPTR_VARIANT_* gpu program, `camera` supplies the image-plane axes the
+ * texture footprint is made from (pt_megakernel.glsl:341-352 uses the view's for queries too), RenderParams / SceneParams / lights are the
+ * handle's. Where the reference leaves things open this ABI pins them:
+ *   1. Random numbers: query q is pixel (q mod W, q div W) of a virtual image as wide as the handle's frame (W) and as tall as needed, so
+ *      the hashed pixel id px + py * W is q and table point sets get a 2-D pixel; the generator is opened as for that pixel and the
+ *      pixel-filter draw is made and dropped, so a query that IS a camera ray sees the stream the pixel's path sees. sample_index =
+ *      first_sample + s, frame_offset = the handle's current one (what the next rptr_hip_render without a reset would use), and the
+ *      view's frame_id of sample s = its sample_index (a one-sample frame at that point of the accumulation). The reference always
+ *      starts at sample 0; first_sample lets a host refine the same probes over several calls.
+ *   2. The result is the running mean in sample order, r += (new - r) / (sample_index + 1), a plain store for sample_index 0; for
+ *      first_sample > 0 the old mean is read from the result slot. (accumulate_query as written adds the new mean onto the old value
+ *      for sample_index > 0 and lets the samples of a dispatch race on the slot.) k calls of one sample == one call of k samples, bit
+ *      for bit; so is any split of the queries over calls with the same indices.
+ *   3. mode_or_data < 0 leaves the result slot untouched (as rptr_hip_trace; the megakernel does not read the field).
+ * A run waits for the frames in flight, writes no AOV image and leaves the accumulation, the frame buffer, frame_id / frame_offset, the
+ * reprojection history and rptr_hip_stats alone. n may exceed width x height. world_size > 1: RPTR_E_UNSUPPORTED (queries are not striped
+ * over the ranks). Before set_scene / initialize, unknown variant, samples_per_query < 1, first_sample < 0, NULL camera: RPTR_E_INVALID.
+ *
+ * rptr_hip_trace_radiance: host arrays, synchronous; out4 is read as well as written (slots of skipped queries, old means); out_stats (may
+ * be NULL) gets rays_closest / rays_shadow / hits_shaded of the run, spp = first_sample + samples_per_query, times 0.
+ * rptr_hip_trace_radiance_device: DEVICE buffers, asynchronously on `hip_stream` (NULL: the backend's stream), ordered as rptr_hip_trace_device.
+ * rptr_hip_render_radiance_queries: over the first num_queries records of the buffers of rptr_hip_enable_ray_queries, on the backend's stream
+ * (more than the budget: RPTR_E_INVALID). */
+int rptr_hip_trace_radiance(rptr_hip_t *h, const RptrRenderRayQuery *queries, int n, const RptrCamera *camera, int variant, int samples_per_query,
+                            int first_sample, float *out4, RptrStats *out_stats);
+int rptr_hip_trace_radiance_device(rptr_hip_t *h, const RptrRenderRayQuery *device_queries, int n, const RptrCamera *camera, int variant,
+                                   int samples_per_query, int first_sample, float *device_out4, void *hip_stream);
+int rptr_hip_render_radiance_queries(rptr_hip_t *h, int num_queries, const RptrCamera *camera, int variant, int samples_per_query, int first_sample);
 /* RenderBackendOptions::light_sampling_variant (rendering/mc/light_sampling.h:11-20, rendering/mc/nee.glsl:12-14): 0 =
  * LIGHT_SAMPLING_VARIANT_NONE disables next-event estimation towards the emissive triangles (every NEE sample goes to the sun; emitters
  * that a path HITS still contribute, at full weight), 1 = LIGHT_SAMPLING_VARIANT_RIS (the default: binned RIS). The image is that of

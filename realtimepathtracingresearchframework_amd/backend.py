@@ -70,6 +70,9 @@ def load_library(path=None):
     L.rptr_hip_trace_device.argtypes = [vp, vp, i32, vp, vp]
     L.rptr_hip_enable_ray_queries.argtypes = [vp, i32, i32, C.POINTER(vp), C.POINTER(vp)]
     L.rptr_hip_render_ray_queries.argtypes = [vp, i32]
+    L.rptr_hip_trace_radiance.argtypes = [vp, vp, i32, C.POINTER(abi.Camera), i32, i32, i32, vp, C.POINTER(abi.Stats)]
+    L.rptr_hip_trace_radiance_device.argtypes = [vp, vp, i32, C.POINTER(abi.Camera), i32, i32, i32, vp, vp]
+    L.rptr_hip_render_radiance_queries.argtypes = [vp, i32, C.POINTER(abi.Camera), i32, i32, i32]
     L.rptr_hip_set_light_sampling_variant.argtypes = [vp, i32]
     L.rptr_hip_set_freeze_frame.argtypes = [vp, i32]
     L.rptr_hip_set_option.argtypes = [vp, C.c_char_p, C.c_int64]
@@ -183,6 +186,7 @@ class RenderHip:
         self.rank, self.world_size = rank, world_size
         self._variant = abi.VARIANT_GLTF
         self._stats = None
+        self._query_stats = None
         self._fb_dims = (0, 0)
         self._spp_per_frame = 1
 
@@ -384,6 +388,39 @@ class RenderHip:
 
     def trace_device(self, device_queries, n, device_results, stream=None):
         self._check(self._L.rptr_hip_trace_device(self._h, C.c_void_p(device_queries), int(n), C.c_void_p(device_results), C.c_void_p(stream or 0)))
+
+    # ---- ray queries with a path-tracing variant: radiance along the query rays (include/rptr_hip.h rptr_hip_trace_radiance)
+    def render_radiance_queries(self, queries: np.ndarray, camera, variant=abi.VARIANT_GLTF, spp=1, first_sample=0, results: np.ndarray = None):
+        """queries: (n,8) float32 view of RenderRayQuery[n]; camera: abi.Camera (its image-plane axes size the texture footprint).
+        Returns (n,4) float32 = (radiance.rgb, alpha): the running mean over samples first_sample .. first_sample + spp - 1, folded into
+        `results` (read for first_sample > 0 and for the slots of queries with mode_or_data < 0, which stay as they are). The frame in
+        progress is left alone; the run's ray counts: radiance_query_stats()."""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, 8)
+        if results is None:
+            results = np.zeros((len(q), 4), dtype=np.float32)
+        if results.dtype != np.float32 or not results.flags["C_CONTIGUOUS"] or results.size < 4 * len(q):
+            raise ValueError("render_radiance_queries: results must be a C-contiguous float32 array of n x 4")
+        self._push_params()
+        st = abi.Stats()
+        self._check(self._L.rptr_hip_trace_radiance(self._h, q.ctypes.data_as(C.c_void_p), len(q), C.byref(camera), int(variant), int(spp), int(first_sample),
+                                                    results.ctypes.data_as(C.c_void_p), C.byref(st)))
+        self._query_stats = st
+        return results
+
+    def radiance_query_stats(self):
+        """RenderStats of the last render_radiance_queries (rays_closest / rays_shadow / hits_shaded; stats() stays the last frame's)"""
+        return RenderStats(self._query_stats)
+
+    def render_radiance_queries_device(self, num_queries, camera, variant=abi.VARIANT_GLTF, spp=1, first_sample=0, device_queries=None, device_results=None,
+                                       stream=None):
+        """the same over DEVICE buffers, asynchronously: the backend's own (enable_ray_queries_device; on the backend's stream) unless
+        device_queries / device_results name others (then on `stream`, None = the backend's)"""
+        self._push_params()
+        if device_queries is None and device_results is None:
+            self._check(self._L.rptr_hip_render_radiance_queries(self._h, int(num_queries), C.byref(camera), int(variant), int(spp), int(first_sample)))
+        else:
+            self._check(self._L.rptr_hip_trace_radiance_device(self._h, C.c_void_p(device_queries), int(num_queries), C.byref(camera), int(variant), int(spp),
+                                                               int(first_sample), C.c_void_p(device_results), C.c_void_p(stream or 0)))
 
     def set_light_sampling_variant(self, variant):
         """RenderBackendOptions::light_sampling_variant: 0 = NONE (no NEE towards emissive triangles), 1 = RIS (default)"""

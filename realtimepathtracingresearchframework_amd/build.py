@@ -17,8 +17,9 @@ UNITS = [
     ("bvh_build", "bvh_build.cpp", []),
     ("k_extend", "k_extend.hip", []),
 ] + [("k_shade_v%d%s" % (v, "_fast" if m else ""), "k_shade.hip", ["-DRP_INST_VARIANT=%d" % v, "-DRP_FAST_MATH=%d" % m]) for m in range(2) for v in range(3)] \
+  + [("k_shade_query_v%d%s" % (v, "_fast" if m else ""), "k_shade_query.hip", ["-DRP_INST_VARIANT=%d" % v, "-DRP_FAST_MATH=%d" % m]) for m in range(2) for v in range(3)] \
   + [("k_tail_v%d%s" % (v, "_fast" if m else ""), "k_tail.hip", ["-DRP_INST_VARIANT=%d" % v, "-DRP_FAST_MATH=%d" % m]) for m in range(2) for v in range(3)]
-# (k_shade / k_tail: once per gpu-program variant and per build of the shading arithmetic -- IEEE division / square root, the oracle's bits,
+# (k_shade / k_shade_query / k_tail: once per gpu-program variant and per build of the shading arithmetic -- IEEE division / square root, the oracle's bits,
 # or the hardware's 1-ulp reciprocal / square root: option "fast_math", csrc/dmath.h)
 SOURCES = sorted({u[1] for u in UNITS})
 HEADERS = ["kernels.h", "kernels_misc.h", "realtime_resolve.h", "launch.h", "host_state.h", "host_bvh.inl", "host_scene.inl", "host_frame.inl", "host_access.inl", "host_comm.h", "lbvh.h", "ploc.h", "dtraverse.h", "bvh4.h", "dshade.h", "dmath.h", "bvh_build.h",

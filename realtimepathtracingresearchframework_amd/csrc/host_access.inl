@@ -1,5 +1,5 @@
 // host_access.inl -- everything else a host reaches through the handle: BVH policy, freeze frame, point sets, stage timing, the option calls, frame buffer / tile /
-// AOV read-backs, ray queries (rptr_hip_trace*), the exported tree
+// AOV read-backs, ray queries (rptr_hip_trace*: closest hits, and path-traced radiance), the exported tree
 // Part of the ONE translation unit rptr_hip.hip (included there, in this order: host_state.h, host_bvh.inl, host_scene.inl,
 // host_frame.inl, host_access.inl, host_comm.h): the host runtime split along its seams; no symbol changed.
 int rptr_hip_set_bvh_policy(rptr_hip_t *h, int force_bvh_rebuild, int rebuild_triangle_budget) {
@@ -342,6 +342,78 @@ int rptr_hip_render_ray_queries(rptr_hip_t *h, int num_queries) {
     if (!h || num_queries < 0) return fail(h, RPTR_E_INVALID, "bad argument");
     if ((size_t)num_queries > h->rq_capacity) return fail(h, RPTR_E_INVALID, "%d ray queries exceed the budget of %zu (rptr_hip_enable_ray_queries)", num_queries, h->rq_capacity);
     return rptr_hip_trace_device(h, h->rq_queries, num_queries, reinterpret_cast<float *>(h->rq_results), nullptr);
+}
+
+// ---- radiance queries: the path-tracing variants of RenderBackend::render_ray_queries (host_frame.inl radiance_queries_on)
+int rptr_hip_trace_radiance(rptr_hip_t *h, const RptrRenderRayQuery *queries, int n, const RptrCamera *camera, int variant, int samples_per_query, int first_sample,
+                            float *out4, RptrStats *out_stats) {
+    int rc = check_radiance_arguments(h, queries, n, camera, variant, samples_per_query, first_sample, out4);
+    if (rc) return rc;
+    if ((rc = drain(h)) || (rc = ensure_master_tree(h))) return rc; // the run borrows context 0
+    if (out_stats) memset(out_stats, 0, sizeof(*out_stats));
+    if (n == 0) return RPTR_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    RptrRenderRayQuery *dq = nullptr;
+    float4 *dr = nullptr;
+    if (hipMalloc((void **)&dq, (size_t)n * sizeof(RptrRenderRayQuery)) != hipSuccess || hipMalloc((void **)&dr, (size_t)n * sizeof(float4)) != hipSuccess) {
+        (void)hipFree(dq);
+        return fail(h, RPTR_E_NOMEM, "hipMalloc failed");
+    }
+    RpCounters tot;
+    memset(&tot, 0, sizeof(tot));
+    do {
+        // (the results go up whatever first_sample is: slots of skipped queries keep what the caller put there)
+        if (hipMemcpyAsync(dq, queries, (size_t)n * sizeof(RptrRenderRayQuery), hipMemcpyHostToDevice, h->stream) != hipSuccess ||
+            hipMemcpyAsync(dr, out4, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, h->stream) != hipSuccess) {
+            rc = fail(h, RPTR_E_HIP, "upload failed");
+            break;
+        }
+        if ((rc = radiance_queries_on(h, dq, n, camera, variant, samples_per_query, first_sample, dr, h->stream, &tot))) break;
+        if (hipMemcpyAsync(out4, dr, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost, h->stream) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess ||
+            hipGetLastError() != hipSuccess) {
+            rc = fail(h, RPTR_E_HIP, "radiance query kernels failed");
+            break;
+        }
+    } while (0);
+    if (rc) (void)hipStreamSynchronize(h->stream); // nothing of the run may still use the buffers freed below
+    (void)hipFree(dq);
+    (void)hipFree(dr);
+    if (!rc && out_stats) {
+        out_stats->rays_closest = tot.rays_closest;
+        out_stats->rays_shadow = tot.rays_shadow;
+        out_stats->hits_shaded = tot.hits_shaded;
+        out_stats->spp = first_sample + samples_per_query;
+        out_stats->device_bytes_allocated = h->bytes_allocated;
+    }
+    return rc;
+}
+
+int rptr_hip_trace_radiance_device(rptr_hip_t *h, const RptrRenderRayQuery *device_queries, int n, const RptrCamera *camera, int variant, int samples_per_query,
+                                   int first_sample, float *device_out4, void *hip_stream) {
+    int rc = check_radiance_arguments(h, device_queries, n, camera, variant, samples_per_query, first_sample, device_out4);
+    if (rc) return rc;
+    if ((rc = drain(h)) || (rc = ensure_master_tree(h))) return rc; // the run borrows context 0
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : h->stream;
+    float4 *dr = reinterpret_cast<float4 *>(device_out4);
+    if (st != h->stream) { // the caller's stream sees the scene uploads / refits queued on the backend's, and later frames see the queries
+        hipEvent_t e;
+        HIP_TRY(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        (void)hipEventRecord(e, h->stream);
+        (void)hipStreamWaitEvent(st, e, 0);
+        rc = radiance_queries_on(h, device_queries, n, camera, variant, samples_per_query, first_sample, dr, st, nullptr);
+        (void)hipEventRecord(e, st);
+        (void)hipStreamWaitEvent(h->stream, e, 0);
+        (void)hipEventDestroy(e);
+        return rc;
+    }
+    return radiance_queries_on(h, device_queries, n, camera, variant, samples_per_query, first_sample, dr, st, nullptr);
+}
+
+int rptr_hip_render_radiance_queries(rptr_hip_t *h, int num_queries, const RptrCamera *camera, int variant, int samples_per_query, int first_sample) {
+    if (!h || num_queries < 0) return fail(h, RPTR_E_INVALID, "bad argument");
+    if ((size_t)num_queries > h->rq_capacity) return fail(h, RPTR_E_INVALID, "%d ray queries exceed the budget of %zu (rptr_hip_enable_ray_queries)", num_queries, h->rq_capacity);
+    return rptr_hip_trace_radiance_device(h, h->rq_queries, num_queries, camera, variant, samples_per_query, first_sample, reinterpret_cast<float *>(h->rq_results), nullptr);
 }
 
 int rptr_hip_set_light_sampling_variant(rptr_hip_t *h, int variant) {

@@ -71,12 +71,36 @@ static inline void pick(bool v, F &&f) {
         f(std::false_type());
 }
 
+// Which instantiations of the path stages a launch sequence runs, and where it hands over to the tail kernel: ONE place for frames
+// (render_batch_impl) and radiance-query runs (radiance_queries_on), whose later bounces must be the frame's kernels to give the frame's bits.
+struct PathKernelFlags {
+    bool lights;    // light-sampling code: without emissive triangles and with all NEE probability on the sun that branch is dead code
+    bool table_rng; // the general instantiations: a table point set, or a screen jitter (raster TAA) -- the shipped path carries neither
+    bool single;    // the top level holds one instance record
+    bool full;      // the tail kernel's one instantiation for textured and alpha-tested scenes
+    bool fast_math;
+};
+static PathKernelFlags path_kernel_flags(const rptr_hip *h, const RpScene &scene, const RpFrame &f) {
+    PathKernelFlags k;
+    k.lights = (h->num_lights > 0 && !h->lights_disabled) || f.sp.sun_radiance[3] < 1.0f;
+    k.table_rng = h->rng_variant != RPTR_RNG_VARIANT_UNIFORM || h->params.enable_raster_taa != 0;
+    k.single = scene.single_instance != 0;
+    k.full = h->uses_textures || h->uses_alpha;
+    k.fast_math = h->opt.v[OPT_FAST_MATH] != 0;
+    return k;
+}
+// the bounce at which the tail kernel takes over (kernels.h rp_k_tail; max_path_depth: never); counting keeps the stand-alone kernels
+static int tail_hand_over(const rptr_hip *h, bool count_traversal) {
+    const int depth = h->params.max_path_depth;
+    if (h->tail_mode == 0 || count_traversal) return depth;
+    return std::max(1, std::min(depth, h->tail_mode > 0 ? h->tail_mode : h->tail_adaptive));
+}
+
 static void launch_shade(rptr_hip *h, FrameCtx &c, int variant, const RpScene &scene, const RpFrame &f, const uint32_t *order, int bounce, int out) {
-    // without emissive triangles and with all NEE probability on the sun the light-sampling branch is dead code
-    const bool lights = (h->num_lights > 0 && !h->lights_disabled) || f.sp.sun_radiance[3] < 1.0f;
+    const PathKernelFlags k = path_kernel_flags(h, scene, f);
     const RpLaunch l = {(unsigned)grid_for(h, h->path_capacity), c.stream, nullptr, nullptr};
-    rp_launch_shade(variant, h->opt.v[OPT_FAST_MATH] != 0, l, bounce == 0, lights, h->uses_textures,
-                    f.rng_variant != RPTR_RNG_VARIANT_UNIFORM || f.rp.enable_raster_taa != 0, scene, f, c.ps, c.sq, order,
+    rp_launch_shade(variant, k.fast_math, l, bounce == 0, k.lights, h->uses_textures,
+                    k.table_rng, scene, f, c.ps, c.sq, order,
                     (const uint32_t *)&c.counters->bounce[bounce].queue_count, c.queue[out], &c.counters->bounce[bounce + 1].queue_count,
                     &c.counters->bounce[bounce].shadow_count, c.counters);
 }
@@ -412,6 +436,7 @@ static int render_batch_impl(rptr_hip_t *h, const RptrCamera *camera, bool per_f
         return l;
     };
     // the general instantiation of the path stages: a table point set, or a screen jitter (raster TAA) -- the shipped path carries neither
+    // (path_kernel_flags: f.rng_variant is set below from the same h->rng_variant)
     const bool table_rng_later = h->rng_variant != RPTR_RNG_VARIANT_UNIFORM || h->params.enable_raster_taa != 0;
     const bool table_rng = table_rng_later;
     // the frames of this handle that will share the GPU with this one: those still in flight on the device (up to the most that can run
@@ -483,18 +508,15 @@ static int render_batch_impl(rptr_hip_t *h, const RptrCamera *camera, bool per_f
             const uint32_t *first_ids = nullptr;
             HIP_TRY(h, hipMemsetD32Async((hipDeviceptr_t)&c.counters->bounce[0].queue_count, (int)first_count, 1, c.stream));
             // the late bounces in one launch (kernels.h rp_k_tail); counting keeps the stand-alone kernels
-            int tail_from = h->params.max_path_depth;
-            if (h->tail_mode != 0 && !count_traversal)
-                tail_from = std::max(1, std::min(h->params.max_path_depth, h->tail_mode > 0 ? h->tail_mode : h->tail_adaptive));
+            const int tail_from = tail_hand_over(h, count_traversal != 0);
             c.tail_from = tail_from;
             for (int b = 0; b < h->params.max_path_depth; ++b) {
                 const int in = b & 1, out = in ^ 1;
                 RpBounceCounters *bc = &c.counters->bounce[b];
                 if (b == tail_from) {
                     if (side && b > 0) HIP_TRY(h, hipStreamWaitEvent(c.stream, c.ev_side, 0)); // join: connect(b-1) on the side stream
-                    const bool lights = (h->num_lights > 0 && !h->lights_disabled) || f.sp.sun_radiance[3] < 1.0f;
-                    const bool full = h->uses_textures || h->uses_alpha; // one instantiation serves textured and alpha-tested scenes
-                    rp_launch_tail(variant, h->opt.v[OPT_FAST_MATH] != 0, timed_launch(c.stream, 3, (unsigned)h->tail_blocks), lights, full, single, table_rng_later, scn.dscene, f, c.ps, c.sq,
+                    const PathKernelFlags k = path_kernel_flags(h, scn.dscene, f);
+                    rp_launch_tail(variant, k.fast_math, timed_launch(c.stream, 3, (unsigned)h->tail_blocks), k.lights, k.full, k.single, k.table_rng, scn.dscene, f, c.ps, c.sq,
                                    (const uint32_t *)c.queue[in], c.counters, b, c.gstack);
                     break;
                 }
@@ -603,6 +625,117 @@ static int render_batch_impl(rptr_hip_t *h, const RptrCamera *camera, bool per_f
     h->next_ticket += (uint64_t)n_frames;
     if (out_tickets)
         for (int k = 0; k < n_frames; ++k) out_tickets[k] = c.ticket + (uint64_t)k;
+    return RPTR_OK;
+}
+} // extern "C++"
+
+extern "C++" {
+// ---- radiance queries (kernels.h RpQueries): the path pipeline on the rays of a query buffer instead of the camera's
+// (RenderBackend::render_ray_queries with a path-tracing variant: render_vulkan.cpp:1867-1876, 2961-3059)
+static int check_radiance_arguments(rptr_hip_t *h, const void *queries, int n, const RptrCamera *camera, int variant, int samples_per_query, int first_sample,
+                                    const void *out4) {
+    if (!h) return fail(nullptr, RPTR_E_INVALID, "NULL handle");
+    if (!camera) return fail(h, RPTR_E_INVALID, "radiance queries: NULL camera (its image-plane axes size the texture footprint)");
+    if (n < 0) return fail(h, RPTR_E_INVALID, "radiance queries: n must be >= 0");
+    if (n > 0 && (!queries || !out4)) return fail(h, RPTR_E_INVALID, "radiance queries: NULL query or result buffer");
+    if (!h->have_scene) return fail(h, RPTR_E_INVALID, "radiance queries before set_scene");
+    if (h->width == 0 || h->ctx.empty() || !h->ctx[0].gstack) return fail(h, RPTR_E_INVALID, "radiance queries before initialize");
+    if (variant != RPTR_VARIANT_GLTF && variant != RPTR_VARIANT_SIMPLE && variant != RPTR_VARIANT_GLTF_TRANSMISSION)
+        return fail(h, RPTR_E_INVALID, "unknown variant %d", variant);
+    if (samples_per_query < 1) return fail(h, RPTR_E_INVALID, "samples_per_query must be >= 1");
+    if (first_sample < 0) return fail(h, RPTR_E_INVALID, "first_sample must be >= 0");
+    if ((long long)first_sample + samples_per_query > 0x7fffffffll) return fail(h, RPTR_E_INVALID, "first_sample + samples_per_query overflows");
+    if (h->world > 1) return fail(h, RPTR_E_UNSUPPORTED, "radiance queries need world_size 1: queries are not striped over the ranks");
+    return RPTR_OK;
+}
+// Queues the run on `st` for DEVICE buffers. The caller has drained the frames in flight: the run borrows context 0's path state, queues,
+// counters and stack scratch, and leaves everything a frame owns alone (accumulation and frame buffers, AOV images, frame_id, frame_offset,
+// the previous view, the last frame's statistics and hand-over bounce).
+// The virtual image (width = the frame's, query q = pixel (q mod W, q div W)) is walked in slices of at most the frame's rows, the samples
+// of a slice in batches of at most the context's sample slots; a path's result is a function of its query and sample index alone, so
+// neither shows in the results. Sample s runs as a one-sample frame at that point of the accumulation would: sample_index = frame_id =
+// first_sample + s (frame_id seeds the alpha test of shadow rays and the blue-noise point set) -- one call of k samples and k calls of one
+// give the same bits.
+// totals != NULL: the ray counters of every batch are added to it (the host waits for each batch); NULL: nothing is waited for.
+static int radiance_queries_on(rptr_hip_t *h, const RptrRenderRayQuery *dq, int n, const RptrCamera *camera, int variant, int spp, int first_sample, float4 *dr,
+                               hipStream_t st, RpCounters *totals) {
+    if (n == 0) return RPTR_OK;
+    FrameCtx &c = h->ctx[0];
+    const SceneCopy &scn = h->master;
+    RpFrame f;
+    {
+        const RptrCamera keep = h->prev_camera; // (fill_frame_constants notes the view for the next frame's motion vectors: not a query run's)
+        const bool have = h->have_prev_camera;
+        fill_frame_constants(h, c, camera, false, variant, 1, 1, 0, f);
+        h->prev_camera = keep;
+        h->have_prev_camera = have;
+    }
+    f.aov_albedo_roughness = f.aov_normal_depth = f.aov_motion_jitter = nullptr;
+    f.alpha_test = h->uses_alpha ? 1 : 0;
+    f.rng_variant = h->rng_variant;
+    f.rng_table = h->rng_table;
+    const int slice_rows = h->local_rows; // (world_size 1: the frame's height)
+    f.world = 1;
+    f.stripe_rows = slice_rows;
+    f.div_stripe_rows = rp_make_div((uint32_t)slice_rows);
+    f.frame_spp = 1;
+    f.div_frame_spp = rp_make_div(1u);
+    f.batch_reset = 0;
+    const RpQueries rq = {dq, (uint32_t)n, 0u};
+    const PathKernelFlags k = path_kernel_flags(h, scn.dscene, f);
+    const bool table_rng = k.table_rng, single = k.single, lights = k.lights, fast_math = k.fast_math;
+    const int depth = h->params.max_path_depth;
+    // (nothing else of this handle is on the GPU: the grids of a frame alone)
+    const unsigned blocks_first = (unsigned)traversal_grid(h, 0, 1), blocks_later = (unsigned)traversal_grid(h, 1, 1);
+    const unsigned blocks_connect = (unsigned)traversal_grid(h, single ? 3 : 2, 1);
+    const unsigned blocks_shade = (unsigned)grid_for(h, h->path_capacity);
+    const int tail_from = tail_hand_over(h, false);
+    const long long total_rows = ((long long)n + h->width - 1) / h->width;
+    for (long long row0 = 0; row0 < total_rows; row0 += slice_rows) {
+        f.rank = (int)(row0 / slice_rows);
+        f.local_rows = (int)std::min<long long>(slice_rows, total_rows - row0);
+        for (int done = 0; done < spp;) {
+            const int batch = std::min(spp - done, h->max_batch_spp);
+            f.sample_base = (uint32_t)(first_sample + done);
+            f.frame_id = f.sample_base;
+            f.batch_spp = batch;
+            f.batch_frames = batch; // one "frame" per sample slot (dshade.h rp_slot_frame): frame_id = sample_index
+            HIP_TRY(h, hipMemsetAsync(c.counters, 0, sizeof(RpCounters), st));
+            const uint32_t first_count = (uint32_t)((size_t)batch * h->npix_padded); // the identity queue over the batch's path ids
+            HIP_TRY(h, hipMemsetD32Async((hipDeviceptr_t)&c.counters->bounce[0].queue_count, (int)first_count, 1, st));
+            const RpLaunch l_first = {blocks_first, st, nullptr, nullptr}, l_later = {blocks_later, st, nullptr, nullptr};
+            const RpLaunch l_connect = {blocks_connect, st, nullptr, nullptr}, l_shade = {blocks_shade, st, nullptr, nullptr};
+            for (int b = 0; b < depth; ++b) {
+                const int in = b & 1, out = in ^ 1;
+                RpBounceCounters *bc = &c.counters->bounce[b];
+                if (b == tail_from) {
+                    const bool full = k.full;
+                    const RpLaunch l_tail = {(unsigned)h->tail_blocks, st, nullptr, nullptr};
+                    rp_launch_tail(variant, fast_math, l_tail, lights, full, single, table_rng, scn.dscene, f, c.ps, c.sq, (const uint32_t *)c.queue[in], c.counters, b,
+                                   c.gstack);
+                    break;
+                }
+                if (b == 0) {
+                    rp_launch_extend_query(l_first, h->uses_alpha, single, table_rng, scn.dscene, f, c.ps, rq, bc, c.counters, c.gstack);
+                    rp_launch_shade_query(variant, fast_math, l_shade, lights, h->uses_textures, table_rng, scn.dscene, f, c.ps, c.sq,
+                                          (const uint32_t *)&bc->queue_count, c.queue[out], &c.counters->bounce[1].queue_count, &bc->shadow_count, c.counters);
+                } else {
+                    rp_launch_extend(l_later, false, false, h->uses_alpha, single, table_rng, scn.dscene, f, c.ps, (const uint32_t *)c.queue[in], bc, c.counters, c.gstack);
+                    rp_launch_shade(variant, fast_math, l_shade, false, lights, h->uses_textures, table_rng, scn.dscene, f, c.ps, c.sq, (const uint32_t *)c.queue[in],
+                                    (const uint32_t *)&bc->queue_count, c.queue[out], &c.counters->bounce[b + 1].queue_count, &bc->shadow_count, c.counters);
+                }
+                rp_launch_connect(l_connect, false, h->uses_alpha, single, scn.dscene, f, c.ps, c.sq, bc, c.counters, c.gstack);
+            }
+            hipLaunchKernelGGL(rp_k_resolve_queries, dim3(grid_for(h, (size_t)h->width * (size_t)f.local_rows)), dim3(256), 0, st, f, c.ps, rq, dr);
+            HIP_TRY(h, hipGetLastError());
+            if (totals) {
+                HIP_TRY(h, hipMemcpyAsync(c.host_counters, c.counters, sizeof(RpCounters), hipMemcpyDeviceToHost, st));
+                HIP_TRY(h, hipStreamSynchronize(st));
+                add_counters(*totals, *c.host_counters);
+            }
+            done += batch;
+        }
+    }
     return RPTR_OK;
 }
 } // extern "C++"

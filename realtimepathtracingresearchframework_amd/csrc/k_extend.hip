@@ -1,4 +1,4 @@
-// k_extend.hip -- instantiations of the traversal stages (kernels.h rp_k_extend, rp_k_connect) and their launchers (launch.h)
+// k_extend.hip -- instantiations of the traversal stages (kernels.h rp_k_extend, rp_k_extend_query, rp_k_connect) and their launchers (launch.h)
 #include "launch.h"
 
 void rp_launch_extend(const RpLaunch &l, bool count, bool first, bool alpha, bool single, bool table, const RpScene &sc, const RpFrame &f, const RpPathState &ps,
@@ -36,6 +36,17 @@ void rp_launch_connect(const RpLaunch &l, bool count, bool alpha, bool single, c
         rp_pick(alpha, [&](auto A) {
             rp_pick(single, [&](auto S) {
                 rp_launch_kernel(l, rp_k_connect<decltype(C)::value, decltype(A)::value, decltype(S)::value>, RP_TRAVERSE_BLOCK, sc, f, ps, sq, bc, ctr, gstack);
+            });
+        });
+    });
+}
+
+void rp_launch_extend_query(const RpLaunch &l, bool alpha, bool single, bool table, const RpScene &sc, const RpFrame &f, const RpPathState &ps, const RpQueries &rq,
+                            RpBounceCounters *bc, RpCounters *ctr, int *gstack) {
+    rp_pick(alpha, [&](auto A) {
+        rp_pick(single, [&](auto S) {
+            rp_pick(table, [&](auto T) {
+                rp_launch_kernel(l, rp_k_extend_query<decltype(A)::value, decltype(S)::value, decltype(T)::value>, RP_TRAVERSE_BLOCK, sc, f, ps, rq, bc, ctr, gstack);
             });
         });
     });

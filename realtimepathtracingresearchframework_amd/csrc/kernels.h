@@ -167,23 +167,76 @@ RP_DEV bool rp_primary_ray(const RpFrame &f, uint32_t p, RpRng &rng, V3 &dir, V3
 // hit_ids.x of a slot of the first queue that names no pixel sample (tile padding): neither a hit nor a miss
 #define RP_HIT_PADDING (-2)
 
+// ------------------------------------------------------------------ radiance queries (pt_megakernel.glsl:276-302, 327-334: ENABLE_RAYQUERIES)
+// A query run is the path pipeline with another front: the first ray of path p comes from a RenderRayQuery record instead of the camera.
+// Query q is pixel (q mod W, q div W) of a VIRTUAL image as wide as the handle's frame and as tall as the run needs (the reference
+// dispatches into a square and numbers queries by work-group, setup_pixel_assignment.glsl:18-22: nothing a host could rely on), and the host
+// walks that image in slices of at most the handle's rows: slice k is what "rank" k of a striped frame with stripes of slice height owns
+// (f.rank = k, f.world = 1, f.stripe_rows = slice height: rp_local_row_to_global is then k * slice height + local row), so every later
+// stage -- generators of table point sets, the alpha generators -- finds the virtual pixel of a path id the way it finds a frame's pixel.
+// f.height stays the handle's (the texture footprint divides by it, :341-352); f.local_rows are the rows of this slice.
+struct RpQueries {
+    const RptrRenderRayQuery *records; // origin.xyz, mode_or_data | dir.xyz, t_max
+    uint32_t n;
+    uint32_t _pad;
+};
+// the query of path p; false: the slot names none (tile padding, or behind the last query)
+RP_DEV bool rp_query_of_path(const RpFrame &f, const RpQueries &rq, uint32_t p, uint32_t &q, uint32_t &sslot, int &lx, int &gy) {
+    sslot = rp_div(p, f.div_npix_padded);
+    int ly = 0;
+    lx = gy = 0;
+    q = 0u;
+    if (!rp_slot_to_local(f, p - sslot * uint32_t(f.npix_padded), lx, ly)) return false;
+    gy = rp_local_row_to_global(f, ly);
+    q = uint32_t(gy) * uint32_t(f.width) + uint32_t(lx);
+    return q < rq.n;
+}
+
 // ------------------------------------------------------------------ extend (closest hit), persistent waves
 // FIRST: bounce 0, the rays are the camera rays (computed, not loaded)
+// QUERY (with FIRST): ... or the rays of a radiance-query run, loaded from its records (two 16-byte loads). The generator is opened as for
+// the pixel and the pixel-filter draw is made and dropped (pt_megakernel.glsl:314-317), origin, direction (as given: :331 does not normalise) and
+// generator state go to ray_o[p] / ray_d[p] for the first shade -- with table point sets too. Records with mode_or_data < 0 are skipped like tile padding.
 // ALPHA: the scene has alpha-tested materials. The test of a candidate may draw from the path's generator
 // (pt_megakernel.glsl:354-358), so the lane carries it through the traversal and hands it back in the path state.
 // SINGLE: the scene has one instance record; queries start inside it (dtraverse.h).
 // LOCAL: `queue` / `cursor` are a block-local list and its cursor in LDS (rp_k_tail).
 // EXTLDS (rp_k_tail): the stacks' LDS belongs to the caller.
-template <bool COUNT, bool FIRST, bool ALPHA, bool SINGLE, bool LOCAL, bool TABLE, int LDSTOP = 0, bool EXTLDS = false>
+template <bool COUNT, bool FIRST, bool ALPHA, bool SINGLE, bool LOCAL, bool TABLE, int LDSTOP = 0, bool EXTLDS = false, bool QUERY = false>
 RP_DEV void rp_extend_body(const RpScene &sc, const RpFrame &f, const RpPathState &ps, const uint32_t *queue, uint32_t n, uint32_t *cursor, RpCounters *ctr,
-                           int *gstack, int *ext_stack = nullptr) {
+                           int *gstack, int *ext_stack = nullptr, const RpQueries rq = RpQueries{nullptr, 0u, 0u}) {
+    static_assert(!QUERY || FIRST, "query rays are first rays");
     uint32_t n_nodes = 0, n_tris = 0;
     uint32_t lane_rng = 0, lane_rng_in = 0; // ALPHA only
     uint32_t lane_p = 0; // the path whose ray this lane traces
     auto load = [&](uint32_t i, V3 &ro, V3 &rd, float &tmin, float &tmax) -> bool {
         const uint32_t p = (FIRST && !queue) ? i : queue[i]; // FIRST: the first queue is the identity (NULL) unless the caller stored it
         lane_p = p;
-        if (FIRST) {
+        if (QUERY) {
+            uint32_t q, sslot;
+            int lx, gy;
+            bool ok = rp_query_of_path(f, rq, p, q, sslot, lx, gy);
+            float4 q0 = make_float4(0.f, 0.f, 0.f, 0.f), q1 = q0;
+            if (ok) {
+                const float4 *qp = reinterpret_cast<const float4 *>(rq.records + q);
+                q0 = qp[0];
+                q1 = qp[1];
+                ok = __float_as_int(q0.w) >= 0; // mode_or_data < 0: the result slot stays untouched
+            }
+            if (!ok) {
+                ps.hit_ids[p] = make_int2(RP_HIT_PADDING, -1);
+                return false;
+            }
+            RpRng rng = rp_rng_open<TABLE>(f, rp_slot_frame(f, sslot), uint32_t(lx), uint32_t(gy));
+            if (!TABLE || f.rp.enable_raster_taa == 0) (void)rp_draw2<TABLE>(f, rng, 0u /* DIM_PIXEL_X */);
+            ro = xyz(q0);
+            rd = xyz(q1);
+            ps.ray_o[p] = f4(ro, 0.0f); // origin, path length 0: what the first shade starts from (a frame's first shade takes the camera's)
+            ps.ray_d[p] = f4(rd, __uint_as_float(rng.s));
+            tmin = 0.0f;
+            tmax = q1.w;
+            if (ALPHA) lane_rng = (!TABLE || f.rng_variant == RPTR_RNG_VARIANT_UNIFORM) ? rng.s : rp_alpha_seed(f, p);
+        } else if (FIRST) {
             RpRng rng;
             rd = v3(0.0f, 0.0f, 1.0f);
             if (!rp_primary_ray<TABLE>(f, p, rng, rd, ro)) { // tile padding: no such pixel sample (the first shade's regrouping pass skips it)
@@ -236,6 +289,17 @@ template <bool COUNT, bool FIRST, bool ALPHA, bool SINGLE, bool TABLE>
 __global__ __launch_bounds__(RP_TRAVERSE_BLOCK, ((SINGLE && !ALPHA) ? RP_SINGLE_EXTEND_WAVES : (FIRST ? RP_TRAVERSE_WAVES : RP_EXTEND_LATER_WAVES))) void rp_k_extend(RpScene sc, RpFrame f, RpPathState ps, const uint32_t *queue, RpBounceCounters *bc, RpCounters *ctr,
                                                int *gstack) {
     rp_extend_body<COUNT, FIRST, ALPHA, SINGLE, false, TABLE>(sc, f, ps, queue, bc->queue_count, &bc->cursor_extend, ctr, gstack);
+}
+// the first extend of a radiance-query run: the bounds of the first extend of a frame, except with the alpha test -- there the lane's generator
+// rides through the walk and at the 80 VGPRs of six waves per SIMD the kernel spills 2-7 words to scratch (rp_k_extend<.., FIRST, ALPHA, ..>
+// does too: 0-24 bytes); compiled for five (96 VGPRs) it needs none. The grid stays the frame's (the kernel pulls its work from a cursor:
+// blocks that are not resident at once take what is left when they start).
+#ifndef RP_QUERY_ALPHA_EXTEND_WAVES
+#define RP_QUERY_ALPHA_EXTEND_WAVES 5
+#endif
+template <bool ALPHA, bool SINGLE, bool TABLE>
+__global__ __launch_bounds__(RP_TRAVERSE_BLOCK, (ALPHA ? RP_QUERY_ALPHA_EXTEND_WAVES : (SINGLE ? RP_SINGLE_EXTEND_WAVES : RP_TRAVERSE_WAVES))) void rp_k_extend_query(RpScene sc, RpFrame f, RpPathState ps, RpQueries rq, RpBounceCounters *bc, RpCounters *ctr, int *gstack) {
+    rp_extend_body<false, true, ALPHA, SINGLE, false, TABLE, 0, false, true>(sc, f, ps, nullptr, bc->queue_count, &bc->cursor_extend, ctr, gstack, nullptr, rq);
 }
 // the same with the top of the tree staged in LDS (dtraverse.h LDSTOP; RPTR_LDS_TOP=1): plain scenes only (one instance record, no alpha
 // test, the LCG point set)
@@ -354,10 +418,14 @@ struct RpShadeLds {
 #define RP_SHADE_RIS_REQ_FLOATS ((256 / 64) * 64 * 8)
 #define RP_SHADE_RIS_CONTRIB_FLOATS ((256 / 64) * 64 * RPTR_BINNED_LIGHTS_BIN_MAX_SIZE)
 // EXTLDS: as for rp_extend_body
-template <int VARIANT, bool FIRST, bool LIGHTS, bool TEX, bool LOCAL, bool TABLE, bool EXTLDS = false>
+// QUERY (with FIRST): the first vertex of a radiance-query run -- origin, direction and generator state as rp_k_extend_query left them in
+// ray_o[p] / ray_d[p] (the kernel needs no query buffer), the texture footprint from the frame constants' camera (pt_megakernel.glsl:341-352 does the same for
+// queries); the AOV stores are compiled out (a query run writes no image)
+template <int VARIANT, bool FIRST, bool LIGHTS, bool TEX, bool LOCAL, bool TABLE, bool EXTLDS = false, bool QUERY = false>
 RP_DEV void rp_shade_body(const RpScene &sc, const RpFrame &f, const RpPathState &ps, const RpShadowRays &sq, const uint32_t *order, const uint32_t n,
                           uint32_t *next_queue, uint32_t *next_count, uint32_t *shadow_count, RpCounters *ctr, uint32_t *&local_next, uint32_t &n_next,
                           uint32_t *&local_shadow, uint32_t &n_shadow, const RpShadeLds *ext = nullptr) {
+    static_assert(!QUERY || FIRST, "query rays are first rays");
     __shared__ uint32_t s_next_own[EXTLDS ? 1 : RP_CHUNK], s_shadow_own[EXTLDS ? 1 : RP_CHUNK];
     __shared__ uint32_t s_nn, s_ns, s_base;
     __shared__ uint32_t s_stat[3];
@@ -478,7 +546,17 @@ RP_DEV void rp_shade_body(const RpScene &sc, const RpFrame &f, const RpPathState
                 p = il < chunk_hits ? s_list[il] : s_list[RP_CHUNK - 1 - (il - chunk_hits)];
                 // bounce 0: the camera ray -- as the first extend stored it (direction, generator state; the origin is the frame's camera), or made
                 // again (table point sets). Ids of tile padding were dropped by the regrouping pass.
-                if (FIRST && RP_FIRST_RAY_STORED && !TABLE) {
+                if (QUERY) {
+                    const float4 rd4 = ps.ray_d[p];
+                    ray_dir = xyz(rd4);
+                    rng.s = __float_as_uint(rd4.w);
+                    if (TABLE) rng = rp_rng_resume<TABLE>(f, p, rng.s);
+                    ray_origin = xyz(ps.ray_o[p]); // (slots without a query were dropped by the regrouping pass: every path here has both)
+                    if (TEX) {
+                        first_du_dv[0] = ld3(f.cam_du);
+                        first_du_dv[1] = ld3(f.cam_dv);
+                    }
+                } else if (FIRST && RP_FIRST_RAY_STORED && !TABLE) {
                     const float4 rd4 = ps.ray_d[p];
                     ray_dir = xyz(rd4);
                     rng.s = __float_as_uint(rd4.w);
@@ -504,9 +582,9 @@ RP_DEV void rp_shade_body(const RpScene &sc, const RpFrame &f, const RpPathState
             if (present) {
                 my_closest++;
                 if (FIRST) { // init_shading_sample_state (shading_interface.glsl:20-22)
-                    if (f.alpha_test && (!TABLE || f.rng_variant == RPTR_RNG_VARIANT_UNIFORM) && !(RP_FIRST_RAY_STORED && !TABLE))
+                    if (!QUERY && f.alpha_test && (!TABLE || f.rng_variant == RPTR_RNG_VARIANT_UNIFORM) && !(RP_FIRST_RAY_STORED && !TABLE))
                         rng.s = (reinterpret_cast<const uint32_t *>(ps.ray_d))[4u * p + 3u]; // alpha tests of the first extend may have drawn from it
-                    if (f.aov_albedo_roughness) { // the first sample of the (last) frame (of the batch) writes the AOVs
+                    if (!QUERY && f.aov_albedo_roughness) { // the first sample of the (last) frame (of the batch) writes the AOVs
                         const RpSlotFrame sf = rp_slot_frame(f, first_sslot);
                         if (sf.sample_index == sf.frame_id && int(sf.frame) == f.batch_frames - 1) {
                             aov_px = first_ly * f.width + first_lx;
@@ -546,7 +624,7 @@ RP_DEV void rp_shade_body(const RpScene &sc, const RpFrame &f, const RpPathState
                     // miss: pt_megakernel.glsl:480-489
                     illum = illum + throughput * rp_compute_sky_illum(f, ray_dir, prev_bounce_pdf);
                     ps.illum[p] = f4(illum, __int_as_float(bounce));
-                    if (FIRST && aov_px >= 0) { // pt_megakernel.glsl:482-487
+                    if (FIRST && !QUERY && aov_px >= 0) { // pt_megakernel.glsl:482-487
                         rp_store_geometry_aovs(f, aov_px, v3s(0.0f), v3s(2.e32f), aov_jitter);
                         rp_store_material_aovs(f, aov_px, v3s(0.0f), 1.0f, 1.0f);
                     }
@@ -627,7 +705,7 @@ RP_DEV void rp_shade_body(const RpScene &sc, const RpFrame &f, const RpPathState
                     V3 emit;
                     rp_unpack_material<VARIANT, TEX>(sc, mat, emit, mp, tc);
                     scatter_throughput = throughput;
-                    if (FIRST && aov_px >= 0) { // pt_megakernel.glsl:670-673, shade_base_material.glsl:28-31
+                    if (FIRST && !QUERY && aov_px >= 0) { // pt_megakernel.glsl:670-673, shade_base_material.glsl:28-31
                         rp_store_geometry_aovs(f, aov_px, nn, ip_p, aov_jitter);
                         rp_store_material_aovs(f, aov_px, throughput * mat.base_color, mat.roughness, mat.ior);
                     }
@@ -856,6 +934,20 @@ __global__ __launch_bounds__(256, (rp_shade_waves<VARIANT, LIGHTS, TEX, TABLE>()
     rp_shade_body<VARIANT, FIRST, LIGHTS, TEX, false, TABLE>(sc, f, ps, sq, order, *count_ptr, next_queue, next_count, shadow_count, ctr, ln, nn, ls, ns);
 }
 
+// the first shade of a radiance-query run: (RpScene, RpFrame, ...) first, as rp_kernarg needs them.
+// Waves per SIMD as for the frame's shade kernels, except the glTF programs on textured scenes: at the 128 VGPRs of four waves they spill
+// 2-4 words to scratch (as rp_k_shade<.., FIRST, .., TEX, ..> does: 8-24 bytes); compiled for three (168 VGPRs) they need 146-159 and none.
+template <int VARIANT, bool LIGHTS, bool TEX, bool TABLE>
+constexpr int rp_shade_query_waves() { return (TEX && VARIANT != RPTR_VARIANT_SIMPLE) ? 3 : rp_shade_waves<VARIANT, LIGHTS, TEX, TABLE>(); }
+template <int VARIANT, bool LIGHTS, bool TEX, bool TABLE, int MATH = RP_FAST_MATH>
+__global__ __launch_bounds__(256, (rp_shade_query_waves<VARIANT, LIGHTS, TEX, TABLE>())) void rp_k_shade_query(RpScene sc, RpFrame f, RpPathState ps, RpShadowRays sq,
+                                                  const uint32_t *count_ptr, uint32_t *next_queue, uint32_t *next_count, uint32_t *shadow_count,
+                                                  RpCounters *ctr) {
+    uint32_t *ln = nullptr, *ls = nullptr;
+    uint32_t nn = 0, ns = 0;
+    rp_shade_body<VARIANT, true, LIGHTS, TEX, false, TABLE, false, true>(sc, f, ps, sq, nullptr, *count_ptr, next_queue, next_count, shadow_count, ctr, ln, nn, ls, ns);
+}
+
 // ------------------------------------------------------------------ tail: the late bounces of a frame in ONE launch
 // From some bounce on a frame's queues hold a few thousand paths, and what a bounce then costs is its three launches
 // (a command-processor packet each, ~14 us when several frames are in flight: profiles/r01_notes.md), not its rays. Paths are
@@ -907,12 +999,13 @@ __global__ __launch_bounds__(256, 1) void rp_k_tail(RpScene sc, RpFrame f, RpPat
     }
 }
 
-// rp_kernarg (above) reads RpScene / RpFrame at the offsets they have as the FIRST TWO by-value arguments of a kernel: both kernels that run
+// rp_kernarg (above) reads RpScene / RpFrame at the offsets they have as the FIRST TWO by-value arguments of a kernel: every kernel that runs
 // rp_shade_body must start their argument lists that way.
 template <class F>
 struct rp_args_start_with_scene_and_frame : std::false_type {};
 template <class... Rest>
 struct rp_args_start_with_scene_and_frame<void (*)(RpScene, RpFrame, Rest...)> : std::true_type {};
 static_assert(rp_args_start_with_scene_and_frame<decltype(&rp_k_shade<RPTR_VARIANT_SIMPLE, true, false, false, false>)>::value &&
-                  rp_args_start_with_scene_and_frame<decltype(&rp_k_tail<RPTR_VARIANT_SIMPLE, false, false, false, true, false>)>::value,
-              "rp_k_shade / rp_k_tail: (RpScene, RpFrame, ...) must come first (kernels.h rp_kernarg)");
+                  rp_args_start_with_scene_and_frame<decltype(&rp_k_tail<RPTR_VARIANT_SIMPLE, false, false, false, true, false>)>::value &&
+                  rp_args_start_with_scene_and_frame<decltype(&rp_k_shade_query<RPTR_VARIANT_SIMPLE, false, false, false>)>::value,
+              "rp_k_shade / rp_k_shade_query / rp_k_tail: (RpScene, RpFrame, ...) must come first (kernels.h rp_kernarg)");

@@ -1,5 +1,5 @@
 // kernels_misc.h -- the kernels around the path stages: resolve (accumulate.glsl +
-// process_samples.comp), the ray-query kernel (rt_intersect.comp) and the refit of dynamic meshes. Included by rptr_hip.hip only
+// process_samples.comp), the resolve of a radiance-query run, the ray-query kernel (rt_intersect.comp) and the refit of dynamic meshes. Included by rptr_hip.hip only
 // (non-template kernels: one definition); the path stages themselves are templates in kernels.h, instantiated in k_*.hip.
 #pragma once
 #include "kernels.h"
@@ -121,6 +121,45 @@ __global__ __launch_bounds__(256) void rp_k_resolve(RpFrame f, RpPathState ps, f
         }
         accum[i] = acc;
         if (fb) fb[i] = shown;
+    }
+}
+
+// ------------------------------------------------------------------ resolve of a radiance-query run (accumulate.glsl:31-42 accumulate_query)
+// Folds the batch's sample slots of every query of the slice (kernels.h RpQueries) into its result slot, in sample order: the running mean of
+// the frame resolve, r += (new - r) / (sample_index + 1), a plain store for sample_index 0, the old value read from the result slot when the
+// batch starts behind sample 0. rgba is what a frame's sample is (alpha 0 when the first ray left the scene). One thread per query.
+// Differences from accumulate_query as written:
+//   - for sample_index > 0 it stores old + (old + (new - old) / (sample_index + 1)): the new mean ADDED onto the old value. The reference
+//     always runs its queries from sample 0 with one layer, where that line is not reached; a mean is what the name and the first line say.
+//   - its layers (samples of one dispatch) read and write the same slot without order ("todo: atomic support required?"). Here the
+//     samples of a query are folded by one thread.
+//   - records with mode_or_data < 0 keep their slot (the convention of rp_k_trace; the megakernel does not read the field).
+__global__ __launch_bounds__(256) void rp_k_resolve_queries(RpFrame f, RpPathState ps, RpQueries rq, float4 *results) {
+    const uint32_t first = uint32_t(rp_local_row_to_global(f, 0)) * uint32_t(f.width); // the slice's rows are consecutive rows of the virtual image
+    const uint32_t count = uint32_t(f.width) * uint32_t(f.local_rows);
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
+        const uint32_t q = first + i;
+        if (q >= rq.n) return; // (i grows with the stride: nothing behind it either)
+        if (rq.records[q].mode_or_data < 0) continue;
+        const int ly = int(rp_div(i, f.div_width)), lx = int(i) - ly * f.width;
+        const uint32_t slot = rp_local_to_slot(f, lx, ly);
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (f.sample_base > 0u) acc = results[q];
+        for (int s = 0; s < f.batch_spp; ++s) {
+            const float4 il = ps.illum[size_t(s) * size_t(f.npix_padded) + slot];
+            const float4 c = make_float4(il.x, il.y, il.z, __float_as_int(il.w) == 0 ? 0.0f : 1.0f); // pt_megakernel.glsl:736
+            const uint32_t sample_index = f.sample_base + uint32_t(s);
+            if (sample_index == 0)
+                acc = c;
+            else {
+                const float denom = float(int(sample_index) + 1);
+                acc.x += (c.x - acc.x) / denom;
+                acc.y += (c.y - acc.y) / denom;
+                acc.z += (c.z - acc.z) / denom;
+                acc.w += (c.w - acc.w) / denom;
+            }
+        }
+        results[q] = acc;
     }
 }
 

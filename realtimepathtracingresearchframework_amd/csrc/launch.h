@@ -33,6 +33,9 @@ void rp_launch_extend(const RpLaunch &l, bool count, bool first, bool alpha, boo
                       const uint32_t *queue, RpBounceCounters *bc, RpCounters *ctr, int *gstack);
 void rp_launch_connect(const RpLaunch &l, bool count, bool alpha, bool single, const RpScene &sc, const RpFrame &f, const RpPathState &ps, const RpShadowRays &sq,
                        RpBounceCounters *bc, RpCounters *ctr, int *gstack);
+// the first extend of a radiance-query run (kernels.h rp_k_extend_query)
+void rp_launch_extend_query(const RpLaunch &l, bool alpha, bool single, bool table, const RpScene &sc, const RpFrame &f, const RpPathState &ps, const RpQueries &rq,
+                            RpBounceCounters *bc, RpCounters *ctr, int *gstack);
 hipError_t rp_extend_blocks_per_cu(int *out);
 hipError_t rp_connect_blocks_per_cu(int single, int *out);
 hipError_t rp_extend_later_blocks_per_cu(int *out);
@@ -40,12 +43,15 @@ hipError_t rp_extend_later_blocks_per_cu(int *out);
 hipError_t rp_prof_exchange(unsigned long long out[16]); // reads and clears the -DRP_PROF counters of rp_k_extend / rp_k_connect
 #endif // occupancy of the traversal kernels (they all fit the same budget)
 
-// k_shade.hip / k_tail.hip, built once per gpu-program variant (-DRP_INST_VARIANT=RPTR_VARIANT_*) and build of the shading arithmetic
+// k_shade.hip / k_shade_query.hip / k_tail.hip, built once per gpu-program variant (-DRP_INST_VARIANT=RPTR_VARIANT_*) and build of the shading arithmetic
 // (-DRP_FAST_MATH=0|1, dmath.h: IEEE division / square root, or the hardware's 1-ulp reciprocal / square root; option "fast_math")
 #define RP_DECLARE_VARIANT(V)                                                                                                                          \
     void rp_launch_shade_##V(const RpLaunch &l, bool first, bool lights, bool tex, bool table, const RpScene &sc, const RpFrame &f, const RpPathState &ps,  \
                               const RpShadowRays &sq, const uint32_t *order, const uint32_t *count_ptr, uint32_t *next_queue, uint32_t *next_count,     \
                               uint32_t *shadow_count, RpCounters *ctr);                                                                                  \
+    void rp_launch_shade_query_##V(const RpLaunch &l, bool lights, bool tex, bool table, const RpScene &sc, const RpFrame &f, const RpPathState &ps,       \
+                                    const RpShadowRays &sq, const uint32_t *count_ptr, uint32_t *next_queue, uint32_t *next_count,                          \
+                                    uint32_t *shadow_count, RpCounters *ctr);                                                                              \
     void rp_launch_tail_##V(const RpLaunch &l, bool lights, bool full, bool single, bool table, const RpScene &sc, const RpFrame &f, const RpPathState &ps,  \
                              const RpShadowRays &sq, const uint32_t *queue, RpCounters *ctr, int first_bounce, int *gstack);
 RP_DECLARE_VARIANT(ieee_v0)
@@ -64,6 +70,15 @@ static inline void rp_launch_shade(int variant, bool fast_math, const RpLaunch &
         fast_math ? rp_launch_shade_fast_v2(l, args...) : rp_launch_shade_ieee_v2(l, args...);
     else
         fast_math ? rp_launch_shade_fast_v0(l, args...) : rp_launch_shade_ieee_v0(l, args...);
+}
+template <class... A>
+static inline void rp_launch_shade_query(int variant, bool fast_math, const RpLaunch &l, A... args) {
+    if (variant == RPTR_VARIANT_SIMPLE)
+        fast_math ? rp_launch_shade_query_fast_v1(l, args...) : rp_launch_shade_query_ieee_v1(l, args...);
+    else if (variant == RPTR_VARIANT_GLTF_TRANSMISSION)
+        fast_math ? rp_launch_shade_query_fast_v2(l, args...) : rp_launch_shade_query_ieee_v2(l, args...);
+    else
+        fast_math ? rp_launch_shade_query_fast_v0(l, args...) : rp_launch_shade_query_ieee_v0(l, args...);
 }
 template <class... A>
 static inline void rp_launch_tail(int variant, bool fast_math, const RpLaunch &l, A... args) {

@@ -96,6 +96,23 @@ int main() {
         std::memcpy(&prim2, &host_res[11], 4);
         std::printf("ray queries: device buffers %s host arrays; primitives %d %d %d\n", same ? "=" : "!=", prim0, prim1, prim2);
         if (!same || prim0 != 2 || prim1 < 0 || prim1 > 1 || prim2 != -1) return 9;
+        // ---- the same three rays with a path-tracing variant: radiance instead of hit records (render_ray_queries(num_queries, params,
+        // variant_idx)); two calls of two samples refine the same probes to the mean one call of four gives
+        {
+            float rad4[12] = {0}, rad22[12] = {0}, dev_rad[12];
+            if (!backend.render_ray_queries(rq, 3, backend.params, RPTR_VARIANT_GLTF, cfg.camera, rad4, 4, 0)) return 11;
+            backend.render_ray_queries(rq, 3, backend.params, RPTR_VARIANT_GLTF, cfg.camera, rad22, 2, 0);
+            backend.render_ray_queries(rq, 3, backend.params, RPTR_VARIANT_GLTF, cfg.camera, rad22, 2, 2);
+            if (hip_memcpy(backend.ray_query_buffer(), rq, sizeof rq, 1) != 0) return 6;
+            if (!backend.render_ray_queries(3, backend.params, RPTR_VARIANT_GLTF, cfg.camera, 4, 0)) return 11;
+            backend.render_ray_queries(rq, 3, again); // (synchronous: the backend's stream has run the queries)
+            if (hip_memcpy(dev_rad, backend.ray_result_buffer(), sizeof dev_rad, 2) != 0) return 8;
+            const bool same_rad = std::memcmp(rad4, rad22, sizeof rad4) == 0 && std::memcmp(rad4, dev_rad, sizeof rad4) == 0;
+            std::printf("radiance queries: %s; rgba %.4f %.4f %.4f %.1f | %.4f %.4f %.4f %.1f | %.4f %.4f %.4f %.1f\n", same_rad ? "split = whole = device buffers" : "DIFFERENT",
+                        rad4[0], rad4[1], rad4[2], rad4[3], rad4[4], rad4[5], rad4[6], rad4[7], rad4[8], rad4[9], rad4[10], rad4[11]);
+            // (the third ray leaves the scene: alpha 0, what the sky model gives)
+            if (!same_rad || rad4[3] != 1.0f || rad4[7] != 1.0f || rad4[11] != 0.0f || !(rad4[0] >= 0.0f) || !(rad4[8] >= 0.0f)) return 12;
+        }
         // ---- the ray-query-only surface (struct RaytraceBackend, librender/raytrace_backend.h:13-19)
         {
             rptr::RaytraceHip rt;

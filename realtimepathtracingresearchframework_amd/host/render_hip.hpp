@@ -282,9 +282,31 @@ public:
     }
     void *ray_query_buffer() const { return ray_query_buffer_; }
     void *ray_result_buffer() const { return ray_result_buffer_; }
-    bool render_ray_queries(int num_queries) { // (RenderParams / variant / command stream of the reference's signature select nothing here)
+    bool render_ray_queries(int num_queries) { // the RQ_CLOSEST program: hit records (the reference's params / variant select nothing for it)
         if (!ray_query_buffer_) return false;
         check(rptr_hip_render_ray_queries(h_, num_queries));
+        return true;
+    }
+    // RenderBackend::render_ray_queries(num_queries, params, variant_idx, ...) with a path-tracing variant (render_vulkan.cpp:2961-3059):
+    // the path tracer runs on the query rays and ray_result_buffer receives (radiance.rgb, alpha) -- the mean over samples_per_query
+    // samples from first_sample on (the reference: one sample, from 0). `camera` supplies the image-plane axes of the texture footprint,
+    // as the reference's view does. An index that is no RPTR_VARIANT_* gpu program is refused (the RQ_CLOSEST program has the overload above).
+    // render_params become the handle's RenderParams (rptr_hip_set_params): later frames render with them too.
+    bool render_ray_queries(int num_queries, const RptrRenderParams &render_params, int variant_idx, const RenderCameraParams &camera, int samples_per_query = 1,
+                            int first_sample = 0) {
+        if (!ray_query_buffer_) return false;
+        check(rptr_hip_set_params(h_, &render_params, nullptr, nullptr));
+        const RptrCamera cam = to_abi(camera);
+        check(rptr_hip_render_radiance_queries(h_, num_queries, &cam, variant_idx, samples_per_query, first_sample));
+        return true;
+    }
+    // ... over HOST arrays (results4 is read as well as written: old means for first_sample > 0, slots of skipped queries)
+    bool render_ray_queries(const RptrRenderRayQuery *queries, int num_queries, const RptrRenderParams &render_params, int variant_idx, const RenderCameraParams &camera,
+                            float *results4, int samples_per_query = 1, int first_sample = 0) {
+        if (num_queries < 0) return false;
+        check(rptr_hip_set_params(h_, &render_params, nullptr, nullptr));
+        const RptrCamera cam = to_abi(camera);
+        check(rptr_hip_trace_radiance(h_, queries, num_queries, &cam, variant_idx, samples_per_query, first_sample, results4, nullptr));
         return true;
     }
     // convenience over HOST arrays (tests, tools): rptr_hip_trace uploads, traces, reads back
@@ -300,6 +322,16 @@ public:
     rptr_hip_t *handle() { return h_; }
 
 private:
+    static RptrCamera to_abi(const RenderCameraParams &c) {
+        RptrCamera cam{};
+        for (int k = 0; k < 3; ++k) {
+            cam.pos[k] = c.pos[k];
+            cam.dir[k] = c.dir[k];
+            cam.up[k] = c.up[k];
+        }
+        cam.fovy = c.fovy;
+        return cam;
+    }
     void check(int rc) const {
         if (rc != RPTR_OK) throw std::runtime_error(std::string("rptr_hip: ") + rptr_hip_last_error(h_));
     }

@@ -1,0 +1,108 @@
+"""Radiance ray queries without a GPU: the C ABI, the Python methods, the C++ adapter overloads and the code-object facts of the query
+kernels (tests/test_gpu_radiance_queries.py runs them)."""
+import inspect
+import os
+import re
+import shutil
+import subprocess
+
+import pytest
+
+from realtimepathtracingresearchframework_amd import abi, backend, build
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW = ["rptr_hip_trace_radiance", "rptr_hip_trace_radiance_device", "rptr_hip_render_radiance_queries"]
+
+
+def test_entry_points_are_declared_exported_and_bound():
+    hdr = open(os.path.join(ROOT, "include", "rptr_hip.h")).read()
+    L = backend.load_library()
+    for name in NEW:
+        assert re.search(r"^int %s\(rptr_hip_t \*h," % name, hdr, re.M), name
+        assert name in abi.EXPORTED_SYMBOLS and hasattr(L, name)
+        assert getattr(L, name).argtypes is not None
+    assert len(L.rptr_hip_trace_radiance.argtypes) == 9 and len(L.rptr_hip_trace_radiance_device.argtypes) == 9
+    assert len(L.rptr_hip_render_radiance_queries.argtypes) == 6
+
+
+def test_python_methods_have_the_documented_signature():
+    p = inspect.signature(backend.RenderHip.render_radiance_queries).parameters
+    assert list(p)[:3] == ["self", "queries", "camera"]
+    assert (p["variant"].default, p["spp"].default, p["first_sample"].default, p["results"].default) == (abi.VARIANT_GLTF, 1, 0, None)
+    d = inspect.signature(backend.RenderHip.render_radiance_queries_device).parameters
+    assert list(d)[:3] == ["self", "num_queries", "camera"] and (d["spp"].default, d["first_sample"].default) == (1, 0)
+
+
+def test_arguments_are_checked_before_the_device_is_touched():
+    """NULL handle / camera and bad counts are refused without a GPU"""
+    L = backend.load_library()
+    assert L.rptr_hip_trace_radiance(None, None, 0, None, 0, 1, 0, None, None) == abi.RPTR_E_INVALID
+    assert L.rptr_hip_render_radiance_queries(None, 0, None, 0, 1, 0) == abi.RPTR_E_INVALID
+
+
+def test_cpp_overloads_compile_and_link(tmp_path):
+    """RenderHip::render_ray_queries in the reference's shape (num_queries, params, variant_idx, ...) next to the closest-hit one"""
+    src = tmp_path / "rq.cpp"
+    src.write_text('''#include "render_hip.hpp"
+int main(int argc, char **) {
+    if (argc < 100) return 0; // (compiled and linked, not run: no device here)
+    rptr::RenderHip b;
+    rptr::RenderCameraParams cam{};
+    RptrRenderRayQuery q[2] = {};
+    float out[8] = {0};
+    b.enable_ray_queries(16);
+    bool ok = b.render_ray_queries(2) && b.render_ray_queries(2, b.params, RPTR_VARIANT_GLTF, cam) && b.render_ray_queries(2, b.params, RPTR_VARIANT_SIMPLE, cam, 4, 8) &&
+              b.render_ray_queries(q, 2, out) && b.render_ray_queries(q, 2, b.params, RPTR_VARIANT_GLTF, cam, out, 4, 0);
+    return ok ? 0 : 1;
+}
+''')
+    exe = str(tmp_path / "rq")
+    libdir = os.path.dirname(build.LIB_PATH)
+    if not os.path.exists(build.LIB_PATH):
+        build.build_library()
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I" + os.path.join(libdir, "host"), str(src), "-o", exe, "-L" + libdir, "-lrptr_hip",
+                           "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"])
+    assert subprocess.call([exe]) == 0
+
+
+def _regs():
+    if not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-objdump") or shutil.which("bash") is None:
+        pytest.skip("no llvm-objdump")
+    if not os.path.exists(build.LIB_PATH):
+        build.build_library()
+    out = subprocess.run(["bash", os.path.join(ROOT, "tools", "kernel_regs.sh"), build.LIB_PATH], stdout=subprocess.PIPE, universal_newlines=True, check=True).stdout
+    regs = {}
+    for line in out.splitlines():
+        m = re.match(r"(\S+)\s+vgpr\s+(\d+)\s+sgpr\s+(\d+)\s+scratch\s+(\d+)\s+lds\s+(\d+)", line)
+        if m:
+            regs[m.group(1)] = tuple(int(x) for x in m.groups()[1:])
+    return regs
+
+
+def test_query_traversal_and_resolve_kernels_are_present_and_free_of_scratch():
+    """rp_k_extend_query<ALPHA, SINGLE, TABLE>: all eight instantiations without a private segment. Without the alpha test they keep the
+    frame's budgets (six / seven waves per SIMD: 80 / 72 VGPRs); with it they are compiled for five waves (96 VGPRs: at 80 the generator a
+    lane carries through the walk spills, as it does in rp_k_extend<.., FIRST, ALPHA, ..>). rp_k_resolve_queries: no scratch, no LDS."""
+    regs = _regs()
+    ext = {k: v for k, v in regs.items() if k.startswith("_Z17rp_k_extend_queryILb")}
+    assert len(ext) == 8, sorted(ext)
+    for k, v in ext.items():
+        alpha, single = k.startswith("_Z17rp_k_extend_queryILb1E"), k[len("_Z17rp_k_extend_queryILb0E"):].startswith("Lb1E")
+        assert v[2] == 0, (k, v)
+        assert v[0] <= (96 if alpha else 72 if single else 80), (k, v)
+    res = [v for k, v in regs.items() if k.startswith("_Z20rp_k_resolve_queries")]
+    assert len(res) == 1 and res[0][2] == 0 and res[0][3] == 0, res
+
+
+def test_query_shade_kernels_are_present_and_free_of_scratch():
+    """rp_k_shade_query<VARIANT, LIGHTS, TEX, TABLE, MATH>: 3 x 2 x 2 x 2 x 2 instantiations, none with a private segment (the kernel takes
+    origin, direction and generator state from the path state, where rp_k_extend_query left them: with the query buffer among its
+    arguments most instantiations reserved 8-40 bytes)"""
+    regs = _regs()
+    sh = {k: v for k, v in regs.items() if k.startswith("_Z16rp_k_shade_queryILi")}
+    assert len(sh) == 48, len(sh)
+    # (four waves per SIMD = 128 VGPRs; the glTF programs on textured scenes are compiled for three = 168: kernels.h rp_shade_query_waves)
+    assert all(v[0] <= (168 if re.match(r"_Z16rp_k_shade_queryILi[02]ELb[01]ELb1E", k) else 128) for k, v in sh.items())
+    with_scratch = {k[:40]: v[2] for k, v in sh.items() if v[2] != 0}
+    print("rp_k_shade_query private segment bytes:", sorted(set(with_scratch.values())), "in", len(with_scratch), "of", len(sh))
+    assert not with_scratch, with_scratch
