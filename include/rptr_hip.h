@@ -207,13 +207,17 @@ typedef struct RptrGeometryDesc {
 /* a mesh = one bottom-level acceleration structure (librender/mesh.h:43-72) */
 #define RPTR_MESH_DYNAMIC 1u
 #define RPTR_MESH_SUBTLY_DYNAMIC 2u
+#define RPTR_MESH_INSTANCES_MOVE 4u /* RptrMeshDesc.dynamic bit 2: instances of this mesh may be moved (rptr_hip_update_instances) */
 typedef struct RptrMeshDesc {
     uint32_t first_geometry;
     uint32_t num_geometries;
     uint32_t dynamic; /* Mesh::flags (librender/mesh.h:44-47): 0 static; bit 0 RPTR_MESH_DYNAMIC: vertices may be updated, the tree
                        * is refitted -- or, under rptr_hip_set_bvh_policy, rebuilt on the device; bit 1 RPTR_MESH_SUBTLY_DYNAMIC (small
                        * deformations: SceneLoaderParams::small_deformation): updated and refitted, never rebuilt -- the reference builds
-                       * such meshes PREFER_FAST_TRACE | ALLOW_UPDATE instead of PREFER_FAST_BUILD (render_vulkan.cpp:942-952)          */
+                       * such meshes PREFER_FAST_TRACE | ALLOW_UPDATE instead of PREFER_FAST_BUILD (render_vulkan.cpp:942-952);
+                       * bit 2 RPTR_MESH_INSTANCES_MOVE: only read by set_scene -- the mesh's instances keep top-level records of their own
+                       * instead of being baked into the flattened world-space tree (as for any non-zero value), and the top level gets
+                       * room for device-side rebuilds. With this bit alone the mesh's tree is a static build                           */
 } RptrMeshDesc;
 
 /* a mesh with a material assignment (librender/mesh.h:78-108, ParameterizedMesh) */
@@ -381,6 +385,44 @@ int rptr_hip_refit(rptr_hip_t *h);
  * by ids); only the number of node visits differs. rptr_hip_bvh_rebuild_count: device-side rebuilds so far (all scene copies). */
 int rptr_hip_set_bvh_policy(rptr_hip_t *h, int force_bvh_rebuild, int rebuild_triangle_budget);
 int rptr_hip_bvh_rebuild_count(const rptr_hip_t *h, uint64_t *out_rebuilds);
+
+/* ---- moving instances (the reference rebuilds its TLAS from the instance list every time it changes: default_update_tlas,
+ * render_vulkan.cpp:1219-1321; request_tlas_operation(Rebuild | Refit), :1323-1354, picks between a build and an update).
+ * rptr_hip_update_instances: transforms12 holds `count` row-major 3x4 object-to-world matrices (the layout of
+ * RptrInstanceDesc.transform) for scene instances [first_instance, first_instance + count). Like update_vertices the call only STAGES
+ * the change: the next rptr_hip_refit writes it into the instance records of every scene copy, on that copy's stream, together with the
+ * vertex updates staged for the same refit -- world_to_object with the arithmetic of set_scene, so the records equal those of a fresh
+ * set_scene of the moved scene bit for bit -- re-bounds the records and updates the top level. The _device form reads DEVICE memory,
+ * ordered on the backend's stream, no host synchronisation; it cannot report a bad matrix: a matrix that is not finite or singular
+ * leaves its instance where it was and is counted: rptr_hip_get_option(h, "instance_updates_rejected") (read-only, since set_scene;
+ * reading it waits for the backend's stream).
+ * Which instances can move: every instance that has top-level records -- all of them in a two-level scene (option flatten = 0, or the
+ * scene was not flattened), and in a flattened scene those of meshes with a non-zero RptrMeshDesc.dynamic (RPTR_MESH_INSTANCES_MOVE is
+ * the bit that says nothing else). An instance baked into the flat tree: RPTR_E_INVALID. A bad range, NULL, a matrix that is not
+ * finite or whose inverse is not (det == 0): RPTR_E_INVALID, nothing is staged. An instance whose parameterized mesh uses an emissive
+ * material: RPTR_E_UNSUPPORTED -- RptrSceneDesc.lights are world-space triangles collected by the host and would go stale.
+ * rptr_hip_set_tlas_policy: RPTR_TLAS_REBUILD (default, what default_update_tlas does): a refit that finds moved instances builds a
+ * NEW top level on the device (csrc/tlas_build.h: Morton keys of the record boxes + radix sort + binary radix tree + 4-wide collapse,
+ * one record per leaf, boxes and encoding through the refit) -- in scenes where set_scene reserved room for one, i.e. where some
+ * instanced mesh has RPTR_MESH_INSTANCES_MOVE; elsewhere, and under RPTR_TLAS_REFIT, the topology stays and the boxes follow, which
+ * degrades without bound once instances travel. Ray-query results are those of any tree. rptr_hip_tlas_rebuild_count: device-side
+ * rebuilds of the top level so far (all scene copies); RPTR_TLAS_REFIT leaves it alone.
+ * Traversal stack: a rebuilt top level has another depth than the host-built one. set_scene BOUNDS the need of any tree the device build
+ * can make over the scene's records (its keys are 30 Morton bits + the index bits wide: at most 3 entries per 4-wide level, never more
+ * than records - 1) and fails with the usual RPTR_E_UNSUPPORTED stack message when that bound plus the bottom-level need exceeds the
+ * stack; nothing is checked again per rebuild.
+ * Frames in flight: a scene with a RPTR_MESH_INSTANCES_MOVE (or dynamic) mesh gives every frame context its own tree and instance
+ * records, so a refit never waits -- per context a copy of the node array (88 bytes per node, top level and bottom-level trees are one
+ * array) and of the instance records; triangles and shading records are shared unless a mesh deforms --; in any other scene rptr_hip_refit waits for the frames in flight first, as it always did.
+ * Limits: the motion AOV stays motion_vector = 0 for moved objects (rigid-motion vectors need the previous transform next to the 128-byte
+ * record): under reprojection_mode = 2 a moved object ghosts until its history is rejected. rptr_hip_traversal_preset keeps what set_scene
+ * chose. The top level's refit after a rebuild runs in one block up to 8192 records; that break-even was estimated, not measured. */
+#define RPTR_TLAS_REBUILD 0
+#define RPTR_TLAS_REFIT 1
+int rptr_hip_update_instances(rptr_hip_t *h, uint32_t first_instance, uint32_t count, const float *transforms12);
+int rptr_hip_update_instances_device(rptr_hip_t *h, uint32_t first_instance, uint32_t count, const float *device_transforms12);
+int rptr_hip_set_tlas_policy(rptr_hip_t *h, int mode);
+int rptr_hip_tlas_rebuild_count(const rptr_hip_t *h, uint64_t *out_rebuilds);
 
 /* ---- RenderBackend::params / lighting_params / update_config
  * (render_backend.h:69-76, render_vulkan.cpp:2943-2959) */

@@ -82,6 +82,10 @@ def load_library(path=None):
     L.rptr_hip_set_rng_variant.argtypes = [vp, i32, vp, C.c_size_t]
     L.rptr_hip_set_bvh_policy.argtypes = [vp, i32, i32]
     L.rptr_hip_bvh_rebuild_count.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.rptr_hip_update_instances.argtypes = [vp, C.c_uint32, C.c_uint32, vp]
+    L.rptr_hip_update_instances_device.argtypes = [vp, C.c_uint32, C.c_uint32, vp]
+    L.rptr_hip_set_tlas_policy.argtypes = [vp, i32]
+    L.rptr_hip_tlas_rebuild_count.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.rptr_hip_bvh_build_info.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.rptr_hip_traversal_preset.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.rptr_hip_get_framebuffer_size.argtypes = [vp, C.POINTER(C.c_uint32)]
@@ -463,6 +467,26 @@ class RenderHip:
 
     def refit(self):
         self._check(self._L.rptr_hip_refit(self._h))
+
+    # ---- moving instances (TLAS rebuild / update from the instance list, render_vulkan.cpp:1219-1354)
+    def update_instances(self, first, transforms: np.ndarray):
+        """New object-to-world transforms for scene instances [first, first + n): transforms is (n, 12) or (n, 3, 4) float32,
+        row-major 3x4. Staged; the next refit() applies them."""
+        t = np.ascontiguousarray(transforms, dtype=np.float32).reshape(-1, 12)
+        self._check(self._L.rptr_hip_update_instances(self._h, int(first), t.shape[0], t.ctypes.data_as(C.c_void_p)))
+
+    def update_instances_device(self, first, device_ptr, count):
+        """same from a device buffer (12 float32 per instance) written on the backend's stream."""
+        self._check(self._L.rptr_hip_update_instances_device(self._h, int(first), int(count), C.c_void_p(device_ptr)))
+
+    def set_tlas_policy(self, mode):
+        """abi.TLAS_REBUILD (default): moved instances get a new top level built on the device; abi.TLAS_REFIT: the topology stays"""
+        self._check(self._L.rptr_hip_set_tlas_policy(self._h, int(mode)))
+
+    def tlas_rebuild_count(self):
+        n = C.c_uint64()
+        self._check(self._L.rptr_hip_tlas_rebuild_count(self._h, C.byref(n)))
+        return int(n.value)
 
     def set_rng_variant(self, rng_variant, table=None):
         """RenderBackendOptions::rng_variant (render_params.glsl.h:34-37,76) + the table upload of the point set's render extension

@@ -77,6 +77,16 @@ int rptr_hip_get_option(const rptr_hip_t *h, const char *key, int64_t *out_value
         *out_value = (int64_t)h->rebuild_failures;
         return RPTR_OK;
     }
+    if (h && key && out_value && !strcmp(key, "instance_updates_rejected")) { // (read-only: matrices rptr_hip_update_instances_device skipped
+        uint32_t n = 0;                                                       // since set_scene; waits for the backend's stream)
+        if (h->have_scene && h->d_inst_rejected) {
+            if (hipSetDevice(h->device) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess ||
+                hipMemcpy(&n, h->d_inst_rejected, sizeof(n), hipMemcpyDeviceToHost) != hipSuccess)
+                return fail(nullptr, RPTR_E_HIP, "reading the counter failed");
+        }
+        *out_value = (int64_t)n;
+        return RPTR_OK;
+    }
     if (h && key && out_value && !strcmp(key, "sample_slots")) { // (read-only: the sample slots a frame context holds once initialize has sized
         *out_value = (int64_t)h->max_batch_spp;                  // the path state -- "max_batch_spp" or what the budget allows; 0 before initialize)
         return RPTR_OK;
@@ -454,6 +464,9 @@ int rptr_hip_export_bvh(rptr_hip_t *h, void *nodes, size_t *n_nodes, void *tris,
         HIP_TRY(h, hipStreamSynchronize(h->stream));
         HIP_TRY(h, hipMemcpy(h->h_nodes.data(), h->master.dscene.nodes, h->h_nodes.size() * sizeof(RptrBvh4Node), hipMemcpyDeviceToHost));
         if (!h->h_tris.empty()) HIP_TRY(h, hipMemcpy(h->h_tris.data(), h->master.dscene.tris, h->h_tris.size() * sizeof(RptrBvhTri), hipMemcpyDeviceToHost));
+        if (h->host_insts_stale && !h->h_insts.empty()) // (instances moved: rptr_hip_update_instances)
+            HIP_TRY(h, hipMemcpy(h->h_insts.data(), h->master.dscene.insts, h->h_insts.size() * sizeof(RptrBvhInstance), hipMemcpyDeviceToHost));
+        h->host_insts_stale = false;
         h->host_bvh_stale = false;
     }
     if (nodes && n_nodes && *n_nodes >= h->h_nodes.size()) memcpy(nodes, h->h_nodes.data(), h->h_nodes.size() * sizeof(RptrBvh4Node));

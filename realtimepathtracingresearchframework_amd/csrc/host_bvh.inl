@@ -18,6 +18,7 @@ struct HostBvh {
     int num_tlas_insts = 0; // instance records the top level refers to (a flattened scene keeps the scene's own records behind them)
     float scene_lo[3] = {0, 0, 0}, scene_hi[3] = {1, 1, 1};
     int stack_need = 0;
+    int tlas_capacity = 0; // > 0: some instanced mesh has RPTR_MESH_INSTANCES_MOVE -- top-level nodes reserved for device-side rebuilds (tlas_build.h)
     size_t flat_tris = 0, flat_nodes = 0; // a (partially) flattened scene: triangles / nodes of its one world-space tree (they come first)
     int flat_id_bias = 0;                 // ... and where its triangles' own instance records start (record = bias + instance id)
     bool device_built = false; // some bottom-level tree came from the device builder (ploc.h)
@@ -75,6 +76,7 @@ static std::string validate_scene_tables(const RptrSceneDesc *s) {
 // 0: two-level; 1: the whole scene is one world-space tree (every instanced mesh is static); 2: PARTIAL -- the scene has dynamic meshes: the
 // instances of its static meshes are flattened into one tree, which the top level holds as one identity instance beside the records of the
 // dynamic meshes' instances (round 5: a forest with one animated character used to fall back to the two-level walk as a whole: 1.5 x)
+static const uint32_t kMeshDeforms = RPTR_MESH_DYNAMIC | RPTR_MESH_SUBTLY_DYNAMIC; // the bits of RptrMeshDesc.dynamic that say "vertices change"
 static int want_flatten(const RptrSceneDesc *s, const RpOptions &o) {
     // option "flatten": -1 / 1 = every static multi-instance scene that fits "flatten_max_tris" (the default: the library knows which
     // meshes are dynamic -- RptrMeshDesc.dynamic, the reference's per-mesh build intent, vulkan/render_vulkan.cpp:942-952 -- and a flattened
@@ -193,7 +195,7 @@ static bool device_build_tree(rptr_hip *h, const std::vector<RpBuildSegment> &se
     hipLaunchKernelGGL(rp_k_lbvh_bounds, dim3(g), dim3(256), 0, st, box_a, n, bounds);
     int index_bits = 1;
     while ((1ull << index_bits) < (unsigned long long)n) ++index_bits;
-    hipLaunchKernelGGL(rp_k_lbvh_keys, dim3(g), dim3(256), 0, st, box_a, n, bounds, keys_a, index_bits);
+    hipLaunchKernelGGL(rp_k_lbvh_keys, dim3(g), dim3(256), 0, st, box_a, n, bounds, keys_a, index_bits, 21);
     size_t bytes = cub_bytes;
     DB_TRY(hipcub::DeviceRadixSort::SortKeys(cub_tmp, bytes, keys_a, keys_b, (int)n, 0, 64, st));
     hipLaunchKernelGGL(rp_k_lbvh_gather, dim3(g), dim3(256), 0, st, keys_b, n, tris_a, box_a, tris_b, box_b, (1ull << index_bits) - 1ull);
@@ -599,7 +601,7 @@ static void build_host_bvh(const RptrSceneDesc *s, HostBvh &B, const RpOptions &
         {
             size_t total = 0;
             for (uint32_t j = 0; j < mesh.num_geometries; ++j) total += s->geometries[mesh.first_geometry + j].num_tris;
-            if (mesh.dynamic == 0 && on_device(total) && dev->d_qpos) {
+            if ((mesh.dynamic & kMeshDeforms) == 0 && on_device(total) && dev->d_qpos) { // (RPTR_MESH_INSTANCES_MOVE alone: a static build)
                 std::vector<RpBuildSegment> segs;
                 std::vector<size_t> geom_first(mesh.num_geometries, 0);
                 size_t at = 0;
@@ -654,7 +656,7 @@ static void build_host_bvh(const RptrSceneDesc *s, HostBvh &B, const RpOptions &
         std::vector<rptr::BuildPrim> prims;
         std::vector<RptrBvhTri> mtris;
         std::vector<rptr::TriVerts> verts;
-        const bool split_mesh = mesh.dynamic == 0 && split_density > 0.0f && split_budget > 0.0f; // (a refit recomputes boxes from whole triangles)
+        const bool split_mesh = (mesh.dynamic & kMeshDeforms) == 0 && split_density > 0.0f && split_budget > 0.0f; // (a refit recomputes boxes from whole triangles)
         for (uint32_t j = 0; j < mesh.num_geometries; ++j) {
             const RptrGeometryDesc &gd = s->geometries[mesh.first_geometry + j];
             for (uint32_t t = 0; t < gd.num_tris; ++t) {
@@ -682,7 +684,7 @@ static void build_host_bvh(const RptrSceneDesc *s, HostBvh &B, const RpOptions &
             }
         }
         MeshRt &mr = B.meshes[m];
-        mr.dynamic = mesh.dynamic != 0;
+        mr.dynamic = (mesh.dynamic & kMeshDeforms) != 0; // (instances that move do not make the mesh's own tree dynamic)
         mr.rebuildable = mr.dynamic && (mesh.dynamic & RPTR_MESH_SUBTLY_DYNAMIC) == 0;
         std::vector<uint32_t> ref_tri;
         if (split_mesh) rptr::presplit_triangles(verts.data(), (uint32_t)verts.size(), split_density, split_budget, 256, 0, prims, ref_tri);
@@ -843,11 +845,25 @@ static void build_host_bvh(const RptrSceneDesc *s, HostBvh &B, const RpOptions &
         B.scene_lo[k] = std::isfinite(tlas.lo[k]) ? tlas.lo[k] : 0.0f;
         B.scene_hi[k] = std::isfinite(tlas.hi[k]) ? tlas.hi[k] : 1.0f;
     }
-    const int reloc = (int)tlas_wide.nodes.size();
+    // instances that may move (RPTR_MESH_INSTANCES_MOVE on some instanced mesh): the top level gets room for the worst case of a device-side
+    // build over its records -- one 4-wide node per binary inner node at most --, the bottom-level trees lie behind that. Without the bit
+    // nothing is reserved and the buffers are what they always were.
+    bool reserve = false;
+    for (uint32_t i = 0; i < s->num_instances; ++i)
+        reserve = reserve || (s->meshes[s->parameterized_meshes[s->instances[i].parameterized_mesh].mesh].dynamic & RPTR_MESH_INSTANCES_MOVE) != 0;
+    B.tlas_capacity = reserve ? (int)std::max(tlas_wide.nodes.size(), std::max<size_t>(insts.size(), 1)) : 0;
+    const int reloc = reserve ? B.tlas_capacity : (int)tlas_wide.nodes.size();
     B.num_tlas_nodes = reloc;
     B.nodes.clear();
     B.node_box.clear();
     encode_tree(tlas_wide, 0, 0, B.nodes, B.node_box); // TLAS leaf 'first' already indexes the reordered instance array
+    if ((int)B.nodes.size() < reloc) { // unreachable empty nodes, as behind a rebuildable mesh's tree
+        RptrBvh4Node empty;
+        memset(&empty, 0, sizeof(empty));
+        for (int k = 0; k < 4; ++k) empty.child[k] = RPTR_BVH4_EMPTY;
+        B.nodes.resize((size_t)reloc, empty);
+        B.node_box.resize((size_t)reloc, std::array<float, 6>{0, 0, 0, 0, 0, 0});
+    }
     for (size_t i = 0; i < blas_nodes.size(); ++i) {
         RptrBvh4Node nd = blas_nodes[i];
         for (int k = 0; k < 4; ++k)
@@ -884,7 +900,9 @@ static void build_host_bvh(const RptrSceneDesc *s, HostBvh &B, const RpOptions &
         }
         int blas_need = 0;
         for (size_t m = 0; m < B.meshes.size(); ++m) blas_need = std::max(blas_need, need[B.mesh_root[m]]);
-        const int total = 1 + need[0] + 1 + blas_need;
+        // (a top level the device may rebuild: whatever tree that build can make over these records must fit too, tlas_build.h)
+        const int tlas_need = B.tlas_capacity > 0 ? std::max(need[0], rp_tlas_stack_bound((size_t)B.num_tlas_insts)) : need[0];
+        const int total = 1 + tlas_need + 1 + blas_need;
         B.stack_need = total;
     }
 }

@@ -465,6 +465,8 @@ static int render_batch_impl(rptr_hip_t *h, const RptrCamera *camera, bool per_f
             if (scn.dynpos[gi])
                 HIP_TRY(h, hipMemcpyAsync(scn.dynpos[gi], h->master.dynpos[gi], (size_t)h->geom_tris[gi] * 9 * sizeof(float), hipMemcpyDeviceToDevice,
                                           h->stream));
+        if (scn.inst_version != h->inst_version && h->num_instances) // ... and so do the staged instance transforms (rptr_hip_update_instances)
+            HIP_TRY(h, hipMemcpyAsync(scn.inst_xf, h->master.inst_xf, (size_t)96 * h->num_instances, hipMemcpyDeviceToDevice, h->stream));
     }
     // whatever the caller queued on the backend's stream (vertex updates, the copy above) comes first. When that stream has nothing
     // unfinished there is nothing to wait for, and no event is recorded: an event on a stream that shares its hardware queue with another

@@ -107,7 +107,7 @@ static int scene_upload_vertex_streams(rptr_hip *h, const RptrSceneDesc *s, std:
             const RptrGeometryDesc &gd = s->geometries[gi];
             h->geom_tris[gi] = gd.num_tris;
             h->geom_mesh[gi] = (int)m;
-            if (!mesh.dynamic) continue;
+            if (!(mesh.dynamic & kMeshDeforms)) continue;
             std::vector<float> pos((size_t)gd.num_tris * 9);
             for (size_t v = 0; v < (size_t)gd.num_tris * 3; ++v) dequantize_position(gd.qpos[v], gd.quantized_scaling, gd.quantized_offset, &pos[3 * v]);
             float *dp = nullptr;
@@ -116,7 +116,7 @@ static int scene_upload_vertex_streams(rptr_hip *h, const RptrSceneDesc *s, std:
             h->master.dynpos[gi] = dp;
             table[j] = dp;
         }
-        if (mesh.dynamic) {
+        if (mesh.dynamic & kMeshDeforms) {
             const float **dt = nullptr;
             if ((rc = dev_alloc(h, &dt, table.size(), &h->scene_allocs))) return rc;
             if (!table.empty()) HIP_TRY(h, hipMemcpy(dt, table.data(), table.size() * sizeof(float *), hipMemcpyHostToDevice));
@@ -375,6 +375,28 @@ int rptr_hip_set_scene(rptr_hip_t *h, const RptrSceneDesc *s) {
     h->num_tlas_nodes = B.num_tlas_nodes;
     h->flat_tris = B.flat_tris;
     h->flat_nodes = B.flat_nodes;
+    h->tlas_capacity = B.tlas_capacity;
+    // ---- moving instances: which instances have top-level records of their own, which ones carry lights
+    h->num_instances = s->num_instances;
+    h->inst_movable.assign(s->num_instances, 0);
+    for (int k = 0; k < h->num_tlas_insts; ++k)
+        if (h->h_insts[(size_t)k].instance_id >= 0 && (uint32_t)h->h_insts[(size_t)k].instance_id < s->num_instances) h->inst_movable[(size_t)h->h_insts[(size_t)k].instance_id] = 1;
+    {
+        std::vector<char> pmesh_emissive(s->num_parameterized_meshes, 0);
+        for (uint32_t p = 0; p < s->num_parameterized_meshes; ++p) {
+            const RptrParameterizedMeshDesc &pm = s->parameterized_meshes[p];
+            const RptrMeshDesc &mesh = s->meshes[pm.mesh];
+            size_t off = 0;
+            for (uint32_t j = 0; j < mesh.num_geometries; ++j) {
+                const uint32_t nt = s->geometries[mesh.first_geometry + j].num_tris;
+                for (uint32_t t = 0; t < (pm.tri_material_ids ? nt : std::min(nt, 1u)); ++t) // (validated: every id is a material of the scene)
+                    if (s->materials[(size_t)pm.material_offsets[j] + (pm.tri_material_ids ? pm.tri_material_ids[off + t] : 0)].emission_intensity > 0.0f) pmesh_emissive[p] = 1;
+                off += nt;
+            }
+        }
+        h->inst_emissive.assign(s->num_instances, 0);
+        for (uint32_t i = 0; i < s->num_instances; ++i) h->inst_emissive[i] = pmesh_emissive[s->instances[i].parameterized_mesh];
+    }
     memcpy(h->scene_lo, B.scene_lo, 12);
     memcpy(h->scene_hi, B.scene_hi, 12);
     // ---- refit tables
@@ -432,6 +454,16 @@ int rptr_hip_set_scene(rptr_hip_t *h, const RptrSceneDesc *s) {
         release_scene_copy_host(sc);
         sc.pinned_levels.assign(h->meshes.size(), nullptr);
         sc.ev_levels.assign(h->meshes.size(), nullptr);
+        sc.inst_version = h->inst_version;
+        sc.tlas_rebuilt = false;
+        sc.tlas_list = nullptr;
+        sc.tlas_levels = nullptr;
+        sc.tlas_count = nullptr;
+        if (h->tlas_capacity > 0) { // the level lists of a top level this copy builds itself (tlas_build.h)
+            if ((rc2 = dev_alloc(h, &sc.tlas_list, (size_t)h->tlas_capacity, &h->scene_allocs))) return rc2;
+            if ((rc2 = dev_alloc(h, &sc.tlas_levels, RP_REFIT_LEVELS, &h->scene_allocs))) return rc2;
+            if ((rc2 = dev_alloc(h, &sc.tlas_count, 1, &h->scene_allocs))) return rc2;
+        }
         if (!h->has_dynamic) return RPTR_OK;
         if ((rc2 = dev_alloc(h, &sc.blas_list, h->h_nodes.size(), &h->scene_allocs))) return rc2;
         if ((rc2 = dev_alloc(h, &sc.blas_levels, h->meshes.size() * RP_REFIT_LEVELS, &h->scene_allocs))) return rc2;
@@ -450,6 +482,18 @@ int rptr_hip_set_scene(rptr_hip_t *h, const RptrSceneDesc *s) {
         return RPTR_OK;
     };
     if ((rc = make_refit_tables(h->master))) return rc;
+    {   // the table rptr_hip_update_instances stages into: per instance object_to_world + world_to_object, as the records hold them
+        std::vector<float> xf((size_t)24 * s->num_instances);
+        for (uint32_t i = 0; i < s->num_instances; ++i) {
+            memcpy(&xf[(size_t)24 * i], s->instances[i].transform, 48);
+            invert_affine(s->instances[i].transform, &xf[(size_t)24 * i + 12]);
+        }
+        if ((rc = dev_alloc(h, &h->master.inst_xf, xf.size(), &h->scene_allocs))) return rc;
+        if (!xf.empty()) HIP_TRY(h, hipMemcpy(h->master.inst_xf, xf.data(), xf.size() * sizeof(float), hipMemcpyHostToDevice));
+        if ((rc = dev_alloc(h, &h->d_inst_rejected, 1, &h->scene_allocs))) return rc;
+        HIP_TRY(h, hipMemset(h->d_inst_rejected, 0, sizeof(uint32_t)));
+    }
+    h->host_insts_stale = false;
     h->host_bvh_stale = false;
     h->master_refit_pending = false;
     if ((rc = dev_alloc(h, &h->master.node_box, (size_t)6 * h->h_nodes.size(), &h->scene_allocs))) return rc;
@@ -494,30 +538,47 @@ int rptr_hip_set_scene(rptr_hip_t *h, const RptrSceneDesc *s) {
     }
     h->num_lights = (int)s->num_lights;
     h->num_materials = (int)s->num_materials;
-    // ---- dynamic scene + frames in flight: every frame context gets its own set of what a refit rewrites
+    // ---- dynamic scene (meshes that deform, or instances that move: RPTR_MESH_INSTANCES_MOVE) + frames in flight: every frame context
+    // gets its own set of what a refit rewrites
     for (SceneCopy &sc : h->ctx_scene) release_scene_copy_host(sc);
     h->ctx_scene.clear();
-    if (h->has_dynamic && h->ctx.size() > 1) {
+    if ((h->has_dynamic || h->tlas_capacity > 0) && h->ctx.size() > 1) {
         h->ctx_scene.resize(h->ctx.size());
         for (SceneCopy &sc : h->ctx_scene) {
             sc.dscene = h->master.dscene;
             sc.mesh_dirty.assign(s->num_meshes, 0);
             sc.dynpos.assign(s->num_geometries, nullptr);
             sc.mesh_dyn.assign(s->num_meshes, nullptr);
+            // (the node array is ONE array, top level first: a copy holds all of it, 88 bytes per node with its box. Triangles, shading
+            // records and triangle bounds only change when a mesh deforms: a scene whose instances move and nothing else shares the master's)
             if ((rc = dev_alloc(h, &sc.nodes, h->h_nodes.size(), &h->scene_allocs))) return rc;
-            if ((rc = dev_alloc(h, &sc.tris, h->h_tris.size() + 2, &h->scene_allocs))) return rc;
-            if ((rc = dev_alloc(h, &sc.shade, h->h_tris.size() + 1, &h->scene_allocs))) return rc;
-            if (!h->h_tris.empty()) HIP_TRY(h, hipMemcpy(sc.shade, h->master.shade, h->h_tris.size() * sizeof(RpShadeTri), hipMemcpyDeviceToDevice));
+            if (h->has_dynamic) {
+                if ((rc = dev_alloc(h, &sc.tris, h->h_tris.size() + 2, &h->scene_allocs))) return rc;
+                if ((rc = dev_alloc(h, &sc.shade, h->h_tris.size() + 1, &h->scene_allocs))) return rc;
+                if (!h->h_tris.empty()) HIP_TRY(h, hipMemcpy(sc.shade, h->master.shade, h->h_tris.size() * sizeof(RpShadeTri), hipMemcpyDeviceToDevice));
+                if ((rc = dev_alloc(h, &sc.tri_box, (size_t)6 * h->h_tris.size(), &h->scene_allocs))) return rc;
+            } else {
+                sc.tris = h->master.tris;
+                sc.shade = h->master.shade;
+                sc.tri_box = nullptr;
+            }
             if ((rc = dev_alloc(h, &sc.node_box, (size_t)6 * h->h_nodes.size(), &h->scene_allocs))) return rc;
-            if ((rc = dev_alloc(h, &sc.tri_box, (size_t)6 * h->h_tris.size(), &h->scene_allocs))) return rc;
             if ((rc = dev_alloc(h, &sc.inst_box, (size_t)6 * h->h_insts.size(), &h->scene_allocs))) return rc;
+            {   // its own instance records and staged transforms: a frame still rendering never sees an instance move
+                RptrBvhInstance *ci = nullptr;
+                if ((rc = dev_alloc(h, &ci, h->h_insts.size(), &h->scene_allocs))) return rc;
+                if (!h->h_insts.empty()) HIP_TRY(h, hipMemcpy(ci, d_insts, h->h_insts.size() * sizeof(RptrBvhInstance), hipMemcpyDeviceToDevice));
+                sc.dscene.insts = ci;
+                if ((rc = dev_alloc(h, &sc.inst_xf, (size_t)24 * s->num_instances, &h->scene_allocs))) return rc;
+                if (s->num_instances) HIP_TRY(h, hipMemcpy(sc.inst_xf, h->master.inst_xf, (size_t)96 * s->num_instances, hipMemcpyDeviceToDevice));
+            }
             HIP_TRY(h, hipMemcpy(sc.nodes, d_nodes, h->h_nodes.size() * sizeof(RptrBvh4Node), hipMemcpyDeviceToDevice));
-            if (!h->h_tris.empty()) HIP_TRY(h, hipMemcpy(sc.tris, d_tris, h->h_tris.size() * sizeof(RptrBvhTri), hipMemcpyDeviceToDevice));
+            if (h->has_dynamic && !h->h_tris.empty()) HIP_TRY(h, hipMemcpy(sc.tris, d_tris, h->h_tris.size() * sizeof(RptrBvhTri), hipMemcpyDeviceToDevice));
             HIP_TRY(h, hipMemcpy(sc.node_box, h->master.node_box, h->h_node_box.size() * 24, hipMemcpyDeviceToDevice));
             std::vector<RpGeomRecord> cgeoms = geoms; // same records, pointing at this copy's float positions
             for (uint32_t m = 0; m < s->num_meshes; ++m) {
                 const RptrMeshDesc &mesh = s->meshes[m];
-                if (!mesh.dynamic) continue;
+                if (!(mesh.dynamic & kMeshDeforms)) continue;
                 std::vector<const float *> table(mesh.num_geometries, nullptr);
                 for (uint32_t j = 0; j < mesh.num_geometries; ++j) {
                     const uint32_t gi = mesh.first_geometry + j;
@@ -587,6 +648,61 @@ int rptr_hip_update_vertices_device(rptr_hip_t *h, uint32_t geometry, const floa
     return update_vertices_common(h, geometry, device_xyz, num_vertices, true);
 }
 
+// ---- moving instances: new object-to-world transforms for scene instances [first, first + count), staged for the next refit
+static int update_instances_common(rptr_hip_t *h, uint32_t first, uint32_t count, const float *xf12, bool device_src) {
+    if (!h) return fail(nullptr, RPTR_E_INVALID, "NULL handle");
+    if (!h->have_scene) return fail(h, RPTR_E_INVALID, "update_instances before set_scene");
+    if ((uint64_t)first + count > h->num_instances)
+        return fail(h, RPTR_E_INVALID, "instances [%u, +%u) are outside the scene's %u instances", first, count, h->num_instances);
+    if (count == 0) return RPTR_OK;
+    if (!xf12) return fail(h, RPTR_E_INVALID, "NULL transforms");
+    for (uint32_t i = first; i < first + count; ++i) {
+        if (!h->inst_movable[i])
+            return fail(h, RPTR_E_INVALID, "instance %u is baked into the flattened world-space tree and cannot move: set RPTR_MESH_INSTANCES_MOVE in "
+                                           "RptrMeshDesc.dynamic of its mesh (or option flatten = 0) before set_scene", i);
+        if (h->inst_emissive[i])
+            return fail(h, RPTR_E_UNSUPPORTED, "instance %u uses an emissive material: RptrSceneDesc.lights holds its triangles in world space and would go stale", i);
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (device_src)
+        hipLaunchKernelGGL(rp_k_stage_instance_transforms, dim3(grid_for(h, count)), dim3(256), 0, h->stream, xf12, first, count, h->master.inst_xf, h->d_inst_rejected);
+    else {
+        std::vector<float> rows((size_t)24 * count);
+        for (uint32_t i = 0; i < count; ++i) {
+            const float *m = xf12 + 12ull * i;
+            float *row = &rows[(size_t)24 * i];
+            memcpy(row, m, 48);
+            invert_affine(m, row + 12);
+            bool ok = true;
+            for (int k = 0; k < 24; ++k) ok = ok && std::isfinite(row[k]); // (det == 0: 1 / det is infinite)
+            if (!ok) return fail(h, RPTR_E_INVALID, "transform %u (instance %u) is not finite or singular", i, first + i);
+        }
+        HIP_TRY(h, hipMemcpyAsync(h->master.inst_xf + 24ull * first, rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream)); // (pageable staging: the copy must be over before `rows` goes)
+    }
+    HIP_TRY(h, hipGetLastError());
+    h->inst_version++;
+    h->vertex_updates++; // (one counter for everything a refit has to pick up: rptr_hip_refit with frame contexts that own their sets)
+    return RPTR_OK;
+}
+int rptr_hip_update_instances(rptr_hip_t *h, uint32_t first_instance, uint32_t count, const float *transforms12) {
+    return update_instances_common(h, first_instance, count, transforms12, false);
+}
+int rptr_hip_update_instances_device(rptr_hip_t *h, uint32_t first_instance, uint32_t count, const float *device_transforms12) {
+    return update_instances_common(h, first_instance, count, device_transforms12, true);
+}
+int rptr_hip_set_tlas_policy(rptr_hip_t *h, int mode) {
+    if (!h) return fail(nullptr, RPTR_E_INVALID, "NULL handle");
+    if (mode != RPTR_TLAS_REBUILD && mode != RPTR_TLAS_REFIT) return fail(h, RPTR_E_INVALID, "unknown top-level policy %d (0 = REBUILD, 1 = REFIT)", mode);
+    h->tlas_policy = mode;
+    return RPTR_OK;
+}
+int rptr_hip_tlas_rebuild_count(const rptr_hip_t *h, uint64_t *out_rebuilds) {
+    if (!h || !out_rebuilds) return fail(nullptr, RPTR_E_INVALID, "NULL argument");
+    *out_rebuilds = h->tlas_rebuilds;
+    return RPTR_OK;
+}
+
 // ≙ BLAS update (VK_BUILD_ACCELERATION_STRUCTURE_MODE_UPDATE) of the dirty dynamic meshes + TLAS refit
 // (render_vulkan.cpp:1323-1354, executed at the top of draw_frame :2165): topology is kept, triangles and all
 // boxes are recomputed on the device, level by level from the leaves up.
@@ -621,7 +737,7 @@ static void refit_mesh_levels(rptr_hip *h, SceneCopy &sc, size_t m, hipStream_t 
             work = sc.host_levels[m][(size_t)slot].y - sc.host_levels[m][(size_t)slot].x;
             if (!work) continue;
         }
-        hipLaunchKernelGGL(rp_k_refit_level, dim3(grid_for(h, work, 4)), dim3(256), 0, st, sc.nodes, sc.node_box, sc.tri_box, sc.blas_list, dev_levels + slot);
+        hipLaunchKernelGGL(rp_k_refit_level, dim3(grid_for(h, work, 4)), dim3(256), 0, st, sc.nodes, sc.node_box, sc.tri_box, nullptr, sc.blas_list, dev_levels + slot);
     }
     RptrBvhInstance *insts = const_cast<RptrBvhInstance *>(sc.dscene.insts);
     hipLaunchKernelGGL(rp_k_refit_top, dim3(1), dim3(1024), 0, st, sc.nodes, sc.node_box, sc.tri_box, sc.inst_box, sc.blas_list,
@@ -629,16 +745,15 @@ static void refit_mesh_levels(rptr_hip *h, SceneCopy &sc, size_t m, hipStream_t 
                        with_top ? (uint32_t)h->num_tlas_insts : 0u);
 }
 
-// device-side rebuild of the bottom-level tree of dynamic mesh m of one scene copy (lbvh.h), on stream `st`. The triangles of the mesh
-// (current order) must hold the new vertices already (rp_k_refit_tris). Ends with the refit that gives the new topology its boxes.
-static int lbvh_rebuild(rptr_hip *h, SceneCopy &sc, size_t m, hipStream_t st, bool with_top) {
-    const MeshRt &mr = h->meshes[m];
-    const uint32_t n = (uint32_t)mr.tri_count;
+// work space of the device-side builds of one scene copy (lbvh.h RpLbvhScratch), for n primitives
+static int lbvh_scratch(rptr_hip *h, SceneCopy &sc, size_t n, hipStream_t st) {
     RpLbvhScratch &w = sc.scratch;
-    if (w.capacity < (size_t)std::max<uint32_t>(n, 2)) { // first rebuild (of a mesh this large): work space for the largest dynamic mesh
-        size_t cap = 2;
+    if (w.capacity < std::max<size_t>(n, 2)) { // first rebuild (of a set this large): work space for the largest dynamic mesh / the top level's records
+        size_t cap = 2, cap_tris = 0; // (cap_tris: the triangle copies of the gather -- a top-level build gathers nothing)
         for (const MeshRt &x : h->meshes)
-            if (x.dynamic) cap = std::max<size_t>(cap, (size_t)x.tri_count);
+            if (x.dynamic) cap_tris = std::max<size_t>(cap_tris, (size_t)x.tri_count);
+        cap = std::max(cap, cap_tris);
+        if (h->tlas_capacity > 0) cap = std::max<size_t>(cap, (size_t)h->num_tlas_insts);
         // the work space is allocated into a local record and committed as a whole: a failure half way frees what it got (the rebuild is
         // retried with every refit, and a retry must not leak the earlier attempt's buffers while the device is short of memory)
         RpLbvhScratch t = w;
@@ -662,8 +777,8 @@ static int lbvh_rebuild(rptr_hip *h, SceneCopy &sc, size_t m, hipStream_t st, bo
             if ((rc = alloc(p, cap))) return fail_alloc(rc);
         for (uint32_t **p : {&t.flag, &t.slot, &t.depth4})
             if ((rc = alloc(p, cap))) return fail_alloc(rc);
-        if ((rc = alloc(&t.level_hist, RP_REFIT_LEVELS)) || (rc = alloc(&t.level_cursor, RP_REFIT_LEVELS)) || (rc = alloc(&t.tri_copy, cap)) ||
-            (rc = alloc(&t.tribox_copy, 6 * cap)) || (rc = alloc(&t.bounds, 8)))
+        if ((rc = alloc(&t.level_hist, RP_REFIT_LEVELS)) || (rc = alloc(&t.level_cursor, RP_REFIT_LEVELS)) || (rc = alloc(&t.tri_copy, cap_tris)) ||
+            (rc = alloc(&t.tribox_copy, 6 * cap_tris)) || (rc = alloc(&t.bounds, 8)))
             return fail_alloc(rc);
         size_t sort_bytes = 0, scan_bytes = 0;
         (void)hipcub::DeviceRadixSort::SortKeys(nullptr, sort_bytes, t.keys_a, t.keys_b, (int)cap, 0, 64, st);
@@ -678,6 +793,19 @@ static int lbvh_rebuild(rptr_hip *h, SceneCopy &sc, size_t m, hipStream_t st, bo
         }
         w = t;
     }
+    return RPTR_OK;
+}
+
+// device-side rebuild of the bottom-level tree of dynamic mesh m of one scene copy (lbvh.h), on stream `st`. The triangles of the mesh
+// (current order) must hold the new vertices already (rp_k_refit_tris). Ends with the refit that gives the new topology its boxes.
+static int lbvh_rebuild(rptr_hip *h, SceneCopy &sc, size_t m, hipStream_t st, bool with_top) {
+    const MeshRt &mr = h->meshes[m];
+    const uint32_t n = (uint32_t)mr.tri_count;
+    {
+        const int rc = lbvh_scratch(h, sc, n, st);
+        if (rc) return rc;
+    }
+    RpLbvhScratch &w = sc.scratch;
     RptrBvhTri *tris = sc.tris + mr.tri_base;
     float *tri_box = sc.tri_box + 6ull * mr.tri_base;
     const int g = grid_for(h, n);
@@ -686,24 +814,24 @@ static int lbvh_rebuild(rptr_hip *h, SceneCopy &sc, size_t m, hipStream_t st, bo
         hipLaunchKernelGGL(rp_k_lbvh_bounds, dim3(g), dim3(256), 0, st, tri_box, n, w.bounds);
         int index_bits = 1;
         while ((1ull << index_bits) < (unsigned long long)n) ++index_bits;
-        hipLaunchKernelGGL(rp_k_lbvh_keys, dim3(g), dim3(256), 0, st, tri_box, n, w.bounds, w.keys_a, index_bits);
+        hipLaunchKernelGGL(rp_k_lbvh_keys, dim3(g), dim3(256), 0, st, tri_box, n, w.bounds, w.keys_a, index_bits, 21);
         size_t bytes = w.cub_bytes;
         HIP_TRY(h, hipcub::DeviceRadixSort::SortKeys(w.cub_tmp, bytes, w.keys_a, w.keys_b, (int)n, 0, 64, st));
         hipLaunchKernelGGL(rp_k_lbvh_hierarchy, dim3(g), dim3(256), 0, st, w.keys_b, (int)n, w.left, w.right, w.parent, w.first, w.last);
         HIP_TRY(h, hipMemcpyAsync(w.tri_copy, tris, (size_t)n * sizeof(RptrBvhTri), hipMemcpyDeviceToDevice, st));
         HIP_TRY(h, hipMemcpyAsync(w.tribox_copy, tri_box, (size_t)n * 24, hipMemcpyDeviceToDevice, st));
         hipLaunchKernelGGL(rp_k_lbvh_gather, dim3(g), dim3(256), 0, st, w.keys_b, n, w.tri_copy, w.tribox_copy, tris, tri_box, (1ull << index_bits) - 1ull);
-        hipLaunchKernelGGL(rp_k_lbvh_flags, dim3(g), dim3(256), 0, st, (int)n, w.parent, w.first, w.last, w.flag, w.depth4);
+        hipLaunchKernelGGL(rp_k_lbvh_flags, dim3(g), dim3(256), 0, st, (int)n, w.parent, w.first, w.last, w.flag, w.depth4, RP_LBVH_LEAF_TRIS);
         bytes = w.cub_bytes;
         HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(w.cub_tmp, bytes, w.flag, w.slot, (int)n - 1, st));
     }
     HIP_TRY(h, hipMemsetAsync(w.level_hist, 0, RP_REFIT_LEVELS * sizeof(uint32_t), st));
     hipLaunchKernelGGL(rp_k_lbvh_emit, dim3(g), dim3(256), 0, st, (int)n, w.left, w.right, w.first, w.last, w.flag, w.slot, w.depth4, mr.node_base, mr.tri_base, sc.nodes,
-                       w.level_hist, sc.mesh_count + m);
+                       w.level_hist, sc.mesh_count + m, RpLbvhLeaves{RP_LBVH_LEAF_TRIS, nullptr, 0ull});
     uint2 *dev_levels = sc.blas_levels + m * RP_REFIT_LEVELS;
     hipLaunchKernelGGL(rp_k_lbvh_level_scan, dim3(1), dim3(64), 0, st, w.level_hist, (uint32_t)mr.node_base, dev_levels, w.level_cursor);
     hipLaunchKernelGGL(rp_k_lbvh_level_scatter, dim3(grid_for(h, (size_t)mr.node_capacity)), dim3(256), 0, st, sc.nodes, mr.node_base, sc.mesh_count + m, w.level_cursor,
-                       sc.blas_list);
+                       sc.blas_list, 0u);
     // the host learns the level sizes when this copy has arrived; until then a refit launches every possible level
     sc.levels_known[m] = 0;
     HIP_TRY(h, hipMemcpyAsync(sc.pinned_levels[m], dev_levels, RP_REFIT_LEVELS * sizeof(uint2), hipMemcpyDeviceToHost, st));
@@ -715,12 +843,68 @@ static int lbvh_rebuild(rptr_hip *h, SceneCopy &sc, size_t m, hipStream_t st, bo
     return RPTR_OK;
 }
 
+// the top level of one scene copy by ITS OWN level lists (a device-built top level): boxes and encoding, deepest level first. The
+// instance bounds must be current. Up to kTlasSingleBlock records the levels run in the one block of rp_k_refit_top (a block barrier per
+// level instead of a launch); above it every level gets a launch. The break-even was ESTIMATED, not measured: 40 dependent launches cost
+// about 40 x 5 us, one block of 1024 threads refits about 1000 nodes per pass, so the block wins while the tree has a few thousand nodes.
+static const int kTlasSingleBlock = 8192;
+static void tlas_refit_own(rptr_hip *h, SceneCopy &sc, hipStream_t st) {
+    RptrBvhInstance *insts = const_cast<RptrBvhInstance *>(sc.dscene.insts);
+    if (h->num_tlas_insts <= kTlasSingleBlock)
+        hipLaunchKernelGGL(rp_k_refit_top, dim3(1), dim3(1024), 0, st, sc.nodes, sc.node_box, sc.tri_box, sc.inst_box, sc.blas_list, sc.blas_levels, 0, sc.tlas_list,
+                           sc.tlas_levels, RP_REFIT_LEVELS, insts, 0u);
+    else
+        for (int slot = 0; slot < RP_REFIT_LEVELS; ++slot)
+            hipLaunchKernelGGL(rp_k_refit_level, dim3(grid_for(h, (size_t)h->tlas_capacity, 4)), dim3(256), 0, st, sc.nodes, sc.node_box, sc.tri_box, sc.inst_box, sc.tlas_list,
+                               sc.tlas_levels + slot);
+}
+
+// device-side rebuild of the top level of one scene copy over its instance records (tlas_build.h), on stream `st`. The instance bounds
+// (sc.inst_box) must be current. Nodes [0, tlas_capacity) are rewritten; the records stay where they are.
+static int tlas_rebuild(rptr_hip *h, SceneCopy &sc, hipStream_t st) {
+    const uint32_t n = (uint32_t)h->num_tlas_insts;
+    if ((size_t)std::max<uint32_t>(n, 1) > (size_t)h->tlas_capacity) return fail(h, RPTR_E_INVALID, "no top-level capacity for %u records", n);
+    {
+        const int rc = lbvh_scratch(h, sc, n, st);
+        if (rc) return rc;
+    }
+    RpLbvhScratch &w = sc.scratch;
+    const int g = grid_for(h, n);
+    int index_bits = 1;
+    while ((1ull << index_bits) < (unsigned long long)n) ++index_bits;
+    if (n >= 2) {
+        hipLaunchKernelGGL(rp_k_lbvh_reset, dim3(1), dim3(64), 0, st, w.bounds);
+        hipLaunchKernelGGL(rp_k_lbvh_bounds, dim3(g), dim3(256), 0, st, sc.inst_box, n, w.bounds);
+        hipLaunchKernelGGL(rp_k_lbvh_keys, dim3(g), dim3(256), 0, st, sc.inst_box, n, w.bounds, w.keys_a, index_bits, RP_TLAS_AXIS_BITS);
+        size_t bytes = w.cub_bytes;
+        HIP_TRY(h, hipcub::DeviceRadixSort::SortKeys(w.cub_tmp, bytes, w.keys_a, w.keys_b, (int)n, 0, 64, st));
+        hipLaunchKernelGGL(rp_k_lbvh_hierarchy, dim3(g), dim3(256), 0, st, w.keys_b, (int)n, w.left, w.right, w.parent, w.first, w.last);
+        hipLaunchKernelGGL(rp_k_lbvh_flags, dim3(g), dim3(256), 0, st, (int)n, w.parent, w.first, w.last, w.flag, w.depth4, 1);
+        bytes = w.cub_bytes;
+        HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(w.cub_tmp, bytes, w.flag, w.slot, (int)n - 1, st));
+    }
+    HIP_TRY(h, hipMemsetAsync(w.level_hist, 0, RP_REFIT_LEVELS * sizeof(uint32_t), st));
+    hipLaunchKernelGGL(rp_k_tlas_clear, dim3(grid_for(h, (size_t)h->tlas_capacity)), dim3(256), 0, st, sc.nodes, sc.node_box, (uint32_t)h->tlas_capacity);
+    hipLaunchKernelGGL(rp_k_lbvh_emit, dim3(g), dim3(256), 0, st, (int)n, w.left, w.right, w.first, w.last, w.flag, w.slot, w.depth4, 0, 0, sc.nodes, w.level_hist,
+                       sc.tlas_count, RpLbvhLeaves{1, n >= 2 ? w.keys_b : nullptr, (1ull << index_bits) - 1ull});
+    hipLaunchKernelGGL(rp_k_lbvh_level_scan, dim3(1), dim3(64), 0, st, w.level_hist, 0u, sc.tlas_levels, w.level_cursor);
+    hipLaunchKernelGGL(rp_k_lbvh_level_scatter, dim3(grid_for(h, (size_t)h->tlas_capacity)), dim3(256), 0, st, sc.nodes, 0, sc.tlas_count, w.level_cursor, sc.tlas_list,
+                       0x80000000u);
+    sc.tlas_rebuilt = true;
+    tlas_refit_own(h, sc, st); // (rp_refit_node rewrites the whole node: the depth the emit kernel parked in its padding goes)
+    HIP_TRY(h, hipGetLastError());
+    h->tlas_rebuilds++;
+    return RPTR_OK;
+}
+
 // refits one copy of the mutable scene on stream `st`; all_dynamic: treat every dynamic mesh as changed. A mesh whose tree is older
 // than the rebuild the policy asked for (rptr_hip_refit) is rebuilt instead of refitted. A rebuild that cannot start (no memory for its
 // work space) is reported through *err -- the error text is in the handle -- and the mesh is refitted on its old topology instead, so
 // that its boxes always match the new vertices; the rebuild is tried again with the next refit.
 static bool refit_scene_copy(rptr_hip *h, SceneCopy &sc, bool all_dynamic, hipStream_t st, int *err) {
     bool any = all_dynamic && h->has_dynamic;
+    const bool insts_moved = sc.inst_version != h->inst_version;
+    any = any || insts_moved;
     for (size_t m = 0; m < h->meshes.size(); ++m) any = any || sc.mesh_dirty[m] == 1 || (h->meshes[m].dynamic && sc.built_epoch[m] != h->rebuild_epoch[m]);
     if (!any) return false;
     std::vector<size_t> todo;
@@ -731,12 +915,22 @@ static bool refit_scene_copy(rptr_hip *h, SceneCopy &sc, bool all_dynamic, hipSt
         if (!all_dynamic && !sc.mesh_dirty[m] && !rebuild) continue; // 1 = new vertices, 2 = dynamic but its triangle bounds were never written
         todo.push_back(m);
     }
+    // staged instance transforms go into this copy's records first: everything below bounds the records from them
+    if (insts_moved) {
+        hipLaunchKernelGGL(rp_k_update_instance_records, dim3(grid_for(h, h->h_insts.size())), dim3(256), 0, st, const_cast<RptrBvhInstance *>(sc.dscene.insts),
+                           (uint32_t)h->h_insts.size(), sc.inst_xf, h->num_instances);
+        sc.inst_version = h->inst_version;
+    }
+    // moved instances under RPTR_TLAS_REBUILD get a new top level (where set_scene reserved room for one); a top level that was rebuilt
+    // before is refitted by its own level lists, not the host's
+    const bool rebuild_top = insts_moved && h->tlas_policy == RPTR_TLAS_REBUILD && h->tlas_capacity > 0 && h->num_tlas_insts > 0;
+    const bool own_top = rebuild_top || sc.tlas_rebuilt;
     // the instance bounds and the top level ride in the single-block launch of the last mesh when they are small
     bool top_done = false;
     for (size_t k = 0; k < todo.size(); ++k) {
         const size_t m = todo[k];
         const MeshRt &mr = h->meshes[m];
-        const bool with_top = h->refit_top_all && k + 1 == todo.size();
+        const bool with_top = h->refit_top_all && !own_top && k + 1 == todo.size();
         if (mr.tri_count)
             hipLaunchKernelGGL(rp_k_refit_tris, dim3(grid_for(h, (size_t)mr.tri_count)), dim3(256), 0, st, sc.tris, sc.tri_box, sc.shade, (uint32_t)mr.tri_base,
                                (uint32_t)mr.tri_count, sc.mesh_dyn[m]);
@@ -753,6 +947,18 @@ static bool refit_scene_copy(rptr_hip *h, SceneCopy &sc, bool all_dynamic, hipSt
         } else
             refit_mesh_levels(h, sc, m, st, with_top);
         top_done = top_done || with_top;
+    }
+    if (!top_done && own_top) {
+        RptrBvhInstance *insts = const_cast<RptrBvhInstance *>(sc.dscene.insts);
+        const uint32_t ni = (uint32_t)h->num_tlas_insts;
+        if (ni) hipLaunchKernelGGL(rp_k_refit_instances, dim3(grid_for(h, ni)), dim3(256), 0, st, sc.node_box, insts, sc.inst_box, ni);
+        int rc = rebuild_top ? tlas_rebuild(h, sc, st) : RPTR_E_INVALID;
+        if (rebuild_top && rc != RPTR_OK && err && *err == RPTR_OK) *err = rc; // (no memory for the work space: refitted instead, tried again next time)
+        if (rc == RPTR_OK) top_done = true;
+        else if (sc.tlas_rebuilt) {
+            tlas_refit_own(h, sc, st);
+            top_done = true;
+        }
     }
     if (!top_done) { // instance bounds, then the top level
         RptrBvhInstance *insts = const_cast<RptrBvhInstance *>(sc.dscene.insts);
@@ -813,6 +1019,7 @@ int rptr_hip_refit(rptr_hip_t *h) {
             h->vertex_updates_refitted = h->vertex_updates;
             h->master_refit_pending = true;
             h->host_bvh_stale = true;
+            h->host_insts_stale = true;
             h->refit_version++;
         }
         return RPTR_OK;
@@ -821,6 +1028,7 @@ int rptr_hip_refit(rptr_hip_t *h) {
     if (refit_scene_copy(h, h->master, false, h->stream, &err)) {
         HIP_TRY(h, hipGetLastError());
         h->host_bvh_stale = true;
+        h->host_insts_stale = true;
         h->refit_version++; // the frame contexts' own sets follow when their next frame is submitted
         h->master.version = h->refit_version;
     }

@@ -49,6 +49,14 @@ struct SceneCopy {
     std::vector<char> device_built;         // per mesh: its tree was rebuilt on the device (node count lives in mesh_count)
     std::vector<uint64_t> built_epoch;      // per mesh: rptr_hip.rebuild_epoch this copy's tree reflects
     RpLbvhScratch scratch;                  // work space of device-side rebuilds (allocated at the first one)
+    // moving instances (tlas_build.h): the staged transforms this copy reads (the master set: the table rptr_hip_update_instances writes),
+    // the instance update it reflects, and -- once the top level was rebuilt on the device -- the level lists of ITS top level
+    float *inst_xf = nullptr;
+    uint64_t inst_version = 0;              // rptr_hip.inst_version this copy's records reflect
+    uint32_t *tlas_list = nullptr;          // top-level nodes (bit 31 set) by depth, deepest first (scenes with reserved top-level capacity)
+    uint2 *tlas_levels = nullptr;           // RP_REFIT_LEVELS [begin, end) pairs into it
+    int *tlas_count = nullptr;              // nodes of the rebuilt top level
+    bool tlas_rebuilt = false;              // the top level is a device-built one: refits go by tlas_list / tlas_levels
 };
 
 struct Span {
@@ -302,6 +310,16 @@ struct rptr_hip {
     bool host_bvh_stale = false;
     uint64_t vertex_updates = 0, vertex_updates_refitted = 0;
     bool master_refit_pending = false; // rptr_hip_refit with frame contexts that own their sets: the master tree is refitted on demand
+    // moving instances (rptr_hip_update_instances, tlas_build.h)
+    uint32_t num_instances = 0;             // instances of the scene
+    std::vector<char> inst_movable;         // per scene instance: it has top-level records of its own (not baked into the flat tree)
+    std::vector<char> inst_emissive;        // per scene instance: its parameterized mesh uses an emissive material (its light triangles would go stale)
+    uint64_t inst_version = 0;              // bumped by every update_instances call that staged something
+    int tlas_policy = RPTR_TLAS_REBUILD;    // rptr_hip_set_tlas_policy
+    int tlas_capacity = 0;                  // top-level nodes set_scene reserved for device-side rebuilds (0: none, RPTR_MESH_INSTANCES_MOVE was not set)
+    uint64_t tlas_rebuilds = 0;             // device-side rebuilds of the top level so far (all scene copies)
+    bool host_insts_stale = false;          // the device's instance records are newer than h_insts
+    uint32_t *d_inst_rejected = nullptr;    // matrices of device-source updates that were not finite or singular and were skipped (this scene)
 
     // device buffers (frame sized)
     std::vector<FrameCtx> ctx;      // frames in flight (RptrCreateInfo.frames_in_flight, at least 1)

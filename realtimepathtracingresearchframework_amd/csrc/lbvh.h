@@ -94,9 +94,11 @@ RP_DEV unsigned long long rp_expand_bits21(uint32_t v) { // 21 bits -> every thi
 }
 // 2. keys
 // key = Morton code of the centroid in the high bits | triangle position in the low `index_bits` bits (unique keys). The code gets
-// all the bits the index leaves: 14 per axis for a million triangles
-__global__ __launch_bounds__(256) void rp_k_lbvh_keys(const float *tri_box, uint32_t n, const uint32_t *bounds, unsigned long long *keys, int index_bits) {
-    const int axis_bits = min(21, (64 - index_bits) / 3);
+// all the bits the index leaves: 14 per axis for a million triangles. max_axis_bits caps them (21 = no cap): the key width bounds the depth
+// of the radix tree, which is how the top-level build (tlas_build.h) keeps its promise about the traversal stack
+__global__ __launch_bounds__(256) void rp_k_lbvh_keys(const float *tri_box, uint32_t n, const uint32_t *bounds, unsigned long long *keys, int index_bits,
+                                                      int max_axis_bits) {
+    const int axis_bits = min(max_axis_bits, (64 - index_bits) / 3);
     const float cells = (float)((1u << axis_bits) - 1u);
     // CUBIC cells: one scale for the three axes. Scaling every axis to the full range makes the curve split a flat mesh along its thin
     // axis at every third level (a height field by height: children that overlap completely in plan).
@@ -168,9 +170,10 @@ __global__ __launch_bounds__(256) void rp_k_lbvh_gather(const unsigned long long
     }
 }
 // 6. which binary inner nodes become 4-wide nodes: inner (range > leaf size) and of even depth. depth4[i] = depth / 2 for those.
-__global__ __launch_bounds__(256) void rp_k_lbvh_flags(int n, const int *parent, const int *first, const int *last, uint32_t *flag, uint32_t *depth4) {
+// leaf_max: primitives per leaf (RP_LBVH_LEAF_TRIS for a mesh's triangles, 1 for the instance records of the top level)
+__global__ __launch_bounds__(256) void rp_k_lbvh_flags(int n, const int *parent, const int *first, const int *last, uint32_t *flag, uint32_t *depth4, int leaf_max) {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n - 1; i += gridDim.x * blockDim.x) {
-        const bool inner = last[i] - first[i] + 1 > RP_LBVH_LEAF_TRIS;
+        const bool inner = last[i] - first[i] + 1 > leaf_max;
         int depth = 0;
         for (int p = parent[i]; p >= 0; p = parent[p]) ++depth;
         const bool node = (inner && (depth & 1) == 0) || i == 0; // (the root is always a node, also of a mesh of <= RP_LBVH_LEAF_TRIS triangles)
@@ -181,15 +184,26 @@ __global__ __launch_bounds__(256) void rp_k_lbvh_flags(int n, const int *parent,
 // 7. topology of one 4-wide node per flagged binary node: child references only -- boxes and encoding come from the refit that
 // follows (rp_refit_node: leaf children from the triangle bounds, inner children from the exact float bounds of the level below).
 // A binary child that is a leaf of the binary tree, or an inner node with a small range, is a leaf of the 4-wide tree.
-RP_DEV int32_t rp_lbvh_child_ref(int c, const int *first, const int *last, const uint32_t *slot, int node_base, int tri_base) {
-    if (c < 0) return RPTR_BVH_LEAF(tri_base + ~c, 1);
+// What a leaf names: the sorted positions [f, l] of primitives that were gathered into sorted order (a mesh's triangles), or -- `named`
+// set, one primitive per leaf -- the primitive the sorted key itself carries in its index bits: the primitives stay where they are
+// (the instance records of the top level: their order is part of what a host sees through the export).
+struct RpLbvhLeaves {
+    int leaf_max;                    // primitives per leaf
+    const unsigned long long *named; // sorted keys, or NULL
+    unsigned long long index_mask;
+};
+RP_DEV int32_t rp_lbvh_leaf_ref(int f, int count, int tri_base, const RpLbvhLeaves &lv) {
+    return RPTR_BVH_LEAF(tri_base + (lv.named ? (int)(lv.named[f] & lv.index_mask) : f), count);
+}
+RP_DEV int32_t rp_lbvh_child_ref(int c, const int *first, const int *last, const uint32_t *slot, int node_base, int tri_base, const RpLbvhLeaves &lv) {
+    if (c < 0) return rp_lbvh_leaf_ref(~c, 1, tri_base, lv);
     const int f = first[c], l = last[c];
-    return l - f + 1 > RP_LBVH_LEAF_TRIS ? node_base + (int)slot[c] : RPTR_BVH_LEAF(tri_base + f, l - f + 1);
+    return l - f + 1 > lv.leaf_max ? node_base + (int)slot[c] : rp_lbvh_leaf_ref(f, l - f + 1, tri_base, lv);
 }
 // levels: slot k of the level table holds the nodes of depth RP_REFIT_LEVELS - 1 - k, so that ascending k = deepest first
 __global__ __launch_bounds__(256) void rp_k_lbvh_emit(int n, const int *left, const int *right, const int *first, const int *last, const uint32_t *flag,
                                                       const uint32_t *slot, const uint32_t *depth4, int node_base, int tri_base, RptrBvh4Node *nodes,
-                                                      uint32_t *level_hist, int *out_count) {
+                                                      uint32_t *level_hist, int *out_count, RpLbvhLeaves lv) {
     __shared__ uint32_t s_hist[RP_REFIT_LEVELS];
     if (threadIdx.x < RP_REFIT_LEVELS) s_hist[threadIdx.x] = 0;
     __syncthreads();
@@ -199,25 +213,25 @@ __global__ __launch_bounds__(256) void rp_k_lbvh_emit(int n, const int *left, co
         int me = node_base;
         uint32_t depth = 0;
         if (n < 2) { // a mesh of one triangle (or none): a root with that leaf
-            if (n == 1) child[0] = RPTR_BVH_LEAF(tri_base, 1);
+            if (n == 1) child[0] = RPTR_BVH_LEAF(tri_base, 1); // (one primitive: sorted position 0 is primitive 0 either way)
             *out_count = 1;
         } else {
             if (i == n - 2) *out_count = (int)(slot[i] + flag[i]); // (the scan is exclusive: the last element closes the count)
             if (!flag[i]) continue;
             me = node_base + (int)slot[i];
             depth = depth4[i];
-            if (last[i] - first[i] + 1 <= RP_LBVH_LEAF_TRIS) // only the root of a tiny mesh: one leaf with everything
-                child[0] = RPTR_BVH_LEAF(tri_base + first[i], last[i] - first[i] + 1);
+            if (last[i] - first[i] + 1 <= lv.leaf_max) // only the root of a tiny mesh: one leaf with everything
+                child[0] = rp_lbvh_leaf_ref(first[i], last[i] - first[i] + 1, tri_base, lv);
             else {
                 int nc = 0;
                 const int two[2] = {left[i], right[i]};
                 for (int c = 0; c < 2; ++c) {
                     const int ch = two[c];
-                    if (ch >= 0 && last[ch] - first[ch] + 1 > RP_LBVH_LEAF_TRIS) { // an inner node of odd depth: its children move up
-                        child[nc++] = rp_lbvh_child_ref(left[ch], first, last, slot, node_base, tri_base);
-                        child[nc++] = rp_lbvh_child_ref(right[ch], first, last, slot, node_base, tri_base);
+                    if (ch >= 0 && last[ch] - first[ch] + 1 > lv.leaf_max) { // an inner node of odd depth: its children move up
+                        child[nc++] = rp_lbvh_child_ref(left[ch], first, last, slot, node_base, tri_base, lv);
+                        child[nc++] = rp_lbvh_child_ref(right[ch], first, last, slot, node_base, tri_base, lv);
                     } else
-                        child[nc++] = rp_lbvh_child_ref(ch, first, last, slot, node_base, tri_base);
+                        child[nc++] = rp_lbvh_child_ref(ch, first, last, slot, node_base, tri_base, lv);
                 }
             }
         }
@@ -241,17 +255,20 @@ __global__ void rp_k_lbvh_level_scan(const uint32_t *level_hist, uint32_t list_b
         at += level_hist[k];
     }
 }
-__global__ __launch_bounds__(256) void rp_k_lbvh_level_scatter(const RptrBvh4Node *nodes, int node_base, const int *count_ptr, uint32_t *cursor, uint32_t *list) {
+// tag: ORed into every entry (bit 31 marks a top-level node for rp_refit_node: its leaves are instance records)
+__global__ __launch_bounds__(256) void rp_k_lbvh_level_scatter(const RptrBvh4Node *nodes, int node_base, const int *count_ptr, uint32_t *cursor, uint32_t *list,
+                                                               uint32_t tag) {
     const int count = *count_ptr;
     for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x) {
         const uint32_t depth = nodes[node_base + k]._pad1[0];
-        list[atomicAdd(&cursor[RP_REFIT_LEVELS - 1 - depth], 1u)] = (uint32_t)(node_base + k);
+        list[atomicAdd(&cursor[RP_REFIT_LEVELS - 1 - depth], 1u)] = (uint32_t)(node_base + k) | tag;
     }
 }
 
 // ------------------------------------------------------------------ refit by depth levels whose sizes live on the device
 // one level of a mesh: the nodes list[levels[k].x .. levels[k].y)
-__global__ __launch_bounds__(256) void rp_k_refit_level(RptrBvh4Node *nodes, float *node_box, const float *tri_box, const uint32_t *list, const uint2 *level) {
+__global__ __launch_bounds__(256) void rp_k_refit_level(RptrBvh4Node *nodes, float *node_box, const float *tri_box, const float *inst_box, const uint32_t *list,
+                                                        const uint2 *level) {
     const uint2 lv = *level;
-    for (uint32_t i = lv.x + blockIdx.x * blockDim.x + threadIdx.x; i < lv.y; i += gridDim.x * blockDim.x) rp_refit_node(nodes, node_box, tri_box, nullptr, list[i]);
+    for (uint32_t i = lv.x + blockIdx.x * blockDim.x + threadIdx.x; i < lv.y; i += gridDim.x * blockDim.x) rp_refit_node(nodes, node_box, tri_box, inst_box, list[i]);
 }

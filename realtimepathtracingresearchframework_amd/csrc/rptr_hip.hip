@@ -12,6 +12,7 @@
 #include "realtime_resolve.h"
 #include "launch.h"
 #include "lbvh.h"
+#include "tlas_build.h"
 #include "ploc.h"
 #include <hip/hip_ext.h>
 

@@ -51,6 +51,21 @@ public:
     void refit() {
         for (auto &r : ranks_) r->refit();
     }
+    void update_instances(uint32_t first, uint32_t count, const float *transforms12) { // every GPU holds the whole scene
+        for (auto &r : ranks_) r->update_instances(first, count, transforms12);
+    }
+    // (device memory belongs to one GPU: rank k reads device_transforms12[k])
+    void update_instances_device(uint32_t first, uint32_t count, const std::vector<const float *> &device_transforms12) {
+        for (size_t k = 0; k < ranks_.size(); ++k) ranks_[k]->update_instances_device(first, count, device_transforms12.at(k));
+    }
+    void set_tlas_policy(int mode) {
+        for (auto &r : ranks_) r->set_tlas_policy(mode);
+    }
+    uint64_t tlas_rebuild_count() const { // over every GPU
+        uint64_t n = 0;
+        for (auto &r : ranks_) n += r->tlas_rebuild_count();
+        return n;
+    }
     void set_rng_variant(int rng_variant, const std::vector<uint32_t> &table = {}) {
         for (auto &r : ranks_) r->set_rng_variant(rng_variant, table);
     }

@@ -100,6 +100,17 @@ public:
         check(rptr_hip_update_vertices_device(h_, geometry, device_xyz, num_vertices));
     }
     void refit() { check(rptr_hip_refit(h_)); }
+    // moving instances: `count` row-major 3x4 object-to-world transforms for scene instances [first, first + count), applied by the next refit
+    void update_instances(uint32_t first, uint32_t count, const float *transforms12) { check(rptr_hip_update_instances(h_, first, count, transforms12)); }
+    void update_instances_device(uint32_t first, uint32_t count, const float *device_transforms12) {
+        check(rptr_hip_update_instances_device(h_, first, count, device_transforms12));
+    }
+    void set_tlas_policy(int mode) { check(rptr_hip_set_tlas_policy(h_, mode)); } // RPTR_TLAS_REBUILD | RPTR_TLAS_REFIT
+    uint64_t tlas_rebuild_count() const {
+        uint64_t n = 0;
+        rptr_hip_tlas_rebuild_count(h_, &n);
+        return n;
+    }
     // RenderBackendOptions (render_params.glsl.h:56-93): the point set with the table its render extension uploads, and the BVH policy
     void set_rng_variant(int rng_variant, const std::vector<uint32_t> &table = {}) {
         check(rptr_hip_set_rng_variant(h_, rng_variant, table.empty() ? nullptr : table.data(), table.size() * sizeof(uint32_t)));

@@ -527,6 +527,25 @@ inline std::string extended_material_name(const std::string &tex_dir, const std:
     return exists ? std::string(ex.begin(), ex.end()) : name;
 }
 
+// The object-to-world transforms (12 floats each, row-major 3x4: what RenderHip::update_instances takes) of frame `frame` of an OPENED
+// file -- `v` is what read_header returned, nothing is loaded again -- for the instances read_scene makes of it, in its order:
+// AnimationData::dequantize(index, frame), librender/scene.cpp:22-41. Equal to the instance transforms of read_scene with lp.frame = frame.
+inline std::vector<float> frame_transforms(const Header &v, uint64_t frame, float instance_pruning_probability = 0.0f) {
+    if (frame >= std::max<uint64_t>(1, v.numFrames)) throw Error("frame index beyond the frames of the file");
+    std::vector<float> out;
+    for (size_t idx = 0; idx < v.instances.size(); ++idx) {
+        const InstanceHeader &vi = v.instances[idx];
+        const LodGroup &lod = v.lodGroups[(size_t)v.meshes[(size_t)vi.meshId].lodGroup];
+        if (!lod.meshIds.empty() && lod.meshIds[0] != vi.meshId) continue;
+        if (instance_pruning_probability != 0.0f && halton2((uint32_t)idx) < instance_pruning_probability) continue;
+        const uint64_t at = transform_offset(vi.transformIndex, v.numStaticTransforms, v.numAnimatedTransforms, frame) * QUANTIZED_TRANSFORM_SIZE;
+        if (at + QUANTIZED_TRANSFORM_SIZE > v.transforms.size()) throw Error("transform index beyond the table of the file");
+        out.resize(out.size() + 12);
+        instance_transform(v.transforms.data() + at, out.data() + out.size() - 12);
+    }
+    return out;
+}
+
 inline SceneDump read_scene(const std::string &path, const std::string &data_dir, const LoadParams &lp) {
     const bool ignore_textures = lp.ignore_textures, load_specularity = lp.load_specularity;
     const uint64_t frame = lp.frame;
@@ -610,6 +629,8 @@ inline SceneDump read_scene(const std::string &path, const std::string &data_dir
         if (remove_first_lods > 0 && lod.meshIds.size() > 1) // SceneLoaderParams::PerFile::remove_first_LODs (scene.cpp:801-815, :229-246)
             in.parameterized_mesh = (uint32_t)lod.meshIds[std::min((size_t)remove_first_lods, lod.meshIds.size() - 1)];
         s.instances.push_back(in);
+        // an animated transform: the instances of this mesh move (frame_transforms + RenderHip::update_instances play the frames)
+        if (vi.transformIndex >= v.numStaticTransforms && !lp.ignore_animation) s.meshes[s.pmeshes[in.parameterized_mesh].mesh].dynamic |= RPTR_MESH_INSTANCES_MOVE;
     }
     auto add_texture = [&](std::vector<uint8_t> rgba, uint32_t w, uint32_t h, bool srgb, uint32_t levels = 0) {
         s.texels.push_back(std::move(rgba));

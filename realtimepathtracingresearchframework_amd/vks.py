@@ -496,6 +496,38 @@ def transform_offset(index, num_static, num_animated, frame):   # vkr_get_transf
     return num_static + (index - num_static) + frame * num_animated
 
 
+def _instanced(v, instance_pruning_probability=0.0):
+    """The instances of an opened file that `read_vks` turns into scene instances, in its order: base levels of LoD groups only
+    (scene.cpp:722-736), minus the pruned ones (:734-749). Yields (index in the file, VkrInstance dict, LoD group)."""
+    for idx, vi in enumerate(v["instances"]):
+        lod = v["lodGroups"][v["meshes"][vi["meshId"]]["lodGroup"]]
+        if lod["numLevelsOfDetail"] != 0 and lod["meshIds"][0] != vi["meshId"]:
+            continue
+        if instance_pruning_probability and halton2(idx) < instance_pruning_probability:
+            continue
+        yield idx, vi, lod
+
+
+def frame_transforms(v, frame, instance_pruning_probability=0.0):
+    """The (n, 12) float32 object-to-world transforms (row-major 3x4, what `update_instances` takes) of frame `frame` of an OPENED
+    scene -- `v` is what `read_vks_header` returned; nothing is loaded again -- for the instances `read_vks` made of it, in its order:
+    `AnimationData::dequantize(index, frame)` (librender/scene.cpp:22-41) per instance. Equal to the instance transforms of
+    `read_vks(path, frame=frame)` bit for bit."""
+    if not 0 <= frame < max(1, v["numFrames"]):
+        raise VksError("frame %d of %d" % (frame, v["numFrames"]))
+    out = []
+    for _, vi, _ in _instanced(v, instance_pruning_probability):
+        at = transform_offset(vi["transformIndex"], v["numStaticTransforms"], v["numAnimatedTransforms"], frame) * QUANTIZED_TRANSFORM_SIZE
+        out.append(np.asarray(instance_transform(v["transforms"][at:at + QUANTIZED_TRANSFORM_SIZE]), f32).reshape(12))
+    return np.stack(out) if out else np.zeros((0, 12), f32)
+
+
+def animated_instances(v, instance_pruning_probability=0.0):
+    """indices (into the instance list `read_vks` makes) of the instances whose transform changes with the frame: transformIndex >=
+    numStaticTransforms"""
+    return [k for k, (_, vi, _) in enumerate(_instanced(v, instance_pruning_probability)) if vi["transformIndex"] >= v["numStaticTransforms"]]
+
+
 def _load_material_files(tex_dir, name):
     """vkr_load_material (vkr.c:509-620): parameter files and the three standard textures of one material"""
     m = {"name": name, "emissionIntensity": 0.0, "emitterBaseColor": [0.0, 0.0, 0.0], "specularTransmission": 0.0, "iorEta": 1.5,
@@ -578,12 +610,7 @@ def read_vks(path, ignore_textures=False, load_specularity=False, frame=0, remov
                     ext = mat_files[off]["extended_name"] if 0 <= off < len(mat_files) else ""
                     if "_SHADERMESH_" in ext or "_SHADERSUBMESH_" in ext:
                         s.meshes[-1].dynamic = int(s.meshes[-1].dynamic) | dynamic_flag
-    for idx, vi in enumerate(v["instances"]):              # scene.cpp:722-745: only the base level of a LoD group is instanced
-        lod = v["lodGroups"][v["meshes"][vi["meshId"]]["lodGroup"]]
-        if lod["numLevelsOfDetail"] != 0 and lod["meshIds"][0] != vi["meshId"]:
-            continue
-        if instance_pruning_probability and halton2(idx) < instance_pruning_probability:
-            continue
+    for idx, vi, lod in _instanced(v, instance_pruning_probability):   # scene.cpp:722-745: only the base level of a LoD group is instanced
         pmesh = vi["meshId"]
         if remove_first_lods > 0 and lod["numLevelsOfDetail"] > 1:
             # SceneLoaderParams::PerFile::remove_first_LODs (scene.cpp:801-815): the first n levels are replaced by level n (or the
@@ -591,6 +618,10 @@ def read_vks(path, ignore_textures=False, load_specularity=False, frame=0, remov
             pmesh = int(lod["meshIds"][min(remove_first_lods, lod["numLevelsOfDetail"] - 1)])
         at = transform_offset(vi["transformIndex"], v["numStaticTransforms"], v["numAnimatedTransforms"], frame) * QUANTIZED_TRANSFORM_SIZE
         s.instances.append(Instance(transform=instance_transform(v["transforms"][at:at + QUANTIZED_TRANSFORM_SIZE]), pmesh=pmesh))
+        if vi["transformIndex"] >= v["numStaticTransforms"] and not ignore_animation:
+            # an animated transform: the instances of this mesh move (`frame_transforms` + RenderHip.update_instances play the frames)
+            mesh = s.meshes[s.pmeshes[pmesh].mesh]
+            mesh.dynamic = int(mesh.dynamic) | abi.MESH_INSTANCES_MOVE
     for i, name in enumerate(v["materialNames"]):   # scene.cpp:818-975
         vm = mat_files[i]
         mat = abi.make_material(flags=0)
@@ -685,7 +716,8 @@ def _normal_uv_stream(g):
     return qn.astype(np.uint64) | (qu.astype(np.uint64) << np.uint64(32))
 
 
-def write_vks(path, scene: Scene, version=4, material_names=None, lod_groups=None, wide_material_ids=None, index_buffers=False):
+def write_vks(path, scene: Scene, version=4, material_names=None, lod_groups=None, wide_material_ids=None, index_buffers=False, animation=None,
+              animation_start=0.0, animation_step=1.0 / 30.0):
     """Writes `scene` as <path> (.vks, file version 3 or 4) plus <base>_textures/ with what `read_vks` / the reference's
     `load_vkrs` pick up again. Constraints of the format, checked here: every parameterized mesh becomes a .vks mesh (a mesh
     shared by several parameterized meshes is written once per use), its geometries share one quantisation grid, instance
@@ -700,7 +732,18 @@ def write_vks(path, scene: Scene, version=4, material_names=None, lod_groups=Non
     wide_material_ids: {parameterized mesh: uint16 ids} -- that mesh is written with 16-bit per-triangle material ids and a material
     range above 256 (vkr.c:1127-1130: two bytes per id when numMaterialsInRange > 0x100); index_buffers: every mesh also carries the
     (redundant, identity) index buffer of VKR_MESH_FLAGS_INDICES files -- the vertex streams of a .vks file are unrolled either way.
+    animation (file version 4): {instance index: [3x4 transform of frame 0, of frame 1, ...]} -- the same number of frames for every
+    entry (numFrames). Those instances get animated transform indices (>= numStaticTransforms); the table holds the static transforms,
+    then per frame the animated ones (vkr_get_transform_offset, vkr.c:197-208). The scene's own transform of such an instance is not written.
     Returns the material names."""
+    animation = {int(k): list(fr) for k, fr in (animation or {}).items()}
+    n_frames = 1
+    if animation:
+        if version < 4:
+            raise VksError("animated transforms need file version 4")
+        n_frames = len(next(iter(animation.values())))
+        if n_frames < 1 or any(len(fr) != n_frames for fr in animation.values()) or any(not 0 <= k < len(scene.instances) for k in animation):
+            raise VksError("animation: one transform per frame for every animated instance of the scene")
     wide_material_ids = wide_material_ids or {}
     names = material_names or ["mat%03d" % i for i in range(len(scene.materials))]
     lod_groups = lod_groups or []
@@ -754,7 +797,12 @@ def write_vks(path, scene: Scene, version=4, material_names=None, lod_groups=Non
         if index_buffers:
             blob += np.arange(3 * n, dtype=np.uint32).tobytes()
         mesh_blobs.append(blob)
-    transforms = [storable_transform(inst.transform) for inst in scene.instances]
+    transforms = [storable_transform(inst.transform) for inst in scene.instances]   # (version 3: one per instance, in the groups)
+    static_ids = [k for k in range(len(scene.instances)) if k not in animation]
+    animated_ids = sorted(animation)
+    transform_index = {k: j for j, k in enumerate(static_ids)}
+    transform_index.update({k: len(static_ids) + j for j, k in enumerate(animated_ids)})
+    table = [transforms[k] for k in static_ids] + [storable_transform(animation[k][fr]) for fr in range(n_frames) for k in animated_ids]
     # ---- sizes first: every header carries absolute offsets
     scene_header = 8 + 24 + 5 * 8 + (struct.calcsize("<QqQqffQQQq") if version >= 4 else 0)
     at = scene_header
@@ -785,12 +833,13 @@ def write_vks(path, scene: Scene, version=4, material_names=None, lod_groups=Non
         f.write(struct.pack("<ii3Q", VKR_MAGIC, version, 0, scene_header, data_offset))
         f.write(struct.pack("<5Q", len(scene.pmeshes), len(scene.instances), len(names), n_tris_total, len(scene.instances)))
         if version >= 4:
-            f.write(struct.pack("<QqQqffQQQq", 1 + len(lod_groups), lod_offset, 0, 0, 0.0, 0.0, 1, len(transforms), 0, animation_offset))
+            f.write(struct.pack("<QqQqffQQQq", 1 + len(lod_groups), lod_offset, 0, 0, float(animation_start) if animation else 0.0,
+                                float(animation_step) if animation else 0.0, n_frames, len(static_ids), len(animated_ids), animation_offset))
         for (head, tail), end, off in zip(mesh_headers, mesh_header_end, mesh_data_offset):
             f.write(head + struct.pack("<3Q", MESH_FLAGS_INDICES if index_buffers else 0, end, off) + tail)
         for k, (inst, (name, data_off, end)) in enumerate(zip(scene.instances, group_meta)):
             f.write(struct.pack("<Ii3Q", 0, inst.pmesh, end, data_off, 1) + name)
-            f.write(struct.pack("<I", k) if version >= 4 else np.asarray(transforms[k], f32).tobytes())
+            f.write(struct.pack("<I", transform_index[k]) if version >= 4 else np.asarray(transforms[k], f32).tobytes())
         if version >= 4:
             f.write(struct.pack("<Q", 0))
             for group in lod_groups:
@@ -801,7 +850,7 @@ def write_vks(path, scene: Scene, version=4, material_names=None, lod_groups=Non
         for blob in mesh_blobs:
             f.write(blob)
         if version >= 4:
-            for t in transforms:
+            for t in table:
                 f.write(quantize_transform(t))
     # ---- materials
     tdir = texture_dir(path)
