@@ -266,7 +266,7 @@ int rptr_hip_trace_counted(rptr_hip_t *h, const RptrRenderRayQuery *queries, int
             hipLaunchKernelGGL(kernel, dim3(h->persistent_blocks), dim3(RP_TRAVERSE_BLOCK), 0, h->stream, h->master.dscene, dq, (uint32_t)n, dr,
                                &h->ctx[0].counters->bounce[0].cursor_extend, h->ctx[0].gstack, dv, dt);
         };
-        pick(h->master.dscene.single_instance != 0, [&](auto S) {
+        rp_pick(h->master.dscene.single_instance != 0, [&](auto S) {
             if (any_hit)
                 launch(rp_k_trace<true, true, decltype(S)::value>);
             else if (visits2)
@@ -293,12 +293,28 @@ extern "C++" {
 static int trace_device_on(rptr_hip *h, const RptrRenderRayQuery *dq, int n, float4 *dr, hipStream_t st) {
     if (n == 0) return RPTR_OK;
     hipLaunchKernelGGL(rp_k_reset_u32, dim3(1), dim3(1), 0, st, &h->ctx[0].counters->bounce[0].cursor_extend);
-    pick(h->master.dscene.single_instance != 0, [&](auto S) {
+    rp_pick(h->master.dscene.single_instance != 0, [&](auto S) {
         hipLaunchKernelGGL((rp_k_trace<false, false, decltype(S)::value>), dim3(h->persistent_blocks), dim3(RP_TRAVERSE_BLOCK), 0, st, h->master.dscene, dq, (uint32_t)n, dr,
                            &h->ctx[0].counters->bounce[0].cursor_extend, h->ctx[0].gstack, (uint2 *)nullptr, (const float *)nullptr);
     });
     HIP_TRY(h, hipGetLastError());
     return RPTR_OK;
+}
+// queue(st) on the stream the caller named (NULL: the backend's). A stream of the caller's sees the scene uploads / refits queued on the
+// backend's, and later frames see what was queued
+template <class F>
+static int on_callers_stream(rptr_hip *h, void *hip_stream, F &&queue) {
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : h->stream;
+    if (st == h->stream) return queue(st);
+    hipEvent_t e;
+    HIP_TRY(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    (void)hipEventRecord(e, h->stream);
+    (void)hipStreamWaitEvent(st, e, 0);
+    const int rc = queue(st);
+    (void)hipEventRecord(e, st);
+    (void)hipStreamWaitEvent(h->stream, e, 0);
+    (void)hipEventDestroy(e);
+    return rc;
 }
 }
 
@@ -309,19 +325,7 @@ int rptr_hip_trace_device(rptr_hip_t *h, const RptrRenderRayQuery *device_querie
     int rc = drain(h); // the query kernel borrows context 0's cursor and stack scratch
     if (rc || (rc = ensure_master_tree(h))) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : h->stream;
-    if (st != h->stream) { // the caller's stream sees the scene uploads / refits queued on the backend's, and later frames see the queries
-        hipEvent_t e;
-        HIP_TRY(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        (void)hipEventRecord(e, h->stream);
-        (void)hipStreamWaitEvent(st, e, 0);
-        rc = trace_device_on(h, device_queries, n, reinterpret_cast<float4 *>(device_out4), st);
-        (void)hipEventRecord(e, st);
-        (void)hipStreamWaitEvent(h->stream, e, 0);
-        (void)hipEventDestroy(e);
-        return rc;
-    }
-    return trace_device_on(h, device_queries, n, reinterpret_cast<float4 *>(device_out4), st);
+    return on_callers_stream(h, hip_stream, [&](hipStream_t st) { return trace_device_on(h, device_queries, n, reinterpret_cast<float4 *>(device_out4), st); });
 }
 
 int rptr_hip_enable_ray_queries(rptr_hip_t *h, int max_queries, int max_queries_per_pixel, void **out_device_queries, void **out_device_results) {
@@ -404,20 +408,9 @@ int rptr_hip_trace_radiance_device(rptr_hip_t *h, const RptrRenderRayQuery *devi
     if (rc) return rc;
     if ((rc = drain(h)) || (rc = ensure_master_tree(h))) return rc; // the run borrows context 0
     HIP_TRY(h, hipSetDevice(h->device));
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : h->stream;
-    float4 *dr = reinterpret_cast<float4 *>(device_out4);
-    if (st != h->stream) { // the caller's stream sees the scene uploads / refits queued on the backend's, and later frames see the queries
-        hipEvent_t e;
-        HIP_TRY(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        (void)hipEventRecord(e, h->stream);
-        (void)hipStreamWaitEvent(st, e, 0);
-        rc = radiance_queries_on(h, device_queries, n, camera, variant, samples_per_query, first_sample, dr, st, nullptr);
-        (void)hipEventRecord(e, st);
-        (void)hipStreamWaitEvent(h->stream, e, 0);
-        (void)hipEventDestroy(e);
-        return rc;
-    }
-    return radiance_queries_on(h, device_queries, n, camera, variant, samples_per_query, first_sample, dr, st, nullptr);
+    return on_callers_stream(h, hip_stream, [&](hipStream_t st) {
+        return radiance_queries_on(h, device_queries, n, camera, variant, samples_per_query, first_sample, reinterpret_cast<float4 *>(device_out4), st, nullptr);
+    });
 }
 
 int rptr_hip_render_radiance_queries(rptr_hip_t *h, int num_queries, const RptrCamera *camera, int variant, int samples_per_query, int first_sample) {

@@ -1,13 +1,15 @@
-// host_frame.inl -- a frame: camera basis, the stage launches of a launch sequence (render_batch_impl), collecting a frame (finish_frame), wait / render / stats
+// host_frame.inl -- a frame: camera basis, the bounce schedule of the path pipeline (queue_path_bounces: the ONE place that launches the path
+// stages, for frames and for radiance-query runs), submitting a launch sequence (render_batch_impl and its steps), radiance-query runs
+// (radiance_queries_on), collecting a frame (finish_frame), wait / render / stats
 // Part of the ONE translation unit rptr_hip.hip (included there, in this order: host_state.h, host_bvh.inl, host_scene.inl,
 // host_frame.inl, host_access.inl, host_comm.h): the host runtime split along its seams; no symbol changed.
 // host part of a3: vulkan/render_vulkan.cpp:2880-2896
+static void cross3(const float a[3], const float b[3], float o[3]) {
+    o[0] = a[1] * b[2] - b[1] * a[2];
+    o[1] = a[2] * b[0] - b[2] * a[0];
+    o[2] = a[0] * b[1] - b[0] * a[1];
+}
 static void compute_view(const RptrCamera &c, int W, int H, RpFrame &f) {
-    auto cross = [](const float a[3], const float b[3], float o[3]) {
-        o[0] = a[1] * b[2] - b[1] * a[2];
-        o[1] = a[2] * b[0] - b[2] * a[0];
-        o[2] = a[0] * b[1] - b[0] * a[1];
-    };
     auto normalize = [](float v[3]) {
         float inv = 1.0f / sqrtf((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
         v[0] *= inv;
@@ -18,10 +20,10 @@ static void compute_view(const RptrCamera &c, int W, int H, RpFrame &f) {
     const float aspect = static_cast<float>(W) / H;
     const float plane_x = plane_y * aspect;
     float du[3], dv[3];
-    cross(c.dir, c.up, du);
+    cross3(c.dir, c.up, du);
     normalize(du);
     for (int k = 0; k < 3; ++k) du[k] *= plane_x;
-    cross(du, c.dir, dv);
+    cross3(du, c.dir, dv);
     normalize(dv);
     for (int k = 0; k < 3; ++k) dv[k] = -dv[k] * plane_y;
     for (int k = 0; k < 3; ++k) {
@@ -35,17 +37,12 @@ static void compute_view(const RptrCamera &c, int W, int H, RpFrame &f) {
 // x / y / w rows of VP (render_vulkan.cpp:2926-2931): inverse of the camera-to-world matrix with columns cross(dir, up), up, -dir,
 // pos; glm::infinitePerspective(radians(fovy), aspect, 0.5f) contributes P00 and P11 (GLM's published formulas)
 static void compute_view_projection(const RptrCamera &c, int W, int H, float view[12], float proj[2]) {
-    auto cross = [](const float a[3], const float b[3], float o[3]) {
-        o[0] = a[1] * b[2] - b[1] * a[2];
-        o[1] = a[2] * b[0] - b[2] * a[0];
-        o[2] = a[0] * b[1] - b[0] * a[1];
-    };
     auto dot = [](const float a[3], const float b[3]) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; };
     float cx[3], cz[3] = {-c.dir[0], -c.dir[1], -c.dir[2]}, r[3][3];
-    cross(c.dir, c.up, cx);
-    cross(c.up, cz, r[0]);
-    cross(cz, cx, r[1]);
-    cross(cx, c.up, r[2]);
+    cross3(c.dir, c.up, cx);
+    cross3(c.up, cz, r[0]);
+    cross3(cz, cx, r[1]);
+    cross3(cx, c.up, r[2]);
     const float inv_det = 1.0f / dot(cx, r[0]);
     for (int k = 0; k < 3; ++k) {
         for (int j = 0; j < 3; ++j) r[k][j] *= inv_det;
@@ -62,17 +59,7 @@ static void compute_view_projection(const RptrCamera &c, int W, int H, float vie
 }
 
 extern "C++" {
-// runtime flag -> template argument: f(std::true_type) or f(std::false_type)
-template <class F>
-static inline void pick(bool v, F &&f) {
-    if (v)
-        f(std::true_type());
-    else
-        f(std::false_type());
-}
-
-// Which instantiations of the path stages a launch sequence runs, and where it hands over to the tail kernel: ONE place for frames
-// (render_batch_impl) and radiance-query runs (radiance_queries_on), whose later bounces must be the frame's kernels to give the frame's bits.
+// Which instantiations of the path stages a launch sequence runs, and where it hands over to the tail kernel
 struct PathKernelFlags {
     bool lights;    // light-sampling code: without emissive triangles and with all NEE probability on the sun that branch is dead code
     bool table_rng; // the general instantiations: a table point set, or a screen jitter (raster TAA) -- the shipped path carries neither
@@ -84,7 +71,7 @@ static PathKernelFlags path_kernel_flags(const rptr_hip *h, const RpScene &scene
     PathKernelFlags k;
     k.lights = (h->num_lights > 0 && !h->lights_disabled) || f.sp.sun_radiance[3] < 1.0f;
     k.table_rng = h->rng_variant != RPTR_RNG_VARIANT_UNIFORM || h->params.enable_raster_taa != 0;
-    k.single = scene.single_instance != 0;
+    k.single = scene.single_instance != 0; // (the same in every copy: set_scene decides it before it copies the master's RpScene, nothing writes it later)
     k.full = h->uses_textures || h->uses_alpha;
     k.fast_math = h->opt.v[OPT_FAST_MATH] != 0;
     return k;
@@ -96,13 +83,89 @@ static int tail_hand_over(const rptr_hip *h, bool count_traversal) {
     return std::max(1, std::min(depth, h->tail_mode > 0 ? h->tail_mode : h->tail_adaptive));
 }
 
-static void launch_shade(rptr_hip *h, FrameCtx &c, int variant, const RpScene &scene, const RpFrame &f, const uint32_t *order, int bounce, int out) {
+// Where the launches of one submission put their timing spans: the context's event pool (from `cursor` on) and span list
+struct StageTimer {
+    FrameCtx *c;
+    size_t cursor;
+    int level; // stage_timing: 1 times kind 0 (closest-hit traversal) only, 2 every kind (host_state.h Span)
+};
+// (stream, kind, grid) -> the launch. When the level times this kind its start / stop events ride on the dispatch packet itself
+// (launch.h rp_launch_kernel), no extra barrier packets in the queue -- the command processor's packet rate is what bounds small frames
+// (profiles/r01_notes.md). timer == NULL: never timed.
+static RpLaunch timed_launch(StageTimer *t, hipStream_t st, int kind, dim3 grid) {
+    RpLaunch l = {grid, st, nullptr, nullptr};
+    if (t && (t->level >= 2 || (t->level == 1 && kind == 0))) {
+        l.start = next_event(*t->c, t->cursor);
+        l.stop = next_event(*t->c, t->cursor);
+        t->c->spans.push_back({l.start, l.stop, kind});
+    }
+    return l;
+}
+
+// One batch of paths through the pipeline: extend -> shade -> connect per bounce, then the tail launch. What differs between a frame
+// (render_batch_impl) and a radiance-query run (radiance_queries_on):
+struct PathRun {
+    FrameCtx *c;          // whose path state, queues, counters and stack scratch are used
+    const RpScene *scene; // the scene copy that is traced
+    const RpFrame *f;     // (f->batch_spp sizes the first bounce's queue)
+    int variant;
+    hipStream_t stream;
+    hipStream_t side;     // NULL: connect on `stream` with c->gstack; otherwise on this stream with c->gstack_side, next to the following extend
+    int grids[4];         // traversal_grid kinds: first extend, later extends, connect, connect of a single-instance scene
+    int grid_shade, grid_tail;
+    bool count_traversal;
+    int tail_from;             // the bounce the tail kernel takes over at (tail_hand_over)
+    const RpQueries *queries;  // non-NULL: bounce 0 traces and shades the rays of the query buffer; NULL: the camera's
+    StageTimer *timer;         // NULL: no timing spans
+};
+struct BounceLaunches {
+    int extend = 0, connect = 0;
+};
+static int queue_path_bounces(rptr_hip *h, const PathRun &run, BounceLaunches &launched) {
+    FrameCtx &c = *run.c;
+    const RpScene &scene = *run.scene;
+    const RpFrame &f = *run.f;
     const PathKernelFlags k = path_kernel_flags(h, scene, f);
-    const RpLaunch l = {(unsigned)grid_for(h, h->path_capacity), c.stream, nullptr, nullptr};
-    rp_launch_shade(variant, k.fast_math, l, bounce == 0, k.lights, h->uses_textures,
-                    k.table_rng, scene, f, c.ps, c.sq, order,
-                    (const uint32_t *)&c.counters->bounce[bounce].queue_count, c.queue[out], &c.counters->bounce[bounce + 1].queue_count,
-                    &c.counters->bounce[bounce].shadow_count, c.counters);
+    const bool alpha = h->uses_alpha, tex = h->uses_textures;
+    HIP_TRY(h, hipMemsetAsync(c.counters, 0, sizeof(RpCounters), run.stream));
+    // the first bounce's queue is the identity over the batch's path ids and is not stored (kernels.h)
+    const uint32_t first_count = (uint32_t)((size_t)f.batch_spp * h->npix_padded);
+    HIP_TRY(h, hipMemsetD32Async((hipDeviceptr_t)&c.counters->bounce[0].queue_count, (int)first_count, 1, run.stream));
+    for (int b = 0; b < h->params.max_path_depth; ++b) {
+        const int in = b & 1, out = in ^ 1;
+        RpBounceCounters *bc = &c.counters->bounce[b];
+        const uint32_t *in_queue = b == 0 ? nullptr : c.queue[in];
+        if (b == run.tail_from) { // the late bounces in one launch (kernels.h rp_k_tail)
+            if (run.side && b > 0) HIP_TRY(h, hipStreamWaitEvent(run.stream, c.ev_side, 0)); // join: connect(b-1) on the side stream
+            rp_launch_tail(run.variant, k.fast_math, timed_launch(run.timer, run.stream, 3, (unsigned)run.grid_tail), k.lights, k.full, k.single, k.table_rng, scene, f, c.ps,
+                           c.sq, (const uint32_t *)c.queue[in], c.counters, b, c.gstack);
+            break;
+        }
+        const RpLaunch l_extend = timed_launch(run.timer, run.stream, 0, (unsigned)run.grids[b == 0 ? 0 : 1]);
+        if (b == 0 && run.queries)
+            rp_launch_extend_query(l_extend, alpha, k.single, k.table_rng, scene, f, c.ps, *run.queries, bc, c.counters, c.gstack);
+        else
+            rp_launch_extend(l_extend, run.count_traversal, b == 0, alpha, k.single, k.table_rng, scene, f, c.ps, in_queue, bc, c.counters, c.gstack);
+        launched.extend++;
+        if (run.side && b > 0) HIP_TRY(h, hipStreamWaitEvent(run.stream, c.ev_side, 0)); // join: connect(b-1) wrote illum, frees the shadow queue
+        const RpLaunch l_shade = timed_launch(run.timer, run.stream, 2, (unsigned)run.grid_shade);
+        if (b == 0 && run.queries)
+            rp_launch_shade_query(run.variant, k.fast_math, l_shade, k.lights, tex, k.table_rng, scene, f, c.ps, c.sq, (const uint32_t *)&bc->queue_count, c.queue[out],
+                                  &c.counters->bounce[b + 1].queue_count, &bc->shadow_count, c.counters);
+        else
+            rp_launch_shade(run.variant, k.fast_math, l_shade, b == 0, k.lights, tex, k.table_rng, scene, f, c.ps, c.sq, in_queue, (const uint32_t *)&bc->queue_count,
+                            c.queue[out], &c.counters->bounce[b + 1].queue_count, &bc->shadow_count, c.counters);
+        if (run.side) { // fork: the side stream sees shade(b)
+            HIP_TRY(h, hipEventRecord(c.ev_fork, run.stream));
+            HIP_TRY(h, hipStreamWaitEvent(run.side, c.ev_fork, 0));
+        }
+        rp_launch_connect(timed_launch(run.timer, run.side ? run.side : run.stream, 1, (unsigned)run.grids[k.single ? 3 : 2]), run.count_traversal, alpha, k.single, scene, f,
+                          c.ps, c.sq, bc, c.counters, run.side ? c.gstack_side : c.gstack);
+        if (run.side) HIP_TRY(h, hipEventRecord(c.ev_side, run.side));
+        launched.connect++;
+    }
+    if (run.side) HIP_TRY(h, hipStreamWaitEvent(run.stream, c.ev_side, 0)); // the last connect
+    return RPTR_OK;
 }
 
 static void add_counters(RpCounters &dst, const RpCounters &c) {
@@ -113,6 +176,15 @@ static void add_counters(RpCounters &dst, const RpCounters &c) {
     dst.nodes_shadow += c.nodes_shadow;
     dst.tris_shadow += c.tris_shadow;
     dst.hits_shaded += c.hits_shaded;
+}
+
+// read-backs of the image get, from here on, the one frame `which` of this context's batch produced (its context keeps a copy)
+static void note_output(rptr_hip *h, FrameCtx &c, int which) {
+    if (h->ctx.size() > 1) {
+        h->output_ctx = (int)(&c - h->ctx.data());
+        h->output_index = std::max(which, 0);
+        h->output_overwritten = false;
+    }
 }
 
 // waits for the frame in flight on `c` and turns its events / counters into RptrStats
@@ -127,11 +199,7 @@ static int finish_frame(rptr_hip *h, FrameCtx &c, RptrStats *out_stats, int whic
         if (out_stats) *out_stats = st;
         c.collected |= which < 0 ? all : (1u << which);
         if (c.collected == all) c.pending = false;
-        if (h->ctx.size() > 1) {
-            h->output_ctx = (int)(&c - h->ctx.data());
-            h->output_index = std::max(which, 0);
-            h->output_overwritten = false;
-        }
+        note_output(h, c, which);
         return RPTR_OK;
     }
     // work queued on the backend's stream from here on (tile copies, read-backs) sees this frame: the host has waited for its end, so
@@ -202,11 +270,7 @@ static int finish_frame(rptr_hip *h, FrameCtx &c, RptrStats *out_stats, int whic
     }
     c.batch_stats = st;
     st.spp = c.batch_spp_after[std::max(which, 0)];
-    if (h->ctx.size() > 1) {
-        h->output_ctx = (int)(&c - h->ctx.data());
-        h->output_index = std::max(which, 0);
-        h->output_overwritten = false;
-    }
+    note_output(h, c, which);
     h->aov_ctx = (int)(&c - h->ctx.data());
     h->aov_overwritten = false;
     if (h->local_rows > 0) {
@@ -293,8 +357,10 @@ static int check_render_arguments(rptr_hip_t *h, const RptrCamera *camera, bool 
     return RPTR_OK;
 }
 // the frame constants of a launch sequence (RpFrame: render / scene / lighting parameters, the camera basis of frame 0 and -- per_frame_cameras --
-// of every frame, the AOV view of the last frame, tiling and divisors, light bins); frame_id / sample bookkeeping is the caller's
-static void fill_frame_constants(rptr_hip_t *h, FrameCtx &c, const RptrCamera *camera, bool per_frame_cameras, int variant, int spp, int n_frames, int reset_rest, RpFrame &f) {
+// of every frame, the AOV view of the last frame, tiling and divisors, light bins, alpha test and point set); frame_id / sample bookkeeping is
+// the caller's. note_view: the last camera becomes the previous view of the next frame's motion vectors (a frame's does, a query run's does not)
+static void fill_frame_constants(rptr_hip_t *h, FrameCtx &c, const RptrCamera *camera, bool per_frame_cameras, int variant, int spp, int n_frames, int reset_rest, bool note_view,
+                                 RpFrame &f) {
     memset(&f, 0, sizeof(f));
     f.rp = h->params;
     f.sp = h->scene_params;
@@ -319,8 +385,10 @@ static void fill_frame_constants(rptr_hip_t *h, FrameCtx &c, const RptrCamera *c
         compute_view_projection(last, h->width, h->height, f.view, f.proj);
         compute_view_projection(before, h->width, h->height, f.view_ref, f.proj_ref);
         memcpy(f.aov_cam_pos, last.pos, sizeof(f.aov_cam_pos));
-        h->prev_camera = last;
-        h->have_prev_camera = true;
+        if (note_view) {
+            h->prev_camera = last;
+            h->have_prev_camera = true;
+        }
     }
     f.aov_albedo_roughness = c.aov[0];
     f.aov_normal_depth = c.aov[1];
@@ -358,105 +426,40 @@ static void fill_frame_constants(rptr_hip_t *h, FrameCtx &c, const RptrCamera *c
     // so it is off unless asked for. The separate counting-sort pass of rounds 1-2 (rp_k_sort_*: three launches per bounce, one frame
     // context only, 0.4 ms per frame) lost on every configuration and is gone (profiles/r03_notes.md section 6).
     f.regroup_materials = h->opt.v[OPT_REGROUP] != 0 ? 1 : 0;
+    f.alpha_test = h->uses_alpha ? 1 : 0;
+    f.rng_variant = h->rng_variant;
+    f.rng_table = h->rng_table;
 }
-static int render_batch_impl(rptr_hip_t *h, const RptrCamera *camera, bool per_frame_cameras, int variant, int spp, int n_frames, int reset_first, int reset_rest,
-                             int count_traversal, uint64_t *out_tickets) {
-    const int reset_accumulation = reset_first;
-    {
-        const int rc_args = check_render_arguments(h, camera, per_frame_cameras, variant, spp, n_frames);
-        if (rc_args) return rc_args;
+// ---- the steps of render_batch_impl, in the order it takes them
+// reprojection_mode 2: the images of realtime_resolve.h, made by the first frame that needs them
+static int ensure_realtime_images(rptr_hip_t *h, bool taa) {
+    const size_t npix = (size_t)h->width * (size_t)h->local_rows;
+    int rc = RPTR_OK;
+    if (!h->rt.cur) {
+        if ((rc = dev_alloc(h, &h->rt.cur, npix, nullptr)) || (rc = dev_alloc(h, &h->rt.accum_other, npix, nullptr)) ||
+            (rc = dev_alloc(h, &h->rt.nd[0], npix, nullptr)) || (rc = dev_alloc(h, &h->rt.nd[1], npix, nullptr)))
+            return rc;
+        h->rt.chain = false;
     }
-    HIP_TRY(h, hipSetDevice(h->device));
-    FrameCtx &c = h->ctx[(size_t)h->next_ctx];
-    if (c.pending)
-        return fail(h, RPTR_E_INVALID, "all %zu frames in flight are busy: rptr_hip_wait for ticket %llu first", h->ctx.size(),
-                    (unsigned long long)c.ticket);
-    h->next_ctx = (h->next_ctx + 1) % (int)h->ctx.size();
-    const bool multi = h->ctx.size() > 1;
-    if (multi) { // this context's images are about to be rewritten: what was queued on the backend's stream so far still sees the old
-                 // ones (ev_dep below), a read-back issued after this submission would not
-        if ((int)(&c - h->ctx.data()) == h->output_ctx) h->output_overwritten = true;
-        if ((int)(&c - h->ctx.data()) == h->aov_ctx) h->aov_overwritten = true;
+    if (taa && !h->rt.fb_pre) {
+        if ((rc = dev_alloc(h, &h->rt.fb_pre, npix, nullptr)) || (rc = dev_alloc(h, &h->rt.fb_other, npix, nullptr))) return rc;
     }
-    // begin_frame: render_vulkan.cpp:1937-1941
-    if (reset_accumulation) {
-        if (!h->freeze_frame) h->frame_offset += h->frame_id;
-        h->frame_id = 0;
-    }
-    const uint32_t frame_id_before = h->frame_id;
-    // reprojection_mode 2: the images of realtime_resolve.h, made by the first frame that needs them
-    const bool realtime = h->params.reprojection_mode == 2 && h->local_rows > 0;
-    const bool taa = realtime && h->opt.v[OPT_TAA] != 0;
-    if (realtime) {
-        const size_t npix = (size_t)h->width * (size_t)h->local_rows;
-        int rc = RPTR_OK;
-        if (!h->rt.cur) {
-            if ((rc = dev_alloc(h, &h->rt.cur, npix, nullptr)) || (rc = dev_alloc(h, &h->rt.accum_other, npix, nullptr)) ||
-                (rc = dev_alloc(h, &h->rt.nd[0], npix, nullptr)) || (rc = dev_alloc(h, &h->rt.nd[1], npix, nullptr)))
-                return rc;
-            h->rt.chain = false;
-        }
-        if (taa && !h->rt.fb_pre) {
-            if ((rc = dev_alloc(h, &h->rt.fb_pre, npix, nullptr)) || (rc = dev_alloc(h, &h->rt.fb_other, npix, nullptr))) return rc;
-        }
-    }
-    RpFrame f;
-    fill_frame_constants(h, c, camera, per_frame_cameras, variant, spp, n_frames, reset_rest, f);
-    size_t ev_cursor = 0;
-    c.spans.clear();
-    auto timed_on = [&](hipStream_t st, int kind, auto &&launch) {
-        if (h->stage_timing >= 2 || (h->stage_timing == 1 && kind == 0)) {
-            hipEvent_t a = next_event(c, ev_cursor), b = next_event(c, ev_cursor);
-            (void)hipEventRecord(a, st);
-            launch();
-            (void)hipEventRecord(b, st);
-            c.spans.push_back({a, b, kind});
-        } else
-            launch();
-    };
-    auto timed = [&](int kind, auto &&launch) { timed_on(c.stream, kind, launch); };
-    // a stage that is ONE kernel: its start / stop events ride on the dispatch packet itself (hipExtLaunchKernelGGL), no extra
-    // barrier packets in the queue -- the command processor's packet rate is what bounds small frames (profiles/r01_notes.md)
-    auto timed_kernel = [&](hipStream_t st, int kind, auto kernel, dim3 grid, dim3 block, auto... args) {
-        if (h->stage_timing >= 2 || (h->stage_timing == 1 && kind == 0)) {
-            hipEvent_t a = next_event(c, ev_cursor), b = next_event(c, ev_cursor);
-            hipExtLaunchKernelGGL(kernel, grid, block, 0, st, a, b, 0, args...);
-            c.spans.push_back({a, b, kind});
-        } else
-            hipLaunchKernelGGL(kernel, grid, block, 0, st, args...);
-    };
-    // ... the same for the path stages, whose kernels are picked by the launchers of launch.h
-    auto timed_launch = [&](hipStream_t st, int kind, unsigned grid) -> RpLaunch {
-        RpLaunch l = {grid, st, nullptr, nullptr};
-        if (h->stage_timing >= 2 || (h->stage_timing == 1 && kind == 0)) {
-            l.start = next_event(c, ev_cursor);
-            l.stop = next_event(c, ev_cursor);
-            c.spans.push_back({l.start, l.stop, kind});
-        }
-        return l;
-    };
-    // the general instantiation of the path stages: a table point set, or a screen jitter (raster TAA) -- the shipped path carries neither
-    // (path_kernel_flags: f.rng_variant is set below from the same h->rng_variant)
-    const bool table_rng_later = h->rng_variant != RPTR_RNG_VARIANT_UNIFORM || h->params.enable_raster_taa != 0;
-    const bool table_rng = table_rng_later;
-    // the frames of this handle that will share the GPU with this one: those still in flight on the device (up to the most that can run
-    // side by side). A frame alone gets the full grids (and, when the library chose side streams, its side stream); counted frames are
-    // launched as frames side by side are.
+    return RPTR_OK;
+}
+// The traversal grids of the frame submitted on `c`, and whether its shadow rays go to the side stream, for the frames of this handle that
+// will share the GPU with it: those still in flight on the device (up to the most that can run side by side). A frame alone gets the full
+// grids (and, when the library chose side streams, its side stream); counted frames are launched as frames side by side are.
+static void plan_frame_grids(rptr_hip_t *h, FrameCtx &c, int count_traversal, int grids[4], bool *side) {
     int concurrency = 1;
     for (FrameCtx &o : h->ctx)
         if (concurrency < h->max_concurrency && &o != &c && o.pending && !o.synced && hipEventQuery(o.ev_end) != hipSuccess) ++concurrency;
     const bool alone = concurrency == 1;
-    bool side = c.side != nullptr;
-    if (side && h->side_only_alone && !alone) side = false;
+    *side = c.side != nullptr && !(h->side_only_alone && !alone);
     if (count_traversal) concurrency = h->max_concurrency;
-    const int blocks_first = traversal_grid(h, 0, concurrency), blocks_later = traversal_grid(h, 1, concurrency);
-    const int blocks_connect[2] = {traversal_grid(h, 2, concurrency), traversal_grid(h, 3, concurrency)};
-    h->last_grids[0] = blocks_first;
-    h->last_grids[1] = blocks_later;
-    h->last_grids[2] = blocks_connect[0];
-    h->last_grids[3] = blocks_connect[1];
-
-    SceneCopy &scn = h->ctx_scene.empty() ? h->master : h->ctx_scene[(size_t)(&c - h->ctx.data())];
+    for (int kind = 0; kind < 4; ++kind) h->last_grids[kind] = grids[kind] = traversal_grid(h, kind, concurrency);
+}
+// The context's scene follows the master, behind whatever the caller queued on the backend's stream
+static int follow_master_scene(rptr_hip_t *h, FrameCtx &c, SceneCopy &scn) {
     const bool follow = !h->ctx_scene.empty() && scn.version != h->refit_version;
     if (follow) {
         // this context's own vertices follow the master set: the copy of the float positions is queued on the backend's stream,
@@ -471,7 +474,7 @@ static int render_batch_impl(rptr_hip_t *h, const RptrCamera *camera, bool per_f
     // whatever the caller queued on the backend's stream (vertex updates, the copy above) comes first. When that stream has nothing
     // unfinished there is nothing to wait for, and no event is recorded: an event on a stream that shares its hardware queue with another
     // frame context completes only after that context's frame, and would serialise the frames in flight.
-    if (multi && hipStreamQuery(h->stream) != hipSuccess) {
+    if (h->ctx.size() > 1 && hipStreamQuery(h->stream) != hipSuccess) {
         HIP_TRY(h, hipEventRecord(c.ev_dep, h->stream));
         HIP_TRY(h, hipStreamWaitEvent(c.stream, c.ev_dep, 0));
     }
@@ -484,124 +487,64 @@ static int render_batch_impl(rptr_hip_t *h, const RptrCamera *camera, bool per_f
         // advance, and the failures are counted (rptr_hip_get_option(h, "bvh_rebuild_failures"))
         if (err != RPTR_OK) h->rebuild_failures++;
     }
-    if (c.gather_pending) { // the image this context produced last is still being sent to rank 0 (host_comm.h)
-        HIP_TRY(h, hipStreamWaitEvent(c.stream, c.ev_gather, 0));
-        c.gather_pending = false;
-    }
-    HIP_TRY(h, hipEventRecord(c.ev_begin, c.stream));
-    c.launches_extend = c.launches_connect = 0;
-    memset(&c.earlier_batches, 0, sizeof(c.earlier_batches));
-    memset(c.host_counters, 0, sizeof(RpCounters));
-    int remaining = spp * n_frames; // (n_frames > 1: one internal batch holds them all, checked above)
-    const bool local_work = h->local_rows > 0;
-    f.frame_id = h->frame_id; // the whole call is one frame of the reference (its batch_spp = spp), whatever the internal batches
-    f.alpha_test = h->uses_alpha ? 1 : 0;
-    f.rng_variant = h->rng_variant;
-    f.rng_table = h->rng_table;
-    const bool single = h->master.dscene.single_instance != 0;
-    while (remaining > 0) {
-        const int batch = std::min(remaining, h->max_batch_spp);
-        f.sample_base = h->frame_id;
-        f.batch_spp = batch;
-        if (local_work) {
-            HIP_TRY(h, hipMemsetAsync(c.counters, 0, sizeof(RpCounters), c.stream));
-            // the first bounce's queue is the identity over the batch's path ids and is not stored (kernels.h)
-            const uint32_t first_count = (uint32_t)((size_t)batch * h->npix_padded);
-            const uint32_t *first_ids = nullptr;
-            HIP_TRY(h, hipMemsetD32Async((hipDeviceptr_t)&c.counters->bounce[0].queue_count, (int)first_count, 1, c.stream));
-            // the late bounces in one launch (kernels.h rp_k_tail); counting keeps the stand-alone kernels
-            const int tail_from = tail_hand_over(h, count_traversal != 0);
-            c.tail_from = tail_from;
-            for (int b = 0; b < h->params.max_path_depth; ++b) {
-                const int in = b & 1, out = in ^ 1;
-                RpBounceCounters *bc = &c.counters->bounce[b];
-                if (b == tail_from) {
-                    if (side && b > 0) HIP_TRY(h, hipStreamWaitEvent(c.stream, c.ev_side, 0)); // join: connect(b-1) on the side stream
-                    const PathKernelFlags k = path_kernel_flags(h, scn.dscene, f);
-                    rp_launch_tail(variant, k.fast_math, timed_launch(c.stream, 3, (unsigned)h->tail_blocks), k.lights, k.full, k.single, k.table_rng, scn.dscene, f, c.ps, c.sq,
-                                   (const uint32_t *)c.queue[in], c.counters, b, c.gstack);
-                    break;
-                }
-                rp_launch_extend(timed_launch(c.stream, 0, (unsigned)(b == 0 ? blocks_first : blocks_later)), count_traversal, b == 0, h->uses_alpha, single, b == 0 ? table_rng : table_rng_later, scn.dscene, f, c.ps,
-                                 b == 0 ? first_ids : (const uint32_t *)c.queue[in], bc, c.counters, c.gstack);
-                c.launches_extend++;
-                const uint32_t *in_queue = b == 0 ? first_ids : c.queue[in];
-                const uint32_t *order = in_queue;
-                if (side && b > 0) HIP_TRY(h, hipStreamWaitEvent(c.stream, c.ev_side, 0)); // join: connect(b-1) wrote illum, frees the shadow queue
-                timed(2, [&] {
-                    launch_shade(h, c, variant, scn.dscene, f, order, b, out);
-                });
-                {
-                    hipStream_t cs = side ? c.side : c.stream;
-                    int *stack = side ? c.gstack_side : c.gstack;
-                    if (side) { // fork: the side stream sees shade(b)
-                        HIP_TRY(h, hipEventRecord(c.ev_fork, c.stream));
-                        HIP_TRY(h, hipStreamWaitEvent(c.side, c.ev_fork, 0));
-                    }
-                    rp_launch_connect(timed_launch(cs, 1, (unsigned)blocks_connect[single ? 1 : 0]), count_traversal, h->uses_alpha, single, scn.dscene, f, c.ps, c.sq, bc, c.counters,
-                                      stack);
-                    if (side) HIP_TRY(h, hipEventRecord(c.ev_side, c.side));
-                }
-                c.launches_connect++;
-            }
-            if (side) HIP_TRY(h, hipStreamWaitEvent(c.stream, c.ev_side, 0)); // the last connect
-            // resolves fold into one history buffer: they run in submission order across the contexts
-            if (multi && h->last_resolved && h->last_resolved != c.ev_resolved) HIP_TRY(h, hipStreamWaitEvent(c.stream, h->last_resolved, 0));
-            {
-                const size_t npix = (size_t)h->width * h->local_rows;
-                if (!realtime)
-                    timed_kernel(c.stream, 4, rp_k_resolve, dim3(grid_for(h, npix)), dim3(256), f, c.ps, h->accum, h->fb, c.out_accum, c.out_fb);
-                else // the mean of this frame's samples (kernels_misc.h), then, after its last batch, the reprojection (and TAA) passes
-                    timed_kernel(c.stream, 4, rp_k_resolve, dim3(grid_for(h, npix)), dim3(256), f, c.ps, h->rt.cur, (uchar4 *)nullptr,
-                                 (float4 *)nullptr, (uchar4 *)nullptr);
-            }
-            if (realtime && remaining - batch == 0) {
-                // process_taa.cpp:92 reads frame_id after end_frame: this call's samples included
-                const bool taa_now = taa && frame_id_before + (uint32_t)spp > 1u;
-                RpReprojectArgs ra;
-                ra.cur = h->rt.cur;
-                ra.nd = c.aov[1];
-                ra.mj = c.aov[2];
-                ra.hist = h->accum;
-                ra.hist_nd = h->rt.nd[h->rt.parity];
-                ra.accum = h->rt.accum_other;
-                ra.out_nd = h->rt.nd[h->rt.parity ^ 1];
-                ra.fb = taa_now ? h->rt.fb_pre : h->fb;
-                ra.fb_keep = h->fb;
-                ra.out_accum = c.out_accum;
-                ra.out_fb = c.out_fb; // (with TAA, rp_k_taa overwrites it with the frame after the pass)
-                ra.min_sample_weight = 1.0f / float(h->params.spp_accumulation_window);
-                ra.sample_batch_size = spp;
-                ra.use_history = (f.frame_id > 0 && h->rt.chain) ? 1 : 0;
-                const dim3 tiles((unsigned)((h->width + RP_RT_TILE - 1) / RP_RT_TILE), (unsigned)((h->local_rows + RP_RT_TILE - 1) / RP_RT_TILE));
-                timed_kernel(c.stream, 4, rp_k_reproject, tiles, dim3(64), f, ra);
-                std::swap(h->accum, h->rt.accum_other);
-                h->rt.parity ^= 1;
-                if (taa_now) {
-                    timed_kernel(c.stream, 4, rp_k_taa, tiles, dim3(64), f, (const uchar4 *)h->rt.fb_pre, (const uchar4 *)h->fb, (const uint2 *)c.aov[2],
-                                 h->rt.fb_other, c.out_fb);
-                    std::swap(h->fb, h->rt.fb_other);
-                }
-            }
-            if (multi) { // (the resolve also kept a copy of the image this frame produced: the next frame's resolve overwrites the shared buffers)
-                HIP_TRY(h, hipEventRecord(c.ev_resolved, c.stream));
-                h->last_resolved = c.ev_resolved;
-            }
-            HIP_TRY(h, hipMemcpyAsync(c.host_counters, c.counters, sizeof(RpCounters), hipMemcpyDeviceToHost, c.stream));
-            // the host copy above must land before the next batch's memset: batches are few, sync here
-            if (remaining - batch > 0) {
-                HIP_TRY(h, hipStreamSynchronize(c.stream));
-                add_counters(c.earlier_batches, *c.host_counters);
-                memset(c.host_counters, 0, sizeof(RpCounters));
-            }
+    return RPTR_OK;
+}
+// The resolve of one internal batch and, in reprojection_mode 2 after the
+// frame's last batch (spp: the frame's), the reprojection and TAA passes; resolves run in submission order across the contexts
+static int queue_resolve(rptr_hip_t *h, FrameCtx &c, const RpFrame &f, StageTimer *timer, bool realtime, bool last_batch, int spp, bool taa_now) {
+    const bool multi = h->ctx.size() > 1;
+    // resolves fold into one history buffer: they run in submission order across the contexts
+    if (multi && h->last_resolved && h->last_resolved != c.ev_resolved) HIP_TRY(h, hipStreamWaitEvent(c.stream, h->last_resolved, 0));
+    const RpLaunch l_resolve = timed_launch(timer, c.stream, 4, (unsigned)grid_for(h, (size_t)h->width * h->local_rows));
+    if (!realtime)
+        rp_launch_kernel(l_resolve, rp_k_resolve, 256u, f, c.ps, h->accum, h->fb, c.out_accum, c.out_fb);
+    else // the mean of this frame's samples (kernels_misc.h), then, after its last batch, the reprojection (and TAA) passes
+        rp_launch_kernel(l_resolve, rp_k_resolve, 256u, f, c.ps, h->rt.cur, (uchar4 *)nullptr, (float4 *)nullptr, (uchar4 *)nullptr);
+    if (realtime && last_batch) {
+        RpReprojectArgs ra;
+        ra.cur = h->rt.cur;
+        ra.nd = c.aov[1];
+        ra.mj = c.aov[2];
+        ra.hist = h->accum;
+        ra.hist_nd = h->rt.nd[h->rt.parity];
+        ra.accum = h->rt.accum_other;
+        ra.out_nd = h->rt.nd[h->rt.parity ^ 1];
+        ra.fb = taa_now ? h->rt.fb_pre : h->fb;
+        ra.fb_keep = h->fb;
+        ra.out_accum = c.out_accum;
+        ra.out_fb = c.out_fb; // (with TAA, rp_k_taa overwrites it with the frame after the pass)
+        ra.min_sample_weight = 1.0f / float(h->params.spp_accumulation_window);
+        ra.sample_batch_size = spp;
+        ra.use_history = (f.frame_id > 0 && h->rt.chain) ? 1 : 0;
+        const dim3 tiles((unsigned)((h->width + RP_RT_TILE - 1) / RP_RT_TILE), (unsigned)((h->local_rows + RP_RT_TILE - 1) / RP_RT_TILE));
+        rp_launch_kernel(timed_launch(timer, c.stream, 4, tiles), rp_k_reproject, 64u, f, ra);
+        std::swap(h->accum, h->rt.accum_other);
+        h->rt.parity ^= 1;
+        if (taa_now) {
+            rp_launch_kernel(timed_launch(timer, c.stream, 4, tiles), rp_k_taa, 64u, f, (const uchar4 *)h->rt.fb_pre, (const uchar4 *)h->fb, (const uint2 *)c.aov[2],
+                             h->rt.fb_other, c.out_fb);
+            std::swap(h->fb, h->rt.fb_other);
         }
-        // end_frame: render_vulkan.cpp:2152-2154
-        if (n_frames == 1) {
-            h->accumulated_spp = int(h->frame_id) + batch;
-            h->frame_id += (uint32_t)batch;
-        }
-        remaining -= batch;
     }
+    if (multi) { // (the resolve also kept a copy of the image this frame produced: the next frame's resolve overwrites the shared buffers)
+        HIP_TRY(h, hipEventRecord(c.ev_resolved, c.stream));
+        h->last_resolved = c.ev_resolved;
+    }
+    return RPTR_OK;
+}
+// The counters of one internal batch come back to the host; between batches the host waits for them
+static int read_back_counters(rptr_hip_t *h, FrameCtx &c, bool more_batches) {
+    HIP_TRY(h, hipMemcpyAsync(c.host_counters, c.counters, sizeof(RpCounters), hipMemcpyDeviceToHost, c.stream));
+    // the host copy above must land before the next batch's memset: batches are few, sync here
+    if (more_batches) {
+        HIP_TRY(h, hipStreamSynchronize(c.stream));
+        add_counters(c.earlier_batches, *c.host_counters);
+        memset(c.host_counters, 0, sizeof(RpCounters));
+    }
+    return RPTR_OK;
+}
+// The end of the submission: the sample counts of a batch's frames, the end event, the tickets
+static int close_submission(rptr_hip_t *h, FrameCtx &c, int spp, int n_frames, int reset_rest, bool realtime, uint32_t frame_id_before, uint64_t *out_tickets) {
     c.batch_spp_after[0] = h->accumulated_spp;
     if (n_frames > 1) { // begin_frame / end_frame of every frame of the batch (kernels: dshade.h rp_slot_frame)
         for (int k = 0; k < n_frames; ++k) {
@@ -628,6 +571,83 @@ static int render_batch_impl(rptr_hip_t *h, const RptrCamera *camera, bool per_f
     if (out_tickets)
         for (int k = 0; k < n_frames; ++k) out_tickets[k] = c.ticket + (uint64_t)k;
     return RPTR_OK;
+}
+
+static int render_batch_impl(rptr_hip_t *h, const RptrCamera *camera, bool per_frame_cameras, int variant, int spp, int n_frames, int reset_first, int reset_rest,
+                             int count_traversal, uint64_t *out_tickets) {
+    int rc = check_render_arguments(h, camera, per_frame_cameras, variant, spp, n_frames);
+    if (rc) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    FrameCtx &c = h->ctx[(size_t)h->next_ctx];
+    if (c.pending)
+        return fail(h, RPTR_E_INVALID, "all %zu frames in flight are busy: rptr_hip_wait for ticket %llu first", h->ctx.size(),
+                    (unsigned long long)c.ticket);
+    h->next_ctx = (h->next_ctx + 1) % (int)h->ctx.size();
+    if (h->ctx.size() > 1) { // this context's images are about to be rewritten: what was queued on the backend's stream so far still sees the old
+                             // ones (ev_dep, follow_master_scene), a read-back issued after this submission would not
+        if ((int)(&c - h->ctx.data()) == h->output_ctx) h->output_overwritten = true;
+        if ((int)(&c - h->ctx.data()) == h->aov_ctx) h->aov_overwritten = true;
+    }
+    // begin_frame: render_vulkan.cpp:1937-1941
+    if (reset_first) {
+        if (!h->freeze_frame) h->frame_offset += h->frame_id;
+        h->frame_id = 0;
+    }
+    const uint32_t frame_id_before = h->frame_id;
+    const bool realtime = h->params.reprojection_mode == 2 && h->local_rows > 0;
+    const bool taa = realtime && h->opt.v[OPT_TAA] != 0;
+    if (realtime && (rc = ensure_realtime_images(h, taa))) return rc;
+    RpFrame f;
+    fill_frame_constants(h, c, camera, per_frame_cameras, variant, spp, n_frames, reset_rest, true, f);
+    f.frame_id = h->frame_id; // the whole call is one frame of the reference (its batch_spp = spp), whatever the internal batches
+    c.spans.clear();
+    StageTimer timer = {&c, 0, h->stage_timing};
+    SceneCopy &scn = h->ctx_scene.empty() ? h->master : h->ctx_scene[(size_t)(&c - h->ctx.data())];
+    PathRun run = {};
+    run.c = &c;
+    run.scene = &scn.dscene;
+    run.f = &f;
+    run.variant = variant;
+    run.stream = c.stream;
+    bool side = false;
+    plan_frame_grids(h, c, count_traversal, run.grids, &side);
+    run.side = side ? c.side : nullptr;
+    run.grid_shade = grid_for(h, h->path_capacity);
+    run.grid_tail = h->tail_blocks;
+    run.count_traversal = count_traversal != 0;
+    run.timer = &timer;
+    if ((rc = follow_master_scene(h, c, scn))) return rc;
+    if (c.gather_pending) { // the image this context produced last is still being sent to rank 0 (host_comm.h)
+        HIP_TRY(h, hipStreamWaitEvent(c.stream, c.ev_gather, 0));
+        c.gather_pending = false;
+    }
+    HIP_TRY(h, hipEventRecord(c.ev_begin, c.stream));
+    BounceLaunches launched;
+    memset(&c.earlier_batches, 0, sizeof(c.earlier_batches));
+    memset(c.host_counters, 0, sizeof(RpCounters));
+    int remaining = spp * n_frames; // (n_frames > 1: one internal batch holds them all, checked above)
+    while (remaining > 0) {
+        const int batch = std::min(remaining, h->max_batch_spp);
+        f.sample_base = h->frame_id;
+        f.batch_spp = batch;
+        if (h->local_rows > 0) {
+            c.tail_from = run.tail_from = tail_hand_over(h, run.count_traversal);
+            if ((rc = queue_path_bounces(h, run, launched))) return rc;
+            // process_taa.cpp:92 reads frame_id after end_frame: this call's samples included
+            const bool taa_now = taa && frame_id_before + (uint32_t)spp > 1u;
+            if ((rc = queue_resolve(h, c, f, &timer, realtime, remaining - batch == 0, spp, taa_now))) return rc;
+            if ((rc = read_back_counters(h, c, remaining - batch > 0))) return rc;
+        }
+        // end_frame: render_vulkan.cpp:2152-2154
+        if (n_frames == 1) {
+            h->accumulated_spp = int(h->frame_id) + batch;
+            h->frame_id += (uint32_t)batch;
+        }
+        remaining -= batch;
+    }
+    c.launches_extend = launched.extend;
+    c.launches_connect = launched.connect;
+    return close_submission(h, c, spp, n_frames, reset_rest, realtime, frame_id_before, out_tickets);
 }
 } // extern "C++"
 
@@ -663,35 +683,26 @@ static int radiance_queries_on(rptr_hip_t *h, const RptrRenderRayQuery *dq, int 
                                hipStream_t st, RpCounters *totals) {
     if (n == 0) return RPTR_OK;
     FrameCtx &c = h->ctx[0];
-    const SceneCopy &scn = h->master;
     RpFrame f;
-    {
-        const RptrCamera keep = h->prev_camera; // (fill_frame_constants notes the view for the next frame's motion vectors: not a query run's)
-        const bool have = h->have_prev_camera;
-        fill_frame_constants(h, c, camera, false, variant, 1, 1, 0, f);
-        h->prev_camera = keep;
-        h->have_prev_camera = have;
-    }
+    fill_frame_constants(h, c, camera, false, variant, 1, 1, 0, false, f);
     f.aov_albedo_roughness = f.aov_normal_depth = f.aov_motion_jitter = nullptr;
-    f.alpha_test = h->uses_alpha ? 1 : 0;
-    f.rng_variant = h->rng_variant;
-    f.rng_table = h->rng_table;
     const int slice_rows = h->local_rows; // (world_size 1: the frame's height)
     f.world = 1;
     f.stripe_rows = slice_rows;
     f.div_stripe_rows = rp_make_div((uint32_t)slice_rows);
-    f.frame_spp = 1;
-    f.div_frame_spp = rp_make_div(1u);
-    f.batch_reset = 0;
     const RpQueries rq = {dq, (uint32_t)n, 0u};
-    const PathKernelFlags k = path_kernel_flags(h, scn.dscene, f);
-    const bool table_rng = k.table_rng, single = k.single, lights = k.lights, fast_math = k.fast_math;
-    const int depth = h->params.max_path_depth;
-    // (nothing else of this handle is on the GPU: the grids of a frame alone)
-    const unsigned blocks_first = (unsigned)traversal_grid(h, 0, 1), blocks_later = (unsigned)traversal_grid(h, 1, 1);
-    const unsigned blocks_connect = (unsigned)traversal_grid(h, single ? 3 : 2, 1);
-    const unsigned blocks_shade = (unsigned)grid_for(h, h->path_capacity);
-    const int tail_from = tail_hand_over(h, false);
+    PathRun run = {};
+    run.c = &c;
+    run.scene = &h->master.dscene;
+    run.f = &f;
+    run.variant = variant;
+    run.stream = st;
+    for (int kind = 0; kind < 4; ++kind) run.grids[kind] = traversal_grid(h, kind, 1); // (nothing else of this handle is on the GPU: the grids of a frame alone)
+    run.grid_shade = grid_for(h, h->path_capacity);
+    run.grid_tail = h->tail_blocks;
+    run.tail_from = tail_hand_over(h, false);
+    run.queries = &rq;
+    BounceLaunches launched; // (a frame's statistic: dropped)
     const long long total_rows = ((long long)n + h->width - 1) / h->width;
     for (long long row0 = 0; row0 < total_rows; row0 += slice_rows) {
         f.rank = (int)(row0 / slice_rows);
@@ -702,32 +713,8 @@ static int radiance_queries_on(rptr_hip_t *h, const RptrRenderRayQuery *dq, int 
             f.frame_id = f.sample_base;
             f.batch_spp = batch;
             f.batch_frames = batch; // one "frame" per sample slot (dshade.h rp_slot_frame): frame_id = sample_index
-            HIP_TRY(h, hipMemsetAsync(c.counters, 0, sizeof(RpCounters), st));
-            const uint32_t first_count = (uint32_t)((size_t)batch * h->npix_padded); // the identity queue over the batch's path ids
-            HIP_TRY(h, hipMemsetD32Async((hipDeviceptr_t)&c.counters->bounce[0].queue_count, (int)first_count, 1, st));
-            const RpLaunch l_first = {blocks_first, st, nullptr, nullptr}, l_later = {blocks_later, st, nullptr, nullptr};
-            const RpLaunch l_connect = {blocks_connect, st, nullptr, nullptr}, l_shade = {blocks_shade, st, nullptr, nullptr};
-            for (int b = 0; b < depth; ++b) {
-                const int in = b & 1, out = in ^ 1;
-                RpBounceCounters *bc = &c.counters->bounce[b];
-                if (b == tail_from) {
-                    const bool full = k.full;
-                    const RpLaunch l_tail = {(unsigned)h->tail_blocks, st, nullptr, nullptr};
-                    rp_launch_tail(variant, fast_math, l_tail, lights, full, single, table_rng, scn.dscene, f, c.ps, c.sq, (const uint32_t *)c.queue[in], c.counters, b,
-                                   c.gstack);
-                    break;
-                }
-                if (b == 0) {
-                    rp_launch_extend_query(l_first, h->uses_alpha, single, table_rng, scn.dscene, f, c.ps, rq, bc, c.counters, c.gstack);
-                    rp_launch_shade_query(variant, fast_math, l_shade, lights, h->uses_textures, table_rng, scn.dscene, f, c.ps, c.sq,
-                                          (const uint32_t *)&bc->queue_count, c.queue[out], &c.counters->bounce[1].queue_count, &bc->shadow_count, c.counters);
-                } else {
-                    rp_launch_extend(l_later, false, false, h->uses_alpha, single, table_rng, scn.dscene, f, c.ps, (const uint32_t *)c.queue[in], bc, c.counters, c.gstack);
-                    rp_launch_shade(variant, fast_math, l_shade, false, lights, h->uses_textures, table_rng, scn.dscene, f, c.ps, c.sq, (const uint32_t *)c.queue[in],
-                                    (const uint32_t *)&bc->queue_count, c.queue[out], &c.counters->bounce[b + 1].queue_count, &bc->shadow_count, c.counters);
-                }
-                rp_launch_connect(l_connect, false, h->uses_alpha, single, scn.dscene, f, c.ps, c.sq, bc, c.counters, c.gstack);
-            }
+            const int rc = queue_path_bounces(h, run, launched);
+            if (rc) return rc;
             hipLaunchKernelGGL(rp_k_resolve_queries, dim3(grid_for(h, (size_t)h->width * (size_t)f.local_rows)), dim3(256), 0, st, f, c.ps, rq, dr);
             HIP_TRY(h, hipGetLastError());
             if (totals) {

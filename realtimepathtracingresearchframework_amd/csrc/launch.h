@@ -8,16 +8,16 @@
 #include "kernels.h"
 
 struct RpLaunch {
-    unsigned grid;
+    dim3 grid;
     hipStream_t stream;
     hipEvent_t start, stop; // non-NULL: start / stop events ride on the dispatch packet itself (hipExtLaunchKernelGGL)
 };
 template <class K, class... A>
 static inline void rp_launch_kernel(const RpLaunch &l, K kernel, unsigned block, A... args) {
     if (l.start)
-        hipExtLaunchKernelGGL(kernel, dim3(l.grid), dim3(block), 0, l.stream, l.start, l.stop, 0, args...);
+        hipExtLaunchKernelGGL(kernel, l.grid, dim3(block), 0, l.stream, l.start, l.stop, 0, args...);
     else
-        hipLaunchKernelGGL(kernel, dim3(l.grid), dim3(block), 0, l.stream, args...);
+        hipLaunchKernelGGL(kernel, l.grid, dim3(block), 0, l.stream, args...);
 }
 // run-time flag -> template argument: f(std::true_type) or f(std::false_type)
 template <class F>

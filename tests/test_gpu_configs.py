@@ -759,3 +759,46 @@ def test_light_sampling_variant_none_equals_a_scene_without_a_light_array():
     ok = np.isfinite(ref).all(axis=2)
     assert ok.mean() > 0.9 and np.array_equal(none[ok].view(np.uint32), ref[ok].view(np.uint32)) and int(st.raw.rays_shadow) == int(st_ref.raw.rays_shadow)
     assert np.array_equal(ris.view(np.uint32), ris2.view(np.uint32)) and not np.array_equal(ris, none)
+
+
+STAGE_TIME_FIELDS = ("extend_time_ms", "connect_time_ms", "shade_time_ms", "shade_only_time_ms", "tail_time_ms", "resolve_time_ms")
+
+
+@pytest.mark.parametrize("tail_bounce", [0, 1])
+def test_stage_timing_levels_fill_the_stage_times_and_change_nothing_else(tail_bounce):
+    """stage_timing 0 / 1 / 2 (rptr_hip_set_stage_timing) on one frame context, synchronously, without the tail kernel and with it from
+    bounce 1: level 0 fills render_time_ms alone, level 1 the closest-hit traversal time alone, level 2 every stage; the launch counts and
+    the image do not depend on the level. Every level renders on a fresh handle (the same seeds)."""
+    s = scenes.cornell32()
+    W, H, spp = 64, 48, 2
+    depth = abi.RenderParams.default().max_path_depth
+    assert depth >= 3
+    out = {}
+    for level in (0, 1, 2):
+        r = backend.RenderHip(frames_in_flight=1, options={"tail_bounce": tail_bounce})
+        r.initialize(W, H)
+        r.set_scene(s)
+        r.set_stage_timing(level)
+        st = r.render(backend.RenderConfiguration(s.camera_params(), active_variant=abi.VARIANT_GLTF, reset_accumulation=True), spp=spp).raw
+        img = np.zeros((H, W, 4), np.float32)
+        assert r.readback_framebuffer(img) == W * H * 4
+        r.close()
+        t = {k: float(getattr(st, k)) for k in STAGE_TIME_FIELDS + ("render_time_ms",)}
+        print("tail_bounce %d level %d: extend launches %d connect launches %d %s" % (tail_bounce, level, st.launches_extend, st.launches_connect, t))
+        out[level] = (t, int(st.launches_extend), int(st.launches_connect), img)
+    t0, t1, t2 = out[0][0], out[1][0], out[2][0]
+    assert t0["render_time_ms"] > 0 and all(t0[k] == 0 for k in STAGE_TIME_FIELDS), t0
+    assert t1["extend_time_ms"] > 0, t1
+    assert all(t1[k] == 0 for k in STAGE_TIME_FIELDS if k != "extend_time_ms"), t1
+    assert all(t2[k] > 0 for k in ("extend_time_ms", "connect_time_ms", "shade_only_time_ms", "resolve_time_ms")), t2
+    assert (t2["tail_time_ms"] > 0) == (out[2][1] < depth), (t2, out[2][1], depth)
+    # shade_time_ms sums the spans of shade, tail and resolve, its parts sum them by kind: float32 sums of at most depth + 2 positive
+    # terms each, relative error at most (depth + 2) * 2^-24 < 1e-6 on either side
+    parts = t2["shade_only_time_ms"] + t2["tail_time_ms"] + t2["resolve_time_ms"]
+    assert t2["shade_time_ms"] >= parts * (1 - 2e-6), t2
+    for t in (t1, t2):
+        assert all(t[k] <= t["render_time_ms"] for k in STAGE_TIME_FIELDS), t
+    assert out[0][1:3] == out[1][1:3] == out[2][1:3], [o[1:3] for o in out.values()]
+    assert out[0][1] == (depth if tail_bounce == 0 else 1)
+    for level in (1, 2):
+        assert np.array_equal(out[0][3].view(np.uint32), out[level][3].view(np.uint32)), level
