@@ -143,7 +143,26 @@ typedef struct RptrLightSamplingConfig {
  * starts from its mean. Mode 2 returns RPTR_E_UNSUPPORTED with world_size > 1 (a stripe's edge pixels reproject into other ranks' rows),
  * for launch sequences of several frames (rptr_hip_render_batch*_async with n_frames > 1) and with option "aovs" = 0 (no motion or
  * normal + depth); option "taa" = 1 with mode 1, or with render_upscale_factor 2, does too. Modes 0 and 1 launch nothing new.
- * (RPTR_HIP_ABI_VERSION stays: no layout changes, and mode 2 was accepted before -- as mode 0.) */
+ * (RPTR_HIP_ABI_VERSION stays: no layout changes, and mode 2 was accepted before -- as mode 0.)
+ *
+ * Depth of field: aperture_radius (scene units; default 0 = a pinhole, bit-identical to what earlier versions rendered whatever
+ * focus_distance holds) and focus_distance (scene units along the pinhole ray, default 2.5). With aperture_radius > 0 a camera ray of a
+ * frame starts on a uniformly sampled disc of that radius around the camera position, in the plane of the image axes, and passes through
+ * the point focus_distance along the pinhole ray of its pixel sample:
+ *     focus  = cam_pos + focus_distance * dir
+ *     r2     = the path's sample of dimensions DIM_APERTURE_X, _Y (pathspace.h:16-17: 4, 5; the uniform generator: its next two numbers
+ *              after the pixel-filter draw -- its first two with enable_raster_taa != 0, which makes no pixel-filter draw)
+ *     lens   = (cos(2 pi r2.x), sin(2 pi r2.x)) * sqrt(r2.y) * aperture_radius        [evaluated as sincospif(2 * r2.x)]
+ *     origin = cam_pos + lens.x * normalize(cam_du) + lens.y * normalize(cam_dv);  dir = normalize(focus - origin)
+ * with the frame's own camera when a launch sequence carries one per frame. Square root and normalisations are IEEE with option
+ * "fast_math" too. This is the rule of the reference's vulkan/raygen.rgen:151-160 and pipeline_pt/perspective.rgen:100-108; the
+ * pt_megakernel.glsl this library ports is pinhole only (:322-325), so the lens is a stated extension of that port, not parity with it.
+ * Not ported: the transport_footprint term of raygen.rgen:216-222 -- the texture footprint stays that of the pinhole axes
+ * (pt_megakernel.glsl:341-351). The AOVs keep their definitions (depth is the distance of the hit from the camera position). Ray and
+ * radiance queries carry their own origin and direction and ignore the lens. Lens frames run the general kernel instantiations (as
+ * raster TAA and table point sets do). A render call returns RPTR_E_INVALID for an aperture_radius that is negative or not finite, and,
+ * with aperture_radius > 0, for a focus_distance that is not finite or not > 0.
+ * focal_length is accepted and unread: no shipped GPU program of the reference reads it. */
 typedef struct RptrRenderParams {
     int32_t batch_spp;
     int32_t max_path_depth;

@@ -182,6 +182,9 @@ class RenderHip:
             self.set_option(k, v)
         # public data members the app mutates directly (render_backend.h:69-76)
         self.params = abi.RenderParams.default()
+        # RenderBackendOptions::enable_raytraced_dof (render_params.glsl.h:97, default true): a switch of this class, not a library option.
+        # False hands the library aperture_radius = focal_length = 0 (render_vulkan.cpp:2945-2947); self.params stays the caller's.
+        self.enable_raytraced_dof = True
         self.lighting_params = abi.LightSamplingConfig.default()
         self.scene_params = None
         self.camera = None
@@ -243,7 +246,11 @@ class RenderHip:
 
     def _push_params(self):
         self._check(self._L.rptr_hip_set_freeze_frame(self._h, 1 if self.freeze_frame else 0))
-        self._check(self._L.rptr_hip_set_params(self._h, C.byref(self.params), C.byref(self.scene_params) if self.scene_params else None,
+        params = self.params
+        if not self.enable_raytraced_dof:
+            params = abi.RenderParams.from_buffer_copy(self.params)
+            params.aperture_radius = params.focal_length = 0.0
+        self._check(self._L.rptr_hip_set_params(self._h, C.byref(params), C.byref(self.scene_params) if self.scene_params else None,
                                                 C.byref(self.lighting_params)))
 
     def begin_frame(self, cmd_stream, config: RenderConfiguration):

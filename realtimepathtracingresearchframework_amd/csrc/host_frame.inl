@@ -62,7 +62,7 @@ extern "C++" {
 // Which instantiations of the path stages a launch sequence runs, and where it hands over to the tail kernel
 struct PathKernelFlags {
     bool lights;    // light-sampling code: without emissive triangles and with all NEE probability on the sun that branch is dead code
-    bool table_rng; // the general instantiations: a table point set, or a screen jitter (raster TAA) -- the shipped path carries neither
+    bool table_rng; // the general instantiations: a table point set, a screen jitter (raster TAA) or a lens (aperture_radius > 0) -- the shipped path carries none
     bool single;    // the top level holds one instance record
     bool full;      // the tail kernel's one instantiation for textured and alpha-tested scenes
     bool fast_math;
@@ -70,7 +70,7 @@ struct PathKernelFlags {
 static PathKernelFlags path_kernel_flags(const rptr_hip *h, const RpScene &scene, const RpFrame &f) {
     PathKernelFlags k;
     k.lights = (h->num_lights > 0 && !h->lights_disabled) || f.sp.sun_radiance[3] < 1.0f;
-    k.table_rng = h->rng_variant != RPTR_RNG_VARIANT_UNIFORM || h->params.enable_raster_taa != 0;
+    k.table_rng = h->rng_variant != RPTR_RNG_VARIANT_UNIFORM || h->params.enable_raster_taa != 0 || f.rp.aperture_radius > 0.0f;
     k.single = scene.single_instance != 0; // (the same in every copy: set_scene decides it before it copies the master's RpScene, nothing writes it later)
     k.full = h->uses_textures || h->uses_alpha;
     k.fast_math = h->opt.v[OPT_FAST_MATH] != 0;
@@ -341,6 +341,11 @@ static int check_render_arguments(rptr_hip_t *h, const RptrCamera *camera, bool 
     if (variant != RPTR_VARIANT_GLTF && variant != RPTR_VARIANT_SIMPLE && variant != RPTR_VARIANT_GLTF_TRANSMISSION)
         return fail(h, RPTR_E_INVALID, "unknown variant %d", variant);
     if (spp < 1) return fail(h, RPTR_E_INVALID, "spp must be >= 1");
+    // the thin lens (kernels.h rp_primary_ray_ex); aperture_radius == 0 checks nothing: hosts pass whatever focus_distance they like
+    if (!(h->params.aperture_radius >= 0.0f) || !std::isfinite(h->params.aperture_radius))
+        return fail(h, RPTR_E_INVALID, "aperture_radius must be finite and >= 0 (is %g)", (double)h->params.aperture_radius);
+    if (h->params.aperture_radius > 0.0f && (!std::isfinite(h->params.focus_distance) || !(h->params.focus_distance > 0.0f)))
+        return fail(h, RPTR_E_INVALID, "focus_distance must be finite and > 0 with aperture_radius > 0 (is %g)", (double)h->params.focus_distance);
     // reprojection_mode 2 (realtime_resolve.h) covers one frame per call on one device with the AOV images
     if (h->params.reprojection_mode == 2) {
         if (h->world > 1)
@@ -685,6 +690,7 @@ static int radiance_queries_on(rptr_hip_t *h, const RptrRenderRayQuery *dq, int 
     FrameCtx &c = h->ctx[0];
     RpFrame f;
     fill_frame_constants(h, c, camera, false, variant, 1, 1, 0, false, f);
+    f.rp.aperture_radius = 0.0f; // a query's own origin and direction replace the camera ray, lens included (raygen.rgen:162-168): the same kernels, the same bits
     f.aov_albedo_roughness = f.aov_normal_depth = f.aov_motion_jitter = nullptr;
     const int slice_rows = h->local_rows; // (world_size 1: the frame's height)
     f.world = 1;

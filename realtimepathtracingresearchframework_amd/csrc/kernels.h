@@ -91,7 +91,7 @@ RP_DEV void rp_block_flush(const uint32_t *staged, uint32_t n_local, uint32_t *q
 // The camera ray of path p (pt_megakernel.glsl:314-325 + :330-352 pinhole branch): a pure function of the frame
 // constants and the path id, so nothing of it is stored -- the first extend and the first shade both call it
 // (saves writing and re-reading 72 bytes of path state per pixel sample). Returns false for padding slots.
-// origin: the camera position of the path's frame; du_dv (may be NULL): its image-plane axes. Frames with cameras of their own
+// origin: the camera position of the path's frame (a point of its lens with an aperture, below); du_dv (may be NULL): its image-plane axes. Frames with cameras of their own
 // (f.per_frame_cams; wave-uniform, so the branch is a scalar one) read cams[frame] per lane -- a launch sequence's frames differ by sample
 // slot, and a wave's pool may straddle two of them -- in every instantiation (round 4: routing them through the general TABLE kernels
 // cost 3-5 % of a C2 frame for what is three cached 16-byte loads per camera ray).
@@ -124,6 +124,25 @@ RP_DEV bool rp_primary_ray_ex(const RpFrame &f, uint32_t p, RpRng &rng, V3 &dir,
         du_dv[1] = dv;
     }
     dir = norm3_ieee(point.x * du + point.y * dv + tl); // (IEEE in both builds of the shading stages: the first extend and a first shade that makes the ray again agree)
+    // Thin lens (vulkan/raygen.rgen:151-160 = pipeline_pt/perspective.rgen:100-108; pt_megakernel.glsl:322-325 itself is pinhole only: a stated
+    // extension by its sibling integrators' rule). A frame with aperture_radius > 0 is rendered by the TABLE instantiation (host_frame.inl
+    // path_kernel_flags), whose first shade makes the camera ray again: the shipped path has no branch on it, stores no origin, and the
+    // per-path origin and the generator advanced by the two aperture draws reach the miss / sky path and bounce 0's emitter-MIS state from here.
+    // Draws: DIM_APERTURE_X, _Y (pathspace.h:16-17: dimensions 4, 5) of a table point set; the next two LCG numbers after the pixel-filter
+    // draw of the uniform generator (the first two with raster TAA, which makes none). cos / sin(2 pi x) are sincospif(2 x) (2 x is exact);
+    // normalisations and the square root are IEEE in both fast_math builds, like the pinhole direction. Not ported: the transport_footprint
+    // term of raygen.rgen:216-222 (the megakernel's texture footprint stays that of the pinhole axes, :341-351).
+    if (TABLE && f.rp.aperture_radius > 0.0f) {
+        const V3 focus = origin + f.rp.focus_distance * dir;
+        const V2 r2 = rp_draw2<TABLE>(f, rng, 4u /* DIM_APERTURE_X */);
+        float sn, cs;
+        sincospif(2.0f * r2.x, &sn, &cs);
+        const float rad = sqrtf(r2.y);
+        const V2 lens = v2((cs * rad) * f.rp.aperture_radius, (sn * rad) * f.rp.aperture_radius);
+        origin = origin + lens.x * norm3_ieee(du);
+        origin = origin + lens.y * norm3_ieee(dv);
+        dir = norm3_ieee(focus - origin);
+    }
     return true;
 }
 // the generator of path p at a later bounce: index / pixel recomputed, the state `s` from the path state

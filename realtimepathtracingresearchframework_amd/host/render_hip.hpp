@@ -44,10 +44,18 @@ struct RenderConfiguration { // librender/render_backend.h:33-40
 // carries the distinction.
 struct CommandStream {};
 
+// The RenderBackendOptions (render_params.glsl.h:74-99) that are switches of the HOST class alone, not keys of the library's option table.
+// enable_raytraced_dof: false hands the library aperture_radius = 0 and focal_length = 0 whatever `params` says (render_vulkan.cpp:2945-2947);
+// `params` itself stays the caller's.
+struct RenderBackendOptions {
+    bool enable_raytraced_dof = true;
+};
+
 class RenderHip {
 public:
     // public data members the app mutates directly (render_backend.h:69-76)
     RptrRenderParams params;
+    RenderBackendOptions options;
     RptrLightSamplingConfig lighting_params;
     RenderCameraParams camera;
     bool reset_accumulation = false;
@@ -355,9 +363,14 @@ private:
         if (rc == RPTR_OK) ++stats_serial_;
         if (rc != RPTR_OK && !(rc == RPTR_E_INVALID && std::string(rptr_hip_last_error(h_)).find("not in flight") != std::string::npos)) check(rc);
     }
+    RptrRenderParams effective_params(RptrRenderParams p) const { // what the library is handed: `options` applied to a copy
+        if (!options.enable_raytraced_dof) p.aperture_radius = p.focal_length = 0.f;
+        return p;
+    }
     int batch_spp(int spp) const { return spp > 0 ? spp : (params.batch_spp > 0 ? params.batch_spp : 1); }
     void push_state() { // RenderBackend::begin_frame "update params" (render_backend.cpp:17-23): the public members as they are NOW
-        check(rptr_hip_set_params(h_, &params, have_scene_params_ ? &scene_params_ : nullptr, &lighting_params));
+        const RptrRenderParams pushed = effective_params(params);
+        check(rptr_hip_set_params(h_, &pushed, have_scene_params_ ? &scene_params_ : nullptr, &lighting_params));
         check(rptr_hip_set_freeze_frame(h_, freeze_frame ? 1 : 0));
     }
     RptrCamera abi_camera() const {

@@ -1,0 +1,415 @@
+"""Thin-lens depth of field (RptrRenderParams.aperture_radius / focus_distance) on the device.
+
+The camera ray itself is probed (tests/device_probes/camera_probe.hip calls csrc/kernels.h rp_primary_ray_ex<true>) and compared with the
+numpy model of tests/dof_ref.py, which is fed the same generator numbers and the same camera basis bits. Tolerance of a ray: RAY_ULPS
+float32 ulps of the vector's largest component -- the model takes sin / cos of pi * (2 x) correctly rounded, the device's sincospif is
+an ulp or two from that; every other operation (+ - * / sqrt) is correctly rounded on both sides.
+
+Whole frames: aperture 0 renders what it always did, a lens frame is the same image by every route a frame can take, defocus has the
+width the model predicts, queries ignore the lens, bad parameters are refused."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import dof_ref as D
+import oracle_lib as O
+from realtimepathtracingresearchframework_amd import abi, backend, pointsets, scenes
+from realtimepathtracingresearchframework_amd.scenes import IDENTITY, Instance, ParameterizedMesh, Scene, SceneConfig, SKY_CONFIGS, _add_mesh, _quad
+
+pytestmark = pytest.mark.gpu
+
+RAY_ULPS = 4
+PW, PH, PSPP = 16, 8, 2  # the probed frame
+CAM_A = dict(pos=(0.3, 0.2, 0.9), dir=(-0.2672612419, -0.5345224838, -0.8017837257), up=(0.0, 1.0, 0.0), fovy=35.0)
+CAM_B = dict(pos=(-0.4, 0.6, 0.5), dir=(0.4242640687, -0.5656854249, -0.7071067812), up=(0.0, 1.0, 0.0), fovy=50.0)
+APERTURE, FOCUS = 0.1, 2.5
+
+
+# ------------------------------------------------------------------ the probe
+class CpArgs(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("frame_spp", C.c_int32), ("n_frames", C.c_int32), ("batch_reset", C.c_int32),
+                ("frame_offset", C.c_uint32), ("sample_base", C.c_uint32), ("frame_id", C.c_uint32), ("rng_variant", C.c_int32),
+                ("enable_raster_taa", C.c_int32), ("aperture_radius", C.c_float), ("focus_distance", C.c_float), ("per_frame_cams", C.c_int32),
+                ("_pad", C.c_int32), ("cams", (C.c_float * 12) * 8)]
+
+
+_LIB = None
+
+
+def _probe_lib():
+    global _LIB
+    if _LIB is None:
+        from device_probes import camera
+        if camera.needs_build():
+            camera.build()
+        _LIB = C.CDLL(camera.lib_path())
+        _LIB.cp_path_count.restype = C.c_int
+        _LIB.cp_path_count.argtypes = [C.POINTER(CpArgs)]
+        _LIB.cp_primary_rays.restype = C.c_int
+        _LIB.cp_primary_rays.argtypes = [C.POINTER(CpArgs), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    return _LIB
+
+
+def probe_rays(bases, aperture=APERTURE, focus=FOCUS, rng_variant=abi.RNG_VARIANT_UNIFORM, table=None, taa=0, n_frames=1, frame_offset=3,
+               frame_id=0):
+    """-> (origin, dir, state, px, py, sslot) of the pixel samples of the probed launch sequence (tile padding dropped)"""
+    a = CpArgs()
+    a.width, a.height, a.frame_spp, a.n_frames, a.batch_reset = PW, PH, PSPP, n_frames, 1
+    a.frame_offset, a.sample_base, a.frame_id = frame_offset, 0, frame_id
+    a.rng_variant, a.enable_raster_taa = rng_variant, taa
+    a.aperture_radius, a.focus_distance = aperture, focus
+    a.per_frame_cams = 1 if n_frames > 1 else 0
+    for k in range(8):
+        a.cams[k][:] = [float(x) for x in np.concatenate(bases[min(k, len(bases) - 1)])]
+    L = _probe_lib()
+    n = L.cp_path_count(C.byref(a))
+    assert n > 0
+    o, d = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32)
+    st, pix = np.zeros(n, np.uint32), np.zeros((n, 3), np.int32)
+    t = None if table is None else np.ascontiguousarray(table, np.uint32)
+    rc = L.cp_primary_rays(C.byref(a), None if t is None else t.ctypes.data_as(C.c_void_p), 0 if t is None else t.size, o.ctypes.data_as(C.c_void_p),
+                           d.ctypes.data_as(C.c_void_p), st.ctypes.data_as(C.c_void_p), pix.ctypes.data_as(C.c_void_p))
+    assert rc == 0
+    keep = pix[:, 0] >= 0
+    assert keep.sum() == PW * PH * PSPP * n_frames  # every pixel sample once
+    assert len(np.unique(pix[keep], axis=0)) == keep.sum()
+    return o[keep], d[keep], st[keep].astype(np.uint64), pix[keep, 0], pix[keep, 1], pix[keep, 2]
+
+
+def assert_rays(got, want, what):
+    for g, w, name in zip(got, want, ("origin", "direction")):
+        tol = RAY_ULPS * np.spacing(np.abs(w).max(axis=1).astype(np.float32)).astype(np.float64)
+        err = np.abs(g.astype(np.float64) - w.astype(np.float64)).max(axis=1)
+        print("%s %s: max error %.2f ulps of the largest component" % (what, name, (err / (tol / RAY_ULPS)).max()))
+        assert (err <= tol).all(), "%s %s: %d rays off by more than %d ulps (max %.1f)" % (what, name, (err > tol).sum(), RAY_ULPS,
+                                                                                          (err / (tol / RAY_ULPS)).max())
+
+
+def screen_jitter(frame_offset, frame_id, W, H):
+    """view_params.screen_jitter in float32, as csrc/dshade.h rp_screen_jitter computes it from the Halton table"""
+    h = O.halton23((frame_offset + frame_id) & 15)
+    w_, h_ = np.float32(W), np.float32(H)
+    return (np.float32(np.float32(h[0] * np.float32(2.0)) / w_) - np.float32(np.float32(1.0) / w_),
+            np.float32(np.float32(h[1] * np.float32(2.0)) / h_) - np.float32(np.float32(1.0) / h_))
+
+
+def test_lens_rays_uniform_generator():
+    basis = D.camera_basis(CAM_A, PW, PH)
+    o, d, st, px, py, ss = probe_rays([basis])
+    s0 = D.lcg_seed(ss, 3, px, py, PW)
+    s1, pixel_draw = D.lcg_draw2(s0)
+    s2, aperture_draw = D.lcg_draw2(s1)
+    assert_rays((o, d), D.lens_ray(None, PW, PH, px, py, pixel_draw, aperture_draw, APERTURE, FOCUS, basis=basis), "uniform")
+    assert np.abs(o - basis[0]).max() > 0.5 * APERTURE and not np.array_equal(o[0], o[1])  # a lens, one point per path
+    # the generator: the pinhole's state advanced by exactly two draws
+    po, pd, pst, ppx, ppy, pss = probe_rays([basis], aperture=0.0)
+    assert np.array_equal(ppx, px) and np.array_equal(ppy, py) and np.array_equal(pss, ss)
+    assert np.array_equal(pst, s1) and np.array_equal(st, D.lcg_next(D.lcg_next(pst))) and np.array_equal(st, s2)
+    # ... and aperture 0 is the pinhole ray, bit for bit
+    mo, md = D.lens_ray(None, PW, PH, px, py, pixel_draw, None, 0.0, FOCUS, basis=basis)
+    assert np.array_equal(po.view(np.uint32), mo.view(np.uint32)) and np.array_equal(pd.view(np.uint32), md.view(np.uint32))
+
+
+def _sobol_u32(matrices, index, dim):
+    r = np.zeros(len(index), np.uint64)
+    index = np.asarray(index, np.uint64).copy()
+    for j in range(32):
+        r ^= np.where((index >> np.uint64(j)) & np.uint64(1), np.uint64(matrices[dim, j]), np.uint64(0))
+    return r
+
+
+def test_lens_rays_sobol_take_dimensions_4_and_5():
+    basis = D.camera_basis(CAM_A, PW, PH)
+    table = pointsets.sobol_table()
+    m = pointsets.sobol_matrices()
+    o, d, st, px, py, ss = probe_rays([basis], rng_variant=abi.RNG_VARIANT_SOBOL, table=table)
+    # sobol.glsl: the scramble is an LCG seeded per pixel; every draw advances it and XORs it into the point's coordinate
+    s = D.murmur_finalize(D.murmur_mix(D.murmur_mix(np.uint64(0), px.astype(np.uint64) + py.astype(np.uint64) * np.uint64(PW)), np.uint64(3)))
+    vals = []
+    for dim in (0, 1, 4, 5):
+        s = D.lcg_next(s)
+        u = _sobol_u32(m, ss, dim) ^ s
+        vals.append((u.astype(np.uint32).astype(np.float32) * np.float32(2.0 ** -32)).astype(np.float32))
+    assert_rays((o, d), D.lens_ray(None, PW, PH, px, py, np.stack(vals[0:2], -1), np.stack(vals[2:4], -1), APERTURE, FOCUS, basis=basis), "sobol")
+    assert np.array_equal(st, s)
+
+
+def test_lens_rays_with_raster_taa_draw_the_aperture_first():
+    basis = D.camera_basis(CAM_A, PW, PH)
+    o, d, st, px, py, ss = probe_rays([basis], taa=1, frame_offset=3, frame_id=6)
+    s0 = D.lcg_seed(ss, 3, px, py, PW)
+    s1, aperture_draw = D.lcg_draw2(s0)  # no pixel-filter draw
+    jit = screen_jitter(3, 6, PW, PH)
+    assert jit[0] != 0 and jit[1] != 0
+    assert_rays((o, d), D.lens_ray(None, PW, PH, px, py, None, aperture_draw, APERTURE, FOCUS, jitter=jit, basis=basis), "raster TAA")
+    assert np.array_equal(st, s1)
+    unjittered = D.lens_ray(None, PW, PH, px, py, None, aperture_draw, APERTURE, FOCUS, basis=basis)
+    assert np.abs(d - unjittered[1]).max() > 1e-4  # the jitter is applied
+
+
+def test_lens_rays_of_two_frames_with_their_own_cameras():
+    bases = [D.camera_basis(CAM_A, PW, PH), D.camera_basis(CAM_B, PW, PH)]
+    o, d, st, px, py, ss = probe_rays(bases, n_frames=2)
+    frame = ss // PSPP
+    assert set(frame) == {0, 1}
+    for k in (0, 1):
+        sel = frame == k
+        # frames behind the first restart the accumulation (dshade.h rp_slot_frame): sample_index from 0, frame_offset moved on
+        s0 = D.lcg_seed(ss[sel] - k * PSPP, 3 + k * PSPP, px[sel], py[sel], PW)
+        s1, pixel_draw = D.lcg_draw2(s0)
+        s2, aperture_draw = D.lcg_draw2(s1)
+        assert_rays((o[sel], d[sel]), D.lens_ray(None, PW, PH, px[sel], py[sel], pixel_draw, aperture_draw, APERTURE, FOCUS, basis=bases[k]), "frame %d" % k)
+        assert np.array_equal(st[sel], s2)
+        assert np.abs(o[sel] - bases[k][0]).max() <= APERTURE * (1 + 1e-5)  # around its own frame's camera
+
+
+# ------------------------------------------------------------------ whole frames
+def _renderer(s, W, H, **kw):
+    r = backend.RenderHip(**kw)
+    r.initialize(W, H)
+    r.set_scene(s)
+    return r
+
+
+def _images(r, W, H):
+    img, u8 = np.zeros((H, W, 4), np.float32), np.zeros((H, W, 4), np.uint8)
+    assert r.readback_framebuffer(img) == W * H * 4 and r.readback_framebuffer(u8) == W * H * 4
+    return img, u8
+
+
+def _same(a, b):
+    return np.array_equal(a[0].view(np.uint32), b[0].view(np.uint32)) and np.array_equal(a[1], b[1])
+
+
+def _cfg(s, variant=abi.VARIANT_GLTF, cam=None, reset=True):
+    return backend.RenderConfiguration(cam or s.camera_params(), active_variant=variant, reset_accumulation=reset)
+
+
+@pytest.fixture(scope="module")
+def cornell():
+    return scenes.cornell32()
+
+
+@pytest.fixture(scope="module")
+def cornell_inside():
+    """the Cornell box from close enough that every camera ray, through the lens too, enters the box: coverage 1 everywhere"""
+    s = scenes.cornell32()
+    s.camera = dict(s.camera, eye=(0, 0, 2.6))
+    return s
+
+
+def test_aperture_zero_leaves_everything_alone(cornell):
+    W, H, spp = 64, 48, 2
+    r = _renderer(cornell, W, H)
+    r.render(_cfg(cornell), spp=spp)
+    ref = _images(r, W, H)
+    r.close()
+    for focus in (0.5, 2.5, 50.0):
+        r = _renderer(cornell, W, H)
+        r.params.aperture_radius = 0.0
+        r.params.focus_distance = focus
+        r.render(_cfg(cornell), spp=spp)
+        assert _same(_images(r, W, H), ref), focus
+        r.close()
+
+
+@pytest.mark.parametrize("fast_math", [0, 1])
+def test_first_extend_and_first_shade_agree_on_the_lens_ray(cornell_inside, fast_math):
+    """No run-time switch disables the stored first ray (RP_FIRST_RAY_STORED is a compile-time constant, and the general instantiations that
+    render a lens frame make the ray again in the first shade), so: the lens image is finite, every pixel is covered as with the pinhole
+    (a first shade that disagreed with the first extend about the ray would shade hits at wrong points or lose them), and the image
+    differs from the pinhole's. test_defocus_has_the_width_the_model_predicts runs in both builds too."""
+    s = cornell_inside
+    W, H, spp = 64, 48, 4
+    out = []
+    for aperture in (0.0, 0.05):
+        r = _renderer(s, W, H, options={"fast_math": fast_math})
+        r.params.aperture_radius = aperture
+        r.params.focus_distance = 2.5
+        st = r.render(_cfg(s), spp=spp, count_traversal=True)
+        out.append((_images(r, W, H)[0], st.raw))
+        r.close()
+    (pin, pst), (lens, lst) = out
+    assert np.isfinite(lens).all() and np.isfinite(pin).all()
+    assert np.array_equal(lens[..., 3], pin[..., 3]) and (pin[..., 3] == 1.0).all()
+    assert not np.array_equal(lens[..., :3], pin[..., :3])
+    # every camera ray hits in both, so bounce 0 traces and shades W H spp rays either way (later bounces differ with the paths)
+    assert lst.rays_closest >= W * H * spp and pst.rays_closest >= W * H * spp and lst.hits_shaded >= W * H * spp
+
+
+# ---- focus: a black / white edge on a plane at distance d
+EDGE_W, EDGE_H, EDGE_SPP, EDGE_FOV, EDGE_F = 96, 64, 256, 20.0, 4.0
+EDGE_ROWS = list(range(EDGE_H // 2 - 8, EDGE_H // 2 + 8))
+EDGE_PIX = 2.0 * np.tan(np.radians(EDGE_FOV / 2)) / EDGE_H  # pixel size at distance 1
+EDGE_R = 8.0 * EDGE_PIX * (0.5 * EDGE_F)  # circle of confusion at d = 0.5 f: diameter 2 R |d - f| / f = R, 8 pixels of that plane
+
+
+def edge_scene(d):
+    """the plane z = -d seen from the origin down -z: albedo 0 for x < 0, 1 (0.9) for x > 0, lit by the sky"""
+    s = Scene(name="edge")
+    e = 2.0 * d
+    T = _quad((-e, -e, -d), (0, -e, -d), (0, e, -d), (-e, e, -d)) + _quad((0, -e, -d), (e, -e, -d), (e, e, -d), (0, e, -d))
+    mesh = _add_mesh(s, np.array(T, np.float32))
+    s.pmeshes.append(ParameterizedMesh(mesh=mesh, material_offsets=np.array([0], np.int32), tri_material_ids=np.array([0, 0, 1, 1], np.uint8)))
+    s.instances.append(Instance(transform=IDENTITY.copy(), pmesh=0))
+    s.materials = [abi.make_material((0.0, 0.0, 0.0)), abi.make_material((0.9, 0.9, 0.9))]
+    s.camera = dict(eye=(0, 0, 0), center=(0, 0, -1), up=(0, 1, 0), fov=EDGE_FOV)
+    s.config = SceneConfig(**{k: v for k, v in SKY_CONFIGS["grid"].items()})
+    s.sky_key = "grid"
+    s.prepare_lights()
+    return s
+
+
+@pytest.fixture(scope="module")
+def edge_model():
+    """the model's 10-90 % widths for the three planes (computed once)"""
+    return {k: D.edge_width_10_90(D.edge_profile(EDGE_W, EDGE_H, EDGE_FOV, EDGE_R, EDGE_F, k * EDGE_F, EDGE_ROWS[::4], samples=4096)) for k in (1.0, 0.5, 2.0)}
+
+
+def _edge_width(s, aperture, fast_math):
+    r = _renderer(s, EDGE_W, EDGE_H, options={"fast_math": fast_math})
+    r.params.aperture_radius = aperture
+    r.params.focus_distance = EDGE_F
+    r.render(_cfg(s, abi.VARIANT_SIMPLE), spp=EDGE_SPP)
+    img = _images(r, EDGE_W, EDGE_H)[0]
+    r.close()
+    assert np.isfinite(img).all()
+    profile = img[EDGE_ROWS, :, :3].astype(np.float64).mean(axis=(0, 2))
+    assert profile[-8:].mean() > 10 * max(profile[:8].mean(), 1e-6)  # a white side and a black side
+    return D.edge_width_10_90(profile)
+
+
+@pytest.mark.parametrize("fast_math", [0, 1])
+def test_defocus_has_the_width_the_model_predicts(edge_model, fast_math):
+    """Fails without the lens: all three widths are the pinhole's then."""
+    widths = {}
+    for k in (1.0, 0.5, 2.0):
+        s = edge_scene(k * EDGE_F)
+        widths[k] = _edge_width(s, EDGE_R, fast_math)
+        if k == 1.0:
+            pinhole = _edge_width(s, 0.0, fast_math)
+    print("10-90 %% widths in pixels: in focus %.2f (pinhole %.2f, model %.2f), d = 0.5 f %.2f (model %.2f), d = 2 f %.2f (model %.2f)" % (
+        widths[1.0], pinhole, edge_model[1.0], widths[0.5], edge_model[0.5], widths[2.0], edge_model[2.0]))
+    assert edge_model[0.5] > 4.0 and edge_model[2.0] > 2.0  # the model itself shows defocus
+    for k in (0.5, 2.0):
+        assert abs(widths[k] - edge_model[k]) <= 1.0, (k, widths[k], edge_model[k])
+    assert widths[1.0] <= pinhole + 1.0
+
+
+# ---- the same image by every route
+def _moved(cam, k):
+    c = abi.Camera()
+    c.pos[:] = [cam.pos[0] + 0.05 * k, cam.pos[1] + 0.02 * k, cam.pos[2] - 0.04 * k]
+    c.dir[:] = list(cam.dir[:])
+    c.up[:] = list(cam.up[:])
+    c.fovy = cam.fovy + 0.5 * k
+    return c
+
+
+def _lens(r):
+    r.params.aperture_radius = 0.05
+    r.params.focus_distance = 2.5
+    return r
+
+
+def test_a_lens_frame_is_the_same_image_by_every_route(cornell):
+    s = cornell
+    W, H, spp = 64, 48, 2
+    cams = [_moved(s.camera_params(), k) for k in range(2)]
+    # one rank, one frame at a time
+    r = _lens(_renderer(s, W, H))
+    ref = []
+    for cam in cams:
+        r.render(_cfg(s, cam=cam), spp=spp)
+        ref.append(_images(r, W, H))
+    r.close()
+    assert not _same(ref[0], ref[1])
+    # two frames in flight, submitted ahead
+    r = _lens(_renderer(s, W, H, frames_in_flight=2))
+    tickets = [r.render_async(_cfg(s, cam=cam), spp=spp) for cam in cams]
+    for t, want in zip(tickets, ref):
+        r.wait(t)
+        assert _same(_images(r, W, H), want)
+    r.close()
+    # a batch of two frames with their own cameras
+    r = _lens(_renderer(s, W, H, frames_in_flight=2))
+    for t, want in zip(r.render_batch_cameras_async(_cfg(s, cam=cams[0]), cams, spp=spp, reset_rest=True), ref):
+        r.wait(t)
+        assert _same(_images(r, W, H), want)
+    r.close()
+    # two handles on the same device splitting the stripes
+    frame = (np.zeros((H, W, 4), np.float32), np.zeros((H, W, 4), np.uint8))
+    for rank in range(2):
+        r = _lens(_renderer(s, W, H, rank=rank, world_size=2, stripe_rows=8))
+        r.render(_cfg(s, cam=cams[0]), spp=spp)
+        part = _images(r, W, H)
+        for first, cnt in r.tile_rows():
+            frame[0][first:first + cnt] = part[0][first:first + cnt]
+            frame[1][first:first + cnt] = part[1][first:first + cnt]
+        r.close()
+    assert _same(frame, ref[0])
+
+
+def test_radiance_queries_ignore_the_lens(cornell):
+    s = cornell
+    W, H = 64, 48
+    basis = D.camera_basis(s.camera_params(), W, H)
+    rng = np.random.default_rng(3)
+    px, py = rng.integers(0, W, 256), rng.integers(0, H, 256)
+    o, d = D.lens_ray(None, W, H, px, py, rng.random((256, 2), dtype=np.float32), None, 0.0, 1.0, basis=basis)
+    q = np.zeros((256, 8), np.float32)
+    q[:, 0:3], q[:, 4:7], q[:, 7] = o, d, np.float32(2e32)
+    res = []
+    for aperture in (0.0, 0.1):
+        r = _renderer(s, W, H)
+        r.params.aperture_radius = aperture
+        res.append(r.render_radiance_queries(q, s.camera_params(), variant=abi.VARIANT_GLTF, spp=2, results=np.zeros((256, 4), np.float32)).copy())
+        r.close()
+    assert np.isfinite(res[0]).all() and res[0][:, :3].max() > 0
+    assert np.array_equal(res[0].view(np.uint32), res[1].view(np.uint32))
+
+
+def test_bad_lens_parameters_are_refused_and_the_handle_renders_again(cornell):
+    """... and a refused call leaves the handle as it was: the next frame is the one a handle that was never refused renders second"""
+    s = cornell
+    W, H = 64, 48
+    r = _renderer(s, W, H)
+    r.render(_cfg(s), spp=1)
+    r.render(_cfg(s), spp=1)
+    ref = _images(r, W, H)
+    r.close()
+    r = _renderer(s, W, H)
+    r.render(_cfg(s), spp=1)
+    for focus in (0.0, -1.0, float("nan")):
+        r.params.aperture_radius = 0.1
+        r.params.focus_distance = focus
+        with pytest.raises(backend.BackendError) as e:
+            r.render(_cfg(s), spp=1)
+        assert e.value.code == abi.RPTR_E_INVALID and "focus_distance" in str(e.value)
+    r.params.focus_distance = 2.5
+    r.params.aperture_radius = -1.0
+    with pytest.raises(backend.BackendError) as e:
+        r.render(_cfg(s), spp=1)
+    assert e.value.code == abi.RPTR_E_INVALID and "aperture_radius" in str(e.value)
+    r.params.aperture_radius = 0.0
+    r.render(_cfg(s), spp=1)
+    assert _same(_images(r, W, H), ref)
+    r.close()
+
+
+def test_enable_raytraced_dof_off_renders_the_pinhole_and_keeps_the_callers_params(cornell):
+    s = cornell
+    W, H, spp = 64, 48, 2
+    out = {}
+    for name, aperture, dof in (("pinhole", 0.0, True), ("lens", 0.1, True), ("off", 0.1, False)):
+        r = _renderer(s, W, H)
+        assert r.enable_raytraced_dof is True  # RenderBackendOptions::enable_raytraced_dof: default true
+        r.params.aperture_radius = aperture
+        r.enable_raytraced_dof = dof
+        r.render(_cfg(s), spp=spp)
+        out[name] = _images(r, W, H)
+        assert r.params.aperture_radius == np.float32(aperture)  # the caller's value stays
+        r.close()
+    assert not _same(out["lens"], out["pinhole"])
+    assert _same(out["off"], out["pinhole"])
