@@ -594,6 +594,35 @@ int rptr_hip_readback_u8(rptr_hip_t *h, unsigned char *rgba, size_t n_bytes);
 #define RPTR_AOV_MOTION_JITTER 2
 int rptr_hip_readback_aov(rptr_hip_t *h, int aov_index, uint16_t *rgba16f, size_t n_halfs);
 
+/* ---- the denoiser: a spatial filter for the last finished frame (stands where the reference's hosts link Open Image Denoise:
+ * enable_denoising, process_samples.comp's denoise_buffer). An edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) with the
+ * weights and the variance guidance of SVGF's spatial part, run on albedo-demodulated colour and guided by the frame's own normal +
+ * depth and albedo AOV images; csrc/denoise.h states every operation, tests/denoise_ref.py restates it in numpy, and the stored images
+ * equal that restatement bit for bit. INTEGRATION.md "Denoiser" lists what a host can rely on.
+ * The call is explicit and writes images of its own: it never touches the accumulation image, the RGBA8 frame, the AOV images, the
+ * reprojection / TAA history, frame_id / frame_offset or the statistics; a frame rendered after it is bit-identical to one rendered without it,
+ * and a host that never calls it launches nothing new. The source frame is the one the read-backs return: the frame waited for last (its
+ * frame context's images when frames are in flight). The denoise call is asynchronous on the backend's stream; its images (72 bytes per pixel) are
+ * allocated by the first call and freed with the handle's other frame-sized buffers. The RGBA8 image shows the denoised colour
+ * through the render parameters in force at the call (exposure, early_tone_mapping_mode, sRGB; output_channel != 0: a copy of the
+ * frame's RGBA8 image).
+ * RPTR_E_INVALID: before a frame has finished; NULL or out-of-range parameters; reserved != 0; the frame's images are being overwritten by a
+ * newer frame on the same frame context; the frame waited for last is not the last of its launch sequence (the AOV images are that
+ * one's); a denoised read-back before any denoise call, or after a later frame finished or initialize ran (the image is stale).
+ * RPTR_E_UNSUPPORTED: option "aovs" = 0; world_size > 1 (a stripe's taps lie in other ranks' rows); render_upscale_factor 2. */
+typedef struct RptrDenoiseParams { /* 32 bytes */
+    int32_t iterations;        /* 1..5: passes with tap spacing 1, 2, 4, 8, 16; default 5 */
+    float sigma_luminance;     /* > 0, default 4 */
+    float sigma_depth;         /* > 0, default 1 */
+    int32_t normal_power_log2; /* 0..8, default 7: weight = max(0, n_p . n_q) ^ (2 ^ k) */
+    int32_t demodulate_albedo; /* 0 / 1, default 1 */
+    int32_t reserved[3];       /* must be 0 */
+} RptrDenoiseParams;
+void rptr_hip_denoise_defaults(RptrDenoiseParams *out);
+int rptr_hip_denoise(rptr_hip_t *h, const RptrDenoiseParams *p);
+int rptr_hip_readback_denoised_f32(rptr_hip_t *h, float *rgba, size_t n_floats);
+int rptr_hip_readback_denoised_u8(rptr_hip_t *h, unsigned char *rgba, size_t n_bytes);
+
 /* ---- multi-GPU: this rank's rows, packed top-to-bottom, for the RCCL gather.
  * rptr_hip_tile_rows writes up to `cap` (first_row,num_rows) pairs for `rank`
  * and returns the number of stripes; rptr_hip_copy_tile_to_device copies this

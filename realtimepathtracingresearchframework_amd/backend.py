@@ -92,6 +92,11 @@ def load_library(path=None):
     L.rptr_hip_readback_f32.argtypes = [vp, vp, C.c_size_t]
     L.rptr_hip_readback_u8.argtypes = [vp, vp, C.c_size_t]
     L.rptr_hip_readback_aov.argtypes = [vp, i32, vp, C.c_size_t]
+    L.rptr_hip_denoise_defaults.argtypes = [C.POINTER(abi.DenoiseParams)]
+    L.rptr_hip_denoise_defaults.restype = None
+    L.rptr_hip_denoise.argtypes = [vp, C.POINTER(abi.DenoiseParams)]
+    L.rptr_hip_readback_denoised_f32.argtypes = [vp, vp, C.c_size_t]
+    L.rptr_hip_readback_denoised_u8.argtypes = [vp, vp, C.c_size_t]
     L.rptr_hip_tile_rows.argtypes = [vp, i32, vp, i32]
     L.rptr_hip_local_pixel_count.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.rptr_hip_copy_tile_to_device.argtypes = [vp, vp, C.c_size_t]
@@ -374,6 +379,39 @@ class RenderHip:
             return 0
         self._check(self._L.rptr_hip_readback_aov(self._h, int(aov_index), buffer.ctypes.data_as(C.c_void_p), buffer.size))
         return need
+
+    # ---- the denoiser (include/rptr_hip.h rptr_hip_denoise; csrc/denoise.h)
+    def denoise(self, params=None, **fields):
+        """Denoises the frame the read-backs return (the frame waited for last) into images of its own; asynchronous on the backend's
+        stream. params: an abi.DenoiseParams, or None for the library's defaults; keyword arguments override single fields
+        (iterations, sigma_luminance, sigma_depth, normal_power_log2, demodulate_albedo). The RGBA8 image goes through the render
+        parameters of self.params as they are now. Returns the parameters used."""
+        p = abi.DenoiseParams()
+        if params is None:
+            self._L.rptr_hip_denoise_defaults(C.byref(p))
+        else:
+            C.memmove(C.byref(p), C.byref(params), C.sizeof(p))
+        for k, v in fields.items():
+            if k not in dict(abi.DenoiseParams._fields_) or k == "reserved":
+                raise TypeError("denoise: unknown parameter %r" % k)
+            setattr(p, k, v)
+        self._push_params()
+        self._check(self._L.rptr_hip_denoise(self._h, C.byref(p)))
+        return p
+
+    def readback_denoised_f32(self):
+        """the denoised RGBA32F image of the last denoise() as an (H, W, 4) float32 array"""
+        w, hgt, c = self.get_framebuffer_size()
+        out = np.zeros((hgt, w, c), np.float32)
+        self._check(self._L.rptr_hip_readback_denoised_f32(self._h, out.ctypes.data_as(C.c_void_p), out.size))
+        return out
+
+    def readback_denoised_u8(self):
+        """the denoised sRGB RGBA8 image of the last denoise() as an (H, W, 4) uint8 array"""
+        w, hgt, c = self.get_framebuffer_size()
+        out = np.zeros((hgt, w, c), np.uint8)
+        self._check(self._L.rptr_hip_readback_denoised_u8(self._h, out.ctypes.data_as(C.c_void_p), out.size))
+        return out
 
     # ---- ray queries (RQ_CLOSEST)
     def enable_ray_queries(self, max_queries=512 * 512, max_queries_per_pixel=0):

@@ -225,6 +225,110 @@ int rptr_hip_readback_aov(rptr_hip_t *h, int aov_index, uint16_t *rgba16f, size_
     return readback_rows<uint2>(h, c.aov[aov_index], reinterpret_cast<uint2 *>(rgba16f), n_halfs / 4);
 }
 
+// ---- the denoiser (denoise.h): the last finished frame through prepare, `iterations` a-trous passes and finish, on the backend's stream
+void rptr_hip_denoise_defaults(RptrDenoiseParams *out) {
+    if (!out) return;
+    memset(out, 0, sizeof(*out));
+    out->iterations = 5;
+    out->sigma_luminance = 4.0f;
+    out->sigma_depth = 1.0f;
+    out->normal_power_log2 = 7;
+    out->demodulate_albedo = 1;
+}
+
+int rptr_hip_denoise(rptr_hip_t *h, const RptrDenoiseParams *p) {
+    if (!h) return fail(nullptr, RPTR_E_INVALID, "NULL handle");
+    if (!p) return fail(h, RPTR_E_INVALID, "rptr_hip_denoise: NULL parameters");
+    if (p->iterations < 1 || p->iterations > 5) return fail(h, RPTR_E_INVALID, "rptr_hip_denoise: iterations = %d is outside [1, 5]", p->iterations);
+    if (!(p->sigma_luminance > 0.0f) || !std::isfinite(p->sigma_luminance) || !(p->sigma_depth > 0.0f) || !std::isfinite(p->sigma_depth))
+        return fail(h, RPTR_E_INVALID, "rptr_hip_denoise: sigma_luminance and sigma_depth must be finite and > 0 (are %g, %g)", (double)p->sigma_luminance,
+                    (double)p->sigma_depth);
+    if (p->normal_power_log2 < 0 || p->normal_power_log2 > 8)
+        return fail(h, RPTR_E_INVALID, "rptr_hip_denoise: normal_power_log2 = %d is outside [0, 8]", p->normal_power_log2);
+    if (p->demodulate_albedo != 0 && p->demodulate_albedo != 1) return fail(h, RPTR_E_INVALID, "rptr_hip_denoise: demodulate_albedo must be 0 or 1");
+    if (p->reserved[0] || p->reserved[1] || p->reserved[2]) return fail(h, RPTR_E_INVALID, "rptr_hip_denoise: RptrDenoiseParams.reserved must be 0");
+    if (h->world > 1) return fail(h, RPTR_E_UNSUPPORTED, "rptr_hip_denoise needs world_size 1: the taps of a stripe's pixels lie in other ranks' rows");
+    if (h->width == 0) return fail(h, RPTR_E_INVALID, "rptr_hip_denoise before initialize");
+    if (!h->aovs) return fail(h, RPTR_E_UNSUPPORTED, "rptr_hip_denoise reads the albedo and normal + depth AOV images: option \"aovs\" is 0");
+    if (h->params.render_upscale_factor == 2)
+        return fail(h, RPTR_E_UNSUPPORTED, "rptr_hip_denoise needs render_upscale_factor 1 (its RGBA8 image has the render resolution)");
+    if (h->finished_serial == 0) return fail(h, RPTR_E_INVALID, "rptr_hip_denoise before a frame has finished (render, or wait for a ticket, first)");
+    if (h->output_overwritten || h->aov_overwritten)
+        return fail(h, RPTR_E_INVALID, "the images of the last waited frame are being overwritten by a newer frame in flight on the same frame context: "
+                                       "denoise before submitting that frame, or rptr_hip_wait for it first");
+    const FrameCtx &ac = h->ctx[(size_t)h->aov_ctx];
+    if (h->output_ctx >= 0 && (h->output_ctx != h->aov_ctx || h->output_index != ac.batch_n - 1))
+        return fail(h, RPTR_E_INVALID, "rptr_hip_denoise: the AOV images belong to the last frame of the launch sequence finished last, the frame waited "
+                                       "for last is another one");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t npix = (size_t)h->width * (size_t)h->height;
+    int rc;
+    if (!h->dn.out_u8) {
+        if ((rc = dev_alloc(h, &h->dn.ev[0], npix, nullptr)) || (rc = dev_alloc(h, &h->dn.ev[1], npix, nullptr)) || (rc = dev_alloc(h, &h->dn.ndz, npix, nullptr)) ||
+            (rc = dev_alloc(h, &h->dn.gz, npix, nullptr)) || (rc = dev_alloc(h, &h->dn.out_f32, npix, nullptr)) || (rc = dev_alloc(h, &h->dn.out_u8, npix, nullptr)))
+            return rc;
+    }
+    RpDenoiseArgs a;
+    memset(&a, 0, sizeof(a));
+    a.accum = h->output_ctx >= 0 ? h->ctx[(size_t)h->output_ctx].out_accum + (size_t)h->output_index * npix : h->accum;
+    a.fb = h->output_ctx >= 0 ? h->ctx[(size_t)h->output_ctx].out_fb + (size_t)h->output_index * npix : h->fb;
+    a.albedo = ac.aov[0];
+    a.nd = ac.aov[1];
+    a.ndz = h->dn.ndz;
+    a.gz = h->dn.gz;
+    a.out_f32 = h->dn.out_f32;
+    a.out_u8 = h->dn.out_u8;
+    a.width = h->width;
+    a.height = h->height;
+    a.sigma_luminance = p->sigma_luminance;
+    a.sigma_depth = p->sigma_depth;
+    a.normal_power_log2 = p->normal_power_log2;
+    a.demodulate = p->demodulate_albedo;
+    a.output_channel = h->params.output_channel;
+    a.tone_mapping_mode = h->params.early_tone_mapping_mode;
+    a.exposure_scale = (float)std::exp2((double)h->params.exposure);
+    const unsigned T = RP_DN_TILE;
+    const dim3 tiles(((unsigned)h->width + T - 1) / T, ((unsigned)h->height + T - 1) / T);
+    rp_launch_kernel(RpLaunch{tiles, h->stream, nullptr, nullptr}, rp_k_denoise_prepare, 256u, a, h->dn.ev[0]);
+    for (int i = 0; i < p->iterations; ++i) {
+        const int s = 1 << i;
+        const float4 *in = h->dn.ev[i & 1];
+        float4 *out = h->dn.ev[(i & 1) ^ 1];
+        if (s == 1)
+            rp_launch_kernel(RpLaunch{tiles, h->stream, nullptr, nullptr}, rp_k_denoise_pass<1>, 256u, a, in, out, s);
+        else if (s == 2)
+            rp_launch_kernel(RpLaunch{tiles, h->stream, nullptr, nullptr}, rp_k_denoise_pass<2>, 256u, a, in, out, s);
+        else { // tiles of the s x s sub-lattices: each has at most ceil(W / s) x ceil(H / s) pixels
+            const unsigned us = (unsigned)s;
+            const dim3 lattice(us * ((((unsigned)h->width + us - 1) / us + T - 1) / T), us * ((((unsigned)h->height + us - 1) / us + T - 1) / T));
+            rp_launch_kernel(RpLaunch{lattice, h->stream, nullptr, nullptr}, rp_k_denoise_pass<0>, 256u, a, in, out, s);
+        }
+    }
+    rp_launch_kernel(RpLaunch{dim3((unsigned)grid_for(h, npix)), h->stream, nullptr, nullptr}, rp_k_denoise_finish, 256u, a, (const float4 *)h->dn.ev[p->iterations & 1]);
+    HIP_TRY(h, hipGetLastError());
+    h->dn.serial = h->finished_serial;
+    return RPTR_OK;
+}
+
+extern "C++" {
+static int check_denoised(rptr_hip *h) {
+    if (!h->dn.out_u8 || h->dn.serial == 0) return fail(h, RPTR_E_INVALID, "no denoised image: call rptr_hip_denoise first");
+    if (h->dn.serial != h->finished_serial)
+        return fail(h, RPTR_E_INVALID, "the denoised image is stale: a later frame has finished since rptr_hip_denoise ran; call it again for that frame");
+    return RPTR_OK;
+}
+}
+int rptr_hip_readback_denoised_f32(rptr_hip_t *h, float *rgba, size_t n_floats) {
+    if (!h || !rgba) return fail(h, RPTR_E_INVALID, "NULL argument");
+    const int rc = check_denoised(h);
+    return rc ? rc : readback_rows<float4>(h, h->dn.out_f32, reinterpret_cast<float4 *>(rgba), n_floats / 4);
+}
+int rptr_hip_readback_denoised_u8(rptr_hip_t *h, unsigned char *rgba, size_t n_bytes) {
+    if (!h || !rgba) return fail(h, RPTR_E_INVALID, "NULL argument");
+    const int rc = check_denoised(h);
+    return rc ? rc : readback_rows<uchar4>(h, h->dn.out_u8, reinterpret_cast<uchar4 *>(rgba), n_bytes / 4);
+}
+
 int rptr_hip_trace(rptr_hip_t *h, const RptrRenderRayQuery *queries, int n, float *out4) {
     return rptr_hip_trace_counted(h, queries, n, out4, nullptr, nullptr, 0);
 }

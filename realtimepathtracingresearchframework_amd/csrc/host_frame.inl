@@ -180,6 +180,7 @@ static void add_counters(RpCounters &dst, const RpCounters &c) {
 
 // read-backs of the image get, from here on, the one frame `which` of this context's batch produced (its context keeps a copy)
 static void note_output(rptr_hip *h, FrameCtx &c, int which) {
+    h->finished_serial++; // (a denoised image made from the frame waited for before is stale now: host_access.inl)
     if (h->ctx.size() > 1) {
         h->output_ctx = (int)(&c - h->ctx.data());
         h->output_index = std::max(which, 0);

@@ -357,6 +357,16 @@ struct rptr_hip {
         uchar4 *fb_other = nullptr;  // TAA: the partner of `fb` (the pass reads the history in fb and writes here, then they swap)
         bool chain = false;          // the previously submitted frame ran the mode-2 resolve: its images are this frame's history
     } rt;
+    // the denoiser (denoise.h, rptr_hip_denoise): its images, made by the first call and freed with the other frame-sized buffers
+    struct Denoise {
+        float4 *ev[2] = {nullptr, nullptr}; // (e, v), the passes ping-pong
+        float4 *ndz = nullptr;
+        float *gz = nullptr;
+        float4 *out_f32 = nullptr;
+        uchar4 *out_u8 = nullptr;
+        uint64_t serial = 0;                // finished_serial of the frame the images were made from (0: none)
+    } dn;
+    uint64_t finished_serial = 0;           // frames waited for since initialize: the read-backs' frame changes with each
     size_t path_capacity = 0;
     // persistent traversal grids (traversal_grid below): [0] first / [1] later closest-hit, shadow rays [2] two-level / [3] one instance record
     int resident_per_cu[4] = {0, 0, 0, 0}; // blocks per CU of each kernel that fit at once (its occupancy, at most 8)

@@ -207,6 +207,10 @@ public:
         for (auto &r : ranks_) n = r->readback_framebuffer(buffer_size, buffer);
         return n;
     }
+    // the denoiser works on one GPU's whole frame (rptr_hip_denoise refuses world_size > 1: a stripe's taps lie in other ranks' rows)
+    void denoise(const RptrDenoiseParams &p) { ranks_[0]->denoise(p); }
+    size_t readback_denoised(size_t buffer_size, float *buffer) { return ranks_[0]->readback_denoised(buffer_size, buffer); }
+    size_t readback_denoised(size_t buffer_size, unsigned char *buffer) { return ranks_[0]->readback_denoised(buffer_size, buffer); }
     size_t readback_aov(RenderHip::AOVBufferIndex aov, size_t buffer_size, uint16_t *buffer) {
         size_t n = 0;
         for (auto &r : ranks_) n = r->readback_aov(aov, buffer_size, buffer);

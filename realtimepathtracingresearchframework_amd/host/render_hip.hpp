@@ -281,6 +281,34 @@ public:
         return need;
     }
 
+    // The denoiser (include/rptr_hip.h rptr_hip_denoise): the frame the read-backs return -- everything in flight is finished first --
+    // into images of its own; the frame's images, its history and the statistics stay as they are. Asynchronous on the backend's stream.
+    static RptrDenoiseParams denoise_defaults() {
+        RptrDenoiseParams p;
+        rptr_hip_denoise_defaults(&p);
+        return p;
+    }
+    void denoise(const RptrDenoiseParams &p) {
+        flush_pipeline();
+        check(rptr_hip_denoise(h_, &p));
+    }
+    size_t readback_denoised(size_t buffer_size, float *buffer) { // RGBA32F
+        uint32_t whc[3];
+        get_framebuffer_size(whc);
+        const size_t need = size_t(whc[0]) * whc[1] * 4;
+        if (buffer_size < need) return 0;
+        check(rptr_hip_readback_denoised_f32(h_, buffer, buffer_size));
+        return need;
+    }
+    size_t readback_denoised(size_t buffer_size, unsigned char *buffer) { // sRGB RGBA8
+        uint32_t whc[3];
+        get_framebuffer_size(whc);
+        const size_t need = size_t(whc[0]) * whc[1] * 4;
+        if (buffer_size < need) return 0;
+        check(rptr_hip_readback_denoised_u8(h_, buffer, buffer_size));
+        return need;
+    }
+
     // RenderGraphic::readback_aov (util/display/render_graphic.h:12-17,40): RGBA16F, the reference's AOVBufferIndex order
     enum AOVBufferIndex { AOVAlbedoRoughnessIndex = 0, AOVNormalDepthIndex, AOVMotionJitterIndex, AOVBufferCount };
     size_t readback_aov(AOVBufferIndex aov_index, size_t buffer_size, uint16_t *buffer, bool /*force_refresh*/ = false) {

@@ -1,7 +1,7 @@
 // rptr_cli.cpp -- the reference's headless run modes through the C ABI (binary: bin/rptr_hip):
 //
 //   <scene> = the reference's .vks file (textures in <name>_textures/) or the flat dump scenes.py writes (.rpsc)
-//   rptr_hip <scene> --validation <prefix> [--validation-spp n] [--img w h] [--pfm]
+//   rptr_hip <scene> --validation <prefix> [--validation-spp n] [--img w h] [--pfm] [--denoise iterations]
 //   rptr_hip <scene.rpsc> --profiling <csv prefix> [--profiling-fps f] [--profiling-img <prefix>] [--profiling-frames n]
 //            [--animate-wave amplitude kx] [--synchronous] [--fly-through] [--frames-in-flight n [--frames-per-launch b]]
 //   common:  [--eye x y z] [--center x y z] [--up x y z] [--fov deg] [--variant gltf|diffuse|gltf-transmission] [--batch-spp k] [--every-frame]
@@ -60,18 +60,28 @@ enum OutputFormat { FORMAT_EXR, FORMAT_PFM, FORMAT_PNG }; // cmdline.cpp:450-460
 
 // BasicApplicationState::save_framebuffer (libapp/app_state.cpp:341-438): the float accumulation buffer as EXR / PFM, the 8-bit
 // frame buffer as PNG, under <prefix>_<number> (+ suffix)
+// --denoise <iterations> (this host's; the reference's enable_denoising links Open Image Denoise): the images written are the denoised ones
+// (include/rptr_hip.h rptr_hip_denoise with the library's defaults and that many passes); 0: the frame's own, as without the flag
+static int g_denoise_iterations = 0;
 static void save_image(rptr::RenderGroup &backend, OutputFormat format, const std::string &prefix, int number, const std::string &suffix, int width, int height,
                        std::vector<float> &img) {
     char name[32];
     std::snprintf(name, sizeof(name), "_%04d", number);
     const std::string base = prefix + name + suffix;
     bool ok = false;
+    if (g_denoise_iterations > 0) {
+        RptrDenoiseParams dp = rptr::RenderHip::denoise_defaults();
+        dp.iterations = g_denoise_iterations;
+        backend.denoise(dp);
+    }
     if (format == FORMAT_PNG) {
         std::vector<unsigned char> rgba8((size_t)width * height * 4);
-        if (backend.readback_framebuffer(rgba8.size(), rgba8.data()) != rgba8.size()) throw std::runtime_error("read-back failed");
+        if ((g_denoise_iterations > 0 ? backend.readback_denoised(rgba8.size(), rgba8.data()) : backend.readback_framebuffer(rgba8.size(), rgba8.data())) != rgba8.size())
+            throw std::runtime_error("read-back failed");
         ok = rptr::write_png(base, (unsigned)width, (unsigned)height, 4, rgba8.data());
     } else {
-        if (backend.readback_framebuffer(img.size(), img.data()) != img.size()) throw std::runtime_error("read-back failed");
+        if ((g_denoise_iterations > 0 ? backend.readback_denoised(img.size(), img.data()) : backend.readback_framebuffer(img.size(), img.data())) != img.size())
+            throw std::runtime_error("read-back failed");
         ok = format == FORMAT_PFM ? rptr::write_pfm(base, (unsigned)width, (unsigned)height, 4, img.data())
                                   : rptr::write_exr<float>(base, (unsigned)width, (unsigned)height, 4, img.data());
     }
@@ -180,6 +190,7 @@ int main(int argc, char **argv) {
         else if (a == "--fly-through") fly_through = true;   // (this host's: bench.py's camera path)
         else if (a == "--profiling-count") { need(1); profiling_frames = std::atoi(argv[++i]); have_profiling_options = true; } // (this host's: frames of a run without keyframes)
         else if (a == "--animate-wave") { need(2); wave_amp = (float)std::atof(argv[++i]); wave_k = (float)std::atof(argv[++i]); }
+        else if (a == "--denoise") { need(1); g_denoise_iterations = std::atoi(argv[++i]); if (g_denoise_iterations < 1 || g_denoise_iterations > 5) { std::fprintf(stderr, "--denoise takes 1..5 iterations\n"); return 2; } }
         else if (a == "--img") { need(2); width = std::atoi(argv[++i]); height = std::atoi(argv[++i]); }
         else if (a == "--eye") { vec3(eye); got_eye = true; }
         else if (a == "--center") { vec3(center); got_center = true; }
@@ -329,7 +340,7 @@ int main(int argc, char **argv) {
     if (want_help) scene_path.clear(); // prints the usage
     if (scene_path.empty() || (int)validation + (int)profiling + (int)data_capture != 1 || batch_spp < 1 || width < 1 || height < 1 || (profiling && profiling_frames < 1)) {
         std::fprintf(stderr, "usage: rptr_hip <scene.rpsc> (--validation <prefix> [--validation-spp n] | --profiling <csv prefix> [--profiling-fps f] "
-                             "[--profiling-img <prefix>] [--keyframe [len:]file.ini ...] [--profiling-count n] [--synchronous] [--fly-through] [--frames-in-flight n [--frames-per-launch b]] [--animate-wave a k]) [--img w h] [--eye x y z] [--center x y z] "
+                             "[--profiling-img <prefix>] [--keyframe [len:]file.ini ...] [--profiling-count n] [--synchronous] [--fly-through] [--frames-in-flight n [--frames-per-launch b]] [--animate-wave a k]) [--img w h] [--denoise iterations] [--eye x y z] [--center x y z] "
                              "[--up x y z] [--fov deg] [--variant gltf|diffuse] [--batch-spp k] [--every-frame] [--exr|--pfm|--png] [--config file.ini ...] [--sky-data <dir of the Hosek-Wilkie data headers>]\n"
                              "       rptr_hip <scene.rpsc> --data-capture <prefix> [--data-capture-spp n] [--data-capture-no-rgba] [--data-capture-no-aovs] "
                              "[--data-capture-albedo-roughness] [--data-capture-normal-depth] [--data-capture-motion] [--keyframe ...]   (EXR images per keyframe)\n"
