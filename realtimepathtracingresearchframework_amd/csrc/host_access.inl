@@ -1,5 +1,5 @@
 // host_access.inl -- everything else a host reaches through the handle: BVH policy, freeze frame, point sets, stage timing, the option calls, frame buffer / tile /
-// AOV read-backs, ray queries (rptr_hip_trace*: closest hits, and path-traced radiance), the exported tree
+// AOV read-backs (last_finished_image: which image they mean), the denoiser, ray queries (rptr_hip_trace*: closest hits, and path-traced radiance), the exported tree
 // Part of the ONE translation unit rptr_hip.hip (included there, in this order: host_state.h, host_bvh.inl, host_scene.inl,
 // host_frame.inl, host_access.inl, host_comm.h): the host runtime split along its seams; no symbol changed.
 int rptr_hip_set_bvh_policy(rptr_hip_t *h, int force_bvh_rebuild, int rebuild_triangle_budget) {
@@ -142,17 +142,33 @@ int rptr_hip_local_pixel_count(const rptr_hip_t *h, uint64_t *out_pixels) {
     return RPTR_OK;
 }
 
+// The last finished image: what read-backs, the denoiser and the gather (host_comm.h) refer to. One frame at a time it is the handle's
+// accumulation buffer and RGBA8 frame; with frames in flight the context of the frame that was waited for last keeps a copy (one per
+// frame of a launch sequence; `back` steps that many frames back in it). Refused while a newer frame on that context rewrites it.
+static int last_finished_image(rptr_hip *h, const float4 **accum, const uchar4 **fb, int back = 0) {
+    if (h->output_overwritten)
+        return fail(h, RPTR_E_INVALID, "the image of the last waited frame is being overwritten by a newer frame in flight on the same frame context: "
+                                       "read back before submitting that frame, or rptr_hip_wait for it first");
+    const FrameCtx *c = h->output_ctx >= 0 ? &h->ctx[(size_t)h->output_ctx] : nullptr;
+    if (!c) {
+        if (accum) *accum = h->accum;
+        if (fb) *fb = h->fb;
+        return RPTR_OK;
+    }
+    const size_t at = (size_t)(h->output_index - back) * ((size_t)h->width * (size_t)std::max(h->local_rows, 1));
+    if (accum) *accum = c->out_accum + at;
+    if (fb) *fb = c->out_fb + at;
+    return RPTR_OK;
+}
+
 int rptr_hip_copy_tile_to_device(rptr_hip_t *h, void *device_dst, size_t n_bytes) {
     if (!h || !device_dst) return fail(h, RPTR_E_INVALID, "NULL argument");
     const size_t need = (size_t)h->width * h->local_rows * sizeof(float4);
     if (n_bytes < need) return fail(h, RPTR_E_INVALID, "destination too small: %zu < %zu", n_bytes, need);
-    if (h->output_overwritten)
-        return fail(h, RPTR_E_INVALID, "the image of the last waited frame is being overwritten by a newer frame in flight on the same frame context: "
-                                       "read back before submitting that frame, or rptr_hip_wait for it first");
+    const float4 *src = nullptr;
+    const int rc = last_finished_image(h, &src, nullptr);
+    if (rc) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
-    // frames in flight: the image of the frame that was waited for last (its context keeps a copy)
-    const size_t out_stride = (size_t)h->width * (size_t)std::max(h->local_rows, 1);
-    const float4 *src = h->output_ctx >= 0 ? h->ctx[(size_t)h->output_ctx].out_accum + (size_t)h->output_index * out_stride : h->accum;
     if (need) HIP_TRY(h, hipMemcpyAsync(device_dst, src, need, hipMemcpyDeviceToDevice, h->stream));
     return RPTR_OK;
 }
@@ -180,20 +196,15 @@ static int readback_rows(rptr_hip *h, const T *dev_local, T *host_full, size_t n
 
 int rptr_hip_readback_f32(rptr_hip_t *h, float *rgba, size_t n_floats) {
     if (!h || !rgba) return fail(h, RPTR_E_INVALID, "NULL argument");
-    if (h->output_overwritten)
-        return fail(h, RPTR_E_INVALID, "the image of the last waited frame is being overwritten by a newer frame in flight on the same frame context: "
-                                       "read back before submitting that frame, or rptr_hip_wait for it first");
-    const size_t out_stride = (size_t)h->width * (size_t)std::max(h->local_rows, 1);
-    return readback_rows<float4>(h, h->output_ctx >= 0 ? h->ctx[(size_t)h->output_ctx].out_accum + (size_t)h->output_index * out_stride : h->accum,
-                                 reinterpret_cast<float4 *>(rgba), n_floats / 4);
+    const float4 *src = nullptr;
+    const int rc = last_finished_image(h, &src, nullptr);
+    return rc ? rc : readback_rows<float4>(h, src, reinterpret_cast<float4 *>(rgba), n_floats / 4);
 }
 int rptr_hip_readback_u8(rptr_hip_t *h, unsigned char *rgba, size_t n_bytes) {
     if (!h || !rgba) return fail(h, RPTR_E_INVALID, "NULL argument");
-    if (h->output_overwritten)
-        return fail(h, RPTR_E_INVALID, "the image of the last waited frame is being overwritten by a newer frame in flight on the same frame context: "
-                                       "read back before submitting that frame, or rptr_hip_wait for it first");
-    const size_t out_stride = (size_t)h->width * (size_t)std::max(h->local_rows, 1);
-    const uchar4 *src = h->output_ctx >= 0 ? h->ctx[(size_t)h->output_ctx].out_fb + (size_t)h->output_index * out_stride : h->fb;
+    const uchar4 *src = nullptr;
+    int rc = last_finished_image(h, nullptr, &src);
+    if (rc) return rc;
     if (h->params.render_upscale_factor != 2) return readback_rows<uchar4>(h, src, reinterpret_cast<uchar4 *>(rgba), n_bytes / 4);
     // render_upscale_factor == 2 (process_samples.comp:192-197): the frame buffer has twice the render resolution, every rendered
     // pixel fills a 2x2 block. Replicated here, on the way out (rows of other ranks stay untouched, as in the 1:1 read-back).
@@ -203,8 +214,7 @@ int rptr_hip_readback_u8(rptr_hip_t *h, unsigned char *rgba, size_t n_bytes) {
     const uchar4 *big = reinterpret_cast<const uchar4 *>(rgba);
     for (size_t y = 0; y < H; ++y) // keep what the caller's buffer holds for rows this rank does not own
         for (size_t x = 0; x < W; ++x) lo[y * W + x] = big[(2 * y) * (2 * W) + 2 * x];
-    int rc = readback_rows<uchar4>(h, src, lo.data(), lo.size());
-    if (rc) return rc;
+    if ((rc = readback_rows<uchar4>(h, src, lo.data(), lo.size()))) return rc;
     uchar4 *out = reinterpret_cast<uchar4 *>(rgba);
     for (size_t y = 0; y < H; ++y)
         for (size_t x = 0; x < W; ++x) {
@@ -270,8 +280,7 @@ int rptr_hip_denoise(rptr_hip_t *h, const RptrDenoiseParams *p) {
     }
     RpDenoiseArgs a;
     memset(&a, 0, sizeof(a));
-    a.accum = h->output_ctx >= 0 ? h->ctx[(size_t)h->output_ctx].out_accum + (size_t)h->output_index * npix : h->accum;
-    a.fb = h->output_ctx >= 0 ? h->ctx[(size_t)h->output_ctx].out_fb + (size_t)h->output_index * npix : h->fb;
+    if ((rc = last_finished_image(h, &a.accum, &a.fb))) return rc; // (world_size 1: an image is the whole frame, npix pixels)
     a.albedo = ac.aov[0];
     a.nd = ac.aov[1];
     a.ndz = h->dn.ndz;

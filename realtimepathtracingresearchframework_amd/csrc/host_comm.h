@@ -284,17 +284,6 @@ void comm_release(rptr_hip *h) {
 // the slot (rank 0's receive buffer + assembled frame) the gather that is being issued works on
 inline int comm_slot(const RptrComm *c) { return (int)(c->gathers & 1u); }
 
-// the image the gather sends: the rows of the frame that was waited for last
-// nb > 1: the last nb frames of the waited launch sequence (images output_index - nb + 1 .. output_index of its context)
-const float4 *comm_source(rptr_hip *h, FrameCtx *&owner, int nb) {
-    if (h->output_ctx >= 0) {
-        owner = &h->ctx[(size_t)h->output_ctx];
-        return owner->out_accum + (size_t)(h->output_index - (nb - 1)) * ((size_t)h->width * (size_t)std::max(h->local_rows, 1));
-    }
-    owner = &h->ctx[0];
-    return h->accum;
-}
-
 void comm_collect_timing(RptrComm *c, bool wait) {
     if (!c->timing_pending) return;
     if (wait) (void)hipEventSynchronize(c->ev_t1);
@@ -319,7 +308,13 @@ int comm_begin(rptr_hip *h, const float4 *&src, FrameCtx *&owner, int nb) {
         return fail(h, RPTR_E_INVALID, "the image of the last waited frame is being overwritten by a newer frame on the same frame context: gather right "
                                        "after rptr_hip_wait");
     HIP_TRY(h, hipSetDevice(h->device));
-    src = comm_source(h, owner, nb);
+    // the image the gather sends: the rows of the frame that was waited for last (host_access.inl last_finished_image; one frame at a time
+    // context 0 stands for the handle's own image). nb > 1: the last nb frames of the waited launch sequence, from nb - 1 images back
+    owner = &h->ctx[(size_t)std::max(h->output_ctx, 0)];
+    {
+        const int rc = last_finished_image(h, &src, nullptr, nb - 1);
+        if (rc) return rc;
+    }
     HIP_TRY(h, hipEventRecord(c->ev_src, h->stream)); // the frame has ended (finish_frame waited for it); the caller's work on the stream comes first
     HIP_TRY(h, hipStreamWaitEvent(c->stream, c->ev_src, 0));
     comm_collect_timing(c, false);

@@ -1,4 +1,5 @@
-// host_scene.inl -- rptr_hip_set_scene (upload, device tables, shading records, per-context scene copies), vertex updates, refit and device rebuild
+// host_scene.inl -- rptr_hip_set_scene (static uploads, tree, refit tables, then every scene copy -- the master's and the frame contexts' --
+// through scene_copy_build), vertex and instance updates, refit and the device rebuilds (one front half: lbvh_front_half)
 // Part of the ONE translation unit rptr_hip.hip (included there, in this order: host_state.h, host_bvh.inl, host_scene.inl,
 // host_frame.inl, host_access.inl, host_comm.h): the host runtime split along its seams; no symbol changed.
 // ---- set_scene, step by step (each returns RPTR_OK or the error it reported through fail())
@@ -58,24 +59,21 @@ static int scene_upload_textures(rptr_hip *h, const RptrSceneDesc *s, RpTexture 
             const uint32_t levels = td.mip_levels > 1u ? td.mip_levels : 1u;
             size_t n = 0; // the levels back to back, level l = max(1, w >> l) x max(1, h >> l) (vulkan/resource_utils.cpp:86-100)
             for (uint32_t l = 0, w = td.width, hh = td.height; l < levels; ++l, w = std::max(1u, w / 2), hh = std::max(1u, hh / 2)) n += (size_t)w * hh;
-            if ((rc = dev_alloc(h, &dt, n, &h->scene_allocs))) return rc;
-            HIP_TRY(h, hipMemcpy(dt, td.rgba8, n * 4, hipMemcpyHostToDevice));
+            if ((rc = dev_upload(h, &dt, n, td.rgba8, hipMemcpyHostToDevice, &h->scene_allocs))) return rc;
             tex[t].texels = dt;
             tex[t].width = (int)td.width;
             tex[t].height = (int)td.height;
             tex[t].srgb = td.srgb ? 1 : 0;
             tex[t].levels = (int)levels;
         }
-        if ((rc = dev_alloc(h, &d_textures, std::max<size_t>(1, tex.size()), &h->scene_allocs))) return rc;
-        if (!tex.empty()) HIP_TRY(h, hipMemcpy(d_textures, tex.data(), tex.size() * sizeof(RpTexture), hipMemcpyHostToDevice));
+        if ((rc = dev_upload(h, &d_textures, tex.size(), tex.data(), hipMemcpyHostToDevice, &h->scene_allocs))) return rc;
         float lut[256];
         rp_srgb_decode_lut(lut);
-        if ((rc = dev_alloc(h, &d_srgb_lut, 256, &h->scene_allocs))) return rc;
-        HIP_TRY(h, hipMemcpy(d_srgb_lut, lut, sizeof(lut), hipMemcpyHostToDevice));
+        if ((rc = dev_upload(h, &d_srgb_lut, 256, lut, hipMemcpyHostToDevice, &h->scene_allocs))) return rc;
     }
     return RPTR_OK;
 }
-// the quantised vertex streams, one allocation per stream; dynamic meshes keep full-precision float positions next to them
+// the quantised vertex streams, one allocation per stream (the float positions of deforming meshes belong to the scene copies: scene_copy_build)
 static int scene_upload_vertex_streams(rptr_hip *h, const RptrSceneDesc *s, std::vector<const uint64_t *> &d_qpos, std::vector<const uint64_t *> &d_qnu) {
     int rc;
     d_qpos.assign(s->num_geometries, nullptr);
@@ -83,66 +81,45 @@ static int scene_upload_vertex_streams(rptr_hip *h, const RptrSceneDesc *s, std:
     for (uint32_t g = 0; g < s->num_geometries; ++g) {
         const RptrGeometryDesc &gd = s->geometries[g];
         uint64_t *dp = nullptr;
-        if ((rc = dev_alloc(h, &dp, (size_t)gd.num_tris * 3, &h->scene_allocs))) return rc;
-        if (gd.num_tris) HIP_TRY(h, hipMemcpy(dp, gd.qpos, (size_t)gd.num_tris * 24, hipMemcpyHostToDevice));
+        if ((rc = dev_upload(h, &dp, (size_t)gd.num_tris * 3, gd.qpos, hipMemcpyHostToDevice, &h->scene_allocs))) return rc;
         d_qpos[g] = dp;
         if (gd.qnrm_uv && (gd.has_normals || gd.has_uvs)) {
             uint64_t *dn = nullptr;
-            if ((rc = dev_alloc(h, &dn, (size_t)gd.num_tris * 3, &h->scene_allocs))) return rc;
-            if (gd.num_tris) HIP_TRY(h, hipMemcpy(dn, gd.qnrm_uv, (size_t)gd.num_tris * 24, hipMemcpyHostToDevice));
+            if ((rc = dev_upload(h, &dn, (size_t)gd.num_tris * 3, gd.qnrm_uv, hipMemcpyHostToDevice, &h->scene_allocs))) return rc;
             d_qnu[g] = dn;
         }
     }
-    // ---- dynamic meshes keep full-precision float positions next to the quantised stream
-    h->master.dynpos.assign(s->num_geometries, nullptr);
     h->geom_tris.assign(s->num_geometries, 0);
     h->geom_mesh.assign(s->num_geometries, -1);
-    h->master.mesh_dirty.assign(s->num_meshes, 0);
-    h->master.mesh_dyn.assign(s->num_meshes, nullptr);
-    for (uint32_t m = 0; m < s->num_meshes; ++m) {
-        const RptrMeshDesc &mesh = s->meshes[m];
-        std::vector<const float *> table(mesh.num_geometries, nullptr);
-        for (uint32_t j = 0; j < mesh.num_geometries; ++j) {
-            const uint32_t gi = mesh.first_geometry + j;
-            const RptrGeometryDesc &gd = s->geometries[gi];
-            h->geom_tris[gi] = gd.num_tris;
-            h->geom_mesh[gi] = (int)m;
-            if (!(mesh.dynamic & kMeshDeforms)) continue;
-            std::vector<float> pos((size_t)gd.num_tris * 9);
-            for (size_t v = 0; v < (size_t)gd.num_tris * 3; ++v) dequantize_position(gd.qpos[v], gd.quantized_scaling, gd.quantized_offset, &pos[3 * v]);
-            float *dp = nullptr;
-            if ((rc = dev_alloc(h, &dp, pos.size(), &h->scene_allocs))) return rc;
-            if (!pos.empty()) HIP_TRY(h, hipMemcpy(dp, pos.data(), pos.size() * sizeof(float), hipMemcpyHostToDevice));
-            h->master.dynpos[gi] = dp;
-            table[j] = dp;
+    for (uint32_t m = 0; m < s->num_meshes; ++m)
+        for (uint32_t j = 0; j < s->meshes[m].num_geometries; ++j) {
+            h->geom_tris[s->meshes[m].first_geometry + j] = s->geometries[s->meshes[m].first_geometry + j].num_tris;
+            h->geom_mesh[s->meshes[m].first_geometry + j] = (int)m;
         }
-        if (mesh.dynamic & kMeshDeforms) {
-            const float **dt = nullptr;
-            if ((rc = dev_alloc(h, &dt, table.size(), &h->scene_allocs))) return rc;
-            if (!table.empty()) HIP_TRY(h, hipMemcpy(dt, table.data(), table.size() * sizeof(float *), hipMemcpyHostToDevice));
-            h->master.mesh_dyn[m] = dt;
-            h->master.mesh_dirty[m] = 2;
-        }
-    }
     return RPTR_OK;
 }
+// what set_scene works out on the host and every scene copy is made from
+struct SceneTables {
+    std::vector<RpGeomRecord> geoms;  // per (parameterized mesh, geometry); dyn_pos is left NULL: a copy's records point at ITS positions
+    std::vector<uint32_t> geom_index; // ... and the global geometry each record is about
+    std::vector<int> pmesh_base;      // per parameterized mesh: its first record
+    std::vector<uint32_t> blas_list;  // scene_refit_tables: the node lists and depth levels of the dynamic meshes' trees
+    std::vector<std::array<uint2, RP_REFIT_LEVELS>> levels;
+};
 // geometry records per (parameterized mesh, geometry): instanced_geometry[] (render_vulkan.cpp:2748-2850)
-static int scene_geometry_records(rptr_hip *h, const RptrSceneDesc *s, const std::vector<const uint64_t *> &d_qpos, const std::vector<const uint64_t *> &d_qnu,
-                                  std::vector<RpGeomRecord> &geoms, std::vector<int> &pmesh_base) {
+static int scene_geometry_records(rptr_hip *h, const RptrSceneDesc *s, const std::vector<const uint64_t *> &d_qpos, const std::vector<const uint64_t *> &d_qnu, SceneTables &T) {
     int rc;
-    geoms.clear();
-    pmesh_base.assign(s->num_parameterized_meshes, 0);
+    T.geoms.clear();
+    T.geom_index.clear();
+    T.pmesh_base.assign(s->num_parameterized_meshes, 0);
     for (uint32_t p = 0; p < s->num_parameterized_meshes; ++p) {
         const RptrParameterizedMeshDesc &pm = s->parameterized_meshes[p];
         const RptrMeshDesc &mesh = s->meshes[pm.mesh];
-        pmesh_base[p] = (int)geoms.size();
+        T.pmesh_base[p] = (int)T.geoms.size();
         size_t total_tris = 0;
         for (uint32_t j = 0; j < mesh.num_geometries; ++j) total_tris += s->geometries[mesh.first_geometry + j].num_tris;
         uint8_t *d_ids = nullptr;
-        if (pm.tri_material_ids) {
-            if ((rc = dev_alloc(h, &d_ids, total_tris, &h->scene_allocs))) return rc;
-            if (total_tris) HIP_TRY(h, hipMemcpy(d_ids, pm.tri_material_ids, total_tris, hipMemcpyHostToDevice));
-        }
+        if (pm.tri_material_ids && (rc = dev_upload(h, &d_ids, total_tris, pm.tri_material_ids, hipMemcpyHostToDevice, &h->scene_allocs))) return rc;
         size_t prim_offset = 0;
         for (uint32_t j = 0; j < mesh.num_geometries; ++j) {
             const uint32_t gi = mesh.first_geometry + j;
@@ -152,13 +129,13 @@ static int scene_geometry_records(rptr_hip *h, const RptrSceneDesc *s, const std
             r.qpos = d_qpos[gi];
             r.qnrm_uv = d_qnu[gi];
             r.mat_ids = d_ids ? d_ids + prim_offset : nullptr;
-            r.dyn_pos = h->master.dynpos[gi];
             memcpy(r.scaling, gd.quantized_scaling, 12);
             memcpy(r.offset, gd.quantized_offset, 12);
             r.material_id = d_ids ? -1 - pm.material_offsets[j] : pm.material_offsets[j];
             r.flags = (gd.has_normals && d_qnu[gi] ? RP_GEOM_HAS_NORMALS : 0u) | (gd.has_uvs && d_qnu[gi] ? RP_GEOM_HAS_UVS : 0u) |
-                      (h->master.dynpos[gi] ? RP_GEOM_DYNAMIC : 0u);
-            geoms.push_back(r);
+                      (mesh.dynamic & kMeshDeforms ? RP_GEOM_DYNAMIC : 0u);
+            T.geoms.push_back(r);
+            T.geom_index.push_back(gi);
             prim_offset += gd.num_tris;
         }
     }
@@ -203,11 +180,13 @@ static int scene_build_acceleration_structure(rptr_hip *h, const RptrSceneDesc *
     }
     return RPTR_OK;
 }
-// refit tables: the top level by height (children before parents); the depth levels of every dynamic mesh's tree
-static int scene_refit_tables(rptr_hip *h, std::vector<uint32_t> &refit_list, std::vector<uint32_t> &h_blas_list, std::vector<std::array<uint2, RP_REFIT_LEVELS>> &h_levels) {
-    refit_list.clear();
-    h_blas_list.assign(h->h_nodes.size(), 0u);
-    h_levels.assign(h->meshes.size(), std::array<uint2, RP_REFIT_LEVELS>());
+// refit tables. The top level by height (children before parents) is the same for every scene copy: worked out and uploaded here
+// (d_refit_list, d_refit_levels, refit_top_all). The depth levels of every dynamic mesh's tree differ per copy once a copy is rebuilt:
+// worked out here, left in T, uploaded per copy (scene_copy_refit_tables).
+static int scene_refit_tables(rptr_hip *h, SceneTables &T) {
+    std::vector<uint32_t> refit_list;
+    T.blas_list.assign(h->h_nodes.size(), 0u);
+    T.levels.assign(h->meshes.size(), std::array<uint2, RP_REFIT_LEVELS>());
     // (the bottom-level trees of dynamic meshes are refitted bottom-up with arrival counters, lbvh.h rp_k_refit_up: per node its parent and the
     // number of its inner children)
     h->refit_levels_tlas.clear();
@@ -243,7 +222,7 @@ static int scene_refit_tables(rptr_hip *h, std::vector<uint32_t> &refit_list, st
         }
         for (size_t m = 0; m < h->meshes.size(); ++m) {
             const MeshRt &mr = h->meshes[m];
-            for (auto &l : h_levels[m]) l = make_uint2((uint32_t)mr.node_base, (uint32_t)mr.node_base);
+            for (auto &l : T.levels[m]) l = make_uint2((uint32_t)mr.node_base, (uint32_t)mr.node_base);
             if (!mr.dynamic) continue;
             std::vector<std::vector<uint32_t>> by_depth;
             std::vector<std::pair<int, int>> bfs{{h->mesh_root[m], 0}};
@@ -259,12 +238,23 @@ static int scene_refit_tables(rptr_hip *h, std::vector<uint32_t> &refit_list, st
             for (int slot = 0; slot < RP_REFIT_LEVELS; ++slot) {
                 const int d = RP_REFIT_LEVELS - 1 - slot;
                 const uint32_t cnt = (size_t)d < by_depth.size() ? (uint32_t)by_depth[(size_t)d].size() : 0u;
-                h_levels[m][(size_t)slot] = make_uint2(at, at + cnt);
-                for (uint32_t k = 0; k < cnt; ++k) h_blas_list[at + k] = by_depth[(size_t)d][k];
+                T.levels[m][(size_t)slot] = make_uint2(at, at + cnt);
+                for (uint32_t k = 0; k < cnt; ++k) T.blas_list[at + k] = by_depth[(size_t)d][k];
                 at += cnt;
             }
         }
     }
+    int rc;
+    if ((rc = dev_upload(h, &h->d_refit_list, refit_list.size(), refit_list.data(), hipMemcpyHostToDevice, &h->scene_allocs))) return rc;
+    // the instance bounds and the (small) top-level levels of a refit share one launch (kernels.h rp_k_refit_top): every level is one
+    // more dependent launch otherwise, and an animated frame pays for them whatever its size
+    const uint32_t small = 4096;
+    std::vector<uint2> lv;
+    for (auto &l : h->refit_levels_tlas) lv.push_back(make_uint2(l[0], l[1]));
+    h->refit_top_all = (size_t)h->num_tlas_insts <= 4 * small; // (only the records the top level refers to have bounds: a flattened tree's triangles name the others)
+    for (auto &l : h->refit_levels_tlas) h->refit_top_all = h->refit_top_all && l[1] - l[0] <= small;
+    h->d_refit_levels = nullptr;
+    if (!lv.empty() && (rc = dev_upload(h, &h->d_refit_levels, lv.size(), lv.data(), hipMemcpyHostToDevice, &h->scene_allocs))) return rc;
     return RPTR_OK;
 }
 // the traversal's scheduling thresholds and pool size for this scene's trees (RpScene.node_min / refill_min / fetch_max)
@@ -336,6 +326,132 @@ static void scene_traversal_preset(rptr_hip *h) {
         h->master.dscene.fetch_max = h->opt.v[OPT_TRAVERSE_FETCH] > 0 ? (int)std::max(64ll, h->opt.v[OPT_TRAVERSE_FETCH] / 64 * 64) : (best_cost >= 24.0 ? 0 : 384);
     }
 }
+// level tables + node lists of the dynamic meshes + per-mesh node counts (one set per scene copy: copies are rebuilt independently)
+static int scene_copy_refit_tables(rptr_hip *h, const SceneTables &T, SceneCopy &sc) {
+    int rc;
+    sc.device_built.assign(h->meshes.size(), 0);
+    sc.built_epoch.assign(h->meshes.size(), 0);
+    sc.scratch = RpLbvhScratch();
+    sc.blas_list = nullptr;
+    sc.blas_levels = nullptr;
+    sc.mesh_count = nullptr;
+    sc.host_levels = T.levels;
+    sc.levels_known.assign(h->meshes.size(), 1);
+    release_scene_copy_host(sc);
+    sc.pinned_levels.assign(h->meshes.size(), nullptr);
+    sc.ev_levels.assign(h->meshes.size(), nullptr);
+    sc.inst_version = h->inst_version;
+    sc.tlas_rebuilt = false;
+    sc.tlas_list = nullptr;
+    sc.tlas_levels = nullptr;
+    sc.tlas_count = nullptr;
+    if (h->tlas_capacity > 0) { // the level lists of a top level this copy builds itself (tlas_build.h)
+        if ((rc = dev_alloc(h, &sc.tlas_list, (size_t)h->tlas_capacity, &h->scene_allocs))) return rc;
+        if ((rc = dev_alloc(h, &sc.tlas_levels, RP_REFIT_LEVELS, &h->scene_allocs))) return rc;
+        if ((rc = dev_alloc(h, &sc.tlas_count, 1, &h->scene_allocs))) return rc;
+    }
+    if (!h->has_dynamic) return RPTR_OK;
+    std::vector<int> counts;
+    for (const MeshRt &mr : h->meshes) counts.push_back(mr.node_count);
+    if ((rc = dev_upload(h, &sc.blas_list, T.blas_list.size(), T.blas_list.data(), hipMemcpyHostToDevice, &h->scene_allocs))) return rc;
+    if ((rc = dev_upload(h, &sc.blas_levels, T.levels.size() * RP_REFIT_LEVELS, T.levels.data(), hipMemcpyHostToDevice, &h->scene_allocs))) return rc;
+    if ((rc = dev_upload(h, &sc.mesh_count, counts.size(), counts.data(), hipMemcpyHostToDevice, &h->scene_allocs))) return rc;
+    for (size_t m = 0; m < h->meshes.size(); ++m)
+        if (h->meshes[m].dynamic) {
+            if (hipHostMalloc((void **)&sc.pinned_levels[m], RP_REFIT_LEVELS * sizeof(uint2), hipHostMallocDefault) != hipSuccess)
+                return fail(h, RPTR_E_NOMEM, "hipHostMalloc failed");
+            HIP_TRY(h, hipEventCreateWithFlags(&sc.ev_levels[m], hipEventDisableTiming));
+        }
+    return RPTR_OK;
+}
+// One scene copy (host_state.h SceneCopy), given where its contents come from: the master set (from == NULL) is filled from the host's
+// arrays, a frame context's copy from the master's device buffers. Either way the copy owns the node array with its boxes (ONE array,
+// top level first: 88 bytes per node), the instance bounds, records and staged transforms (a frame still rendering never sees an instance
+// move), the float positions of the deforming meshes with their per-mesh tables, geometry records that point at THOSE positions, and its
+// refit tables. Triangles, shading records and triangle bounds only change when a mesh deforms: the context copies of a scene whose
+// instances move and nothing else share the master's. The master's shading records are made afterwards (build_shade_records); a
+// context's copy takes them from there.
+static int scene_copy_build(rptr_hip *h, const RptrSceneDesc *s, const SceneTables &T, SceneCopy &sc, const SceneCopy *from) {
+    int rc;
+    std::vector<void *> *const A = &h->scene_allocs;
+    const hipMemcpyKind kind = from ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    const size_t nn = h->h_nodes.size(), nt = h->h_tris.size(), ni = h->h_insts.size();
+    // the table rptr_hip_update_instances stages into: per instance object_to_world + world_to_object, as the records hold them
+    std::vector<float> xf(from ? 0 : (size_t)24 * s->num_instances);
+    for (size_t i = 0; i * 24 < xf.size(); ++i) {
+        memcpy(&xf[24 * i], s->instances[i].transform, 48);
+        invert_affine(s->instances[i].transform, &xf[24 * i + 12]);
+    }
+    const void *src_nodes = h->h_nodes.data(), *src_node_box = h->h_node_box.data(), *src_tris = h->h_tris.data(), *src_insts = h->h_insts.data(), *src_xf = xf.data();
+    if (from) {
+        sc.dscene = from->dscene; // (the static arrays are shared between all copies)
+        src_nodes = from->nodes, src_node_box = from->node_box, src_tris = from->tris, src_insts = from->dscene.insts, src_xf = from->inst_xf;
+    }
+    if ((rc = dev_upload(h, &sc.nodes, nn, src_nodes, kind, A))) return rc;
+    if ((rc = dev_upload(h, &sc.node_box, 6 * nn, src_node_box, kind, A))) return rc;
+    if ((rc = dev_alloc(h, &sc.inst_box, 6 * ni, A))) return rc;
+    RptrBvhInstance *insts = nullptr;
+    if ((rc = dev_upload(h, &insts, ni, src_insts, kind, A))) return rc;
+    if ((rc = dev_upload(h, &sc.inst_xf, (size_t)24 * s->num_instances, src_xf, kind, A))) return rc;
+    sc.tri_box = nullptr;
+    if (!from || h->has_dynamic) {
+        if ((rc = dev_upload(h, &sc.tris, nt, src_tris, kind, A, 2))) return rc; // +2: a leaf is fetched as whole pairs
+        if ((rc = from ? dev_upload(h, &sc.shade, nt, from->shade, kind, A, 1) : dev_alloc(h, &sc.shade, nt + 1, A))) return rc;
+        if (h->has_dynamic && (rc = dev_alloc(h, &sc.tri_box, 6 * nt, A))) return rc;
+    } else {
+        sc.tris = from->tris;
+        sc.shade = from->shade;
+    }
+    // ---- deforming meshes keep full-precision float positions next to the quantised stream, and a table of them per mesh
+    sc.dynpos.assign(s->num_geometries, nullptr);
+    sc.mesh_dirty.assign(s->num_meshes, 0);
+    sc.mesh_dyn.assign(s->num_meshes, nullptr);
+    for (uint32_t m = 0; m < s->num_meshes; ++m) {
+        const RptrMeshDesc &mesh = s->meshes[m];
+        if (!(mesh.dynamic & kMeshDeforms)) continue;
+        std::vector<const float *> table(mesh.num_geometries, nullptr);
+        for (uint32_t j = 0; j < mesh.num_geometries; ++j) {
+            const uint32_t gi = mesh.first_geometry + j;
+            const RptrGeometryDesc &gd = s->geometries[gi];
+            std::vector<float> pos(from ? 0 : (size_t)gd.num_tris * 9);
+            for (size_t v = 0; 3 * v < pos.size(); ++v) dequantize_position(gd.qpos[v], gd.quantized_scaling, gd.quantized_offset, &pos[3 * v]);
+            if ((rc = dev_upload(h, &sc.dynpos[gi], (size_t)gd.num_tris * 9, from ? (const void *)from->dynpos[gi] : pos.data(), kind, A))) return rc;
+            table[j] = sc.dynpos[gi];
+        }
+        if ((rc = dev_upload(h, &sc.mesh_dyn[m], table.size(), table.data(), hipMemcpyHostToDevice, A))) return rc;
+        sc.mesh_dirty[m] = 2;
+    }
+    std::vector<RpGeomRecord> geoms = T.geoms;
+    for (size_t r = 0; r < geoms.size(); ++r) geoms[r].dyn_pos = sc.dynpos[T.geom_index[r]];
+    RpGeomRecord *d_geoms = nullptr;
+    if ((rc = dev_upload(h, &d_geoms, geoms.size(), geoms.data(), hipMemcpyHostToDevice, A))) return rc;
+    sc.dscene.nodes = sc.nodes;
+    sc.dscene.tris = sc.tris;
+    sc.dscene.shade = sc.shade;
+    sc.dscene.insts = insts;
+    sc.dscene.geoms = d_geoms;
+    sc.version = h->refit_version;
+    return scene_copy_refit_tables(h, T, sc);
+}
+// what build_host_bvh made becomes the handle's
+static void scene_adopt_bvh(rptr_hip *h, HostBvh &B) {
+    h->h_nodes = std::move(B.nodes);
+    h->h_node_box = std::move(B.node_box);
+    h->h_tris = std::move(B.tris);
+    h->h_insts = std::move(B.insts);
+    h->meshes = std::move(B.meshes);
+    h->mesh_root = std::move(B.mesh_root);
+    h->num_tlas_insts = B.num_tlas_insts;
+    h->num_tlas_nodes = B.num_tlas_nodes;
+    h->flat_tris = B.flat_tris;
+    h->flat_nodes = B.flat_nodes;
+    h->tlas_capacity = B.tlas_capacity;
+    memcpy(h->scene_lo, B.scene_lo, 12);
+    memcpy(h->scene_hi, B.scene_hi, 12);
+    h->master.dscene.num_nodes = (uint32_t)h->h_nodes.size();
+    h->master.dscene.flat_id_bias = B.flat_id_bias > 0 ? B.flat_id_bias : 1;
+    h->master.dscene.single_instance = (h->num_tlas_insts == 1 && h->opt.v[OPT_SINGLE_INSTANCE] != 0) ? 1 : 0;
+}
 int rptr_hip_set_scene(rptr_hip_t *h, const RptrSceneDesc *s) {
     if (!h || !s) return fail(h, RPTR_E_INVALID, "NULL argument");
     HIP_TRY(h, hipSetDevice(h->device));
@@ -353,29 +469,34 @@ int rptr_hip_set_scene(rptr_hip_t *h, const RptrSceneDesc *s) {
     h->have_scene = false;
     int rc;
     if ((rc = scene_validate(h, s))) return rc;
-    // ---- uploads: textures, vertex streams, geometry records
+    // ---- the static data, shared by every scene copy: textures, vertex streams, per-triangle material ids (with the host side of the
+    // geometry records that name them), materials, lights
+    RpScene &ds = h->master.dscene;
     RpTexture *d_textures = nullptr;
     float *d_srgb_lut = nullptr;
     if ((rc = scene_upload_textures(h, s, d_textures, d_srgb_lut))) return rc;
     std::vector<const uint64_t *> d_qpos, d_qnu;
     if ((rc = scene_upload_vertex_streams(h, s, d_qpos, d_qnu))) return rc;
-    std::vector<RpGeomRecord> geoms;
-    std::vector<int> pmesh_base;
-    if ((rc = scene_geometry_records(h, s, d_qpos, d_qnu, geoms, pmesh_base))) return rc;
+    SceneTables T;
+    if ((rc = scene_geometry_records(h, s, d_qpos, d_qnu, T))) return rc;
+    RptrBaseMaterial *d_mats = nullptr;
+    RptrTriLightData *d_lights = nullptr;
+    if ((rc = dev_upload(h, &d_mats, s->num_materials, s->materials, hipMemcpyHostToDevice, &h->scene_allocs))) return rc;
+    // light buffer padded with one zeroed bin (+1): sample_tri_lights may read light_id == bin_end
+    const size_t light_pad = RPTR_BINNED_LIGHTS_BIN_MAX_SIZE + 1;
+    if ((rc = dev_upload(h, &d_lights, s->num_lights, s->lights, hipMemcpyHostToDevice, &h->scene_allocs, light_pad))) return rc;
+    HIP_TRY(h, hipMemset(d_lights + s->num_lights, 0, light_pad * sizeof(RptrTriLightData)));
+    ds.materials = d_mats;
+    ds.lights = d_lights;
+    ds.num_lights = h->num_lights = (int)s->num_lights;
+    ds.num_materials = h->num_materials = (int)s->num_materials;
+    ds.num_textures = (int)s->num_textures;
+    ds.textures = d_textures;
+    ds.srgb_lut = d_srgb_lut;
     // ---- acceleration structure
     HostBvh B;
-    if ((rc = scene_build_acceleration_structure(h, s, d_qpos, geoms, B))) return rc;
-    h->h_nodes = std::move(B.nodes);
-    h->h_node_box = std::move(B.node_box);
-    h->h_tris = std::move(B.tris);
-    h->h_insts = std::move(B.insts);
-    h->num_tlas_insts = B.num_tlas_insts;
-    h->meshes = std::move(B.meshes);
-    h->mesh_root = std::move(B.mesh_root);
-    h->num_tlas_nodes = B.num_tlas_nodes;
-    h->flat_tris = B.flat_tris;
-    h->flat_nodes = B.flat_nodes;
-    h->tlas_capacity = B.tlas_capacity;
+    if ((rc = scene_build_acceleration_structure(h, s, d_qpos, T.geoms, B))) return rc;
+    scene_adopt_bvh(h, B);
     // ---- moving instances: which instances have top-level records of their own, which ones carry lights
     h->num_instances = s->num_instances;
     h->inst_movable.assign(s->num_instances, 0);
@@ -397,221 +518,32 @@ int rptr_hip_set_scene(rptr_hip_t *h, const RptrSceneDesc *s) {
         h->inst_emissive.assign(s->num_instances, 0);
         for (uint32_t i = 0; i < s->num_instances; ++i) h->inst_emissive[i] = pmesh_emissive[s->instances[i].parameterized_mesh];
     }
-    memcpy(h->scene_lo, B.scene_lo, 12);
-    memcpy(h->scene_hi, B.scene_hi, 12);
-    // ---- refit tables
-    std::vector<uint32_t> refit_list, h_blas_list;
-    std::vector<std::array<uint2, RP_REFIT_LEVELS>> h_levels;
-    if ((rc = scene_refit_tables(h, refit_list, h_blas_list, h_levels))) return rc;
+    if ((rc = dev_alloc(h, &h->d_inst_rejected, 1, &h->scene_allocs))) return rc;
+    HIP_TRY(h, hipMemset(h->d_inst_rejected, 0, sizeof(uint32_t)));
+    // ---- refit tables, then the master copy
+    if ((rc = scene_refit_tables(h, T))) return rc;
     h->rebuild_epoch.assign(h->meshes.size(), 0);
     h->bvh_credit = 0;
     h->rebuild_cursor = 0;
-    // ---- upload
-    RptrBvh4Node *d_nodes = nullptr;
-    RptrBvhTri *d_tris = nullptr;
-    RptrBvhInstance *d_insts = nullptr;
-    RpGeomRecord *d_geoms = nullptr;
-    RptrBaseMaterial *d_mats = nullptr;
-    RptrTriLightData *d_lights = nullptr;
-    if ((rc = dev_alloc(h, &d_nodes, h->h_nodes.size(), &h->scene_allocs))) return rc;
-    if ((rc = dev_alloc(h, &d_tris, h->h_tris.size() + 2, &h->scene_allocs))) return rc; // +2: a leaf is fetched as whole pairs
-    if ((rc = dev_alloc(h, &d_insts, h->h_insts.size(), &h->scene_allocs))) return rc;
-    if ((rc = dev_alloc(h, &d_geoms, geoms.size(), &h->scene_allocs))) return rc;
-    if ((rc = dev_alloc(h, &d_mats, s->num_materials, &h->scene_allocs))) return rc;
-    // light buffer padded with one zeroed bin (+1): sample_tri_lights may read light_id == bin_end
-    const size_t light_cap = (size_t)s->num_lights + RPTR_BINNED_LIGHTS_BIN_MAX_SIZE + 1;
-    if ((rc = dev_alloc(h, &d_lights, light_cap, &h->scene_allocs))) return rc;
-    if ((rc = dev_alloc(h, &h->d_refit_list, refit_list.size(), &h->scene_allocs))) return rc;
-    if ((rc = dev_alloc(h, &h->master.inst_box, (size_t)6 * h->h_insts.size(), &h->scene_allocs))) return rc;
-    h->master.tri_box = nullptr;
-    if (h->has_dynamic && (rc = dev_alloc(h, &h->master.tri_box, (size_t)6 * h->h_tris.size(), &h->scene_allocs))) return rc;
-    if (!refit_list.empty()) HIP_TRY(h, hipMemcpy(h->d_refit_list, refit_list.data(), refit_list.size() * 4, hipMemcpyHostToDevice));
-    {
-        // the instance bounds and the (small) top-level levels of a refit share one launch (kernels.h rp_k_refit_top): every level is one
-        // more dependent launch otherwise, and an animated frame pays for them whatever its size
-        const uint32_t small = 4096;
-        std::vector<uint2> lv;
-        for (auto &l : h->refit_levels_tlas) lv.push_back(make_uint2(l[0], l[1]));
-        h->refit_top_all = (size_t)h->num_tlas_insts <= 4 * small; // (only the records the top level refers to have bounds: a flattened tree's triangles name the others)
-        for (auto &l : h->refit_levels_tlas) h->refit_top_all = h->refit_top_all && l[1] - l[0] <= small;
-        h->d_refit_levels = nullptr;
-        if (!lv.empty()) {
-            if ((rc = dev_alloc(h, &h->d_refit_levels, lv.size(), &h->scene_allocs))) return rc;
-            HIP_TRY(h, hipMemcpy(h->d_refit_levels, lv.data(), lv.size() * sizeof(uint2), hipMemcpyHostToDevice));
-        }
-    }
-    // level tables + node lists of the dynamic meshes + per-mesh node counts (one set per scene copy: copies are rebuilt independently)
-    auto make_refit_tables = [&](SceneCopy &sc) -> int {
-        int rc2;
-        sc.device_built.assign(h->meshes.size(), 0);
-        sc.built_epoch.assign(h->meshes.size(), 0);
-        sc.scratch = RpLbvhScratch();
-        sc.blas_list = nullptr;
-        sc.blas_levels = nullptr;
-        sc.mesh_count = nullptr;
-        sc.host_levels = h_levels;
-        sc.levels_known.assign(h->meshes.size(), 1);
-        release_scene_copy_host(sc);
-        sc.pinned_levels.assign(h->meshes.size(), nullptr);
-        sc.ev_levels.assign(h->meshes.size(), nullptr);
-        sc.inst_version = h->inst_version;
-        sc.tlas_rebuilt = false;
-        sc.tlas_list = nullptr;
-        sc.tlas_levels = nullptr;
-        sc.tlas_count = nullptr;
-        if (h->tlas_capacity > 0) { // the level lists of a top level this copy builds itself (tlas_build.h)
-            if ((rc2 = dev_alloc(h, &sc.tlas_list, (size_t)h->tlas_capacity, &h->scene_allocs))) return rc2;
-            if ((rc2 = dev_alloc(h, &sc.tlas_levels, RP_REFIT_LEVELS, &h->scene_allocs))) return rc2;
-            if ((rc2 = dev_alloc(h, &sc.tlas_count, 1, &h->scene_allocs))) return rc2;
-        }
-        if (!h->has_dynamic) return RPTR_OK;
-        if ((rc2 = dev_alloc(h, &sc.blas_list, h->h_nodes.size(), &h->scene_allocs))) return rc2;
-        if ((rc2 = dev_alloc(h, &sc.blas_levels, h->meshes.size() * RP_REFIT_LEVELS, &h->scene_allocs))) return rc2;
-        if ((rc2 = dev_alloc(h, &sc.mesh_count, h->meshes.size(), &h->scene_allocs))) return rc2;
-        HIP_TRY(h, hipMemcpy(sc.blas_list, h_blas_list.data(), h_blas_list.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        HIP_TRY(h, hipMemcpy(sc.blas_levels, h_levels.data(), h_levels.size() * sizeof(h_levels[0]), hipMemcpyHostToDevice));
-        std::vector<int> counts;
-        for (const MeshRt &mr : h->meshes) counts.push_back(mr.node_count);
-        HIP_TRY(h, hipMemcpy(sc.mesh_count, counts.data(), counts.size() * sizeof(int), hipMemcpyHostToDevice));
-        for (size_t m = 0; m < h->meshes.size(); ++m)
-            if (h->meshes[m].dynamic) {
-                if (hipHostMalloc((void **)&sc.pinned_levels[m], RP_REFIT_LEVELS * sizeof(uint2), hipHostMallocDefault) != hipSuccess)
-                    return fail(h, RPTR_E_NOMEM, "hipHostMalloc failed");
-                HIP_TRY(h, hipEventCreateWithFlags(&sc.ev_levels[m], hipEventDisableTiming));
-            }
-        return RPTR_OK;
-    };
-    if ((rc = make_refit_tables(h->master))) return rc;
-    {   // the table rptr_hip_update_instances stages into: per instance object_to_world + world_to_object, as the records hold them
-        std::vector<float> xf((size_t)24 * s->num_instances);
-        for (uint32_t i = 0; i < s->num_instances; ++i) {
-            memcpy(&xf[(size_t)24 * i], s->instances[i].transform, 48);
-            invert_affine(s->instances[i].transform, &xf[(size_t)24 * i + 12]);
-        }
-        if ((rc = dev_alloc(h, &h->master.inst_xf, xf.size(), &h->scene_allocs))) return rc;
-        if (!xf.empty()) HIP_TRY(h, hipMemcpy(h->master.inst_xf, xf.data(), xf.size() * sizeof(float), hipMemcpyHostToDevice));
-        if ((rc = dev_alloc(h, &h->d_inst_rejected, 1, &h->scene_allocs))) return rc;
-        HIP_TRY(h, hipMemset(h->d_inst_rejected, 0, sizeof(uint32_t)));
-    }
     h->host_insts_stale = false;
     h->host_bvh_stale = false;
     h->master_refit_pending = false;
-    if ((rc = dev_alloc(h, &h->master.node_box, (size_t)6 * h->h_nodes.size(), &h->scene_allocs))) return rc;
-    HIP_TRY(h, hipMemcpy(h->master.node_box, h->h_node_box.data(), h->h_node_box.size() * 24, hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemcpy(d_nodes, h->h_nodes.data(), h->h_nodes.size() * sizeof(RptrBvh4Node), hipMemcpyHostToDevice));
-    if (!h->h_tris.empty()) HIP_TRY(h, hipMemcpy(d_tris, h->h_tris.data(), h->h_tris.size() * sizeof(RptrBvhTri), hipMemcpyHostToDevice));
-    if (!h->h_insts.empty())
-        HIP_TRY(h, hipMemcpy(d_insts, h->h_insts.data(), h->h_insts.size() * sizeof(RptrBvhInstance), hipMemcpyHostToDevice));
-    if (!geoms.empty()) HIP_TRY(h, hipMemcpy(d_geoms, geoms.data(), geoms.size() * sizeof(RpGeomRecord), hipMemcpyHostToDevice));
-    if (s->num_materials) HIP_TRY(h, hipMemcpy(d_mats, s->materials, s->num_materials * sizeof(RptrBaseMaterial), hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemset(d_lights, 0, light_cap * sizeof(RptrTriLightData)));
-    if (s->num_lights) HIP_TRY(h, hipMemcpy(d_lights, s->lights, s->num_lights * sizeof(RptrTriLightData), hipMemcpyHostToDevice));
-    h->master.nodes = d_nodes;
-    h->master.tris = d_tris;
-    h->master.version = h->refit_version;
-    h->master.dscene.nodes = d_nodes;
-    h->master.dscene.tris = d_tris;
-    h->master.dscene.insts = d_insts;
-    h->master.dscene.geoms = d_geoms;
-    h->master.dscene.materials = d_mats;
-    h->master.dscene.lights = d_lights;
-    h->master.dscene.num_lights = (int)s->num_lights;
-    h->master.dscene.num_materials = (int)s->num_materials;
-    h->master.dscene.num_nodes = (uint32_t)h->h_nodes.size();
-    h->master.dscene.flat_id_bias = B.flat_id_bias > 0 ? B.flat_id_bias : 1;
-    h->master.dscene.single_instance = (h->num_tlas_insts == 1 && h->opt.v[OPT_SINGLE_INSTANCE] != 0) ? 1 : 0;
-    h->master.dscene.num_textures = (int)s->num_textures;
-    h->master.dscene.textures = d_textures;
-    h->master.dscene.srgb_lut = d_srgb_lut;
+    if ((rc = scene_copy_build(h, s, T, h->master, nullptr))) return rc;
     scene_traversal_preset(h);
     // ---- one shading record per BVH triangle (dshade.h RpShadeTri), made on the device from what was just uploaded: per mesh with the
     // geometry records of the first parameterized mesh that uses it, or -- a flattened scene -- per triangle through the instance it names
-    {
-        RpShadeTri *d_shade = nullptr;
-        if ((rc = dev_alloc(h, &d_shade, h->h_tris.size() + 1, &h->scene_allocs))) return rc;
-        h->master.shade = d_shade;
-        h->master.dscene.shade = d_shade;
-        h->mesh_geometry_base.assign(s->num_meshes, -1);
-        for (uint32_t p = s->num_parameterized_meshes; p-- > 0;) h->mesh_geometry_base[s->parameterized_meshes[p].mesh] = pmesh_base[p];
-        if ((rc = build_shade_records(h, h->master, -1, h->stream))) return rc;
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-    }
-    h->num_lights = (int)s->num_lights;
-    h->num_materials = (int)s->num_materials;
+    h->mesh_geometry_base.assign(s->num_meshes, -1);
+    for (uint32_t p = s->num_parameterized_meshes; p-- > 0;) h->mesh_geometry_base[s->parameterized_meshes[p].mesh] = T.pmesh_base[p];
+    if ((rc = build_shade_records(h, h->master, -1, h->stream))) return rc;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
     // ---- dynamic scene (meshes that deform, or instances that move: RPTR_MESH_INSTANCES_MOVE) + frames in flight: every frame context
     // gets its own set of what a refit rewrites
     for (SceneCopy &sc : h->ctx_scene) release_scene_copy_host(sc);
     h->ctx_scene.clear();
     if ((h->has_dynamic || h->tlas_capacity > 0) && h->ctx.size() > 1) {
         h->ctx_scene.resize(h->ctx.size());
-        for (SceneCopy &sc : h->ctx_scene) {
-            sc.dscene = h->master.dscene;
-            sc.mesh_dirty.assign(s->num_meshes, 0);
-            sc.dynpos.assign(s->num_geometries, nullptr);
-            sc.mesh_dyn.assign(s->num_meshes, nullptr);
-            // (the node array is ONE array, top level first: a copy holds all of it, 88 bytes per node with its box. Triangles, shading
-            // records and triangle bounds only change when a mesh deforms: a scene whose instances move and nothing else shares the master's)
-            if ((rc = dev_alloc(h, &sc.nodes, h->h_nodes.size(), &h->scene_allocs))) return rc;
-            if (h->has_dynamic) {
-                if ((rc = dev_alloc(h, &sc.tris, h->h_tris.size() + 2, &h->scene_allocs))) return rc;
-                if ((rc = dev_alloc(h, &sc.shade, h->h_tris.size() + 1, &h->scene_allocs))) return rc;
-                if (!h->h_tris.empty()) HIP_TRY(h, hipMemcpy(sc.shade, h->master.shade, h->h_tris.size() * sizeof(RpShadeTri), hipMemcpyDeviceToDevice));
-                if ((rc = dev_alloc(h, &sc.tri_box, (size_t)6 * h->h_tris.size(), &h->scene_allocs))) return rc;
-            } else {
-                sc.tris = h->master.tris;
-                sc.shade = h->master.shade;
-                sc.tri_box = nullptr;
-            }
-            if ((rc = dev_alloc(h, &sc.node_box, (size_t)6 * h->h_nodes.size(), &h->scene_allocs))) return rc;
-            if ((rc = dev_alloc(h, &sc.inst_box, (size_t)6 * h->h_insts.size(), &h->scene_allocs))) return rc;
-            {   // its own instance records and staged transforms: a frame still rendering never sees an instance move
-                RptrBvhInstance *ci = nullptr;
-                if ((rc = dev_alloc(h, &ci, h->h_insts.size(), &h->scene_allocs))) return rc;
-                if (!h->h_insts.empty()) HIP_TRY(h, hipMemcpy(ci, d_insts, h->h_insts.size() * sizeof(RptrBvhInstance), hipMemcpyDeviceToDevice));
-                sc.dscene.insts = ci;
-                if ((rc = dev_alloc(h, &sc.inst_xf, (size_t)24 * s->num_instances, &h->scene_allocs))) return rc;
-                if (s->num_instances) HIP_TRY(h, hipMemcpy(sc.inst_xf, h->master.inst_xf, (size_t)96 * s->num_instances, hipMemcpyDeviceToDevice));
-            }
-            HIP_TRY(h, hipMemcpy(sc.nodes, d_nodes, h->h_nodes.size() * sizeof(RptrBvh4Node), hipMemcpyDeviceToDevice));
-            if (h->has_dynamic && !h->h_tris.empty()) HIP_TRY(h, hipMemcpy(sc.tris, d_tris, h->h_tris.size() * sizeof(RptrBvhTri), hipMemcpyDeviceToDevice));
-            HIP_TRY(h, hipMemcpy(sc.node_box, h->master.node_box, h->h_node_box.size() * 24, hipMemcpyDeviceToDevice));
-            std::vector<RpGeomRecord> cgeoms = geoms; // same records, pointing at this copy's float positions
-            for (uint32_t m = 0; m < s->num_meshes; ++m) {
-                const RptrMeshDesc &mesh = s->meshes[m];
-                if (!(mesh.dynamic & kMeshDeforms)) continue;
-                std::vector<const float *> table(mesh.num_geometries, nullptr);
-                for (uint32_t j = 0; j < mesh.num_geometries; ++j) {
-                    const uint32_t gi = mesh.first_geometry + j;
-                    const size_t nfl = (size_t)s->geometries[gi].num_tris * 9;
-                    float *dp = nullptr;
-                    if ((rc = dev_alloc(h, &dp, nfl, &h->scene_allocs))) return rc;
-                    if (nfl) HIP_TRY(h, hipMemcpy(dp, h->master.dynpos[gi], nfl * sizeof(float), hipMemcpyDeviceToDevice));
-                    sc.dynpos[gi] = dp;
-                    table[j] = dp;
-                }
-                const float **dt = nullptr;
-                if ((rc = dev_alloc(h, &dt, table.size(), &h->scene_allocs))) return rc;
-                if (!table.empty()) HIP_TRY(h, hipMemcpy(dt, table.data(), table.size() * sizeof(float *), hipMemcpyHostToDevice));
-                sc.mesh_dyn[m] = dt;
-                sc.mesh_dirty[m] = 2;
-            }
-            for (RpGeomRecord &r : cgeoms)
-                if (r.dyn_pos)
-                    for (uint32_t gi = 0; gi < s->num_geometries; ++gi)
-                        if (r.dyn_pos == h->master.dynpos[gi]) {
-                            r.dyn_pos = sc.dynpos[gi];
-                            break;
-                        }
-            RpGeomRecord *cg = nullptr;
-            if ((rc = dev_alloc(h, &cg, cgeoms.size(), &h->scene_allocs))) return rc;
-            if (!cgeoms.empty()) HIP_TRY(h, hipMemcpy(cg, cgeoms.data(), cgeoms.size() * sizeof(RpGeomRecord), hipMemcpyHostToDevice));
-            sc.dscene.nodes = sc.nodes;
-            sc.dscene.tris = sc.tris;
-            sc.dscene.shade = sc.shade;
-            sc.dscene.geoms = cg;
-            sc.version = h->refit_version;
-            if ((rc = make_refit_tables(sc))) return rc;
-        }
+        for (SceneCopy &sc : h->ctx_scene)
+            if ((rc = scene_copy_build(h, s, T, sc, &h->master))) return rc;
     }
     h->have_scene = true;
     // a new scene restarts accumulation (Shell::set_scene -> reset, libapp/shell.cpp:96-126)
@@ -796,6 +728,34 @@ static int lbvh_scratch(rptr_hip *h, SceneCopy &sc, size_t n, hipStream_t st) {
     return RPTR_OK;
 }
 
+// bits that tell n primitives apart (the low bits of a sort key)
+static int lbvh_index_bits(uint32_t n) {
+    int bits = 1;
+    while ((1ull << bits) < (unsigned long long)n) ++bits;
+    return bits;
+}
+// the front half both device builds share (lbvh.h), over the n boxes of `box`: bounds -> keys -> sort -> hierarchy -> flags -> scan, with
+// `after_hierarchy` (the bottom-level build's triangle gather) between hierarchy and flags. One primitive has no hierarchy: nothing runs.
+template <class F>
+static int lbvh_front_half(rptr_hip *h, RpLbvhScratch &w, const float *box, uint32_t n, int axis_bits, int leaf_size, hipStream_t st, F after_hierarchy) {
+    if (n < 2) return RPTR_OK;
+    const int g = grid_for(h, n);
+    hipLaunchKernelGGL(rp_k_lbvh_reset, dim3(1), dim3(64), 0, st, w.bounds);
+    hipLaunchKernelGGL(rp_k_lbvh_bounds, dim3(g), dim3(256), 0, st, box, n, w.bounds);
+    hipLaunchKernelGGL(rp_k_lbvh_keys, dim3(g), dim3(256), 0, st, box, n, w.bounds, w.keys_a, lbvh_index_bits(n), axis_bits);
+    size_t bytes = w.cub_bytes;
+    HIP_TRY(h, hipcub::DeviceRadixSort::SortKeys(w.cub_tmp, bytes, w.keys_a, w.keys_b, (int)n, 0, 64, st));
+    hipLaunchKernelGGL(rp_k_lbvh_hierarchy, dim3(g), dim3(256), 0, st, w.keys_b, (int)n, w.left, w.right, w.parent, w.first, w.last);
+    {
+        const int rc = after_hierarchy();
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(rp_k_lbvh_flags, dim3(g), dim3(256), 0, st, (int)n, w.parent, w.first, w.last, w.flag, w.depth4, leaf_size);
+    bytes = w.cub_bytes;
+    HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(w.cub_tmp, bytes, w.flag, w.slot, (int)n - 1, st));
+    return RPTR_OK;
+}
+
 // device-side rebuild of the bottom-level tree of dynamic mesh m of one scene copy (lbvh.h), on stream `st`. The triangles of the mesh
 // (current order) must hold the new vertices already (rp_k_refit_tris). Ends with the refit that gives the new topology its boxes.
 static int lbvh_rebuild(rptr_hip *h, SceneCopy &sc, size_t m, hipStream_t st, bool with_top) {
@@ -809,21 +769,14 @@ static int lbvh_rebuild(rptr_hip *h, SceneCopy &sc, size_t m, hipStream_t st, bo
     RptrBvhTri *tris = sc.tris + mr.tri_base;
     float *tri_box = sc.tri_box + 6ull * mr.tri_base;
     const int g = grid_for(h, n);
-    if (n >= 2) {
-        hipLaunchKernelGGL(rp_k_lbvh_reset, dim3(1), dim3(64), 0, st, w.bounds);
-        hipLaunchKernelGGL(rp_k_lbvh_bounds, dim3(g), dim3(256), 0, st, tri_box, n, w.bounds);
-        int index_bits = 1;
-        while ((1ull << index_bits) < (unsigned long long)n) ++index_bits;
-        hipLaunchKernelGGL(rp_k_lbvh_keys, dim3(g), dim3(256), 0, st, tri_box, n, w.bounds, w.keys_a, index_bits, 21);
-        size_t bytes = w.cub_bytes;
-        HIP_TRY(h, hipcub::DeviceRadixSort::SortKeys(w.cub_tmp, bytes, w.keys_a, w.keys_b, (int)n, 0, 64, st));
-        hipLaunchKernelGGL(rp_k_lbvh_hierarchy, dim3(g), dim3(256), 0, st, w.keys_b, (int)n, w.left, w.right, w.parent, w.first, w.last);
-        HIP_TRY(h, hipMemcpyAsync(w.tri_copy, tris, (size_t)n * sizeof(RptrBvhTri), hipMemcpyDeviceToDevice, st));
-        HIP_TRY(h, hipMemcpyAsync(w.tribox_copy, tri_box, (size_t)n * 24, hipMemcpyDeviceToDevice, st));
-        hipLaunchKernelGGL(rp_k_lbvh_gather, dim3(g), dim3(256), 0, st, w.keys_b, n, w.tri_copy, w.tribox_copy, tris, tri_box, (1ull << index_bits) - 1ull);
-        hipLaunchKernelGGL(rp_k_lbvh_flags, dim3(g), dim3(256), 0, st, (int)n, w.parent, w.first, w.last, w.flag, w.depth4, RP_LBVH_LEAF_TRIS);
-        bytes = w.cub_bytes;
-        HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(w.cub_tmp, bytes, w.flag, w.slot, (int)n - 1, st));
+    {
+        const int rc = lbvh_front_half(h, w, tri_box, n, 21, RP_LBVH_LEAF_TRIS, st, [&]() -> int { // the triangles and their boxes follow the sort
+            HIP_TRY(h, hipMemcpyAsync(w.tri_copy, tris, (size_t)n * sizeof(RptrBvhTri), hipMemcpyDeviceToDevice, st));
+            HIP_TRY(h, hipMemcpyAsync(w.tribox_copy, tri_box, (size_t)n * 24, hipMemcpyDeviceToDevice, st));
+            hipLaunchKernelGGL(rp_k_lbvh_gather, dim3(g), dim3(256), 0, st, w.keys_b, n, w.tri_copy, w.tribox_copy, tris, tri_box, (1ull << lbvh_index_bits(n)) - 1ull);
+            return RPTR_OK;
+        });
+        if (rc) return rc;
     }
     HIP_TRY(h, hipMemsetAsync(w.level_hist, 0, RP_REFIT_LEVELS * sizeof(uint32_t), st));
     hipLaunchKernelGGL(rp_k_lbvh_emit, dim3(g), dim3(256), 0, st, (int)n, w.left, w.right, w.first, w.last, w.flag, w.slot, w.depth4, mr.node_base, mr.tri_base, sc.nodes,
@@ -870,23 +823,14 @@ static int tlas_rebuild(rptr_hip *h, SceneCopy &sc, hipStream_t st) {
     }
     RpLbvhScratch &w = sc.scratch;
     const int g = grid_for(h, n);
-    int index_bits = 1;
-    while ((1ull << index_bits) < (unsigned long long)n) ++index_bits;
-    if (n >= 2) {
-        hipLaunchKernelGGL(rp_k_lbvh_reset, dim3(1), dim3(64), 0, st, w.bounds);
-        hipLaunchKernelGGL(rp_k_lbvh_bounds, dim3(g), dim3(256), 0, st, sc.inst_box, n, w.bounds);
-        hipLaunchKernelGGL(rp_k_lbvh_keys, dim3(g), dim3(256), 0, st, sc.inst_box, n, w.bounds, w.keys_a, index_bits, RP_TLAS_AXIS_BITS);
-        size_t bytes = w.cub_bytes;
-        HIP_TRY(h, hipcub::DeviceRadixSort::SortKeys(w.cub_tmp, bytes, w.keys_a, w.keys_b, (int)n, 0, 64, st));
-        hipLaunchKernelGGL(rp_k_lbvh_hierarchy, dim3(g), dim3(256), 0, st, w.keys_b, (int)n, w.left, w.right, w.parent, w.first, w.last);
-        hipLaunchKernelGGL(rp_k_lbvh_flags, dim3(g), dim3(256), 0, st, (int)n, w.parent, w.first, w.last, w.flag, w.depth4, 1);
-        bytes = w.cub_bytes;
-        HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(w.cub_tmp, bytes, w.flag, w.slot, (int)n - 1, st));
+    {
+        const int rc = lbvh_front_half(h, w, sc.inst_box, n, RP_TLAS_AXIS_BITS, 1, st, [] { return RPTR_OK; });
+        if (rc) return rc;
     }
     HIP_TRY(h, hipMemsetAsync(w.level_hist, 0, RP_REFIT_LEVELS * sizeof(uint32_t), st));
     hipLaunchKernelGGL(rp_k_tlas_clear, dim3(grid_for(h, (size_t)h->tlas_capacity)), dim3(256), 0, st, sc.nodes, sc.node_box, (uint32_t)h->tlas_capacity);
     hipLaunchKernelGGL(rp_k_lbvh_emit, dim3(g), dim3(256), 0, st, (int)n, w.left, w.right, w.first, w.last, w.flag, w.slot, w.depth4, 0, 0, sc.nodes, w.level_hist,
-                       sc.tlas_count, RpLbvhLeaves{1, n >= 2 ? w.keys_b : nullptr, (1ull << index_bits) - 1ull});
+                       sc.tlas_count, RpLbvhLeaves{1, n >= 2 ? w.keys_b : nullptr, (1ull << lbvh_index_bits(n)) - 1ull});
     hipLaunchKernelGGL(rp_k_lbvh_level_scan, dim3(1), dim3(64), 0, st, w.level_hist, 0u, sc.tlas_levels, w.level_cursor);
     hipLaunchKernelGGL(rp_k_lbvh_level_scatter, dim3(grid_for(h, (size_t)h->tlas_capacity)), dim3(256), 0, st, sc.nodes, 0, sc.tlas_count, w.level_cursor, sc.tlas_list,
                        0x80000000u);

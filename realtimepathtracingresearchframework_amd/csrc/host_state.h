@@ -1,5 +1,5 @@
 // host_state.h -- what every part of the host runtime shares: the handle (rptr_hip), frame contexts, scene copies, the option table and its
-// process defaults, error reporting, device allocation, the hardware-queue note
+// process defaults, error reporting, device allocation and upload (dev_alloc / dev_upload), the hardware-queue note
 // Part of the ONE translation unit rptr_hip.hip (included there, in this order: host_state.h, host_bvh.inl, host_scene.inl,
 // host_frame.inl, host_access.inl, host_comm.h): the host runtime split along its seams; no symbol changed.
 #pragma once
@@ -479,6 +479,15 @@ int dev_alloc(rptr_hip *h, T **out, size_t count, std::vector<void *> *track) {
     h->bytes_allocated = h->bytes_scene + h->bytes_frame;
     (track ? track : &h->allocations)->push_back(p);
     *out = reinterpret_cast<T *>(p);
+    return RPTR_OK;
+}
+
+// dev_alloc of count + pad elements, the first `count` of them filled from `src` (nothing is copied when count == 0)
+template <class T>
+int dev_upload(rptr_hip *h, T **out, size_t count, const void *src, hipMemcpyKind kind, std::vector<void *> *track, size_t pad = 0) {
+    const int rc = dev_alloc(h, out, count + pad, track);
+    if (rc) return rc;
+    if (count) HIP_TRY(h, hipMemcpy(*out, src, count * sizeof(T), kind));
     return RPTR_OK;
 }
 
