@@ -303,7 +303,9 @@ typedef struct RptrSceneDesc {
  * returns the library's value. Fields named _pad must be zero. 4 = round 5: rptr_hip_set_option / _get_option; rptr_hip_set_frame_schedule /
  * _get_frame_schedule are gone (the device-driven frame schedules they selected lost to the stage launches and left the product).
  * 5 = round 6: RptrCreateInfo.flags (the library no longer touches GPU_MAX_HW_QUEUES unless RPTR_CREATE_SET_HW_QUEUES asks it to),
- * rptr_hip_build_id, option "fast_math", builder experiments behind the "experimental." key prefix. */
+ * rptr_hip_build_id, option "fast_math", builder experiments behind the "experimental." key prefix.
+ * (Moving lights -- RptrLightSource, rptr_hip_set_light_sources, rptr_hip_readback_lights -- leave it at 5: a new struct and two new
+ * entry points, no existing struct changes layout and no existing field changes meaning, which is what the number counts.) */
 #define RPTR_HIP_ABI_VERSION 5
 /* RptrCreateInfo.flags */
 #define RPTR_CREATE_SET_HW_QUEUES 1u /* rptr_hip_create may set the HIP runtime's GPU_MAX_HW_QUEUES for the WHOLE host process (setenv) when the
@@ -419,7 +421,8 @@ int rptr_hip_bvh_rebuild_count(const rptr_hip_t *h, uint64_t *out_rebuilds);
  * scene was not flattened), and in a flattened scene those of meshes with a non-zero RptrMeshDesc.dynamic (RPTR_MESH_INSTANCES_MOVE is
  * the bit that says nothing else). An instance baked into the flat tree: RPTR_E_INVALID. A bad range, NULL, a matrix that is not
  * finite or whose inverse is not (det == 0): RPTR_E_INVALID, nothing is staged. An instance whose parameterized mesh uses an emissive
- * material: RPTR_E_UNSUPPORTED -- RptrSceneDesc.lights are world-space triangles collected by the host and would go stale.
+ * material: RPTR_E_UNSUPPORTED -- RptrSceneDesc.lights are world-space triangles collected by the host and would go stale -- unless
+ * rptr_hip_set_light_sources registered where the lights came from (below).
  * rptr_hip_set_tlas_policy: RPTR_TLAS_REBUILD (default, what default_update_tlas does): a refit that finds moved instances builds a
  * NEW top level on the device (csrc/tlas_build.h: Morton keys of the record boxes + radix sort + binary radix tree + 4-wide collapse,
  * one record per leaf, boxes and encoding through the refit) -- in scenes where set_scene reserved room for one, i.e. where some
@@ -442,6 +445,37 @@ int rptr_hip_update_instances(rptr_hip_t *h, uint32_t first_instance, uint32_t c
 int rptr_hip_update_instances_device(rptr_hip_t *h, uint32_t first_instance, uint32_t count, const float *device_transforms12);
 int rptr_hip_set_tlas_policy(rptr_hip_t *h, int mode);
 int rptr_hip_tlas_rebuild_count(const rptr_hip_t *h, uint64_t *out_rebuilds);
+
+/* ---- moving lights: where every entry of RptrSceneDesc.lights came from, so that a refit can put it where its triangle is now.
+ * RptrSceneDesc.lights are world-space triangles the host collected and bin-equalised (librender/lights.cpp:14-90,220-349); the library
+ * does not know their origin, so without this call a moved emissive instance is refused (RPTR_E_UNSUPPORTED) and
+ * rptr_hip_update_vertices on an emissive dynamic mesh is accepted but leaves the lights WHERE THEY WERE: paths that hit the deformed
+ * emitter see it where it is, next-event estimation samples the old triangles, and the estimate is wrong without an error.
+ * rptr_hip_set_light_sources(h, sources, count): after set_scene, count == RptrSceneDesc.num_lights, sources[i] describes lights[i]
+ * (clones of one emitter repeat its source). Placement rule: a light's world-space vertex is its instance's object_to_world applied to
+ * the object-space vertex -- v0..v2 for a static mesh, the current float positions [9 * triangle ..] of `geometry` for a mesh flagged
+ * RPTR_MESH_DYNAMIC / _SUBTLY_DYNAMIC -- per row (m0 * x + m1 * y) + (m2 * z + m3) in float32 without contraction, the order of
+ * collect_emitters; radiance is never touched. The call checks the provenance on the host, once: the rule with the transforms set_scene
+ * received must reproduce lights[i] to 2^-20 * (|m0 x| + |m1 y| + |m2 z| + |m3|) per coordinate. RPTR_E_INVALID, naming the first
+ * offending light, for a mismatch, an instance / geometry / triangle out of range, a geometry that is not one of the instance's mesh,
+ * count != num_lights, or a call before set_scene; nothing changes then. (NULL, 0) unregisters: the light buffer is the one set_scene
+ * uploaded again. A new set_scene drops the registration. world_size > 1 is fine: every rank holds the whole scene, register on each.
+ * With sources registered, rptr_hip_update_instances[_device] accepts movable emissive instances, and the next rptr_hip_refit re-places
+ * the lights of every scene copy on that copy's stream (csrc/tlas_build.h rp_k_place_lights) when instances moved or a dynamic mesh
+ * that carries lights got new vertices. Every scene copy then owns its light buffer, like its instance records. The call waits for the
+ * frames in flight. Without registration nothing changes: the same refusals, the same launches.
+ * Bin membership, clone counts and order stay as the host made them. Bins are chosen uniformly and a bin's lights by resampling on
+ * their actual contribution, so the estimator stays unbiased under any motion; only how evenly the bins share the power -- the
+ * variance -- can drift when emitters change size (non-rigid change). Re-equalise with a new set_scene when that matters.
+ * rptr_hip_readback_lights: the master copy's light buffer (count == num_lights) after all pending work, a deferred refit included. */
+typedef struct RptrLightSource { /* 48 bytes, one per entry of RptrSceneDesc.lights, same order */
+    float v0[3], v1[3], v2[3];   /* object-space vertices as dequantized (dequantize.glsl:8-21) */
+    uint32_t instance;           /* scene instance the triangle belongs to */
+    uint32_t geometry;           /* global geometry index */
+    uint32_t triangle;           /* triangle within that geometry (unrolled order) */
+} RptrLightSource;
+int rptr_hip_set_light_sources(rptr_hip_t *h, const RptrLightSource *sources, uint32_t count);
+int rptr_hip_readback_lights(rptr_hip_t *h, RptrTriLightData *out, uint32_t count);
 
 /* ---- RenderBackend::params / lighting_params / update_config
  * (render_backend.h:69-76, render_vulkan.cpp:2943-2959) */

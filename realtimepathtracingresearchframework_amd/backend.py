@@ -86,6 +86,8 @@ def load_library(path=None):
     L.rptr_hip_update_instances_device.argtypes = [vp, C.c_uint32, C.c_uint32, vp]
     L.rptr_hip_set_tlas_policy.argtypes = [vp, i32]
     L.rptr_hip_tlas_rebuild_count.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.rptr_hip_set_light_sources.argtypes = [vp, vp, C.c_uint32]
+    L.rptr_hip_readback_lights.argtypes = [vp, vp, C.c_uint32]
     L.rptr_hip_bvh_build_info.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.rptr_hip_traversal_preset.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.rptr_hip_get_framebuffer_size.argtypes = [vp, C.POINTER(C.c_uint32)]
@@ -236,6 +238,7 @@ class RenderHip:
         """scene: realtimepathtracingresearchframework_amd.scenes.Scene (≙ const Scene&)."""
         desc = scene.desc()
         self._check(self._L.rptr_hip_set_scene(self._h, C.byref(desc)))
+        self._num_lights = int(desc.num_lights)
         self.update_config(scene)
 
     def update_config(self, scene_or_params):
@@ -532,6 +535,27 @@ class RenderHip:
         n = C.c_uint64()
         self._check(self._L.rptr_hip_tlas_rebuild_count(self._h, C.byref(n)))
         return int(n.value)
+
+    # ---- moving lights (rptr_hip_set_light_sources): where RptrSceneDesc.lights came from, so that a refit can re-place them
+    def set_light_sources(self, scene_or_array):
+        """Register the provenance of the scene's lights: a scenes.Scene (its `light_sources`, filled by prepare_lights) or an array of
+        lights.LIGHT_SOURCE_DTYPE, one record per light in the lights' order; None unregisters. Afterwards emissive instances may move
+        and refit() re-places the lights. set_scene never registers on its own, and a new set_scene drops the registration."""
+        from . import lights as L
+        src = getattr(scene_or_array, "light_sources", scene_or_array)
+        if src is None:
+            self._check(self._L.rptr_hip_set_light_sources(self._h, None, 0))
+            return
+        src = np.ascontiguousarray(src, dtype=L.LIGHT_SOURCE_DTYPE).reshape(-1)
+        self._check(self._L.rptr_hip_set_light_sources(self._h, src.ctypes.data_as(C.c_void_p) if len(src) else None, len(src)))
+
+    def readback_lights(self, count=None):
+        """The master scene copy's light buffer after all pending work: (n, 4, 3) float32 -- v0, v1, v2, radiance -- like Scene.lights.
+        count: the scene's number of lights (default: that of the last set_scene)."""
+        n = getattr(self, "_num_lights", 0) if count is None else int(count)
+        out = np.zeros((n, 4, 3), dtype=np.float32)
+        self._check(self._L.rptr_hip_readback_lights(self._h, out.ctypes.data_as(C.c_void_p), n))
+        return out
 
     def set_rng_variant(self, rng_variant, table=None):
         """RenderBackendOptions::rng_variant (render_params.glsl.h:34-37,76) + the table upload of the point set's render extension

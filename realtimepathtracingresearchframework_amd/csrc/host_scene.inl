@@ -364,6 +364,27 @@ static int scene_copy_refit_tables(rptr_hip *h, const SceneTables &T, SceneCopy 
         }
     return RPTR_OK;
 }
+// the light buffer of one scene copy. Without registered light sources every copy reads the buffer set_scene uploaded. With them
+// (rptr_hip_set_light_sources) the copy owns a buffer -- padded with the zeroed bin like the shared one, filled from `src` -- that its
+// refits re-place (refit_scene_copy), and the table of its float positions the placement reads.
+static int scene_copy_lights(rptr_hip *h, SceneCopy &sc, const RptrTriLightData *src) {
+    int rc;
+    sc.lights = nullptr;
+    sc.geom_dyn = nullptr;
+    sc.dscene.lights = h->d_lights_shared;
+    if (!h->d_light_sources) return RPTR_OK;
+    const size_t before = h->scene_allocs.size(), bytes_before = h->bytes_scene;
+    const size_t light_pad = RPTR_BINNED_LIGHTS_BIN_MAX_SIZE + 1, n = (size_t)h->num_lights;
+    std::vector<const float *> table(sc.dynpos.begin(), sc.dynpos.end());
+    rc = dev_upload(h, &sc.lights, n, src, hipMemcpyDeviceToDevice, &h->scene_allocs, light_pad);
+    if (!rc) rc = dev_upload(h, &sc.geom_dyn, table.size(), table.data(), hipMemcpyHostToDevice, &h->scene_allocs);
+    h->light_allocs.insert(h->light_allocs.end(), h->scene_allocs.begin() + (long)before, h->scene_allocs.end());
+    h->light_bytes += h->bytes_scene - bytes_before;
+    if (rc) return rc;
+    HIP_TRY(h, hipMemset(sc.lights + n, 0, light_pad * sizeof(RptrTriLightData)));
+    sc.dscene.lights = sc.lights;
+    return RPTR_OK;
+}
 // One scene copy (host_state.h SceneCopy), given where its contents come from: the master set (from == NULL) is filled from the host's
 // arrays, a frame context's copy from the master's device buffers. Either way the copy owns the node array with its boxes (ONE array,
 // top level first: 88 bytes per node), the instance bounds, records and staged transforms (a frame still rendering never sees an instance
@@ -431,6 +452,7 @@ static int scene_copy_build(rptr_hip *h, const RptrSceneDesc *s, const SceneTabl
     sc.dscene.insts = insts;
     sc.dscene.geoms = d_geoms;
     sc.version = h->refit_version;
+    if ((rc = scene_copy_lights(h, sc, from ? from->dscene.lights : h->d_lights_shared))) return rc;
     return scene_copy_refit_tables(h, T, sc);
 }
 // what build_host_bvh made becomes the handle's
@@ -464,6 +486,10 @@ int rptr_hip_set_scene(rptr_hip_t *h, const RptrSceneDesc *s) {
         (void)hipFree(p);
     }
     h->scene_allocs.clear();
+    h->light_bytes = 0;
+    h->light_allocs.clear(); // (a new scene drops the light-source registration: its buffers went with the rest)
+    h->d_light_sources = nullptr;
+    h->d_lights_shared = nullptr;
     h->bytes_scene = 0;
     h->bytes_allocated = h->bytes_frame;
     h->have_scene = false;
@@ -487,7 +513,8 @@ int rptr_hip_set_scene(rptr_hip_t *h, const RptrSceneDesc *s) {
     if ((rc = dev_upload(h, &d_lights, s->num_lights, s->lights, hipMemcpyHostToDevice, &h->scene_allocs, light_pad))) return rc;
     HIP_TRY(h, hipMemset(d_lights + s->num_lights, 0, light_pad * sizeof(RptrTriLightData)));
     ds.materials = d_mats;
-    ds.lights = d_lights;
+    ds.lights = h->d_lights_shared = d_lights;
+    h->h_lights.assign(s->lights, s->lights + s->num_lights); // (what rptr_hip_set_light_sources checks a registration against)
     ds.num_lights = h->num_lights = (int)s->num_lights;
     ds.num_materials = h->num_materials = (int)s->num_materials;
     ds.num_textures = (int)s->num_textures;
@@ -517,6 +544,13 @@ int rptr_hip_set_scene(rptr_hip_t *h, const RptrSceneDesc *s) {
         }
         h->inst_emissive.assign(s->num_instances, 0);
         for (uint32_t i = 0; i < s->num_instances; ++i) h->inst_emissive[i] = pmesh_emissive[s->instances[i].parameterized_mesh];
+        h->inst_mesh.assign(s->num_instances, 0);
+        h->scene_xf.assign((size_t)12 * s->num_instances, 0.0f);
+        for (uint32_t i = 0; i < s->num_instances; ++i) {
+            h->inst_mesh[i] = (int)s->parameterized_meshes[s->instances[i].parameterized_mesh].mesh;
+            memcpy(&h->scene_xf[(size_t)12 * i], s->instances[i].transform, 48);
+        }
+        h->mesh_has_lights.assign(s->num_meshes, 0);
     }
     if ((rc = dev_alloc(h, &h->d_inst_rejected, 1, &h->scene_allocs))) return rc;
     HIP_TRY(h, hipMemset(h->d_inst_rejected, 0, sizeof(uint32_t)));
@@ -592,8 +626,9 @@ static int update_instances_common(rptr_hip_t *h, uint32_t first, uint32_t count
         if (!h->inst_movable[i])
             return fail(h, RPTR_E_INVALID, "instance %u is baked into the flattened world-space tree and cannot move: set RPTR_MESH_INSTANCES_MOVE in "
                                            "RptrMeshDesc.dynamic of its mesh (or option flatten = 0) before set_scene", i);
-        if (h->inst_emissive[i])
-            return fail(h, RPTR_E_UNSUPPORTED, "instance %u uses an emissive material: RptrSceneDesc.lights holds its triangles in world space and would go stale", i);
+        if (h->inst_emissive[i] && !h->d_light_sources)
+            return fail(h, RPTR_E_UNSUPPORTED, "instance %u uses an emissive material: RptrSceneDesc.lights holds its triangles in world space and would go stale "
+                                               "(register rptr_hip_set_light_sources first)", i);
     }
     HIP_TRY(h, hipSetDevice(h->device));
     if (device_src)
@@ -865,6 +900,15 @@ static bool refit_scene_copy(rptr_hip *h, SceneCopy &sc, bool all_dynamic, hipSt
                            (uint32_t)h->h_insts.size(), sc.inst_xf, h->num_instances);
         sc.inst_version = h->inst_version;
     }
+    // registered light sources (rptr_hip_set_light_sources): this copy's lights go where their triangles are now -- behind the records'
+    // update and the vertex copies (queued on this stream, or waited for by it), in front of every frame this copy renders next
+    if (sc.lights && h->num_lights > 0) {
+        bool place = insts_moved;
+        for (size_t m : todo) place = place || h->mesh_has_lights[m];
+        if (place)
+            hipLaunchKernelGGL(rp_k_place_lights, dim3(grid_for(h, (size_t)h->num_lights)), dim3(256), 0, st, sc.lights, h->d_light_sources, (uint32_t)h->num_lights,
+                               sc.inst_xf, sc.geom_dyn);
+    }
     // moved instances under RPTR_TLAS_REBUILD get a new top level (where set_scene reserved room for one); a top level that was rebuilt
     // before is refitted by its own level lists, not the host's
     const bool rebuild_top = insts_moved && h->tlas_policy == RPTR_TLAS_REBUILD && h->tlas_capacity > 0 && h->num_tlas_insts > 0;
@@ -989,3 +1033,99 @@ static int ensure_master_tree(rptr_hip *h) {
     return err;
 }
 
+// ---- moving lights: the provenance of RptrSceneDesc.lights (include/rptr_hip.h)
+// what the registration allocated goes: every copy reads the buffer set_scene uploaded again
+static void drop_light_sources(rptr_hip *h) {
+    h->bytes_scene -= std::min(h->light_bytes, h->bytes_scene);
+    h->light_bytes = 0;
+    for (void *p : h->light_allocs) {
+        (void)hipFree(p);
+        h->scene_allocs.erase(std::remove(h->scene_allocs.begin(), h->scene_allocs.end(), p), h->scene_allocs.end());
+    }
+    h->bytes_allocated = h->bytes_scene + h->bytes_frame;
+    h->light_allocs.clear();
+    h->d_light_sources = nullptr;
+    h->master.lights = nullptr, h->master.geom_dyn = nullptr, h->master.dscene.lights = h->d_lights_shared;
+    for (SceneCopy &sc : h->ctx_scene) sc.lights = nullptr, sc.geom_dyn = nullptr, sc.dscene.lights = h->d_lights_shared;
+    std::fill(h->mesh_has_lights.begin(), h->mesh_has_lights.end(), 0);
+}
+// Allowed difference between a light as uploaded and the placement rule applied to its source, per coordinate, relative to
+// S = |m0 x| + |m1 y| + |m2 z| + |m3|. One evaluation of (m0 x + m1 y) + (m2 z + m3) in float32 rounds three products (each within
+// 2^-24 of itself, together within 2^-24 S), two inner sums (together within 2^-24 S, to first order) and the outer sum (within 2^-24 S):
+// within 3 x 2^-24 S of the exact value, and a fused multiply-add only drops roundings. The host's evaluation and the one here: 6 x 2^-24 S
+// = 0.375 x 2^-20 S. The bound leaves a margin of 2.7 over that; a light of another triangle or instance misses it by orders of magnitude.
+static const double kLightSourceTolerance = 1.0 / 1048576.0; // 2^-20
+int rptr_hip_set_light_sources(rptr_hip_t *h, const RptrLightSource *sources, uint32_t count) {
+    if (!h) return fail(nullptr, RPTR_E_INVALID, "NULL handle");
+    if (!h->have_scene) return fail(h, RPTR_E_INVALID, "set_light_sources before set_scene");
+    if ((sources == nullptr) != (count == 0)) return fail(h, RPTR_E_INVALID, "sources and count must both be given, or NULL and 0 to unregister");
+    if (count && count != (uint32_t)h->num_lights) return fail(h, RPTR_E_INVALID, "%u light sources for a scene of %d lights", count, h->num_lights);
+    std::vector<char> mesh_has_lights(h->mesh_has_lights.size(), 0);
+    for (uint32_t i = 0; i < count; ++i) {
+        const RptrLightSource &s = sources[i];
+        if (s.instance >= h->num_instances) return fail(h, RPTR_E_INVALID, "light source %u: instance %u of %u", i, s.instance, h->num_instances);
+        if (s.geometry >= h->geom_tris.size()) return fail(h, RPTR_E_INVALID, "light source %u: geometry %u of %zu", i, s.geometry, h->geom_tris.size());
+        if (s.triangle >= h->geom_tris[s.geometry])
+            return fail(h, RPTR_E_INVALID, "light source %u: triangle %u of geometry %u, which has %u", i, s.triangle, s.geometry, h->geom_tris[s.geometry]);
+        if (h->geom_mesh[s.geometry] != h->inst_mesh[s.instance])
+            return fail(h, RPTR_E_INVALID, "light source %u: geometry %u belongs to mesh %d, instance %u is one of mesh %d", i, s.geometry, h->geom_mesh[s.geometry],
+                        s.instance, h->inst_mesh[s.instance]);
+        const float *M = &h->scene_xf[(size_t)12 * s.instance];
+        const float *src[3] = {s.v0, s.v1, s.v2}, *dst[3] = {h->h_lights[i].v0, h->h_lights[i].v1, h->h_lights[i].v2};
+        for (int k = 0; k < 3; ++k)
+            for (int r = 0; r < 3; ++r) {
+                const float *m = M + 4 * r, *p = src[k];
+                const float a = m[0] * p[0], b = m[1] * p[1], c = m[2] * p[2];
+                const float ab = a + b, cd = c + m[3];
+                const float placed = ab + cd;
+                const double sum = std::fabs((double)m[0] * p[0]) + std::fabs((double)m[1] * p[1]) + std::fabs((double)m[2] * p[2]) + std::fabs((double)m[3]);
+                if (!(std::fabs((double)placed - (double)dst[k][r]) <= kLightSourceTolerance * sum))
+                    return fail(h, RPTR_E_INVALID, "light source %u: vertex %d coordinate %d of instance %u, geometry %u, triangle %u lands at %.9g, light %u has %.9g: "
+                                                   "not where this light came from", i, k, r, s.instance, s.geometry, s.triangle, (double)placed, i, (double)dst[k][r]);
+            }
+        mesh_has_lights[(size_t)h->geom_mesh[s.geometry]] = 1;
+    }
+    // ---- checked: from here on the scene copies change, so nothing of the handle may still be rendering from them
+    HIP_TRY(h, hipSetDevice(h->device));
+    {
+        int rc0 = drain(h);
+        if (rc0) return rc0;
+    }
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    drop_light_sources(h);
+    if (!count) return RPTR_OK;
+    int rc;
+    {
+        const size_t before = h->scene_allocs.size(), bytes_before = h->bytes_scene;
+        rc = dev_upload(h, &h->d_light_sources, count, sources, hipMemcpyHostToDevice, &h->scene_allocs);
+        h->light_allocs.insert(h->light_allocs.end(), h->scene_allocs.begin() + (long)before, h->scene_allocs.end());
+        h->light_bytes += h->bytes_scene - bytes_before;
+    }
+    // every copy starts from the lights as set_scene got them; its next refit that finds moved instances or new vertices re-places them.
+    // (No copies are made for a scene that has none: rptr_hip_refit waits for the frames in flight when every context reads the master's.)
+    if (!rc) rc = scene_copy_lights(h, h->master, h->d_lights_shared);
+    for (SceneCopy &sc : h->ctx_scene)
+        if (!rc) rc = scene_copy_lights(h, sc, h->d_lights_shared);
+    if (rc) {
+        const std::string why = h->last_error;
+        drop_light_sources(h);
+        h->last_error = why;
+        return rc;
+    }
+    h->mesh_has_lights = mesh_has_lights;
+    return RPTR_OK;
+}
+int rptr_hip_readback_lights(rptr_hip_t *h, RptrTriLightData *out, uint32_t count) {
+    if (!h) return fail(nullptr, RPTR_E_INVALID, "NULL handle");
+    if (!h->have_scene) return fail(h, RPTR_E_INVALID, "readback_lights before set_scene");
+    if (count != (uint32_t)h->num_lights) return fail(h, RPTR_E_INVALID, "room for %u lights, the scene has %d", count, h->num_lights);
+    if (count && !out) return fail(h, RPTR_E_INVALID, "NULL argument");
+    HIP_TRY(h, hipSetDevice(h->device));
+    {
+        int rc0 = ensure_master_tree(h);
+        if (rc0) return rc0;
+    }
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (count) HIP_TRY(h, hipMemcpy(out, h->master.dscene.lights, (size_t)count * sizeof(RptrTriLightData), hipMemcpyDeviceToHost));
+    return RPTR_OK;
+}

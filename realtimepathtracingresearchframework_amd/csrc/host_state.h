@@ -57,6 +57,11 @@ struct SceneCopy {
     uint2 *tlas_levels = nullptr;           // RP_REFIT_LEVELS [begin, end) pairs into it
     int *tlas_count = nullptr;              // nodes of the rebuilt top level
     bool tlas_rebuilt = false;              // the top level is a device-built one: refits go by tlas_list / tlas_levels
+    // moving lights (rptr_hip_set_light_sources): while sources are registered the copy owns the light buffer a refit re-places
+    // (dscene.lights points at it) and a device table of its float positions per global geometry (NULL: static); otherwise both are
+    // NULL and dscene.lights is the buffer set_scene uploaded, shared by every copy
+    RptrTriLightData *lights = nullptr;
+    const float **geom_dyn = nullptr;
 };
 
 struct Span {
@@ -320,6 +325,15 @@ struct rptr_hip {
     uint64_t tlas_rebuilds = 0;             // device-side rebuilds of the top level so far (all scene copies)
     bool host_insts_stale = false;          // the device's instance records are newer than h_insts
     uint32_t *d_inst_rejected = nullptr;    // matrices of device-source updates that were not finite or singular and were skipped (this scene)
+    // moving lights (rptr_hip_set_light_sources, tlas_build.h rp_k_place_lights)
+    RptrTriLightData *d_lights_shared = nullptr; // the light buffer set_scene uploaded (what every copy reads without registration)
+    RptrLightSource *d_light_sources = nullptr;  // the registered sources, one per light (NULL: none registered)
+    std::vector<void *> light_allocs;            // what the registration allocated (also in scene_allocs): freed when it is dropped
+    size_t light_bytes = 0;                      // ... and its share of bytes_scene
+    std::vector<RptrTriLightData> h_lights;      // RptrSceneDesc.lights and ...
+    std::vector<float> scene_xf;                 // ... the 12 floats per instance set_scene received: what a registration is checked against
+    std::vector<int> inst_mesh;                  // per scene instance: its mesh
+    std::vector<char> mesh_has_lights;           // per mesh: a registered source names one of its geometries
 
     // device buffers (frame sized)
     std::vector<FrameCtx> ctx;      // frames in flight (RptrCreateInfo.frames_in_flight, at least 1)

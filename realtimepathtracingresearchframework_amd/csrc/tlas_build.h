@@ -104,3 +104,34 @@ __global__ __launch_bounds__(256) void rp_k_update_instance_records(RptrBvhInsta
         }
     }
 }
+
+// 4. moving lights (rptr_hip_set_light_sources): the world-space vertices of every light from where its triangle is NOW -- the staged
+// object_to_world of its instance applied to the object-space vertices, which are the registered ones for a static mesh and the copy's
+// float positions (geom_dyn[geometry], 9 floats per triangle in unrolled order, NULL for a static geometry) for a deforming one. A
+// device-side rebuild of the mesh's tree reorders the copy's TRIANGLES, never these positions, so `triangle` stays valid. One thread
+// per light; only the 36 bytes of vertices of lights[i], i < n, are written: radiance stays, and so does the zeroed bin behind the
+// array. The association is the one of collect_emitters (librender/lights.cpp:52-56, glm's mat4 * vec4), (m0 x + m1 y) + (m2 z + m3),
+// every product and sum rounded to float (the translation unit is built without contraction; the temporaries below keep the
+// association explicit whatever the flags), so a light placed with the transform set_scene received equals the host's bit for bit.
+// Always from the object-space source, never from the previous placement: nothing drifts however many updates there were.
+RP_DEV float rp_place_coord(const float *row, float x, float y, float z) {
+    const float a = row[0] * x, b = row[1] * y, c = row[2] * z;
+    const float ab = a + b, cd = c + row[3];
+    return ab + cd;
+}
+__global__ __launch_bounds__(256) void rp_k_place_lights(RptrTriLightData *lights, const RptrLightSource *sources, uint32_t n, const float *table24,
+                                                         const float *const *geom_dyn) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const RptrLightSource s = sources[i];
+        float p[9];
+        const float *dyn = geom_dyn[s.geometry];
+        if (dyn)
+            for (int k = 0; k < 9; ++k) p[k] = dyn[9ull * s.triangle + k];
+        else
+            for (int k = 0; k < 3; ++k) p[k] = s.v0[k], p[3 + k] = s.v1[k], p[6 + k] = s.v2[k];
+        const float *m = table24 + 24ull * s.instance;
+        float *out = lights[i].v0; // v0, v1, v2 lie back to back: 9 floats
+        for (int v = 0; v < 3; ++v)
+            for (int r = 0; r < 3; ++r) out[3 * v + r] = rp_place_coord(m + 4 * r, p[3 * v], p[3 * v + 1], p[3 * v + 2]);
+    }
+}

@@ -108,6 +108,73 @@ inline std::vector<RptrTriLightData> collect_emitters(const SceneDump &s) {
     return emitters;
 }
 
+// the provenance of collect_emitters' output, entry for entry in the same order (include/rptr_hip.h RptrLightSource): the object-space
+// vertices as dequantized, the scene instance, the global geometry, the triangle within it
+inline std::vector<RptrLightSource> collect_light_sources(const SceneDump &s) {
+    std::vector<RptrLightSource> sources;
+    std::set<uint32_t> nonemissive;
+    for (size_t inst_id = 0; inst_id < s.instances.size(); ++inst_id) {
+        const uint32_t pm_id = s.instances[inst_id].parameterized_mesh;
+        if (nonemissive.count(pm_id)) continue;
+        const RptrParameterizedMeshDesc &pm = s.pmeshes[pm_id];
+        const RptrMeshDesc &mesh = s.meshes[pm.mesh];
+        std::vector<RptrLightSource> next;
+        size_t tri_base = 0;
+        for (uint32_t j = 0; j < mesh.num_geometries; ++j) {
+            const uint32_t gi = mesh.first_geometry + j;
+            const RptrGeometryDesc &g = s.geometries[gi];
+            const int32_t offs = pm.material_offsets[j];
+            const bool per_tri = pm.tri_material_ids != nullptr;
+            if (!per_tri && !(s.materials[(size_t)offs].emission_intensity > 0.0f)) {
+                tri_base += g.num_tris;
+                continue;
+            }
+            for (uint32_t t = 0; t < g.num_tris; ++t) {
+                const RptrBaseMaterial &mat = s.materials[(size_t)(offs + (per_tri ? (int32_t)pm.tri_material_ids[tri_base + t] : 0))];
+                if (!(mat.emission_intensity > 0.0f)) continue;
+                RptrLightSource e;
+                float *dst[3] = {e.v0, e.v1, e.v2};
+                for (int k = 0; k < 3; ++k) {
+                    const V3 p = dequantize_position(g.qpos[3 * (size_t)t + k], g.quantized_scaling, g.quantized_offset);
+                    dst[k][0] = p.x, dst[k][1] = p.y, dst[k][2] = p.z;
+                }
+                e.instance = (uint32_t)inst_id, e.geometry = gi, e.triangle = t;
+                next.push_back(e);
+            }
+            tri_base += g.num_tris;
+        }
+        if (!next.empty())
+            sources.insert(sources.begin(), next.begin(), next.end());
+        else
+            nonemissive.insert(pm_id);
+    }
+    return sources;
+}
+
+// the placement rule of rptr_hip_set_light_sources on the host: the world-space vertices (radiance = 0) of the lights whose sources are
+// given. transforms12: row-major 3x4 object_to_world per scene instance. positions[g] (may be absent or NULL): the float positions of
+// geometry g of a deforming mesh, 9 per triangle -- its lights take their object-space vertices from there. Per row
+// (m0 x + m1 y) + (m2 z + m3), the arithmetic of collect_emitters (build without contraction).
+inline std::vector<RptrTriLightData> place_light_sources(const std::vector<RptrLightSource> &sources, const float *transforms12,
+                                                         const std::vector<const float *> &positions = {}) {
+    std::vector<RptrTriLightData> out(sources.size());
+    for (size_t i = 0; i < sources.size(); ++i) {
+        const RptrLightSource &s = sources[i];
+        const float *M = transforms12 + 12 * (size_t)s.instance;
+        const float *dyn = s.geometry < positions.size() ? positions[s.geometry] : nullptr;
+        const float *src[3] = {dyn ? dyn + 9 * (size_t)s.triangle : s.v0, dyn ? dyn + 9 * (size_t)s.triangle + 3 : s.v1, dyn ? dyn + 9 * (size_t)s.triangle + 6 : s.v2};
+        RptrTriLightData &e = out[i];
+        float *dst[3] = {e.v0, e.v1, e.v2};
+        for (int k = 0; k < 3; ++k)
+            for (int r = 0; r < 3; ++r) {
+                const float ab = M[4 * r + 0] * src[k][0] + M[4 * r + 1] * src[k][1], cd = M[4 * r + 2] * src[k][2] + M[4 * r + 3];
+                dst[k][r] = ab + cd;
+            }
+        e.radiance[0] = e.radiance[1] = e.radiance[2] = 0.0f;
+    }
+    return out;
+}
+
 // lights.cpp:166-199: luminance x solid angle seen from `min_perceived_receiver_dist` above the centre. (The reference divides by
 // M_2_PI = 2 / pi; reproduced.)
 inline std::vector<float> estimate_normalized_radiance(const std::vector<RptrTriLightData> &emitters, float min_perceived_receiver_dist) {
@@ -130,8 +197,13 @@ inline std::vector<float> estimate_normalized_radiance(const std::vector<RptrTri
 
 // lights.cpp:220-349: bright emitters are split into clones, the list is shuffled by a Halton sequence and padded with clones drawn
 // by importance until every bin of `bin_size` lights carries about the same power
-inline void equalize_emitter_bins(std::vector<RptrTriLightData> &emitters, std::vector<float> &radiances, int bin_size) {
+// (sources, when given: per output entry the index of the input emitter it is, or is a clone of)
+inline void equalize_emitter_bins(std::vector<RptrTriLightData> &emitters, std::vector<float> &radiances, int bin_size, std::vector<size_t> *sources = nullptr) {
     const size_t n = radiances.size();
+    if (sources) {
+        sources->resize(n);
+        for (size_t i = 0; i < n; ++i) (*sources)[i] = i;
+    }
     if (bin_size <= 1 || n == 0) return;
     struct Bin {
         float radiance;
@@ -218,31 +290,51 @@ inline void equalize_emitter_bins(std::vector<RptrTriLightData> &emitters, std::
         for (int c = 0; c < 3; ++c) new_em[i].radiance[c] /= float(bins[i].split);
         new_rad[i] = bins[i].radiance;
     }
+    if (sources) {
+        sources->resize(bins.size());
+        for (size_t i = 0; i < bins.size(); ++i) (*sources)[i] = (size_t)bins[i].source;
+    }
     emitters.swap(new_em);
     radiances.swap(new_rad);
 }
 
-// lights.cpp:75-90 from an invalidated BinnedLightSampling
-inline std::vector<RptrTriLightData> update_light_sampling(std::vector<RptrTriLightData> emitters, const RptrLightSamplingConfig &cfg) {
+// lights.cpp:75-90 from an invalidated BinnedLightSampling. sources, when given: per light the index of the emitter (of those passed in)
+// it is -- trimming drops entries, clones repeat theirs
+inline std::vector<RptrTriLightData> update_light_sampling(std::vector<RptrTriLightData> emitters, const RptrLightSamplingConfig &cfg,
+                                                           std::vector<size_t> *sources = nullptr) {
+    if (sources) sources->clear();
     if (emitters.empty()) return emitters;
     std::vector<float> radiances = estimate_normalized_radiance(emitters, cfg.min_perceived_receiver_dist);
+    std::vector<size_t> kept(emitters.size());
+    for (size_t i = 0; i < kept.size(); ++i) kept[i] = i;
     if (cfg.min_radiance > 0.0f) { // trim_dim_emitters, :201-217
         std::vector<RptrTriLightData> e2;
         std::vector<float> r2;
+        kept.clear();
         for (size_t i = 0; i < emitters.size(); ++i)
             if (radiances[i] >= cfg.min_radiance) {
                 e2.push_back(emitters[i]);
                 r2.push_back(radiances[i]);
+                kept.push_back(i);
             }
         emitters.swap(e2);
         radiances.swap(r2);
     }
-    equalize_emitter_bins(emitters, radiances, cfg.bin_size);
+    equalize_emitter_bins(emitters, radiances, cfg.bin_size, sources);
+    if (sources)
+        for (size_t &k : *sources) k = kept[k];
     return emitters;
 }
 
-// RenderBinnedLightsVulkan::update_scene_from_backend (render_binned_lights.cpp:68-87): fills s.lights
-inline void prepare_lights(SceneDump &s) { s.lights = update_light_sampling(collect_emitters(s), s.lighting); }
+// RenderBinnedLightsVulkan::update_scene_from_backend (render_binned_lights.cpp:68-87): fills s.lights, and s.light_sources with where
+// every light came from (RenderHip::set_light_sources)
+inline void prepare_lights(SceneDump &s) {
+    std::vector<size_t> src;
+    s.lights = update_light_sampling(collect_emitters(s), s.lighting, &src);
+    const std::vector<RptrLightSource> all = collect_light_sources(s);
+    s.light_sources.resize(src.size());
+    for (size_t i = 0; i < src.size(); ++i) s.light_sources[i] = all[src[i]];
+}
 
 } // namespace lights
 } // namespace rptr

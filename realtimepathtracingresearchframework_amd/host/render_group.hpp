@@ -66,6 +66,10 @@ public:
         for (auto &r : ranks_) n += r->tlas_rebuild_count();
         return n;
     }
+    void set_light_sources(const std::vector<RptrLightSource> &sources) { // every GPU holds the whole scene: every rank is registered
+        for (auto &r : ranks_) r->set_light_sources(sources);
+    }
+    std::vector<RptrTriLightData> readback_lights(uint32_t num_lights) { return ranks_[0]->readback_lights(num_lights); } // (the ranks' buffers are equal)
     void set_rng_variant(int rng_variant, const std::vector<uint32_t> &table = {}) {
         for (auto &r : ranks_) r->set_rng_variant(rng_variant, table);
     }

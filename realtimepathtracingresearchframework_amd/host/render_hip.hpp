@@ -119,6 +119,19 @@ public:
         rptr_hip_tlas_rebuild_count(h_, &n);
         return n;
     }
+    // moving lights: where every entry of RptrSceneDesc.lights came from (lights.hpp collect_light_sources / prepare_lights), one record
+    // per light; afterwards emissive instances may move and refit() re-places the lights. An empty vector unregisters; set_scene never
+    // registers on its own and a new set_scene drops the registration.
+    void set_light_sources(const std::vector<RptrLightSource> &sources) {
+        flush_pipeline();
+        check(rptr_hip_set_light_sources(h_, sources.empty() ? nullptr : sources.data(), (uint32_t)sources.size()));
+    }
+    // the master scene copy's light buffer after all pending work (num_lights: RptrSceneDesc.num_lights of the scene)
+    std::vector<RptrTriLightData> readback_lights(uint32_t num_lights) {
+        std::vector<RptrTriLightData> out(num_lights);
+        check(rptr_hip_readback_lights(h_, out.data(), num_lights));
+        return out;
+    }
     // RenderBackendOptions (render_params.glsl.h:56-93): the point set with the table its render extension uploads, and the BVH policy
     void set_rng_variant(int rng_variant, const std::vector<uint32_t> &table = {}) {
         check(rptr_hip_set_rng_variant(h_, rng_variant, table.empty() ? nullptr : table.data(), table.size() * sizeof(uint32_t)));

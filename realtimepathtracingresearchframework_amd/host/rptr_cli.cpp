@@ -417,6 +417,19 @@ int main(int argc, char **argv) {
         rptr::RenderGroup backend(devices, stripe_rows, contexts, RPTR_CREATE_SET_HW_QUEUES); // (this program owns its process: a hardware queue per frame context)
         backend.initialize(width, height);
         backend.set_scene(scene.desc());
+        {
+            // a scene that animates (instances that move, meshes that deform) registers where its lights came from, so that a refit
+            // re-places the lights of emitters that moved (a scene read from a dump carries no provenance: nothing to register)
+            bool animates = false;
+            for (const RptrMeshDesc &m : scene.meshes) animates = animates || m.dynamic != 0;
+            if (animates && !scene.lights.empty() && scene.light_sources.size() == scene.lights.size()) {
+                try {
+                    backend.set_light_sources(scene.light_sources);
+                } catch (const std::exception &e) { // (the scene renders as it did before: lights stay where set_scene got them)
+                    std::fprintf(stderr, "rptr_hip: light sources not registered: %s\n", e.what());
+                }
+            }
+        }
         base.params.batch_spp = batch_spp;
         backend.set_params(base.params, base.lighting);
         backend.update_config(scene.scene_params);

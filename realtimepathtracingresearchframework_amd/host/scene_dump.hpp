@@ -31,6 +31,7 @@ struct SceneDump {
     std::vector<RptrInstanceDesc> instances;
     std::vector<RptrBaseMaterial> materials;
     std::vector<RptrTriLightData> lights;
+    std::vector<RptrLightSource> light_sources; // per light: where it came from (lights.hpp prepare_lights; not part of the file)
     RptrCamera camera{};
     RptrSceneParams scene_params{};
     RptrRenderParams render_params{};

@@ -119,6 +119,73 @@ def collect_emitters(scene):
     return np.stack(emitters).astype(f32)
 
 
+# where one light came from (include/rptr_hip.h RptrLightSource, 48 bytes): object-space vertices as dequantized, scene instance,
+# global geometry, triangle within the geometry
+LIGHT_SOURCE_DTYPE = np.dtype([("v0", "<f4", (3,)), ("v1", "<f4", (3,)), ("v2", "<f4", (3,)), ("instance", "<u4"), ("geometry", "<u4"),
+                               ("triangle", "<u4")])
+assert LIGHT_SOURCE_DTYPE.itemsize == 48
+
+
+def collect_light_sources(scene):
+    """The provenance of collect_emitters' output, entry for entry in the same order: LIGHT_SOURCE_DTYPE records."""
+    from . import scenes as S
+    sources = []
+    nonemissive = set()
+    for inst_id, inst in enumerate(scene.instances):
+        pm_id = inst.pmesh
+        if pm_id in nonemissive:
+            continue
+        pm = scene.pmeshes[pm_id]
+        mesh = scene.meshes[pm.mesh]
+        nxt = []
+        tri_base = 0
+        for j in range(mesh.num_geometries):
+            gi = mesh.first_geometry + j
+            g = scene.geometries[gi]
+            offs = int(pm.material_offsets[j])
+            per_tri = pm.tri_material_ids is not None
+            if per_tri:
+                ids = np.asarray(pm.tri_material_ids[tri_base:tri_base + g.num_tris]).astype(np.int64)
+                tris = [t for t in range(g.num_tris) if scene.materials[offs + int(ids[t])].emission_intensity > 0.0]
+            else:
+                tris = range(g.num_tris) if scene.materials[offs].emission_intensity > 0.0 else []
+            if len(tris):
+                pos = S.dequantize_positions(g.qpos, g.scaling, g.offset).reshape(-1, 3, 3)
+                rec = np.zeros(len(tris), dtype=LIGHT_SOURCE_DTYPE)
+                t = np.asarray(tris, dtype=np.int64)
+                rec["v0"], rec["v1"], rec["v2"] = pos[t, 0], pos[t, 1], pos[t, 2]
+                rec["instance"], rec["geometry"], rec["triangle"] = inst_id, gi, t
+                nxt.append(rec)
+            tri_base += g.num_tris
+        if nxt:
+            sources = nxt + sources  # an instance's emitters go in front of those collected so far
+        else:
+            nonemissive.add(pm_id)
+    if not sources:
+        return np.zeros(0, dtype=LIGHT_SOURCE_DTYPE)
+    return np.concatenate(sources)
+
+
+def place_light_sources(sources, transforms, positions=None):
+    """The placement rule of rptr_hip_set_light_sources in float32 numpy: (n, 3, 3) world-space vertices of the lights whose sources
+    are given. transforms: (num_instances, 3, 4) or (num_instances, 12) row-major object-to-world. positions: {global geometry:
+    float positions, unrolled, 9 per triangle} for the geometries of deforming meshes -- their lights take their object-space vertices
+    from there, all others from the sources. Per row (m0 x + m1 y) + (m2 z + m3), every product and sum rounded to float32: the
+    arithmetic of collect_emitters."""
+    sources = np.asarray(sources, dtype=LIGHT_SOURCE_DTYPE).reshape(-1)
+    M = np.ascontiguousarray(transforms, dtype=f32).reshape(-1, 3, 4)[sources["instance"].astype(np.int64)]  # (n, 3, 4)
+    P = np.stack([sources["v0"], sources["v1"], sources["v2"]], axis=1).astype(f32)                           # (n, vertex, xyz)
+    for gi, pos in (positions or {}).items():
+        sel = np.nonzero(sources["geometry"] == gi)[0]
+        if len(sel):
+            P[sel] = np.ascontiguousarray(pos, dtype=f32).reshape(-1, 3, 3)[sources["triangle"][sel].astype(np.int64)]
+    x, y, z = P[:, :, None, 0], P[:, :, None, 1], P[:, :, None, 2]                                            # (n, vertex, 1)
+    m0, m1, m2, m3 = M[:, None, :, 0], M[:, None, :, 1], M[:, None, :, 2], M[:, None, :, 3]                   # (n, 1, row)
+    ab = ((m0 * x).astype(f32) + (m1 * y).astype(f32)).astype(f32)
+    cd = ((m2 * z).astype(f32) + m3).astype(f32)
+    return (ab + cd).astype(f32)
+
+
 def estimate_normalized_radiance(emitters, min_perceived_receiver_dist):
     """lights.cpp:166-199. Note: the reference divides by M_2_PI (= 2/pi), reproduced."""
     out = np.zeros(len(emitters), dtype=f32)
@@ -146,11 +213,12 @@ def trim_dim_emitters(emitters, radiances, min_radiance):
     return emitters[keep], radiances[keep]
 
 
-def equalize_emitter_bins(emitters, radiances, bin_size):
-    """lights.cpp:220-349. Returns (emitters', radiances')."""
+def equalize_emitter_bins(emitters, radiances, bin_size, return_sources=False):
+    """lights.cpp:220-349. Returns (emitters', radiances'); return_sources: and for every output entry the index of the input emitter
+    it is (a clone of)."""
     n = len(radiances)
     if bin_size <= 1 or n == 0:
-        return emitters, radiances
+        return (emitters, radiances, np.arange(n, dtype=np.int64)) if return_sources else (emitters, radiances)
     original_bin_count = (n + (bin_size - 1)) // bin_size
     average_weight = f32(0.0)
     for r in radiances:
@@ -244,14 +312,22 @@ def equalize_emitter_bins(emitters, radiances, bin_size):
     new_em = np.stack([emitters[b[1]].copy() for b in bins]).astype(f32)
     for i, b in enumerate(bins):
         new_em[i, 3] = (new_em[i, 3] / f32(b[2])).astype(f32)
+    if return_sources:
+        return new_em, new_rad, np.array([b[1] for b in bins], dtype=np.int64)
     return new_em, new_rad
 
 
-def update_light_sampling(emitters, min_perceived_receiver_dist=15.0, min_radiance=0.0, bin_size=16):
-    """lights.cpp:75-90 starting from an invalidated BinnedLightSampling."""
+def update_light_sampling(emitters, min_perceived_receiver_dist=15.0, min_radiance=0.0, bin_size=16, return_sources=False):
+    """lights.cpp:75-90 starting from an invalidated BinnedLightSampling. return_sources: a third result, for every light the index
+    of the emitter (of the `emitters` passed in) it is: trimming drops entries, clones repeat theirs."""
     if len(emitters) == 0:
-        return emitters, np.zeros(0, dtype=f32)
+        return (emitters, np.zeros(0, dtype=f32), np.zeros(0, dtype=np.int64)) if return_sources else (emitters, np.zeros(0, dtype=f32))
     radiances = estimate_normalized_radiance(emitters, min_perceived_receiver_dist)
+    kept = np.arange(len(emitters), dtype=np.int64)
     if min_radiance > 0.0:
+        kept = kept[radiances >= f32(min_radiance)]
         emitters, radiances = trim_dim_emitters(emitters, radiances, min_radiance)
-    return equalize_emitter_bins(emitters, radiances, bin_size)
+    if not return_sources:
+        return equalize_emitter_bins(emitters, radiances, bin_size)
+    em, rad, src = equalize_emitter_bins(emitters, radiances, bin_size, return_sources=True)
+    return em, rad, kept[src]

@@ -165,6 +165,7 @@ class Scene:
     config: SceneConfig = field(default_factory=SceneConfig)
     sky_key: str = ""
     _keep: list = field(default_factory=list, repr=False)
+    light_sources: np.ndarray = field(default_factory=lambda: np.zeros(0, dtype=L.LIGHT_SOURCE_DTYPE), repr=False)  # per light: its provenance (prepare_lights)
 
     def dump(self, path, render_params: abi.RenderParams = None, lighting: abi.LightSamplingConfig = None):
         """Writes the scene as a flat little-endian file for the C++ host tools (host/scene_dump.hpp documents the
@@ -279,8 +280,10 @@ class Scene:
         """≙ RenderBinnedLightsVulkan::update_scene_from_backend (render_binned_lights.cpp:68-87)."""
         lighting = lighting or abi.LightSamplingConfig.default()
         em = L.collect_emitters(self)
-        em, _ = L.update_light_sampling(em, lighting.min_perceived_receiver_dist, lighting.min_radiance, lighting.bin_size)
+        em, _, src = L.update_light_sampling(em, lighting.min_perceived_receiver_dist, lighting.min_radiance, lighting.bin_size, return_sources=True)
         self.lights = em
+        # where every light came from, for backends that re-place the lights of moving emitters (RenderHip.set_light_sources)
+        self.light_sources = L.collect_light_sources(self)[src]
         return self
 
     def desc(self) -> abi.SceneDesc:

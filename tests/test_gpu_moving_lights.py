@@ -1,0 +1,374 @@
+"""Moving lights: rptr_hip_set_light_sources registers where every entry of RptrSceneDesc.lights came from, and rptr_hip_refit re-places
+the lights of instances that moved and of dynamic meshes that were updated (csrc/tlas_build.h rp_k_place_lights).
+
+The scene is two_level_test(n_inst=12) UNCHANGED: its emissive parameterized mesh 2 gives instances 2, 5, 8 and 11 forty light
+triangles each. The yardstick of a moved scene is the moved Scene with lights[:, :3] = place_light_sources(...) in the original order
+(prepare_lights is NOT run again: bins, clones and order stay the host's); it goes into the oracle and into a fresh set_scene.
+
+Frames are 96 x 64, 2 spp, VARIANT_GLTF; image tolerances are those of test_gpu_instances.py (common.RMSE_TOL, image_error). The light
+buffer is compared bit for bit: the placement is the float32 arithmetic of collect_emitters without contraction, on both sides."""
+import copy
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import oracle_lib as O
+from common import RMSE_TOL, assert_ray_visit_parity, gpu_render, image_error, random_queries
+from realtimepathtracingresearchframework_amd import abi, backend, lights as L, scenes
+
+pytestmark = pytest.mark.gpu
+
+POLICIES = [abi.TLAS_REBUILD, abi.TLAS_REFIT]
+W, H, SPP = 96, 64, 2
+EMISSIVE = (2, 5, 8, 11)
+# the transforms of the frame tests. Chosen on the CPU, with the oracle alone: its render of the moved scene with the STALE lights differs
+# from its render with the placed lights by rmse 0.228 (seeds 20..29 give 0.129 .. 0.311), against the 100 x RMSE_TOL = 0.1 asked for
+MOVE_SEED = 22
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def _transforms(n, seed, spread=4.0):
+    """rotation x NON-uniform scale + translation, float32 (n, 3, 4)"""
+    rng = np.random.default_rng(seed)
+    out = np.zeros((n, 3, 4), np.float32)
+    for i in range(n):
+        ang = rng.uniform(0, 2 * np.pi)
+        axis = rng.normal(size=3)
+        axis /= np.linalg.norm(axis)
+        K = np.array([[0, -axis[2], axis[1]], [axis[2], 0, -axis[0]], [-axis[1], axis[0], 0]])
+        R = np.eye(3) + np.sin(ang) * K + (1 - np.cos(ang)) * K @ K
+        out[i, :, :3] = R @ np.diag(rng.uniform(0.5, 1.7, size=3))
+        out[i, :, 3] = rng.uniform(-spread, spread, size=3)
+    return out
+
+
+def _scene(deforming=False):
+    s = scenes.two_level_test(n_inst=12)
+    for m in s.meshes:
+        m.dynamic = abi.MESH_INSTANCES_MOVE
+    if deforming:
+        s.meshes[1].dynamic = abi.MESH_DYNAMIC | abi.MESH_INSTANCES_MOVE
+    return s
+
+
+def _scene_transforms(s):
+    return np.stack([np.asarray(i.transform, np.float32).reshape(3, 4) for i in s.instances])
+
+
+def _moved(scene, xf, positions=None, stale=False):
+    """the yardstick: the Scene with the new transforms and its lights placed by the rule (stale: left where they were)"""
+    s = copy.copy(scene)
+    s.instances = [copy.copy(i) for i in scene.instances]
+    for k, m in enumerate(xf):
+        s.instances[k].transform = np.asarray(m, np.float32).reshape(3, 4).copy()
+    s.lights = scene.lights.copy()
+    if not stale:
+        s.lights[:, :3] = L.place_light_sources(scene.light_sources, xf, positions)
+    return s
+
+
+def _renderer(scene, register=True, **kw):
+    r = backend.RenderHip(**kw)
+    r.initialize(W, H)
+    r.set_scene(scene)
+    if register:
+        r.set_light_sources(scene)
+    return r
+
+
+def _deformed_positions(scene, seed=3):
+    """geometry 1 (mesh 1, forty loose triangles) scaled about its centroid and perturbed by a fiftieth of its size: no triangle
+    degenerates. Scale and seed were chosen on the CPU so that the ORACLE's frames of both cases below have no non-finite pixel: this
+    scene has paths that end in NaN (one pixel of the undeformed scene already), and which pixel that is depends on the last bit of a
+    sampled direction -- with a scale of 1.3 a fresh set_scene of the yardstick, which uses nothing of this feature, has one such pixel
+    more than the oracle."""
+    g = scene.geometries[1]
+    P = scenes.dequantize_positions(g.qpos, g.scaling, g.offset)
+    c = P.mean(axis=0, dtype=np.float64)
+    rng = np.random.default_rng(seed)
+    out = (c + 0.8 * (P - c) + rng.uniform(-0.02, 0.02, P.shape)).astype(np.float32)
+    e1, e2 = out[1::3] - out[0::3], out[2::3] - out[0::3]
+    assert (np.linalg.norm(np.cross(e1, e2), axis=1) > 1e-3).all()
+    return out
+
+
+@pytest.fixture(scope="module")
+def scene():
+    s = _scene()
+    assert sorted(set(s.light_sources["instance"].tolist())) == list(EMISSIVE) and len(s.lights) >= 160
+    return s
+
+
+@pytest.fixture(scope="module")
+def move(scene):
+    """the transforms of the frame tests, the yardstick scene, its oracle and the oracle's frame (made once, never changed)"""
+    xf = _transforms(len(scene.instances), MOVE_SEED)
+    yard = _moved(scene, xf)
+    osc = O.OracleScene(yard)
+    ref, _ = osc.render(W, H, SPP, variant=abi.VARIANT_GLTF)
+    ref.setflags(write=False)
+    return xf, yard, osc, ref
+
+
+# ---- 1. the buffer
+@pytest.mark.parametrize("policy", POLICIES)
+def test_light_buffer_after_a_move_is_the_placement(scene, policy):
+    r = _renderer(scene)
+    r.set_tlas_policy(policy)
+    assert np.array_equal(_bits(r.readback_lights()), _bits(scene.lights))            # registering changes nothing
+    r.update_instances(0, _scene_transforms(scene))                                      # an identity update
+    r.refit()
+    assert np.array_equal(_bits(r.readback_lights()), _bits(scene.lights))
+    xf = _transforms(len(scene.instances), 21)
+    r.update_instances(0, xf)
+    r.refit()
+    got = r.readback_lights()
+    want = _moved(scene, xf).lights
+    assert np.array_equal(_bits(got), _bits(want))
+    assert not np.array_equal(_bits(got[:, :3]), _bits(scene.lights[:, :3])) and np.array_equal(_bits(got[:, 3]), _bits(scene.lights[:, 3]))
+    r.close()
+
+
+# ---- 2. frames
+def test_stale_lights_would_show(scene, move):
+    """the guard of the frame test: in the oracle alone, leaving the lights where they were changes the frame by at least 100 x RMSE_TOL"""
+    xf, _, _, ref = move
+    stale, _ = O.OracleScene(_moved(scene, xf, stale=True)).render(W, H, SPP, variant=abi.VARIANT_GLTF)
+    rmse, _, _ = image_error(stale, ref)
+    print("oracle, stale lights against placed lights: rmse %.3e" % rmse)
+    assert rmse >= 100 * RMSE_TOL
+
+
+@pytest.mark.parametrize("policy", POLICIES)
+def test_frame_after_a_move_equals_the_oracle_and_a_fresh_set_scene(scene, move, policy):
+    xf, yard, osc, ref = move
+    r = _renderer(scene)
+    r.set_tlas_policy(policy)
+    r.update_instances(0, xf)
+    r.refit()
+    img, _, _ = gpu_render(yard, W, H, SPP, abi.VARIANT_GLTF, renderer=r)
+    rmse, same, _ = image_error(img, ref)
+    print("policy %d: rmse vs oracle %.3e" % (policy, rmse))
+    assert same and rmse < RMSE_TOL
+    assert_ray_visit_parity(r, osc, W, H, SPP, abi.VARIANT_GLTF)
+    f = _renderer(yard, register=False)
+    fimg, _, _ = gpu_render(yard, W, H, SPP, abi.VARIANT_GLTF, renderer=f)
+    frmse, fsame, _ = image_error(img, fimg)
+    print("policy %d: rmse vs fresh set_scene %.3e" % (policy, frmse))
+    assert fsame and frmse < RMSE_TOL
+    assert np.array_equal(_bits(r.readback_lights()), _bits(f.readback_lights()))
+    f.close()
+    r.close()
+
+
+# ---- 3. a deforming emitter
+@pytest.mark.parametrize("case", ["vertices", "vertices+move+rebuild"])
+def test_deformed_emitter_takes_its_lights_along(case):
+    s = _scene(deforming=True)
+    P = _deformed_positions(s)
+    xf = _scene_transforms(s)
+    r = _renderer(s)
+    if case != "vertices":     # a vertex update and an instance move in ONE refit, the mesh's tree rebuilt on the device: its triangles
+        r.set_bvh_policy(force_bvh_rebuild=True)   # are reordered, the float positions the placement reads are not
+        xf = _transforms(len(s.instances), MOVE_SEED)
+        r.update_instances(0, xf)
+    r.update_vertices(1, P)
+    r.refit()
+    if case != "vertices":
+        assert r.bvh_rebuild_count() == 1
+    yard = _moved(s, xf, {1: P})
+    assert np.array_equal(_bits(r.readback_lights()), _bits(yard.lights))
+    assert not np.array_equal(_bits(yard.lights[:, :3]), _bits(_moved(s, xf).lights[:, :3]))
+    img, _, _ = gpu_render(yard, W, H, SPP, abi.VARIANT_GLTF, renderer=r)
+    osc = O.OracleScene(yard)
+    osc.set_dynamic_vertices(1, P)
+    ref, _ = osc.render(W, H, SPP, variant=abi.VARIANT_GLTF)
+    rmse, same, _ = image_error(img, ref)
+    print("%s: rmse vs oracle %.3e" % (case, rmse))
+    assert same and rmse < RMSE_TOL
+    r.close()
+
+
+# ---- 4. frames in flight
+def test_moving_lights_with_frames_in_flight_equal_one_at_a_time(scene):
+    """(update, refit, render_async) x 5 over three frame contexts, never waiting in between, gives the frames of the same steps rendered
+    one at a time: every context owns its light buffer, so a refit never rewrites the lights a frame in flight is sampling"""
+    n = len(scene.instances)
+    base = _scene_transforms(scene)
+    steps = []
+    for k in range(5):
+        xf = base.copy()
+        for i in EMISSIVE:
+            xf[i] = _transforms(1, 70 + 10 * k + i)[0]
+        steps.append(xf)
+    assert n == 12
+
+    def run(fif):
+        r = _renderer(scene, frames_in_flight=fif)
+        cam = scene.camera_params()
+        images, queue = [], []
+
+        def collect():
+            r.wait(queue.pop(0))
+            img = np.zeros((H, W, 4), np.float32)
+            r.readback_framebuffer(img)
+            images.append(img)
+        for xf in steps:
+            r.update_instances(0, xf)
+            r.refit()
+            queue.append(r.render_async(backend.RenderConfiguration(cam, active_variant=abi.VARIANT_GLTF, reset_accumulation=True), spp=SPP))
+            if len(queue) >= fif:
+                collect()
+        while queue:
+            collect()
+        lights = r.readback_lights()
+        r.close()
+        return images, lights
+
+    ref_images, ref_lights = run(1)
+    images, lights = run(3)
+    for a, b in zip(images, ref_images):
+        assert np.array_equal(_bits(a), _bits(b))
+    assert np.array_equal(_bits(lights), _bits(ref_lights)) and np.array_equal(_bits(lights), _bits(_moved(scene, steps[-1]).lights))
+    assert not np.array_equal(ref_images[0], ref_images[2])
+
+
+# ---- 5. device source
+def test_device_source_gives_the_same_light_buffer(scene):
+    import torch
+    xf = _transforms(len(scene.instances), 33)
+    a = _renderer(scene)
+    a.update_instances(0, xf)
+    a.refit()
+    b = _renderer(scene)
+    buf = torch.from_numpy(np.ascontiguousarray(xf.reshape(-1, 12))).cuda()
+    torch.cuda.synchronize()
+    b.update_instances_device(0, buf.data_ptr(), xf.shape[0])
+    b.refit()
+    la, lb = a.readback_lights(), b.readback_lights()
+    assert np.array_equal(_bits(la), _bits(lb)) and np.array_equal(_bits(la), _bits(_moved(scene, xf).lights))
+    assert b.get_option("instance_updates_rejected") == 0
+    a.close()
+    b.close()
+
+
+# ---- 6. radiance queries
+def test_radiance_queries_after_a_move_equal_a_fresh_set_scene(scene, move):
+    xf, yard, _, _ = move
+    q = random_queries(np.random.default_rng(9), 6000, -6, 6)
+    cam = scene.camera_params()
+    r = _renderer(scene)
+    before = r.render_radiance_queries(q, cam, variant=abi.VARIANT_GLTF, spp=2).copy()
+    r.update_instances(0, xf)
+    r.refit()
+    res = r.render_radiance_queries(q, cam, variant=abi.VARIANT_GLTF, spp=2).copy()
+    f = _renderer(yard, register=False)
+    fres = f.render_radiance_queries(q, cam, variant=abi.VARIANT_GLTF, spp=2).copy()
+    assert np.array_equal(_bits(res), _bits(fres))     # (bit for bit, like the comparisons between runs in test_gpu_radiance_queries.py)
+    assert not np.array_equal(_bits(res), _bits(before)) and (res[:, :3] > 0).any()
+    f.close()
+    r.close()
+
+
+# ---- 7. rejections and the state of the registration
+def test_rejected_registrations_leave_everything_unchanged(scene):
+    r = backend.RenderHip()
+    r.initialize(W, H)
+    src = scene.light_sources
+
+    def rejected(sources, code=abi.RPTR_E_INVALID):
+        with pytest.raises(backend.BackendError) as e:
+            r.set_light_sources(sources)
+        assert e.value.code == code, str(e.value)
+        return str(e.value)
+
+    rejected(src)                                                    # before set_scene
+    r.set_scene(scene)
+    r.set_light_sources(scene)
+    lights0 = r.readback_lights()
+
+    def frozen_frame():
+        # (RenderConfiguration.freeze_frame: the handle's sample sequence stands still, so two frames of an unchanged scene draw the same
+        # samples and are equal bit for bit; otherwise every reset moves frame_offset on and the noise differs)
+        cfg = backend.RenderConfiguration(scene.camera_params(), active_variant=abi.VARIANT_GLTF, reset_accumulation=True, freeze_frame=True)
+        r.render(cfg, spp=SPP)
+        img = np.zeros((H, W, 4), np.float32)
+        assert r.readback_framebuffer(img) == W * H * 4
+        return img
+
+    img0 = frozen_frame()
+    assert np.array_equal(_bits(frozen_frame()), _bits(img0))      # (the comparison below can tell: frozen frames repeat)
+    rejected(src[:-1])                                               # count != num_lights
+    rejected(np.concatenate([src, src[:1]]))
+    swapped = src.copy()                                             # a light of instance 2 said to come from instance 5: same mesh, same
+    k = int(np.nonzero(src["instance"] == 2)[0][0])                  # triangle, another place -- only the provenance check can tell
+    swapped["instance"][k] = 5
+    assert "light source %d" % k in rejected(swapped)
+    far = src.copy()
+    far["triangle"][3] = scene.geometries[int(src["geometry"][3])].num_tris
+    assert "light source 3" in rejected(far)
+    other = src.copy()
+    other["geometry"][0] = 0                                         # a geometry of mesh 0: not the instance's mesh
+    rejected(other)
+    gone = src.copy()
+    gone["instance"][1] = len(scene.instances)
+    rejected(gone)
+    assert r._L.rptr_hip_set_light_sources(r._h, None, 3) == abi.RPTR_E_INVALID
+    assert r._L.rptr_hip_set_light_sources(r._h, src.ctypes.data_as(C.c_void_p), 0) == abi.RPTR_E_INVALID
+    with pytest.raises(backend.BackendError):
+        r.readback_lights(len(src) + 1)
+    # ... and the registration made before them still stands: same buffer, same frame, an emissive instance still moves
+    assert np.array_equal(_bits(r.readback_lights()), _bits(lights0))
+    assert np.array_equal(_bits(frozen_frame()), _bits(img0))
+    r.update_instances(2, _scene_transforms(scene)[2:3])
+    r.refit()
+    assert np.array_equal(_bits(r.readback_lights()), _bits(lights0))
+    r.close()
+
+
+def test_unregistering_and_a_new_set_scene_drop_the_registration(scene):
+    r = _renderer(scene, register=False)
+    ok = _transforms(1, 3)
+
+    def unsupported():
+        with pytest.raises(backend.BackendError) as e:
+            r.update_instances(2, ok)
+        assert e.value.code == abi.RPTR_E_UNSUPPORTED and "rptr_hip_set_light_sources" in str(e.value), str(e.value)
+
+    unsupported()                                                    # set_scene registers nothing on its own
+    r.set_light_sources(scene)
+    r.update_instances(2, ok)
+    r.refit()
+    moved = r.readback_lights()
+    assert not np.array_equal(_bits(moved), _bits(scene.lights))
+    r.set_light_sources(None)                                        # (NULL, 0): the lights are the ones set_scene uploaded again
+    unsupported()
+    assert np.array_equal(_bits(r.readback_lights()), _bits(scene.lights))
+    r.set_light_sources(scene.light_sources)                         # the array form; registered again
+    r.update_instances(2, ok)
+    r.refit()
+    assert np.array_equal(_bits(r.readback_lights()), _bits(moved))
+    r.set_scene(scene)                                               # a new scene: the registration is gone
+    unsupported()
+    assert np.array_equal(_bits(r.readback_lights()), _bits(scene.lights))
+    r.close()
+
+
+# ---- 8. drift
+def test_fifty_updates_that_end_at_the_start_leave_the_lights_bit_identical(scene):
+    """placement starts from the object-space source every time, never from the previous placement"""
+    n = len(scene.instances)
+    x0, x1 = _scene_transforms(scene), _transforms(n, 6)
+    r = _renderer(scene)
+    for k in range(1, 51):
+        w = np.float32(np.sin(np.pi * k / 50.0))                     # out along the path and back
+        r.update_instances(0, ((1 - w) * x0 + w * x1).astype(np.float32) if k < 50 else x0)
+        r.refit()
+        if k == 25:
+            assert not np.array_equal(_bits(r.readback_lights()), _bits(scene.lights))
+    assert np.array_equal(_bits(r.readback_lights()), _bits(scene.lights))
+    r.close()

@@ -1,0 +1,186 @@
+"""Moving lights on the host: the provenance of Scene.lights (lights.collect_light_sources, carried through update_light_sampling into
+Scene.light_sources) and the placement rule of rptr_hip_set_light_sources (lights.place_light_sources), in Python and in the C++ twin
+(host/lights.hpp). No GPU.
+
+Everything is compared bit for bit: the rule is the arithmetic of collect_emitters, (m0 x + m1 y) + (m2 z + m3) in float32, every
+product and sum rounded."""
+import copy
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from realtimepathtracingresearchframework_amd import abi, lights as L, scenes
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HOST = os.path.join(ROOT, "realtimepathtracingresearchframework_amd", "host")
+
+SCENES = {
+    "two_level": scenes.two_level_test,
+    "textured": scenes.textured_test,
+    "grid40x20": lambda: scenes.grid(nx=40, nz=20, with_emitters=True),
+    "cornell32": scenes.cornell32,
+}
+
+
+@pytest.fixture(scope="module", params=sorted(SCENES))
+def scene(request):
+    return SCENES[request.param]()
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def _scene_transforms(s):
+    return np.stack([np.asarray(i.transform, np.float32).reshape(3, 4) for i in s.instances])
+
+
+def _transforms(n, seed, spread=4.0):
+    """rotation x NON-uniform scale + translation, float32 (n, 3, 4)"""
+    rng = np.random.default_rng(seed)
+    out = np.zeros((n, 3, 4), np.float32)
+    for i in range(n):
+        ang = rng.uniform(0, 2 * np.pi)
+        axis = rng.normal(size=3)
+        axis /= np.linalg.norm(axis)
+        K = np.array([[0, -axis[2], axis[1]], [axis[2], 0, -axis[0]], [-axis[1], axis[0], 0]])
+        R = np.eye(3) + np.sin(ang) * K + (1 - np.cos(ang)) * K @ K
+        out[i, :, :3] = R @ np.diag(rng.uniform(0.5, 1.7, size=3))
+        out[i, :, 3] = rng.uniform(-spread, spread, size=3)
+    return out
+
+
+def _key(src):
+    return list(zip(src["instance"].tolist(), src["geometry"].tolist(), src["triangle"].tolist()))
+
+
+def test_struct_mirrors_agree():
+    import ctypes as C
+    assert L.LIGHT_SOURCE_DTYPE.itemsize == C.sizeof(abi.LightSource) == 48
+    for name, _ in abi.LightSource._fields_:
+        assert L.LIGHT_SOURCE_DTYPE.fields[name][1] == getattr(abi.LightSource, name).offset, name
+
+
+def test_placement_with_the_scene_transforms_gives_the_scene_lights(scene):
+    assert len(scene.lights) > 0 and len(scene.light_sources) == len(scene.lights)
+    placed = L.place_light_sources(scene.light_sources, _scene_transforms(scene))
+    assert placed.dtype == np.float32 and placed.shape == (len(scene.lights), 3, 3)
+    assert np.array_equal(_bits(placed), _bits(scene.lights[:, :3]))
+
+
+def test_lights_are_what_prepare_lights_made_before(scene):
+    lc = abi.LightSamplingConfig.default()
+    em = L.collect_emitters(scene)
+    em, rad = L.update_light_sampling(em, lc.min_perceived_receiver_dist, lc.min_radiance, lc.bin_size)
+    assert em.shape == scene.lights.shape and np.array_equal(_bits(em), _bits(scene.lights))
+    # the optional third result changes neither of the first two
+    em3, rad3, src = L.update_light_sampling(L.collect_emitters(scene), lc.min_perceived_receiver_dist, lc.min_radiance, lc.bin_size, return_sources=True)
+    assert np.array_equal(_bits(em3), _bits(em)) and np.array_equal(_bits(rad3), _bits(rad)) and len(src) == len(em)
+
+
+def test_trimming_keeps_the_sources_in_step():
+    s = scenes.two_level_test()
+    em = L.collect_emitters(s)
+    rad = L.estimate_normalized_radiance(em, 15.0)
+    cut = float(np.median(rad))
+    em2, _, src = L.update_light_sampling(em, 15.0, cut, 16, return_sources=True)
+    assert 0 < len(set(src.tolist())) < len(em) and np.all(rad[src] >= np.float32(cut))
+    assert np.array_equal(_bits(em2[:, :3]), _bits(em[src][:, :3]))   # a clone has its emitter's vertices (its radiance is split)
+
+
+def test_sources_dequantize_to_their_vertices(scene):
+    src = scene.light_sources
+    for i in range(len(src)):
+        inst, gi, t = int(src["instance"][i]), int(src["geometry"][i]), int(src["triangle"][i])
+        mesh = scene.meshes[scene.pmeshes[scene.instances[inst].pmesh].mesh]
+        assert mesh.first_geometry <= gi < mesh.first_geometry + mesh.num_geometries
+        g = scene.geometries[gi]
+        assert t < g.num_tris
+        pos = scenes.dequantize_positions(g.qpos[3 * t:3 * t + 3], g.scaling, g.offset)
+        got = np.stack([src["v0"][i], src["v1"][i], src["v2"][i]])
+        assert np.array_equal(_bits(pos), _bits(got)), i
+
+
+def test_moved_instances_place_like_collect_emitters_of_the_moved_scene(scene):
+    xf = _transforms(len(scene.instances), seed=11)
+    moved = copy.copy(scene)
+    moved.instances = [copy.copy(i) for i in scene.instances]
+    for k, inst in enumerate(moved.instances):
+        inst.transform = xf[k].copy()
+    emitters = L.collect_emitters(moved)               # before equalisation: one entry per emissive triangle of every instance
+    pre = L.collect_light_sources(moved)
+    assert len(pre) == len(emitters)
+    where = {k: i for i, k in enumerate(_key(pre))}
+    assert len(where) == len(pre)
+    placed = L.place_light_sources(scene.light_sources, xf)
+    match = np.array([where[k] for k in _key(scene.light_sources)])
+    assert np.array_equal(_bits(placed), _bits(emitters[match][:, :3]))
+
+
+def test_positions_replace_the_source_vertices_of_a_deforming_geometry():
+    s = scenes.two_level_test()
+    src = s.light_sources
+    gi = int(src["geometry"][0])
+    g = s.geometries[gi]
+    pos = scenes.dequantize_positions(g.qpos, g.scaling, g.offset)
+    xf = _scene_transforms(s)
+    assert np.array_equal(_bits(L.place_light_sources(src, xf, {gi: pos})), _bits(s.lights[:, :3]))
+    new = (pos * np.float32(1.25) + np.float32(0.125)).astype(np.float32)
+    moved_src = src.copy()
+    sel = src["geometry"] == gi
+    tri = new.reshape(-1, 3, 3)[src["triangle"][sel]]
+    moved_src["v0"][sel], moved_src["v1"][sel], moved_src["v2"][sel] = tri[:, 0], tri[:, 1], tri[:, 2]
+    assert sel.any() and np.array_equal(_bits(L.place_light_sources(src, xf, {gi: new})), _bits(L.place_light_sources(moved_src, xf)))
+
+
+CPP = r"""
+#include "lights.hpp"
+#include <cstdio>
+int main(int argc, char **argv) {
+    if (argc < 4) return 2;
+    rptr::SceneDump s = rptr::SceneDump::load(argv[1]);
+    const std::vector<RptrTriLightData> dumped = s.lights;
+    rptr::lights::prepare_lights(s);
+    if (s.lights.size() != dumped.size() || s.light_sources.size() != s.lights.size()) return 3;
+    if (!s.lights.empty() && std::memcmp(s.lights.data(), dumped.data(), dumped.size() * sizeof(RptrTriLightData))) return 4;
+    std::vector<float> xf(12 * s.instances.size());
+    FILE *f = std::fopen(argv[2], "rb");
+    if (!f || std::fread(xf.data(), 4, xf.size(), f) != xf.size()) return 5;
+    std::fclose(f);
+    const std::vector<RptrTriLightData> placed = rptr::lights::place_light_sources(s.light_sources, xf.data());
+    f = std::fopen(argv[3], "wb");
+    if (!f) return 6;
+    std::fwrite(s.light_sources.data(), sizeof(RptrLightSource), s.light_sources.size(), f);
+    std::fwrite(placed.data(), sizeof(RptrTriLightData), placed.size(), f);
+    std::fclose(f);
+    return 0;
+}
+"""
+
+
+@pytest.fixture(scope="module")
+def cpp_program(tmp_path_factory):
+    d = tmp_path_factory.mktemp("moving_lights_cpp")
+    src = d / "light_sources.cpp"
+    src.write_text(CPP)
+    exe = str(d / "light_sources")
+    # (no contraction: the rule's products and sums are each rounded, as in numpy)
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-ffp-contract=off", "-I" + HOST, str(src), "-o", exe])
+    return exe
+
+
+def test_cpp_mirror_equals_python_word_for_word(scene, cpp_program, tmp_path):
+    dump, xf_file, out = str(tmp_path / "scene.rpsc"), str(tmp_path / "xf.f32"), str(tmp_path / "out.bin")
+    scene.dump(dump)
+    xf = _transforms(len(scene.instances), seed=23)
+    xf.tofile(xf_file)
+    subprocess.check_call([cpp_program, dump, xf_file, out])   # (also checks: the C++ prepare_lights reproduces the dumped lights)
+    raw = np.fromfile(out, dtype=np.uint32)
+    n = len(scene.lights)
+    assert raw.size == n * 12 * 2
+    assert np.array_equal(raw[:n * 12], np.ascontiguousarray(scene.light_sources).view(np.uint32).reshape(-1))
+    placed = raw[n * 12:].reshape(n, 4, 3)
+    assert np.array_equal(placed[:, :3], _bits(L.place_light_sources(scene.light_sources, xf)))
+    assert not placed[:, 3].any()
