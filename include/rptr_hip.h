@@ -773,6 +773,51 @@ int rptr_hip_trace_radiance(rptr_hip_t *h, const RptrRenderRayQuery *queries, in
 int rptr_hip_trace_radiance_device(rptr_hip_t *h, const RptrRenderRayQuery *device_queries, int n, const RptrCamera *camera, int variant,
                                    int samples_per_query, int first_sample, float *device_out4, void *hip_stream);
 int rptr_hip_render_radiance_queries(rptr_hip_t *h, int num_queries, const RptrCamera *camera, int variant, int samples_per_query, int first_sample);
+/* ---- surface queries: position, normals and material at a query ray's closest hit
+ * What lies between rptr_hip_trace (barycentrics and indices) and rptr_hip_trace_radiance (radiance): the surface the ray hit, decoded by
+ * the device functions the first shade of a frame uses for its AOV images. The reference's registry declares a GBUFFER computational
+ * raytracer beside RQ_CLOSEST (rendering/gpu_programs.cmake:47) and ships no source for it; this is that program for query rays.
+ * One record of 96 bytes per query: six rows of 16 bytes. For query (origin, dir, t_max) the direction is used as given, the interval is
+ * (0, t_max) as for radiance queries, and w_o = -dir:
+ *   t, position      the closest hit and origin + t * dir, geometric. (The megakernel's VOLUME back-face rule, which moves its interaction
+ *                    point to the ray origin, does NOT apply here.)
+ *   geo_normal, normal   gn and nn of the megakernel's first hit as the normal + depth AOV holds them for a camera ray: hit attributes,
+ *                    normalised geometric normal, the flip towards the ray for two-sided materials (pt_megakernel.glsl:624-633), the normal
+ *                    map at LOD 0 (:634-654), the w_o correction (:656-668).
+ *   instance_geometry, primitive   the two index words of rptr_hip_trace (instance custom index + geometry index; primitive index)
+ *   base_color, roughness, ior, metallic, emission   the hit's material unpacked by gpu program `variant` (RPTR_VARIANT_*) at the hit's
+ *                    texture coordinate, whose footprint is the camera-derived first-hit footprint of radiance queries (`camera`'s
+ *                    image-plane axes, the handle's frame size, RenderParams.pixel_radius; pt_megakernel.glsl:341-352). base_color is 0 on
+ *                    emitters, as in the albedo AOV; emission is the emitter's radiance. RPTR_VARIANT_SIMPLE: roughness 1, ior 1, metallic 0.
+ *   uv, material_id  the interpolated texture coordinate and the index into RptrSceneDesc.materials the shade would load
+ * A miss (also when t_max ends the ray first): t = -1, both indices and material_id -1, roughness 1, ior 1, every other float 0 (the miss
+ * texel of the albedo + roughness AOV). mode_or_data < 0 leaves the record untouched. Alpha-tested geometry is opaque to these queries, as
+ * it is to rptr_hip_trace. */
+typedef struct RptrSurfaceHit {
+    float position[3];
+    float t;
+    float geo_normal[3];
+    int32_t instance_geometry;
+    float normal[3];
+    int32_t primitive;
+    float base_color[3];
+    float roughness;
+    float emission[3];
+    float ior;
+    float uv[2];
+    int32_t material_id;
+    float metallic;
+} RptrSurfaceHit;
+/* rptr_hip_trace_surface: host arrays, synchronous; `out` is read as well as written (the slots of skipped queries are preserved).
+ * rptr_hip_trace_surface_device: DEVICE buffers, asynchronously on `hip_stream` (NULL: the backend's stream), ordered as
+ * rptr_hip_trace_device; device_queries == NULL: the query buffer of rptr_hip_enable_ray_queries (more than its budget: RPTR_E_INVALID).
+ * Both trace the scene copy rptr_hip_trace traces (after update_vertices / update_instances and rptr_hip_refit: the moved geometry), wait
+ * for the frames in flight and leave the accumulation and frame buffers, the AOV images, frame_id / frame_offset, the reprojection history,
+ * the denoised images and rptr_hip_stats alone. world_size > 1: RPTR_E_UNSUPPORTED. NULL camera, query or output pointer, n < 0, unknown
+ * variant, before set_scene / initialize: RPTR_E_INVALID (the argument checks come before the device is touched). */
+int rptr_hip_trace_surface(rptr_hip_t *h, const RptrRenderRayQuery *queries, int n, const RptrCamera *camera, int variant, RptrSurfaceHit *out);
+int rptr_hip_trace_surface_device(rptr_hip_t *h, const RptrRenderRayQuery *device_queries, int n, const RptrCamera *camera, int variant,
+                                  RptrSurfaceHit *device_out, void *hip_stream);
 /* RenderBackendOptions::light_sampling_variant (rendering/mc/light_sampling.h:11-20, rendering/mc/nee.glsl:12-14): 0 =
  * LIGHT_SAMPLING_VARIANT_NONE disables next-event estimation towards the emissive triangles (every NEE sample goes to the sun; emitters
  * that a path HITS still contribute, at full weight), 1 = LIGHT_SAMPLING_VARIANT_RIS (the default: binned RIS). The image is that of

@@ -73,6 +73,8 @@ def load_library(path=None):
     L.rptr_hip_trace_radiance.argtypes = [vp, vp, i32, C.POINTER(abi.Camera), i32, i32, i32, vp, C.POINTER(abi.Stats)]
     L.rptr_hip_trace_radiance_device.argtypes = [vp, vp, i32, C.POINTER(abi.Camera), i32, i32, i32, vp, vp]
     L.rptr_hip_render_radiance_queries.argtypes = [vp, i32, C.POINTER(abi.Camera), i32, i32, i32]
+    L.rptr_hip_trace_surface.argtypes = [vp, vp, i32, C.POINTER(abi.Camera), i32, vp]
+    L.rptr_hip_trace_surface_device.argtypes = [vp, vp, i32, C.POINTER(abi.Camera), i32, vp, vp]
     L.rptr_hip_set_light_sampling_variant.argtypes = [vp, i32]
     L.rptr_hip_set_freeze_frame.argtypes = [vp, i32]
     L.rptr_hip_set_option.argtypes = [vp, C.c_char_p, C.c_int64]
@@ -473,6 +475,27 @@ class RenderHip:
         else:
             self._check(self._L.rptr_hip_trace_radiance_device(self._h, C.c_void_p(device_queries), int(num_queries), C.byref(camera), int(variant), int(spp),
                                                                int(first_sample), C.c_void_p(device_results), C.c_void_p(stream or 0)))
+
+    # ---- surface queries: position, normals and material at the closest hit (include/rptr_hip.h rptr_hip_trace_surface)
+    def render_surface_queries(self, queries: np.ndarray, camera, variant=abi.VARIANT_GLTF, results: np.ndarray = None):
+        """queries: (n,8) float32 view of RenderRayQuery[n]; camera: abi.Camera (its image-plane axes size the texture footprint).
+        Returns n records of abi.SURFACE_HIT_DTYPE, written into `results` when given (read too: the slots of queries with
+        mode_or_data < 0 stay as they are). A miss has t = -1. The frame in progress is left alone."""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, 8)
+        if results is None:
+            results = np.zeros(len(q), dtype=abi.SURFACE_HIT_DTYPE)
+        if results.dtype != abi.SURFACE_HIT_DTYPE or not results.flags["C_CONTIGUOUS"] or results.size < len(q):
+            raise ValueError("render_surface_queries: results must be a C-contiguous array of n abi.SURFACE_HIT_DTYPE records")
+        self._push_params()
+        self._check(self._L.rptr_hip_trace_surface(self._h, q.ctypes.data_as(C.c_void_p), len(q), C.byref(camera), int(variant), results.ctypes.data_as(C.c_void_p)))
+        return results
+
+    def render_surface_queries_device(self, num_queries, camera, variant=abi.VARIANT_GLTF, device_queries=None, device_results=None, stream=None):
+        """the same over DEVICE buffers, asynchronously on `stream` (None = the backend's): device_results names num_queries records of
+        96 bytes; device_queries None = the query buffer of enable_ray_queries_device"""
+        self._push_params()
+        self._check(self._L.rptr_hip_trace_surface_device(self._h, C.c_void_p(device_queries or 0), int(num_queries), C.byref(camera), int(variant),
+                                                          C.c_void_p(device_results or 0), C.c_void_p(stream or 0)))
 
     def set_light_sampling_variant(self, variant):
         """RenderBackendOptions::light_sampling_variant: 0 = NONE (no NEE towards emissive triangles), 1 = RIS (default)"""

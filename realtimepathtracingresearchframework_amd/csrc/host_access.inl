@@ -532,6 +532,121 @@ int rptr_hip_render_radiance_queries(rptr_hip_t *h, int num_queries, const RptrC
     return rptr_hip_trace_radiance_device(h, h->rq_queries, num_queries, camera, variant, samples_per_query, first_sample, reinterpret_cast<float *>(h->rq_results), nullptr);
 }
 
+// ---- surface queries (surface_query.h): the raw closest hits into the handle's scratch, then the decode into RptrSurfaceHit records
+extern "C++" {
+// (the argument checks come first: they need neither a handle nor a device)
+static int check_surface_arguments(rptr_hip_t *h, bool have_queries, int n, const RptrCamera *camera, int variant, const void *out) {
+    if (!camera) return fail(h, RPTR_E_INVALID, "surface queries: NULL camera (its image-plane axes size the texture footprint)");
+    if (n < 0) return fail(h, RPTR_E_INVALID, "surface queries: n must be >= 0");
+    if (!have_queries || !out) return fail(h, RPTR_E_INVALID, "surface queries: NULL query or output buffer");
+    if (variant != RPTR_VARIANT_GLTF && variant != RPTR_VARIANT_SIMPLE && variant != RPTR_VARIANT_GLTF_TRANSMISSION)
+        return fail(h, RPTR_E_INVALID, "surface queries: unknown variant %d", variant);
+    if (!h) return fail(nullptr, RPTR_E_INVALID, "NULL handle");
+    if (!h->have_scene) return fail(h, RPTR_E_INVALID, "surface queries before set_scene");
+    if (h->width == 0 || h->ctx.empty() || !h->ctx[0].gstack) return fail(h, RPTR_E_INVALID, "surface queries before initialize");
+    if (h->world > 1) return fail(h, RPTR_E_UNSUPPORTED, "surface queries need world_size 1: queries are not striped over the ranks");
+    return RPTR_OK;
+}
+// the scratch holds the largest n seen: a run of no more queries than an earlier one allocates nothing
+static int surface_scratch(rptr_hip_t *h, int n) {
+    if ((size_t)n <= h->sq_capacity) return RPTR_OK;
+    HIP_TRY(h, hipStreamSynchronize(h->stream)); // (an earlier run -- on a caller's stream too: the backend's is ordered behind it -- may still use the old one)
+    if (h->sq_raw) (void)hipFree(h->sq_raw);
+    h->sq_raw = nullptr;
+    h->sq_capacity = 0;
+    if (hipMalloc(&h->sq_raw, (size_t)n * sizeof(RpRawHit)) != hipSuccess) {
+        h->sq_raw = nullptr;
+        return fail(h, RPTR_E_NOMEM, "hipMalloc of the surface-query scratch (%d queries) failed", n);
+    }
+    h->sq_capacity = (size_t)n;
+    return RPTR_OK;
+}
+// Queues the two launches on `st` for DEVICE buffers. The caller has drained the frames in flight: the traversal borrows context 0's cursor
+// and stack scratch, nothing a frame owns is written.
+static int surface_queries_on(rptr_hip_t *h, const RptrRenderRayQuery *dq, int n, const RptrCamera *camera, int variant, RptrSurfaceHit *dout, hipStream_t st) {
+    if (n == 0) return RPTR_OK;
+    RpFrame view;
+    compute_view(*camera, h->width, h->height, view);
+    RpSurfaceFrame f;
+    memset(&f, 0, sizeof(f));
+    memcpy(f.cam_du, view.cam_du, sizeof(f.cam_du));
+    memcpy(f.cam_dv, view.cam_dv, sizeof(f.cam_dv));
+    f.width = h->width;
+    f.height = h->height;
+    f.pixel_radius = h->params.pixel_radius;
+    f.normal_z_scale = h->scene_params.normal_z_scale;
+    RpRawHit *raw = static_cast<RpRawHit *>(h->sq_raw);
+    const RpScene &sc = h->master.dscene;
+    // cursor_extend doubles as the pool cursor of the traversal (as for rp_k_trace: no overlap with a frame)
+    uint32_t *cursor = &h->ctx[0].counters->bounce[0].cursor_extend;
+    hipLaunchKernelGGL(rp_k_reset_u32, dim3(1), dim3(1), 0, st, cursor);
+    rp_pick(sc.single_instance != 0, [&](auto S) {
+        hipLaunchKernelGGL((rp_k_trace_surface<decltype(S)::value>), dim3(h->persistent_blocks), dim3(RP_TRAVERSE_BLOCK), 0, st, sc, dq, (uint32_t)n, raw, cursor, h->ctx[0].gstack);
+    });
+    // TEX as the frame's kernels select theirs: no material of the scene reads a texture -> the instantiation without sampling code
+    const dim3 grid((unsigned)grid_for(h, (size_t)n));
+    rp_pick(h->uses_textures, [&](auto T) {
+        constexpr bool tex = decltype(T)::value;
+        if (variant == RPTR_VARIANT_SIMPLE)
+            hipLaunchKernelGGL((rp_k_surface<RPTR_VARIANT_SIMPLE, tex>), grid, dim3(256), 0, st, sc, f, dq, (const RpRawHit *)raw, (uint32_t)n, dout);
+        else if (variant == RPTR_VARIANT_GLTF_TRANSMISSION)
+            hipLaunchKernelGGL((rp_k_surface<RPTR_VARIANT_GLTF_TRANSMISSION, tex>), grid, dim3(256), 0, st, sc, f, dq, (const RpRawHit *)raw, (uint32_t)n, dout);
+        else
+            hipLaunchKernelGGL((rp_k_surface<RPTR_VARIANT_GLTF, tex>), grid, dim3(256), 0, st, sc, f, dq, (const RpRawHit *)raw, (uint32_t)n, dout);
+    });
+    HIP_TRY(h, hipGetLastError());
+    return RPTR_OK;
+}
+}
+
+int rptr_hip_trace_surface(rptr_hip_t *h, const RptrRenderRayQuery *queries, int n, const RptrCamera *camera, int variant, RptrSurfaceHit *out) {
+    int rc = check_surface_arguments(h, queries != nullptr, n, camera, variant, out);
+    if (rc) return rc;
+    if ((rc = drain(h)) || (rc = ensure_master_tree(h))) return rc; // the traversal borrows context 0's cursor and stack scratch
+    if (n == 0) return RPTR_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    if ((rc = surface_scratch(h, n))) return rc;
+    RptrRenderRayQuery *dq = nullptr;
+    RptrSurfaceHit *dout = nullptr;
+    if (hipMalloc((void **)&dq, (size_t)n * sizeof(RptrRenderRayQuery)) != hipSuccess || hipMalloc((void **)&dout, (size_t)n * sizeof(RptrSurfaceHit)) != hipSuccess) {
+        (void)hipFree(dq);
+        return fail(h, RPTR_E_NOMEM, "hipMalloc failed");
+    }
+    do {
+        // (the records go up too: slots of skipped queries keep what the caller put there)
+        if (hipMemcpyAsync(dq, queries, (size_t)n * sizeof(RptrRenderRayQuery), hipMemcpyHostToDevice, h->stream) != hipSuccess ||
+            hipMemcpyAsync(dout, out, (size_t)n * sizeof(RptrSurfaceHit), hipMemcpyHostToDevice, h->stream) != hipSuccess) {
+            rc = fail(h, RPTR_E_HIP, "upload failed");
+            break;
+        }
+        if ((rc = surface_queries_on(h, dq, n, camera, variant, dout, h->stream))) break;
+        if (hipMemcpyAsync(out, dout, (size_t)n * sizeof(RptrSurfaceHit), hipMemcpyDeviceToHost, h->stream) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess ||
+            hipGetLastError() != hipSuccess) {
+            rc = fail(h, RPTR_E_HIP, "surface query kernels failed");
+            break;
+        }
+    } while (0);
+    if (rc) (void)hipStreamSynchronize(h->stream); // nothing of the run may still use the buffers freed below
+    (void)hipFree(dq);
+    (void)hipFree(dout);
+    return rc;
+}
+
+int rptr_hip_trace_surface_device(rptr_hip_t *h, const RptrRenderRayQuery *device_queries, int n, const RptrCamera *camera, int variant, RptrSurfaceHit *device_out,
+                                  void *hip_stream) {
+    int rc = check_surface_arguments(h, true, n, camera, variant, device_out);
+    if (rc) return rc;
+    if (!device_queries) { // the query buffer of rptr_hip_enable_ray_queries
+        if ((size_t)n > h->rq_capacity) return fail(h, RPTR_E_INVALID, "%d ray queries exceed the budget of %zu (rptr_hip_enable_ray_queries)", n, h->rq_capacity);
+        device_queries = h->rq_queries;
+    }
+    if ((rc = drain(h)) || (rc = ensure_master_tree(h))) return rc; // the traversal borrows context 0's cursor and stack scratch
+    if (n == 0) return RPTR_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    if ((rc = surface_scratch(h, n))) return rc;
+    return on_callers_stream(h, hip_stream, [&](hipStream_t st) { return surface_queries_on(h, device_queries, n, camera, variant, device_out, st); });
+}
+
 int rptr_hip_set_light_sampling_variant(rptr_hip_t *h, int variant) {
     if (!h) return fail(nullptr, RPTR_E_INVALID, "NULL handle");
     if (variant != 0 && variant != 1) return fail(h, RPTR_E_INVALID, "unknown light sampling variant %d (0 = NONE, 1 = RIS)", variant);

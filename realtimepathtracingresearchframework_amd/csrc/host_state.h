@@ -353,6 +353,10 @@ struct rptr_hip {
     RptrRenderRayQuery *rq_queries = nullptr;
     float4 *rq_results = nullptr;
     size_t rq_capacity = 0;
+    // surface queries (surface_query.h): the raw hits between the two launches, 32 bytes per query; grows to the largest n seen, freed by
+    // rptr_hip_initialize / rptr_hip_destroy
+    void *sq_raw = nullptr;
+    size_t sq_capacity = 0;
     bool lights_disabled = false;   // light_sampling_variant == LIGHT_SAMPLING_VARIANT_NONE: no area-light NEE (rptr_hip_set_light_sampling_variant)
     bool aovs = true;               // the reference writes its AOV images with every frame (ENABLE_AOV_BUFFERS, render_vulkan.cpp:2083-2086)
     RptrCamera prev_camera;         // the previous frame's view (VP_reference)

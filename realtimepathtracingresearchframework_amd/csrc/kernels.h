@@ -685,6 +685,9 @@ RP_DEV void rp_shade_body(const RpScene &sc, const RpFrame &f, const RpPathState
                     ip_p = ray_origin + hit.dist * ray_dir;
                     gn = hit.geo_normal;
                     nn = hit.normal;
+                    // (:624-668 -- the flip, the normal map, the w_o correction -- have a second copy in surface_query.h rp_k_surface, which decodes the first hit
+                    // of a query ray with the same statements: a change here is a change there. They are not one shared function because hoisting
+                    // them out of this body changes the code generated for the shade and tail kernels.)
                     // :624-633
                     if (dot3(w_o, gn) < 0.0f) {
                         if ((mp.flags & RPTR_BASE_MATERIAL_VOLUME) != 0) {

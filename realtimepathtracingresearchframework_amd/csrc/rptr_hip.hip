@@ -11,6 +11,7 @@
 #include "kernels_misc.h"
 #include "realtime_resolve.h"
 #include "denoise.h"
+#include "surface_query.h"
 #include "launch.h"
 #include "lbvh.h"
 #include "tlas_build.h"
@@ -197,6 +198,7 @@ void rptr_hip_destroy(rptr_hip_t *h) {
     if (h->rng_table) (void)hipFree(h->rng_table);
     if (h->rq_queries) (void)hipFree(h->rq_queries);
     if (h->rq_results) (void)hipFree(h->rq_results);
+    if (h->sq_raw) (void)hipFree(h->sq_raw);
     delete h;
 }
 
@@ -229,6 +231,9 @@ int rptr_hip_initialize(rptr_hip_t *h, int fb_width, int fb_height) {
     comm_release(h); // its receive buffers and the assembled frame are frame-sized: a communicator is made again after a resize
     for (void *p : h->allocations) (void)hipFree(p);
     h->allocations.clear();
+    if (h->sq_raw) (void)hipFree(h->sq_raw); // (the raw hits of surface queries: allocated again by the next run)
+    h->sq_raw = nullptr;
+    h->sq_capacity = 0;
     h->bytes_frame = 0;
     h->bytes_allocated = h->bytes_scene;
     h->width = fb_width;

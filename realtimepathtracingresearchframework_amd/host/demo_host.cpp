@@ -113,6 +113,18 @@ int main() {
             // (the third ray leaves the scene: alpha 0, what the sky model gives)
             if (!same_rad || rad4[3] != 1.0f || rad4[7] != 1.0f || rad4[11] != 0.0f || !(rad4[0] >= 0.0f) || !(rad4[8] >= 0.0f)) return 12;
         }
+        // ---- the same three rays as surface queries: where the ray hit, which way the surface faces, what it is made of
+        {
+            RptrSurfaceHit sh[3] = {};
+            if (!backend.render_surface_queries(rq, 3, backend.params, RPTR_VARIANT_GLTF, cfg.camera, sh)) return 14;
+            std::printf("surface queries: t %.4f at (%.3f %.3f %.3f), normal (%.3f %.3f %.3f), base colour %.2f %.2f %.2f, roughness %.2f, primitive %d, material %d | t %.4f | t %.1f\n",
+                        sh[0].t, sh[0].position[0], sh[0].position[1], sh[0].position[2], sh[0].normal[0], sh[0].normal[1], sh[0].normal[2], sh[0].base_color[0],
+                        sh[0].base_color[1], sh[0].base_color[2], sh[0].roughness, sh[0].primitive, sh[0].material_id, sh[1].t, sh[2].t);
+            // (the triangle faces the ray after the two-sided flip; the third ray leaves the scene: the miss record)
+            if (!(sh[0].t > 3.99f && sh[0].t < 4.01f) || !(sh[0].normal[2] > 0.99f) || sh[0].base_color[0] != 0.8f || sh[0].primitive != prim0 || sh[0].material_id != 0 ||
+                !(sh[1].t > 0.0f) || sh[1].primitive != prim1 || sh[2].t != -1.0f || sh[2].primitive != -1 || sh[2].material_id != -1)
+                return 15;
+        }
         // ---- the ray-query-only surface (struct RaytraceBackend, librender/raytrace_backend.h:13-19)
         {
             rptr::RaytraceHip rt;

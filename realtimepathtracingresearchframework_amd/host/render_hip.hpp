@@ -15,6 +15,8 @@
 
 namespace rptr {
 
+static_assert(sizeof(RptrSurfaceHit) == 96, "RptrSurfaceHit: six 16-byte rows per surface query (include/rptr_hip.h)");
+
 struct RenderStats { // librender/render_backend.h:15-24
     float render_time = 0;
     float rays_per_second = 0;
@@ -367,6 +369,27 @@ public:
         check(rptr_hip_set_params(h_, &render_params, nullptr, nullptr));
         const RptrCamera cam = to_abi(camera);
         check(rptr_hip_trace_radiance(h_, queries, num_queries, &cam, variant_idx, samples_per_query, first_sample, results4, nullptr));
+        return true;
+    }
+    // Surface queries (include/rptr_hip.h rptr_hip_trace_surface): one RptrSurfaceHit per query -- position, normals and material at the closest
+    // hit, decoded as the first shade of a frame decodes it for the AOV images; a miss has t = -1. `camera` supplies the image-plane axes of the
+    // texture footprint, render_params become the handle's (pixel_radius sizes the footprint). Over the query buffer of enable_ray_queries
+    // into a DEVICE buffer of the caller's, asynchronously on `hip_stream` (nullptr: the backend's) ...
+    bool render_surface_queries(int num_queries, const RptrRenderParams &render_params, int variant_idx, const RenderCameraParams &camera, RptrSurfaceHit *device_results,
+                                void *hip_stream = nullptr) {
+        if (!ray_query_buffer_) return false;
+        check(rptr_hip_set_params(h_, &render_params, nullptr, nullptr));
+        const RptrCamera cam = to_abi(camera);
+        check(rptr_hip_trace_surface_device(h_, nullptr, num_queries, &cam, variant_idx, device_results, hip_stream));
+        return true;
+    }
+    // ... and over HOST arrays, synchronously (results is read as well as written: the slots of skipped queries are preserved)
+    bool render_surface_queries(const RptrRenderRayQuery *queries, int num_queries, const RptrRenderParams &render_params, int variant_idx, const RenderCameraParams &camera,
+                                RptrSurfaceHit *results) {
+        if (num_queries < 0) return false;
+        check(rptr_hip_set_params(h_, &render_params, nullptr, nullptr));
+        const RptrCamera cam = to_abi(camera);
+        check(rptr_hip_trace_surface(h_, queries, num_queries, &cam, variant_idx, results));
         return true;
     }
     // convenience over HOST arrays (tests, tools): rptr_hip_trace uploads, traces, reads back
