@@ -4,6 +4,7 @@ brute force finds; the encoding must be conservative and structurally sound."""
 import numpy as np
 import pytest
 
+import bvh_check
 import oracle_lib as O
 from realtimepathtracingresearchframework_amd import backend, scenes
 
@@ -86,57 +87,20 @@ def test_trees_with_split_references_still_equal_brute_force(scene_fn, lo, hi, f
 
 
 def test_encoded_boxes_contain_their_subtrees_and_the_tree_is_sound():
+    """tests/bvh_check.py on the height field: every stored plane holds the exact float bounds of the three vertices of everything below
+    it with ZERO tolerance, origin and exponent are the encoder's for those bounds, every plane lies within 2 grid steps (+ one float
+    spacing) of what it bounds, every triangle record is in exactly one leaf and is its vertices bit for bit, every node is reached
+    exactly once, and the traversal stack the builder reports covers the tree"""
     s = scenes.grid(40, 20)
-    nodes_f, tris_f, insts_f, _ = backend.build_bvh_host(s)
-    nodes = nodes_f.view(NODE_DT)
-    tris = tris_f.view(TRI_DT)
-    n_tlas = 1  # one instance -> one top-level node
-    step = np.ldexp(1.0, nodes["exp"].astype(np.int32) - 127)  # (n, 3)
-
-    def child_box(i, k):
-        lo = nodes["origin"][i].astype(np.float64) + nodes["qlo"][i][:, k] * step[i]
-        hi = nodes["origin"][i].astype(np.float64) + nodes["qhi"][i][:, k] * step[i]
-        return lo, hi
-
-    seen_tris = np.zeros(len(tris), np.int32)
-    seen_nodes = np.zeros(len(nodes), np.int32)
-
-    def bounds(i):
-        """exact float bounds of the triangles below node i; checks every child box on the way"""
-        seen_nodes[i] += 1
-        lo_all, hi_all = np.full(3, np.inf), np.full(3, -np.inf)
-        for k in range(4):
-            c = nodes["child"][i][k]
-            if c == EMPTY:
-                assert (nodes["qlo"][i][:, k] == 255).all() and (nodes["qhi"][i][:, k] == 0).all()
-                continue
-            if c >= 0:
-                lo, hi = bounds(int(c))
-            else:
-                v = -2 - int(c)
-                first, count = v >> 3, v & 7
-                assert 1 <= count <= 4
-                seen_tris[first:first + count] += 1
-                t = tris[first:first + count]
-                p = np.stack([t["v0"], t["v0"] + t["e1"], t["v0"] + t["e2"]]).astype(np.float64).reshape(-1, 3)
-                lo, hi = p.min(axis=0), p.max(axis=0)
-            blo, bhi = child_box(i, k)
-            # the stored planes never cut into the child (1e-6 relative: e1/e2 are rounded differences)
-            tol = 1e-5 * (1.0 + np.abs(hi).max())
-            assert (blo <= lo + tol).all() and (bhi >= hi - tol).all()
-            # and stay within 2 grid steps of it: the compression is tight
-            assert (lo - blo <= 2.01 * step[i] + tol).all() and (bhi - hi <= 2.01 * step[i] + tol).all()
-            lo_all, hi_all = np.minimum(lo_all, lo), np.maximum(hi_all, hi)
-        return lo_all, hi_all
-
-    import sys
-    sys.setrecursionlimit(10000)
-    bounds(n_tlas)  # the mesh root follows the top level
-    assert (seen_tris == 1).all()                      # every triangle in exactly one leaf
-    assert (seen_nodes[n_tlas:] == 1).all()            # every bottom-level node reached exactly once
-    assert len(tris) == s.num_tris()
-    # top level: one leaf with the one instance
-    top = nodes[0]["child"]
+    nodes_f, tris_f, insts_f, need = backend.build_bvh_host(s)
+    rep = bvh_check.check_bvh(nodes_f, tris_f, insts_f, s, stack_bound=need)
+    print("worst slack %.6f grid steps, %d nodes, stack %d of %d" % (rep["worst_slack_steps"], rep["nodes_reached"], rep["stack_entries"], need))
+    assert rep["worst_slack_steps"] < 2.0                                  # the compression is tight
+    assert rep["triangles"] == s.num_tris() == len(tris_f) // 12           # every triangle, in exactly one leaf (rule triangle-once)
+    assert rep["nodes_reached"] == rep["nodes"] == len(nodes_f) // 16 and rep["unreached_nodes"] == 0   # every node reached exactly once
+    # top level: one node with one leaf that names the one instance
+    assert rep["tlas_nodes"] == 1 and rep["top_records"] == 1 and rep["mesh_roots"] == [1]
+    top = nodes_f.view(NODE_DT)[0]["child"]
     assert (top != EMPTY).sum() == 1 and (-2 - int(top[top != EMPTY][0])) == (0 << 3 | 1)
 
 
