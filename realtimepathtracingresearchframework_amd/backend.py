@@ -422,11 +422,24 @@ class RenderHip:
     def enable_ray_queries(self, max_queries=512 * 512, max_queries_per_pixel=0):
         self._max_queries = max_queries
 
+    @staticmethod
+    def _query_rows(queries):
+        """the contiguous (n, 8) float32 view of RenderRayQuery[n]"""
+        return np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, 8)
+
+    @staticmethod
+    def _result_rows(results, n, dtype, row=(), who="", what=""):
+        """`results` when it can hold n rows of shape `row` and type `dtype` (ValueError "<who>: results must be <what>" otherwise), zeros when None"""
+        if results is None:
+            return np.zeros((n,) + row, dtype=dtype)
+        if results.dtype != dtype or not results.flags["C_CONTIGUOUS"] or results.size < n * int(np.prod(row, dtype=np.int64)):
+            raise ValueError("%s: results must be %s" % (who, what))
+        return results
+
     def render_ray_queries(self, queries: np.ndarray, results: np.ndarray = None):
         """queries: (n,8) float32 view of RenderRayQuery[n]; returns (n,4) float32 in rt_intersect layout."""
-        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, 8)
-        if results is None:
-            results = np.zeros((len(q), 4), dtype=np.float32)
+        q = self._query_rows(queries)
+        results = self._result_rows(results, len(q), np.float32, (4,), "render_ray_queries", "a C-contiguous float32 array of n x 4")
         self._check(self._L.rptr_hip_trace(self._h, q.ctypes.data_as(C.c_void_p), len(q), results.ctypes.data_as(C.c_void_p)))
         return results
 
@@ -449,11 +462,8 @@ class RenderHip:
         Returns (n,4) float32 = (radiance.rgb, alpha): the running mean over samples first_sample .. first_sample + spp - 1, folded into
         `results` (read for first_sample > 0 and for the slots of queries with mode_or_data < 0, which stay as they are). The frame in
         progress is left alone; the run's ray counts: radiance_query_stats()."""
-        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, 8)
-        if results is None:
-            results = np.zeros((len(q), 4), dtype=np.float32)
-        if results.dtype != np.float32 or not results.flags["C_CONTIGUOUS"] or results.size < 4 * len(q):
-            raise ValueError("render_radiance_queries: results must be a C-contiguous float32 array of n x 4")
+        q = self._query_rows(queries)
+        results = self._result_rows(results, len(q), np.float32, (4,), "render_radiance_queries", "a C-contiguous float32 array of n x 4")
         self._push_params()
         st = abi.Stats()
         self._check(self._L.rptr_hip_trace_radiance(self._h, q.ctypes.data_as(C.c_void_p), len(q), C.byref(camera), int(variant), int(spp), int(first_sample),
@@ -481,11 +491,8 @@ class RenderHip:
         """queries: (n,8) float32 view of RenderRayQuery[n]; camera: abi.Camera (its image-plane axes size the texture footprint).
         Returns n records of abi.SURFACE_HIT_DTYPE, written into `results` when given (read too: the slots of queries with
         mode_or_data < 0 stay as they are). A miss has t = -1. The frame in progress is left alone."""
-        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, 8)
-        if results is None:
-            results = np.zeros(len(q), dtype=abi.SURFACE_HIT_DTYPE)
-        if results.dtype != abi.SURFACE_HIT_DTYPE or not results.flags["C_CONTIGUOUS"] or results.size < len(q):
-            raise ValueError("render_surface_queries: results must be a C-contiguous array of n abi.SURFACE_HIT_DTYPE records")
+        q = self._query_rows(queries)
+        results = self._result_rows(results, len(q), abi.SURFACE_HIT_DTYPE, (), "render_surface_queries", "a C-contiguous array of n abi.SURFACE_HIT_DTYPE records")
         self._push_params()
         self._check(self._L.rptr_hip_trace_surface(self._h, q.ctypes.data_as(C.c_void_p), len(q), C.byref(camera), int(variant), results.ctypes.data_as(C.c_void_p)))
         return results
@@ -504,9 +511,9 @@ class RenderHip:
     def trace_counted(self, queries: np.ndarray, tmin: np.ndarray = None, any_hit=False):
         """diagnostic: (results (n,4) float32, visits (n,2) uint32 = nodes, triangles per query); tmin: explicit interval
         starts; any_hit: the shadow-ray traversal (results[:,0] = 1 if occluded)."""
-        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, 8)
-        results = np.zeros((len(q), 4), dtype=np.float32)
-        visits = np.zeros((len(q), 2), dtype=np.uint32)
+        q = self._query_rows(queries)
+        results = self._result_rows(None, len(q), np.float32, (4,))
+        visits = self._result_rows(None, len(q), np.uint32, (2,))
         tm = None if tmin is None else np.ascontiguousarray(tmin, dtype=np.float32)
         self._check(self._L.rptr_hip_trace_counted(self._h, q.ctypes.data_as(C.c_void_p), len(q), results.ctypes.data_as(C.c_void_p),
                                                    visits.ctypes.data_as(C.c_void_p), None if tm is None else tm.ctypes.data_as(C.c_void_p),

@@ -1,7 +1,7 @@
 // host_access.inl -- everything else a host reaches through the handle: BVH policy, freeze frame, point sets, stage timing, the option calls, frame buffer / tile /
-// AOV read-backs (last_finished_image: which image they mean), the denoiser, ray queries (rptr_hip_trace*: closest hits, and path-traced radiance), the exported tree
+// AOV read-backs (last_finished_image: which image they mean), the denoiser, the exported tree (ray queries: host_queries.inl)
 // Part of the ONE translation unit rptr_hip.hip (included there, in this order: host_state.h, host_bvh.inl, host_scene.inl,
-// host_frame.inl, host_access.inl, host_comm.h): the host runtime split along its seams; no symbol changed.
+// host_frame.inl, host_access.inl, host_queries.inl, host_comm.h): the host runtime split along its seams; no symbol changed.
 int rptr_hip_set_bvh_policy(rptr_hip_t *h, int force_bvh_rebuild, int rebuild_triangle_budget) {
     if (!h) return fail(nullptr, RPTR_E_INVALID, "NULL handle");
     if (rebuild_triangle_budget < 0) return fail(h, RPTR_E_INVALID, "rebuild_triangle_budget must be >= 0");
@@ -336,315 +336,6 @@ int rptr_hip_readback_denoised_u8(rptr_hip_t *h, unsigned char *rgba, size_t n_b
     if (!h || !rgba) return fail(h, RPTR_E_INVALID, "NULL argument");
     const int rc = check_denoised(h);
     return rc ? rc : readback_rows<uchar4>(h, h->dn.out_u8, reinterpret_cast<uchar4 *>(rgba), n_bytes / 4);
-}
-
-int rptr_hip_trace(rptr_hip_t *h, const RptrRenderRayQuery *queries, int n, float *out4) {
-    return rptr_hip_trace_counted(h, queries, n, out4, nullptr, nullptr, 0);
-}
-
-int rptr_hip_trace_counted(rptr_hip_t *h, const RptrRenderRayQuery *queries, int n, float *out4, uint32_t *visits2, const float *tmin, int any_hit) {
-    if (!h || !queries || !out4 || n < 0) return fail(h, RPTR_E_INVALID, "bad argument");
-    if (!h->have_scene) return fail(h, RPTR_E_INVALID, "trace before set_scene");
-    if (!h->ctx[0].gstack) return fail(h, RPTR_E_INVALID, "trace before initialize");
-    {
-        int rc0 = drain(h); // the query kernel borrows context 0's cursor and stack scratch
-        if (rc0) return rc0;
-        if ((rc0 = ensure_master_tree(h))) return rc0;
-    }
-    if (n == 0) return RPTR_OK;
-    HIP_TRY(h, hipSetDevice(h->device));
-    RptrRenderRayQuery *dq = nullptr;
-    float4 *dr = nullptr;
-    uint2 *dv = nullptr;
-    float *dt = nullptr;
-    HIP_TRY(h, hipMalloc((void **)&dq, (size_t)n * sizeof(RptrRenderRayQuery)));
-    if (hipMalloc((void **)&dr, (size_t)n * sizeof(float4)) != hipSuccess || (visits2 && hipMalloc((void **)&dv, (size_t)n * sizeof(uint2)) != hipSuccess) ||
-        (tmin && hipMalloc((void **)&dt, (size_t)n * sizeof(float)) != hipSuccess)) {
-        (void)hipFree(dq);
-        (void)hipFree(dr);
-        (void)hipFree(dv);
-        return fail(h, RPTR_E_NOMEM, "hipMalloc failed");
-    }
-    int rc = RPTR_OK;
-    do {
-        if (hipMemcpyAsync(dq, queries, (size_t)n * sizeof(RptrRenderRayQuery), hipMemcpyHostToDevice, h->stream) != hipSuccess ||
-            hipMemcpyAsync(dr, out4, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, h->stream) != hipSuccess ||
-            (tmin && hipMemcpyAsync(dt, tmin, (size_t)n * sizeof(float), hipMemcpyHostToDevice, h->stream) != hipSuccess)) {
-            rc = fail(h, RPTR_E_HIP, "upload failed");
-            break;
-        }
-        // cursor_extend doubles as the pool cursor of the query kernel (same stream, no overlap with a frame)
-        hipLaunchKernelGGL(rp_k_reset_u32, dim3(1), dim3(1), 0, h->stream, &h->ctx[0].counters->bounce[0].cursor_extend);
-        auto launch = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, dim3(h->persistent_blocks), dim3(RP_TRAVERSE_BLOCK), 0, h->stream, h->master.dscene, dq, (uint32_t)n, dr,
-                               &h->ctx[0].counters->bounce[0].cursor_extend, h->ctx[0].gstack, dv, dt);
-        };
-        rp_pick(h->master.dscene.single_instance != 0, [&](auto S) {
-            if (any_hit)
-                launch(rp_k_trace<true, true, decltype(S)::value>);
-            else if (visits2)
-                launch(rp_k_trace<true, false, decltype(S)::value>);
-            else
-                launch(rp_k_trace<false, false, decltype(S)::value>);
-        });
-        if ((visits2 && hipMemcpyAsync(visits2, dv, (size_t)n * sizeof(uint2), hipMemcpyDeviceToHost, h->stream) != hipSuccess) ||
-            hipMemcpyAsync(out4, dr, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-            hipStreamSynchronize(h->stream) != hipSuccess || hipGetLastError() != hipSuccess) {
-            rc = fail(h, RPTR_E_HIP, "trace kernel failed");
-            break;
-        }
-    } while (0);
-    (void)hipFree(dq);
-    (void)hipFree(dr);
-    (void)hipFree(dv);
-    (void)hipFree(dt);
-    return rc;
-}
-
-extern "C++" {
-// the RQ_CLOSEST kernel over DEVICE buffers, asynchronously on `st`
-static int trace_device_on(rptr_hip *h, const RptrRenderRayQuery *dq, int n, float4 *dr, hipStream_t st) {
-    if (n == 0) return RPTR_OK;
-    hipLaunchKernelGGL(rp_k_reset_u32, dim3(1), dim3(1), 0, st, &h->ctx[0].counters->bounce[0].cursor_extend);
-    rp_pick(h->master.dscene.single_instance != 0, [&](auto S) {
-        hipLaunchKernelGGL((rp_k_trace<false, false, decltype(S)::value>), dim3(h->persistent_blocks), dim3(RP_TRAVERSE_BLOCK), 0, st, h->master.dscene, dq, (uint32_t)n, dr,
-                           &h->ctx[0].counters->bounce[0].cursor_extend, h->ctx[0].gstack, (uint2 *)nullptr, (const float *)nullptr);
-    });
-    HIP_TRY(h, hipGetLastError());
-    return RPTR_OK;
-}
-// queue(st) on the stream the caller named (NULL: the backend's). A stream of the caller's sees the scene uploads / refits queued on the
-// backend's, and later frames see what was queued
-template <class F>
-static int on_callers_stream(rptr_hip *h, void *hip_stream, F &&queue) {
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : h->stream;
-    if (st == h->stream) return queue(st);
-    hipEvent_t e;
-    HIP_TRY(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    (void)hipEventRecord(e, h->stream);
-    (void)hipStreamWaitEvent(st, e, 0);
-    const int rc = queue(st);
-    (void)hipEventRecord(e, st);
-    (void)hipStreamWaitEvent(h->stream, e, 0);
-    (void)hipEventDestroy(e);
-    return rc;
-}
-}
-
-int rptr_hip_trace_device(rptr_hip_t *h, const RptrRenderRayQuery *device_queries, int n, float *device_out4, void *hip_stream) {
-    if (!h || !device_queries || !device_out4 || n < 0) return fail(h, RPTR_E_INVALID, "bad argument");
-    if (!h->have_scene) return fail(h, RPTR_E_INVALID, "trace before set_scene");
-    if (!h->ctx[0].gstack) return fail(h, RPTR_E_INVALID, "trace before initialize");
-    int rc = drain(h); // the query kernel borrows context 0's cursor and stack scratch
-    if (rc || (rc = ensure_master_tree(h))) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    return on_callers_stream(h, hip_stream, [&](hipStream_t st) { return trace_device_on(h, device_queries, n, reinterpret_cast<float4 *>(device_out4), st); });
-}
-
-int rptr_hip_enable_ray_queries(rptr_hip_t *h, int max_queries, int max_queries_per_pixel, void **out_device_queries, void **out_device_results) {
-    if (!h || max_queries < 0 || max_queries_per_pixel < 0) return fail(h, RPTR_E_INVALID, "bad argument");
-    HIP_TRY(h, hipSetDevice(h->device));
-    // vulkan/render_vulkan.cpp:430-455: max(fixed budget, per-pixel budget x frame size) queries of 32 bytes, as many float4 results
-    const size_t want = std::max<size_t>((size_t)max_queries, (size_t)h->width * (size_t)h->height * (size_t)max_queries_per_pixel);
-    if (want > h->rq_capacity) {
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        if (h->rq_queries) (void)hipFree(h->rq_queries);
-        if (h->rq_results) (void)hipFree(h->rq_results);
-        h->rq_queries = nullptr;
-        h->rq_results = nullptr;
-        h->rq_capacity = 0;
-        if (hipMalloc((void **)&h->rq_queries, want * sizeof(RptrRenderRayQuery)) != hipSuccess || hipMalloc((void **)&h->rq_results, want * sizeof(float4)) != hipSuccess) {
-            if (h->rq_queries) (void)hipFree(h->rq_queries);
-            h->rq_queries = nullptr;
-            return fail(h, RPTR_E_NOMEM, "hipMalloc of the ray query buffers (%zu queries) failed", want);
-        }
-        h->rq_capacity = want;
-    }
-    if (out_device_queries) *out_device_queries = h->rq_queries;
-    if (out_device_results) *out_device_results = h->rq_results;
-    return RPTR_OK;
-}
-
-int rptr_hip_render_ray_queries(rptr_hip_t *h, int num_queries) {
-    if (!h || num_queries < 0) return fail(h, RPTR_E_INVALID, "bad argument");
-    if ((size_t)num_queries > h->rq_capacity) return fail(h, RPTR_E_INVALID, "%d ray queries exceed the budget of %zu (rptr_hip_enable_ray_queries)", num_queries, h->rq_capacity);
-    return rptr_hip_trace_device(h, h->rq_queries, num_queries, reinterpret_cast<float *>(h->rq_results), nullptr);
-}
-
-// ---- radiance queries: the path-tracing variants of RenderBackend::render_ray_queries (host_frame.inl radiance_queries_on)
-int rptr_hip_trace_radiance(rptr_hip_t *h, const RptrRenderRayQuery *queries, int n, const RptrCamera *camera, int variant, int samples_per_query, int first_sample,
-                            float *out4, RptrStats *out_stats) {
-    int rc = check_radiance_arguments(h, queries, n, camera, variant, samples_per_query, first_sample, out4);
-    if (rc) return rc;
-    if ((rc = drain(h)) || (rc = ensure_master_tree(h))) return rc; // the run borrows context 0
-    if (out_stats) memset(out_stats, 0, sizeof(*out_stats));
-    if (n == 0) return RPTR_OK;
-    HIP_TRY(h, hipSetDevice(h->device));
-    RptrRenderRayQuery *dq = nullptr;
-    float4 *dr = nullptr;
-    if (hipMalloc((void **)&dq, (size_t)n * sizeof(RptrRenderRayQuery)) != hipSuccess || hipMalloc((void **)&dr, (size_t)n * sizeof(float4)) != hipSuccess) {
-        (void)hipFree(dq);
-        return fail(h, RPTR_E_NOMEM, "hipMalloc failed");
-    }
-    RpCounters tot;
-    memset(&tot, 0, sizeof(tot));
-    do {
-        // (the results go up whatever first_sample is: slots of skipped queries keep what the caller put there)
-        if (hipMemcpyAsync(dq, queries, (size_t)n * sizeof(RptrRenderRayQuery), hipMemcpyHostToDevice, h->stream) != hipSuccess ||
-            hipMemcpyAsync(dr, out4, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, h->stream) != hipSuccess) {
-            rc = fail(h, RPTR_E_HIP, "upload failed");
-            break;
-        }
-        if ((rc = radiance_queries_on(h, dq, n, camera, variant, samples_per_query, first_sample, dr, h->stream, &tot))) break;
-        if (hipMemcpyAsync(out4, dr, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost, h->stream) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess ||
-            hipGetLastError() != hipSuccess) {
-            rc = fail(h, RPTR_E_HIP, "radiance query kernels failed");
-            break;
-        }
-    } while (0);
-    if (rc) (void)hipStreamSynchronize(h->stream); // nothing of the run may still use the buffers freed below
-    (void)hipFree(dq);
-    (void)hipFree(dr);
-    if (!rc && out_stats) {
-        out_stats->rays_closest = tot.rays_closest;
-        out_stats->rays_shadow = tot.rays_shadow;
-        out_stats->hits_shaded = tot.hits_shaded;
-        out_stats->spp = first_sample + samples_per_query;
-        out_stats->device_bytes_allocated = h->bytes_allocated;
-    }
-    return rc;
-}
-
-int rptr_hip_trace_radiance_device(rptr_hip_t *h, const RptrRenderRayQuery *device_queries, int n, const RptrCamera *camera, int variant, int samples_per_query,
-                                   int first_sample, float *device_out4, void *hip_stream) {
-    int rc = check_radiance_arguments(h, device_queries, n, camera, variant, samples_per_query, first_sample, device_out4);
-    if (rc) return rc;
-    if ((rc = drain(h)) || (rc = ensure_master_tree(h))) return rc; // the run borrows context 0
-    HIP_TRY(h, hipSetDevice(h->device));
-    return on_callers_stream(h, hip_stream, [&](hipStream_t st) {
-        return radiance_queries_on(h, device_queries, n, camera, variant, samples_per_query, first_sample, reinterpret_cast<float4 *>(device_out4), st, nullptr);
-    });
-}
-
-int rptr_hip_render_radiance_queries(rptr_hip_t *h, int num_queries, const RptrCamera *camera, int variant, int samples_per_query, int first_sample) {
-    if (!h || num_queries < 0) return fail(h, RPTR_E_INVALID, "bad argument");
-    if ((size_t)num_queries > h->rq_capacity) return fail(h, RPTR_E_INVALID, "%d ray queries exceed the budget of %zu (rptr_hip_enable_ray_queries)", num_queries, h->rq_capacity);
-    return rptr_hip_trace_radiance_device(h, h->rq_queries, num_queries, camera, variant, samples_per_query, first_sample, reinterpret_cast<float *>(h->rq_results), nullptr);
-}
-
-// ---- surface queries (surface_query.h): the raw closest hits into the handle's scratch, then the decode into RptrSurfaceHit records
-extern "C++" {
-// (the argument checks come first: they need neither a handle nor a device)
-static int check_surface_arguments(rptr_hip_t *h, bool have_queries, int n, const RptrCamera *camera, int variant, const void *out) {
-    if (!camera) return fail(h, RPTR_E_INVALID, "surface queries: NULL camera (its image-plane axes size the texture footprint)");
-    if (n < 0) return fail(h, RPTR_E_INVALID, "surface queries: n must be >= 0");
-    if (!have_queries || !out) return fail(h, RPTR_E_INVALID, "surface queries: NULL query or output buffer");
-    if (variant != RPTR_VARIANT_GLTF && variant != RPTR_VARIANT_SIMPLE && variant != RPTR_VARIANT_GLTF_TRANSMISSION)
-        return fail(h, RPTR_E_INVALID, "surface queries: unknown variant %d", variant);
-    if (!h) return fail(nullptr, RPTR_E_INVALID, "NULL handle");
-    if (!h->have_scene) return fail(h, RPTR_E_INVALID, "surface queries before set_scene");
-    if (h->width == 0 || h->ctx.empty() || !h->ctx[0].gstack) return fail(h, RPTR_E_INVALID, "surface queries before initialize");
-    if (h->world > 1) return fail(h, RPTR_E_UNSUPPORTED, "surface queries need world_size 1: queries are not striped over the ranks");
-    return RPTR_OK;
-}
-// the scratch holds the largest n seen: a run of no more queries than an earlier one allocates nothing
-static int surface_scratch(rptr_hip_t *h, int n) {
-    if ((size_t)n <= h->sq_capacity) return RPTR_OK;
-    HIP_TRY(h, hipStreamSynchronize(h->stream)); // (an earlier run -- on a caller's stream too: the backend's is ordered behind it -- may still use the old one)
-    if (h->sq_raw) (void)hipFree(h->sq_raw);
-    h->sq_raw = nullptr;
-    h->sq_capacity = 0;
-    if (hipMalloc(&h->sq_raw, (size_t)n * sizeof(RpRawHit)) != hipSuccess) {
-        h->sq_raw = nullptr;
-        return fail(h, RPTR_E_NOMEM, "hipMalloc of the surface-query scratch (%d queries) failed", n);
-    }
-    h->sq_capacity = (size_t)n;
-    return RPTR_OK;
-}
-// Queues the two launches on `st` for DEVICE buffers. The caller has drained the frames in flight: the traversal borrows context 0's cursor
-// and stack scratch, nothing a frame owns is written.
-static int surface_queries_on(rptr_hip_t *h, const RptrRenderRayQuery *dq, int n, const RptrCamera *camera, int variant, RptrSurfaceHit *dout, hipStream_t st) {
-    if (n == 0) return RPTR_OK;
-    RpFrame view;
-    compute_view(*camera, h->width, h->height, view);
-    RpSurfaceFrame f;
-    memset(&f, 0, sizeof(f));
-    memcpy(f.cam_du, view.cam_du, sizeof(f.cam_du));
-    memcpy(f.cam_dv, view.cam_dv, sizeof(f.cam_dv));
-    f.width = h->width;
-    f.height = h->height;
-    f.pixel_radius = h->params.pixel_radius;
-    f.normal_z_scale = h->scene_params.normal_z_scale;
-    RpRawHit *raw = static_cast<RpRawHit *>(h->sq_raw);
-    const RpScene &sc = h->master.dscene;
-    // cursor_extend doubles as the pool cursor of the traversal (as for rp_k_trace: no overlap with a frame)
-    uint32_t *cursor = &h->ctx[0].counters->bounce[0].cursor_extend;
-    hipLaunchKernelGGL(rp_k_reset_u32, dim3(1), dim3(1), 0, st, cursor);
-    rp_pick(sc.single_instance != 0, [&](auto S) {
-        hipLaunchKernelGGL((rp_k_trace_surface<decltype(S)::value>), dim3(h->persistent_blocks), dim3(RP_TRAVERSE_BLOCK), 0, st, sc, dq, (uint32_t)n, raw, cursor, h->ctx[0].gstack);
-    });
-    // TEX as the frame's kernels select theirs: no material of the scene reads a texture -> the instantiation without sampling code
-    const dim3 grid((unsigned)grid_for(h, (size_t)n));
-    rp_pick(h->uses_textures, [&](auto T) {
-        constexpr bool tex = decltype(T)::value;
-        if (variant == RPTR_VARIANT_SIMPLE)
-            hipLaunchKernelGGL((rp_k_surface<RPTR_VARIANT_SIMPLE, tex>), grid, dim3(256), 0, st, sc, f, dq, (const RpRawHit *)raw, (uint32_t)n, dout);
-        else if (variant == RPTR_VARIANT_GLTF_TRANSMISSION)
-            hipLaunchKernelGGL((rp_k_surface<RPTR_VARIANT_GLTF_TRANSMISSION, tex>), grid, dim3(256), 0, st, sc, f, dq, (const RpRawHit *)raw, (uint32_t)n, dout);
-        else
-            hipLaunchKernelGGL((rp_k_surface<RPTR_VARIANT_GLTF, tex>), grid, dim3(256), 0, st, sc, f, dq, (const RpRawHit *)raw, (uint32_t)n, dout);
-    });
-    HIP_TRY(h, hipGetLastError());
-    return RPTR_OK;
-}
-}
-
-int rptr_hip_trace_surface(rptr_hip_t *h, const RptrRenderRayQuery *queries, int n, const RptrCamera *camera, int variant, RptrSurfaceHit *out) {
-    int rc = check_surface_arguments(h, queries != nullptr, n, camera, variant, out);
-    if (rc) return rc;
-    if ((rc = drain(h)) || (rc = ensure_master_tree(h))) return rc; // the traversal borrows context 0's cursor and stack scratch
-    if (n == 0) return RPTR_OK;
-    HIP_TRY(h, hipSetDevice(h->device));
-    if ((rc = surface_scratch(h, n))) return rc;
-    RptrRenderRayQuery *dq = nullptr;
-    RptrSurfaceHit *dout = nullptr;
-    if (hipMalloc((void **)&dq, (size_t)n * sizeof(RptrRenderRayQuery)) != hipSuccess || hipMalloc((void **)&dout, (size_t)n * sizeof(RptrSurfaceHit)) != hipSuccess) {
-        (void)hipFree(dq);
-        return fail(h, RPTR_E_NOMEM, "hipMalloc failed");
-    }
-    do {
-        // (the records go up too: slots of skipped queries keep what the caller put there)
-        if (hipMemcpyAsync(dq, queries, (size_t)n * sizeof(RptrRenderRayQuery), hipMemcpyHostToDevice, h->stream) != hipSuccess ||
-            hipMemcpyAsync(dout, out, (size_t)n * sizeof(RptrSurfaceHit), hipMemcpyHostToDevice, h->stream) != hipSuccess) {
-            rc = fail(h, RPTR_E_HIP, "upload failed");
-            break;
-        }
-        if ((rc = surface_queries_on(h, dq, n, camera, variant, dout, h->stream))) break;
-        if (hipMemcpyAsync(out, dout, (size_t)n * sizeof(RptrSurfaceHit), hipMemcpyDeviceToHost, h->stream) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess ||
-            hipGetLastError() != hipSuccess) {
-            rc = fail(h, RPTR_E_HIP, "surface query kernels failed");
-            break;
-        }
-    } while (0);
-    if (rc) (void)hipStreamSynchronize(h->stream); // nothing of the run may still use the buffers freed below
-    (void)hipFree(dq);
-    (void)hipFree(dout);
-    return rc;
-}
-
-int rptr_hip_trace_surface_device(rptr_hip_t *h, const RptrRenderRayQuery *device_queries, int n, const RptrCamera *camera, int variant, RptrSurfaceHit *device_out,
-                                  void *hip_stream) {
-    int rc = check_surface_arguments(h, true, n, camera, variant, device_out);
-    if (rc) return rc;
-    if (!device_queries) { // the query buffer of rptr_hip_enable_ray_queries
-        if ((size_t)n > h->rq_capacity) return fail(h, RPTR_E_INVALID, "%d ray queries exceed the budget of %zu (rptr_hip_enable_ray_queries)", n, h->rq_capacity);
-        device_queries = h->rq_queries;
-    }
-    if ((rc = drain(h)) || (rc = ensure_master_tree(h))) return rc; // the traversal borrows context 0's cursor and stack scratch
-    if (n == 0) return RPTR_OK;
-    HIP_TRY(h, hipSetDevice(h->device));
-    if ((rc = surface_scratch(h, n))) return rc;
-    return on_callers_stream(h, hip_stream, [&](hipStream_t st) { return surface_queries_on(h, device_queries, n, camera, variant, device_out, st); });
 }
 
 int rptr_hip_set_light_sampling_variant(rptr_hip_t *h, int variant) {

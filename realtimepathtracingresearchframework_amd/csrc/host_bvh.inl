@@ -1,7 +1,7 @@
 // host_bvh.inl -- the acceleration structure's host side (rptr_hip_set_scene's first half; no device needed except for the device builder):
 // scene validation, per-mesh binned-SAH trees / the device's PLOC builder, the top level, flattening, the 4-wide collapse and encoding
 // Part of the ONE translation unit rptr_hip.hip (included there, in this order: host_state.h, host_bvh.inl, host_scene.inl,
-// host_frame.inl, host_access.inl, host_comm.h): the host runtime split along its seams; no symbol changed.
+// host_frame.inl, host_access.inl, host_queries.inl, host_comm.h): the host runtime split along its seams; no symbol changed.
 extern "C++" {
 // ------------------------------------------------------------------ host side of the acceleration structure
 // Everything of set_scene that needs no device: per-mesh binned-SAH trees from the dequantised triangles, the

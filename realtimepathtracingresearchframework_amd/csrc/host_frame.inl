@@ -2,7 +2,7 @@
 // stages, for frames and for radiance-query runs), submitting a launch sequence (render_batch_impl and its steps), radiance-query runs
 // (radiance_queries_on), collecting a frame (finish_frame), wait / render / stats
 // Part of the ONE translation unit rptr_hip.hip (included there, in this order: host_state.h, host_bvh.inl, host_scene.inl,
-// host_frame.inl, host_access.inl, host_comm.h): the host runtime split along its seams; no symbol changed.
+// host_frame.inl, host_access.inl, host_queries.inl, host_comm.h): the host runtime split along its seams; no symbol changed.
 // host part of a3: vulkan/render_vulkan.cpp:2880-2896
 static void cross3(const float a[3], const float b[3], float o[3]) {
     o[0] = a[1] * b[2] - b[1] * a[2];
@@ -660,25 +660,9 @@ static int render_batch_impl(rptr_hip_t *h, const RptrCamera *camera, bool per_f
 extern "C++" {
 // ---- radiance queries (kernels.h RpQueries): the path pipeline on the rays of a query buffer instead of the camera's
 // (RenderBackend::render_ray_queries with a path-tracing variant: render_vulkan.cpp:1867-1876, 2961-3059)
-static int check_radiance_arguments(rptr_hip_t *h, const void *queries, int n, const RptrCamera *camera, int variant, int samples_per_query, int first_sample,
-                                    const void *out4) {
-    if (!h) return fail(nullptr, RPTR_E_INVALID, "NULL handle");
-    if (!camera) return fail(h, RPTR_E_INVALID, "radiance queries: NULL camera (its image-plane axes size the texture footprint)");
-    if (n < 0) return fail(h, RPTR_E_INVALID, "radiance queries: n must be >= 0");
-    if (n > 0 && (!queries || !out4)) return fail(h, RPTR_E_INVALID, "radiance queries: NULL query or result buffer");
-    if (!h->have_scene) return fail(h, RPTR_E_INVALID, "radiance queries before set_scene");
-    if (h->width == 0 || h->ctx.empty() || !h->ctx[0].gstack) return fail(h, RPTR_E_INVALID, "radiance queries before initialize");
-    if (variant != RPTR_VARIANT_GLTF && variant != RPTR_VARIANT_SIMPLE && variant != RPTR_VARIANT_GLTF_TRANSMISSION)
-        return fail(h, RPTR_E_INVALID, "unknown variant %d", variant);
-    if (samples_per_query < 1) return fail(h, RPTR_E_INVALID, "samples_per_query must be >= 1");
-    if (first_sample < 0) return fail(h, RPTR_E_INVALID, "first_sample must be >= 0");
-    if ((long long)first_sample + samples_per_query > 0x7fffffffll) return fail(h, RPTR_E_INVALID, "first_sample + samples_per_query overflows");
-    if (h->world > 1) return fail(h, RPTR_E_UNSUPPORTED, "radiance queries need world_size 1: queries are not striped over the ranks");
-    return RPTR_OK;
-}
-// Queues the run on `st` for DEVICE buffers. The caller has drained the frames in flight: the run borrows context 0's path state, queues,
-// counters and stack scratch, and leaves everything a frame owns alone (accumulation and frame buffers, AOV images, frame_id, frame_offset,
-// the previous view, the last frame's statistics and hand-over bounce).
+// Queues the run on `st` for DEVICE buffers. The caller has begun a query run (host_queries.inl begin_query_run: what is borrowed from
+// context 0); everything a frame owns is left alone (accumulation and frame buffers, AOV images, frame_id, frame_offset, the previous view,
+// the last frame's statistics and hand-over bounce).
 // The virtual image (width = the frame's, query q = pixel (q mod W, q div W)) is walked in slices of at most the frame's rows, the samples
 // of a slice in batches of at most the context's sample slots; a path's result is a function of its query and sample index alone, so
 // neither shows in the results. Sample s runs as a one-sample frame at that point of the accumulation would: sample_index = frame_id =

@@ -1,0 +1,298 @@
+// host_queries.inl -- ray queries, three kinds behind eight entry points: closest hits (rptr_hip_trace, _trace_counted, _trace_device,
+// _render_ray_queries), path-traced radiance (rptr_hip_trace_radiance, _trace_radiance_device, _render_radiance_queries; the run itself is
+// host_frame.inl radiance_queries_on) and surface records (rptr_hip_trace_surface, _trace_surface_device). What the kinds share stands
+// here once: the run preamble, the borrowed pool cursor, the staging of host arrays, the budget of the backend's own buffers, the checks.
+// Part of the ONE translation unit rptr_hip.hip (included there after host_access.inl).
+extern "C++" {
+// A query run borrows context 0 and nothing a frame owns: the traversals take its stack scratch and, as their pool cursor, its
+// counters->bounce[0].cursor_extend (borrowed_cursor); a radiance run takes its path state, queues and counters as well. So the frames in
+// flight are drained first, and a run never overlaps a frame. Every entry point starts here, after its argument checks.
+static int begin_query_run(rptr_hip *h) {
+    int rc = drain(h);
+    if (rc || (rc = ensure_master_tree(h))) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    return RPTR_OK;
+}
+// the pool cursor of a traversal over queries, set to zero on `st` ahead of the launch that follows
+static uint32_t *borrowed_cursor(rptr_hip *h, hipStream_t st) {
+    uint32_t *cursor = &h->ctx[0].counters->bounce[0].cursor_extend;
+    hipLaunchKernelGGL(rp_k_reset_u32, dim3(1), dim3(1), 0, st, cursor);
+    return cursor;
+}
+// the device buffers of rptr_hip_enable_ray_queries hold rq_capacity queries and results
+static int check_query_budget(rptr_hip *h, int n) {
+    if ((size_t)n > h->rq_capacity) return fail(h, RPTR_E_INVALID, "%d ray queries exceed the budget of %zu (rptr_hip_enable_ray_queries)", n, h->rq_capacity);
+    return RPTR_OK;
+}
+// queue(st) on the stream the caller named (NULL: the backend's). A stream of the caller's sees the scene uploads / refits queued on the
+// backend's, and later frames see what was queued
+template <class F>
+static int on_callers_stream(rptr_hip *h, void *hip_stream, F &&queue) {
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : h->stream;
+    if (st == h->stream) return queue(st);
+    hipEvent_t e;
+    HIP_TRY(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    (void)hipEventRecord(e, h->stream);
+    (void)hipStreamWaitEvent(st, e, 0);
+    const int rc = queue(st);
+    (void)hipEventRecord(e, st);
+    (void)hipStreamWaitEvent(h->stream, e, 0);
+    (void)hipEventDestroy(e);
+    return rc;
+}
+// Host arrays of a run: every span gets a device copy, the SPAN_UP ones are uploaded, queue(stream, spans) queues the run on the backend's
+// stream (spans[i].dev: the copies), the SPAN_DOWN ones come back and the stream is waited for. Results go both ways: the slots of
+// skipped queries keep what the caller put there. A span without a host pointer is an optional array left out: its dev stays NULL.
+enum { SPAN_UP = 1, SPAN_DOWN = 2 };
+struct HostSpan {
+    void *host;
+    size_t bytes;
+    int dir;
+    void *dev;
+};
+template <class F>
+static int run_on_host_arrays(rptr_hip *h, const char *what, HostSpan *spans, int count, F &&queue) {
+    int rc = RPTR_OK;
+    for (int i = 0; i < count && !rc; ++i)
+        if (spans[i].host && hipMalloc(&spans[i].dev, spans[i].bytes) != hipSuccess) {
+            spans[i].dev = nullptr;
+            rc = fail(h, RPTR_E_NOMEM, "hipMalloc failed");
+        }
+    for (int i = 0; i < count && !rc; ++i)
+        if (spans[i].dev && (spans[i].dir & SPAN_UP) && hipMemcpyAsync(spans[i].dev, spans[i].host, spans[i].bytes, hipMemcpyHostToDevice, h->stream) != hipSuccess)
+            rc = fail(h, RPTR_E_HIP, "upload failed");
+    if (!rc) rc = queue(h->stream, spans);
+    if (!rc) {
+        bool ok = true;
+        for (int i = 0; i < count && ok; ++i)
+            if (spans[i].dev && (spans[i].dir & SPAN_DOWN)) ok = hipMemcpyAsync(spans[i].host, spans[i].dev, spans[i].bytes, hipMemcpyDeviceToHost, h->stream) == hipSuccess;
+        if (!ok || hipStreamSynchronize(h->stream) != hipSuccess || hipGetLastError() != hipSuccess) rc = fail(h, RPTR_E_HIP, "%s failed", what);
+    }
+    if (rc) (void)hipStreamSynchronize(h->stream); // nothing of the run may still use the buffers freed below
+    for (int i = 0; i < count; ++i) (void)hipFree(spans[i].dev);
+    return rc;
+}
+
+// ---- closest hits (RQ_CLOSEST): rp_k_trace over DEVICE buffers, asynchronously on `st`. dv != NULL: nodes and triangles visited per query;
+// dt != NULL: explicit interval starts; any_hit: the shadow-ray traversal
+static int closest_queries_on(rptr_hip *h, const RptrRenderRayQuery *dq, int n, float4 *dr, hipStream_t st, uint2 *dv, const float *dt, bool any_hit) {
+    if (n == 0) return RPTR_OK;
+    uint32_t *cursor = borrowed_cursor(h, st);
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(h->persistent_blocks), dim3(RP_TRAVERSE_BLOCK), 0, st, h->master.dscene, dq, (uint32_t)n, dr, cursor, h->ctx[0].gstack, dv, dt);
+    };
+    rp_pick(h->master.dscene.single_instance != 0, [&](auto S) {
+        if (any_hit)
+            launch(rp_k_trace<true, true, decltype(S)::value>);
+        else if (dv)
+            launch(rp_k_trace<true, false, decltype(S)::value>);
+        else
+            launch(rp_k_trace<false, false, decltype(S)::value>);
+    });
+    HIP_TRY(h, hipGetLastError());
+    return RPTR_OK;
+}
+static int check_closest_arguments(rptr_hip *h, const void *queries, int n, const void *out4) {
+    if (!h || !queries || !out4 || n < 0) return fail(h, RPTR_E_INVALID, "bad argument");
+    if (!h->have_scene) return fail(h, RPTR_E_INVALID, "trace before set_scene");
+    if (!h->ctx[0].gstack) return fail(h, RPTR_E_INVALID, "trace before initialize");
+    return RPTR_OK;
+}
+} // extern "C++"
+
+int rptr_hip_trace(rptr_hip_t *h, const RptrRenderRayQuery *queries, int n, float *out4) {
+    return rptr_hip_trace_counted(h, queries, n, out4, nullptr, nullptr, 0);
+}
+
+int rptr_hip_trace_counted(rptr_hip_t *h, const RptrRenderRayQuery *queries, int n, float *out4, uint32_t *visits2, const float *tmin, int any_hit) {
+    int rc = check_closest_arguments(h, queries, n, out4);
+    if (rc || (rc = begin_query_run(h)) || n == 0) return rc;
+    HostSpan spans[4] = {{const_cast<RptrRenderRayQuery *>(queries), (size_t)n * sizeof(RptrRenderRayQuery), SPAN_UP, nullptr},
+                         {out4, (size_t)n * sizeof(float4), SPAN_UP | SPAN_DOWN, nullptr},
+                         {visits2, (size_t)n * sizeof(uint2), SPAN_DOWN, nullptr},
+                         {const_cast<float *>(tmin), (size_t)n * sizeof(float), SPAN_UP, nullptr}};
+    return run_on_host_arrays(h, "trace kernel", spans, 4, [&](hipStream_t st, const HostSpan *s) {
+        return closest_queries_on(h, (const RptrRenderRayQuery *)s[0].dev, n, (float4 *)s[1].dev, st, (uint2 *)s[2].dev, (const float *)s[3].dev, any_hit != 0);
+    });
+}
+
+int rptr_hip_trace_device(rptr_hip_t *h, const RptrRenderRayQuery *device_queries, int n, float *device_out4, void *hip_stream) {
+    int rc = check_closest_arguments(h, device_queries, n, device_out4);
+    if (rc || (rc = begin_query_run(h))) return rc;
+    return on_callers_stream(h, hip_stream, [&](hipStream_t st) {
+        return closest_queries_on(h, device_queries, n, reinterpret_cast<float4 *>(device_out4), st, nullptr, nullptr, false);
+    });
+}
+
+int rptr_hip_enable_ray_queries(rptr_hip_t *h, int max_queries, int max_queries_per_pixel, void **out_device_queries, void **out_device_results) {
+    if (!h || max_queries < 0 || max_queries_per_pixel < 0) return fail(h, RPTR_E_INVALID, "bad argument");
+    HIP_TRY(h, hipSetDevice(h->device));
+    // vulkan/render_vulkan.cpp:430-455: max(fixed budget, per-pixel budget x frame size) queries of 32 bytes, as many float4 results
+    const size_t want = std::max<size_t>((size_t)max_queries, (size_t)h->width * (size_t)h->height * (size_t)max_queries_per_pixel);
+    if (want > h->rq_capacity) {
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        if (h->rq_queries) (void)hipFree(h->rq_queries);
+        if (h->rq_results) (void)hipFree(h->rq_results);
+        h->rq_queries = nullptr;
+        h->rq_results = nullptr;
+        h->rq_capacity = 0;
+        if (hipMalloc((void **)&h->rq_queries, want * sizeof(RptrRenderRayQuery)) != hipSuccess || hipMalloc((void **)&h->rq_results, want * sizeof(float4)) != hipSuccess) {
+            if (h->rq_queries) (void)hipFree(h->rq_queries);
+            h->rq_queries = nullptr;
+            return fail(h, RPTR_E_NOMEM, "hipMalloc of the ray query buffers (%zu queries) failed", want);
+        }
+        h->rq_capacity = want;
+    }
+    if (out_device_queries) *out_device_queries = h->rq_queries;
+    if (out_device_results) *out_device_results = h->rq_results;
+    return RPTR_OK;
+}
+
+int rptr_hip_render_ray_queries(rptr_hip_t *h, int num_queries) {
+    if (!h || num_queries < 0) return fail(h, RPTR_E_INVALID, "bad argument");
+    const int rc = check_query_budget(h, num_queries);
+    return rc ? rc : rptr_hip_trace_device(h, h->rq_queries, num_queries, reinterpret_cast<float *>(h->rq_results), nullptr);
+}
+
+extern "C++" {
+// ---- the kinds that take a camera and a variant (radiance, surface). The arguments come first: they need neither a handle nor a device.
+// missing_buffer: the kind's own rule, NULL when its buffers pass, else what to call the fault
+static int check_camera_queries(rptr_hip_t *h, const char *kind, int n, const RptrCamera *camera, int variant, const char *missing_buffer) {
+    if (!camera) return fail(h, RPTR_E_INVALID, "%s: NULL camera (its image-plane axes size the texture footprint)", kind);
+    if (n < 0) return fail(h, RPTR_E_INVALID, "%s: n must be >= 0", kind);
+    if (missing_buffer) return fail(h, RPTR_E_INVALID, "%s: %s", kind, missing_buffer);
+    if (variant != RPTR_VARIANT_GLTF && variant != RPTR_VARIANT_SIMPLE && variant != RPTR_VARIANT_GLTF_TRANSMISSION)
+        return fail(h, RPTR_E_INVALID, "%s: unknown variant %d", kind, variant);
+    if (!h) return fail(nullptr, RPTR_E_INVALID, "NULL handle");
+    if (!h->have_scene) return fail(h, RPTR_E_INVALID, "%s before set_scene", kind);
+    if (h->width == 0 || h->ctx.empty() || !h->ctx[0].gstack) return fail(h, RPTR_E_INVALID, "%s before initialize", kind);
+    if (h->world > 1) return fail(h, RPTR_E_UNSUPPORTED, "%s need world_size 1: queries are not striped over the ranks", kind);
+    return RPTR_OK;
+}
+
+// ---- radiance queries: the path-tracing variants of RenderBackend::render_ray_queries (host_frame.inl radiance_queries_on;
+// render_vulkan.cpp:1867-1876, 2961-3059). NULL buffers pass when there is nothing to trace.
+static int check_radiance_arguments(rptr_hip_t *h, const void *queries, int n, const RptrCamera *camera, int variant, int samples_per_query, int first_sample,
+                                    const void *out4) {
+    if (samples_per_query < 1) return fail(h, RPTR_E_INVALID, "samples_per_query must be >= 1");
+    if (first_sample < 0) return fail(h, RPTR_E_INVALID, "first_sample must be >= 0");
+    if ((long long)first_sample + samples_per_query > 0x7fffffffll) return fail(h, RPTR_E_INVALID, "first_sample + samples_per_query overflows");
+    return check_camera_queries(h, "radiance queries", n, camera, variant, n > 0 && (!queries || !out4) ? "NULL query or result buffer" : nullptr);
+}
+} // extern "C++"
+
+int rptr_hip_trace_radiance(rptr_hip_t *h, const RptrRenderRayQuery *queries, int n, const RptrCamera *camera, int variant, int samples_per_query, int first_sample,
+                            float *out4, RptrStats *out_stats) {
+    int rc = check_radiance_arguments(h, queries, n, camera, variant, samples_per_query, first_sample, out4);
+    if (rc || (rc = begin_query_run(h))) return rc;
+    if (out_stats) memset(out_stats, 0, sizeof(*out_stats));
+    if (n == 0) return RPTR_OK;
+    RpCounters tot;
+    memset(&tot, 0, sizeof(tot));
+    HostSpan spans[2] = {{const_cast<RptrRenderRayQuery *>(queries), (size_t)n * sizeof(RptrRenderRayQuery), SPAN_UP, nullptr},
+                         {out4, (size_t)n * sizeof(float4), SPAN_UP | SPAN_DOWN, nullptr}}; // (up whatever first_sample is: the old means, and the skipped slots)
+    rc = run_on_host_arrays(h, "radiance query kernels", spans, 2, [&](hipStream_t st, const HostSpan *s) {
+        return radiance_queries_on(h, (const RptrRenderRayQuery *)s[0].dev, n, camera, variant, samples_per_query, first_sample, (float4 *)s[1].dev, st, &tot);
+    });
+    if (!rc && out_stats) {
+        out_stats->rays_closest = tot.rays_closest;
+        out_stats->rays_shadow = tot.rays_shadow;
+        out_stats->hits_shaded = tot.hits_shaded;
+        out_stats->spp = first_sample + samples_per_query;
+        out_stats->device_bytes_allocated = h->bytes_allocated;
+    }
+    return rc;
+}
+
+int rptr_hip_trace_radiance_device(rptr_hip_t *h, const RptrRenderRayQuery *device_queries, int n, const RptrCamera *camera, int variant, int samples_per_query,
+                                   int first_sample, float *device_out4, void *hip_stream) {
+    int rc = check_radiance_arguments(h, device_queries, n, camera, variant, samples_per_query, first_sample, device_out4);
+    if (rc || (rc = begin_query_run(h))) return rc;
+    return on_callers_stream(h, hip_stream, [&](hipStream_t st) {
+        return radiance_queries_on(h, device_queries, n, camera, variant, samples_per_query, first_sample, reinterpret_cast<float4 *>(device_out4), st, nullptr);
+    });
+}
+
+int rptr_hip_render_radiance_queries(rptr_hip_t *h, int num_queries, const RptrCamera *camera, int variant, int samples_per_query, int first_sample) {
+    if (!h || num_queries < 0) return fail(h, RPTR_E_INVALID, "bad argument");
+    const int rc = check_query_budget(h, num_queries);
+    return rc ? rc
+              : rptr_hip_trace_radiance_device(h, h->rq_queries, num_queries, camera, variant, samples_per_query, first_sample, reinterpret_cast<float *>(h->rq_results), nullptr);
+}
+
+// ---- surface queries (surface_query.h): the raw closest hits into the handle's scratch, then the decode into RptrSurfaceHit records.
+// NULL buffers never pass.
+extern "C++" {
+static int check_surface_arguments(rptr_hip_t *h, bool have_queries, int n, const RptrCamera *camera, int variant, const void *out) {
+    return check_camera_queries(h, "surface queries", n, camera, variant, !have_queries || !out ? "NULL query or output buffer" : nullptr);
+}
+// the scratch holds the largest n seen: a run of no more queries than an earlier one allocates nothing
+static int surface_scratch(rptr_hip_t *h, int n) {
+    if ((size_t)n <= h->sq_capacity) return RPTR_OK;
+    HIP_TRY(h, hipStreamSynchronize(h->stream)); // (an earlier run -- on a caller's stream too: the backend's is ordered behind it -- may still use the old one)
+    if (h->sq_raw) (void)hipFree(h->sq_raw);
+    h->sq_raw = nullptr;
+    h->sq_capacity = 0;
+    if (hipMalloc(&h->sq_raw, (size_t)n * sizeof(RpRawHit)) != hipSuccess) {
+        h->sq_raw = nullptr;
+        return fail(h, RPTR_E_NOMEM, "hipMalloc of the surface-query scratch (%d queries) failed", n);
+    }
+    h->sq_capacity = (size_t)n;
+    return RPTR_OK;
+}
+// queues the two launches on `st` for DEVICE buffers
+static int surface_queries_on(rptr_hip_t *h, const RptrRenderRayQuery *dq, int n, const RptrCamera *camera, int variant, RptrSurfaceHit *dout, hipStream_t st) {
+    if (n == 0) return RPTR_OK;
+    RpFrame view;
+    compute_view(*camera, h->width, h->height, view);
+    RpSurfaceFrame f;
+    memset(&f, 0, sizeof(f));
+    memcpy(f.cam_du, view.cam_du, sizeof(f.cam_du));
+    memcpy(f.cam_dv, view.cam_dv, sizeof(f.cam_dv));
+    f.width = h->width;
+    f.height = h->height;
+    f.pixel_radius = h->params.pixel_radius;
+    f.normal_z_scale = h->scene_params.normal_z_scale;
+    RpRawHit *raw = static_cast<RpRawHit *>(h->sq_raw);
+    const RpScene &sc = h->master.dscene;
+    uint32_t *cursor = borrowed_cursor(h, st);
+    rp_pick(sc.single_instance != 0, [&](auto S) {
+        hipLaunchKernelGGL((rp_k_trace_surface<decltype(S)::value>), dim3(h->persistent_blocks), dim3(RP_TRAVERSE_BLOCK), 0, st, sc, dq, (uint32_t)n, raw, cursor, h->ctx[0].gstack);
+    });
+    // TEX as the frame's kernels select theirs: no material of the scene reads a texture -> the instantiation without sampling code
+    const dim3 grid((unsigned)grid_for(h, (size_t)n));
+    rp_pick(h->uses_textures, [&](auto T) {
+        constexpr bool tex = decltype(T)::value;
+        if (variant == RPTR_VARIANT_SIMPLE)
+            hipLaunchKernelGGL((rp_k_surface<RPTR_VARIANT_SIMPLE, tex>), grid, dim3(256), 0, st, sc, f, dq, (const RpRawHit *)raw, (uint32_t)n, dout);
+        else if (variant == RPTR_VARIANT_GLTF_TRANSMISSION)
+            hipLaunchKernelGGL((rp_k_surface<RPTR_VARIANT_GLTF_TRANSMISSION, tex>), grid, dim3(256), 0, st, sc, f, dq, (const RpRawHit *)raw, (uint32_t)n, dout);
+        else
+            hipLaunchKernelGGL((rp_k_surface<RPTR_VARIANT_GLTF, tex>), grid, dim3(256), 0, st, sc, f, dq, (const RpRawHit *)raw, (uint32_t)n, dout);
+    });
+    HIP_TRY(h, hipGetLastError());
+    return RPTR_OK;
+}
+}
+
+int rptr_hip_trace_surface(rptr_hip_t *h, const RptrRenderRayQuery *queries, int n, const RptrCamera *camera, int variant, RptrSurfaceHit *out) {
+    int rc = check_surface_arguments(h, queries != nullptr, n, camera, variant, out);
+    if (rc || (rc = begin_query_run(h)) || n == 0 || (rc = surface_scratch(h, n))) return rc;
+    HostSpan spans[2] = {{const_cast<RptrRenderRayQuery *>(queries), (size_t)n * sizeof(RptrRenderRayQuery), SPAN_UP, nullptr},
+                         {out, (size_t)n * sizeof(RptrSurfaceHit), SPAN_UP | SPAN_DOWN, nullptr}};
+    return run_on_host_arrays(h, "surface query kernels", spans, 2, [&](hipStream_t st, const HostSpan *s) {
+        return surface_queries_on(h, (const RptrRenderRayQuery *)s[0].dev, n, camera, variant, (RptrSurfaceHit *)s[1].dev, st);
+    });
+}
+
+int rptr_hip_trace_surface_device(rptr_hip_t *h, const RptrRenderRayQuery *device_queries, int n, const RptrCamera *camera, int variant, RptrSurfaceHit *device_out,
+                                  void *hip_stream) {
+    int rc = check_surface_arguments(h, true, n, camera, variant, device_out);
+    if (rc) return rc;
+    if (!device_queries) { // the query buffer of rptr_hip_enable_ray_queries
+        if ((rc = check_query_budget(h, n))) return rc;
+        device_queries = h->rq_queries;
+    }
+    if ((rc = begin_query_run(h)) || n == 0 || (rc = surface_scratch(h, n))) return rc;
+    return on_callers_stream(h, hip_stream, [&](hipStream_t st) { return surface_queries_on(h, device_queries, n, camera, variant, device_out, st); });
+}

@@ -1,7 +1,7 @@
 // host_scene.inl -- rptr_hip_set_scene (static uploads, tree, refit tables, then every scene copy -- the master's and the frame contexts' --
 // through scene_copy_build), vertex and instance updates, refit and the device rebuilds (one front half: lbvh_front_half)
 // Part of the ONE translation unit rptr_hip.hip (included there, in this order: host_state.h, host_bvh.inl, host_scene.inl,
-// host_frame.inl, host_access.inl, host_comm.h): the host runtime split along its seams; no symbol changed.
+// host_frame.inl, host_access.inl, host_queries.inl, host_comm.h): the host runtime split along its seams; no symbol changed.
 // ---- set_scene, step by step (each returns RPTR_OK or the error it reported through fail())
 // what the reference host rejects or this build does not cover yet; sets uses_textures / uses_alpha
 static int scene_validate(rptr_hip *h, const RptrSceneDesc *s) {

@@ -1,7 +1,7 @@
 // host_state.h -- what every part of the host runtime shares: the handle (rptr_hip), frame contexts, scene copies, the option table and its
 // process defaults, error reporting, device allocation and upload (dev_alloc / dev_upload), the hardware-queue note
 // Part of the ONE translation unit rptr_hip.hip (included there, in this order: host_state.h, host_bvh.inl, host_scene.inl,
-// host_frame.inl, host_access.inl, host_comm.h): the host runtime split along its seams; no symbol changed.
+// host_frame.inl, host_access.inl, host_queries.inl, host_comm.h): the host runtime split along its seams; no symbol changed.
 #pragma once
 namespace {
 

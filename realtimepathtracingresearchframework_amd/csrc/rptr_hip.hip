@@ -370,6 +370,7 @@ int rptr_hip_set_params(rptr_hip_t *h, const RptrRenderParams *params, const Rpt
 #include "host_scene.inl"
 #include "host_frame.inl"
 #include "host_access.inl"
+#include "host_queries.inl"
 
 } // extern "C"
 
