@@ -818,6 +818,43 @@ typedef struct RptrSurfaceHit {
 int rptr_hip_trace_surface(rptr_hip_t *h, const RptrRenderRayQuery *queries, int n, const RptrCamera *camera, int variant, RptrSurfaceHit *out);
 int rptr_hip_trace_surface_device(rptr_hip_t *h, const RptrRenderRayQuery *device_queries, int n, const RptrCamera *camera, int variant,
                                   RptrSurfaceHit *device_out, void *hip_stream);
+/* ---- occlusion queries: is anything between these two points? One bit per query
+ * The any-hit query of line-of-sight, shadow, visibility and ambient-occlusion probes and of light baking: the traversal of a frame's
+ * shadow rays (it stops at the first accepted hit) over query records, with the result packed 32 queries to a word. No reference
+ * counterpart: the reference's registry has the closest-hit program RQ_CLOSEST only.
+ *   Interval   query q is occluded when some triangle of the scene intersects its ray in (t_min, t_max), t_min = RPTR_RAY_EPSILON *
+ *              |origin| (the RQ_CLOSEST rule of rptr_hip_trace), `dir` used as given: a point-to-point test from a to b is origin = a,
+ *              dir = b - a, t_max = 1.
+ *   Result     bit (q & 31) of word (q >> 5) of out_bits, 1 = occluded; the buffer holds ceil(n / 32) words. A query with
+ *              mode_or_data < 0 leaves its bit as the caller had it (the convention of every other kind), and so do the bits >= n of
+ *              the last word: the host form uploads out_bits as well as downloading it, the device form merges into the words it finds.
+ *   Opaque     flags == 0: every triangle occludes, alpha-tested geometry included, as for rptr_hip_trace. The answer equals
+ *              out4[4*q] != 0 of rptr_hip_trace_counted with tmin = NULL and any_hit = 1.
+ *   Cutout     RPTR_OCCLUSION_ALPHA_CUTOUT: a candidate hit is ignored when its material lacks RPTR_BASE_MATERIAL_NOALPHA and its alpha is
+ *              < alpha_cutoff. The alpha is the one a frame's alpha test compares: level 0 of the base-colour texture at the candidate's
+ *              interpolated uv, 1 for a literal colour. Deterministic: no random number is drawn (a frame's test is stochastic for
+ *              fractional alpha), so the same query gives the same bit in every run, and raising the cutoff never occludes a clear ray.
+ * Both forms trace the scene copy rptr_hip_trace traces (after update_vertices / update_instances and rptr_hip_refit: the moved geometry),
+ * wait for the frames in flight and leave the accumulation, frame and AOV images, frame_id / frame_offset, the histories, the denoised
+ * images and rptr_hip_stats alone. world_size > 1 is allowed, as for rptr_hip_trace: every rank holds the whole scene.
+ * rptr_hip_occlusion_defaults: flags 0, alpha_cutoff 0.5, reserved 0.
+ * rptr_hip_trace_occlusion: host arrays, synchronous. params NULL = the defaults.
+ * rptr_hip_trace_occlusion_device: DEVICE buffers, asynchronously on `hip_stream` (NULL: the backend's stream), ordered as
+ * rptr_hip_trace_device; device_queries == NULL: the query buffer of rptr_hip_enable_ray_queries (more than its budget: RPTR_E_INVALID).
+ * NULL handle, NULL query or result pointer with n > 0, n < 0, reserved != 0, unknown flag bits, with the cutout flag a cutoff that is not
+ * finite or outside (0, 1], before set_scene / initialize: RPTR_E_INVALID (the argument checks come before the device is touched).
+ * n == 0 succeeds and touches nothing. */
+#define RPTR_OCCLUSION_ALPHA_CUTOUT 1u
+typedef struct RptrOcclusionParams { /* 16 bytes */
+    uint32_t flags;       /* RPTR_OCCLUSION_*; 0: every triangle is opaque, as for rptr_hip_trace */
+    float alpha_cutoff;   /* read with ALPHA_CUTOUT only: 0 < cutoff <= 1, finite; default 0.5 */
+    uint32_t reserved[2]; /* must be 0 */
+} RptrOcclusionParams;
+void rptr_hip_occlusion_defaults(RptrOcclusionParams *out);
+int rptr_hip_trace_occlusion(rptr_hip_t *h, const RptrRenderRayQuery *queries, int n, const RptrOcclusionParams *params /* NULL = defaults */,
+                             uint32_t *out_bits);
+int rptr_hip_trace_occlusion_device(rptr_hip_t *h, const RptrRenderRayQuery *device_queries /* NULL: the buffer of rptr_hip_enable_ray_queries */,
+                                    int n, const RptrOcclusionParams *params, uint32_t *device_out_bits, void *hip_stream);
 /* RenderBackendOptions::light_sampling_variant (rendering/mc/light_sampling.h:11-20, rendering/mc/nee.glsl:12-14): 0 =
  * LIGHT_SAMPLING_VARIANT_NONE disables next-event estimation towards the emissive triangles (every NEE sample goes to the sun; emitters
  * that a path HITS still contribute, at full weight), 1 = LIGHT_SAMPLING_VARIANT_RIS (the default: binned RIS). The image is that of

@@ -75,6 +75,10 @@ def load_library(path=None):
     L.rptr_hip_render_radiance_queries.argtypes = [vp, i32, C.POINTER(abi.Camera), i32, i32, i32]
     L.rptr_hip_trace_surface.argtypes = [vp, vp, i32, C.POINTER(abi.Camera), i32, vp]
     L.rptr_hip_trace_surface_device.argtypes = [vp, vp, i32, C.POINTER(abi.Camera), i32, vp, vp]
+    L.rptr_hip_occlusion_defaults.argtypes = [C.POINTER(abi.OcclusionParams)]
+    L.rptr_hip_occlusion_defaults.restype = None
+    L.rptr_hip_trace_occlusion.argtypes = [vp, vp, i32, C.POINTER(abi.OcclusionParams), vp]
+    L.rptr_hip_trace_occlusion_device.argtypes = [vp, vp, i32, C.POINTER(abi.OcclusionParams), vp, vp]
     L.rptr_hip_set_light_sampling_variant.argtypes = [vp, i32]
     L.rptr_hip_set_freeze_frame.argtypes = [vp, i32]
     L.rptr_hip_set_option.argtypes = [vp, C.c_char_p, C.c_int64]
@@ -503,6 +507,53 @@ class RenderHip:
         self._push_params()
         self._check(self._L.rptr_hip_trace_surface_device(self._h, C.c_void_p(device_queries or 0), int(num_queries), C.byref(camera), int(variant),
                                                           C.c_void_p(device_results or 0), C.c_void_p(stream or 0)))
+
+    # ---- occlusion queries: one bit per query (include/rptr_hip.h rptr_hip_trace_occlusion)
+    @staticmethod
+    def pack_occlusion_bits(occluded) -> np.ndarray:
+        """n bools -> ceil(n / 32) uint32 words, query q in bit q & 31 of word q >> 5 (little-endian bit order)"""
+        b = np.ascontiguousarray(occluded, dtype=bool).reshape(-1)
+        return np.packbits(np.concatenate([b, np.zeros(-len(b) % 32, bool)]), bitorder="little").view("<u4").astype(np.uint32)
+
+    @staticmethod
+    def unpack_occlusion_bits(words, n) -> np.ndarray:
+        """the first n bits of uint32 words as bools"""
+        w = np.ascontiguousarray(words, dtype=np.uint32).astype("<u4")
+        return np.unpackbits(w.view(np.uint8), bitorder="little")[:n].astype(bool)
+
+    def _occlusion_params(self, alpha_cutoff):
+        p = abi.OcclusionParams()
+        self._L.rptr_hip_occlusion_defaults(C.byref(p))
+        if alpha_cutoff is not None:
+            p.flags = abi.OCCLUSION_ALPHA_CUTOUT
+            p.alpha_cutoff = float(alpha_cutoff)
+        return p
+
+    def render_occlusion_queries(self, queries: np.ndarray, alpha_cutoff=None, results: np.ndarray = None) -> np.ndarray:
+        """queries: (n,8) float32 view of RenderRayQuery[n]. Returns n bools, True = something lies on the ray inside (t_min, t_max).
+        alpha_cutoff None: every triangle is opaque; a number in (0, 1]: alpha-tested candidates with alpha below it are ignored.
+        `results` (n bools), when given, supplies the answers of queries with mode_or_data < 0 -- they stay as they are -- and receives
+        all of them."""
+        q = self._query_rows(queries)
+        n = len(q)
+        if results is not None and (results.dtype != np.bool_ or results.shape != (n,)):
+            raise ValueError("render_occlusion_queries: results must be a bool array of shape (n,)")
+        words = self.pack_occlusion_bits(np.zeros(n, bool) if results is None else results)
+        p = self._occlusion_params(alpha_cutoff)
+        self._check(self._L.rptr_hip_trace_occlusion(self._h, q.ctypes.data_as(C.c_void_p), n, C.byref(p), words.ctypes.data_as(C.c_void_p)))
+        out = self.unpack_occlusion_bits(words, n)
+        if results is None:
+            return out
+        results[...] = out
+        return results
+
+    def render_occlusion_queries_device(self, num_queries, alpha_cutoff=None, device_queries=None, device_bits=None, stream=None):
+        """the same over DEVICE buffers, asynchronously on `stream` (None = the backend's): device_bits names ceil(num_queries / 32)
+        uint32 words, merged into (skipped queries and the bits behind num_queries keep theirs); device_queries None = the query buffer of
+        enable_ray_queries_device"""
+        p = self._occlusion_params(alpha_cutoff)
+        self._check(self._L.rptr_hip_trace_occlusion_device(self._h, C.c_void_p(device_queries or 0), int(num_queries), C.byref(p), C.c_void_p(device_bits or 0),
+                                                            C.c_void_p(stream or 0)))
 
     def set_light_sampling_variant(self, variant):
         """RenderBackendOptions::light_sampling_variant: 0 = NONE (no NEE towards emissive triangles), 1 = RIS (default)"""

@@ -801,6 +801,19 @@ RP_DEV bool rp_alpha_rejects(const RpScene &sc, int inst_idx, int geom, int prim
     if (!(alpha > 0.0f)) return true;
     return alpha < 1.0f && rp_randf(rng) > alpha;
 }
+// The cutout rule of occlusion queries (occlusion_query.h; include/rptr_hip.h RPTR_OCCLUSION_ALPHA_CUTOUT): the same alpha -- level 0 of the
+// base-colour texture at the candidate's uv, 1 for a literal colour -- against a fixed threshold. true = the candidate is ignored. No
+// random number: the answer depends on the ray and the scene alone.
+RP_DEV bool rp_alpha_below_cutoff(const RpScene &sc, int inst_idx, int geom, int prim, float bu, float bv, float cutoff) {
+    const int geometry_base = reinterpret_cast<const int *>(sc.insts + inst_idx)[13]; // RptrBvhInstance::geometry_base
+    const RpGeomRecord &g = sc.geoms[geometry_base + geom];
+    const RptrBaseMaterial &m = sc.materials[rp_hit_material_id(g, uint32_t(prim))];
+    if ((m.flags & RPTR_BASE_MATERIAL_NOALPHA) != 0u) return false;
+    const uint32_t mask = __float_as_uint(m.base_color[0]);
+    float alpha = 1.0f;
+    if (mask & RPTR_TEXTURED_PARAM_MASK) alpha = rp_texture_lod0(sc, int(RPTR_TEXTURE_ID(mask)), rp_hit_uv(g, uint32_t(prim), bu, bv)).w;
+    return alpha < cutoff;
+}
 // rendering/rt/material_textures.glsl:95-135 (non-unrolled standard textures: a parameter is a literal or a texture handle;
 // PREMULTIPLIED_BASE_COLOR_ALPHA is defined, vulkan/gpu_params.glsl:12)
 template <int VARIANT, bool TEX>

@@ -1,7 +1,8 @@
-// host_queries.inl -- ray queries, three kinds behind eight entry points: closest hits (rptr_hip_trace, _trace_counted, _trace_device,
+// host_queries.inl -- ray queries, four kinds behind ten entry points: closest hits (rptr_hip_trace, _trace_counted, _trace_device,
 // _render_ray_queries), path-traced radiance (rptr_hip_trace_radiance, _trace_radiance_device, _render_radiance_queries; the run itself is
-// host_frame.inl radiance_queries_on) and surface records (rptr_hip_trace_surface, _trace_surface_device). What the kinds share stands
-// here once: the run preamble, the borrowed pool cursor, the staging of host arrays, the budget of the backend's own buffers, the checks.
+// host_frame.inl radiance_queries_on), surface records (rptr_hip_trace_surface, _trace_surface_device) and occlusion bits
+// (rptr_hip_trace_occlusion, _trace_occlusion_device). What the kinds share stands here once: the run preamble, the borrowed pool cursor,
+// the staging of host arrays, the budget of the backend's own buffers, the checks.
 // Part of the ONE translation unit rptr_hip.hip (included there after host_access.inl).
 extern "C++" {
 // A query run borrows context 0 and nothing a frame owns: the traversals take its stack scratch and, as their pool cursor, its
@@ -295,4 +296,76 @@ int rptr_hip_trace_surface_device(rptr_hip_t *h, const RptrRenderRayQuery *devic
     }
     if ((rc = begin_query_run(h)) || n == 0 || (rc = surface_scratch(h, n))) return rc;
     return on_callers_stream(h, hip_stream, [&](hipStream_t st) { return surface_queries_on(h, device_queries, n, camera, variant, device_out, st); });
+}
+
+// ---- occlusion queries (occlusion_query.h): one any-hit traversal, one bit per query merged into the caller's words. NULL buffers pass
+// when there is nothing to trace.
+void rptr_hip_occlusion_defaults(RptrOcclusionParams *out) {
+    if (!out) return;
+    memset(out, 0, sizeof(*out));
+    out->alpha_cutoff = 0.5f;
+}
+
+extern "C++" {
+// the arguments come first: they need neither a handle nor a device. `p` is never NULL here (the entry points pass the defaults)
+static int check_occlusion_arguments(rptr_hip_t *h, bool have_queries, int n, const RptrOcclusionParams &p, const void *bits) {
+    const char *kind = "occlusion queries";
+    if (n < 0) return fail(h, RPTR_E_INVALID, "%s: n must be >= 0", kind);
+    if (n > 0 && (!have_queries || !bits)) return fail(h, RPTR_E_INVALID, "%s: NULL query or result buffer", kind);
+    if (p.reserved[0] != 0u || p.reserved[1] != 0u) return fail(h, RPTR_E_INVALID, "%s: reserved words must be 0", kind);
+    if ((p.flags & ~RPTR_OCCLUSION_ALPHA_CUTOUT) != 0u) return fail(h, RPTR_E_INVALID, "%s: unknown flag bits 0x%x", kind, p.flags & ~RPTR_OCCLUSION_ALPHA_CUTOUT);
+    if ((p.flags & RPTR_OCCLUSION_ALPHA_CUTOUT) != 0u && !(std::isfinite(p.alpha_cutoff) && p.alpha_cutoff > 0.0f && p.alpha_cutoff <= 1.0f))
+        return fail(h, RPTR_E_INVALID, "%s: alpha_cutoff must be finite and in (0, 1]", kind);
+    if (!h) return fail(nullptr, RPTR_E_INVALID, "NULL handle");
+    if (!h->have_scene) return fail(h, RPTR_E_INVALID, "%s before set_scene", kind);
+    if (h->ctx.empty() || !h->ctx[0].gstack) return fail(h, RPTR_E_INVALID, "%s before initialize", kind);
+    return RPTR_OK;
+}
+// queues the launch on `st` for DEVICE buffers. The cutout instantiation only where it can differ: the flag is set AND the scene has
+// alpha-tested materials (what RpFrame::alpha_test is derived from); grids as a frame's shadow-ray launches alone on the GPU choose theirs
+static int occlusion_queries_on(rptr_hip_t *h, const RptrRenderRayQuery *dq, int n, const RptrOcclusionParams &p, uint32_t *bits, hipStream_t st) {
+    if (n == 0) return RPTR_OK;
+    const RpScene &sc = h->master.dscene;
+    const bool cutout = (p.flags & RPTR_OCCLUSION_ALPHA_CUTOUT) != 0u && h->uses_alpha;
+    const float cutoff = p.alpha_cutoff;
+    uint32_t *cursor = borrowed_cursor(h, st);
+    rp_pick(cutout, [&](auto A) {
+        rp_pick(sc.single_instance != 0, [&](auto S) {
+            constexpr bool alpha = decltype(A)::value, single = decltype(S)::value;
+            const int blocks = alpha ? h->persistent_blocks : h->connect_blocks[single ? 1 : 0];
+            hipLaunchKernelGGL((rp_k_trace_occlusion<alpha, single>), dim3(blocks), dim3(RP_TRAVERSE_BLOCK), 0, st, sc, dq, (uint32_t)n, bits, cutoff, cursor, h->ctx[0].gstack);
+        });
+    });
+    HIP_TRY(h, hipGetLastError());
+    return RPTR_OK;
+}
+static RptrOcclusionParams occlusion_params_or_defaults(const RptrOcclusionParams *params) {
+    RptrOcclusionParams p;
+    rptr_hip_occlusion_defaults(&p);
+    return params ? *params : p;
+}
+}
+
+int rptr_hip_trace_occlusion(rptr_hip_t *h, const RptrRenderRayQuery *queries, int n, const RptrOcclusionParams *params, uint32_t *out_bits) {
+    const RptrOcclusionParams p = occlusion_params_or_defaults(params);
+    int rc = check_occlusion_arguments(h, queries != nullptr, n, p, out_bits);
+    if (rc || n == 0 || (rc = begin_query_run(h))) return rc;
+    HostSpan spans[2] = {{const_cast<RptrRenderRayQuery *>(queries), (size_t)n * sizeof(RptrRenderRayQuery), SPAN_UP, nullptr},
+                         {out_bits, ((size_t)n + 31) / 32 * sizeof(uint32_t), SPAN_UP | SPAN_DOWN, nullptr}}; // (up: the bits of skipped queries and those behind n)
+    return run_on_host_arrays(h, "occlusion query kernel", spans, 2, [&](hipStream_t st, const HostSpan *s) {
+        return occlusion_queries_on(h, (const RptrRenderRayQuery *)s[0].dev, n, p, (uint32_t *)s[1].dev, st);
+    });
+}
+
+int rptr_hip_trace_occlusion_device(rptr_hip_t *h, const RptrRenderRayQuery *device_queries, int n, const RptrOcclusionParams *params, uint32_t *device_out_bits,
+                                    void *hip_stream) {
+    const RptrOcclusionParams p = occlusion_params_or_defaults(params);
+    int rc = check_occlusion_arguments(h, true, n, p, device_out_bits);
+    if (rc || n == 0) return rc;
+    if (!device_queries) { // the query buffer of rptr_hip_enable_ray_queries
+        if ((rc = check_query_budget(h, n))) return rc;
+        device_queries = h->rq_queries;
+    }
+    if ((rc = begin_query_run(h))) return rc;
+    return on_callers_stream(h, hip_stream, [&](hipStream_t st) { return occlusion_queries_on(h, device_queries, n, p, device_out_bits, st); });
 }

@@ -12,6 +12,7 @@
 #include "realtime_resolve.h"
 #include "denoise.h"
 #include "surface_query.h"
+#include "occlusion_query.h"
 #include "launch.h"
 #include "lbvh.h"
 #include "tlas_build.h"

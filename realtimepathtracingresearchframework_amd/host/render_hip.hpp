@@ -15,6 +15,7 @@
 
 namespace rptr {
 
+static_assert(sizeof(RptrOcclusionParams) == 16, "RptrOcclusionParams: flags, alpha_cutoff, two reserved words (include/rptr_hip.h)");
 static_assert(sizeof(RptrSurfaceHit) == 96, "RptrSurfaceHit: six 16-byte rows per surface query (include/rptr_hip.h)");
 
 struct RenderStats { // librender/render_backend.h:15-24
@@ -392,6 +393,23 @@ public:
         check(rptr_hip_trace_surface(h_, queries, num_queries, &cam, variant_idx, results));
         return true;
     }
+    // Occlusion queries (include/rptr_hip.h rptr_hip_trace_occlusion): one BIT per query, bit q & 31 of word q >> 5, 1 = something lies on the
+    // ray inside (t_min, t_max). alpha_cutoff <= 0: every triangle is opaque; in (0, 1]: the cutout rule. Skipped queries and the bits behind
+    // num_queries keep what the words held. Over the query buffer of enable_ray_queries into a DEVICE buffer of ceil(num_queries / 32) words
+    // of the caller's, asynchronously on `hip_stream` (nullptr: the backend's) ...
+    bool render_occlusion_queries(int num_queries, uint32_t *device_bits, float alpha_cutoff = 0.0f, void *hip_stream = nullptr) {
+        if (!ray_query_buffer_) return false;
+        const RptrOcclusionParams p = occlusion_params(alpha_cutoff);
+        check(rptr_hip_trace_occlusion_device(h_, nullptr, num_queries, &p, device_bits, hip_stream));
+        return true;
+    }
+    // ... and over HOST arrays, synchronously (bits is read as well as written)
+    bool render_occlusion_queries(const RptrRenderRayQuery *queries, int num_queries, uint32_t *bits, float alpha_cutoff = 0.0f) {
+        if (num_queries < 0) return false;
+        const RptrOcclusionParams p = occlusion_params(alpha_cutoff);
+        check(rptr_hip_trace_occlusion(h_, queries, num_queries, &p, bits));
+        return true;
+    }
     // convenience over HOST arrays (tests, tools): rptr_hip_trace uploads, traces, reads back
     bool render_ray_queries(const RptrRenderRayQuery *queries, int num_queries, float *results4) {
         if (num_queries < 0) return false;
@@ -405,6 +423,15 @@ public:
     rptr_hip_t *handle() { return h_; }
 
 private:
+    static RptrOcclusionParams occlusion_params(float alpha_cutoff) {
+        RptrOcclusionParams p;
+        rptr_hip_occlusion_defaults(&p);
+        if (alpha_cutoff > 0.0f) {
+            p.flags = RPTR_OCCLUSION_ALPHA_CUTOUT;
+            p.alpha_cutoff = alpha_cutoff;
+        }
+        return p;
+    }
     static RptrCamera to_abi(const RenderCameraParams &c) {
         RptrCamera cam{};
         for (int k = 0; k < 3; ++k) {
