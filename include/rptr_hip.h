@@ -657,6 +657,39 @@ int rptr_hip_denoise(rptr_hip_t *h, const RptrDenoiseParams *p);
 int rptr_hip_readback_denoised_f32(rptr_hip_t *h, float *rgba, size_t n_floats);
 int rptr_hip_readback_denoised_u8(rptr_hip_t *h, unsigned char *rgba, size_t n_bytes);
 
+/* ---- temporal upscaling: the TAA pass at twice the render resolution (vulkan/processing/process_taa.comp with render_upscale_factor = 2,
+ * the way the reference's application renders at half the display resolution in each axis and lets the history fill in the sub-pixel
+ * detail). For a handle initialized at W x H a call makes a 2W x 2H RGBA8 image from the last finished frame's RGBA8 image (every
+ * rendered pixel stands for a 2x2 block of display pixels; the block is never stored), its motion + jitter AOV image and the previous
+ * call's output, the history: per display pixel a 10 x 10 Lanczos window over the history whose taps lie two display pixels apart, then
+ * the blend and the clamp to the 3x3 box of rendered pixels. csrc/taa_upscale.h states every operation, tests/taa_upscale_ref.py restates
+ * it in numpy. INTEGRATION.md "Temporal upscaling" lists what a host can rely on.
+ * The call is explicit and writes images of its own, like the denoiser: it never touches the accumulation image, the RGBA8 frame, the AOV
+ * images, the reprojection / TAA history, frame_id / frame_offset or the statistics; a frame rendered after it is bit-identical to one
+ * rendered without it, and a host that never calls it launches nothing new. It works in every reprojection_mode and whatever
+ * render_upscale_factor and option "taa" are (the option's own pass stays at the render resolution and still refuses factor 2). The
+ * source frame is the one the read-backs return: the frame waited for last. The call is asynchronous on the backend's stream; its two
+ * display-size images (32 bytes per rendered pixel) are allocated by the first call and freed with the handle's other frame-sized
+ * buffers.
+ * History: the output of one call is the history of the next. A call has no history -- and its output is the plain 2x2 replication of
+ * the frame, what the reference's history holds after its first frame -- when it is the first one since rptr_hip_initialize, or when
+ * reset_history is 1. The library does not guess from frame_id: the host sets reset_history for the frame that restarted its
+ * accumulation.
+ * RptrTaaUpscaleParams: rptr_hip_taa_upscale_defaults fills in factor 2, reset_history 0, reserved 0; rptr_hip_taa_upscale(h, NULL) uses them.
+ * rptr_hip_readback_upscaled_u8: the output of the last call, 2W x 2H x 4 bytes, row 0 at the top; waits for the call.
+ * RPTR_E_INVALID: NULL handle; factor != 2; reset_history not 0 / 1; reserved != 0; before initialize or before a frame has finished;
+ * the frame's images are being overwritten by a newer frame on the same frame context; the frame waited for last is not the last of its
+ * launch sequence; a read-back before any call since initialize, or into fewer than 16 W H bytes.
+ * RPTR_E_UNSUPPORTED: option "aovs" = 0; world_size > 1 (a stripe's taps lie in other ranks' rows). */
+typedef struct RptrTaaUpscaleParams { /* 16 bytes */
+    int32_t factor;        /* 2; anything else RPTR_E_INVALID */
+    int32_t reset_history; /* 1: this call has no history: its output is the replicated frame */
+    int32_t reserved[2];   /* must be 0 */
+} RptrTaaUpscaleParams;
+void rptr_hip_taa_upscale_defaults(RptrTaaUpscaleParams *out);
+int rptr_hip_taa_upscale(rptr_hip_t *h, const RptrTaaUpscaleParams *p /* NULL = defaults */);
+int rptr_hip_readback_upscaled_u8(rptr_hip_t *h, unsigned char *rgba, size_t n_bytes);
+
 /* ---- multi-GPU: this rank's rows, packed top-to-bottom, for the RCCL gather.
  * rptr_hip_tile_rows writes up to `cap` (first_row,num_rows) pairs for `rank`
  * and returns the number of stripes; rptr_hip_copy_tile_to_device copies this

@@ -252,6 +252,10 @@ class SurfaceHit(C.Structure):  # include/rptr_hip.h RptrSurfaceHit: six 16-byte
                 ("uv", C.c_float * 2), ("material_id", C.c_int32), ("metallic", C.c_float)]
 
 
+class TaaUpscaleParams(C.Structure):  # include/rptr_hip.h RptrTaaUpscaleParams
+    _fields_ = [("factor", C.c_int32), ("reset_history", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 class OcclusionParams(C.Structure):  # include/rptr_hip.h RptrOcclusionParams
     _fields_ = [("flags", C.c_uint32), ("alpha_cutoff", C.c_float), ("reserved", C.c_uint32 * 2)]
 
@@ -272,6 +276,7 @@ SURFACE_HIT_DTYPE = _surface_hit_dtype()  # numpy structured dtype of SurfaceHit
 
 assert C.sizeof(SurfaceHit) == 96 and SURFACE_HIT_DTYPE.itemsize == 96
 assert C.sizeof(OcclusionParams) == 16
+assert C.sizeof(TaaUpscaleParams) == 16
 assert C.sizeof(LightSource) == 48
 assert C.sizeof(DenoiseParams) == 32
 assert C.sizeof(BaseMaterial) == 80
@@ -293,6 +298,7 @@ EXPORTED_SYMBOLS = [
     "rptr_hip_initialize", "rptr_hip_set_scene", "rptr_hip_update_vertices", "rptr_hip_update_vertices_device", "rptr_hip_refit", "rptr_hip_set_params",
     "rptr_hip_render", "rptr_hip_render_async", "rptr_hip_render_batch_async", "rptr_hip_render_batch_cameras_async", "rptr_hip_wait", "rptr_hip_set_stage_timing", "rptr_hip_set_freeze_frame", "rptr_hip_set_option", "rptr_hip_get_option", "rptr_hip_option_count", "rptr_hip_option_name", "rptr_hip_set_rng_variant", "rptr_hip_set_bvh_policy", "rptr_hip_bvh_rebuild_count", "rptr_hip_update_instances", "rptr_hip_update_instances_device", "rptr_hip_set_tlas_policy", "rptr_hip_tlas_rebuild_count", "rptr_hip_set_light_sources", "rptr_hip_readback_lights", "rptr_hip_get_framebuffer_size", "rptr_hip_readback_f32", "rptr_hip_readback_u8", "rptr_hip_readback_aov",
     "rptr_hip_denoise_defaults", "rptr_hip_denoise", "rptr_hip_readback_denoised_f32", "rptr_hip_readback_denoised_u8",
+    "rptr_hip_taa_upscale_defaults", "rptr_hip_taa_upscale", "rptr_hip_readback_upscaled_u8",
     "rptr_hip_tile_rows", "rptr_hip_local_pixel_count", "rptr_hip_copy_tile_to_device", "rptr_hip_trace", "rptr_hip_trace_device", "rptr_hip_enable_ray_queries", "rptr_hip_render_ray_queries", "rptr_hip_trace_radiance", "rptr_hip_trace_radiance_device", "rptr_hip_render_radiance_queries", "rptr_hip_trace_surface", "rptr_hip_trace_surface_device", "rptr_hip_occlusion_defaults", "rptr_hip_trace_occlusion", "rptr_hip_trace_occlusion_device", "rptr_hip_set_light_sampling_variant", "rptr_hip_trace_counted",
     "rptr_hip_export_bvh", "rptr_hip_build_bvh_host", "rptr_hip_stats",
     "rptr_hip_comm_get_unique_id", "rptr_hip_comm_init_rank", "rptr_hip_comm_init_all", "rptr_hip_comm_destroy", "rptr_hip_comm_transport", "rptr_hip_comm_ipc_export", "rptr_hip_comm_ipc_init", "rptr_hip_gather", "rptr_hip_gather_all", "rptr_hip_gather_batch", "rptr_hip_gather_all_batch", "rptr_hip_readback_gathered_frame_f32",

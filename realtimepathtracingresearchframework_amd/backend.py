@@ -105,6 +105,10 @@ def load_library(path=None):
     L.rptr_hip_denoise.argtypes = [vp, C.POINTER(abi.DenoiseParams)]
     L.rptr_hip_readback_denoised_f32.argtypes = [vp, vp, C.c_size_t]
     L.rptr_hip_readback_denoised_u8.argtypes = [vp, vp, C.c_size_t]
+    L.rptr_hip_taa_upscale_defaults.argtypes = [C.POINTER(abi.TaaUpscaleParams)]
+    L.rptr_hip_taa_upscale_defaults.restype = None
+    L.rptr_hip_taa_upscale.argtypes = [vp, C.POINTER(abi.TaaUpscaleParams)]
+    L.rptr_hip_readback_upscaled_u8.argtypes = [vp, vp, C.c_size_t]
     L.rptr_hip_tile_rows.argtypes = [vp, i32, vp, i32]
     L.rptr_hip_local_pixel_count.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.rptr_hip_copy_tile_to_device.argtypes = [vp, vp, C.c_size_t]
@@ -420,6 +424,31 @@ class RenderHip:
         w, hgt, c = self.get_framebuffer_size()
         out = np.zeros((hgt, w, c), np.uint8)
         self._check(self._L.rptr_hip_readback_denoised_u8(self._h, out.ctypes.data_as(C.c_void_p), out.size))
+        return out
+
+    # ---- temporal 2x upscaling (include/rptr_hip.h rptr_hip_taa_upscale; csrc/taa_upscale.h)
+    def taa_upscale(self, params=None, **fields):
+        """Upscales the frame the read-backs return (the frame waited for last) to twice its resolution with the previous call's output
+        as history; asynchronous on the backend's stream. params: an abi.TaaUpscaleParams, or None for the library's defaults; keyword
+        arguments override single fields (factor, reset_history). Pass reset_history = 1 for the frame that restarted the accumulation
+        (RenderConfiguration.reset_accumulation): its output is the replicated frame. Returns the parameters used."""
+        p = abi.TaaUpscaleParams()
+        if params is None:
+            self._L.rptr_hip_taa_upscale_defaults(C.byref(p))
+        else:
+            C.memmove(C.byref(p), C.byref(params), C.sizeof(p))
+        for k, v in fields.items():
+            if k not in dict(abi.TaaUpscaleParams._fields_) or k == "reserved":
+                raise TypeError("taa_upscale: unknown parameter %r" % k)
+            setattr(p, k, int(v))
+        self._check(self._L.rptr_hip_taa_upscale(self._h, C.byref(p)))
+        return p
+
+    def readback_upscaled(self):
+        """the RGBA8 image of the last taa_upscale() as a (2H, 2W, 4) uint8 array"""
+        w, hgt, c = self.get_framebuffer_size()
+        out = np.zeros((2 * hgt, 2 * w, c), np.uint8)
+        self._check(self._L.rptr_hip_readback_upscaled_u8(self._h, out.ctypes.data_as(C.c_void_p), out.size))
         return out
 
     # ---- ray queries (RQ_CLOSEST)

@@ -235,6 +235,29 @@ int rptr_hip_readback_aov(rptr_hip_t *h, int aov_index, uint16_t *rgba16f, size_
     return readback_rows<uint2>(h, c.aov[aov_index], reinterpret_cast<uint2 *>(rgba16f), n_halfs / 4);
 }
 
+// ---- what the calls that work on the last finished frame and its AOV images (the denoiser, the temporal upscaler) ask of the handle:
+// one device, the AOV images on, a frame finished, its images not being overwritten by a frame in flight, and the AOV images those of
+// the frame waited for last. `who`: the entry point; `verb`: what the host is told to do earlier; `reads`: the AOV images it needs;
+// at_render_resolution: the call's images have the render resolution, so render_upscale_factor 2 is refused
+extern "C++" {
+static int check_finished_frame_with_aovs(rptr_hip *h, const char *who, const char *verb, const char *reads, bool at_render_resolution) {
+    if (h->world > 1) return fail(h, RPTR_E_UNSUPPORTED, "%s needs world_size 1: the taps of a stripe's pixels lie in other ranks' rows", who);
+    if (h->width == 0) return fail(h, RPTR_E_INVALID, "%s before initialize", who);
+    if (!h->aovs) return fail(h, RPTR_E_UNSUPPORTED, "%s reads %s: option \"aovs\" is 0", who, reads);
+    if (at_render_resolution && h->params.render_upscale_factor == 2)
+        return fail(h, RPTR_E_UNSUPPORTED, "%s needs render_upscale_factor 1 (its RGBA8 image has the render resolution)", who);
+    if (h->finished_serial == 0) return fail(h, RPTR_E_INVALID, "%s before a frame has finished (render, or wait for a ticket, first)", who);
+    if (h->output_overwritten || h->aov_overwritten)
+        return fail(h, RPTR_E_INVALID, "the images of the last waited frame are being overwritten by a newer frame in flight on the same frame context: "
+                                       "%s before submitting that frame, or rptr_hip_wait for it first", verb);
+    const FrameCtx &ac = h->ctx[(size_t)h->aov_ctx];
+    if (h->output_ctx >= 0 && (h->output_ctx != h->aov_ctx || h->output_index != ac.batch_n - 1))
+        return fail(h, RPTR_E_INVALID, "%s: the AOV images belong to the last frame of the launch sequence finished last, the frame waited "
+                                       "for last is another one", who);
+    return RPTR_OK;
+}
+}
+
 // ---- the denoiser (denoise.h): the last finished frame through prepare, `iterations` a-trous passes and finish, on the backend's stream
 void rptr_hip_denoise_defaults(RptrDenoiseParams *out) {
     if (!out) return;
@@ -257,22 +280,11 @@ int rptr_hip_denoise(rptr_hip_t *h, const RptrDenoiseParams *p) {
         return fail(h, RPTR_E_INVALID, "rptr_hip_denoise: normal_power_log2 = %d is outside [0, 8]", p->normal_power_log2);
     if (p->demodulate_albedo != 0 && p->demodulate_albedo != 1) return fail(h, RPTR_E_INVALID, "rptr_hip_denoise: demodulate_albedo must be 0 or 1");
     if (p->reserved[0] || p->reserved[1] || p->reserved[2]) return fail(h, RPTR_E_INVALID, "rptr_hip_denoise: RptrDenoiseParams.reserved must be 0");
-    if (h->world > 1) return fail(h, RPTR_E_UNSUPPORTED, "rptr_hip_denoise needs world_size 1: the taps of a stripe's pixels lie in other ranks' rows");
-    if (h->width == 0) return fail(h, RPTR_E_INVALID, "rptr_hip_denoise before initialize");
-    if (!h->aovs) return fail(h, RPTR_E_UNSUPPORTED, "rptr_hip_denoise reads the albedo and normal + depth AOV images: option \"aovs\" is 0");
-    if (h->params.render_upscale_factor == 2)
-        return fail(h, RPTR_E_UNSUPPORTED, "rptr_hip_denoise needs render_upscale_factor 1 (its RGBA8 image has the render resolution)");
-    if (h->finished_serial == 0) return fail(h, RPTR_E_INVALID, "rptr_hip_denoise before a frame has finished (render, or wait for a ticket, first)");
-    if (h->output_overwritten || h->aov_overwritten)
-        return fail(h, RPTR_E_INVALID, "the images of the last waited frame are being overwritten by a newer frame in flight on the same frame context: "
-                                       "denoise before submitting that frame, or rptr_hip_wait for it first");
+    int rc;
+    if ((rc = check_finished_frame_with_aovs(h, "rptr_hip_denoise", "denoise", "the albedo and normal + depth AOV images", true))) return rc;
     const FrameCtx &ac = h->ctx[(size_t)h->aov_ctx];
-    if (h->output_ctx >= 0 && (h->output_ctx != h->aov_ctx || h->output_index != ac.batch_n - 1))
-        return fail(h, RPTR_E_INVALID, "rptr_hip_denoise: the AOV images belong to the last frame of the launch sequence finished last, the frame waited "
-                                       "for last is another one");
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t npix = (size_t)h->width * (size_t)h->height;
-    int rc;
     if (!h->dn.out_u8) {
         if ((rc = dev_alloc(h, &h->dn.ev[0], npix, nullptr)) || (rc = dev_alloc(h, &h->dn.ev[1], npix, nullptr)) || (rc = dev_alloc(h, &h->dn.ndz, npix, nullptr)) ||
             (rc = dev_alloc(h, &h->dn.gz, npix, nullptr)) || (rc = dev_alloc(h, &h->dn.out_f32, npix, nullptr)) || (rc = dev_alloc(h, &h->dn.out_u8, npix, nullptr)))
@@ -336,6 +348,59 @@ int rptr_hip_readback_denoised_u8(rptr_hip_t *h, unsigned char *rgba, size_t n_b
     if (!h || !rgba) return fail(h, RPTR_E_INVALID, "NULL argument");
     const int rc = check_denoised(h);
     return rc ? rc : readback_rows<uchar4>(h, h->dn.out_u8, reinterpret_cast<uchar4 *>(rgba), n_bytes / 4);
+}
+
+// ---- temporal 2x upscaling (taa_upscale.h): the last finished frame and the previous call's output into a display-size image
+void rptr_hip_taa_upscale_defaults(RptrTaaUpscaleParams *out) {
+    if (!out) return;
+    memset(out, 0, sizeof(*out));
+    out->factor = 2;
+}
+
+int rptr_hip_taa_upscale(rptr_hip_t *h, const RptrTaaUpscaleParams *p) {
+    if (!h) return fail(nullptr, RPTR_E_INVALID, "NULL handle");
+    RptrTaaUpscaleParams defaults;
+    rptr_hip_taa_upscale_defaults(&defaults);
+    if (!p) p = &defaults;
+    if (p->factor != 2) return fail(h, RPTR_E_INVALID, "rptr_hip_taa_upscale: factor = %d (2 is the one supported)", p->factor);
+    if (p->reset_history != 0 && p->reset_history != 1) return fail(h, RPTR_E_INVALID, "rptr_hip_taa_upscale: reset_history must be 0 or 1");
+    if (p->reserved[0] || p->reserved[1]) return fail(h, RPTR_E_INVALID, "rptr_hip_taa_upscale: RptrTaaUpscaleParams.reserved must be 0");
+    int rc;
+    if ((rc = check_finished_frame_with_aovs(h, "rptr_hip_taa_upscale", "upscale", "the motion + jitter AOV image", false))) return rc;
+    const FrameCtx &ac = h->ctx[(size_t)h->aov_ctx];
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t npix = (size_t)h->width * (size_t)h->height;
+    if (!h->up.img[0]) {
+        if ((rc = dev_alloc(h, &h->up.img[0], 4 * npix, nullptr)) || (rc = dev_alloc(h, &h->up.img[1], 4 * npix, nullptr))) return rc;
+        h->up.cur = 0;
+        h->up.have = false;
+    }
+    const uchar4 *pre = nullptr;
+    if ((rc = last_finished_image(h, nullptr, &pre))) return rc; // (world_size 1: an image is the whole frame)
+    uchar4 *out = h->up.img[h->up.cur ^ 1];
+    if (p->reset_history || !h->up.have)
+        rp_launch_kernel(RpLaunch{dim3((unsigned)grid_for(h, 4 * npix)), h->stream, nullptr, nullptr}, rp_k_upscale_replicate, 256u, h->width, h->height, pre, out);
+    else {
+        const unsigned T = RP_TU_TILE;
+        const dim3 tiles((2u * (unsigned)h->width + T - 1) / T, (2u * (unsigned)h->height + T - 1) / T);
+        rp_launch_kernel(RpLaunch{tiles, h->stream, nullptr, nullptr}, rp_k_taa_upscale, 64u, h->width, h->height, pre, (const uchar4 *)h->up.img[h->up.cur],
+                         (const uint2 *)ac.aov[2], out);
+    }
+    HIP_TRY(h, hipGetLastError());
+    h->up.cur ^= 1;
+    h->up.have = true;
+    return RPTR_OK;
+}
+
+int rptr_hip_readback_upscaled_u8(rptr_hip_t *h, unsigned char *rgba, size_t n_bytes) {
+    if (!h || !rgba) return fail(h, RPTR_E_INVALID, "NULL argument");
+    if (!h->up.have) return fail(h, RPTR_E_INVALID, "no upscaled image: call rptr_hip_taa_upscale first");
+    const size_t need = 16 * (size_t)h->width * (size_t)h->height;
+    if (n_bytes < need) return fail(h, RPTR_E_INVALID, "read-back buffer too small for the upscaled image: %zu < %zu bytes", n_bytes, need);
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipMemcpyAsync(rgba, h->up.img[h->up.cur], need, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return RPTR_OK;
 }
 
 int rptr_hip_set_light_sampling_variant(rptr_hip_t *h, int variant) {

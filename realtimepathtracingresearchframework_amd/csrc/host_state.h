@@ -384,6 +384,13 @@ struct rptr_hip {
         uchar4 *out_u8 = nullptr;
         uint64_t serial = 0;                // finished_serial of the frame the images were made from (0: none)
     } dn;
+    // temporal 2x upscaling (taa_upscale.h, rptr_hip_taa_upscale): two display-size RGBA8 images, made by the first call and freed with
+    // the other frame-sized buffers; a call reads the history in img[cur] and writes img[cur ^ 1], which becomes `cur`
+    struct TaaUpscale {
+        uchar4 *img[2] = {nullptr, nullptr};
+        int cur = 0;
+        bool have = false;                  // img[cur] holds a call's output: the next call's history, what the read-back returns
+    } up;
     uint64_t finished_serial = 0;           // frames waited for since initialize: the read-backs' frame changes with each
     size_t path_capacity = 0;
     // persistent traversal grids (traversal_grid below): [0] first / [1] later closest-hit, shadow rays [2] two-level / [3] one instance record

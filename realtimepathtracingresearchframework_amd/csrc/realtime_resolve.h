@@ -234,7 +234,8 @@ __global__ __launch_bounds__(64) void rp_k_reproject(RpFrame f, RpReprojectArgs 
 //     (the frame before the pass) is read and `out` written, so every neighbour is the pre-TAA value.
 //   - its 3x3 motion loop (:63-71) loads the CENTRE pixel nine times (fb_pixel / render_upscale_factor, no offset): kept as written, so
 //     the motion is the centre's.
-// render_upscale_factor is 1 here (the library renders and shows at one resolution; option "taa" with factor 2 is refused).
+// render_upscale_factor is 1 here (a frame renders and shows at one resolution; option "taa" with factor 2 is refused). The pass at
+// twice the render resolution is a call of its own on a finished frame: taa_upscale.h.
 // Cost (same frame): 122 us. 100 Lanczos taps per pixel, each an LDS read of the staged history texel plus four LDS reads of the
 // byte / 255 table and four multiply-adds: ~500 LDS reads per pixel, estimated ~50 us of LDS issue alone, the rest VALU. Taps that fall
 // outside the tile's 24 x 24 window (motion differing by more than 3 pixels inside a tile) read global memory instead. Estimated, not

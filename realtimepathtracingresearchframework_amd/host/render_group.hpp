@@ -88,7 +88,11 @@ public:
     // (render_hip.hpp: non-null = submitted, two frames in flight, statistics two frames late). A group of several devices renders such a
     // frame synchronously (its gather follows the frame).
     RenderStats frame(CommandStream *cmd_stream, const RenderConfiguration &config) {
-        if (size() > 1 || !cmd_stream) return render(config);
+        if (size() > 1 || !cmd_stream) {
+            const RenderStats s = render(config);
+            if (upscale_every_frame_) taa_upscale(config.reset_accumulation);
+            return s;
+        }
         RenderHip &r = *ranks_[0];
         r.begin_frame(cmd_stream, config);
         r.draw_frame(cmd_stream, config.active_variant);
@@ -215,6 +219,19 @@ public:
     void denoise(const RptrDenoiseParams &p) { ranks_[0]->denoise(p); }
     size_t readback_denoised(size_t buffer_size, float *buffer) { return ranks_[0]->readback_denoised(buffer_size, buffer); }
     size_t readback_denoised(size_t buffer_size, unsigned char *buffer) { return ranks_[0]->readback_denoised(buffer_size, buffer); }
+    // temporal 2x upscaling works on one GPU's whole frame as well (rptr_hip_taa_upscale refuses world_size > 1)
+    void taa_upscale(const RptrTaaUpscaleParams &p) { ranks_[0]->taa_upscale(p); }
+    void taa_upscale(bool reset_history) {
+        RptrTaaUpscaleParams p = RenderHip::taa_upscale_defaults();
+        p.reset_history = reset_history ? 1 : 0;
+        taa_upscale(p);
+    }
+    // with every frame of frame(): the command-stream loop upscales as it collects (render_hip.hpp), a synchronous frame right after it
+    void upscale_every_frame(bool on) {
+        upscale_every_frame_ = on;
+        ranks_[0]->upscale_every_frame(on);
+    }
+    size_t readback_upscaled(size_t buffer_size, unsigned char *buffer) { return ranks_[0]->readback_upscaled(buffer_size, buffer); }
     size_t readback_aov(RenderHip::AOVBufferIndex aov, size_t buffer_size, uint16_t *buffer) {
         size_t n = 0;
         for (auto &r : ranks_) n = r->readback_aov(aov, buffer_size, buffer);
@@ -239,6 +256,7 @@ private:
     int width_ = 0, height_ = 0;
     double rays_ = 0.0;
     uint64_t counted_serial_ = 0;
+    bool upscale_every_frame_ = false;
 };
 
 } // namespace rptr

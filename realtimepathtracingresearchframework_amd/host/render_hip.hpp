@@ -16,6 +16,7 @@
 namespace rptr {
 
 static_assert(sizeof(RptrOcclusionParams) == 16, "RptrOcclusionParams: flags, alpha_cutoff, two reserved words (include/rptr_hip.h)");
+static_assert(sizeof(RptrTaaUpscaleParams) == 16, "RptrTaaUpscaleParams: factor, reset_history, two reserved words (include/rptr_hip.h)");
 static_assert(sizeof(RptrSurfaceHit) == 96, "RptrSurfaceHit: six 16-byte rows per surface query (include/rptr_hip.h)");
 
 struct RenderStats { // librender/render_backend.h:15-24
@@ -177,6 +178,7 @@ public:
         const RptrCamera cam = abi_camera();
         check(rptr_hip_render_async(h_, &cam, variant_, batch_spp(0), reset_accumulation ? 1 : 0, 0, &ticket_[swap_index_]));
         pending_[swap_index_] = true;
+        slot_reset_[swap_index_] = reset_accumulation;
         asynchronous_ = true;
         count_frame(batch_spp(0));
     }
@@ -199,6 +201,7 @@ public:
         const RptrCamera cam = abi_camera();
         check(rptr_hip_render(h_, &cam, variant_, batch_spp(spp), reset_accumulation ? 1 : 0, 0, &last_));
         ++stats_serial_;
+        frame_collected(reset_accumulation);
         count_frame(batch_spp(spp));
         asynchronous_ = false;
     }
@@ -322,6 +325,32 @@ public:
         const size_t need = size_t(whc[0]) * whc[1] * 4;
         if (buffer_size < need) return 0;
         check(rptr_hip_readback_denoised_u8(h_, buffer, buffer_size));
+        return need;
+    }
+
+    // Temporal 2x upscaling (include/rptr_hip.h rptr_hip_taa_upscale): the frame the read-backs return -- everything in flight is finished
+    // first -- and the previous call's output into a display-size image of its own; the frame's images and histories stay as they are.
+    // Asynchronous on the backend's stream. p.reset_history = 1 for the frame that restarted the accumulation.
+    static RptrTaaUpscaleParams taa_upscale_defaults() {
+        RptrTaaUpscaleParams p;
+        rptr_hip_taa_upscale_defaults(&p);
+        return p;
+    }
+    void taa_upscale(const RptrTaaUpscaleParams &p) {
+        flush_pipeline();
+        check(rptr_hip_taa_upscale(h_, &p));
+    }
+    // ... or with every frame of the reference's loop (begin_frame / draw_frame with or without a command stream), issued when the frame
+    // it belongs to has been collected -- begin_frame's wait for the swap index it reuses, flush_pipeline, the synchronous draw_frame --
+    // with reset_history = that frame's reset_accumulation. Frames collected through wait(ticket) are the host's to upscale.
+    void upscale_every_frame(bool on) { upscale_every_frame_ = on; }
+    size_t readback_upscaled(size_t buffer_size, unsigned char *buffer) { // sRGB RGBA8, twice the width and height
+        uint32_t whc[3];
+        get_framebuffer_size(whc);
+        const size_t need = size_t(whc[0]) * whc[1] * 16;
+        if (buffer_size < need) return 0;
+        if (upscale_every_frame_) flush_pipeline();
+        check(rptr_hip_readback_upscaled_u8(h_, buffer, buffer_size));
         return need;
     }
 
@@ -451,8 +480,17 @@ private:
         // (a library call that needs the device to itself -- set_scene, ray queries over host arrays, a vertex update of a scene without
         // per-context copies -- has finished every frame in flight already: such a ticket is "not in flight" any more, its timings are gone)
         const int rc = rptr_hip_wait(h_, ticket_[i], &last_);
-        if (rc == RPTR_OK) ++stats_serial_;
+        if (rc == RPTR_OK) {
+            ++stats_serial_;
+            frame_collected(slot_reset_[i]);
+        }
         if (rc != RPTR_OK && !(rc == RPTR_E_INVALID && std::string(rptr_hip_last_error(h_)).find("not in flight") != std::string::npos)) check(rc);
+    }
+    void frame_collected(bool restarted) { // upscale_every_frame: the call that belongs to the frame just collected
+        if (!upscale_every_frame_) return;
+        RptrTaaUpscaleParams p = taa_upscale_defaults();
+        p.reset_history = restarted ? 1 : 0;
+        check(rptr_hip_taa_upscale(h_, &p));
     }
     RptrRenderParams effective_params(RptrRenderParams p) const { // what the library is handed: `options` applied to a copy
         if (!options.enable_raytraced_dof) p.aperture_radius = p.focal_length = 0.f;
@@ -484,6 +522,8 @@ private:
     int contexts_ = 1, active_swap_ = 1, swap_index_ = 0;
     uint64_t ticket_[MAX_SWAP_BUFFERS] = {0, 0};
     bool pending_[MAX_SWAP_BUFFERS] = {false, false};
+    bool slot_reset_[MAX_SWAP_BUFFERS] = {false, false}; // reset_accumulation of the frame submitted on each swap index
+    bool upscale_every_frame_ = false;
     bool asynchronous_ = false;
     uint32_t frame_id_ = 0;
     uint64_t stats_serial_ = 0;

@@ -1,7 +1,7 @@
 // rptr_cli.cpp -- the reference's headless run modes through the C ABI (binary: bin/rptr_hip):
 //
 //   <scene> = the reference's .vks file (textures in <name>_textures/) or the flat dump scenes.py writes (.rpsc)
-//   rptr_hip <scene> --validation <prefix> [--validation-spp n] [--img w h] [--pfm] [--denoise iterations]
+//   rptr_hip <scene> --validation <prefix> [--validation-spp n] [--img w h] [--pfm] [--denoise iterations | --taa-upscale]
 //   rptr_hip <scene.rpsc> --profiling <csv prefix> [--profiling-fps f] [--profiling-img <prefix>] [--profiling-frames n]
 //            [--animate-wave amplitude kx] [--synchronous] [--fly-through] [--frames-in-flight n [--frames-per-launch b]]
 //   common:  [--eye x y z] [--center x y z] [--up x y z] [--fov deg] [--variant gltf|diffuse|gltf-transmission] [--batch-spp k] [--every-frame]
@@ -63,6 +63,10 @@ enum OutputFormat { FORMAT_EXR, FORMAT_PFM, FORMAT_PNG }; // cmdline.cpp:450-460
 // --denoise <iterations> (this host's; the reference's enable_denoising links Open Image Denoise): the images written are the denoised ones
 // (include/rptr_hip.h rptr_hip_denoise with the library's defaults and that many passes); 0: the frame's own, as without the flag
 static int g_denoise_iterations = 0;
+// --taa-upscale (this host's): every frame goes through rptr_hip_taa_upscale as it is collected, and the RGBA8 images written (--png)
+// are the upscaled ones, at twice --img; the history restarts with the frames that restart the accumulation (the first one, a new
+// keyframe, moved geometry, a moved camera unless the history is reprojected). The float images stay the frame's own. Not with --denoise.
+static bool g_taa_upscale = false;
 static void save_image(rptr::RenderGroup &backend, OutputFormat format, const std::string &prefix, int number, const std::string &suffix, int width, int height,
                        std::vector<float> &img) {
     char name[32];
@@ -74,7 +78,11 @@ static void save_image(rptr::RenderGroup &backend, OutputFormat format, const st
         dp.iterations = g_denoise_iterations;
         backend.denoise(dp);
     }
-    if (format == FORMAT_PNG) {
+    if (format == FORMAT_PNG && g_taa_upscale) {
+        std::vector<unsigned char> rgba8((size_t)width * height * 16);
+        if (backend.readback_upscaled(rgba8.size(), rgba8.data()) != rgba8.size()) throw std::runtime_error("read-back failed");
+        ok = rptr::write_png(base, 2u * (unsigned)width, 2u * (unsigned)height, 4, rgba8.data());
+    } else if (format == FORMAT_PNG) {
         std::vector<unsigned char> rgba8((size_t)width * height * 4);
         if ((g_denoise_iterations > 0 ? backend.readback_denoised(rgba8.size(), rgba8.data()) : backend.readback_framebuffer(rgba8.size(), rgba8.data())) != rgba8.size())
             throw std::runtime_error("read-back failed");
@@ -191,6 +199,7 @@ int main(int argc, char **argv) {
         else if (a == "--profiling-count") { need(1); profiling_frames = std::atoi(argv[++i]); have_profiling_options = true; } // (this host's: frames of a run without keyframes)
         else if (a == "--animate-wave") { need(2); wave_amp = (float)std::atof(argv[++i]); wave_k = (float)std::atof(argv[++i]); }
         else if (a == "--denoise") { need(1); g_denoise_iterations = std::atoi(argv[++i]); if (g_denoise_iterations < 1 || g_denoise_iterations > 5) { std::fprintf(stderr, "--denoise takes 1..5 iterations\n"); return 2; } }
+        else if (a == "--taa-upscale") g_taa_upscale = true;
         else if (a == "--img") { need(2); width = std::atoi(argv[++i]); height = std::atoi(argv[++i]); }
         else if (a == "--eye") { vec3(eye); got_eye = true; }
         else if (a == "--center") { vec3(center); got_center = true; }
@@ -337,10 +346,18 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "got profiling automation options without profiling mode, enable it using --profiling <stats>\n");
         return 2;
     }
+    if (g_taa_upscale && g_denoise_iterations > 0) {
+        std::fprintf(stderr, "--taa-upscale and --denoise cannot be combined: the denoised image has the render resolution, the upscaler reads the frame's own\n");
+        return 2;
+    }
+    if (g_taa_upscale && devices.size() > 1) {
+        std::fprintf(stderr, "--taa-upscale needs one device (rptr_hip_taa_upscale refuses world_size > 1)\n");
+        return 2;
+    }
     if (want_help) scene_path.clear(); // prints the usage
     if (scene_path.empty() || (int)validation + (int)profiling + (int)data_capture != 1 || batch_spp < 1 || width < 1 || height < 1 || (profiling && profiling_frames < 1)) {
         std::fprintf(stderr, "usage: rptr_hip <scene.rpsc> (--validation <prefix> [--validation-spp n] | --profiling <csv prefix> [--profiling-fps f] "
-                             "[--profiling-img <prefix>] [--keyframe [len:]file.ini ...] [--profiling-count n] [--synchronous] [--fly-through] [--frames-in-flight n [--frames-per-launch b]] [--animate-wave a k]) [--img w h] [--denoise iterations] [--eye x y z] [--center x y z] "
+                             "[--profiling-img <prefix>] [--keyframe [len:]file.ini ...] [--profiling-count n] [--synchronous] [--fly-through] [--frames-in-flight n [--frames-per-launch b]] [--animate-wave a k]) [--img w h] [--denoise iterations | --taa-upscale] [--eye x y z] [--center x y z] "
                              "[--up x y z] [--fov deg] [--variant gltf|diffuse] [--batch-spp k] [--every-frame] [--exr|--pfm|--png] [--config file.ini ...] [--sky-data <dir of the Hosek-Wilkie data headers>]\n"
                              "       rptr_hip <scene.rpsc> --data-capture <prefix> [--data-capture-spp n] [--data-capture-no-rgba] [--data-capture-no-aovs] "
                              "[--data-capture-albedo-roughness] [--data-capture-normal-depth] [--data-capture-motion] [--keyframe ...]   (EXR images per keyframe)\n"
@@ -479,7 +496,7 @@ int main(int argc, char **argv) {
             // every frame bit-identical to the frame rendered on its own) with four sequences in flight, and collected in order -- the images
             // are written at the same sample counts, with the same bits, as by the loop of synchronous frames below (--synchronous; a frozen
             // frame repeats its samples and cannot share a sequence).
-            if (!synchronous && !freeze_frame && (backend.size() == 1 || !every_frame)) { // (a group's gather assembles the LAST frame of a sequence)
+            if (!synchronous && !freeze_frame && !g_taa_upscale && (backend.size() == 1 || !every_frame)) { // (a group's gather assembles the LAST frame of a sequence; the upscaler wants every frame as it finishes)
                 const int total_frames = (target_spp + batch_spp - 1) / batch_spp;
                 // (a launch sequence must fit the sample slots the handle holds: 16 up to ~2.9 Mpixel per rank, fewer above -- 12 at 1440p, 5 at 4K,
                 // rptr_hip_get_option "sample_slots"; a frame of more samples than that is split by the library itself, one frame per sequence)
@@ -517,6 +534,7 @@ int main(int argc, char **argv) {
             }
             while (accumulated < target_spp) {
                 const rptr::RenderStats st = backend.render(cfg); // params.batch_spp samples
+                if (g_taa_upscale) backend.taa_upscale(cfg.reset_accumulation);
                 cfg.reset_accumulation = false;
                 accumulated = freeze_frame ? accumulated + batch_spp : st.spp; // (a frozen frame repeats its samples: the application counts, app_state.cpp)
                 gpu_ms += st.render_time;
@@ -696,7 +714,7 @@ int main(int argc, char **argv) {
             // reprojection_mode 2 folds each frame into the one before it: one frame per launch sequence (include/rptr_hip.h)
             bool realtime = base.params.reprojection_mode == 2;
             for (const rptr::HostConfig &st : frames) realtime = realtime || st.params.reprojection_mode == 2;
-            if (realtime) frames_per_launch = 1;
+            if (realtime || g_taa_upscale) frames_per_launch = 1; // (the upscaler reads the AOV images, which are those of a sequence's last frame)
             struct Pending {
                 rptr::RenderGroup::Sequence q;
                 int first;
@@ -722,6 +740,7 @@ int main(int argc, char **argv) {
                 for (int k = 0; k < p.q.frames; ++k) {
                     const FramePlan &fp = plan[(size_t)(p.first + k)];
                     const rptr::RenderStats st = backend.collect_frame(p.q, k);
+                    if (g_taa_upscale) backend.taa_upscale(fp.reset);
                     gpu_ms += st.render_time;
                     const auto now = std::chrono::steady_clock::now();
                     std::fprintf(csv, "%d,%d,%d,%g,%g\n", ++collected, fp.keyframe_no, fp.accumulated, st.render_time, std::chrono::duration<double, std::milli>(now - last).count());
@@ -756,6 +775,7 @@ int main(int argc, char **argv) {
         // ---- the reference's loop (app.cpp:453-469): begin_frame / draw_frame / end_frame per frame, with the display's command stream (two
         // frames in flight, statistics two frames late) or, --synchronous, without one
         rptr::CommandStream display_stream;
+        backend.upscale_every_frame(g_taa_upscale); // (issued as each frame is collected: render_group.hpp frame)
         rptr::CommandStream *const cmd_stream = synchronous ? nullptr : &display_stream;
         if (!rest.empty() || fly_through) { // (a short warm-up when the run is a measurement: the adaptive tail hand-over settles in two frames)
             apply_key(plan[0].key);

@@ -1,0 +1,237 @@
+"""Temporal 2x upscaling on the GPU (csrc/taa_upscale.h, rptr_hip_taa_upscale) against its numpy restatement
+(tests/taa_upscale_ref.py) fed the library's own per-frame inputs: the RGBA8 frame, the motion AOV and the previous call's output."""
+import ctypes as C
+import functools
+import math
+
+import numpy as np
+import pytest
+
+import taa_upscale_ref as U
+from realtimepathtracingresearchframework_amd import abi, backend, scenes
+
+pytestmark = pytest.mark.gpu
+
+
+def _panned(cam, k, rate):
+    """the view yawed by rate * k radians about its up axis"""
+    d = np.array(cam.dir[:], np.float64)
+    u = np.array(cam.up[:], np.float64)
+    r = np.cross(d, u)
+    r /= np.linalg.norm(r)
+    a = rate * k
+    nd = math.cos(a) * d + math.sin(a) * r
+    nd /= np.linalg.norm(nd)
+    c = abi.Camera()
+    c.pos[:] = cam.pos[:]
+    c.dir[:] = [float(v) for v in nd]
+    c.up[:] = cam.up[:]
+    c.fovy = cam.fovy
+    return c
+
+
+def _images(r, W, H, upscale, **fields):
+    acc = np.zeros((H, W, 4), np.float32)
+    fb = np.zeros((H, W, 4), np.uint8)
+    aov = [np.zeros((H, W, 4), np.float16) for _ in range(3)]
+    r.readback_framebuffer(acc)
+    r.readback_framebuffer(fb)
+    for k in range(3):
+        r.readback_aov(k, aov[k])
+    up = None
+    if upscale:
+        r.taa_upscale(**fields)
+        up = r.readback_upscaled()
+    return acc, fb, aov[0], aov[1], aov[2], up
+
+
+def _sequence(W, H, mode, n, rate, options=None, upscale=True, frames_in_flight=1, asynchronous=False, reset_calls=()):
+    """n frames of 1 spp of scenes.grid(120, 60) along a pan; per frame (accum, fb, albedo, nd, mj, upscaled)"""
+    s = scenes.grid(120, 60)
+    r = backend.RenderHip(options=options, frames_in_flight=frames_in_flight)
+    r.initialize(W, H)
+    r.set_scene(s)
+    r.params.reprojection_mode = mode
+    cam = s.camera_params()
+    cfg = lambda k: backend.RenderConfiguration(_panned(cam, k, rate), active_variant=abi.VARIANT_SIMPLE, reset_accumulation=k == 0)
+    fields = lambda k: {"reset_history": 1} if k in reset_calls else {}
+    out = []
+    if not asynchronous:
+        for k in range(n):
+            r.render(cfg(k), spp=1)
+            out.append(_images(r, W, H, upscale, **fields(k)))
+    else:  # frame k + 1 is submitted before frame k is waited for
+        tickets = [r.render_async(cfg(0), spp=1)]
+        for k in range(n):
+            if k + 1 < n:
+                tickets.append(r.render_async(cfg(k + 1), spp=1))
+            r.wait(tickets[k])
+            out.append(_images(r, W, H, upscale, **fields(k)))
+    r.close()
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def _pan():
+    """the sequence of test_taa_matches_the_restatement (tests/test_gpu_realtime_resolve.py) with a call after every frame; shared"""
+    return _sequence(96, 64, 2, 6, 0.003)
+
+
+def _has_detail(img):
+    """some 2x2 block of the display image holds differing pixels"""
+    b = img.reshape(img.shape[0] // 2, 2, img.shape[1] // 2, 2, 4)
+    return bool((b != b[:, :1, :, :1]).any())
+
+
+def _compare(frames, first=1):
+    """frames[k] for k >= first against the restatement fed the library's own frame, motion and previous output: 1 LSB of RGBA8, the
+    tolerance tests/test_gpu_realtime_resolve.py uses for the same sinf-based arithmetic. Returns the restatement's last image."""
+    want = None
+    for k in range(first, len(frames)):
+        pre, mj, got = frames[k][1], frames[k][4], frames[k][5]
+        want = U.taa_upscale(pre, frames[k - 1][5], mj, 2)
+        d = np.abs(got.astype(np.int32) - want.astype(np.int32))
+        print("frame %d: max |difference| %d, bytes that differ %d of %d, more than 1 LSB: %d" % (k, int(d.max()), int(np.count_nonzero(d)), d.size, int(np.count_nonzero(d > 1))))
+        assert int(d.max()) <= 1, (k, int(d.max()), "bytes that differ: %d, by more than 1: %d" % (int(np.count_nonzero(d)), int(np.count_nonzero(d > 1))))
+    return want
+
+
+def test_matches_the_restatement_along_a_pan():
+    frames = _pan()
+    assert frames[0][5].shape == (128, 192, 4)
+    assert np.array_equal(frames[0][5], U.replicate(frames[0][1]))   # the first call has no history
+    want = _compare(frames)
+    rep = U.replicate(frames[-1][1])
+    # the comparison cannot pass on a replication: the restatement's image has sub-pixel detail and differs from it, and so does the device's
+    assert _has_detail(want) and not np.array_equal(want, rep)
+    assert _has_detail(frames[-1][5]) and not np.array_equal(frames[-1][5], rep)
+
+
+def test_edges_and_fallbacks():
+    """50 x 38 -> 100 x 76: neither a multiple of the 8-pixel tile; a fast pan (0.05 rad per frame), so that reconstruction points leave
+    the image; sky pixels carry NaN motion, and a tile whose first pixel is sky places its staged window nowhere: its other pixels read
+    the history from global memory"""
+    W, H, n = 50, 38, 5
+    frames = _sequence(W, H, 2, n, 0.05)
+    assert np.array_equal(frames[0][5], U.replicate(frames[0][1]))
+    _compare(frames)
+    outside = inside = nan = fallback = 0
+    for k in range(1, n):
+        ins, isnan = U.branches(frames[k][4], 2)
+        outside += int(np.count_nonzero(~ins & ~isnan))
+        inside += int(np.count_nonzero(ins))
+        nan += int(np.count_nonzero(isnan))
+        for ty in range(0, 2 * H, 8):
+            for tx in range(0, 2 * W, 8):
+                fallback += int(isnan[ty, tx] and ins[ty:ty + 8, tx:tx + 8].any())
+    assert outside > 0 and inside > 0 and nan > 0, (outside, inside, nan)   # no history (outside), history inside, NaN motion
+    assert fallback > 0
+
+
+@pytest.mark.parametrize("mode,options", [(0, None), (2, {"taa": 1})], ids=["mode0", "mode2-taa"])
+def test_frame_state_is_left_alone(mode, options):
+    """the same sequence with and without the calls: accumulation images, RGBA8 frames and the three AOV images of every frame are
+    bit-identical"""
+    with_calls = _sequence(96, 64, mode, 6, 0.003, options=options)
+    without = _sequence(96, 64, mode, 6, 0.003, options=options, upscale=False)
+    for k in range(6):
+        assert np.array_equal(with_calls[k][0].view(np.uint32), without[k][0].view(np.uint32)), k
+        assert np.array_equal(with_calls[k][1], without[k][1]), k
+        for a in (2, 3, 4):
+            assert np.array_equal(with_calls[k][a].view(np.uint16), without[k][a].view(np.uint16)), (k, a)
+    assert not np.array_equal(with_calls[-1][5], U.replicate(with_calls[-1][1]))   # (the calls did run)
+
+
+def test_frames_in_flight_are_bit_identical_to_the_synchronous_run():
+    """two frame contexts, frame k + 1 submitted before frame k is waited for, a call after each wait"""
+    sync = _pan()
+    fif = _sequence(96, 64, 2, 6, 0.003, frames_in_flight=2, asynchronous=True)
+    for k in range(6):
+        assert np.array_equal(sync[k][1], fif[k][1]), k
+        assert np.array_equal(sync[k][5], fif[k][5]), k
+
+
+def test_history_control():
+    """reset_history = 1 on call 3 gives the replication and call 4 uses call 3's output; initialize at another size starts over"""
+    base = _pan()
+    frames = _sequence(96, 64, 2, 5, 0.003, reset_calls=(3,))
+    for k in range(3):
+        assert np.array_equal(frames[k][5], base[k][5]), k
+    assert np.array_equal(frames[3][5], U.replicate(frames[3][1]))
+    assert not np.array_equal(base[3][5], U.replicate(base[3][1]))
+    _compare(frames, first=4)                                            # call 4 against the restatement fed call 3's output ...
+    other = U.taa_upscale(frames[4][1], base[3][5], frames[4][4], 2)     # ... which is not what the unbroken history gives
+    assert int(np.abs(other.astype(np.int32) - frames[4][5].astype(np.int32)).max()) > 1
+    s = scenes.grid(120, 60)
+    r = backend.RenderHip()
+    r.initialize(96, 64)
+    r.set_scene(s)
+    cfg = backend.RenderConfiguration(s.camera_params(), active_variant=abi.VARIANT_SIMPLE, reset_accumulation=True)
+    for _ in range(2):
+        r.render(cfg, spp=1)
+        r.taa_upscale()
+    r.initialize(40, 24)
+    r.render(cfg, spp=1)
+    fb = np.zeros((24, 40, 4), np.uint8)
+    r.readback_framebuffer(fb)
+    r.taa_upscale()
+    up = r.readback_upscaled()
+    r.close()
+    assert up.shape == (48, 80, 4) and np.array_equal(up, U.replicate(fb))
+
+
+def test_refusals():
+    s = scenes.grid(120, 60)
+    W, H = 32, 24
+    cfg = backend.RenderConfiguration(s.camera_params(), active_variant=abi.VARIANT_SIMPLE, reset_accumulation=True)
+
+    def handle(**kw):
+        r = backend.RenderHip(**kw)
+        r.initialize(W, H)
+        r.set_scene(s)
+        return r
+
+    def refused(r, fn, code, text):
+        try:
+            fn()
+        except backend.BackendError as e:
+            assert e.code == code, (e.code, r._L.rptr_hip_last_error(r._h))
+        else:
+            raise AssertionError("not refused: " + text.decode())
+        assert text in r._L.rptr_hip_last_error(r._h), r._L.rptr_hip_last_error(r._h)
+
+    INVALID, UNSUPPORTED = abi.RPTR_E_INVALID, abi.RPTR_E_UNSUPPORTED
+    r = handle()
+    refused(r, r.readback_upscaled, INVALID, b"no upscaled image")
+    refused(r, r.taa_upscale, INVALID, b"before a frame has finished")
+    r.render(cfg, spp=1)
+    refused(r, lambda: r.taa_upscale(factor=1), INVALID, b"factor = 1")
+    refused(r, lambda: r.taa_upscale(factor=3), INVALID, b"factor = 3")
+    refused(r, lambda: r.taa_upscale(abi.TaaUpscaleParams(2, 0, (0, 1))), INVALID, b"reserved must be 0")
+    refused(r, lambda: r.taa_upscale(abi.TaaUpscaleParams(2, 0, (7, 0))), INVALID, b"reserved must be 0")
+    refused(r, r.readback_upscaled, INVALID, b"no upscaled image")   # (a refused call leaves no image)
+    r.taa_upscale()
+    assert r.readback_upscaled().shape == (2 * H, 2 * W, 4)
+    short = np.zeros(16 * W * H - 1, np.uint8)
+    assert r._L.rptr_hip_readback_upscaled_u8(r._h, short.ctypes.data_as(C.c_void_p), short.size) == INVALID
+    assert b"too small" in r._L.rptr_hip_last_error(r._h)
+    assert not short.any()
+    r.close()
+    r = handle(options={"aovs": 0})
+    r.render(cfg, spp=1)
+    refused(r, r.taa_upscale, UNSUPPORTED, b'"aovs" is 0')
+    r.close()
+    r = handle(rank=0, world_size=2, stripe_rows=8)
+    r.render(cfg, spp=1)
+    refused(r, r.taa_upscale, UNSUPPORTED, b"world_size 1")
+    r.close()
+    r = handle(frames_in_flight=2)   # a newer frame on the waited frame's context rewrites its images
+    t0 = r.render_async(cfg, spp=1)
+    t1 = r.render_async(cfg, spp=1)
+    r.wait(t0)
+    t2 = r.render_async(cfg, spp=1)
+    refused(r, r.taa_upscale, INVALID, b"being overwritten by a newer frame in flight")
+    r.wait(t1)
+    r.wait(t2)
+    r.taa_upscale()
+    r.close()

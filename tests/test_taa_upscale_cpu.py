@@ -1,0 +1,200 @@
+"""Temporal upscaling without a GPU: the numpy restatement (tests/taa_upscale_ref.py) against the one the GPU TAA test trusts and on
+inputs whose answer is known, the C ABI of rptr_hip_taa_upscale, and the code-object facts of its kernels
+(tests/test_gpu_taa_upscale.py runs them)."""
+import ctypes as C
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import realtime_resolve_ref as R
+import taa_upscale_ref as U
+from realtimepathtracingresearchframework_amd import abi, backend, build
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _inputs(seed, W=24, H=16, factor=1):
+    """seeded random frame, history and motion; the motions cover zero, sub-pixel, more than 4 pixels, NaN and values that push the
+    reconstruction point outside [0, 1] (a motion m moves the point by m / 2 of the image, i.e. m W / 2 pixels)"""
+    rng = np.random.default_rng(seed)
+    pre = rng.integers(0, 256, (H, W, 4), dtype=np.uint8)
+    hist = rng.integers(0, 256, (factor * H, factor * W, 4), dtype=np.uint8)
+    mj = np.zeros((H, W, 4), np.float32)
+    kind = rng.integers(0, 5, (H, W))
+    sub = rng.uniform(-1.0, 1.0, (H, W, 2)) * np.array([2.0 / W, 2.0 / H]) * 0.9           # below one pixel
+    far = rng.uniform(4.0, 7.0, (H, W, 2)) * np.array([2.0 / W, 2.0 / H]) * rng.choice([-1.0, 1.0], (H, W, 2))
+    out = rng.uniform(2.0, 3.0, (H, W, 2)) * rng.choice([-1.0, 1.0], (H, W, 2))             # a whole image and more
+    mj[..., :2] = np.where((kind == 1)[..., None], sub, mj[..., :2])
+    mj[..., :2] = np.where((kind == 2)[..., None], far, mj[..., :2])
+    mj[..., :2] = np.where((kind == 3)[..., None], np.nan, mj[..., :2])
+    mj[..., :2] = np.where((kind == 4)[..., None], out, mj[..., :2])
+    mj = mj.astype(np.float16)   # what the AOV image holds
+    return pre, hist, mj, kind
+
+
+@pytest.mark.parametrize("seed", [1, 2, 3])
+def test_factor_one_is_the_taa_restatement_bit_for_bit(seed):
+    pre, hist, mj, kind = _inputs(seed)
+    assert all(np.count_nonzero(kind == k) > 20 for k in range(5))
+    inside, nan = U.branches(mj, 1)
+    m = mj[..., :2].astype(np.float32)
+    px = np.abs(m) * np.array([24 / 2.0, 16 / 2.0], np.float32)
+    with np.errstate(invalid="ignore"):
+        assert (px[kind == 1] < 1).all() and np.count_nonzero(px[kind == 1] > 0) > 0   # sub-pixel
+        assert (px[kind == 2].max(axis=-1) > 4).all()                                   # more than 4 pixels
+    assert nan[kind == 3].all() and not inside[kind == 3].any()                         # NaN fails the accept rule
+    assert not inside[kind == 4].any() and inside[kind == 0].all()                      # pushed outside / kept inside
+    assert np.count_nonzero(inside[kind == 2]) > 0                                      # long motions that stay inside reach the history
+    got = U.taa_upscale(pre, hist, mj, 1)
+    want = R.taa(pre, hist, mj)
+    assert got.dtype == np.uint8 and got.shape == want.shape
+    assert np.array_equal(got, want), int(np.count_nonzero(got != want))
+    assert not np.array_equal(got, pre)
+
+
+def test_uniform_frame_over_equal_history_is_the_replicated_frame():
+    """every tap reads the same value, so the history equals the frame; the box has no spread and the blend returns the value. Away
+    from the border: there taps and box pixels outside the image read zero. Without motion the Lanczos factors are 1 at the centre tap
+    and sin(k pi) elsewhere; a motion of 0.3 display pixels gives all hundred taps weight"""
+    W, H = 24, 16
+    pre = np.empty((H, W, 4), np.uint8)
+    pre[...] = (200, 96, 17, 255)
+    hist = U.replicate(pre)
+    b = 11   # the window reaches 10 texels before and 8 behind the reconstruction point
+    for shift in (0.0, 0.3):
+        mj = np.zeros((H, W, 4), np.float16)
+        mj[..., 0] = shift / W       # half of it, times 2 W display pixels
+        mj[..., 1] = -shift / H
+        out = U.taa_upscale(pre, hist, mj, 2)
+        assert out.shape == (2 * H, 2 * W, 4)
+        assert np.array_equal(out[b:-b, b:-b], U.replicate(pre)[b:-b, b:-b]), shift
+    assert not np.array_equal(out, U.replicate(pre))   # (with all taps weighted the border does differ: zeros come in)
+
+
+def test_no_history_is_np_repeat_twice():
+    pre = np.random.default_rng(5).integers(0, 256, (7, 9, 4), dtype=np.uint8)
+    want = np.repeat(np.repeat(pre, 2, axis=0), 2, axis=1)
+    got = U.replicate(pre, 2)
+    assert got.shape == (14, 18, 4) and np.array_equal(got, want)
+    assert np.array_equal(got[5, 12], pre[2, 6])
+
+
+def test_stride_two_taps_of_neighbouring_display_pixels_land_in_different_texels():
+    """a history that alternates per display pixel, a mid-grey frame, no motion: display pixel (X, Y) reads texels of its own parity
+    only (its taps lie two apart), so the four pixels of a 2x2 block see different histories -- a replication could not tell them apart"""
+    W, H = 24, 16
+    ys, xs = np.mgrid[0:2 * H, 0:2 * W]
+    hist = np.empty((2 * H, 2 * W, 4), np.uint8)
+    hist[...] = np.where(((xs + ys) & 1)[..., None] == 1, 160, 96)
+    pre = np.full((H, W, 4), 128, np.uint8)
+    pre[::2, ::3] = 100     # some spread, so the clamp box is open
+    pre[1::2, 1::3] = 156
+    mj = np.zeros((H, W, 4), np.float16)
+    out = U.taa_upscale(pre, hist, mj, 2).astype(np.int32)
+    block = out[12:14, 20:22, 0]
+    assert block[0, 0] != block[0, 1] and block[0, 0] != block[1, 0], block
+    assert block[0, 0] == block[1, 1] and block[0, 1] == block[1, 0], block   # the checkerboard's own symmetry
+    inner = out[10:-10, 10:-10, 0]
+    assert (inner[::2, ::2] != inner[::2, 1::2]).all() and (inner[::2, ::2] != inner[1::2, ::2]).all()
+    assert not np.array_equal(out, U.replicate(pre))
+
+
+# ---- the C ABI
+def test_entry_points_are_declared_exported_and_bound():
+    hdr = open(os.path.join(ROOT, "include", "rptr_hip.h")).read()
+    L = backend.load_library()
+    assert re.search(r"^void rptr_hip_taa_upscale_defaults\(RptrTaaUpscaleParams \*out\);", hdr, re.M)
+    assert re.search(r"^int rptr_hip_taa_upscale\(rptr_hip_t \*h, const RptrTaaUpscaleParams \*p", hdr, re.M)
+    assert re.search(r"^int rptr_hip_readback_upscaled_u8\(rptr_hip_t \*h, unsigned char \*rgba, size_t n_bytes\);", hdr, re.M)
+    for name, nargs in {"rptr_hip_taa_upscale_defaults": 1, "rptr_hip_taa_upscale": 2, "rptr_hip_readback_upscaled_u8": 3}.items():
+        assert name in abi.EXPORTED_SYMBOLS and hasattr(L, name), name
+        assert len(getattr(L, name).argtypes) == nargs, name
+    assert L.rptr_hip_option_count() == 22   # no option came with it
+    assert "taa_upscale" not in [L.rptr_hip_option_name(k).decode() for k in range(22)]
+
+
+def test_the_header_documents_the_struct_and_the_calls():
+    hdr = open(os.path.join(ROOT, "include", "rptr_hip.h")).read()
+    at = hdr.index("/* ---- temporal upscaling")
+    doc = hdr[at:hdr.index("int rptr_hip_readback_upscaled_u8", at)]
+    for word in ("render_upscale_factor = 2", "reset_history", "history", "2W x 2H", "RPTR_E_INVALID", "RPTR_E_UNSUPPORTED", "rptr_hip_taa_upscale_defaults",
+                 "rptr_hip_readback_upscaled_u8", "world_size", '"aovs"', "asynchronous", "INTEGRATION.md"):
+        assert word in doc, word
+    m = re.search(r"typedef struct RptrTaaUpscaleParams \{(.*?)\} RptrTaaUpscaleParams;", doc, re.S)
+    assert m and [f for f in re.findall(r"int32_t (\w+)", m.group(1))] == ["factor", "reset_history", "reserved"]
+
+
+def test_the_parameter_block_has_one_layout_in_c_and_in_ctypes(tmp_path):
+    src = tmp_path / "layout.c"
+    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "rptr_hip.h"\nint main(void) {\n'
+                   '    printf("%zu %zu %zu %zu", sizeof(RptrTaaUpscaleParams), offsetof(RptrTaaUpscaleParams, factor),\n'
+                   '           offsetof(RptrTaaUpscaleParams, reset_history), offsetof(RptrTaaUpscaleParams, reserved));\n    return 0;\n}\n')
+    exe = str(tmp_path / "layout")
+    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src), "-o", exe])
+    assert [int(x) for x in subprocess.check_output([exe]).split()] == [16, 0, 4, 8]
+    P = abi.TaaUpscaleParams
+    assert C.sizeof(P) == 16 and [n for n, _ in P._fields_] == ["factor", "reset_history", "reserved"]
+    assert (P.factor.offset, P.reset_history.offset, P.reserved.offset, P.reserved.size) == (0, 4, 8, 8)
+
+
+def test_defaults_and_null_handle():
+    L = backend.load_library()
+    p = abi.TaaUpscaleParams(9, 9, (9, 9))
+    L.rptr_hip_taa_upscale_defaults(C.byref(p))
+    assert (p.factor, p.reset_history, list(p.reserved)) == (2, 0, [0, 0])
+    L.rptr_hip_taa_upscale_defaults(None)   # (nothing to fill: no fault)
+    assert L.rptr_hip_taa_upscale(None, C.byref(p)) == abi.RPTR_E_INVALID
+    assert b"NULL handle" in L.rptr_hip_last_error(None)
+    assert L.rptr_hip_taa_upscale(None, None) == abi.RPTR_E_INVALID
+    buf = np.zeros(64, np.uint8)
+    assert L.rptr_hip_readback_upscaled_u8(None, buf.ctypes.data_as(C.c_void_p), buf.size) == abi.RPTR_E_INVALID
+
+
+def test_cpp_mirror_compiles_and_links(tmp_path):
+    """RenderHip::taa_upscale / taa_upscale_defaults / readback_upscaled (compiled and linked, not run: no device here)"""
+    src = tmp_path / "tu.cpp"
+    src.write_text('''#include "render_group.hpp"
+int main(int argc, char **) {
+    if (argc < 100) return 0;
+    rptr::RenderHip b;
+    RptrTaaUpscaleParams p = rptr::RenderHip::taa_upscale_defaults();
+    p.reset_history = 1;
+    b.taa_upscale(p);
+    std::vector<unsigned char> img(16);
+    return b.readback_upscaled(img.size(), img.data()) == 0 ? 0 : 1;
+}
+''')
+    exe = str(tmp_path / "tu")
+    libdir = os.path.dirname(build.LIB_PATH)
+    if not os.path.exists(build.LIB_PATH):
+        build.build_library()
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I" + os.path.join(libdir, "host"), str(src), "-o", exe, "-L" + libdir, "-lrptr_hip",
+                           "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"])
+    assert subprocess.call([exe]) == 0
+
+
+def test_the_kernels_use_no_scratch():
+    """rp_k_taa_upscale and rp_k_upscale_replicate in the gfx950 code object: no private segment; the upscaler's LDS is the history
+    window (32 rows of 40 words), the 6 x 6 float4 neighbourhood and the byte / 255 table -- 24 one-wave blocks per CU, six waves per SIMD.
+    Registers: at most 128, the step at which four waves per SIMD fit (512 / 128), the occupancy rp_k_taa runs at with the same tap loop"""
+    if not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-objdump") or shutil.which("bash") is None:
+        pytest.skip("no llvm-objdump")
+    if not os.path.exists(build.LIB_PATH):
+        build.build_library()
+    out = subprocess.run(["bash", os.path.join(ROOT, "tools", "kernel_regs.sh"), build.LIB_PATH], stdout=subprocess.PIPE, universal_newlines=True, check=True).stdout
+    regs = {}
+    for line in out.splitlines():
+        m = re.match(r"(\S+)\s+vgpr\s+(\d+)\s+sgpr\s+(\d+)\s+scratch\s+(\d+)\s+lds\s+(\d+)", line)
+        if m:
+            regs[m.group(1)] = tuple(int(x) for x in m.groups()[1:])
+    up = [v for k, v in regs.items() if "rp_k_taa_upscale" in k]
+    rep = [v for k, v in regs.items() if "rp_k_upscale_replicate" in k]
+    assert len(up) == 1 and len(rep) == 1, sorted(regs)
+    vgpr, _, scratch, lds = up[0]
+    assert scratch == 0 and rep[0][2] == 0
+    assert lds == 32 * 40 * 4 + 36 * 16 + 256 * 4, lds
+    assert vgpr <= 128, vgpr
