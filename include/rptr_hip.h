@@ -657,6 +657,48 @@ int rptr_hip_denoise(rptr_hip_t *h, const RptrDenoiseParams *p);
 int rptr_hip_readback_denoised_f32(rptr_hip_t *h, float *rgba, size_t n_floats);
 int rptr_hip_readback_denoised_u8(rptr_hip_t *h, unsigned char *rgba, size_t n_bytes);
 
+/* ---- the temporal denoiser: the denoiser above with the temporal half of SVGF in front of its passes. A call blends the frame's
+ * demodulated colour and the two moments of its luminance with what the previous call left -- the history, fetched along the frame's
+ * motion + jitter AOV with four bilinear taps that must agree with the pixel in normal and depth -- counts per pixel how many calls
+ * the history is long, and hands the a-trous passes the variance of the blended signal in place of one frame's 3x3 estimate. The passes
+ * and the finish are the denoiser's own. csrc/denoise_temporal.h states every operation, tests/denoise_temporal_ref.py restates it in
+ * numpy, and the stored images equal that restatement bit for bit. INTEGRATION.md "Temporal denoiser" lists what a host can rely on.
+ * The call is explicit, like rptr_hip_denoise, with the same source frame (the frame waited for last) and the same promises: it never
+ * touches the accumulation image, the RGBA8 frame, the AOV images, the reprojection / TAA / upscaler histories, frame_id / frame_offset
+ * or the statistics, and a host that never calls it launches nothing new. The result goes into the denoiser's output images:
+ * rptr_hip_readback_denoised_f32 / _u8 return the result of whichever of the two denoise calls ran last, with their staleness rule.
+ * History. The motion AOV describes the step from the previous FRAME's view to this one's, so the contract is one call per frame: a
+ * host that skipped a frame sets reset_history. The library does not guess from frame_id. A call has no history -- and its images then
+ * equal rptr_hip_denoise's with the same five leading parameters bit for bit -- in exactly these cases: it is the first one since
+ * rptr_hip_initialize (which drops and frees the history, whatever the new size); reset_history is 1; demodulate_albedo differs from
+ * the call that wrote the history (the stored colour would be in other units). An rptr_hip_denoise call between two temporal calls does
+ * not disturb the history, which keeps its own copy of normal + depth.
+ * Memory: two sets of history images, 80 bytes per pixel, on top of the denoiser's 72; allocated by the first call, freed with the
+ * handle's other frame-sized buffers.
+ * rptr_hip_denoise_temporal_defaults fills in the defaults below; rptr_hip_denoise_temporal(h, NULL) uses them.
+ * rptr_hip_readback_denoise_history_f32: the history the last temporal call left, W x H x 4 floats, per pixel the blended demodulated
+ * colour e' and the history length n' (1 = no history was found for the pixel, at most 255; all zero where the pixel is not surface).
+ * RPTR_E_INVALID: NULL handle; before a frame has finished; a parameter out of range or not finite; reserved != 0; the frame's images
+ * are being overwritten by a newer frame on the same frame context; the frame waited for last is not the last of its launch sequence;
+ * a history read-back before any temporal call since initialize.
+ * RPTR_E_UNSUPPORTED: option "aovs" = 0; world_size > 1; render_upscale_factor 2. */
+typedef struct RptrDenoiseTemporalParams { /* 64 bytes */
+    int32_t iterations;        /* as RptrDenoiseParams: 1..5, default 5 */
+    float sigma_luminance;     /* > 0, default 4 */
+    float sigma_depth;         /* > 0, default 1 */
+    int32_t normal_power_log2; /* 0..8, default 7 */
+    int32_t demodulate_albedo; /* 0 / 1, default 1 */
+    float alpha_color;         /* (0, 1], default 0.2: least weight of the new frame's colour */
+    float alpha_moments;       /* (0, 1], default 0.2: same for the two luminance moments */
+    float normal_threshold;    /* [-1, 1], default 0.9: a history tap needs dot(N_p, N_q) >= this */
+    float depth_tolerance;     /* >= 0, finite, default 0.1: ... and |z_q - z_p| <= depth_tolerance * z_p + gz_p */
+    int32_t reset_history;     /* 0 / 1, default 0 */
+    int32_t reserved[6];       /* must be 0 */
+} RptrDenoiseTemporalParams;
+void rptr_hip_denoise_temporal_defaults(RptrDenoiseTemporalParams *out);
+int rptr_hip_denoise_temporal(rptr_hip_t *h, const RptrDenoiseTemporalParams *p /* NULL = defaults */);
+int rptr_hip_readback_denoise_history_f32(rptr_hip_t *h, float *rgba, size_t n_floats);
+
 /* ---- temporal upscaling: the TAA pass at twice the render resolution (vulkan/processing/process_taa.comp with render_upscale_factor = 2,
  * the way the reference's application renders at half the display resolution in each axis and lets the history fill in the sub-pixel
  * detail). For a handle initialized at W x H a call makes a 2W x 2H RGBA8 image from the last finished frame's RGBA8 image (every

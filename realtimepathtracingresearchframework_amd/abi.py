@@ -238,6 +238,12 @@ class DenoiseParams(C.Structure):  # include/rptr_hip.h RptrDenoiseParams
                 ("demodulate_albedo", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
+class DenoiseTemporalParams(C.Structure):  # include/rptr_hip.h RptrDenoiseTemporalParams
+    _fields_ = [("iterations", C.c_int32), ("sigma_luminance", C.c_float), ("sigma_depth", C.c_float), ("normal_power_log2", C.c_int32),
+                ("demodulate_albedo", C.c_int32), ("alpha_color", C.c_float), ("alpha_moments", C.c_float), ("normal_threshold", C.c_float),
+                ("depth_tolerance", C.c_float), ("reset_history", C.c_int32), ("reserved", C.c_int32 * 6)]
+
+
 class LightSource(C.Structure):  # include/rptr_hip.h RptrLightSource: where one entry of RptrSceneDesc.lights came from
     _fields_ = [("v0", C.c_float * 3), ("v1", C.c_float * 3), ("v2", C.c_float * 3), ("instance", C.c_uint32), ("geometry", C.c_uint32),
                 ("triangle", C.c_uint32)]
@@ -279,6 +285,7 @@ assert C.sizeof(OcclusionParams) == 16
 assert C.sizeof(TaaUpscaleParams) == 16
 assert C.sizeof(LightSource) == 48
 assert C.sizeof(DenoiseParams) == 32
+assert C.sizeof(DenoiseTemporalParams) == 64
 assert C.sizeof(BaseMaterial) == 80
 assert C.sizeof(TriLightData) == 48
 assert C.sizeof(RenderRayQuery) == 32
@@ -298,6 +305,7 @@ EXPORTED_SYMBOLS = [
     "rptr_hip_initialize", "rptr_hip_set_scene", "rptr_hip_update_vertices", "rptr_hip_update_vertices_device", "rptr_hip_refit", "rptr_hip_set_params",
     "rptr_hip_render", "rptr_hip_render_async", "rptr_hip_render_batch_async", "rptr_hip_render_batch_cameras_async", "rptr_hip_wait", "rptr_hip_set_stage_timing", "rptr_hip_set_freeze_frame", "rptr_hip_set_option", "rptr_hip_get_option", "rptr_hip_option_count", "rptr_hip_option_name", "rptr_hip_set_rng_variant", "rptr_hip_set_bvh_policy", "rptr_hip_bvh_rebuild_count", "rptr_hip_update_instances", "rptr_hip_update_instances_device", "rptr_hip_set_tlas_policy", "rptr_hip_tlas_rebuild_count", "rptr_hip_set_light_sources", "rptr_hip_readback_lights", "rptr_hip_get_framebuffer_size", "rptr_hip_readback_f32", "rptr_hip_readback_u8", "rptr_hip_readback_aov",
     "rptr_hip_denoise_defaults", "rptr_hip_denoise", "rptr_hip_readback_denoised_f32", "rptr_hip_readback_denoised_u8",
+    "rptr_hip_denoise_temporal_defaults", "rptr_hip_denoise_temporal", "rptr_hip_readback_denoise_history_f32",
     "rptr_hip_taa_upscale_defaults", "rptr_hip_taa_upscale", "rptr_hip_readback_upscaled_u8",
     "rptr_hip_tile_rows", "rptr_hip_local_pixel_count", "rptr_hip_copy_tile_to_device", "rptr_hip_trace", "rptr_hip_trace_device", "rptr_hip_enable_ray_queries", "rptr_hip_render_ray_queries", "rptr_hip_trace_radiance", "rptr_hip_trace_radiance_device", "rptr_hip_render_radiance_queries", "rptr_hip_trace_surface", "rptr_hip_trace_surface_device", "rptr_hip_occlusion_defaults", "rptr_hip_trace_occlusion", "rptr_hip_trace_occlusion_device", "rptr_hip_set_light_sampling_variant", "rptr_hip_trace_counted",
     "rptr_hip_export_bvh", "rptr_hip_build_bvh_host", "rptr_hip_stats",

@@ -105,6 +105,10 @@ def load_library(path=None):
     L.rptr_hip_denoise.argtypes = [vp, C.POINTER(abi.DenoiseParams)]
     L.rptr_hip_readback_denoised_f32.argtypes = [vp, vp, C.c_size_t]
     L.rptr_hip_readback_denoised_u8.argtypes = [vp, vp, C.c_size_t]
+    L.rptr_hip_denoise_temporal_defaults.argtypes = [C.POINTER(abi.DenoiseTemporalParams)]
+    L.rptr_hip_denoise_temporal_defaults.restype = None
+    L.rptr_hip_denoise_temporal.argtypes = [vp, C.POINTER(abi.DenoiseTemporalParams)]
+    L.rptr_hip_readback_denoise_history_f32.argtypes = [vp, vp, C.c_size_t]
     L.rptr_hip_taa_upscale_defaults.argtypes = [C.POINTER(abi.TaaUpscaleParams)]
     L.rptr_hip_taa_upscale_defaults.restype = None
     L.rptr_hip_taa_upscale.argtypes = [vp, C.POINTER(abi.TaaUpscaleParams)]
@@ -424,6 +428,34 @@ class RenderHip:
         w, hgt, c = self.get_framebuffer_size()
         out = np.zeros((hgt, w, c), np.uint8)
         self._check(self._L.rptr_hip_readback_denoised_u8(self._h, out.ctypes.data_as(C.c_void_p), out.size))
+        return out
+
+    # ---- the temporal denoiser (include/rptr_hip.h rptr_hip_denoise_temporal; csrc/denoise_temporal.h)
+    def denoise_temporal(self, params=None, **fields):
+        """Denoises the frame the read-backs return (the frame waited for last) with the history the previous call left, fetched along
+        the frame's motion AOV, and leaves the next call's history; the result is read with readback_denoised_f32 / _u8. One call per
+        frame: pass reset_history = 1 for a frame that does not follow the previous call's frame (a skipped frame, a restarted
+        accumulation). params: an abi.DenoiseTemporalParams, or None for the library's defaults; keyword arguments override single
+        fields. The RGBA8 image goes through the render parameters of self.params as they are now. Returns the parameters used."""
+        p = abi.DenoiseTemporalParams()
+        if params is None:
+            self._L.rptr_hip_denoise_temporal_defaults(C.byref(p))
+        else:
+            C.memmove(C.byref(p), C.byref(params), C.sizeof(p))
+        for k, v in fields.items():
+            if k not in dict(abi.DenoiseTemporalParams._fields_) or k == "reserved":
+                raise TypeError("denoise_temporal: unknown parameter %r" % k)
+            setattr(p, k, v)
+        self._push_params()
+        self._check(self._L.rptr_hip_denoise_temporal(self._h, C.byref(p)))
+        return p
+
+    def readback_denoise_history(self):
+        """the history the last denoise_temporal() left as an (H, W, 4) float32 array: the blended demodulated colour and, in channel 3,
+        the history length (1: none was found for the pixel; 0 where the pixel is not surface)"""
+        w, hgt, c = self.get_framebuffer_size()
+        out = np.zeros((hgt, w, c), np.float32)
+        self._check(self._L.rptr_hip_readback_denoise_history_f32(self._h, out.ctypes.data_as(C.c_void_p), out.size))
         return out
 
     # ---- temporal 2x upscaling (include/rptr_hip.h rptr_hip_taa_upscale; csrc/taa_upscale.h)

@@ -248,8 +248,8 @@ static int check_finished_frame_with_aovs(rptr_hip *h, const char *who, const ch
         return fail(h, RPTR_E_UNSUPPORTED, "%s needs render_upscale_factor 1 (its RGBA8 image has the render resolution)", who);
     if (h->finished_serial == 0) return fail(h, RPTR_E_INVALID, "%s before a frame has finished (render, or wait for a ticket, first)", who);
     if (h->output_overwritten || h->aov_overwritten)
-        return fail(h, RPTR_E_INVALID, "the images of the last waited frame are being overwritten by a newer frame in flight on the same frame context: "
-                                       "%s before submitting that frame, or rptr_hip_wait for it first", verb);
+        return fail(h, RPTR_E_INVALID, "%s: the images of the last waited frame are being overwritten by a newer frame in flight on the same frame context: "
+                                       "%s before submitting that frame, or rptr_hip_wait for it first", who, verb);
     const FrameCtx &ac = h->ctx[(size_t)h->aov_ctx];
     if (h->output_ctx >= 0 && (h->output_ctx != h->aov_ctx || h->output_index != ac.batch_n - 1))
         return fail(h, RPTR_E_INVALID, "%s: the AOV images belong to the last frame of the launch sequence finished last, the frame waited "
@@ -269,28 +269,28 @@ void rptr_hip_denoise_defaults(RptrDenoiseParams *out) {
     out->demodulate_albedo = 1;
 }
 
-int rptr_hip_denoise(rptr_hip_t *h, const RptrDenoiseParams *p) {
-    if (!h) return fail(nullptr, RPTR_E_INVALID, "NULL handle");
-    if (!p) return fail(h, RPTR_E_INVALID, "rptr_hip_denoise: NULL parameters");
-    if (p->iterations < 1 || p->iterations > 5) return fail(h, RPTR_E_INVALID, "rptr_hip_denoise: iterations = %d is outside [1, 5]", p->iterations);
-    if (!(p->sigma_luminance > 0.0f) || !std::isfinite(p->sigma_luminance) || !(p->sigma_depth > 0.0f) || !std::isfinite(p->sigma_depth))
-        return fail(h, RPTR_E_INVALID, "rptr_hip_denoise: sigma_luminance and sigma_depth must be finite and > 0 (are %g, %g)", (double)p->sigma_luminance,
-                    (double)p->sigma_depth);
-    if (p->normal_power_log2 < 0 || p->normal_power_log2 > 8)
-        return fail(h, RPTR_E_INVALID, "rptr_hip_denoise: normal_power_log2 = %d is outside [0, 8]", p->normal_power_log2);
-    if (p->demodulate_albedo != 0 && p->demodulate_albedo != 1) return fail(h, RPTR_E_INVALID, "rptr_hip_denoise: demodulate_albedo must be 0 or 1");
-    if (p->reserved[0] || p->reserved[1] || p->reserved[2]) return fail(h, RPTR_E_INVALID, "rptr_hip_denoise: RptrDenoiseParams.reserved must be 0");
+// What the two denoise calls share: the checks of the five spatial parameters (the leading fields of both parameter structs), ...
+extern "C++" {
+static int check_denoise_params(rptr_hip *h, const char *who, const RptrDenoiseParams &p) {
+    if (p.iterations < 1 || p.iterations > 5) return fail(h, RPTR_E_INVALID, "%s: iterations = %d is outside [1, 5]", who, p.iterations);
+    if (!(p.sigma_luminance > 0.0f) || !std::isfinite(p.sigma_luminance) || !(p.sigma_depth > 0.0f) || !std::isfinite(p.sigma_depth))
+        return fail(h, RPTR_E_INVALID, "%s: sigma_luminance and sigma_depth must be finite and > 0 (are %g, %g)", who, (double)p.sigma_luminance,
+                    (double)p.sigma_depth);
+    if (p.normal_power_log2 < 0 || p.normal_power_log2 > 8)
+        return fail(h, RPTR_E_INVALID, "%s: normal_power_log2 = %d is outside [0, 8]", who, p.normal_power_log2);
+    if (p.demodulate_albedo != 0 && p.demodulate_albedo != 1) return fail(h, RPTR_E_INVALID, "%s: demodulate_albedo must be 0 or 1", who);
+    return RPTR_OK;
+}
+// ... the denoiser's images (made by the first call of either) and the kernels' arguments for the last finished frame, ...
+static int denoise_args(rptr_hip *h, const RptrDenoiseParams &p, RpDenoiseArgs &a) {
     int rc;
-    if ((rc = check_finished_frame_with_aovs(h, "rptr_hip_denoise", "denoise", "the albedo and normal + depth AOV images", true))) return rc;
     const FrameCtx &ac = h->ctx[(size_t)h->aov_ctx];
-    HIP_TRY(h, hipSetDevice(h->device));
     const size_t npix = (size_t)h->width * (size_t)h->height;
     if (!h->dn.out_u8) {
         if ((rc = dev_alloc(h, &h->dn.ev[0], npix, nullptr)) || (rc = dev_alloc(h, &h->dn.ev[1], npix, nullptr)) || (rc = dev_alloc(h, &h->dn.ndz, npix, nullptr)) ||
             (rc = dev_alloc(h, &h->dn.gz, npix, nullptr)) || (rc = dev_alloc(h, &h->dn.out_f32, npix, nullptr)) || (rc = dev_alloc(h, &h->dn.out_u8, npix, nullptr)))
             return rc;
     }
-    RpDenoiseArgs a;
     memset(&a, 0, sizeof(a));
     if ((rc = last_finished_image(h, &a.accum, &a.fb))) return rc; // (world_size 1: an image is the whole frame, npix pixels)
     a.albedo = ac.aov[0];
@@ -301,17 +301,25 @@ int rptr_hip_denoise(rptr_hip_t *h, const RptrDenoiseParams *p) {
     a.out_u8 = h->dn.out_u8;
     a.width = h->width;
     a.height = h->height;
-    a.sigma_luminance = p->sigma_luminance;
-    a.sigma_depth = p->sigma_depth;
-    a.normal_power_log2 = p->normal_power_log2;
-    a.demodulate = p->demodulate_albedo;
+    a.sigma_luminance = p.sigma_luminance;
+    a.sigma_depth = p.sigma_depth;
+    a.normal_power_log2 = p.normal_power_log2;
+    a.demodulate = p.demodulate_albedo;
     a.output_channel = h->params.output_channel;
     a.tone_mapping_mode = h->params.early_tone_mapping_mode;
     a.exposure_scale = (float)std::exp2((double)h->params.exposure);
+    return RPTR_OK;
+}
+static dim3 denoise_tiles(const rptr_hip *h) {
     const unsigned T = RP_DN_TILE;
-    const dim3 tiles(((unsigned)h->width + T - 1) / T, ((unsigned)h->height + T - 1) / T);
-    rp_launch_kernel(RpLaunch{tiles, h->stream, nullptr, nullptr}, rp_k_denoise_prepare, 256u, a, h->dn.ev[0]);
-    for (int i = 0; i < p->iterations; ++i) {
+    return dim3(((unsigned)h->width + T - 1) / T, ((unsigned)h->height + T - 1) / T);
+}
+// ... and the launches after prepare (or after rp_k_denoise_temporal in its place): the passes and finish
+static int denoise_filter_and_finish(rptr_hip *h, const RpDenoiseArgs &a, int iterations) {
+    const unsigned T = RP_DN_TILE;
+    const dim3 tiles = denoise_tiles(h);
+    const size_t npix = (size_t)h->width * (size_t)h->height;
+    for (int i = 0; i < iterations; ++i) {
         const int s = 1 << i;
         const float4 *in = h->dn.ev[i & 1];
         float4 *out = h->dn.ev[(i & 1) ^ 1];
@@ -325,17 +333,113 @@ int rptr_hip_denoise(rptr_hip_t *h, const RptrDenoiseParams *p) {
             rp_launch_kernel(RpLaunch{lattice, h->stream, nullptr, nullptr}, rp_k_denoise_pass<0>, 256u, a, in, out, s);
         }
     }
-    rp_launch_kernel(RpLaunch{dim3((unsigned)grid_for(h, npix)), h->stream, nullptr, nullptr}, rp_k_denoise_finish, 256u, a, (const float4 *)h->dn.ev[p->iterations & 1]);
+    rp_launch_kernel(RpLaunch{dim3((unsigned)grid_for(h, npix)), h->stream, nullptr, nullptr}, rp_k_denoise_finish, 256u, a, (const float4 *)h->dn.ev[iterations & 1]);
     HIP_TRY(h, hipGetLastError());
     h->dn.serial = h->finished_serial;
     return RPTR_OK;
 }
+} // extern "C++"
+
+int rptr_hip_denoise(rptr_hip_t *h, const RptrDenoiseParams *p) {
+    if (!h) return fail(nullptr, RPTR_E_INVALID, "NULL handle");
+    if (!p) return fail(h, RPTR_E_INVALID, "rptr_hip_denoise: NULL parameters");
+    int rc;
+    if ((rc = check_denoise_params(h, "rptr_hip_denoise", *p))) return rc;
+    if (p->reserved[0] || p->reserved[1] || p->reserved[2]) return fail(h, RPTR_E_INVALID, "rptr_hip_denoise: RptrDenoiseParams.reserved must be 0");
+    if ((rc = check_finished_frame_with_aovs(h, "rptr_hip_denoise", "denoise", "the albedo and normal + depth AOV images", true))) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    RpDenoiseArgs a;
+    if ((rc = denoise_args(h, *p, a))) return rc;
+    rp_launch_kernel(RpLaunch{denoise_tiles(h), h->stream, nullptr, nullptr}, rp_k_denoise_prepare, 256u, a, h->dn.ev[0]);
+    return denoise_filter_and_finish(h, a, p->iterations);
+}
+
+// ---- the temporal denoiser (denoise_temporal.h): rp_k_denoise_temporal in prepare's place -- it blends the frame with the history the
+// previous call left, along the motion AOV, and leaves the next call's -- then the same passes and finish
+void rptr_hip_denoise_temporal_defaults(RptrDenoiseTemporalParams *out) {
+    if (!out) return;
+    memset(out, 0, sizeof(*out));
+    out->iterations = 5;
+    out->sigma_luminance = 4.0f;
+    out->sigma_depth = 1.0f;
+    out->normal_power_log2 = 7;
+    out->demodulate_albedo = 1;
+    out->alpha_color = 0.2f;
+    out->alpha_moments = 0.2f;
+    out->normal_threshold = 0.9f;
+    out->depth_tolerance = 0.1f;
+}
+
+int rptr_hip_denoise_temporal(rptr_hip_t *h, const RptrDenoiseTemporalParams *p) {
+    const char *who = "rptr_hip_denoise_temporal";
+    if (!h) return fail(nullptr, RPTR_E_INVALID, "NULL handle");
+    RptrDenoiseTemporalParams defaults;
+    rptr_hip_denoise_temporal_defaults(&defaults);
+    if (!p) p = &defaults;
+    RptrDenoiseParams sp; // the five spatial parameters
+    memset(&sp, 0, sizeof(sp));
+    sp.iterations = p->iterations;
+    sp.sigma_luminance = p->sigma_luminance;
+    sp.sigma_depth = p->sigma_depth;
+    sp.normal_power_log2 = p->normal_power_log2;
+    sp.demodulate_albedo = p->demodulate_albedo;
+    int rc;
+    if ((rc = check_denoise_params(h, who, sp))) return rc;
+    if (!(p->alpha_color > 0.0f && p->alpha_color <= 1.0f) || !(p->alpha_moments > 0.0f && p->alpha_moments <= 1.0f))
+        return fail(h, RPTR_E_INVALID, "%s: alpha_color and alpha_moments must be in (0, 1] (are %g, %g)", who, (double)p->alpha_color, (double)p->alpha_moments);
+    if (!(p->normal_threshold >= -1.0f && p->normal_threshold <= 1.0f))
+        return fail(h, RPTR_E_INVALID, "%s: normal_threshold = %g is outside [-1, 1]", who, (double)p->normal_threshold);
+    if (!(p->depth_tolerance >= 0.0f) || !std::isfinite(p->depth_tolerance))
+        return fail(h, RPTR_E_INVALID, "%s: depth_tolerance must be finite and >= 0 (is %g)", who, (double)p->depth_tolerance);
+    if (p->reset_history != 0 && p->reset_history != 1) return fail(h, RPTR_E_INVALID, "%s: reset_history must be 0 or 1", who);
+    for (int r : p->reserved)
+        if (r) return fail(h, RPTR_E_INVALID, "%s: RptrDenoiseTemporalParams.reserved must be 0", who);
+    if ((rc = check_finished_frame_with_aovs(h, who, "denoise", "the albedo, normal + depth and motion + jitter AOV images", true))) return rc;
+    const FrameCtx &ac = h->ctx[(size_t)h->aov_ctx];
+    HIP_TRY(h, hipSetDevice(h->device));
+    RpDenoiseArgs a;
+    if ((rc = denoise_args(h, sp, a))) return rc;
+    const size_t npix = (size_t)h->width * (size_t)h->height;
+    if (!h->dt.hndz[1]) {
+        for (int k = 0; k < 2; ++k)
+            if ((rc = dev_alloc(h, &h->dt.he[k], npix, nullptr)) || (rc = dev_alloc(h, &h->dt.hm[k], npix, nullptr)) || (rc = dev_alloc(h, &h->dt.hndz[k], npix, nullptr)))
+                return rc;
+        h->dt.cur = 0;
+        h->dt.have = false;
+    }
+    const int in = h->dt.cur, out = in ^ 1;
+    RpDenoiseTemporalArgs t;
+    memset(&t, 0, sizeof(t));
+    t.mj = ac.aov[2];
+    t.he_in = h->dt.he[in];
+    t.hm_in = h->dt.hm[in];
+    t.hndz_in = h->dt.hndz[in];
+    t.he_out = h->dt.he[out];
+    t.hm_out = h->dt.hm[out];
+    t.hndz_out = h->dt.hndz[out];
+    t.alpha_color = p->alpha_color;
+    t.alpha_moments = p->alpha_moments;
+    t.normal_threshold = p->normal_threshold;
+    t.depth_tolerance = p->depth_tolerance;
+    t.have_history = (h->dt.have && !p->reset_history && h->dt.demodulate == p->demodulate_albedo) ? 1 : 0;
+    rp_launch_kernel(RpLaunch{denoise_tiles(h), h->stream, nullptr, nullptr}, rp_k_denoise_temporal, 256u, a, t, h->dn.ev[0]);
+    h->dt.cur = out;
+    h->dt.have = true;
+    h->dt.demodulate = p->demodulate_albedo;
+    return denoise_filter_and_finish(h, a, p->iterations);
+}
+
+int rptr_hip_readback_denoise_history_f32(rptr_hip_t *h, float *rgba, size_t n_floats) {
+    if (!h || !rgba) return fail(h, RPTR_E_INVALID, "NULL argument");
+    if (!h->dt.have) return fail(h, RPTR_E_INVALID, "no denoise history: call rptr_hip_denoise_temporal first");
+    return readback_rows<float4>(h, h->dt.he[h->dt.cur], reinterpret_cast<float4 *>(rgba), n_floats / 4);
+}
 
 extern "C++" {
 static int check_denoised(rptr_hip *h) {
-    if (!h->dn.out_u8 || h->dn.serial == 0) return fail(h, RPTR_E_INVALID, "no denoised image: call rptr_hip_denoise first");
+    if (!h->dn.out_u8 || h->dn.serial == 0) return fail(h, RPTR_E_INVALID, "no denoised image: call rptr_hip_denoise_temporal or rptr_hip_denoise first");
     if (h->dn.serial != h->finished_serial)
-        return fail(h, RPTR_E_INVALID, "the denoised image is stale: a later frame has finished since rptr_hip_denoise ran; call it again for that frame");
+        return fail(h, RPTR_E_INVALID, "the denoised image is stale: a later frame has finished since the denoise call ran; call it again for that frame");
     return RPTR_OK;
 }
 }

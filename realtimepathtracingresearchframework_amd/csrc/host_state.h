@@ -384,6 +384,16 @@ struct rptr_hip {
         uchar4 *out_u8 = nullptr;
         uint64_t serial = 0;                // finished_serial of the frame the images were made from (0: none)
     } dn;
+    // the temporal denoiser (denoise_temporal.h, rptr_hip_denoise_temporal): two sets of history images on top of dn's, made by the first
+    // call and freed with the other frame-sized buffers; a call reads set `cur` and writes set cur ^ 1, which becomes `cur`
+    struct DenoiseTemporal {
+        float4 *he[2] = {nullptr, nullptr};   // (e', n')
+        float2 *hm[2] = {nullptr, nullptr};   // (m1', m2')
+        float4 *hndz[2] = {nullptr, nullptr}; // (N, z) of the call's frame: the history's own copy (rptr_hip_denoise rewrites dn.ndz)
+        int cur = 0;
+        bool have = false;                    // set `cur` holds a call's output: the next call's history, what the read-back returns
+        int demodulate = 0;                   // ... and the demodulate_albedo it was written with (another one: the call has no history)
+    } dt;
     // temporal 2x upscaling (taa_upscale.h, rptr_hip_taa_upscale): two display-size RGBA8 images, made by the first call and freed with
     // the other frame-sized buffers; a call reads the history in img[cur] and writes img[cur ^ 1], which becomes `cur`
     struct TaaUpscale {

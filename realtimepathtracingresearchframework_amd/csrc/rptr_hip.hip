@@ -12,6 +12,7 @@
 #include "realtime_resolve.h"
 #include "taa_upscale.h"
 #include "denoise.h"
+#include "denoise_temporal.h"
 #include "surface_query.h"
 #include "occlusion_query.h"
 #include "launch.h"
@@ -307,6 +308,7 @@ int rptr_hip_initialize(rptr_hip_t *h, int fb_width, int fb_height) {
     h->output_ctx = -1;
     h->last_resolved = nullptr;
     h->dn = decltype(h->dn)(); // (the denoiser's images: allocated by the first rptr_hip_denoise, freed with the rest above)
+    h->dt = decltype(h->dt)(); // (the temporal denoiser's history: allocated by the first rptr_hip_denoise_temporal, freed with the rest above)
     h->up = decltype(h->up)(); // (the upscaler's images: allocated by the first rptr_hip_taa_upscale, freed with the rest above)
     h->finished_serial = 0;
     h->rt = decltype(h->rt)(); // (mode-2 images: allocated by the first frame that needs them, freed with the rest above)

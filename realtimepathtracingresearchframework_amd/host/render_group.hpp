@@ -90,6 +90,7 @@ public:
     RenderStats frame(CommandStream *cmd_stream, const RenderConfiguration &config) {
         if (size() > 1 || !cmd_stream) {
             const RenderStats s = render(config);
+            if (denoise_temporal_every_frame_) denoise_temporal(config.reset_accumulation);
             if (upscale_every_frame_) taa_upscale(config.reset_accumulation);
             return s;
         }
@@ -219,6 +220,21 @@ public:
     void denoise(const RptrDenoiseParams &p) { ranks_[0]->denoise(p); }
     size_t readback_denoised(size_t buffer_size, float *buffer) { return ranks_[0]->readback_denoised(buffer_size, buffer); }
     size_t readback_denoised(size_t buffer_size, unsigned char *buffer) { return ranks_[0]->readback_denoised(buffer_size, buffer); }
+    // ... and so does the temporal denoiser (rptr_hip_denoise_temporal refuses world_size > 1); its result is read with readback_denoised
+    void denoise_temporal(const RptrDenoiseTemporalParams &p) { ranks_[0]->denoise_temporal(p); }
+    void denoise_temporal(bool reset_history) {
+        RptrDenoiseTemporalParams p = denoise_temporal_params_;
+        p.reset_history = reset_history ? 1 : 0;
+        denoise_temporal(p);
+    }
+    // with every frame of frame(), as upscale_every_frame below; for one device only
+    void denoise_temporal_every_frame(bool on, const RptrDenoiseTemporalParams &p = RenderHip::denoise_temporal_defaults()) {
+        if (on && size() > 1) throw std::runtime_error("denoise_temporal_every_frame needs one device (rptr_hip_denoise_temporal refuses world_size > 1)");
+        denoise_temporal_every_frame_ = on;
+        denoise_temporal_params_ = p;
+        ranks_[0]->denoise_temporal_every_frame(on, p);
+    }
+    size_t readback_denoise_history(size_t buffer_size, float *buffer) { return ranks_[0]->readback_denoise_history(buffer_size, buffer); }
     // temporal 2x upscaling works on one GPU's whole frame as well (rptr_hip_taa_upscale refuses world_size > 1)
     void taa_upscale(const RptrTaaUpscaleParams &p) { ranks_[0]->taa_upscale(p); }
     void taa_upscale(bool reset_history) {
@@ -257,6 +273,8 @@ private:
     double rays_ = 0.0;
     uint64_t counted_serial_ = 0;
     bool upscale_every_frame_ = false;
+    bool denoise_temporal_every_frame_ = false;
+    RptrDenoiseTemporalParams denoise_temporal_params_ = RenderHip::denoise_temporal_defaults();
 };
 
 } // namespace rptr

@@ -16,6 +16,7 @@
 namespace rptr {
 
 static_assert(sizeof(RptrOcclusionParams) == 16, "RptrOcclusionParams: flags, alpha_cutoff, two reserved words (include/rptr_hip.h)");
+static_assert(sizeof(RptrDenoiseTemporalParams) == 64, "RptrDenoiseTemporalParams: ten parameters and six reserved words (include/rptr_hip.h)");
 static_assert(sizeof(RptrTaaUpscaleParams) == 16, "RptrTaaUpscaleParams: factor, reset_history, two reserved words (include/rptr_hip.h)");
 static_assert(sizeof(RptrSurfaceHit) == 96, "RptrSurfaceHit: six 16-byte rows per surface query (include/rptr_hip.h)");
 
@@ -316,6 +317,7 @@ public:
         get_framebuffer_size(whc);
         const size_t need = size_t(whc[0]) * whc[1] * 4;
         if (buffer_size < need) return 0;
+        if (denoise_temporal_every_frame_) flush_pipeline(); // (the frames in flight are collected, and denoised, first)
         check(rptr_hip_readback_denoised_f32(h_, buffer, buffer_size));
         return need;
     }
@@ -324,7 +326,36 @@ public:
         get_framebuffer_size(whc);
         const size_t need = size_t(whc[0]) * whc[1] * 4;
         if (buffer_size < need) return 0;
+        if (denoise_temporal_every_frame_) flush_pipeline(); // (the frames in flight are collected, and denoised, first)
         check(rptr_hip_readback_denoised_u8(h_, buffer, buffer_size));
+        return need;
+    }
+
+    // The temporal denoiser (include/rptr_hip.h rptr_hip_denoise_temporal): the frame the read-backs return -- everything in flight is
+    // finished first -- blended with the history the previous call left, into the denoiser's images (readback_denoised); one call per
+    // frame, p.reset_history = 1 for a frame that does not follow the previous call's (a restarted accumulation, a skipped frame).
+    static RptrDenoiseTemporalParams denoise_temporal_defaults() {
+        RptrDenoiseTemporalParams p;
+        rptr_hip_denoise_temporal_defaults(&p);
+        return p;
+    }
+    void denoise_temporal(const RptrDenoiseTemporalParams &p) {
+        flush_pipeline();
+        check(rptr_hip_denoise_temporal(h_, &p));
+    }
+    // ... or with every frame of the reference's loop, as upscale_every_frame below: issued when the frame it belongs to has been
+    // collected, with `p` and reset_history = that frame's reset_accumulation.
+    void denoise_temporal_every_frame(bool on, const RptrDenoiseTemporalParams &p = denoise_temporal_defaults()) {
+        denoise_temporal_every_frame_ = on;
+        denoise_temporal_params_ = p;
+    }
+    size_t readback_denoise_history(size_t buffer_size, float *buffer) { // RGBA32F: the blended demodulated colour, the history length
+        uint32_t whc[3];
+        get_framebuffer_size(whc);
+        const size_t need = size_t(whc[0]) * whc[1] * 4;
+        if (buffer_size < need) return 0;
+        if (denoise_temporal_every_frame_) flush_pipeline();
+        check(rptr_hip_readback_denoise_history_f32(h_, buffer, buffer_size));
         return need;
     }
 
@@ -486,7 +517,12 @@ private:
         }
         if (rc != RPTR_OK && !(rc == RPTR_E_INVALID && std::string(rptr_hip_last_error(h_)).find("not in flight") != std::string::npos)) check(rc);
     }
-    void frame_collected(bool restarted) { // upscale_every_frame: the call that belongs to the frame just collected
+    void frame_collected(bool restarted) { // upscale_every_frame, denoise_temporal_every_frame: the call that belongs to the frame just collected
+        if (denoise_temporal_every_frame_) {
+            RptrDenoiseTemporalParams p = denoise_temporal_params_;
+            p.reset_history = restarted ? 1 : 0;
+            check(rptr_hip_denoise_temporal(h_, &p));
+        }
         if (!upscale_every_frame_) return;
         RptrTaaUpscaleParams p = taa_upscale_defaults();
         p.reset_history = restarted ? 1 : 0;
@@ -524,6 +560,8 @@ private:
     bool pending_[MAX_SWAP_BUFFERS] = {false, false};
     bool slot_reset_[MAX_SWAP_BUFFERS] = {false, false}; // reset_accumulation of the frame submitted on each swap index
     bool upscale_every_frame_ = false;
+    bool denoise_temporal_every_frame_ = false;
+    RptrDenoiseTemporalParams denoise_temporal_params_{};
     bool asynchronous_ = false;
     uint32_t frame_id_ = 0;
     uint64_t stats_serial_ = 0;

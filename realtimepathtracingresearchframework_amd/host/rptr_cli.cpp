@@ -1,7 +1,7 @@
 // rptr_cli.cpp -- the reference's headless run modes through the C ABI (binary: bin/rptr_hip):
 //
 //   <scene> = the reference's .vks file (textures in <name>_textures/) or the flat dump scenes.py writes (.rpsc)
-//   rptr_hip <scene> --validation <prefix> [--validation-spp n] [--img w h] [--pfm] [--denoise iterations | --taa-upscale]
+//   rptr_hip <scene> --validation <prefix> [--validation-spp n] [--img w h] [--pfm] [--denoise iterations | --denoise-temporal iterations | --taa-upscale]
 //   rptr_hip <scene.rpsc> --profiling <csv prefix> [--profiling-fps f] [--profiling-img <prefix>] [--profiling-frames n]
 //            [--animate-wave amplitude kx] [--synchronous] [--fly-through] [--frames-in-flight n [--frames-per-launch b]]
 //   common:  [--eye x y z] [--center x y z] [--up x y z] [--fov deg] [--variant gltf|diffuse|gltf-transmission] [--batch-spp k] [--every-frame]
@@ -67,6 +67,20 @@ static int g_denoise_iterations = 0;
 // are the upscaled ones, at twice --img; the history restarts with the frames that restart the accumulation (the first one, a new
 // keyframe, moved geometry, a moved camera unless the history is reprojected). The float images stay the frame's own. Not with --denoise.
 static bool g_taa_upscale = false;
+// --denoise-temporal <iterations> (this host's): every frame goes through rptr_hip_denoise_temporal as it is collected (the library's
+// defaults and that many passes; one frame per launch sequence), the history restarting with the frames that restart the accumulation,
+// and the images written are the denoised ones. Not with --denoise, --taa-upscale or several devices.
+static int g_denoise_temporal_iterations = 0;
+static RptrDenoiseTemporalParams denoise_temporal_params() {
+    RptrDenoiseTemporalParams p = rptr::RenderHip::denoise_temporal_defaults();
+    p.iterations = g_denoise_temporal_iterations;
+    return p;
+}
+static void denoise_temporal(rptr::RenderGroup &backend, bool reset_history) {
+    RptrDenoiseTemporalParams p = denoise_temporal_params();
+    p.reset_history = reset_history ? 1 : 0;
+    backend.denoise_temporal(p);
+}
 static void save_image(rptr::RenderGroup &backend, OutputFormat format, const std::string &prefix, int number, const std::string &suffix, int width, int height,
                        std::vector<float> &img) {
     char name[32];
@@ -78,17 +92,18 @@ static void save_image(rptr::RenderGroup &backend, OutputFormat format, const st
         dp.iterations = g_denoise_iterations;
         backend.denoise(dp);
     }
+    const bool denoised = g_denoise_iterations > 0 || g_denoise_temporal_iterations > 0;
     if (format == FORMAT_PNG && g_taa_upscale) {
         std::vector<unsigned char> rgba8((size_t)width * height * 16);
         if (backend.readback_upscaled(rgba8.size(), rgba8.data()) != rgba8.size()) throw std::runtime_error("read-back failed");
         ok = rptr::write_png(base, 2u * (unsigned)width, 2u * (unsigned)height, 4, rgba8.data());
     } else if (format == FORMAT_PNG) {
         std::vector<unsigned char> rgba8((size_t)width * height * 4);
-        if ((g_denoise_iterations > 0 ? backend.readback_denoised(rgba8.size(), rgba8.data()) : backend.readback_framebuffer(rgba8.size(), rgba8.data())) != rgba8.size())
+        if ((denoised ? backend.readback_denoised(rgba8.size(), rgba8.data()) : backend.readback_framebuffer(rgba8.size(), rgba8.data())) != rgba8.size())
             throw std::runtime_error("read-back failed");
         ok = rptr::write_png(base, (unsigned)width, (unsigned)height, 4, rgba8.data());
     } else {
-        if ((g_denoise_iterations > 0 ? backend.readback_denoised(img.size(), img.data()) : backend.readback_framebuffer(img.size(), img.data())) != img.size())
+        if ((denoised ? backend.readback_denoised(img.size(), img.data()) : backend.readback_framebuffer(img.size(), img.data())) != img.size())
             throw std::runtime_error("read-back failed");
         ok = format == FORMAT_PFM ? rptr::write_pfm(base, (unsigned)width, (unsigned)height, 4, img.data())
                                   : rptr::write_exr<float>(base, (unsigned)width, (unsigned)height, 4, img.data());
@@ -199,6 +214,7 @@ int main(int argc, char **argv) {
         else if (a == "--profiling-count") { need(1); profiling_frames = std::atoi(argv[++i]); have_profiling_options = true; } // (this host's: frames of a run without keyframes)
         else if (a == "--animate-wave") { need(2); wave_amp = (float)std::atof(argv[++i]); wave_k = (float)std::atof(argv[++i]); }
         else if (a == "--denoise") { need(1); g_denoise_iterations = std::atoi(argv[++i]); if (g_denoise_iterations < 1 || g_denoise_iterations > 5) { std::fprintf(stderr, "--denoise takes 1..5 iterations\n"); return 2; } }
+        else if (a == "--denoise-temporal") { need(1); g_denoise_temporal_iterations = std::atoi(argv[++i]); if (g_denoise_temporal_iterations < 1 || g_denoise_temporal_iterations > 5) { std::fprintf(stderr, "--denoise-temporal takes 1..5 iterations\n"); return 2; } }
         else if (a == "--taa-upscale") g_taa_upscale = true;
         else if (a == "--img") { need(2); width = std::atoi(argv[++i]); height = std::atoi(argv[++i]); }
         else if (a == "--eye") { vec3(eye); got_eye = true; }
@@ -350,6 +366,18 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "--taa-upscale and --denoise cannot be combined: the denoised image has the render resolution, the upscaler reads the frame's own\n");
         return 2;
     }
+    if (g_denoise_temporal_iterations > 0 && g_denoise_iterations > 0) {
+        std::fprintf(stderr, "--denoise-temporal and --denoise cannot be combined: both write the denoised images, choose one\n");
+        return 2;
+    }
+    if (g_denoise_temporal_iterations > 0 && g_taa_upscale) {
+        std::fprintf(stderr, "--denoise-temporal and --taa-upscale cannot be combined: the denoised image has the render resolution, the upscaler reads the frame's own\n");
+        return 2;
+    }
+    if (g_denoise_temporal_iterations > 0 && devices.size() > 1) {
+        std::fprintf(stderr, "--denoise-temporal needs one device (rptr_hip_denoise_temporal refuses world_size > 1)\n");
+        return 2;
+    }
     if (g_taa_upscale && devices.size() > 1) {
         std::fprintf(stderr, "--taa-upscale needs one device (rptr_hip_taa_upscale refuses world_size > 1)\n");
         return 2;
@@ -357,7 +385,7 @@ int main(int argc, char **argv) {
     if (want_help) scene_path.clear(); // prints the usage
     if (scene_path.empty() || (int)validation + (int)profiling + (int)data_capture != 1 || batch_spp < 1 || width < 1 || height < 1 || (profiling && profiling_frames < 1)) {
         std::fprintf(stderr, "usage: rptr_hip <scene.rpsc> (--validation <prefix> [--validation-spp n] | --profiling <csv prefix> [--profiling-fps f] "
-                             "[--profiling-img <prefix>] [--keyframe [len:]file.ini ...] [--profiling-count n] [--synchronous] [--fly-through] [--frames-in-flight n [--frames-per-launch b]] [--animate-wave a k]) [--img w h] [--denoise iterations | --taa-upscale] [--eye x y z] [--center x y z] "
+                             "[--profiling-img <prefix>] [--keyframe [len:]file.ini ...] [--profiling-count n] [--synchronous] [--fly-through] [--frames-in-flight n [--frames-per-launch b]] [--animate-wave a k]) [--img w h] [--denoise iterations | --denoise-temporal iterations | --taa-upscale] [--eye x y z] [--center x y z] "
                              "[--up x y z] [--fov deg] [--variant gltf|diffuse] [--batch-spp k] [--every-frame] [--exr|--pfm|--png] [--config file.ini ...] [--sky-data <dir of the Hosek-Wilkie data headers>]\n"
                              "       rptr_hip <scene.rpsc> --data-capture <prefix> [--data-capture-spp n] [--data-capture-no-rgba] [--data-capture-no-aovs] "
                              "[--data-capture-albedo-roughness] [--data-capture-normal-depth] [--data-capture-motion] [--keyframe ...]   (EXR images per keyframe)\n"
@@ -496,7 +524,7 @@ int main(int argc, char **argv) {
             // every frame bit-identical to the frame rendered on its own) with four sequences in flight, and collected in order -- the images
             // are written at the same sample counts, with the same bits, as by the loop of synchronous frames below (--synchronous; a frozen
             // frame repeats its samples and cannot share a sequence).
-            if (!synchronous && !freeze_frame && !g_taa_upscale && (backend.size() == 1 || !every_frame)) { // (a group's gather assembles the LAST frame of a sequence; the upscaler wants every frame as it finishes)
+            if (!synchronous && !freeze_frame && !g_taa_upscale && g_denoise_temporal_iterations == 0 && (backend.size() == 1 || !every_frame)) { // (a group's gather assembles the LAST frame of a sequence; the upscaler and the temporal denoiser want every frame as it finishes)
                 const int total_frames = (target_spp + batch_spp - 1) / batch_spp;
                 // (a launch sequence must fit the sample slots the handle holds: 16 up to ~2.9 Mpixel per rank, fewer above -- 12 at 1440p, 5 at 4K,
                 // rptr_hip_get_option "sample_slots"; a frame of more samples than that is split by the library itself, one frame per sequence)
@@ -535,6 +563,7 @@ int main(int argc, char **argv) {
             while (accumulated < target_spp) {
                 const rptr::RenderStats st = backend.render(cfg); // params.batch_spp samples
                 if (g_taa_upscale) backend.taa_upscale(cfg.reset_accumulation);
+                if (g_denoise_temporal_iterations > 0) denoise_temporal(backend, cfg.reset_accumulation);
                 cfg.reset_accumulation = false;
                 accumulated = freeze_frame ? accumulated + batch_spp : st.spp; // (a frozen frame repeats its samples: the application counts, app_state.cpp)
                 gpu_ms += st.render_time;
@@ -714,7 +743,7 @@ int main(int argc, char **argv) {
             // reprojection_mode 2 folds each frame into the one before it: one frame per launch sequence (include/rptr_hip.h)
             bool realtime = base.params.reprojection_mode == 2;
             for (const rptr::HostConfig &st : frames) realtime = realtime || st.params.reprojection_mode == 2;
-            if (realtime || g_taa_upscale) frames_per_launch = 1; // (the upscaler reads the AOV images, which are those of a sequence's last frame)
+            if (realtime || g_taa_upscale || g_denoise_temporal_iterations > 0) frames_per_launch = 1; // (the upscaler and the temporal denoiser read the AOV images, which are those of a sequence's last frame)
             struct Pending {
                 rptr::RenderGroup::Sequence q;
                 int first;
@@ -741,6 +770,7 @@ int main(int argc, char **argv) {
                     const FramePlan &fp = plan[(size_t)(p.first + k)];
                     const rptr::RenderStats st = backend.collect_frame(p.q, k);
                     if (g_taa_upscale) backend.taa_upscale(fp.reset);
+                    if (g_denoise_temporal_iterations > 0) denoise_temporal(backend, fp.reset);
                     gpu_ms += st.render_time;
                     const auto now = std::chrono::steady_clock::now();
                     std::fprintf(csv, "%d,%d,%d,%g,%g\n", ++collected, fp.keyframe_no, fp.accumulated, st.render_time, std::chrono::duration<double, std::milli>(now - last).count());
@@ -776,6 +806,7 @@ int main(int argc, char **argv) {
         // frames in flight, statistics two frames late) or, --synchronous, without one
         rptr::CommandStream display_stream;
         backend.upscale_every_frame(g_taa_upscale); // (issued as each frame is collected: render_group.hpp frame)
+        backend.denoise_temporal_every_frame(g_denoise_temporal_iterations > 0, denoise_temporal_params());
         rptr::CommandStream *const cmd_stream = synchronous ? nullptr : &display_stream;
         if (!rest.empty() || fly_through) { // (a short warm-up when the run is a measurement: the adaptive tail hand-over settles in two frames)
             apply_key(plan[0].key);
