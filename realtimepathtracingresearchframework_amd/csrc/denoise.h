@@ -104,17 +104,14 @@ RP_DEV float4 rp_dn_signal(const RpDenoiseArgs &a, size_t i, bool surface) {
     return make_float4(c.x / d.x, c.y / d.y, c.z / d.z, 0.0f);
 }
 
-// One block = 16 x 16 adjacent pixels; lum and (N, z) (zeros: outside the image, or not surface) of the tile and a 1-pixel apron go
-// through LDS.
-__global__ __launch_bounds__(256) void rp_k_denoise_prepare(RpDenoiseArgs a, float4 *ev) {
-    constexpr int SPAN = RP_DN_TILE + 2;
-    __shared__ float s_lum[SPAN * SPAN];
-    __shared__ float4 s_nd[SPAN * SPAN];
+// What prepare and rp_k_denoise_temporal (denoise_temporal.h) share. One block = 16 x 16 adjacent pixels; lum and (N, z) (zeros: outside
+// the image, or not surface) of the tile and a 1-pixel apron go through LDS, in two arrays of RP_DN_SPAN * RP_DN_SPAN the kernel declares.
+#define RP_DN_SPAN (RP_DN_TILE + 2)
+RP_DEV void rp_dn_stage(const RpDenoiseArgs &a, float *s_lum, float4 *s_nd) {
     const int W = a.width, H = a.height;
     const int tx0 = int(blockIdx.x) * RP_DN_TILE, ty0 = int(blockIdx.y) * RP_DN_TILE;
-    const int t = int(threadIdx.x);
-    for (int k = t; k < SPAN * SPAN; k += 256) {
-        const int sy = k / SPAN, sx = k - sy * SPAN;
+    for (int k = int(threadIdx.x); k < RP_DN_SPAN * RP_DN_SPAN; k += 256) {
+        const int sy = k / RP_DN_SPAN, sx = k - sy * RP_DN_SPAN;
         const int gx = tx0 + sx - 1, gy = ty0 + sy - 1;
         float lum = 0.0f;
         float4 ndz = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -130,35 +127,45 @@ __global__ __launch_bounds__(256) void rp_k_denoise_prepare(RpDenoiseArgs a, flo
         s_nd[k] = ndz;
     }
     __syncthreads();
+}
+// v_s and gz (the header's "Prepare") of the surface pixel at cell c of the staged arrays, ndp = s_nd[c]
+RP_DEV void rp_dn_spatial(const float *s_lum, const float4 *s_nd, int c, float4 ndp, float &v_s, float &gz) {
+    float s1 = 0.0f, s2 = 0.0f;
+    int n = 0;
+    for (int dy = -1; dy <= 1; ++dy)
+        for (int dx = -1; dx <= 1; ++dx) {
+            const int q = c + dy * RP_DN_SPAN + dx;
+            const float4 ndq = s_nd[q];
+            if (ndq.w > 0.0f && ((ndp.x * ndq.x + ndp.y * ndq.y) + ndp.z * ndq.z) > 0.0f) {
+                const float l = s_lum[q];
+                s1 += l;
+                s2 += l * l;
+                ++n;
+            }
+        }
+    const float m1 = s1 / float(n), m2 = s2 / float(n); // (n >= 1: p itself)
+    v_s = fmaxf(m2 - m1 * m1, 0.0f);
+    gz = 0.0f;
+    const float zr = s_nd[c + 1].w, zd = s_nd[c + RP_DN_SPAN].w;
+    if (zr > 0.0f) gz = fmaxf(gz, fabsf(zr - ndp.w));
+    if (zd > 0.0f) gz = fmaxf(gz, fabsf(zd - ndp.w));
+}
+
+__global__ __launch_bounds__(256) void rp_k_denoise_prepare(RpDenoiseArgs a, float4 *ev) {
+    __shared__ float s_lum[RP_DN_SPAN * RP_DN_SPAN];
+    __shared__ float4 s_nd[RP_DN_SPAN * RP_DN_SPAN];
+    rp_dn_stage(a, s_lum, s_nd);
+    const int t = int(threadIdx.x);
     const int lx = t & (RP_DN_TILE - 1), ly = t / RP_DN_TILE;
-    const int px = tx0 + lx, py = ty0 + ly;
-    if (px >= W || py >= H) return;
-    const size_t i = size_t(py) * size_t(W) + size_t(px);
-    const int c = (ly + 1) * SPAN + (lx + 1);
+    const int px = int(blockIdx.x) * RP_DN_TILE + lx, py = int(blockIdx.y) * RP_DN_TILE + ly;
+    if (px >= a.width || py >= a.height) return;
+    const size_t i = size_t(py) * size_t(a.width) + size_t(px);
+    const int c = (ly + 1) * RP_DN_SPAN + (lx + 1);
     const float4 ndp = s_nd[c];
     const bool surface = ndp.w > 0.0f;
     float4 e = rp_dn_signal(a, i, surface);
     float gz = 0.0f;
-    if (surface) {
-        float s1 = 0.0f, s2 = 0.0f;
-        int n = 0;
-        for (int dy = -1; dy <= 1; ++dy)
-            for (int dx = -1; dx <= 1; ++dx) {
-                const int q = c + dy * SPAN + dx;
-                const float4 ndq = s_nd[q];
-                if (ndq.w > 0.0f && ((ndp.x * ndq.x + ndp.y * ndq.y) + ndp.z * ndq.z) > 0.0f) {
-                    const float l = s_lum[q];
-                    s1 += l;
-                    s2 += l * l;
-                    ++n;
-                }
-            }
-        const float m1 = s1 / float(n), m2 = s2 / float(n); // (n >= 1: p itself)
-        e.w = fmaxf(m2 - m1 * m1, 0.0f);
-        const float zr = s_nd[c + 1].w, zd = s_nd[c + SPAN].w;
-        if (zr > 0.0f) gz = fmaxf(gz, fabsf(zr - ndp.w));
-        if (zd > 0.0f) gz = fmaxf(gz, fabsf(zd - ndp.w));
-    }
+    if (surface) rp_dn_spatial(s_lum, s_nd, c, ndp, e.w, gz);
     ev[i] = e;
     a.gz[i] = gz;
     a.ndz[i] = ndp;

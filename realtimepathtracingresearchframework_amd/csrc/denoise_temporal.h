@@ -35,12 +35,13 @@
 // The history ping-pongs between two sets of images: a call reads one and writes the other, no thread reads what another stores.
 //
 // Layout. Prepare's: one block = 256 threads = 16 x 16 adjacent pixels, lum and (N, z) of the tile and a 1-pixel apron staged in LDS
-// (18 x 18 x 20 bytes = 6.3 KB) for v_s and gz. The four history taps are gathered from global memory where the motion points: Hndz
-// (16 bytes) of every tap in the image first, He (16 bytes) and Hm (8 bytes) of the valid ones after the tests. Neighbouring lanes'
-// taps are neighbours for a smooth motion, so a wave's 16-byte loads cover whole 128-byte lines and the four taps of a pixel share
-// lines with its neighbours' -- staging a window as rp_k_taa does would save nothing but L1 hits and would need the tile's motion to
-// be nearly uniform. Per pixel: 40 bytes in (accumulation, three AOVs), 40 unique bytes of history for a smooth motion, 76 bytes out:
-// ~160 bytes, estimated; profiles/denoise_temporal_notes.md has what was measured, and the kernel's registers and LDS (no scratch).
+// (18 x 18 x 20 bytes = 6.3 KB) for v_s and gz, by the two functions both kernels call (denoise.h rp_dn_stage, rp_dn_spatial). The four
+// history taps are gathered from global memory where the motion points: Hndz (16 bytes) of every tap in the image first, He (16 bytes)
+// and Hm (8 bytes) of the valid ones after the tests. Neighbouring lanes' taps are neighbours for a smooth motion, so a wave's 16-byte
+// loads cover whole 128-byte lines and the four taps of a pixel share lines with its neighbours' -- staging a window as rp_k_taa does
+// would save nothing but L1 hits and would need the tile's motion to be nearly uniform. Per pixel: 40 bytes in (accumulation, three
+// AOVs), 40 unique bytes of history for a smooth motion, 76 bytes out: ~160 bytes, estimated; profiles/denoise_temporal_notes.md has
+// what was measured, and the kernel's registers and LDS (no scratch).
 #pragma once
 #include "denoise.h"
 
@@ -56,36 +57,18 @@ struct RpDenoiseTemporalArgs {
     int have_history;
 };
 
-// rp_k_denoise_prepare's staging and its v_s / gz, then steps 1 to 7 of the header
+// steps 1 to 7 of the header
 __global__ __launch_bounds__(256) void rp_k_denoise_temporal(RpDenoiseArgs a, RpDenoiseTemporalArgs h, float4 *ev) {
-    constexpr int SPAN = RP_DN_TILE + 2;
-    __shared__ float s_lum[SPAN * SPAN];
-    __shared__ float4 s_nd[SPAN * SPAN];
+    __shared__ float s_lum[RP_DN_SPAN * RP_DN_SPAN];
+    __shared__ float4 s_nd[RP_DN_SPAN * RP_DN_SPAN];
+    rp_dn_stage(a, s_lum, s_nd);
     const int W = a.width, H = a.height;
-    const int tx0 = int(blockIdx.x) * RP_DN_TILE, ty0 = int(blockIdx.y) * RP_DN_TILE;
     const int t = int(threadIdx.x);
-    for (int k = t; k < SPAN * SPAN; k += 256) {
-        const int sy = k / SPAN, sx = k - sy * SPAN;
-        const int gx = tx0 + sx - 1, gy = ty0 + sy - 1;
-        float lum = 0.0f;
-        float4 ndz = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (gx >= 0 && gy >= 0 && gx < W && gy < H) {
-            const size_t g = size_t(gy) * size_t(W) + size_t(gx);
-            const float4 nd = rp_half4_to_float4(a.nd[g]);
-            if (rp_dn_surface(nd, a.albedo[g])) {
-                lum = rp_dn_lum(rp_dn_signal(a, g, true));
-                ndz = nd;
-            }
-        }
-        s_lum[k] = lum;
-        s_nd[k] = ndz;
-    }
-    __syncthreads();
     const int lx = t & (RP_DN_TILE - 1), ly = t / RP_DN_TILE;
-    const int px = tx0 + lx, py = ty0 + ly;
+    const int px = int(blockIdx.x) * RP_DN_TILE + lx, py = int(blockIdx.y) * RP_DN_TILE + ly;
     if (px >= W || py >= H) return;
     const size_t i = size_t(py) * size_t(W) + size_t(px);
-    const int c = (ly + 1) * SPAN + (lx + 1);
+    const int c = (ly + 1) * RP_DN_SPAN + (lx + 1);
     const float4 ndp = s_nd[c];
     const bool surface = ndp.w > 0.0f;
     float4 e = rp_dn_signal(a, i, surface);
@@ -93,25 +76,8 @@ __global__ __launch_bounds__(256) void rp_k_denoise_temporal(RpDenoiseArgs a, Rp
     float4 he = make_float4(0.f, 0.f, 0.f, 0.f);
     float2 hm = make_float2(0.f, 0.f);
     if (surface) {
-        float s1 = 0.0f, s2 = 0.0f;
-        int n = 0;
-        for (int dy = -1; dy <= 1; ++dy)
-            for (int dx = -1; dx <= 1; ++dx) {
-                const int q = c + dy * SPAN + dx;
-                const float4 ndq = s_nd[q];
-                if (ndq.w > 0.0f && ((ndp.x * ndq.x + ndp.y * ndq.y) + ndp.z * ndq.z) > 0.0f) {
-                    const float l = s_lum[q];
-                    s1 += l;
-                    s2 += l * l;
-                    ++n;
-                }
-            }
-        const float sm1 = s1 / float(n), sm2 = s2 / float(n); // (n >= 1: p itself)
-        const float v_s = fmaxf(sm2 - sm1 * sm1, 0.0f);
-        const float zr = s_nd[c + 1].w, zd = s_nd[c + SPAN].w;
-        if (zr > 0.0f) gz = fmaxf(gz, fabsf(zr - ndp.w));
-        if (zd > 0.0f) gz = fmaxf(gz, fabsf(zd - ndp.w));
-
+        float v_s;
+        rp_dn_spatial(s_lum, s_nd, c, ndp, v_s, gz);
         const float l = s_lum[c];
         float n1 = 1.0f, ac = 1.0f, m1 = l, m2 = l * l;
         if (h.have_history) {

@@ -269,8 +269,15 @@ void rptr_hip_denoise_defaults(RptrDenoiseParams *out) {
     out->demodulate_albedo = 1;
 }
 
-// What the two denoise calls share: the checks of the five spatial parameters (the leading fields of both parameter structs), ...
+// What the two denoise calls share: the five spatial parameters (the leading fields of both parameter structs) and their checks, ...
 extern "C++" {
+template <class To, class From> static void copy_spatial_params(To &to, const From &from) {
+    to.iterations = from.iterations;
+    to.sigma_luminance = from.sigma_luminance;
+    to.sigma_depth = from.sigma_depth;
+    to.normal_power_log2 = from.normal_power_log2;
+    to.demodulate_albedo = from.demodulate_albedo;
+}
 static int check_denoise_params(rptr_hip *h, const char *who, const RptrDenoiseParams &p) {
     if (p.iterations < 1 || p.iterations > 5) return fail(h, RPTR_E_INVALID, "%s: iterations = %d is outside [1, 5]", who, p.iterations);
     if (!(p.sigma_luminance > 0.0f) || !std::isfinite(p.sigma_luminance) || !(p.sigma_depth > 0.0f) || !std::isfinite(p.sigma_depth))
@@ -359,11 +366,9 @@ int rptr_hip_denoise(rptr_hip_t *h, const RptrDenoiseParams *p) {
 void rptr_hip_denoise_temporal_defaults(RptrDenoiseTemporalParams *out) {
     if (!out) return;
     memset(out, 0, sizeof(*out));
-    out->iterations = 5;
-    out->sigma_luminance = 4.0f;
-    out->sigma_depth = 1.0f;
-    out->normal_power_log2 = 7;
-    out->demodulate_albedo = 1;
+    RptrDenoiseParams sp;
+    rptr_hip_denoise_defaults(&sp);
+    copy_spatial_params(*out, sp);
     out->alpha_color = 0.2f;
     out->alpha_moments = 0.2f;
     out->normal_threshold = 0.9f;
@@ -378,11 +383,7 @@ int rptr_hip_denoise_temporal(rptr_hip_t *h, const RptrDenoiseTemporalParams *p)
     if (!p) p = &defaults;
     RptrDenoiseParams sp; // the five spatial parameters
     memset(&sp, 0, sizeof(sp));
-    sp.iterations = p->iterations;
-    sp.sigma_luminance = p->sigma_luminance;
-    sp.sigma_depth = p->sigma_depth;
-    sp.normal_power_log2 = p->normal_power_log2;
-    sp.demodulate_albedo = p->demodulate_albedo;
+    copy_spatial_params(sp, *p);
     int rc;
     if ((rc = check_denoise_params(h, who, sp))) return rc;
     if (!(p->alpha_color > 0.0f && p->alpha_color <= 1.0f) || !(p->alpha_moments > 0.0f && p->alpha_moments <= 1.0f))
@@ -485,7 +486,7 @@ int rptr_hip_taa_upscale(rptr_hip_t *h, const RptrTaaUpscaleParams *p) {
     if (p->reset_history || !h->up.have)
         rp_launch_kernel(RpLaunch{dim3((unsigned)grid_for(h, 4 * npix)), h->stream, nullptr, nullptr}, rp_k_upscale_replicate, 256u, h->width, h->height, pre, out);
     else {
-        const unsigned T = RP_TU_TILE;
+        const unsigned T = RP_TAA_TILE;
         const dim3 tiles((2u * (unsigned)h->width + T - 1) / T, (2u * (unsigned)h->height + T - 1) / T);
         rp_launch_kernel(RpLaunch{tiles, h->stream, nullptr, nullptr}, rp_k_taa_upscale, 64u, h->width, h->height, pre, (const uchar4 *)h->up.img[h->up.cur],
                          (const uint2 *)ac.aov[2], out);

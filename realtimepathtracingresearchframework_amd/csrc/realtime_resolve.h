@@ -229,35 +229,52 @@ __global__ __launch_bounds__(64) void rp_k_reproject(RpFrame f, RpReprojectArgs 
 // ------------------------------------------------------------------ TAA (vulkan/processing/process_taa.comp)
 // Runs after the resolve on the RGBA8 frame, when option "taa" is 1 in mode 2 and frame_id (after the call) > 1 (process_taa.cpp:92).
 // History: the previous frame's post-TAA RGBA8 image (render_targets[!active_render_target], the screen sampler; texelFetch of RGBA8 =
-// byte / 255). Deviations from the reference, both stated:
+// byte / 255). taa_upscale.h states every operation of the pass for a render_upscale_factor F; rp_taa_pass<F> below is that text.
+// Deviations from the reference, both stated:
 //   - process_taa.comp:91 reads the 3x3 neighbours from the frame buffer it stores to in place -- a race between invocations. Here `pre`
 //     (the frame before the pass) is read and `out` written, so every neighbour is the pre-TAA value.
 //   - its 3x3 motion loop (:63-71) loads the CENTRE pixel nine times (fb_pixel / render_upscale_factor, no offset): kept as written, so
 //     the motion is the centre's.
-// render_upscale_factor is 1 here (a frame renders and shows at one resolution; option "taa" with factor 2 is refused). The pass at
-// twice the render resolution is a call of its own on a finished frame: taa_upscale.h.
-// Cost (same frame): 122 us. 100 Lanczos taps per pixel, each an LDS read of the staged history texel plus four LDS reads of the
-// byte / 255 table and four multiply-adds: ~500 LDS reads per pixel, estimated ~50 us of LDS issue alone, the rest VALU. Taps that fall
-// outside the tile's 24 x 24 window (motion differing by more than 3 pixels inside a tile) read global memory instead. Estimated, not
-// measured with counters.
-#define RP_TAA_WIN 24 // history texels staged per tile and axis (the 8 pixels' 10-tap windows + 3 pixels of motion spread each side)
+// render_upscale_factor is 1 in a frame (it renders and shows at one resolution; option "taa" with factor 2 is refused): rp_k_taa. The
+// pass at twice the render resolution is a call of its own on a finished frame: rp_k_taa_upscale, taa_upscale.h.
+// Cost of rp_k_taa (same frame): 122 us. 100 Lanczos taps per pixel, each an LDS read of the staged history texel plus four LDS reads of
+// the byte / 255 table and four multiply-adds: ~500 LDS reads per pixel, estimated ~50 us of LDS issue alone, the rest VALU. Estimated,
+// not measured with counters.
+//
+// Layout, for both factors. One block = one 8 x 8 tile of DISPLAY pixels (F W x F H of them over a W x H frame) = one wave. Staged in
+// LDS: the render pixels under the tile and one each side as float4, the byte / 255 table, and a window of history texels placed by the
+// motion of the tile's first pixel. The tile's ten stride-F taps per axis span 8 + 9 F texels; with 3 texels of motion spread each side
+// that is 23 of 24 at factor 1 and 32 of 32 at factor 2. The window's rows are PITCH words apart: a half-wave's lanes (8 columns x 4 rows
+// of the tile) read texels whose addresses differ by lx + PITCH * ly, and both 24 and 40 put the four rows into 32 different banks (32
+// would put them into the same eight). Taps outside the window (motions that differ by more than 3 display pixels inside a tile, NaN
+// motion of the first pixel) read global memory: the same values.
+#define RP_TAA_TILE RP_RT_TILE // display pixels per block and axis (8; a frame launches rp_k_taa on rp_k_reproject's grid of tiles)
+template <int F> struct RpTaaLayout {
+    static constexpr int SHIFT = F == 1 ? 0 : 1;    // log2(F): display pixel p lies over render pixel p >> SHIFT
+    static constexpr int PRE = RP_TAA_TILE / F + 2; // render pixels staged per axis: the tile's 8 / F and one each side
+    static constexpr int WIN = F == 1 ? 24 : 32;    // history texels staged per axis
+    static constexpr int PITCH = F == 1 ? 24 : 40;  // words between the window's rows in LDS (see above)
+    static constexpr int LEAD = 5 * F + 3;          // the window starts this many texels before the first pixel's ceil(pt): its first tap (-5 F) and 3 of spread
+};
 RP_DEV float rp_lanczos_weight(float x, float r) { // :28-31
     const float pi = 3.14159265358979323846f;
     if (x == 0.0f) return 1.0f;
     return r * sinf(x * pi) * sinf((x / r) * pi) / (pi * pi * x * x);
 }
-__global__ __launch_bounds__(64) void rp_k_taa(RpFrame f, const uchar4 *pre, const uchar4 *hist, const uint2 *mj, uchar4 *out, uchar4 *out_copy) {
-    __shared__ float4 s_pre[RP_RT_SPAN * RP_RT_SPAN];
-    __shared__ uchar4 s_hist[RP_TAA_WIN * RP_TAA_WIN];
-    __shared__ int s_base[2];
+// pre, mj: W x H; hist, out, out_copy (a second image that gets the same texels, or NULL): F W x F H
+template <int F> RP_DEV void rp_taa_pass(int W, int H, const uchar4 *pre, const uchar4 *hist, const uint2 *mj, uchar4 *out, uchar4 *out_copy) {
+    using L = RpTaaLayout<F>;
+    __shared__ float4 s_pre[L::PRE * L::PRE];
+    __shared__ uchar4 s_hist[L::WIN * L::PITCH];
     __shared__ float s_unorm[256]; // byte / 255 (texelFetch of RGBA8), the same IEEE quotients without a division per tap
-    const int W = f.width, H = f.height;
-    const int tx0 = int(blockIdx.x) * RP_RT_TILE, ty0 = int(blockIdx.y) * RP_RT_TILE;
+    const int DW = F * W, DH = F * H;
+    const int tx0 = int(blockIdx.x) * RP_TAA_TILE, ty0 = int(blockIdx.y) * RP_TAA_TILE; // (multiples of F: the tile covers whole F x F blocks)
     const int t = int(threadIdx.x);
+    const float fw = float(DW), fh = float(DH);
     for (int k = t; k < 256; k += 64) s_unorm[k] = float(k) / 255.0f;
-    for (int k = t; k < RP_RT_SPAN * RP_RT_SPAN; k += 64) {
-        const int sy = k / RP_RT_SPAN, sx = k - sy * RP_RT_SPAN;
-        const int gx = tx0 + sx - 1, gy = ty0 + sy - 1;
+    for (int k = t; k < L::PRE * L::PRE; k += 64) {
+        const int sy = k / L::PRE, sx = k - sy * L::PRE;
+        const int gx = (tx0 >> L::SHIFT) + sx - 1, gy = (ty0 >> L::SHIFT) + sy - 1;
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f); // imageLoad outside the image: zero
         if (gx >= 0 && gy >= 0 && gx < W && gy < H) {
             const uchar4 b = pre[size_t(gy) * size_t(W) + size_t(gx)];
@@ -265,42 +282,38 @@ __global__ __launch_bounds__(64) void rp_k_taa(RpFrame f, const uchar4 *pre, con
         }
         s_pre[k] = v;
     }
-    // The history taps of the tile: the 10 x 10 windows of its pixels lie in a 24 x 24 region around the first pixel's window when the
-    // motions inside the tile differ by less than 4 pixels (a smooth pan); that region is staged in LDS, taps outside it read global
-    // memory. Either way the same texel values are read.
+    // the window: where the first pixel's taps begin (every thread computes the same two integers)
+    int bx, by;
     {
-        const float2 m0 = rp_half2_lo(mj[size_t(ty0) * size_t(W) + size_t(tx0)].x);
-        const float bpx = (((float(tx0) + 0.5f) / float(W) + 0.5f * m0.x) * float(W)) - 0.5f;
-        const float bpy = (((float(ty0) + 0.5f) / float(H) + 0.5f * m0.y) * float(H)) - 0.5f;
-        const int bx = rp_trunc_i(ceilf(bpx)) - 8, by = rp_trunc_i(ceilf(bpy)) - 8;
-        if (t == 0) {
-            s_base[0] = bx;
-            s_base[1] = by;
-        }
-        for (int k = t; k < RP_TAA_WIN * RP_TAA_WIN; k += 64) {
-            const int qy = by + k / RP_TAA_WIN, qx = bx + k % RP_TAA_WIN;
-            s_hist[k] = (qx >= 0 && qy >= 0 && qx < W && qy < H) ? hist[size_t(qy) * size_t(W) + size_t(qx)] : make_uchar4(0, 0, 0, 0);
+        const float2 m0 = rp_half2_lo(mj[size_t(ty0 >> L::SHIFT) * size_t(W) + size_t(tx0 >> L::SHIFT)].x);
+        const float bpx = (((float(tx0) + 0.5f) / fw + 0.5f * m0.x) * fw) - 0.5f;
+        const float bpy = (((float(ty0) + 0.5f) / fh + 0.5f * m0.y) * fh) - 0.5f;
+        bx = rp_trunc_i(ceilf(bpx)) - L::LEAD;
+        by = rp_trunc_i(ceilf(bpy)) - L::LEAD;
+        for (int k = t; k < L::WIN * L::WIN; k += 64) {
+            const int wy = k / L::WIN, wx = k % L::WIN;
+            const int qy = by + wy, qx = bx + wx;
+            s_hist[wy * L::PITCH + wx] = (qx >= 0 && qy >= 0 && qx < DW && qy < DH) ? hist[size_t(qy) * size_t(DW) + size_t(qx)] : make_uchar4(0, 0, 0, 0);
         }
     }
     __syncthreads();
     const int lx = t & 7, ly = t >> 3;
     const int px = tx0 + lx, py = ty0 + ly;
-    if (px >= W || py >= H) return;
-    const size_t i = size_t(py) * size_t(W) + size_t(px);
-    const int c = (ly + 1) * RP_RT_SPAN + (lx + 1);
-    const int bx = s_base[0], by = s_base[1];
+    if (px >= DW || py >= DH) return;
+    const size_t i = size_t(py) * size_t(DW) + size_t(px);
+    const size_t ri = size_t(py >> L::SHIFT) * size_t(W) + size_t(px >> L::SHIFT); // the render pixel under this display pixel
+    const int c = ((ly >> L::SHIFT) + 1) * L::PRE + ((lx >> L::SHIFT) + 1);
     float4 col = s_pre[c];
-    float2 motion = rp_half2_lo(mj[i].x);
+    float2 motion = rp_half2_lo(mj[ri].x);
     float motion_len = motion.x * motion.x + motion.y * motion.y;
     for (int k = 0; k < 9; ++k) { // :63-71 as written: the centre, nine times
-        const float2 m = rp_half2_lo(mj[i].x);
+        const float2 m = rp_half2_lo(mj[ri].x);
         const float ml = m.x * m.x + m.y * m.y;
         if (ml > motion_len) {
             motion = m;
             motion_len = ml;
         }
     }
-    const float fw = float(W), fh = float(H);
     const float spx = (float(px) + 0.5f) / fw, spy = (float(py) + 0.5f) / fh;
     const float rpx = spx + 0.5f * motion.x, rpy = spy + 0.5f * motion.y;
     float4 hc = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -308,41 +321,40 @@ __global__ __launch_bounds__(64) void rp_k_taa(RpFrame f, const uchar4 *pre, con
     if (rpx >= 0.0f && rpy >= 0.0f && rpx <= 1.0f && rpy <= 1.0f) { // lanczos(reconstruction_point, 5) (:35-51, 82)
         const float ptx = rpx * fw - 0.5f, pty = rpy * fh - 0.5f;
         const float cpx = ceilf(ptx), cpy = ceilf(pty);
-        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-        float total = 0.0f;
         // lanczosWeight(vec2) is a product of one factor per axis: the 10 + 10 factors are evaluated once (the same values the
-        // reference's 100 taps compute, in the same products)
+        // reference's 100 taps compute, in the same products). At F = 1 the division is by 1.0f: exact, and the compiler drops it
         float wx[10], wy[10];
         for (int o = 0; o < 10; ++o) {
-            wx[o] = rp_lanczos_weight((float(o - 5) + cpx) - ptx, 5.0f);
-            wy[o] = rp_lanczos_weight((float(o - 5) + cpy) - pty, 5.0f);
+            wx[o] = rp_lanczos_weight(((float(F * (o - 5)) + cpx) - ptx) / float(F), 5.0f);
+            wy[o] = rp_lanczos_weight(((float(F * (o - 5)) + cpy) - pty) / float(F), 5.0f);
         }
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        float total = 0.0f;
         for (int oy = -5; oy < 5; ++oy)
             for (int ox = -5; ox < 5; ++ox) {
-                const float npx = float(ox) + cpx, npy = float(oy) + cpy;
+                const float npx = float(F * ox) + cpx, npy = float(F * oy) + cpy;
                 const float w = wx[ox + 5] * wy[oy + 5];
                 const int qx = rp_trunc_i(npx), qy = rp_trunc_i(npy);
                 uchar4 b = make_uchar4(0, 0, 0, 0);
                 const unsigned wxi = unsigned(qx - bx), wyi = unsigned(qy - by);
-                if (wxi < unsigned(RP_TAA_WIN) && wyi < unsigned(RP_TAA_WIN))
-                    b = s_hist[wyi * RP_TAA_WIN + wxi];
-                else if (qx >= 0 && qy >= 0 && qx < W && qy < H)
-                    b = hist[size_t(qy) * size_t(W) + size_t(qx)];
-                const float4 v = make_float4(s_unorm[b.x], s_unorm[b.y], s_unorm[b.z], s_unorm[b.w]);
-                acc.x += w * v.x;
-                acc.y += w * v.y;
-                acc.z += w * v.z;
-                acc.w += w * v.w;
+                if (wxi < unsigned(L::WIN) && wyi < unsigned(L::WIN))
+                    b = s_hist[wyi * L::PITCH + wxi];
+                else if (qx >= 0 && qy >= 0 && qx < DW && qy < DH)
+                    b = hist[size_t(qy) * size_t(DW) + size_t(qx)];
+                acc.x += w * s_unorm[b.x];
+                acc.y += w * s_unorm[b.y];
+                acc.z += w * s_unorm[b.z];
+                acc.w += w * s_unorm[b.w];
                 total += w;
             }
         hc = make_float4(acc.x / total, acc.y / total, acc.z / total, acc.w / total);
         new_w = 0.15f;
     }
-    if (new_w < 1.0f) { // the neighbourhood's trimmed box (:86-106)
+    if (new_w < 1.0f) { // the neighbourhood's trimmed box over the render pixels (:86-106)
         float4 trim = make_float4(0.f, 0.f, 0.f, 0.f), max2 = make_float4(0.f, 0.f, 0.f, 0.f);
         for (int oy = -1; oy <= 1; ++oy)
             for (int ox = -1; ox <= 1; ++ox) {
-                const float4 v = s_pre[c + oy * RP_RT_SPAN + ox];
+                const float4 v = s_pre[c + oy * L::PRE + ox];
                 trim.x += v.x;
                 trim.y += v.y;
                 trim.z += v.z;
@@ -352,7 +364,7 @@ __global__ __launch_bounds__(64) void rp_k_taa(RpFrame f, const uchar4 *pre, con
                 max2.z += v.z * v.z;
                 max2.w += v.w * v.w;
             }
-        float tr[4] = {trim.x / 9.0f, trim.y / 9.0f, trim.z / 9.0f, trim.w / 9.0f};
+        const float tr[4] = {trim.x / 9.0f, trim.y / 9.0f, trim.z / 9.0f, trim.w / 9.0f};
         const float m2[4] = {sqrtf(max2.x / 9.0f), sqrtf(max2.y / 9.0f), sqrtf(max2.z / 9.0f), sqrtf(max2.w / 9.0f)};
         float cc[4] = {col.x, col.y, col.z, col.w};
         const float hh[4] = {hc.x, hc.y, hc.z, hc.w};
@@ -368,3 +380,7 @@ __global__ __launch_bounds__(64) void rp_k_taa(RpFrame f, const uchar4 *pre, con
     out[i] = o;
     if (out_copy) out_copy[i] = o;
 }
+__global__ __launch_bounds__(64) void rp_k_taa(RpFrame f, const uchar4 *pre, const uchar4 *hist, const uint2 *mj, uchar4 *out, uchar4 *out_copy) {
+    rp_taa_pass<1>(f.width, f.height, pre, hist, mj, out, out_copy);
+}
+

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import realtime_resolve_ref as R
+import taa_upscale_ref as U
 from realtimepathtracingresearchframework_amd import abi, backend, scenes
 
 pytestmark = pytest.mark.gpu
@@ -161,6 +162,35 @@ def test_taa_matches_the_restatement():
         assert int(d.max()) <= 1, (k, int(d.max()), int(np.count_nonzero(d > 1)))
         changed += int(np.count_nonzero(post[k][1] != pre[k][1]))
     assert changed > 0
+
+
+def test_taa_edges_and_fallbacks():
+    """the in-frame pass where test_edges_and_fallbacks (tests/test_gpu_taa_upscale.py) takes the upscaler: 50 x 38, neither a multiple of
+    the 8-pixel tile; that test's scene and fast pan (0.05 rad per frame, 5 frames), so that reconstruction points leave the image; sky
+    pixels carry NaN motion, and a tile whose first pixel is sky places its staged window nowhere: its other pixels read the history
+    from global memory. Each frame after the first against the restatement, 1 LSB as in test_taa_matches_the_restatement"""
+    s = scenes.grid(120, 60)
+    W, H, n = 50, 38, 5
+    pre = _sequence(s, abi.VARIANT_SIMPLE, W, H, 2, n, 1, rate=0.05)
+    post = _sequence(s, abi.VARIANT_SIMPLE, W, H, 2, n, 1, options={"taa": 1}, rate=0.05)
+    assert np.array_equal(post[0][1], pre[0][1])
+    outside = inside = nan = fallback = 0
+    for k in range(1, n):
+        assert np.array_equal(pre[k][3].view(np.uint16), post[k][3].view(np.uint16)), k   # the same frames in both runs
+        want = R.taa(pre[k][1], post[k - 1][1], post[k][3])
+        d = np.abs(post[k][1].astype(np.int32) - want.astype(np.int32))
+        print("frame %d: max |difference| %d, bytes that differ %d of %d, more than 1 LSB: %d" % (k, int(d.max()), int(np.count_nonzero(d)), d.size, int(np.count_nonzero(d > 1))))
+        assert int(d.max()) <= 1, (k, int(d.max()), int(np.count_nonzero(d > 1)))
+        ins, isnan = U.branches(post[k][3], 1)
+        outside += int(np.count_nonzero(~ins & ~isnan))
+        inside += int(np.count_nonzero(ins))
+        nan += int(np.count_nonzero(isnan))
+        for ty in range(0, H, 8):
+            for tx in range(0, W, 8):
+                fallback += int(isnan[ty, tx] and ins[ty:ty + 8, tx:tx + 8].any())
+    print("outside %d, with history %d, NaN motion %d, fallback tiles %d" % (outside, inside, nan, fallback))
+    assert outside > 0 and inside > 0 and nan > 0, (outside, inside, nan)   # no history (outside), history inside, NaN motion
+    assert fallback > 0
 
 
 def test_taa_with_frames_in_flight_is_bit_identical_to_the_synchronous_run():
