@@ -410,7 +410,7 @@ struct rptr_hip {
     int max_concurrency = 1;         // frames of this handle that can run side by side: min(frame contexts, hw_queues)
     int last_grids[4] = {0, 0, 0, 0}; // the grids of the last submitted frame (read-only options "last_grid_*")
     int persistent_blocks = 0;       // the grids of max_concurrency frames side by side: ray queries and counted frames
-    int extend_later_blocks = 0;     // grid of a closest-hit launch of bounce >= 1 (RP_EXTEND_LATER_WAVES)
+    int extend_later_blocks = 0;     // grid of a closest-hit launch of bounce >= 1 (that instantiation's own register count)
     int connect_blocks[2] = {0, 0};  // grid of a stand-alone shadow-ray launch, [single instance record ? 1 : 0] (RP_CONNECT_WAVES)
 
     // options (environment, read once)

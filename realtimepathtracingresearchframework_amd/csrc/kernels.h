@@ -179,10 +179,7 @@ RP_DEV bool rp_primary_ray(const RpFrame &f, uint32_t p, RpRng &rng, V3 &dir, V3
 // Round 5: the first extend STORES the camera ray's direction and generator state (ray_d[p], 16 bytes) and the first shade loads them instead
 // of making the camera ray a second time (generator seeding, the pixel jitter, an IEEE normalisation, the tile -> pixel arithmetic: ~150 of the
 // 910 instructions a first-bounce shade wave executes; the pipeline is bound by instruction issue, HBM carries 0.17 of its peak) -- the same
-// float bits either way. Not for table point sets (TABLE: the generator's other fields would have to travel too). -DRP_FIRST_RAY_STORED=0: as before.
-#ifndef RP_FIRST_RAY_STORED
-#define RP_FIRST_RAY_STORED 1
-#endif
+// float bits either way. Not for table point sets (TABLE: the generator's other fields would have to travel too).
 // hit_ids.x of a slot of the first queue that names no pixel sample (tile padding): neither a hit nor a miss
 #define RP_HIT_PADDING (-2)
 
@@ -262,7 +259,7 @@ RP_DEV void rp_extend_body(const RpScene &sc, const RpFrame &f, const RpPathStat
                 ps.hit_ids[p] = make_int2(RP_HIT_PADDING, -1);
                 return false;
             }
-            if (RP_FIRST_RAY_STORED && !TABLE) ps.ray_d[p] = f4(rd, __uint_as_float(rng.s)); // (an alpha test that draws from the generator stores its new state in done())
+            if (!TABLE) ps.ray_d[p] = f4(rd, __uint_as_float(rng.s)); // (an alpha test that draws from the generator stores its new state in done())
             tmin = 0.0f;
             tmax = 2.e32f;
             if (ALPHA) lane_rng = (!TABLE || f.rng_variant == RPTR_RNG_VARIANT_UNIFORM) ? rng.s : rp_alpha_seed(f, p);
@@ -305,7 +302,7 @@ RP_DEV void rp_extend_body(const RpScene &sc, const RpFrame &f, const RpPathStat
     }
 }
 template <bool COUNT, bool FIRST, bool ALPHA, bool SINGLE, bool TABLE>
-__global__ __launch_bounds__(RP_TRAVERSE_BLOCK, ((SINGLE && !ALPHA) ? RP_SINGLE_EXTEND_WAVES : (FIRST ? RP_TRAVERSE_WAVES : RP_EXTEND_LATER_WAVES))) void rp_k_extend(RpScene sc, RpFrame f, RpPathState ps, const uint32_t *queue, RpBounceCounters *bc, RpCounters *ctr,
+__global__ __launch_bounds__(RP_TRAVERSE_BLOCK, ((SINGLE && !ALPHA) ? RP_SINGLE_EXTEND_WAVES : RP_TRAVERSE_WAVES)) void rp_k_extend(RpScene sc, RpFrame f, RpPathState ps, const uint32_t *queue, RpBounceCounters *bc, RpCounters *ctr,
                                                int *gstack) {
     rp_extend_body<COUNT, FIRST, ALPHA, SINGLE, false, TABLE>(sc, f, ps, queue, bc->queue_count, &bc->cursor_extend, ctr, gstack);
 }
@@ -398,15 +395,12 @@ __global__ RP_TRAVERSE_BOUNDS void rp_k_connect_ldstop(RpScene sc, RpFrame f, Rp
 // TEX = false: no material of the scene reads a texture (textured parameters, normal maps): sampling code compiled out
 // LOCAL (rp_k_tail): `order` is a block-local list of n <= RP_CHUNK path ids; the survivors and the shadow rays are not
 // published to the global queues but left in shared memory for the caller (local_next / local_shadow, counts in n_next / n_shadow)
-// RP_KERNARG_RELOAD: left alone, the shade kernels keep ~300 scalar values of their by-value arguments (RpFrame, RpScene) alive across the
+// Kernel-argument reload: left alone, the shade kernels keep ~300 scalar values of their by-value arguments (RpFrame, RpScene) alive across the
 // whole loop and spill 200-330 of them into VGPR lanes (v_writelane / v_readlane: VALU instructions, a tenth of the loop's). The loop body
 // therefore reads the two structs from the kernel-argument segment again at three points -- scalar loads from constant memory behind an asm
 // barrier that keeps them from being hoisted -- so that nothing of them has to stay in registers from one stretch to the next: 25 spilled
 // SGPRs instead of 199-330, VGPR spills 44 -> 5 (glTF + lights) and 114 -> 33 (textured), the Lambert kernel 110 -> 97 VGPRs; shade launches
-// -6 % on C3 and on textured scenes, frames -1 % (C2) ... -3 % (C3) (profiles/r03_notes.md section 9). -DRP_KERNARG_RELOAD=0: the old code.
-#ifndef RP_KERNARG_RELOAD
-#define RP_KERNARG_RELOAD 1
-#endif
+// -6 % on C3 and on textured scenes, frames -1 % (C2) ... -3 % (C3) (profiles/r03_notes.md section 9).
 template <class T>
 RP_DEV const T &rp_kernarg(uint32_t offset) {
     typedef const T __attribute__((address_space(4))) *KP;
@@ -418,15 +412,11 @@ RP_DEV const T &rp_kernarg(uint32_t offset) {
 // kernel-argument segment from offset 0 at their natural alignment (the whole-frame parity tests would not survive a wrong offset)
 #define RP_KERNARG_OFF_SC 0u
 #define RP_KERNARG_OFF_F ((uint32_t)((sizeof(RpScene) + alignof(RpFrame) - 1) / alignof(RpFrame) * alignof(RpFrame)))
-#if RP_KERNARG_RELOAD
 #define RP_RELOAD_ARGS                                               \
     const RpFrame &f = rp_kernarg<RpFrame>(RP_KERNARG_OFF_F);        \
     const RpScene &sc = rp_kernarg<RpScene>(RP_KERNARG_OFF_SC);      \
     (void)f;                                                         \
     (void)sc;
-#else
-#define RP_RELOAD_ARGS
-#endif
 // the LDS buffers of rp_shade_body when the caller owns them (EXTLDS; rp_k_tail): `next` and `shadow` (RP_CHUNK words each) outlive the call
 // (the survivors and the shadow rays of the chunk), `list` (RP_CHUNK words), `ris_req` (2048 floats) and `ris_contrib` (4096 floats; LIGHTS
 // only) are scratch the caller may reuse between calls
@@ -575,7 +565,7 @@ RP_DEV void rp_shade_body(const RpScene &sc, const RpFrame &f, const RpPathState
                         first_du_dv[0] = ld3(f.cam_du);
                         first_du_dv[1] = ld3(f.cam_dv);
                     }
-                } else if (FIRST && RP_FIRST_RAY_STORED && !TABLE) {
+                } else if (FIRST && !TABLE) {
                     const float4 rd4 = ps.ray_d[p];
                     ray_dir = xyz(rd4);
                     rng.s = __float_as_uint(rd4.w);
@@ -601,8 +591,9 @@ RP_DEV void rp_shade_body(const RpScene &sc, const RpFrame &f, const RpPathState
             if (present) {
                 my_closest++;
                 if (FIRST) { // init_shading_sample_state (shading_interface.glsl:20-22)
-                    if (!QUERY && f.alpha_test && (!TABLE || f.rng_variant == RPTR_RNG_VARIANT_UNIFORM) && !(RP_FIRST_RAY_STORED && !TABLE))
-                        rng.s = (reinterpret_cast<const uint32_t *>(ps.ray_d))[4u * p + 3u]; // alpha tests of the first extend may have drawn from it
+                    // alpha tests of the first extend may have drawn from the generator (!TABLE: the stored first ray's state was loaded above)
+                    if (!QUERY && f.alpha_test && TABLE && f.rng_variant == RPTR_RNG_VARIANT_UNIFORM)
+                        rng.s = (reinterpret_cast<const uint32_t *>(ps.ray_d))[4u * p + 3u];
                     if (!QUERY && f.aov_albedo_roughness) { // the first sample of the (last) frame (of the batch) writes the AOVs
                         const RpSlotFrame sf = rp_slot_frame(f, first_sslot);
                         if (sf.sample_index == sf.frame_id && int(sf.frame) == f.batch_frames - 1) {

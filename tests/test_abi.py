@@ -6,6 +6,7 @@ import re
 import numpy as np
 import pytest
 
+from code_object import kernel_regs
 from realtimepathtracingresearchframework_amd import abi, backend, build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -224,16 +225,7 @@ def test_traversal_kernels_keep_their_register_budgets_and_their_node_fetch():
     the benchmarked traversal instantiations -- one instance record, no alpha test -- fit the register budgets of seven (closest hit) and eight
     (shadow rays) waves per SIMD without scratch, hold 20 KB of LDS stacks per block, and fetch a node as 16 + 16 + 16 + 8 bytes (the
     vectoriser once made the last load 16: 8 bytes of padding per lane and node visit, profiles/r06_notes.md section 9)."""
-    import shutil
-    if not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-objdump") or shutil.which("bash") is None:
-        pytest.skip("no llvm-objdump")
-    if not os.path.exists(build.LIB_PATH):
-        build.build_library()
-    regs = {}
-    for line in _tool("tools/kernel_regs.sh", build.LIB_PATH).splitlines():
-        m = re.match(r"(\S+)\s+vgpr\s+(\d+)\s+sgpr\s+(\d+)\s+scratch\s+(\d+)\s+lds\s+(\d+)", line)
-        if m:
-            regs[m.group(1)] = tuple(int(x) for x in m.groups()[1:])
+    regs = kernel_regs()
     budgets = {"_Z11rp_k_extendILb0ELb1ELb0ELb1ELb0EE": 72, "_Z11rp_k_extendILb0ELb0ELb0ELb1ELb0EE": 72, "_Z12rp_k_connectILb0ELb0ELb1EE": 64}
     for prefix, budget in budgets.items():
         hits = [v for k, v in regs.items() if k.startswith(prefix)]

@@ -216,7 +216,7 @@ def test_aperture_zero_leaves_everything_alone(cornell):
 
 @pytest.mark.parametrize("fast_math", [0, 1])
 def test_first_extend_and_first_shade_agree_on_the_lens_ray(cornell_inside, fast_math):
-    """No run-time switch disables the stored first ray (RP_FIRST_RAY_STORED is a compile-time constant, and the general instantiations that
+    """No run-time switch disables the stored first ray (the non-TABLE kernels always store and load it, and the general instantiations that
     render a lens frame make the ray again in the first shade), so: the lens image is finite, every pixel is covered as with the pinhole
     (a first shade that disagreed with the first extend about the ray would shade hits at wrong points or lose them), and the image
     differs from the pinhole's. test_defocus_has_the_width_the_model_predicts runs in both builds too."""

@@ -5,12 +5,12 @@ import ctypes as C
 import inspect
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+from code_object import kernel_regs
 from realtimepathtracingresearchframework_amd import abi, backend, build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -146,25 +146,11 @@ def test_python_pack_and_unpack_round_trip_in_little_endian_bit_order(n):
     assert np.array_equal(R.unpack_occlusion_bits(words, n), np.where(skipped, b, answers))
 
 
-def _regs():
-    if not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-objdump") or shutil.which("bash") is None:
-        pytest.skip("no llvm-objdump")
-    if not os.path.exists(build.LIB_PATH):
-        build.build_library()
-    out = subprocess.run(["bash", os.path.join(ROOT, "tools", "kernel_regs.sh"), build.LIB_PATH], stdout=subprocess.PIPE, universal_newlines=True, check=True).stdout
-    regs = {}
-    for line in out.splitlines():
-        m = re.match(r"(\S+)\s+vgpr\s+(\d+)\s+sgpr\s+(\d+)\s+scratch\s+(\d+)\s+lds\s+(\d+)", line)
-        if m:
-            regs[m.group(1)] = tuple(int(x) for x in m.groups()[1:])
-    return regs
-
-
 def test_the_kernels_are_present_and_free_of_scratch():
     """rp_k_trace_occlusion<ALPHA, SINGLE>: the opaque and the cutout instantiation, each for scenes with one instance record and for the
     two-level walk, without a private segment and inside the VGPR budget of their launch bounds (csrc/occlusion_query.h: eight, six and
     five waves per SIMD -- 64, 80 and 96 registers). Metadata of the gfx950 code object only."""
-    regs = _regs()
+    regs = kernel_regs()
     k = {name[len("_Z20rp_k_trace_occlusionIL"):][:8]: v for name, v in regs.items() if name.startswith("_Z20rp_k_trace_occlusionILb")}
     assert sorted(k) == ["b0ELb0EE", "b0ELb1EE", "b1ELb0EE", "b1ELb1EE"], sorted(regs)[:4]
     budget = {"b0ELb1EE": 64, "b0ELb0EE": 80, "b1ELb1EE": 96, "b1ELb0EE": 96}

@@ -3,11 +3,10 @@ kernels (tests/test_gpu_radiance_queries.py runs them)."""
 import inspect
 import os
 import re
-import shutil
 import subprocess
 
-import pytest
 
+from code_object import kernel_regs
 from realtimepathtracingresearchframework_amd import abi, backend, build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -65,25 +64,11 @@ int main(int argc, char **) {
     assert subprocess.call([exe]) == 0
 
 
-def _regs():
-    if not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-objdump") or shutil.which("bash") is None:
-        pytest.skip("no llvm-objdump")
-    if not os.path.exists(build.LIB_PATH):
-        build.build_library()
-    out = subprocess.run(["bash", os.path.join(ROOT, "tools", "kernel_regs.sh"), build.LIB_PATH], stdout=subprocess.PIPE, universal_newlines=True, check=True).stdout
-    regs = {}
-    for line in out.splitlines():
-        m = re.match(r"(\S+)\s+vgpr\s+(\d+)\s+sgpr\s+(\d+)\s+scratch\s+(\d+)\s+lds\s+(\d+)", line)
-        if m:
-            regs[m.group(1)] = tuple(int(x) for x in m.groups()[1:])
-    return regs
-
-
 def test_query_traversal_and_resolve_kernels_are_present_and_free_of_scratch():
     """rp_k_extend_query<ALPHA, SINGLE, TABLE>: all eight instantiations without a private segment. Without the alpha test they keep the
     frame's budgets (six / seven waves per SIMD: 80 / 72 VGPRs); with it they are compiled for five waves (96 VGPRs: at 80 the generator a
     lane carries through the walk spills, as it does in rp_k_extend<.., FIRST, ALPHA, ..>). rp_k_resolve_queries: no scratch, no LDS."""
-    regs = _regs()
+    regs = kernel_regs()
     ext = {k: v for k, v in regs.items() if k.startswith("_Z17rp_k_extend_queryILb")}
     assert len(ext) == 8, sorted(ext)
     for k, v in ext.items():
@@ -98,7 +83,7 @@ def test_query_shade_kernels_are_present_and_free_of_scratch():
     """rp_k_shade_query<VARIANT, LIGHTS, TEX, TABLE, MATH>: 3 x 2 x 2 x 2 x 2 instantiations, none with a private segment (the kernel takes
     origin, direction and generator state from the path state, where rp_k_extend_query left them: with the query buffer among its
     arguments most instantiations reserved 8-40 bytes)"""
-    regs = _regs()
+    regs = kernel_regs()
     sh = {k: v for k, v in regs.items() if k.startswith("_Z16rp_k_shade_queryILi")}
     assert len(sh) == 48, len(sh)
     # (four waves per SIMD = 128 VGPRs; the glTF programs on textured scenes are compiled for three = 168: kernels.h rp_shade_query_waves)

@@ -3,13 +3,12 @@ hold csrc/realtime_resolve.h to), the .ini reader's REPROJECTION_MODE_ACCUMULATE
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
-import pytest
 
 import realtime_resolve_ref as R
+from code_object import kernel_regs
 from realtimepathtracingresearchframework_amd import abi, backend, build, scenes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -168,16 +167,7 @@ def test_the_taa_kernel_uses_no_scratch():
     """rp_k_taa in the gfx950 code object: no private segment; its LDS is the 24 x 24 history window, the 10 x 10 float4 neighbourhood and
     the byte / 255 table (the window's base lives in registers). Registers: at most 128, the step at which four waves per SIMD fit
     (512 / 128)"""
-    if not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-objdump") or shutil.which("bash") is None:
-        pytest.skip("no llvm-objdump")
-    if not os.path.exists(build.LIB_PATH):
-        build.build_library()
-    out = subprocess.run(["bash", os.path.join(ROOT, "tools", "kernel_regs.sh"), build.LIB_PATH], stdout=subprocess.PIPE, universal_newlines=True, check=True).stdout
-    regs = {}
-    for line in out.splitlines():
-        m = re.match(r"(\S+)\s+vgpr\s+(\d+)\s+sgpr\s+(\d+)\s+scratch\s+(\d+)\s+lds\s+(\d+)", line)
-        if m:
-            regs[m.group(1)] = tuple(int(x) for x in m.groups()[1:])
+    regs = kernel_regs()
     taa = [v for k, v in regs.items() if "rp_k_taa" in k and "rp_k_taa_upscale" not in k]
     assert len(taa) == 1, sorted(regs)
     vgpr, _, scratch, lds = taa[0]

@@ -4,12 +4,11 @@ import ctypes as C
 import inspect
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
-import pytest
 
+from code_object import kernel_regs
 from realtimepathtracingresearchframework_amd import abi, backend, build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -108,25 +107,11 @@ int main(int argc, char **) {
     assert subprocess.call([exe]) == 0
 
 
-def _regs():
-    if not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-objdump") or shutil.which("bash") is None:
-        pytest.skip("no llvm-objdump")
-    if not os.path.exists(build.LIB_PATH):
-        build.build_library()
-    out = subprocess.run(["bash", os.path.join(ROOT, "tools", "kernel_regs.sh"), build.LIB_PATH], stdout=subprocess.PIPE, universal_newlines=True, check=True).stdout
-    regs = {}
-    for line in out.splitlines():
-        m = re.match(r"(\S+)\s+vgpr\s+(\d+)\s+sgpr\s+(\d+)\s+scratch\s+(\d+)\s+lds\s+(\d+)", line)
-        if m:
-            regs[m.group(1)] = tuple(int(x) for x in m.groups()[1:])
-    return regs
-
-
 def test_the_two_kernels_are_present_and_free_of_scratch():
     """rp_k_trace_surface<SINGLE>: both instantiations inside the traversal kernels' budget (six waves per SIMD: 80 VGPRs) without a
     private segment. rp_k_surface<VARIANT, TEX>: 3 x 2 instantiations, no private segment, no LDS; the ones without texture code are the
     small ones."""
-    regs = _regs()
+    regs = kernel_regs()
     tr = {k: v for k, v in regs.items() if k.startswith("_Z18rp_k_trace_surfaceILb")}
     assert len(tr) == 2, sorted(tr)
     for k, v in tr.items():

@@ -4,7 +4,6 @@ inputs whose answer is known, the C ABI of rptr_hip_taa_upscale, and the code-ob
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
@@ -12,6 +11,7 @@ import pytest
 
 import realtime_resolve_ref as R
 import taa_upscale_ref as U
+from code_object import kernel_regs
 from realtimepathtracingresearchframework_amd import abi, backend, build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -181,16 +181,7 @@ def test_the_kernels_use_no_scratch():
     """rp_k_taa_upscale and rp_k_upscale_replicate in the gfx950 code object: no private segment; the upscaler's LDS is the history
     window (32 rows of 40 words), the 6 x 6 float4 neighbourhood and the byte / 255 table -- 24 one-wave blocks per CU, six waves per SIMD.
     Registers: at most 128, the step at which four waves per SIMD fit (512 / 128), the occupancy rp_k_taa runs at with the same tap loop"""
-    if not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-objdump") or shutil.which("bash") is None:
-        pytest.skip("no llvm-objdump")
-    if not os.path.exists(build.LIB_PATH):
-        build.build_library()
-    out = subprocess.run(["bash", os.path.join(ROOT, "tools", "kernel_regs.sh"), build.LIB_PATH], stdout=subprocess.PIPE, universal_newlines=True, check=True).stdout
-    regs = {}
-    for line in out.splitlines():
-        m = re.match(r"(\S+)\s+vgpr\s+(\d+)\s+sgpr\s+(\d+)\s+scratch\s+(\d+)\s+lds\s+(\d+)", line)
-        if m:
-            regs[m.group(1)] = tuple(int(x) for x in m.groups()[1:])
+    regs = kernel_regs()
     up = [v for k, v in regs.items() if "rp_k_taa_upscale" in k]
     rep = [v for k, v in regs.items() if "rp_k_upscale_replicate" in k]
     assert len(up) == 1 and len(rep) == 1, sorted(regs)
