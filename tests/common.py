@@ -1,10 +1,191 @@
-"""Shared helpers for the parity tests."""
+"""Shared helpers of the tests: renderer handles, configurations, read-backs, cameras, transforms and query rays. The helpers that build
+random data are pinned by the tests that use them: the same arguments must keep giving the same arrays."""
+import copy
+import ctypes as C
+import math
+
 import numpy as np
 
 import oracle_lib as O
-from realtimepathtracingresearchframework_amd import abi, backend
+from realtimepathtracingresearchframework_amd import abi, backend, scenes
 
 RMSE_TOL = 1e-3  # north_star: validation image error < 1e-3 RMSE at fixed seed/spp
+
+
+def renderer(scene, W, H, **kw):
+    """an initialized RenderHip(**kw) of W x H with the scene set"""
+    r = backend.RenderHip(**kw)
+    r.initialize(W, H)
+    r.set_scene(scene)
+    return r
+
+
+def config(scene, variant=abi.VARIANT_GLTF, reset=True, camera=None, freeze_frame=False):
+    return backend.RenderConfiguration(camera or scene.camera_params(), active_variant=variant, reset_accumulation=reset, freeze_frame=freeze_frame)
+
+
+def float_bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def read_frame(r, W, H, aovs=True):
+    """(accum, fb, albedo + roughness, normal + depth, motion + jitter) of the frame the read-backs return; aovs=False: the first two"""
+    acc = np.zeros((H, W, 4), np.float32)
+    fb = np.zeros((H, W, 4), np.uint8)
+    assert r.readback_framebuffer(acc) == W * H * 4 and r.readback_framebuffer(fb) == W * H * 4
+    if not aovs:
+        return acc, fb
+    aov = [np.zeros((H, W, 4), np.float16) for _ in range(3)]
+    for k in range(3):
+        assert r.readback_aov(k, aov[k]) == W * H * 4
+    return acc, fb, aov[0], aov[1], aov[2]
+
+
+def same_images(a, b):
+    """two tuples of images, byte for byte"""
+    return all(np.array_equal(x.view(np.uint8), y.view(np.uint8)) for x, y in zip(a, b))
+
+
+def raw_stats(r):
+    st = abi.Stats()
+    assert r._L.rptr_hip_stats(r._h, C.byref(st)) == 0
+    return st
+
+
+def aov_close(a, b, what):
+    """float16 images with the same finite / non-finite pattern (more than 99.95 % of the values) and values within 2^-9 max(|ref|, 2^-5),
+    two half ulps (more than 99.9 % of them): the floats behind them differ by libm ulps between host and device, an RGBA16F store
+    rounds them"""
+    a32, b32 = a.astype(np.float32), b.astype(np.float32)
+    fa, fb = np.isfinite(a32), np.isfinite(b32)
+    same_pattern = float((fa == fb).mean())
+    both = fa & fb
+    err = np.abs(a32[both] - b32[both])
+    tol = 2.0 ** -9 * np.maximum(np.abs(b32[both]), 2.0 ** -5)
+    inside = float((err <= tol).mean())
+    print("%s: finite pattern equal %.6f, inside the bound %.6f, worst error %.3e" % (what, same_pattern, inside, float(err.max())))
+    assert same_pattern > 0.9995, what
+    assert inside > 0.999, (what, float(err.max()))
+
+
+def panned_camera(cam, k, rate):
+    """the view yawed by rate * k radians about its up axis"""
+    d = np.array(cam.dir[:], np.float64)
+    u = np.array(cam.up[:], np.float64)
+    r = np.cross(d, u)
+    r /= np.linalg.norm(r)
+    a = rate * k
+    nd = math.cos(a) * d + math.sin(a) * r
+    nd /= np.linalg.norm(nd)
+    c = abi.Camera()
+    c.pos[:] = cam.pos[:]
+    c.dir[:] = [float(v) for v in nd]
+    c.up[:] = cam.up[:]
+    c.fovy = cam.fovy
+    return c
+
+
+def fly_camera(cam, k):
+    """frame k of --fly-through (host/rptr_cli.cpp fly_camera, bench.py's path): yawed by 0.002 rad x s about the up axis from 2 cm x s
+    further to the right, s = k mod 64 - 32; evaluated in double, rounded to float once"""
+    s = k % 64 - 32
+    a = 0.002 * s
+    d = [float(v) for v in cam.dir[:]]
+    u = [float(v) for v in cam.up[:]]
+    r = [d[1] * u[2] - d[2] * u[1], d[2] * u[0] - d[0] * u[2], d[0] * u[1] - d[1] * u[0]]
+    rl = math.sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2])
+    r = [x / rl for x in r]
+    nd = [math.cos(a) * d[i] + math.sin(a) * r[i] for i in range(3)]
+    nl = math.sqrt(nd[0] * nd[0] + nd[1] * nd[1] + nd[2] * nd[2])
+    c = abi.Camera()
+    c.pos[:] = [float(np.float32(float(cam.pos[i]) + 0.02 * s * r[i])) for i in range(3)]
+    c.dir[:] = [float(np.float32(nd[i] / nl)) for i in range(3)]
+    c.up[:] = cam.up[:]
+    c.fovy = cam.fovy
+    return c
+
+
+def random_transforms(n, seed, spread=4.0):
+    """rotation x NON-uniform scale + translation, float32 (n, 3, 4)"""
+    rng = np.random.default_rng(seed)
+    out = np.zeros((n, 3, 4), np.float32)
+    for i in range(n):
+        ang = rng.uniform(0, 2 * np.pi)
+        axis = rng.normal(size=3)
+        axis /= np.linalg.norm(axis)
+        K = np.array([[0, -axis[2], axis[1]], [axis[2], 0, -axis[0]], [-axis[1], axis[0], 0]])
+        R = np.eye(3) + np.sin(ang) * K + (1 - np.cos(ang)) * K @ K
+        out[i, :, :3] = R @ np.diag(rng.uniform(0.5, 1.7, size=3))
+        out[i, :, 3] = rng.uniform(-spread, spread, size=3)
+    return out
+
+
+def scene_transforms(s):
+    return np.stack([np.asarray(i.transform, np.float32).reshape(3, 4) for i in s.instances])
+
+
+def with_transforms(scene, xf, first=0):
+    """a copy of the scene whose instances first, first + 1, ... have the transforms xf"""
+    s = copy.copy(scene)
+    s.instances = [copy.copy(i) for i in scene.instances]
+    for k, m in enumerate(xf):
+        s.instances[first + k].transform = np.asarray(m, np.float32).reshape(3, 4).copy()
+    return s
+
+
+def movable_two_level(n_inst=12, move_bit=True):
+    """two_level_test without its emissive material (instances of an emissive mesh cannot move), every mesh MESH_INSTANCES_MOVE"""
+    s = scenes.two_level_test(n_inst=n_inst)
+    s.materials[3] = abi.make_material((1, 1, 1), roughness=0.4)
+    s.prepare_lights()
+    if move_bit:
+        for m in s.meshes:
+            m.dynamic = abi.MESH_INSTANCES_MOVE
+    return s
+
+
+def probe_queries(n, seed=3, spread=0.8, centre=(0.0, 1.0, 0.0), short=False):
+    """random rays from inside the scene; short: every second one ends after 0.2 ... 3 units"""
+    rng = np.random.default_rng(seed)
+    q = np.zeros((n, 8), np.float32)
+    q[:, 0:3] = rng.uniform(-spread, spread, (n, 3)).astype(np.float32) + np.float32(centre)
+    d = rng.normal(size=(n, 3))
+    q[:, 4:7] = (d / np.linalg.norm(d, axis=1, keepdims=True)).astype(np.float32)
+    q[:, 7] = 1e20
+    if short:
+        q[1::2, 7] = rng.uniform(0.2, 3.0, len(q[1::2])).astype(np.float32)
+    return q
+
+
+def synthetic_frame(H=32, W=48, amplitude=0.35):
+    """albedo checker x smooth irradiance + deterministic hash noise on the irradiance -> (noisy accum, albedo, nd, clean rgb)"""
+    ys, xs = np.mgrid[0:H, 0:W]
+    checker = ((xs // 6 + ys // 6) & 1).astype(np.float32)
+    albedo = np.stack([np.float32(0.2) + np.float32(0.6) * checker, np.float32(0.7) - np.float32(0.4) * checker, np.full((H, W), np.float32(0.5))], -1).astype(np.float16)
+    irr = (np.float32(0.6) + np.float32(0.3) * np.sin(xs / np.float32(9.0)) * np.cos(ys / np.float32(7.0))).astype(np.float32)
+    clean = albedo.astype(np.float32) * irr[..., None]
+    hsh = (xs.astype(np.uint64) * 73856093) ^ (ys.astype(np.uint64) * 19349663)
+    noise = np.empty((H, W, 3), np.float32)
+    for ch in range(3):
+        v = (hsh + np.uint64(ch * 83492791)) * np.uint64(2654435761) % np.uint64(1 << 32)
+        v = (v ^ (v >> np.uint64(15))) * np.uint64(2246822519) % np.uint64(1 << 32)
+        noise[..., ch] = (v % np.uint64(65536)).astype(np.float32) / np.float32(65536) - np.float32(0.5)
+    accum = np.empty((H, W, 4), np.float32)
+    accum[..., :3] = albedo.astype(np.float32) * (irr[..., None] + np.float32(amplitude) * noise)
+    accum[..., 3] = 1.0
+    alb = np.concatenate([albedo, np.ones((H, W, 1), np.float16)], -1)
+    nd = np.empty((H, W, 4), np.float16)
+    nd[..., :3] = (0.0, 0.0, 1.0)
+    nd[..., 3] = (np.float32(5.0) + xs * np.float32(0.02)).astype(np.float16)
+    return accum, alb, nd, clean
+
+
+def rel_excess(got, lo, hi):
+    """how far a binary32 result lies outside the float64 band [lo, hi], relative to the band's larger end (0 inside)"""
+    got = np.asarray(got, np.float64)
+    with np.errstate(invalid="ignore"):
+        d = np.maximum(lo - got, got - hi)
+        return np.where(d > 0, d / np.maximum(np.maximum(np.abs(lo), np.abs(hi)), 1e-30), 0.0)
 
 
 def gpu_render(scene, W, H, spp, variant, rank=0, world=1, stripe_rows=32, count=False, params=None, lighting=None, reset=True,

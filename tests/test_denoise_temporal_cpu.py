@@ -10,16 +10,12 @@ import numpy as np
 
 import denoise_ref as D
 import denoise_temporal_ref as T
+from common import float_bits, synthetic_frame
 from realtimepathtracingresearchframework_amd import abi, backend
-from test_denoise_cpu import synthetic_frame
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ["rptr_hip_denoise_temporal_defaults", "rptr_hip_denoise_temporal", "rptr_hip_readback_denoise_history_f32"]
 F = np.float32
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, F).view(np.uint32)
 
 
 def _motion(H, W, mx=0.0, my=0.0):
@@ -85,16 +81,16 @@ def test_the_first_call_and_a_reset_equal_the_spatial_denoiser_bit_for_bit():
             assert td.history() is None
             f, u = td.step(accum, alb, nd, mj, fb, iterations=it, demodulate_albedo=demod)
             wf, wu = D.denoise(accum, alb, nd, fb, iterations=it, demodulate_albedo=demod)
-            assert np.array_equal(_bits(f), _bits(wf)) and np.array_equal(u, wu), (demod, it)
+            assert np.array_equal(float_bits(f), float_bits(wf)) and np.array_equal(u, wu), (demod, it)
             assert not td.had_history.any() and np.all(td.history()[..., 3] == 1)
             f, _ = td.step(accum2, alb, nd, mj, iterations=it, demodulate_albedo=demod)       # history: another image ...
             wf, wu = D.denoise(accum2, alb, nd, fb, iterations=it, demodulate_albedo=demod)
-            assert td.had_history.all() and not np.array_equal(_bits(f), _bits(wf))
+            assert td.had_history.all() and not np.array_equal(float_bits(f), float_bits(wf))
             f, u = td.step(accum2, alb, nd, mj, fb, iterations=it, demodulate_albedo=demod, reset_history=1)   # ... a reset: the spatial one
-            assert np.array_equal(_bits(f), _bits(wf)) and np.array_equal(u, wu), (demod, it)
+            assert np.array_equal(float_bits(f), float_bits(wf)) and np.array_equal(u, wu), (demod, it)
             assert not td.had_history.any()
             f, _ = td.step(accum, alb, nd, mj, iterations=it, demodulate_albedo=1 - demod)    # other units: no history either
-            assert np.array_equal(_bits(f), _bits(D.denoise(accum, alb, nd, iterations=it, demodulate_albedo=1 - demod)[0]))
+            assert np.array_equal(float_bits(f), float_bits(D.denoise(accum, alb, nd, iterations=it, demodulate_albedo=1 - demod)[0]))
             assert not td.had_history.any()
 
 
@@ -142,9 +138,9 @@ def test_an_integer_pan_blends_with_the_texel_four_pixels_away():
     assert np.array_equal(td.had_history, inside)
     e = D.prepare(a1, alb1, nd1)[0][..., :3]
     want = (F(1) - F(0.5)) * shift(prev[..., :3]) + F(0.5) * e            # ac = fmax(1 / 2, 0.2)
-    assert np.array_equal(_bits(hist[..., :3])[inside], _bits(want)[inside])
-    assert np.array_equal(_bits(hist[..., :3])[~inside], _bits(e)[~inside])
-    assert np.array_equal(_bits(ev[..., :3]), _bits(hist[..., :3]))
+    assert np.array_equal(float_bits(hist[..., :3])[inside], float_bits(want)[inside])
+    assert np.array_equal(float_bits(hist[..., :3])[~inside], float_bits(e)[~inside])
+    assert np.array_equal(float_bits(ev[..., :3]), float_bits(hist[..., :3]))
 
 
 def test_disocclusion_by_normal_and_by_depth_drops_the_history():
@@ -168,8 +164,8 @@ def test_disocclusion_by_normal_and_by_depth_drops_the_history():
         mj = _motion(H, W, 0.0107, -0.0041)              # fractional taps: pixels left of the edge have taps on it
         out_a, _ = td.step(a1, alb, nd, mj)
         out_b, _ = other.step(a1, alb, nd, mj)
-        assert np.array_equal(_bits(out_a), _bits(out_b)), how
-        assert np.array_equal(_bits(td.history()), _bits(other.history())), how
+        assert np.array_equal(float_bits(out_a), float_bits(out_b)), how
+        assert np.array_equal(float_bits(td.history()), float_bits(other.history())), how
         n = td.history()[..., 3]
         assert np.all(n[:, W // 2 + 1:] == 1), how       # (the column at the edge may find the left half's texels)
         assert np.all(n[2:-2, 2:W // 2 - 2] == 2), how
@@ -202,12 +198,12 @@ def test_pixels_that_are_not_surface_come_back_bit_identical_and_are_never_tappe
             if variant:
                 accum[off, :3] = 0.125
             out, _ = td.step(accum, alb, nd, mj)
-            assert np.array_equal(_bits(out)[off], _bits(accum)[off])
+            assert np.array_equal(float_bits(out)[off], float_bits(accum)[off])
             assert np.all(td.history()[off] == 0) and np.all(td.hm[off] == 0) and np.all(td.hndz[off] == 0)
         assert (td.history()[..., 3] > 1).any()
         outs.append((out, td.history()))
-    assert np.array_equal(_bits(outs[0][0])[~off], _bits(outs[1][0])[~off])
-    assert np.array_equal(_bits(outs[0][1]), _bits(outs[1][1]))
+    assert np.array_equal(float_bits(outs[0][0])[~off], float_bits(outs[1][0])[~off])
+    assert np.array_equal(float_bits(outs[0][1]), float_bits(outs[1][1]))
 
 
 def test_an_interleaved_spatial_call_changes_nothing():
@@ -222,4 +218,4 @@ def test_an_interleaved_spatial_call_changes_nothing():
             if interleave:
                 D.denoise(accum, alb, nd, iterations=3, demodulate_albedo=0)
         runs.append((out, td.history()))
-    assert np.array_equal(_bits(runs[0][0]), _bits(runs[1][0])) and np.array_equal(_bits(runs[0][1]), _bits(runs[1][1]))
+    assert np.array_equal(float_bits(runs[0][0]), float_bits(runs[1][0])) and np.array_equal(float_bits(runs[0][1]), float_bits(runs[1][1]))

@@ -1,39 +1,18 @@
 """bin/rptr_hip --denoise <iterations> (host/rptr_cli.cpp): the image files of a run hold the denoised frame, the one the Python mirror's
 denoise(iterations=n) returns for that frame; without the flag the files are what they always were."""
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
-from realtimepathtracingresearchframework_amd import abi, backend, build, scenes
+from host_tools import build_host_tool, read_pfm
+from realtimepathtracingresearchframework_amd import abi, backend, scenes
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST = os.path.join(ROOT, "realtimepathtracingresearchframework_amd", "host")
-
-
-def _build_cli(tmp_path):
-    if not os.path.exists(build.LIB_PATH):
-        build.build_library()
-    exe = str(tmp_path / "rptr_hip")
-    libdir = os.path.dirname(build.LIB_PATH)
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", os.path.join(HOST, "rptr_cli.cpp"), "-o", exe, "-L" + libdir,
-                           "-lrptr_hip", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"])
-    return exe
-
-
-def _read_pfm(path):
-    with open(path, "rb") as f:
-        assert f.readline() == b"PF\n"
-        w, h = (int(v) for v in f.readline().split())
-        assert f.readline() == b"-1.0\n"
-        data = np.frombuffer(f.read(), dtype="<f4")
-    return data.reshape(h, w, 3)[::-1]
 
 
 def test_denoise_flag_writes_the_mirrors_denoised_image(tmp_path):
-    exe = _build_cli(tmp_path)
+    exe = build_host_tool("rptr_cli")
     s = scenes.cornell32()
     path = str(tmp_path / "cornell.rpsc")
     s.dump(path)
@@ -52,8 +31,8 @@ def test_denoise_flag_writes_the_mirrors_denoised_image(tmp_path):
     r.denoise(iterations=3)
     want = r.readback_denoised_f32()
     r.close()
-    got_plain = _read_pfm("%s_%04d.pfm" % (tmp_path / "plain", spp))
-    got_den = _read_pfm("%s_%04d.pfm" % (tmp_path / "den", spp))
+    got_plain = read_pfm("%s_%04d.pfm" % (tmp_path / "plain", spp))
+    got_den = read_pfm("%s_%04d.pfm" % (tmp_path / "den", spp))
     assert np.array_equal(got_plain.view(np.uint32), np.ascontiguousarray(raw[..., :3]).view(np.uint32))     # without the flag: the frame
     assert np.array_equal(got_den.view(np.uint32), np.ascontiguousarray(want[..., :3]).view(np.uint32))
     assert not np.array_equal(got_den, got_plain)

@@ -3,72 +3,16 @@
 history must agree bit for bit and byte for byte along a moving camera; a call without history equals rptr_hip_denoise; and what the call
 promises to leave alone is compared before and after."""
 import ctypes as C
-import math
 
 import numpy as np
 import pytest
 
 import denoise_ref as D
 import denoise_temporal_ref as T
+from common import config, float_bits, fly_camera, raw_stats, read_frame, renderer, same_images
 from realtimepathtracingresearchframework_amd import abi, backend, scenes
 
 pytestmark = pytest.mark.gpu
-
-
-def _fly_camera(cam, k):
-    """frame k of the fly-through path (host/rptr_cli.cpp fly_camera, restated as in tests/test_gpu_taa_upscale_cli.py): yawed by
-    0.002 rad x s about the up axis from 2 cm x s further to the right, s = k mod 64 - 32; in double, rounded to float once"""
-    s = k % 64 - 32
-    a = 0.002 * s
-    d = [float(v) for v in cam.dir[:]]
-    u = [float(v) for v in cam.up[:]]
-    r = [d[1] * u[2] - d[2] * u[1], d[2] * u[0] - d[0] * u[2], d[0] * u[1] - d[1] * u[0]]
-    rl = math.sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2])
-    r = [x / rl for x in r]
-    nd = [math.cos(a) * d[i] + math.sin(a) * r[i] for i in range(3)]
-    nl = math.sqrt(nd[0] * nd[0] + nd[1] * nd[1] + nd[2] * nd[2])
-    c = abi.Camera()
-    c.pos[:] = [float(np.float32(float(cam.pos[i]) + 0.02 * s * r[i])) for i in range(3)]
-    c.dir[:] = [float(np.float32(nd[i] / nl)) for i in range(3)]
-    c.up[:] = cam.up[:]
-    c.fovy = cam.fovy
-    return c
-
-
-def _cfg(scene, variant, reset=True, camera=None):
-    return backend.RenderConfiguration(camera or scene.camera_params(), active_variant=variant, reset_accumulation=reset)
-
-
-def _handle(scene, W, H, **kw):
-    r = backend.RenderHip(**kw)
-    r.initialize(W, H)
-    r.set_scene(scene)
-    return r
-
-
-def _frame(r, W, H):
-    """(accum, fb, albedo + roughness, normal + depth, motion + jitter) of the frame the read-backs return"""
-    acc = np.zeros((H, W, 4), np.float32)
-    fb = np.zeros((H, W, 4), np.uint8)
-    aov = [np.zeros((H, W, 4), np.float16) for _ in range(3)]
-    assert r.readback_framebuffer(acc) and r.readback_framebuffer(fb)
-    for k in range(3):
-        assert r.readback_aov(k, aov[k])
-    return acc, fb, aov[0], aov[1], aov[2]
-
-
-def _same(a, b):
-    return all(np.array_equal(x.view(np.uint8), y.view(np.uint8)) for x, y in zip(a, b))
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def _stats_bytes(r):
-    st = abi.Stats()
-    assert r._L.rptr_hip_stats(r._h, C.byref(st)) == 0
-    return bytes(st)
 
 
 SCENES = [("cornell-37x21", scenes.cornell32, abi.VARIANT_GLTF, 37, 21),
@@ -85,21 +29,21 @@ def test_images_and_history_equal_the_restatement_bit_for_bit(name, make, varian
     own history. 37 x 21: partial tiles on both axes; 72 x 40: several tiles, sky. On the Cornell box the case is shown not to pass
     trivially: there is motion, pixels with and without history from the second frame on, and the result is not rptr_hip_denoise's."""
     s = make()
-    r = _handle(s, W, H)
+    r = renderer(s, W, H)
     r.params.reprojection_mode = 1
     td = T.TemporalDenoiser()
     cam = s.camera_params()
     bad = []
     for k in range(5):
-        r.render(_cfg(s, variant, reset=k == 0, camera=_fly_camera(cam, k)), spp=1)
-        acc, fb, alb, nd, mj = _frame(r, W, H)
+        r.render(config(s, variant, reset=k == 0, camera=fly_camera(cam, k)), spp=1)
+        acc, fb, alb, nd, mj = read_frame(r, W, H)
         r.denoise_temporal(**fields)
         got_f, got_u, got_h = r.readback_denoised_f32(), r.readback_denoised_u8(), r.readback_denoise_history()
         want_f, want_u = td.step(acc, alb, nd, mj, fb, **fields)
         want_h = td.history()
-        nf = int(np.count_nonzero(_bits(got_f) != _bits(want_f)))
+        nf = int(np.count_nonzero(float_bits(got_f) != float_bits(want_f)))
         nu = int(np.count_nonzero(got_u != want_u))
-        nh = int(np.count_nonzero(_bits(got_h) != _bits(want_h)))
+        nh = int(np.count_nonzero(float_bits(got_h) != float_bits(want_h)))
         surf = D.surface(nd, alb)
         n = got_h[..., 3]
         moved = int(np.count_nonzero(mj[..., :2]))
@@ -115,7 +59,7 @@ def test_images_and_history_equal_the_restatement_bit_for_bit(name, make, varian
             if k == 4:
                 spatial = {f: v for f, v in fields.items() if f in D.DEFAULTS}
                 r.denoise(**spatial)
-                assert not np.array_equal(_bits(r.readback_denoised_f32()), _bits(got_f))
+                assert not np.array_equal(float_bits(r.readback_denoised_f32()), float_bits(got_f))
         else:
             assert (~surf).any()
     r.close()
@@ -127,7 +71,7 @@ def test_first_call_reset_and_reinitialize_equal_the_spatial_denoiser():
     demodulate_albedo differs from the history's -- stores rptr_hip_denoise's images of the same frame bit for bit"""
     s = scenes.cornell32()
     W, H = 37, 21
-    r = _handle(s, W, H)
+    r = renderer(s, W, H)
     r.params.reprojection_mode = 1
 
     def both(**fields):
@@ -136,18 +80,18 @@ def test_first_call_reset_and_reinitialize_equal_the_spatial_denoiser():
         want = r.readback_denoised_f32(), r.readback_denoised_u8()
         r.denoise_temporal(**fields)
         got = r.readback_denoised_f32(), r.readback_denoised_u8()
-        return _same(got, want), r.readback_denoise_history()
+        return same_images(got, want), r.readback_denoise_history()
 
-    r.render(_cfg(s, abi.VARIANT_GLTF), spp=1)
+    r.render(config(s, abi.VARIANT_GLTF), spp=1)
     same, hist = both(iterations=3)
     assert same and set(np.unique(hist[..., 3])) <= {0.0, 1.0}                       # the first call
-    r.render(_cfg(s, abi.VARIANT_GLTF, reset=False), spp=1)
+    r.render(config(s, abi.VARIANT_GLTF, reset=False), spp=1)
     same, hist = both(iterations=3)
     assert not same and hist[..., 3].max() == 2                                      # (a call with history is another image)
-    r.render(_cfg(s, abi.VARIANT_GLTF, reset=False), spp=1)
+    r.render(config(s, abi.VARIANT_GLTF, reset=False), spp=1)
     same, hist = both(iterations=3, reset_history=1)
     assert same and hist[..., 3].max() == 1                                          # reset_history
-    r.render(_cfg(s, abi.VARIANT_GLTF, reset=False), spp=1)
+    r.render(config(s, abi.VARIANT_GLTF, reset=False), spp=1)
     same, hist = both(iterations=3, demodulate_albedo=0)
     assert same and hist[..., 3].max() == 1                                          # the history is in other units
     W, H = 40, 24
@@ -155,7 +99,7 @@ def test_first_call_reset_and_reinitialize_equal_the_spatial_denoiser():
     r.set_scene(s)
     with pytest.raises(backend.BackendError):
         r.readback_denoise_history()                                                 # initialize dropped it
-    r.render(_cfg(s, abi.VARIANT_GLTF), spp=1)
+    r.render(config(s, abi.VARIANT_GLTF), spp=1)
     same, hist = both(iterations=3, demodulate_albedo=0)
     assert same and hist.shape == (H, W, 4) and hist[..., 3].max() == 1              # the first call after initialize at another size
     r.close()
@@ -166,14 +110,14 @@ def test_it_denoises_better_than_one_frame_can():
     the spatial denoiser's on the 8th frame, and below the raw frame's"""
     s = scenes.cornell32()
     W, H = 64, 64
-    r = _handle(s, W, H)
-    r.render(_cfg(s, abi.VARIANT_GLTF), spp=512)
-    ref = _frame(r, W, H)[0]
+    r = renderer(s, W, H)
+    r.render(config(s, abi.VARIANT_GLTF), spp=512)
+    ref = read_frame(r, W, H)[0]
     r.params.reprojection_mode = 1
     raws = []
     for k in range(8):
-        r.render(_cfg(s, abi.VARIANT_GLTF, reset=k == 0), spp=1)
-        raws.append(_frame(r, W, H)[0])
+        r.render(config(s, abi.VARIANT_GLTF, reset=k == 0), spp=1)
+        raws.append(read_frame(r, W, H)[0])
         if k == 1:
             assert not np.array_equal(raws[0], raws[1])                              # fresh samples per frame
         r.denoise_temporal()
@@ -189,19 +133,19 @@ def test_it_denoises_better_than_one_frame_can():
 def _run(scene, variant, W, H, mode, taa, calls_after):
     """frames 0..3 of 1 spp (no reset after the first); calls_after: frame indices after which denoise_temporal() is called. -> per frame
     its read-backs, and the handle's stats bytes before / after each call"""
-    r = _handle(scene, W, H, options={"taa": 1} if taa else None)
+    r = renderer(scene, W, H, options={"taa": 1} if taa else None)
     r.params.reprojection_mode = mode
     out, stats = [], []
     for k in range(4):
-        r.render(_cfg(scene, variant, reset=k == 0), spp=1)
-        before = _frame(r, W, H)
+        r.render(config(scene, variant, reset=k == 0), spp=1)
+        before = read_frame(r, W, H)
         if k in calls_after:
-            st0 = _stats_bytes(r)
+            st0 = bytes(raw_stats(r))
             r.denoise_temporal()
             den = r.readback_denoised_f32()
             assert not np.array_equal(den, before[0])
-            stats.append((st0, _stats_bytes(r)))
-            assert _same(before, _frame(r, W, H)), k     # the frame's own images and AOVs are what they were
+            stats.append((st0, bytes(raw_stats(r))))
+            assert same_images(before, read_frame(r, W, H)), k     # the frame's own images and AOVs are what they were
         out.append(before)
     r.close()
     return out, stats
@@ -217,7 +161,7 @@ def test_frame_state_is_left_alone(mode, taa):
     with_calls, stats = _run(s, abi.VARIANT_GLTF, W, H, mode, taa, (0, 1, 2))
     assert len(stats) == 3 and all(a == b for a, b in stats)
     for k in range(4):
-        assert _same(plain[k], with_calls[k]), k
+        assert same_images(plain[k], with_calls[k]), k
 
 
 def test_a_spatial_call_between_two_temporal_calls_changes_nothing():
@@ -227,11 +171,11 @@ def test_a_spatial_call_between_two_temporal_calls_changes_nothing():
     W, H = 40, 24
     results = []
     for interleave in (False, True):
-        r = _handle(s, W, H)
+        r = renderer(s, W, H)
         r.params.reprojection_mode = 1
         cam = s.camera_params()
         for k in range(3):
-            r.render(_cfg(s, abi.VARIANT_GLTF, reset=k == 0, camera=_fly_camera(cam, k)), spp=1)
+            r.render(config(s, abi.VARIANT_GLTF, reset=k == 0, camera=fly_camera(cam, k)), spp=1)
             r.denoise_temporal()
             out = r.readback_denoised_f32(), r.readback_denoised_u8(), r.readback_denoise_history()
             if interleave:
@@ -240,7 +184,7 @@ def test_a_spatial_call_between_two_temporal_calls_changes_nothing():
         results.append(out)
         r.close()
     assert results[0][2][..., 3].max() == 3
-    assert _same(results[0], results[1])
+    assert same_images(results[0], results[1])
 
 
 def test_frames_in_flight_denoise_the_waited_frame():
@@ -248,16 +192,16 @@ def test_frames_in_flight_denoise_the_waited_frame():
     frame's context images and equal the synchronous run bit for bit"""
     s = scenes.cornell32()
     W, H = 40, 24
-    r = _handle(s, W, H)
+    r = renderer(s, W, H)
     want = []
     for k in range(2):
-        r.render(_cfg(s, abi.VARIANT_GLTF, reset=k == 0), spp=1)
+        r.render(config(s, abi.VARIANT_GLTF, reset=k == 0), spp=1)
         r.denoise_temporal(iterations=4)
         want.append((r.readback_denoised_f32(), r.readback_denoised_u8(), r.readback_denoise_history()))
     r.close()
-    r = _handle(s, W, H, frames_in_flight=2)
-    t0 = r.render_async(_cfg(s, abi.VARIANT_GLTF), spp=1)
-    t1 = r.render_async(_cfg(s, abi.VARIANT_GLTF, reset=False), spp=1)
+    r = renderer(s, W, H, frames_in_flight=2)
+    t0 = r.render_async(config(s, abi.VARIANT_GLTF), spp=1)
+    t1 = r.render_async(config(s, abi.VARIANT_GLTF, reset=False), spp=1)
     r.wait(t0)
     r.denoise_temporal(iterations=4)
     got0 = r.readback_denoised_f32(), r.readback_denoised_u8(), r.readback_denoise_history()
@@ -268,7 +212,7 @@ def test_frames_in_flight_denoise_the_waited_frame():
     r.denoise_temporal(iterations=4)
     got1 = r.readback_denoised_f32(), r.readback_denoised_u8(), r.readback_denoise_history()
     r.close()
-    assert _same(got0, want[0]) and _same(got1, want[1])
+    assert same_images(got0, want[0]) and same_images(got1, want[1])
     assert want[1][2][..., 3].max() == 2
 
 
@@ -283,9 +227,9 @@ def _refused(fn, code, names_call=True):
 def test_refusals():
     s = scenes.cornell32()
     W, H = 32, 24
-    cfg = _cfg(s, abi.VARIANT_GLTF)
+    cfg = config(s, abi.VARIANT_GLTF)
     INV, UNS = abi.RPTR_E_INVALID, abi.RPTR_E_UNSUPPORTED
-    r = _handle(s, W, H)
+    r = renderer(s, W, H)
     assert "before a frame" in _refused(r.denoise_temporal, INV)                 # no frame yet
     assert "rptr_hip_denoise_temporal first" in _refused(r.readback_denoise_history, INV, False)
     r.render(cfg, spp=1)
@@ -325,16 +269,16 @@ def test_refusals():
     r.params.render_upscale_factor = 1
     r.denoise_temporal()
     r.close()
-    r = _handle(s, W, H, options={"aovs": 0})
+    r = renderer(s, W, H, options={"aovs": 0})
     r.render(cfg, spp=1)
     msg = _refused(r.denoise_temporal, UNS)
     assert '"aovs" is 0' in msg and "motion" in msg
     r.close()
-    r = _handle(s, W, H, rank=0, world_size=2, stripe_rows=8)
+    r = renderer(s, W, H, rank=0, world_size=2, stripe_rows=8)
     r.render(cfg, spp=1)
     assert "world_size" in _refused(r.denoise_temporal, UNS)
     r.close()
-    r = _handle(s, W, H, frames_in_flight=2)                                     # the waited frame's context is being rendered to again
+    r = renderer(s, W, H, frames_in_flight=2)                                     # the waited frame's context is being rendered to again
     t0 = r.render_async(cfg, spp=1)
     r.wait(t0)
     t1 = r.render_async(cfg, spp=1)
@@ -344,7 +288,7 @@ def test_refusals():
     r.wait(t2)
     r.denoise_temporal()
     r.close()
-    r = _handle(s, W, H, frames_in_flight=2)                                     # the waited frame is not the last of its launch sequence
+    r = renderer(s, W, H, frames_in_flight=2)                                     # the waited frame is not the last of its launch sequence
     tickets = r.render_batch_async(cfg, spp=1, n_frames=2, reset_rest=False)
     r.wait(tickets[0])
     assert "launch sequence" in _refused(r.denoise_temporal, INV)

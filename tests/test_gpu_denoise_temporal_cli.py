@@ -7,19 +7,20 @@ import subprocess
 import numpy as np
 import pytest
 
+from common import fly_camera
+from host_tools import ACCUMULATE_INI, build_host_tool, read_png
 from realtimepathtracingresearchframework_amd import abi, backend, scenes
-from test_gpu_taa_upscale_cli import INI, _build_cli, _fly_camera, _read_png
 
 pytestmark = pytest.mark.gpu
 
 
 def test_denoise_temporal_flag_writes_the_mirrors_denoised_images(tmp_path):
-    exe = _build_cli(tmp_path)
+    exe = build_host_tool("rptr_cli")
     s = scenes.cornell32()
     path = str(tmp_path / "cornell.rpsc")
     s.dump(path)
     ini = tmp_path / "realtime.ini"
-    ini.write_text(INI)   # (reprojection_mode 2: the moving camera keeps its accumulation, so only the first frame resets the history)
+    ini.write_text(ACCUMULATE_INI)   # (reprojection_mode 2: the moving camera keeps its accumulation, so only the first frame resets the history)
     W, H, n = 64, 48, 3
     run = subprocess.run([exe, path, "--config", str(ini), "--img", str(W), str(H), "--batch-spp", "1", "--synchronous", "--fly-through", "--png",
                           "--profiling-fps", "1", "--profiling-count", str(n), "--profiling", str(tmp_path / "dt"), "--profiling-img", str(tmp_path / "dt"),
@@ -32,10 +33,10 @@ def test_denoise_temporal_flag_writes_the_mirrors_denoised_images(tmp_path):
     r.params.reprojection_mode = 2
     cam = s.camera_params()
     for _ in range(4):
-        r.render(backend.RenderConfiguration(_fly_camera(cam, 0), active_variant=abi.VARIANT_GLTF, reset_accumulation=True), spp=1)
+        r.render(backend.RenderConfiguration(fly_camera(cam, 0), active_variant=abi.VARIANT_GLTF, reset_accumulation=True), spp=1)
     want = []
     for k in range(n):
-        r.render(backend.RenderConfiguration(_fly_camera(cam, k), active_variant=abi.VARIANT_GLTF, reset_accumulation=k == 0), spp=1)
+        r.render(backend.RenderConfiguration(fly_camera(cam, k), active_variant=abi.VARIANT_GLTF, reset_accumulation=k == 0), spp=1)
         r.denoise_temporal(iterations=3, reset_history=int(k == 0))
         want.append(r.readback_denoised_u8())
     assert r.readback_denoise_history()[..., 3].max() == n                    # the last image carries the history of all three
@@ -43,7 +44,7 @@ def test_denoise_temporal_flag_writes_the_mirrors_denoised_images(tmp_path):
     assert not np.array_equal(r.readback_denoised_u8(), want[-1])             # ... and is not the spatial denoiser's
     r.close()
     for k in range(n):
-        got = _read_png("%s_%04d.png" % (tmp_path / "dt", k + 1))
+        got = read_png("%s_%04d.png" % (tmp_path / "dt", k + 1))
         assert got.shape == (H, W, 4)
         assert np.array_equal(got, want[k]), (k, int(np.count_nonzero(got != want[k])))
 
@@ -54,7 +55,7 @@ REFUSED = [(["--denoise", "3"], "--denoise-temporal and --denoise cannot be comb
 
 
 def test_denoise_temporal_refused_combinations(tmp_path):
-    exe = _build_cli(tmp_path)
+    exe = build_host_tool("rptr_cli")
     s = scenes.cornell32()
     path = str(tmp_path / "cornell.rpsc")
     s.dump(path)

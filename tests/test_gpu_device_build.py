@@ -14,17 +14,10 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
-from common import RMSE_TOL, assert_ray_visit_parity, gpu_render, image_error, random_queries
+from common import RMSE_TOL, assert_ray_visit_parity, gpu_render, image_error, random_queries, renderer
 from realtimepathtracingresearchframework_amd import abi, backend, scenes
 
 pytestmark = pytest.mark.gpu
-
-
-def _renderer(scene, W=64, H=48):
-    r = backend.RenderHip()
-    r.initialize(W, H)
-    r.set_scene(scene)
-    return r
 
 
 @pytest.mark.parametrize("scene_fn,lo,hi,flatten", [
@@ -39,7 +32,7 @@ def test_device_built_trees_answer_like_brute_force_and_like_their_host_statemen
     monkeypatch.setenv("RPTR_FLATTEN", flatten)
     monkeypatch.setenv("RPTR_BVH_BUILDER", "device")
     monkeypatch.setenv("RPTR_PLOC_TOP", "64")        # small scenes: leave the clustering some iterations and the top some clusters
-    r = _renderer(s)
+    r = renderer(s, 64, 48)
     built, ms, dms = r.bvh_build_info()
     assert built and dms > 0.0
     nodes, tris, insts = r.export_bvh()

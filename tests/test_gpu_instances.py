@@ -5,59 +5,18 @@ independently of the tree (min t, ties by ids), so query results are compared bi
 
 two_level_test has one emissive parameterized mesh, and instances of an emissive mesh cannot move (their light triangles are world-space
 data of the host). The parity tests move EVERY instance, so they run on two_level_test with that material's emission set to 0
-(`_movable_two_level`); the emissive rejection has its own test on the unchanged scene."""
-import copy
-
+(`movable_two_level`); the emissive rejection has its own test on the unchanged scene."""
 import numpy as np
 import pytest
 
 import oracle_lib as O
-from common import RMSE_TOL, assert_ray_visit_parity, gpu_render, image_error, random_queries
+from common import (RMSE_TOL, assert_ray_visit_parity, gpu_render, image_error, movable_two_level, random_queries, random_transforms, renderer,
+                    with_transforms)
 from realtimepathtracingresearchframework_amd import abi, backend, scenes
 
 pytestmark = pytest.mark.gpu
 
 POLICIES = [abi.TLAS_REBUILD, abi.TLAS_REFIT]
-
-
-def _movable_two_level(n_inst=12, move_bit=True):
-    s = scenes.two_level_test(n_inst=n_inst)
-    s.materials[3] = abi.make_material((1, 1, 1), roughness=0.4)
-    s.prepare_lights()
-    if move_bit:
-        for m in s.meshes:
-            m.dynamic = abi.MESH_INSTANCES_MOVE
-    return s
-
-
-def _transforms(n, seed, spread=4.0):
-    """rotation x NON-uniform scale + translation, float32 (n, 3, 4)"""
-    rng = np.random.default_rng(seed)
-    out = np.zeros((n, 3, 4), np.float32)
-    for i in range(n):
-        ang = rng.uniform(0, 2 * np.pi)
-        axis = rng.normal(size=3)
-        axis /= np.linalg.norm(axis)
-        K = np.array([[0, -axis[2], axis[1]], [axis[2], 0, -axis[0]], [-axis[1], axis[0], 0]])
-        R = np.eye(3) + np.sin(ang) * K + (1 - np.cos(ang)) * K @ K
-        out[i, :, :3] = R @ np.diag(rng.uniform(0.5, 1.7, size=3))
-        out[i, :, 3] = rng.uniform(-spread, spread, size=3)
-    return out
-
-
-def _moved(scene, xf, first=0):
-    s = copy.copy(scene)
-    s.instances = [copy.copy(i) for i in scene.instances]
-    for k, m in enumerate(xf):
-        s.instances[first + k].transform = np.asarray(m, np.float32).reshape(3, 4).copy()
-    return s
-
-
-def _renderer(scene, W=96, H=64, **kw):
-    r = backend.RenderHip(**kw)
-    r.initialize(W, H)
-    r.set_scene(scene)
-    return r
 
 
 def _records(insts):
@@ -66,10 +25,10 @@ def _records(insts):
 
 @pytest.mark.parametrize("policy", POLICIES)
 def test_moved_scene_equals_the_oracle_and_a_fresh_set_scene(policy):
-    s = _movable_two_level()
-    xf = _transforms(len(s.instances), 21)
-    moved = _moved(s, xf)
-    r = _renderer(s)
+    s = movable_two_level()
+    xf = random_transforms(len(s.instances), 21)
+    moved = with_transforms(s, xf)
+    r = renderer(s, 96, 64)
     r.set_tlas_policy(policy)
     q = random_queries(np.random.default_rng(4), 20000, -6, 6)
     before = r.render_ray_queries(q).copy()
@@ -94,7 +53,7 @@ def test_moved_scene_equals_the_oracle_and_a_fresh_set_scene(policy):
     assert same and rmse < RMSE_TOL
     assert_ray_visit_parity(r, osc, 96, 64, 2, abi.VARIANT_GLTF)
     # a fresh set_scene of the moved scene: same records, same query results, same image
-    f = _renderer(moved)
+    f = renderer(moved, 96, 64)
     fres = f.render_ray_queries(q).copy()
     assert np.array_equal(res.view(np.uint32), fres.view(np.uint32))
     ri, fi = _records(r.export_bvh()[2]), _records(f.export_bvh()[2])  # (one record per instance here; each build orders them its own way)
@@ -108,8 +67,8 @@ def test_moved_scene_equals_the_oracle_and_a_fresh_set_scene(policy):
 
 
 def test_identity_update_under_refit_reproduces_the_built_tree():
-    s = _movable_two_level()
-    r = _renderer(s)
+    s = movable_two_level()
+    r = renderer(s, 96, 64)
     r.set_tlas_policy(abi.TLAS_REFIT)
     n0, t0, i0 = (a.copy() for a in r.export_bvh())
     r.update_instances(0, np.stack([np.asarray(i.transform, np.float32) for i in s.instances]))
@@ -125,13 +84,13 @@ def test_identity_update_under_refit_reproduces_the_built_tree():
 @pytest.mark.parametrize("policy", POLICIES)
 def test_device_source_equals_host_source(policy):
     import torch
-    s = _movable_two_level()
-    xf = _transforms(len(s.instances), 33)
-    a = _renderer(s)
+    s = movable_two_level()
+    xf = random_transforms(len(s.instances), 33)
+    a = renderer(s, 96, 64)
     a.set_tlas_policy(policy)
     a.update_instances(0, xf)
     a.refit()
-    b = _renderer(s)
+    b = renderer(s, 96, 64)
     b.set_tlas_policy(policy)
     buf = torch.from_numpy(np.ascontiguousarray(xf.reshape(-1, 12))).cuda()
     torch.cuda.synchronize()
@@ -143,7 +102,7 @@ def test_device_source_equals_host_source(policy):
     assert b.get_option("instance_updates_rejected") == 0
     # a device-source call cannot return an error for a bad matrix: a singular and a NaN matrix leave their instances where they are
     # and are counted; the good ones of the same call move
-    xf2 = _transforms(len(s.instances), 34)
+    xf2 = random_transforms(len(s.instances), 34)
     bad = xf2.copy()
     bad[3, 2, :3] = bad[3, 1, :3]
     bad[7, 0, 3] = np.nan
@@ -163,16 +122,16 @@ def test_device_source_equals_host_source(policy):
 
 @pytest.mark.parametrize("policy", POLICIES)
 def test_fifty_updates_along_a_path_do_not_drift(policy):
-    s = _movable_two_level()
+    s = movable_two_level()
     n = len(s.instances)
-    x0, x1 = _transforms(n, 5), _transforms(n, 6)
-    r = _renderer(s)
+    x0, x1 = random_transforms(n, 5), random_transforms(n, 6)
+    r = renderer(s, 96, 64)
     r.set_tlas_policy(policy)
     for k in range(1, 51):
         w = np.float32(k / 50.0)
         r.update_instances(0, ((1 - w) * x0 + w * x1).astype(np.float32) if k < 50 else x1)
         r.refit()
-    one = _renderer(s)
+    one = renderer(s, 96, 64)
     one.set_tlas_policy(policy)
     one.update_instances(0, x1)
     one.refit()
@@ -190,7 +149,7 @@ def test_partial_flattening_moves_the_movers_and_leaves_the_flat_tree():
     s.meshes[1].dynamic = abi.MESH_INSTANCES_MOVE
     movers = [i for i, inst in enumerate(s.instances) if s.pmeshes[inst.pmesh].mesh == 1]
     baked = [i for i, inst in enumerate(s.instances) if s.pmeshes[inst.pmesh].mesh != 1]
-    r = _renderer(s)
+    r = renderer(s, 96, 64)
     n0, t0, i0 = (a.copy() for a in r.export_bvh())
     rec0 = _records(i0).view(np.int32)
     assert int(((rec0[:, 12] >= 0) & (rec0[:, 14] < 0)).sum()) == 1  # partially flattened: the flat tree's identity record
@@ -200,7 +159,7 @@ def test_partial_flattening_moves_the_movers_and_leaves_the_flat_tree():
     moved = s
     for k, i in enumerate(movers):  # (instances of one mesh are not contiguous: one call each)
         r.update_instances(i, xf[k:k + 1])
-        moved = _moved(moved, xf[k:k + 1], first=i)
+        moved = with_transforms(moved, xf[k:k + 1], first=i)
     r.refit()
     n1, t1, i1 = r.export_bvh()
     assert np.array_equal(t0.view(np.uint32), t1.view(np.uint32))  # no triangle of the flat tree (world space) or of a mesh changed
@@ -229,19 +188,19 @@ def test_partial_flattening_moves_the_movers_and_leaves_the_flat_tree():
 
 @pytest.mark.parametrize("policy", POLICIES)
 def test_deformed_and_moved_in_one_refit(policy):
-    s = _movable_two_level()
+    s = movable_two_level()
     s.meshes[1].dynamic = abi.MESH_DYNAMIC | abi.MESH_INSTANCES_MOVE
-    xf = _transforms(len(s.instances), 8)
+    xf = random_transforms(len(s.instances), 8)
     g = s.geometries[1]
     P = (scenes.dequantize_positions(g.qpos, g.scaling, g.offset) * np.float32(1.4) + np.array([0.2, -0.3, 0.1], np.float32)).astype(np.float32)
-    r = _renderer(s)
+    r = renderer(s, 96, 64)
     r.set_tlas_policy(policy)
     r.update_vertices(1, P)
     r.update_instances(0, xf)
     r.refit()
     q = random_queries(np.random.default_rng(9), 20000, -6, 6)
     res = r.render_ray_queries(q).copy()
-    osc = O.OracleScene(_moved(s, xf))
+    osc = O.OracleScene(with_transforms(s, xf))
     osc.set_dynamic_vertices(1, P)
     ref = np.zeros_like(res)
     osc.trace(q, bvh_mode=O.BVH_BRUTE, out=ref)
@@ -254,15 +213,15 @@ def test_deformed_and_moved_in_one_refit(policy):
 def test_animated_instances_with_frames_in_flight_equal_one_at_a_time(dynamic_mesh):
     """(update, refit, render_async) x 5 with 3 frame contexts gives the frames of the same sequence one at a time. With a dynamic mesh in
     the scene every context owns its tree AND its instance records; without one a refit waits for the frames in flight."""
-    s = _movable_two_level()
+    s = movable_two_level()
     if dynamic_mesh:
         s.meshes[0].dynamic = abi.MESH_DYNAMIC | abi.MESH_INSTANCES_MOVE
     n = len(s.instances)
-    steps = [_transforms(n, 40), None, _transforms(n, 41), _transforms(n, 41), _transforms(n, 42)]
+    steps = [random_transforms(n, 40), None, random_transforms(n, 41), random_transforms(n, 41), random_transforms(n, 42)]
     W, H = 96, 64
 
     def run(fif):
-        r = _renderer(s, W, H, frames_in_flight=fif)
+        r = renderer(s, W, H, frames_in_flight=fif)
         cam = s.camera_params()
         images, queue = [], []
 
@@ -291,7 +250,7 @@ def test_animated_instances_with_frames_in_flight_equal_one_at_a_time(dynamic_me
         assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
     assert np.array_equal(q3.view(np.uint32), ref_q.view(np.uint32))
     assert not np.array_equal(ref_images[0], ref_images[2])
-    ref, _ = O.OracleScene(_moved(s, steps[-1])).render(W, H, 1, variant=abi.VARIANT_SIMPLE, frame_offset=4)
+    ref, _ = O.OracleScene(with_transforms(s, steps[-1])).render(W, H, 1, variant=abi.VARIANT_SIMPLE, frame_offset=4)
     rmse, same, _ = image_error(images[-1], ref)
     assert same and rmse < RMSE_TOL
 
@@ -301,15 +260,15 @@ def test_coincident_instances_and_a_single_instance(policy):
     """All centroids equal: every Morton code ties and the radix tree is the one over the index bits. One instance: a root with one leaf."""
     q = random_queries(np.random.default_rng(12), 8000, -3, 3)
     for n_inst in (12, 1):
-        s = _movable_two_level(n_inst=n_inst)
+        s = movable_two_level(n_inst=n_inst)
         one = np.array([[0.9, 0, 0, 0.5], [0, 1.1, 0, -0.25], [0, 0, 1.0, 0.75]], np.float32)
         xf = np.repeat(one[None], n_inst, axis=0)
-        r = _renderer(s)
+        r = renderer(s, 96, 64)
         r.set_tlas_policy(policy)
         r.update_instances(0, xf)
         r.refit()
         res = r.render_ray_queries(q).copy()
-        osc = O.OracleScene(_moved(s, xf))
+        osc = O.OracleScene(with_transforms(s, xf))
         ref = np.zeros_like(res)
         osc.trace(q, bvh_mode=O.BVH_BRUTE, out=ref)
         assert np.array_equal(res.view(np.uint32), ref.view(np.uint32))
@@ -325,9 +284,9 @@ def test_rejected_updates_leave_the_scene_unchanged():
     s = scenes.two_level_test()  # (unchanged: parameterized mesh 2 is emissive)
     for m in s.meshes:
         m.dynamic = abi.MESH_INSTANCES_MOVE
-    r = _renderer(s)
+    r = renderer(s, 96, 64)
     before = [a.copy() for a in r.export_bvh()]
-    ok = _transforms(1, 3)
+    ok = random_transforms(1, 3)
 
     def rejected(code, first, xf):
         with pytest.raises(backend.BackendError) as e:
@@ -357,13 +316,13 @@ def test_rejected_updates_leave_the_scene_unchanged():
 
 
 def test_rebuild_count_counts_every_scene_copy():
-    s = _movable_two_level()
+    s = movable_two_level()
     s.meshes[0].dynamic = abi.MESH_DYNAMIC | abi.MESH_INSTANCES_MOVE  # dynamic + 2 contexts: two scene copies beside the master set
-    r = _renderer(s, frames_in_flight=2)
+    r = renderer(s, 96, 64, frames_in_flight=2)
     cam = s.camera_params()
     tickets = []
     for k in range(2):
-        r.update_instances(0, _transforms(len(s.instances), 50 + k))
+        r.update_instances(0, random_transforms(len(s.instances), 50 + k))
         r.refit()
         tickets.append(r.render_async(backend.RenderConfiguration(cam, active_variant=abi.VARIANT_SIMPLE, reset_accumulation=True), spp=1))
     for t in tickets:
@@ -372,7 +331,7 @@ def test_rebuild_count_counts_every_scene_copy():
     r.export_bvh()                                                  # the master tree follows on demand
     assert r.tlas_rebuild_count() == 3
     r.set_tlas_policy(abi.TLAS_REFIT)
-    r.update_instances(0, _transforms(len(s.instances), 60))
+    r.update_instances(0, random_transforms(len(s.instances), 60))
     r.refit()
     r.export_bvh()
     assert r.tlas_rebuild_count() == 3
@@ -410,7 +369,7 @@ def test_stack_bound_of_set_scene_covers_the_rebuilt_top_level(layout):
     else:
         xf[:, :, 3] = 0
         xf[:, 0, 3] = (np.float32(2.0) ** (np.arange(n) % 11) + np.arange(n) // 11 * 1e-3).astype(np.float32)
-    r = _renderer(s)
+    r = renderer(s, 96, 64)
     r.update_instances(0, xf)
     r.refit()
     assert r.tlas_rebuild_count() == 1
@@ -424,7 +383,7 @@ def test_stack_bound_of_set_scene_covers_the_rebuilt_top_level(layout):
     q = random_queries(np.random.default_rng(1), 4000, -20, 20)
     res = r.render_ray_queries(q).copy()
     ref = np.zeros_like(res)
-    O.OracleScene(_moved(s, xf)).trace(q, bvh_mode=O.BVH_BRUTE, out=ref)
+    O.OracleScene(with_transforms(s, xf)).trace(q, bvh_mode=O.BVH_BRUTE, out=ref)
     assert np.array_equal(res.view(np.uint32), ref.view(np.uint32))
     r.close()
 
@@ -454,16 +413,16 @@ def test_rebuild_earns_its_place_after_a_permutation(seed):
     xf = np.stack([np.asarray(i.transform, np.float32) for i in s.instances[:n]])
     new = xf.copy()
     new[:, :, 3] = xf[perm][:, :, 3]
-    moved = _moved(s, new)
+    moved = with_transforms(s, new)
     out = {}
     for name, policy in (("rebuild", abi.TLAS_REBUILD), ("refit", abi.TLAS_REFIT)):
-        r = _renderer(s, 256, 144)
+        r = renderer(s, 256, 144)
         r.set_tlas_policy(policy)
         r.update_instances(0, new)
         r.refit()
         out[name] = _visits_per_ray(r, moved)
         r.close()
-    f = _renderer(moved, 256, 144)
+    f = renderer(moved, 256, 144)
     out["fresh"] = _visits_per_ray(f, moved)
     f.close()
     print("seed %d: closest-hit node visits per ray: rebuild %.2f refit %.2f fresh set_scene %.2f (rebuild / fresh %.3f)"

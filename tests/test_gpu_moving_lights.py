@@ -7,14 +7,14 @@ triangles each. The yardstick of a moved scene is the moved Scene with lights[:,
 
 Frames are 96 x 64, 2 spp, VARIANT_GLTF; image tolerances are those of test_gpu_instances.py (common.RMSE_TOL, image_error). The light
 buffer is compared bit for bit: the placement is the float32 arithmetic of collect_emitters without contraction, on both sides."""
-import copy
 import ctypes as C
 
 import numpy as np
 import pytest
 
 import oracle_lib as O
-from common import RMSE_TOL, assert_ray_visit_parity, gpu_render, image_error, random_queries
+from common import (RMSE_TOL, assert_ray_visit_parity, float_bits, gpu_render, image_error, random_queries, random_transforms, renderer,
+                    scene_transforms, with_transforms)
 from realtimepathtracingresearchframework_amd import abi, backend, lights as L, scenes
 
 pytestmark = pytest.mark.gpu
@@ -27,25 +27,6 @@ EMISSIVE = (2, 5, 8, 11)
 MOVE_SEED = 22
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def _transforms(n, seed, spread=4.0):
-    """rotation x NON-uniform scale + translation, float32 (n, 3, 4)"""
-    rng = np.random.default_rng(seed)
-    out = np.zeros((n, 3, 4), np.float32)
-    for i in range(n):
-        ang = rng.uniform(0, 2 * np.pi)
-        axis = rng.normal(size=3)
-        axis /= np.linalg.norm(axis)
-        K = np.array([[0, -axis[2], axis[1]], [axis[2], 0, -axis[0]], [-axis[1], axis[0], 0]])
-        R = np.eye(3) + np.sin(ang) * K + (1 - np.cos(ang)) * K @ K
-        out[i, :, :3] = R @ np.diag(rng.uniform(0.5, 1.7, size=3))
-        out[i, :, 3] = rng.uniform(-spread, spread, size=3)
-    return out
-
-
 def _scene(deforming=False):
     s = scenes.two_level_test(n_inst=12)
     for m in s.meshes:
@@ -55,16 +36,9 @@ def _scene(deforming=False):
     return s
 
 
-def _scene_transforms(s):
-    return np.stack([np.asarray(i.transform, np.float32).reshape(3, 4) for i in s.instances])
-
-
 def _moved(scene, xf, positions=None, stale=False):
     """the yardstick: the Scene with the new transforms and its lights placed by the rule (stale: left where they were)"""
-    s = copy.copy(scene)
-    s.instances = [copy.copy(i) for i in scene.instances]
-    for k, m in enumerate(xf):
-        s.instances[k].transform = np.asarray(m, np.float32).reshape(3, 4).copy()
+    s = with_transforms(scene, xf)
     s.lights = scene.lights.copy()
     if not stale:
         s.lights[:, :3] = L.place_light_sources(scene.light_sources, xf, positions)
@@ -72,9 +46,7 @@ def _moved(scene, xf, positions=None, stale=False):
 
 
 def _renderer(scene, register=True, **kw):
-    r = backend.RenderHip(**kw)
-    r.initialize(W, H)
-    r.set_scene(scene)
+    r = renderer(scene, W, H, **kw)
     if register:
         r.set_light_sources(scene)
     return r
@@ -106,7 +78,7 @@ def scene():
 @pytest.fixture(scope="module")
 def move(scene):
     """the transforms of the frame tests, the yardstick scene, its oracle and the oracle's frame (made once, never changed)"""
-    xf = _transforms(len(scene.instances), MOVE_SEED)
+    xf = random_transforms(len(scene.instances), MOVE_SEED)
     yard = _moved(scene, xf)
     osc = O.OracleScene(yard)
     ref, _ = osc.render(W, H, SPP, variant=abi.VARIANT_GLTF)
@@ -119,17 +91,17 @@ def move(scene):
 def test_light_buffer_after_a_move_is_the_placement(scene, policy):
     r = _renderer(scene)
     r.set_tlas_policy(policy)
-    assert np.array_equal(_bits(r.readback_lights()), _bits(scene.lights))            # registering changes nothing
-    r.update_instances(0, _scene_transforms(scene))                                      # an identity update
+    assert np.array_equal(float_bits(r.readback_lights()), float_bits(scene.lights))            # registering changes nothing
+    r.update_instances(0, scene_transforms(scene))                                      # an identity update
     r.refit()
-    assert np.array_equal(_bits(r.readback_lights()), _bits(scene.lights))
-    xf = _transforms(len(scene.instances), 21)
+    assert np.array_equal(float_bits(r.readback_lights()), float_bits(scene.lights))
+    xf = random_transforms(len(scene.instances), 21)
     r.update_instances(0, xf)
     r.refit()
     got = r.readback_lights()
     want = _moved(scene, xf).lights
-    assert np.array_equal(_bits(got), _bits(want))
-    assert not np.array_equal(_bits(got[:, :3]), _bits(scene.lights[:, :3])) and np.array_equal(_bits(got[:, 3]), _bits(scene.lights[:, 3]))
+    assert np.array_equal(float_bits(got), float_bits(want))
+    assert not np.array_equal(float_bits(got[:, :3]), float_bits(scene.lights[:, :3])) and np.array_equal(float_bits(got[:, 3]), float_bits(scene.lights[:, 3]))
     r.close()
 
 
@@ -160,7 +132,7 @@ def test_frame_after_a_move_equals_the_oracle_and_a_fresh_set_scene(scene, move,
     frmse, fsame, _ = image_error(img, fimg)
     print("policy %d: rmse vs fresh set_scene %.3e" % (policy, frmse))
     assert fsame and frmse < RMSE_TOL
-    assert np.array_equal(_bits(r.readback_lights()), _bits(f.readback_lights()))
+    assert np.array_equal(float_bits(r.readback_lights()), float_bits(f.readback_lights()))
     f.close()
     r.close()
 
@@ -170,19 +142,19 @@ def test_frame_after_a_move_equals_the_oracle_and_a_fresh_set_scene(scene, move,
 def test_deformed_emitter_takes_its_lights_along(case):
     s = _scene(deforming=True)
     P = _deformed_positions(s)
-    xf = _scene_transforms(s)
+    xf = scene_transforms(s)
     r = _renderer(s)
     if case != "vertices":     # a vertex update and an instance move in ONE refit, the mesh's tree rebuilt on the device: its triangles
         r.set_bvh_policy(force_bvh_rebuild=True)   # are reordered, the float positions the placement reads are not
-        xf = _transforms(len(s.instances), MOVE_SEED)
+        xf = random_transforms(len(s.instances), MOVE_SEED)
         r.update_instances(0, xf)
     r.update_vertices(1, P)
     r.refit()
     if case != "vertices":
         assert r.bvh_rebuild_count() == 1
     yard = _moved(s, xf, {1: P})
-    assert np.array_equal(_bits(r.readback_lights()), _bits(yard.lights))
-    assert not np.array_equal(_bits(yard.lights[:, :3]), _bits(_moved(s, xf).lights[:, :3]))
+    assert np.array_equal(float_bits(r.readback_lights()), float_bits(yard.lights))
+    assert not np.array_equal(float_bits(yard.lights[:, :3]), float_bits(_moved(s, xf).lights[:, :3]))
     img, _, _ = gpu_render(yard, W, H, SPP, abi.VARIANT_GLTF, renderer=r)
     osc = O.OracleScene(yard)
     osc.set_dynamic_vertices(1, P)
@@ -198,12 +170,12 @@ def test_moving_lights_with_frames_in_flight_equal_one_at_a_time(scene):
     """(update, refit, render_async) x 5 over three frame contexts, never waiting in between, gives the frames of the same steps rendered
     one at a time: every context owns its light buffer, so a refit never rewrites the lights a frame in flight is sampling"""
     n = len(scene.instances)
-    base = _scene_transforms(scene)
+    base = scene_transforms(scene)
     steps = []
     for k in range(5):
         xf = base.copy()
         for i in EMISSIVE:
-            xf[i] = _transforms(1, 70 + 10 * k + i)[0]
+            xf[i] = random_transforms(1, 70 + 10 * k + i)[0]
         steps.append(xf)
     assert n == 12
 
@@ -232,15 +204,15 @@ def test_moving_lights_with_frames_in_flight_equal_one_at_a_time(scene):
     ref_images, ref_lights = run(1)
     images, lights = run(3)
     for a, b in zip(images, ref_images):
-        assert np.array_equal(_bits(a), _bits(b))
-    assert np.array_equal(_bits(lights), _bits(ref_lights)) and np.array_equal(_bits(lights), _bits(_moved(scene, steps[-1]).lights))
+        assert np.array_equal(float_bits(a), float_bits(b))
+    assert np.array_equal(float_bits(lights), float_bits(ref_lights)) and np.array_equal(float_bits(lights), float_bits(_moved(scene, steps[-1]).lights))
     assert not np.array_equal(ref_images[0], ref_images[2])
 
 
 # ---- 5. device source
 def test_device_source_gives_the_same_light_buffer(scene):
     import torch
-    xf = _transforms(len(scene.instances), 33)
+    xf = random_transforms(len(scene.instances), 33)
     a = _renderer(scene)
     a.update_instances(0, xf)
     a.refit()
@@ -250,7 +222,7 @@ def test_device_source_gives_the_same_light_buffer(scene):
     b.update_instances_device(0, buf.data_ptr(), xf.shape[0])
     b.refit()
     la, lb = a.readback_lights(), b.readback_lights()
-    assert np.array_equal(_bits(la), _bits(lb)) and np.array_equal(_bits(la), _bits(_moved(scene, xf).lights))
+    assert np.array_equal(float_bits(la), float_bits(lb)) and np.array_equal(float_bits(la), float_bits(_moved(scene, xf).lights))
     assert b.get_option("instance_updates_rejected") == 0
     a.close()
     b.close()
@@ -268,8 +240,8 @@ def test_radiance_queries_after_a_move_equal_a_fresh_set_scene(scene, move):
     res = r.render_radiance_queries(q, cam, variant=abi.VARIANT_GLTF, spp=2).copy()
     f = _renderer(yard, register=False)
     fres = f.render_radiance_queries(q, cam, variant=abi.VARIANT_GLTF, spp=2).copy()
-    assert np.array_equal(_bits(res), _bits(fres))     # (bit for bit, like the comparisons between runs in test_gpu_radiance_queries.py)
-    assert not np.array_equal(_bits(res), _bits(before)) and (res[:, :3] > 0).any()
+    assert np.array_equal(float_bits(res), float_bits(fres))     # (bit for bit, like the comparisons between runs in test_gpu_radiance_queries.py)
+    assert not np.array_equal(float_bits(res), float_bits(before)) and (res[:, :3] > 0).any()
     f.close()
     r.close()
 
@@ -301,7 +273,7 @@ def test_rejected_registrations_leave_everything_unchanged(scene):
         return img
 
     img0 = frozen_frame()
-    assert np.array_equal(_bits(frozen_frame()), _bits(img0))      # (the comparison below can tell: frozen frames repeat)
+    assert np.array_equal(float_bits(frozen_frame()), float_bits(img0))      # (the comparison below can tell: frozen frames repeat)
     rejected(src[:-1])                                               # count != num_lights
     rejected(np.concatenate([src, src[:1]]))
     swapped = src.copy()                                             # a light of instance 2 said to come from instance 5: same mesh, same
@@ -322,17 +294,17 @@ def test_rejected_registrations_leave_everything_unchanged(scene):
     with pytest.raises(backend.BackendError):
         r.readback_lights(len(src) + 1)
     # ... and the registration made before them still stands: same buffer, same frame, an emissive instance still moves
-    assert np.array_equal(_bits(r.readback_lights()), _bits(lights0))
-    assert np.array_equal(_bits(frozen_frame()), _bits(img0))
-    r.update_instances(2, _scene_transforms(scene)[2:3])
+    assert np.array_equal(float_bits(r.readback_lights()), float_bits(lights0))
+    assert np.array_equal(float_bits(frozen_frame()), float_bits(img0))
+    r.update_instances(2, scene_transforms(scene)[2:3])
     r.refit()
-    assert np.array_equal(_bits(r.readback_lights()), _bits(lights0))
+    assert np.array_equal(float_bits(r.readback_lights()), float_bits(lights0))
     r.close()
 
 
 def test_unregistering_and_a_new_set_scene_drop_the_registration(scene):
     r = _renderer(scene, register=False)
-    ok = _transforms(1, 3)
+    ok = random_transforms(1, 3)
 
     def unsupported():
         with pytest.raises(backend.BackendError) as e:
@@ -344,17 +316,17 @@ def test_unregistering_and_a_new_set_scene_drop_the_registration(scene):
     r.update_instances(2, ok)
     r.refit()
     moved = r.readback_lights()
-    assert not np.array_equal(_bits(moved), _bits(scene.lights))
+    assert not np.array_equal(float_bits(moved), float_bits(scene.lights))
     r.set_light_sources(None)                                        # (NULL, 0): the lights are the ones set_scene uploaded again
     unsupported()
-    assert np.array_equal(_bits(r.readback_lights()), _bits(scene.lights))
+    assert np.array_equal(float_bits(r.readback_lights()), float_bits(scene.lights))
     r.set_light_sources(scene.light_sources)                         # the array form; registered again
     r.update_instances(2, ok)
     r.refit()
-    assert np.array_equal(_bits(r.readback_lights()), _bits(moved))
+    assert np.array_equal(float_bits(r.readback_lights()), float_bits(moved))
     r.set_scene(scene)                                               # a new scene: the registration is gone
     unsupported()
-    assert np.array_equal(_bits(r.readback_lights()), _bits(scene.lights))
+    assert np.array_equal(float_bits(r.readback_lights()), float_bits(scene.lights))
     r.close()
 
 
@@ -362,13 +334,13 @@ def test_unregistering_and_a_new_set_scene_drop_the_registration(scene):
 def test_fifty_updates_that_end_at_the_start_leave_the_lights_bit_identical(scene):
     """placement starts from the object-space source every time, never from the previous placement"""
     n = len(scene.instances)
-    x0, x1 = _scene_transforms(scene), _transforms(n, 6)
+    x0, x1 = scene_transforms(scene), random_transforms(n, 6)
     r = _renderer(scene)
     for k in range(1, 51):
         w = np.float32(np.sin(np.pi * k / 50.0))                     # out along the path and back
         r.update_instances(0, ((1 - w) * x0 + w * x1).astype(np.float32) if k < 50 else x0)
         r.refit()
         if k == 25:
-            assert not np.array_equal(_bits(r.readback_lights()), _bits(scene.lights))
-    assert np.array_equal(_bits(r.readback_lights()), _bits(scene.lights))
+            assert not np.array_equal(float_bits(r.readback_lights()), float_bits(scene.lights))
+    assert np.array_equal(float_bits(r.readback_lights()), float_bits(scene.lights))
     r.close()

@@ -7,19 +7,13 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from common import raw_stats, read_frame, renderer, same_images
 from realtimepathtracingresearchframework_amd import abi, backend, scenes
 
 pytestmark = pytest.mark.gpu
 
 SIZES = (1, 31, 33, 65, 4099)
 SKIP = np.int32(-1).view(np.float32)  # mode_or_data < 0
-
-
-def _renderer(s, W=64, H=48, **kw):
-    r = backend.RenderHip(**kw)
-    r.initialize(W, H)
-    r.set_scene(s)
-    return r
 
 
 def _rays(n, seed, lo, hi):
@@ -57,7 +51,7 @@ CASES = {  # scene, renderer options, the box the origins come from
 def test_opaque_bits_are_the_counted_diagnostics_the_brute_forces_and_the_closest_hit_querys(case):
     make, options, lo, hi = CASES[case]
     s = make()
-    r = _renderer(s, options=options)
+    r = renderer(s, 64, 48, options=options)
     osc = O.OracleScene(s)
     full = _rays(max(SIZES), 1000 + len(case), lo, hi)
     for n in SIZES:
@@ -89,7 +83,7 @@ def test_opaque_bits_are_the_counted_diagnostics_the_brute_forces_and_the_closes
 def test_skipped_queries_and_the_bits_behind_n_keep_the_callers_pattern(n):
     import torch
     s = scenes.two_level_test()
-    r = _renderer(s)
+    r = renderer(s, 64, 48)
     q = _rays(n, 50 + n, (-5, -5, -5), (5, 5, 5))
     answer = _bits_of(r, q)
     assert n < 100 or (answer.sum() > 20 and (~answer).sum() > 20)
@@ -162,7 +156,7 @@ def test_world_size_two_answers_like_one_rank():
     """every rank holds the whole scene: as for rptr_hip_trace, the ranks are not asked"""
     s = scenes.cornell32()
     q = _rays(500, 3, (-1, -1, -1), (1, 1, 1))
-    r = _renderer(s)
+    r = renderer(s, 64, 48)
     one = _bits_of(r, q)
     r.close()
     r = backend.RenderHip(rank=0, world_size=2)
@@ -177,7 +171,7 @@ def test_world_size_two_answers_like_one_rank():
 def test_waves_that_take_several_pools_agree_with_the_closest_hit_query_and_with_themselves():
     import torch
     s = scenes.cornell32()
-    r = _renderer(s)
+    r = renderer(s, 64, 48)
     n = 2 ** 20 + 37
     resident_waves = r.get_option("traversal_resident_blocks") * 4  # 256 threads per block
     while n <= resident_waves * 64:
@@ -253,7 +247,7 @@ def test_cutout_bits_are_the_opaque_bits_of_the_scene_without_what_the_cutoff_ig
     everything = (A64, A191, NOALPHA0, LITERAL)
     q = _rays(6000, 404, (-2.0, -1.0, 0.1), (2.0, 1.6, 3.0))
     q[:, 6] = -np.abs(q[:, 6])  # towards the screens and the wall
-    handles = {name: _renderer(_screens_scene(keep, wall)) for name, keep, wall in (
+    handles = {name: renderer(_screens_scene(keep, wall), 64, 48) for name, keep, wall in (
         ("all", everything, True), ("without 64", (A191, NOALPHA0, LITERAL), True), ("without both", (NOALPHA0, LITERAL), True),
         ("only the two solid", (NOALPHA0, LITERAL), False))}
     opaque = {name: _bits_of(h, q) for name, h in handles.items()}
@@ -276,7 +270,7 @@ def test_cutout_bits_are_the_opaque_bits_of_the_scene_without_what_the_cutoff_ig
 # ---------------------------------------------------------------- 5. the cutout rule on fractional texels: properties
 def test_cutout_on_fractional_texels_is_monotonic_and_a_subset_of_opaque():
     s = scenes.alpha_test()
-    r = _renderer(s)
+    r = renderer(s, 64, 48)
     q = _rays(8000, 55, (-2.0, 0.05, -1.0), (2.0, 2.5, 3.0))
     opaque = _bits_of(r, q)
     counted = r.trace_counted(q, tmin=None, any_hit=True)[0][:, 0] != 0
@@ -312,7 +306,7 @@ def test_bits_follow_moved_instances_like_a_fresh_scene():
         M[:, :3] = M[:, :3] @ np.float32([[0, 1, 0], [-1, 0, 0], [0, 0, 1]])  # a quarter turn as well
         moved[k] = M
     q = _rays(6000, 66, (-5, -5, -5), (5, 5, 5))
-    r = _renderer(s)
+    r = renderer(s, 64, 48)
     before = _bits_of(r, q)
     for k, M in moved.items():
         r.update_instances(k, M[None])
@@ -320,7 +314,7 @@ def test_bits_follow_moved_instances_like_a_fresh_scene():
     after = _bits_of(r, q)
     assert np.array_equal(after, _closest_hit(r, q))
     r.close()
-    fresh = _renderer(scene(moved))
+    fresh = renderer(scene(moved), 64, 48)
     want = _bits_of(fresh, q)
     fresh.close()
     print("occluded before / after the move: %d / %d, %d bits changed" % (int(before.sum()), int(after.sum()), int((before != after).sum())))
@@ -329,49 +323,29 @@ def test_bits_follow_moved_instances_like_a_fresh_scene():
 
 
 # ---------------------------------------------------------------- 7. frames in flight and isolation
-def _frame_images(r, W, H):
-    img = np.zeros((H, W, 4), np.float32)
-    assert r.readback_framebuffer(img) == W * H * 4
-    u8 = np.zeros((H, W, 4), np.uint8)
-    assert r.readback_framebuffer(u8) == W * H * 4
-    aovs = []
-    for k in range(3):
-        a = np.zeros((H, W, 4), np.float16)
-        assert r.readback_aov(k, a) == W * H * 4
-        aovs.append(a.view(np.uint16).copy())
-    return [img.view(np.uint32), u8] + aovs
-
-
-def _raw_stats(r):
-    st = abi.Stats()
-    assert r._L.rptr_hip_stats(r._h, C.byref(st)) == 0
-    return st
-
-
 def test_a_run_beside_a_frame_in_flight_is_right_and_leaves_the_frame_alone():
     s = scenes.two_level_test()
     W, H = 96, 64
     cam = s.camera_params()
     q = _rays(3000, 12, (-5, -5, -5), (5, 5, 5))
-    r = _renderer(s, W, H)
+    r = renderer(s, W, H)
     want = _bits_of(r, q)
     r.close()
 
     def run(with_queries):
-        r = _renderer(s, W, H, frames_in_flight=2)
+        r = renderer(s, W, H, frames_in_flight=2)
         t0 = r.render_async(backend.RenderConfiguration(cam, active_variant=abi.VARIANT_GLTF, reset_accumulation=True), spp=2)
         if with_queries:  # submitted and not waited for: the run waits for it
             assert np.array_equal(_bits_of(r, q), want)
         else:
             r.wait(t0)
-        st = _raw_stats(r)
-        out = _frame_images(r, W, H), (st.spp, int(st.rays_closest), int(st.rays_shadow), int(st.hits_shaded))
+        st = raw_stats(r)
+        out = read_frame(r, W, H), (st.spp, int(st.rays_closest), int(st.rays_shadow), int(st.hits_shaded))
         r.close()
         return out
 
     a, b = run(False), run(True)
-    for x, y in zip(a[0], b[0]):
-        assert np.array_equal(x, y)
+    assert same_images(a[0], b[0])
     assert a[1] == b[1] and a[1][0] == 2
 
 
@@ -380,13 +354,12 @@ def test_a_run_on_an_idle_handle_leaves_images_and_stats_alone():
     W, H = 96, 64
     cam = s.camera_params()
     q = _rays(W * H + 50, 2, (-5, -5, -5), (5, 5, 5))
-    r = _renderer(s, W, H)
+    r = renderer(s, W, H)
     r.render(backend.RenderConfiguration(cam, active_variant=abi.VARIANT_GLTF, reset_accumulation=True), spp=2)
-    before, first = _raw_stats(r), _frame_images(r, W, H)
+    before, first = raw_stats(r), read_frame(r, W, H)
     assert _bits_of(r, q).any()
-    assert bytes(before) == bytes(_raw_stats(r)) and before.spp == 2 and before.rays_closest > 0
-    for x, y in zip(first, _frame_images(r, W, H)):
-        assert np.array_equal(x, y)
+    assert bytes(before) == bytes(raw_stats(r)) and before.spp == 2 and before.rays_closest > 0
+    assert same_images(first, read_frame(r, W, H))
     r.close()
 
 

@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
-from common import RMSE_TOL, assert_ray_visit_parity, gpu_render, image_error, random_queries
+from common import RMSE_TOL, aov_close, assert_ray_visit_parity, gpu_render, image_error, random_queries
 from realtimepathtracingresearchframework_amd import abi, backend, scenes
 from realtimepathtracingresearchframework_amd import distributed as D
 
@@ -712,18 +712,6 @@ def test_vks_scene_renders_like_the_oracle(version):
 
 
 # ---------------------------------------------------------------- AOV images (RenderGraphic::readback_aov)
-def _aov_close(a, b, what):
-    """float16 images: the same finite / non-finite pattern and values within two half ulps (the floats behind them differ by
-    libm ulps between host and device; an RGBA16F store rounds them)"""
-    a32, b32 = a.astype(np.float32), b.astype(np.float32)
-    fa, fb = np.isfinite(a32), np.isfinite(b32)
-    assert (fa == fb).mean() > 0.9995, what
-    both = fa & fb
-    err = np.abs(a32[both] - b32[both])
-    tol = 2.0 ** -9 * np.maximum(np.abs(b32[both]), 2.0 ** -5)
-    assert (err <= tol).mean() > 0.999, (what, float(err.max()))
-
-
 @pytest.mark.parametrize("variant", [abi.VARIANT_GLTF, abi.VARIANT_SIMPLE])
 def test_aov_images_match_the_oracle(variant):
     s = scenes.textured_test()
@@ -733,13 +721,13 @@ def test_aov_images_match_the_oracle(variant):
     for k, name in enumerate(("albedo_roughness", "normal_depth", "motion_jitter")):
         got = np.zeros((H, W, 4), np.float16)
         assert r.readback_aov(k, got) == W * H * 4
-        _aov_close(got, aovs[k], name)
+        aov_close(got, aovs[k], name)
     # the next frame accumulates; its first sample (index 2) writes the AOVs again, the view did not move
     img2, _, _ = gpu_render(s, W, H, spp, variant, reset=False, renderer=r)
     _, _, aovs2 = O.OracleScene(s).render(W, H, spp, variant=variant, sample_begin=spp, accum=ref.copy(), aovs=True)
     got = np.zeros((H, W, 4), np.float16)
     r.readback_aov(r.AOVNormalDepthIndex, got)
-    _aov_close(got, aovs2[1], "normal_depth of the second frame")
+    aov_close(got, aovs2[1], "normal_depth of the second frame")
     assert r.readback_aov(0, np.zeros(10, np.float16)) == 0          # too small -> 0
     with pytest.raises(backend.BackendError):
         r.readback_aov(5, got)
@@ -762,7 +750,7 @@ def test_aov_motion_and_tiles():
     # the reset before the second frame moved frame_offset on by the one sample of the first (render_vulkan.cpp:1937-1941)
     _, _, aovs = O.OracleScene(s).render(W, H, 1, aovs=True, prev_camera=prev, frame_offset=1)
     hit = np.isfinite(aovs[1].astype(np.float32)[..., 3])       # sky pixels project the point (2e32, 2e32, 2e32): inf - inf, not compared
-    _aov_close(got[hit], aovs[2][hit], "motion_jitter")
+    aov_close(got[hit], aovs[2][hit], "motion_jitter")
     assert np.abs(got.astype(np.float32)[hit][:, 0]).max() > 0.01
     r.close()
     full = np.zeros((H, W, 4), np.float16)

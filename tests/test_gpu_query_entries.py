@@ -5,7 +5,7 @@ advanced. A run that started from a stale cursor would leave result slots untouc
 import numpy as np
 import pytest
 
-from common import random_queries
+from common import random_queries, renderer
 from realtimepathtracingresearchframework_amd import abi, backend, scenes
 
 pytestmark = pytest.mark.gpu
@@ -16,10 +16,7 @@ FETCH = 64           # the smallest pool a traversal wave takes (option "travers
 
 
 def _renderer(s, frames_in_flight):
-    r = backend.RenderHip(frames_in_flight=frames_in_flight, options={"traverse_fetch": FETCH})
-    r.initialize(64, 64)
-    r.set_scene(s)
-    return r
+    return renderer(s, 64, 64, frames_in_flight=frames_in_flight, options={"traverse_fetch": FETCH})
 
 
 def _untouched(rows):

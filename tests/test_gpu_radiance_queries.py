@@ -7,17 +7,10 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
-from common import RMSE_TOL, image_error
+from common import RMSE_TOL, float_bits, image_error, probe_queries, renderer
 from realtimepathtracingresearchframework_amd import abi, backend, pointsets, scenes
 
 pytestmark = pytest.mark.gpu
-
-
-def _renderer(s, W, H, **kw):
-    r = backend.RenderHip(**kw)
-    r.initialize(W, H)
-    r.set_scene(s)
-    return r
 
 
 def _primary_rays(osc, s, W, H, sample, **kw):
@@ -58,7 +51,7 @@ def test_camera_ray_queries_give_the_oracle_frame(name, variant, W, H):
     """1 + 2: queries that are the camera rays of sample 0 (fresh handle) and of sample 3 (first_sample = 3, zeroed results) give the
     oracle's frame of that sample: image, NaN mask, alpha, ray counts"""
     s = _scene(name)
-    r = _renderer(s, W, H)
+    r = renderer(s, W, H)
     osc = O.OracleScene(s)
     kw = {}
     if name == "alpha_test":  # (the alpha tests depend on the order candidates turn up in: the oracle walks the device's tree)
@@ -75,7 +68,7 @@ def test_camera_ray_queries_with_table_point_sets(rng_variant):
     s = scenes.cornell32()
     W, H = 300, 140
     table = pointsets.default_table(rng_variant, seed=5)
-    r = _renderer(s, W, H)
+    r = renderer(s, W, H)
     r.set_rng_variant(rng_variant, table)
     osc = O.OracleScene(s)
     osc.set_rng_variant(rng_variant, table)
@@ -84,38 +77,24 @@ def test_camera_ray_queries_with_table_point_sets(rng_variant):
     r.close()
 
 
-def _probe_queries(n, seed=3):
-    rng = np.random.default_rng(seed)
-    q = np.zeros((n, 8), np.float32)
-    q[:, 0:3] = rng.uniform(-0.8, 0.8, (n, 3)).astype(np.float32) + np.float32([0.0, 1.0, 0.0])
-    d = rng.normal(size=(n, 3))
-    q[:, 4:7] = (d / np.linalg.norm(d, axis=1, keepdims=True)).astype(np.float32)
-    q[:, 7] = 1e20
-    return q
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
 def test_samples_split_over_calls_and_query_prefixes_are_bit_identical():
     """3 + 4: one call of 4 samples == four calls of one sample on the same buffer; the first m results of an n-query run == an m-query run"""
     s = scenes.cornell32()
     W, H = 64, 48
-    r = _renderer(s, W, H)
+    r = renderer(s, W, H)
     cam = s.camera_params()
-    q = _probe_queries(5000)
+    q = probe_queries(5000)
     once = r.render_radiance_queries(q, cam, spp=4)
     assert np.isfinite(once).all() and once[:, :3].max() > 0
     buf = np.full((len(q), 4), 7.0, np.float32)
     for k in range(4):
         r.render_radiance_queries(q, cam, spp=1, first_sample=k, results=buf)
-    assert np.array_equal(_bits(once), _bits(buf))
+    assert np.array_equal(float_bits(once), float_bits(buf))
     m = 1237  # not a multiple of 64
     part = r.render_radiance_queries(q[:m], cam, spp=4)
-    assert np.array_equal(_bits(once[:m]), _bits(part))
+    assert np.array_equal(float_bits(once[:m]), float_bits(part))
     # and the samples matter
-    assert not np.array_equal(_bits(once), _bits(r.render_radiance_queries(q, cam, spp=1)))
+    assert not np.array_equal(float_bits(once), float_bits(r.render_radiance_queries(q, cam, spp=1)))
     r.close()
 
 
@@ -125,20 +104,20 @@ def test_slicing_of_queries_and_samples_does_not_show(monkeypatch):
     s = scenes.two_level_test()
     W, H = 72, 40
     cam = s.camera_params()
-    q = _probe_queries(3 * W * H + 17, seed=9)
-    r = _renderer(s, W, H)
+    q = probe_queries(3 * W * H + 17, seed=9)
+    r = renderer(s, W, H)
     a = r.render_radiance_queries(q, cam, spp=5)
     r.close()
-    r = _renderer(s, W, 4 * H)
+    r = renderer(s, W, 4 * H)
     b = r.render_radiance_queries(q, cam, spp=5)
     r.close()
-    assert np.array_equal(_bits(a), _bits(b))
+    assert np.array_equal(float_bits(a), float_bits(b))
     monkeypatch.setenv("RPTR_MAX_BATCH_SPP", "2")
-    r = _renderer(s, W, H)
+    r = renderer(s, W, H)
     assert r.get_option("sample_slots") == 2
     c = r.render_radiance_queries(q, cam, spp=5)
     r.close()
-    assert np.array_equal(_bits(a), _bits(c))
+    assert np.array_equal(float_bits(a), float_bits(c))
 
 
 @pytest.mark.parametrize("rng_variant", [abi.RNG_VARIANT_BN, abi.RNG_VARIANT_SOBOL, abi.RNG_VARIANT_Z_SBL])
@@ -149,39 +128,39 @@ def test_slicing_does_not_show_with_table_point_sets(rng_variant):
     W, H = 264, 24
     cam = s.camera_params()
     table = pointsets.default_table(rng_variant, seed=5)
-    q = _probe_queries(3 * W * H + 17, seed=13)
+    q = probe_queries(3 * W * H + 17, seed=13)
     out = []
     for h in (H, 4 * H):
-        r = _renderer(s, W, h)
+        r = renderer(s, W, h)
         r.set_rng_variant(rng_variant, table)
         out.append(r.render_radiance_queries(q, cam, spp=3))
         r.close()
-    assert np.isfinite(out[0]).all() and np.array_equal(_bits(out[0]), _bits(out[1]))
-    r = _renderer(s, W, H)  # and the point set matters
+    assert np.isfinite(out[0]).all() and np.array_equal(float_bits(out[0]), float_bits(out[1]))
+    r = renderer(s, W, H)  # and the point set matters
     u = r.render_radiance_queries(q, cam, spp=3)
     r.close()
-    assert not np.array_equal(_bits(u), _bits(out[0]))
+    assert not np.array_equal(float_bits(u), float_bits(out[0]))
 
 
 def test_tail_hand_over_does_not_show():
     """6: the late bounces in the tail kernel from bounce 1 / 2, or not at all: same bits"""
     s = scenes.cornell32()
     cam = s.camera_params()
-    q = _probe_queries(20000, seed=5)
+    q = probe_queries(20000, seed=5)
     out = []
     for tail in (0, 1, 2):
-        r = _renderer(s, 128, 96, options={"tail_bounce": tail})
+        r = renderer(s, 128, 96, options={"tail_bounce": tail})
         out.append(r.render_radiance_queries(q, cam, spp=2))
         r.close()
-    assert np.array_equal(_bits(out[0]), _bits(out[1])) and np.array_equal(_bits(out[0]), _bits(out[2]))
+    assert np.array_equal(float_bits(out[0]), float_bits(out[1])) and np.array_equal(float_bits(out[0]), float_bits(out[2]))
 
 
 def test_skipped_queries_keep_their_slot_and_short_rays_see_the_sky():
     """7: mode_or_data < 0 leaves the slot alone; a query whose t_max ends before the first surface == the query in the empty scene"""
     s = scenes.cornell32()
     cam = s.camera_params()
-    r = _renderer(s, 64, 48)
-    q = _probe_queries(300, seed=11)
+    r = renderer(s, 64, 48)
+    q = probe_queries(300, seed=11)
     skip = np.arange(0, 300, 7)
     q.view(np.int32)[skip, 3] = -5
     buf = np.full((300, 4), 1234.5, np.float32)
@@ -196,10 +175,10 @@ def test_skipped_queries_keep_their_slot_and_short_rays_see_the_sky():
     e = scenes.cornell32()
     e.instances = []
     e.prepare_lights()
-    r = _renderer(e, 64, 48)
+    r = renderer(e, 64, 48)
     sky = r.render_radiance_queries(short, cam, spp=2)
     r.close()
-    assert (got[:, 3] == 0).all() and np.array_equal(_bits(got), _bits(sky))
+    assert (got[:, 3] == 0).all() and np.array_equal(float_bits(got), float_bits(sky))
 
 
 @pytest.mark.parametrize("fif", [1, 3])
@@ -208,10 +187,10 @@ def test_a_query_run_leaves_the_frame_alone(fif):
     s = scenes.two_level_test()
     W, H = 96, 64
     cam = s.camera_params()
-    q = _probe_queries(W * H + 50, seed=2)
+    q = probe_queries(W * H + 50, seed=2)
 
     def run(with_queries):
-        r = _renderer(s, W, H, frames_in_flight=fif)
+        r = renderer(s, W, H, frames_in_flight=fif)
         cfg = backend.RenderConfiguration(cam, active_variant=abi.VARIANT_GLTF, reset_accumulation=True)
         r.render(cfg, spp=2)
         if with_queries:  # ... and right after the run: rptr_hip_stats and the image are the frame's
@@ -221,7 +200,7 @@ def test_a_query_run_leaves_the_frame_alone(fif):
             r.render_radiance_queries(q, cam, spp=3)
             assert r._L.rptr_hip_stats(r._h, C.byref(after)) == 0 and r.readback_framebuffer(img1) == W * H * 4
             assert bytes(before) == bytes(after) and before.spp == 2 and before.rays_closest > 0
-            assert np.array_equal(_bits(img0), _bits(img1))
+            assert np.array_equal(float_bits(img0), float_bits(img1))
         cfg.reset_accumulation = False
         st = r.render(cfg, spp=2)
         img = np.zeros((H, W, 4), np.float32)
@@ -237,7 +216,7 @@ def test_a_query_run_leaves_the_frame_alone(fif):
         return img, u8, aovs, st.spp, int(st.raw.rays_closest), int(st.raw.rays_shadow)
 
     a, b = run(False), run(True)
-    assert np.array_equal(_bits(a[0]), _bits(b[0])) and np.array_equal(a[1], b[1])
+    assert np.array_equal(float_bits(a[0]), float_bits(b[0])) and np.array_equal(a[1], b[1])
     for x, y in zip(a[2], b[2]):
         assert np.array_equal(x, y)
     assert a[3:] == b[3:] and a[3] == 4
@@ -249,9 +228,9 @@ def test_device_entry_budget_and_refusals():
     import torch
     s = scenes.cornell32()
     cam = s.camera_params()
-    r = _renderer(s, 64, 48)
+    r = renderer(s, 64, 48)
     n = 4000
-    q = _probe_queries(n, seed=4)
+    q = probe_queries(n, seed=4)
     host = r.render_radiance_queries(q, cam, spp=3)
     dq, dr = r.enable_ray_queries_device(n)
     hip = C.CDLL("libamdhip64.so")
@@ -261,7 +240,7 @@ def test_device_entry_budget_and_refusals():
     r.render_ray_queries(q[:1])  # (a synchronous call on the backend's stream: the run above has finished)
     dev = np.zeros((n, 4), np.float32)
     assert hip.hipMemcpy(dev.ctypes.data_as(C.c_void_p), dr, dev.nbytes, 2) == 0
-    assert np.array_equal(_bits(host), _bits(dev))
+    assert np.array_equal(float_bits(host), float_bits(dev))
     # a caller's buffers on a caller's stream
     tq = torch.from_numpy(q).cuda()
     tr = torch.zeros((n, 4), dtype=torch.float32, device="cuda")
@@ -269,7 +248,7 @@ def test_device_entry_budget_and_refusals():
     torch.cuda.synchronize()
     r.render_radiance_queries_device(n, cam, spp=3, device_queries=tq.data_ptr(), device_results=tr.data_ptr(), stream=st.cuda_stream)
     st.synchronize()
-    assert np.array_equal(_bits(host), _bits(tr.cpu().numpy()))
+    assert np.array_equal(float_bits(host), float_bits(tr.cpu().numpy()))
 
     def refused(code, what, call):
         with pytest.raises(backend.BackendError) as e:

@@ -1,56 +1,30 @@
 """reprojection_mode 2 (REPROJECTION_MODE_ACCUMULATE) and the TAA pass on the GPU (csrc/realtime_resolve.h), against their numpy
 restatement (tests/realtime_resolve_ref.py) fed the library's own per-frame inputs: the frame means and AOV images of a mode-1 run of
 the same sequence (frame_offset / frame_id advance alike, so the random streams are the same), and the previous frame's stored images."""
-import math
 
 import numpy as np
 import pytest
 
 import realtime_resolve_ref as R
 import taa_upscale_ref as U
+from common import panned_camera, read_frame, renderer
 from realtimepathtracingresearchframework_amd import abi, backend, scenes
 
 pytestmark = pytest.mark.gpu
 
 
-def _panned(cam, k, rate=0.003):
-    """the view yawed by rate * k radians about its up axis (a slow pan)"""
-    d = np.array(cam.dir[:], np.float64)
-    u = np.array(cam.up[:], np.float64)
-    r = np.cross(d, u)
-    r /= np.linalg.norm(r)
-    a = rate * k
-    nd = math.cos(a) * d + math.sin(a) * r
-    nd /= np.linalg.norm(nd)
-    c = abi.Camera()
-    c.pos[:] = cam.pos[:]
-    c.dir[:] = [float(v) for v in nd]
-    c.up[:] = cam.up[:]
-    c.fovy = cam.fovy
-    return c
-
-
 def _readback(r, W, H):
-    acc = np.zeros((H, W, 4), np.float32)
-    fb = np.zeros((H, W, 4), np.uint8)
-    nd = np.zeros((H, W, 4), np.float16)
-    mj = np.zeros((H, W, 4), np.float16)
-    r.readback_framebuffer(acc)
-    r.readback_framebuffer(fb)
-    r.readback_aov(1, nd)
-    r.readback_aov(2, mj)
+    acc, fb, _, nd, mj = read_frame(r, W, H)
     return acc, fb, nd, mj
 
 
 def _sequence(scene, variant, W, H, mode, n, spp, options=None, resets=(0,), rate=0.003, frames_in_flight=1, asynchronous=False):
     """n frames along the pan; per frame (accum, fb, nd, mj)"""
-    r = backend.RenderHip(options=options, frames_in_flight=frames_in_flight)
-    r.initialize(W, H)
-    r.set_scene(scene)
+    r = renderer(scene, W, H, options=options, frames_in_flight=frames_in_flight)
     r.params.reprojection_mode = mode
     cam = scene.camera_params()
     out = []
-    cfg = lambda k: backend.RenderConfiguration(_panned(cam, k, rate), active_variant=variant, reset_accumulation=k in resets)
+    cfg = lambda k: backend.RenderConfiguration(panned_camera(cam, k, rate), active_variant=variant, reset_accumulation=k in resets)
     if not asynchronous:
         for k in range(n):
             r.render(cfg(k), spp=spp)
@@ -112,7 +86,7 @@ def test_reprojection_lowers_the_error_of_a_panning_camera():
     r = backend.RenderHip()
     r.initialize(W, H)
     r.set_scene(s)
-    r.render(backend.RenderConfiguration(_panned(s.camera_params(), n - 1, 0.002), active_variant=abi.VARIANT_SIMPLE, reset_accumulation=True), spp=256)
+    r.render(backend.RenderConfiguration(panned_camera(s.camera_params(), n - 1, 0.002), active_variant=abi.VARIANT_SIMPLE, reset_accumulation=True), spp=256)
     ref = np.zeros((H, W, 4), np.float32)
     r.readback_framebuffer(ref)
     r.close()

@@ -1,14 +1,14 @@
 """Scene copies (csrc/host_scene.inl scene_copy_build: the master set and the frame contexts' own sets go through one constructor)
 and the last-finished-image accessor (csrc/host_access.inl last_finished_image). Everything at 96 x 64 with 1 spp.
 
-The scene is the 12-instance movable two-level scene of test_gpu_instances.py. With meshes[0] MESH_DYNAMIC | MESH_INSTANCES_MOVE and
+The scene is the 12-instance movable two-level scene of test_gpu_instances.py (common.movable_two_level). With meshes[0] MESH_DYNAMIC | MESH_INSTANCES_MOVE and
 three frames in flight it is the smallest scene that has every part of a context copy: its own triangles, shading records, float
 positions, instance records and reserved top-level capacity. With MESH_INSTANCES_MOVE alone the contexts share the master's triangles."""
 import numpy as np
 import pytest
 
+from common import config, movable_two_level, random_transforms
 from realtimepathtracingresearchframework_amd import abi, backend, scenes
-from test_gpu_instances import _movable_two_level, _transforms
 
 pytestmark = pytest.mark.gpu
 
@@ -16,14 +16,10 @@ W, H = 96, 64
 
 
 def _scene(deforms):
-    s = _movable_two_level()
+    s = movable_two_level()
     if deforms:
         s.meshes[0].dynamic = abi.MESH_DYNAMIC | abi.MESH_INSTANCES_MOVE
     return s
-
-
-def _cfg(s, freeze_frame=False):
-    return backend.RenderConfiguration(s.camera_params(), active_variant=abi.VARIANT_SIMPLE, reset_accumulation=True, freeze_frame=freeze_frame)
 
 
 def _round(r, s):
@@ -33,9 +29,9 @@ def _round(r, s):
     g = s.geometries[0]
     P = (scenes.dequantize_positions(g.qpos, g.scaling, g.offset) * np.float32(1.2) + np.array([0.1, 0.2, -0.1], np.float32)).astype(np.float32)
     r.update_vertices(0, P)
-    r.update_instances(0, _transforms(len(s.instances), 70))
+    r.update_instances(0, random_transforms(len(s.instances), 70))
     r.refit()
-    tickets = [r.render_async(_cfg(s, freeze_frame=True), spp=1) for _ in range(3)]
+    tickets = [r.render_async(config(s, abi.VARIANT_SIMPLE, freeze_frame=True), spp=1) for _ in range(3)]
     for t in tickets:
         st = r.wait(t)
     img = np.zeros((H, W, 4), np.float32)
@@ -84,7 +80,7 @@ def reported_bytes(name, fif):
     r = backend.RenderHip(frames_in_flight=fif)
     r.initialize(W, H)
     r.set_scene(s)
-    st = r.wait(r.render_async(_cfg(s), spp=1))
+    st = r.wait(r.render_async(config(s, abi.VARIANT_SIMPLE), spp=1))
     r.close()
     return int(st.raw.device_bytes_allocated)
 
@@ -108,10 +104,10 @@ def test_the_last_image_is_refused_while_a_newer_frame_overwrites_it():
     r = backend.RenderHip(frames_in_flight=2)
     r.initialize(W, H)
     r.set_scene(s)
-    t0 = r.render_async(_cfg(s), spp=1)
-    t1 = r.render_async(_cfg(s), spp=1)
+    t0 = r.render_async(config(s, abi.VARIANT_SIMPLE), spp=1)
+    t1 = r.render_async(config(s, abi.VARIANT_SIMPLE), spp=1)
     r.wait(t0)
-    t2 = r.render_async(_cfg(s), spp=1)
+    t2 = r.render_async(config(s, abi.VARIANT_SIMPLE), spp=1)
     f32, u8 = np.zeros((H, W, 4), np.float32), np.zeros((H, W, 4), np.uint8)
     tile = torch.zeros((r.local_pixel_count(), 4), dtype=torch.float32, device="cuda")
     calls = [lambda: r.readback_framebuffer(f32), lambda: r.readback_framebuffer(u8), lambda: r.copy_tile_to_device(tile.data_ptr(), tile.numel() * 4),

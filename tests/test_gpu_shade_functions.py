@@ -26,6 +26,8 @@ import oracle_lib as O
 import shade_cases as S
 import shade_ref64 as R
 import device_probes as DP
+from common import rel_excess
+from oracle_lib import _p
 from realtimepathtracingresearchframework_amd import abi
 
 pytestmark = pytest.mark.gpu
@@ -39,10 +41,6 @@ EXCEPTIONS = 1e-3      # share of samples allowed to take another branch (their 
 FAST_GLTF_REL_MAX, FAST_GLTF_REL_TAIL = 2e-3, 4e-5   # measured: 1.15e-3 max, like IEEE
 IEEE_GLTF_REL_MAX, IEEE_GLTF_REL_TAIL = 2e-3, 2e-5   # tests/test_shade_ref64.py (the IEEE build equals the oracle bit for bit)
 TEXTURE_ULPS = {0: 16, 1: 64}
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 _LIBS = {}
@@ -103,13 +101,6 @@ def line(name, build, ulp_max, rel, nonfinite):
 
 def nonfinite(*a):
     return int(sum((~np.isfinite(np.asarray(x, np.float32))).sum() for x in a))
-
-
-def rel_excess(got, lo, hi):
-    got = np.asarray(got, np.float64)
-    with np.errstate(invalid="ignore"):
-        d = np.maximum(lo - got, got - hi)
-        return np.where(d > 0, d / np.maximum(np.maximum(np.abs(lo), np.abs(hi)), 1e-30), 0.0)
 
 
 def gltf_eval(fast, m, n, wo, wi, t=False):

@@ -2,58 +2,33 @@
 (tests/taa_upscale_ref.py) fed the library's own per-frame inputs: the RGBA8 frame, the motion AOV and the previous call's output."""
 import ctypes as C
 import functools
-import math
 
 import numpy as np
 import pytest
 
 import taa_upscale_ref as U
+from common import panned_camera, read_frame, renderer
 from realtimepathtracingresearchframework_amd import abi, backend, scenes
 
 pytestmark = pytest.mark.gpu
 
 
-def _panned(cam, k, rate):
-    """the view yawed by rate * k radians about its up axis"""
-    d = np.array(cam.dir[:], np.float64)
-    u = np.array(cam.up[:], np.float64)
-    r = np.cross(d, u)
-    r /= np.linalg.norm(r)
-    a = rate * k
-    nd = math.cos(a) * d + math.sin(a) * r
-    nd /= np.linalg.norm(nd)
-    c = abi.Camera()
-    c.pos[:] = cam.pos[:]
-    c.dir[:] = [float(v) for v in nd]
-    c.up[:] = cam.up[:]
-    c.fovy = cam.fovy
-    return c
-
-
 def _images(r, W, H, upscale, **fields):
-    acc = np.zeros((H, W, 4), np.float32)
-    fb = np.zeros((H, W, 4), np.uint8)
-    aov = [np.zeros((H, W, 4), np.float16) for _ in range(3)]
-    r.readback_framebuffer(acc)
-    r.readback_framebuffer(fb)
-    for k in range(3):
-        r.readback_aov(k, aov[k])
+    frame = read_frame(r, W, H)
     up = None
     if upscale:
         r.taa_upscale(**fields)
         up = r.readback_upscaled()
-    return acc, fb, aov[0], aov[1], aov[2], up
+    return frame + (up,)
 
 
 def _sequence(W, H, mode, n, rate, options=None, upscale=True, frames_in_flight=1, asynchronous=False, reset_calls=()):
     """n frames of 1 spp of scenes.grid(120, 60) along a pan; per frame (accum, fb, albedo, nd, mj, upscaled)"""
     s = scenes.grid(120, 60)
-    r = backend.RenderHip(options=options, frames_in_flight=frames_in_flight)
-    r.initialize(W, H)
-    r.set_scene(s)
+    r = renderer(s, W, H, options=options, frames_in_flight=frames_in_flight)
     r.params.reprojection_mode = mode
     cam = s.camera_params()
-    cfg = lambda k: backend.RenderConfiguration(_panned(cam, k, rate), active_variant=abi.VARIANT_SIMPLE, reset_accumulation=k == 0)
+    cfg = lambda k: backend.RenderConfiguration(panned_camera(cam, k, rate), active_variant=abi.VARIANT_SIMPLE, reset_accumulation=k == 0)
     fields = lambda k: {"reset_history": 1} if k in reset_calls else {}
     out = []
     if not asynchronous:

@@ -26,6 +26,7 @@ import pytest
 
 import oracle_lib as O
 from common import RMSE_TOL, gpu_render, image_error
+from host_tools import build_host_tool, read_pfm
 from realtimepathtracingresearchframework_amd import abi, backend, scenes
 
 pytestmark = pytest.mark.gpu
@@ -60,8 +61,7 @@ def compare_whole_frame(tag, got, ref, st=None, ost=None, coverage=True, rmse_to
 
 # ---------------------------------------------------------------- C1
 def test_c1_cornell_256x256_1spp_through_the_validation_cli(tmp_path):
-    from test_validation_cli import _build_cli, read_pfm
-    exe = _build_cli(tmp_path)
+    exe = build_host_tool("rptr_cli")
     s = scenes.cornell32()
     assert s.num_tris() == 32
     path = str(tmp_path / "cornell.rpsc")

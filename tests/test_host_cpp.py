@@ -5,20 +5,9 @@ import subprocess
 
 import pytest
 
-from realtimepathtracingresearchframework_amd import build
+from host_tools import build_host_tool
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST = os.path.join(ROOT, "realtimepathtracingresearchframework_amd", "host")
-
-
-def _build_demo(tmp_path):
-    if not os.path.exists(build.LIB_PATH):
-        build.build_library()
-    exe = str(tmp_path / "demo_host")
-    libdir = os.path.dirname(build.LIB_PATH)
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", os.path.join(HOST, "demo_host.cpp"), "-o", exe, "-L" + libdir, "-lrptr_hip",
-                           "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"])
-    return exe
 
 
 def test_header_is_valid_c(tmp_path):
@@ -34,14 +23,14 @@ def test_cpp_host_fails_loudly_without_gpu(tmp_path):
     import torch
     if torch.cuda.is_available():
         pytest.skip("GPU present")
-    exe = _build_demo(tmp_path)
+    exe = build_host_tool("demo_host", werror=False)
     p = subprocess.run([exe], capture_output=True, text=True)
     assert p.returncode == 3 and "no CPU fallback" in p.stderr
 
 
 @pytest.mark.gpu
 def test_cpp_host_renders_on_gpu(tmp_path):
-    exe = _build_demo(tmp_path)
+    exe = build_host_tool("demo_host", werror=False)
     p = subprocess.run([exe], capture_output=True, text=True)
     assert p.returncode == 0, p.stderr
     assert "mean radiance" in p.stdout

@@ -10,13 +10,10 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from oracle_lib import _p
 from realtimepathtracingresearchframework_amd import abi, scenes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 # ---------------------------------------------------------------- RNG (pinned)

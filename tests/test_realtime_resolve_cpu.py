@@ -9,6 +9,7 @@ import numpy as np
 
 import realtime_resolve_ref as R
 from code_object import kernel_regs
+from host_tools import build_host_tool
 from realtimepathtracingresearchframework_amd import abi, backend, build, scenes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -135,8 +136,7 @@ ACCUMULATE= 1
 
 def test_ini_reprojection_accumulate_is_mode_two(tmp_path):
     """.ini `reprojection ACCUMULATE` (REPROJECTION_MODE_NAMES) is the real-time resolve, mode 2, without a note that NONE is used"""
-    from test_validation_cli import _build_cli
-    exe = _build_cli(tmp_path)
+    exe = build_host_tool("rptr_cli")
     path = str(tmp_path / "c.rpsc")
     scenes.cornell32().dump(path)
     (tmp_path / "acc.ini").write_text(INI)

@@ -23,16 +23,13 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from oracle_lib import _p
 from realtimepathtracingresearchframework_amd import abi, scenes
 
 FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_shaders.json")
 pytestmark = pytest.mark.skipif(not os.path.exists(FIXTURE), reason="tests/golden/ref_shaders.json absent: it is written by `make -C oracle ref_shaders "
                                 "GLM_ROOT=<dir with glm/glm.hpp>` from the reference's own rendering/*.glsl; this image has no GLM")
 RTOL, ATOL = 2e-5, 1e-6
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 @pytest.fixture(scope="module")

@@ -20,7 +20,7 @@ import pytest
 
 import oracle_lib as O
 from realtimepathtracingresearchframework_amd import abi, build, scenes, vks
-from test_vks import REF_LIB, _compare_with_dump, _ref, _same_streams
+from vks_checks import REF_LIB, compare_with_dump, ref_reader, same_streams
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools", "reference_crosscheck"))
@@ -41,9 +41,9 @@ def test_exported_configuration_is_the_procedural_scene(exported, name):
     assert man["triangles"] == s.num_tris() and man["emitters"] == len(s.lights) and os.access(os.path.join(d, "commands.sh"), os.X_OK)
     if os.path.isfile(REF_LIB):   # the reference's reader on the exported files
         dump = os.path.join(d, "ref_dump.json")
-        assert _ref().ref_vkr_dump(path.encode(), dump.encode()) == 0
-        _compare_with_dump(path, json.load(open(dump)))
-    _same_streams(s, back)
+        assert ref_reader().ref_vkr_dump(path.encode(), dump.encode()) == 0
+        compare_with_dump(path, json.load(open(dump)))
+    same_streams(s, back)
     assert len(back.instances) == len(s.instances) and len(back.lights) == len(s.lights)
     assert len(back.textures) == 3 * len(s.materials)   # the loader's three textures per material: nothing is left a literal
     back.camera, back.config, back.sky_key = s.camera, s.config, s.sky_key

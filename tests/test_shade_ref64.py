@@ -22,12 +22,10 @@ import pytest
 import oracle_lib as O
 import shade_cases as S
 import shade_ref64 as R
+from common import rel_excess
+from oracle_lib import _p
 
 K_IEEE = 4.0
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 def oracle_gltf_eval(m, n, wo, wi, transmission=False):
@@ -41,14 +39,6 @@ def oracle_gltf_eval(m, n, wo, wi, transmission=False):
 def _report(name, e):
     e = e[np.isfinite(e)] if np.any(np.isfinite(e)) else np.zeros(1)
     print("%-34s max band excess %.2f ulp" % (name, float(np.max(e))))
-
-
-def rel_excess(got, lo, hi):
-    """how far a binary32 result lies outside the float64 band [lo, hi], relative to the band's larger end (0 inside)"""
-    got = np.asarray(got, np.float64)
-    with np.errstate(invalid="ignore"):
-        d = np.maximum(lo - got, got - hi)
-        return np.where(d > 0, d / np.maximum(np.maximum(np.abs(lo), np.abs(hi)), 1e-30), 0.0)
 
 
 LAMBERT_REL_MAX = 1e-6

@@ -4,11 +4,11 @@ compiled in place (oracle/_ref/libsky_ref.so) -- bit for bit on random scene sta
 (/root/reference), so these tests run there; the GPU-side test (tests/test_validation_cli.py) uses synthetic tables of the same layout."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from host_tools import build_sky_shim, sky_words
 from realtimepathtracingresearchframework_amd import abi, sky_fit
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -17,39 +17,10 @@ SKY_REF = os.path.join(ROOT, "oracle", "_ref", "libsky_ref.so")
 needs_reference = pytest.mark.skipif(not (os.path.isdir(REF_DATA) and os.path.exists(SKY_REF)),
                                      reason="the Hosek-Wilkie data headers and oracle/_ref/libsky_ref.so exist in the build container only")
 
-SHIM = r'''
-#include "sky_fit.hpp"
-extern "C" int shim_fit(const char *where, const float *sun_dir, float turbidity, const float *albedo, int light_count, RptrSceneParams *out, char *err, int cap) {
-    static rptr::SkyTables t;
-    static std::string loaded;
-    std::string e;
-    if (loaded != where) {
-        t = rptr::SkyTables();
-        if (!rptr::load_sky_tables(where, t, e)) { snprintf(err, cap, "%s", e.c_str()); return 1; }
-        loaded = where;
-    }
-    snprintf(err, cap, "%s", e.c_str());
-    return rptr::fit_sky(t, sun_dir, turbidity, albedo, light_count, *out) ? 0 : 2;
-}
-extern "C" void shim_sun(float h, float a, float *out) { rptr::sun_dir_from_height_angle(h, a, out); }
-'''
-
 
 class RefSkyOut(C.Structure):
     _fields_ = [("configs", (C.c_float * 4) * 9), ("radiances", C.c_float * 4), ("sun_dir", C.c_float * 3), ("sun_cos_angle", C.c_float),
                 ("sun_radiance", C.c_float * 4)]
-
-
-def build_shim(tmp_path):
-    src = tmp_path / "sky_shim.cpp"
-    src.write_text(SHIM)
-    so = str(tmp_path / "libsky_shim.so")
-    # (the reference side is built with plain -O2: no contraction on x86-64 without -mfma, same here)
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "realtimepathtracingresearchframework_amd", "host"),
-                           str(src), "-o", so])
-    L = C.CDLL(so)
-    L.shim_fit.argtypes = [C.c_char_p, C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_float), C.c_int, C.POINTER(abi.SceneParams), C.c_char_p, C.c_int]
-    return L
 
 
 def states(n, seed=5):
@@ -63,10 +34,6 @@ def states(n, seed=5):
         t = float(rng.integers(1, 11)) if rng.uniform() < 0.2 else float(rng.uniform(1.0, 10.0))
         out.append((tuple(float(v) for v in d), t, tuple(float(v) for v in rng.uniform(0, 1, 3))))
     return out
-
-
-def as_words(sp):
-    return np.frombuffer(bytes(sp), np.uint32)[:(160 + 12 + 4 + 16) // 4]   # sky params, sun_dir, sun_cos_angle, sun_radiance
 
 
 def reference_params(R, d, t, al, lights):
@@ -94,7 +61,7 @@ def test_data_headers_are_parsed_completely():
 
 @needs_reference
 def test_cpp_and_python_fit_equal_the_references_code_bit_for_bit(tmp_path):
-    L = build_shim(tmp_path)
+    L = build_sky_shim(tmp_path)
     R = C.CDLL(SKY_REF)
     tables = sky_fit.SkyTables(REF_DATA)
     err = C.create_string_buffer(512)
@@ -105,9 +72,9 @@ def test_cpp_and_python_fit_equal_the_references_code_bit_for_bit(tmp_path):
         got = abi.SceneParams()
         rc = L.shim_fit(REF_DATA.encode(), (C.c_float * 3)(*d), C.c_float(t), (C.c_float * 3)(*al), lights, C.byref(got), err, 512)
         assert rc == 0, err.value
-        assert np.array_equal(as_words(got), as_words(want)), (k, d, t, al)
+        assert np.array_equal(sky_words(got), sky_words(want)), (k, d, t, al)
         py = sky_fit.fit_sky(tables, d, t, al, lights)
-        assert np.array_equal(as_words(py), as_words(want)), (k, d, t, al)
+        assert np.array_equal(sky_words(py), sky_words(want)), (k, d, t, al)
         n_lit += want.sun_radiance[0] > 0
     assert n_lit > 40    # most states have the sun above the horizon: its radiance went through the spectral model
 
@@ -128,7 +95,7 @@ def test_fit_reproduces_the_packaged_sky_configurations():
 
 
 def test_sun_sliders_and_missing_data(tmp_path):
-    L = build_shim(tmp_path)
+    L = build_sky_shim(tmp_path)
     out = (C.c_float * 3)()
     for h, a in ((90.0, 0.0), (30.0, 45.0), (0.0, -180.0), (61.5, 170.25)):
         L.shim_sun(C.c_float(h), C.c_float(a), out)

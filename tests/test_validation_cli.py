@@ -7,35 +7,14 @@ import subprocess
 import numpy as np
 import pytest
 
-from realtimepathtracingresearchframework_amd import abi, build, scenes
+from host_tools import HOST, build_host_tool, read_exr, read_pfm, read_png
+from realtimepathtracingresearchframework_amd import abi, scenes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST = os.path.join(ROOT, "realtimepathtracingresearchframework_amd", "host")
-
-
-def _build_cli(tmp_path):
-    if not os.path.exists(build.LIB_PATH):
-        build.build_library()
-    exe = str(tmp_path / "rptr_hip")
-    libdir = os.path.dirname(build.LIB_PATH)
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", os.path.join(HOST, "rptr_cli.cpp"), "-o", exe, "-L" + libdir,
-                           "-lrptr_hip", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"])
-    return exe
-
-
-def read_pfm(path):
-    """the reference's layout: 'PF', 'w h', '-1.0' (little endian), rows bottom-up, RGB float32"""
-    with open(path, "rb") as f:
-        assert f.readline() == b"PF\n"
-        w, h = (int(v) for v in f.readline().split())
-        assert f.readline() == b"-1.0\n"
-        data = np.frombuffer(f.read(), dtype="<f4")
-    assert data.size == w * h * 3
-    return data.reshape(h, w, 3)[::-1]
 
 
 def test_scene_dump_round_trips_through_the_cpp_loader(tmp_path):
-    exe = _build_cli(tmp_path)
+    exe = build_host_tool("rptr_cli")
     s = scenes.grid(20, 10, with_emitters=True)
     path = str(tmp_path / "grid.rpsc")
     s.dump(path)
@@ -56,64 +35,6 @@ def test_scene_dump_round_trips_through_the_cpp_loader(tmp_path):
     with open(path, "wb") as f:
         f.write(blob[:len(blob) // 2])
     assert subprocess.run([exe, path, "--describe"], capture_output=True).returncode == 3
-
-
-def read_exr(path):
-    """minimal reader of what write_image.hpp writes: single-part scan-line OpenEXR, no compression, channels A B G R of one
-    type -> (h, w, 4) RGBA array (float32, or uint16 holding halfs)"""
-    import struct
-    raw = open(path, "rb").read()
-    assert struct.unpack_from("<II", raw, 0) == (20000630, 2)
-    at, attrs = 8, {}
-    while raw[at] != 0:
-        name_end = raw.index(b"\0", at)
-        type_end = raw.index(b"\0", name_end + 1)
-        size = struct.unpack_from("<I", raw, type_end + 1)[0]
-        attrs[raw[at:name_end].decode()] = (raw[name_end + 1:type_end].decode(), raw[type_end + 5:type_end + 5 + size])
-        at = type_end + 5 + size
-    at += 1
-    assert attrs["compression"][1] == b"\0" and attrs["lineOrder"][1] == b"\0"
-    x0, y0, x1, y1 = struct.unpack("<4i", attrs["dataWindow"][1])
-    w, h = x1 - x0 + 1, y1 - y0 + 1
-    ch, names, types = attrs["channels"][1], [], []
-    k = 0
-    while ch[k] != 0:
-        e = ch.index(b"\0", k)
-        names.append(ch[k:e].decode())
-        types.append(struct.unpack_from("<I", ch, e + 1)[0])
-        k = e + 1 + 16
-    assert names == ["A", "B", "G", "R"] and len(set(types)) == 1
-    dt = np.float32 if types[0] == 2 else np.uint16
-    offsets = struct.unpack_from("<%dQ" % h, raw, at)
-    img = np.zeros((h, w, 4), dt)
-    for y in range(h):
-        yy, size = struct.unpack_from("<iI", raw, offsets[y])
-        assert yy == y and size == w * 4 * np.dtype(dt).itemsize
-        rows = np.frombuffer(raw, dtype=dt, count=4 * w, offset=offsets[y] + 8).reshape(4, w)
-        img[y, :, 3], img[y, :, 2], img[y, :, 1], img[y, :, 0] = rows[0], rows[1], rows[2], rows[3]
-    return img
-
-
-def read_png(path):
-    """8-bit RGBA PNG with filter type 0 rows (what write_image.hpp writes) -> (h, w, 4) uint8; checks every chunk's CRC"""
-    import struct
-    import zlib
-    raw = open(path, "rb").read()
-    assert raw[:8] == b"\x89PNG\r\n\x1a\n"
-    at, idat, w, h = 8, b"", 0, 0
-    while at < len(raw):
-        n, kind = struct.unpack_from(">I4s", raw, at)
-        data = raw[at + 8:at + 8 + n]
-        assert zlib.crc32(kind + data) == struct.unpack_from(">I", raw, at + 8 + n)[0]
-        if kind == b"IHDR":
-            w, h, depth, colour = struct.unpack_from(">IIBB", data, 0)
-            assert (depth, colour) == (8, 6)
-        elif kind == b"IDAT":
-            idat += data
-        at += 12 + n
-    rows = np.frombuffer(zlib.decompress(idat), np.uint8).reshape(h, 1 + 4 * w)
-    assert (rows[:, 0] == 0).all()
-    return rows[:, 1:].reshape(h, w, 4).copy()
 
 
 def test_image_writers(tmp_path):
@@ -152,7 +73,7 @@ int main(int, char **argv) {
 def test_vks_scene_reaches_the_cpp_host_tool(tmp_path):
     """.vks -> `python -m ...vks --dump` -> bin/rptr_hip: the reference's asset format in front of the C++ host"""
     from realtimepathtracingresearchframework_amd import vks
-    exe = _build_cli(tmp_path)
+    exe = build_host_tool("rptr_cli")
     src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "vks", "alpha_v4.vks")
     dump = str(tmp_path / "alpha.rpsc")
     assert vks.main([src, "--dump", dump, "--eye", "0.4", "1.3", "4.6", "--center", "0", "0.9", "0", "--fov", "45", "--sky", "low_sun"]) == 0
@@ -169,7 +90,7 @@ def test_validation_cli_fails_loudly_without_gpu(tmp_path):
     import torch
     if torch.cuda.is_available():
         pytest.skip("GPU present")
-    exe = _build_cli(tmp_path)
+    exe = build_host_tool("rptr_cli")
     path = str(tmp_path / "c.rpsc")
     scenes.cornell32().dump(path)
     p = subprocess.run([exe, path, "--validation", str(tmp_path / "out"), "--validation-spp", "1", "--img", "32", "32", "--pfm"],
@@ -183,7 +104,7 @@ def test_validation_pfm_matches_backend_and_oracle(tmp_path):
     and within the north_star tolerance of the oracle."""
     import oracle_lib as O
     from common import RMSE_TOL, gpu_render, image_error
-    exe = _build_cli(tmp_path)
+    exe = build_host_tool("rptr_cli")
     s = scenes.cornell32()
     path = str(tmp_path / "cornell.rpsc")
     s.dump(path)
@@ -210,7 +131,7 @@ def test_validation_accumulates_in_launch_sequences_with_the_bits_of_synchronous
     frame continues the accumulation of the one before it), instead of one synchronous frame per batch_spp samples: every image it writes
     -- with --every-frame one per frame, at the same sample counts -- has the bits the synchronous loop writes (--synchronous), for a
     target that is not a multiple of the sequence length and for frames of several samples."""
-    exe = _build_cli(tmp_path)
+    exe = build_host_tool("rptr_cli")
     s = scenes.grid(60, 30, with_emitters=True)
     path = str(tmp_path / "grid.rpsc")
     s.dump(path)
@@ -238,7 +159,7 @@ def test_queued_validation_fits_its_launch_sequences_to_the_sample_slots_of_a_la
     """above ~2.9 Mpixel per rank a frame context holds fewer than 16 sample slots (rptr_hip_get_option "sample_slots": 5 at 4K with
     the default path budget), and the queued --validation run used to ask for sequences of 16 samples regardless -- RPTR_E_INVALID, no image.
     The CLI now clamps a sequence to the slots: a 4K run with 2-sample frames completes, and writes the synchronous loop's bits."""
-    exe = _build_cli(tmp_path)
+    exe = build_host_tool("rptr_cli")
     path = str(tmp_path / "c.rpsc")
     scenes.cornell32().dump(path)
     W, H = 3840, 2160
@@ -259,7 +180,7 @@ def test_queued_validation_fits_its_launch_sequences_to_the_sample_slots_of_a_la
 
 
 def test_cli_rejects_bad_mode_combinations(tmp_path):
-    exe = _build_cli(tmp_path)
+    exe = build_host_tool("rptr_cli")
     path = str(tmp_path / "c.rpsc")
     scenes.cornell32().dump(path)
     # validation and profiling are mutually exclusive (cmdline.cpp:479-486); one of them is required
@@ -273,7 +194,7 @@ def test_cli_rejects_bad_mode_combinations(tmp_path):
 def test_textured_scene_through_the_dump_and_the_cli(tmp_path):
     """textures travel in the scene dump: the C++ host renders the textured scene like the Python mirror, bit for bit"""
     from common import gpu_render
-    exe = _build_cli(tmp_path)
+    exe = build_host_tool("rptr_cli")
     s = scenes.textured_test()
     path = str(tmp_path / "tex.rpsc")
     s.dump(path)
@@ -291,7 +212,7 @@ def test_profiling_mode_csv_images_and_camera_flags(tmp_path):
     second of animation time; --eye/--center/--fov move the camera (compared with the Python mirror)."""
     from common import gpu_render
     from realtimepathtracingresearchframework_amd import backend
-    exe = _build_cli(tmp_path)
+    exe = build_host_tool("rptr_cli")
     s = scenes.cornell32()
     path = str(tmp_path / "cornell.rpsc")
     s.dump(path)
@@ -344,7 +265,7 @@ def test_profiling_mode_csv_images_and_camera_flags(tmp_path):
 @pytest.mark.gpu
 def test_profiling_mode_animated_wave_refits_every_frame(tmp_path):
     """SURVEY 8d C5 in the C++ host: --animate-wave moves the dynamic mesh before every frame, refit, accumulation restarts."""
-    exe = _build_cli(tmp_path)
+    exe = build_host_tool("rptr_cli")
     s = scenes.grid(64, 32, deform_t=0.0)
     path = str(tmp_path / "grid.rpsc")
     s.dump(path)
@@ -370,7 +291,7 @@ def test_exr_png_and_data_capture_outputs(tmp_path):
     stores the accumulation buffer and the three AOV images as EXR (libapp/app_state.cpp:499-531) = what the Python mirror reads back"""
     from common import gpu_render
     from realtimepathtracingresearchframework_amd import backend
-    exe = _build_cli(tmp_path)
+    exe = build_host_tool("rptr_cli")
     s = scenes.textured_test()
     path = str(tmp_path / "t.rpsc")
     s.dump(path)
@@ -476,7 +397,7 @@ exposure= -5.000000e-01
 def test_cli_reads_the_reference_ini_configuration_files(tmp_path):
     """--config / --keyframe: the ImGui-settings text the reference serialises its state to (imstate.cpp:226-330): objects, nested
     headers, combo boxes, %e floats. --describe prints what the files make of the scene's defaults (no GPU needed)."""
-    exe = _build_cli(tmp_path)
+    exe = build_host_tool("rptr_cli")
     s = scenes.cornell32()
     path = str(tmp_path / "c.rpsc")
     s.dump(path)
@@ -510,7 +431,7 @@ def test_cli_keyframes_and_two_ranks_on_one_device(tmp_path):
     """profiling mode over two keyframes (0.5 s + 1 s at 4 fps = 6 frames, the accumulation restarts with the second keyframe, one
     image per keyframe), --freeze-frame repeats the frame, and --devices 0,0 (two ranks of the frame on one GPU, tiles gathered by the
     library) writes the image of a single device, bit for bit"""
-    exe = _build_cli(tmp_path)
+    exe = build_host_tool("rptr_cli")
     s = scenes.cornell32()
     path = str(tmp_path / "c.rpsc")
     s.dump(path)
@@ -547,7 +468,7 @@ def test_cli_point_sets_match_the_python_host(tmp_path, name, rng_variant):
     """--rng-variant: the C++ host derives the same SobolData from the package's matrices as pointsets.py (tile inversion included)
     -> the validation image of the CLI equals the Python host's, bit for bit; the blue-noise stand-in table renders too"""
     from realtimepathtracingresearchframework_amd import backend
-    exe = _build_cli(tmp_path)
+    exe = build_host_tool("rptr_cli")
     s = scenes.cornell32()
     path = str(tmp_path / "c.rpsc")
     s.dump(path)
@@ -589,7 +510,7 @@ def test_cpp_vks_reader_equals_the_python_reader(tmp_path, name):
     libvkr itself reads the same way, tests/test_vks.py): geometry streams, per-triangle material ids, instance transforms (version 3:
     quantised on reading), materials with texture handles, decoded BC textures, the binned emitters, default camera and sky --
     the flat scene `rptr_hip --dump-scene` writes is the one the Python path dumps, byte for byte"""
-    exe = _build_cli(tmp_path)
+    exe = build_host_tool("rptr_cli")
     src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "vks", name)
     if not os.path.exists(src):
         pytest.skip("fixture %s not present" % name)
@@ -608,7 +529,7 @@ def test_cpp_vks_reader_equals_the_python_reader(tmp_path, name):
 def test_cpp_lights_on_a_many_emitter_scene(tmp_path):
     """the bin equalisation (clones, Halton shuffles, importance padding) on 512 emitters of very different power: C++ == Python"""
     from realtimepathtracingresearchframework_amd import vks
-    exe = _build_cli(tmp_path)
+    exe = build_host_tool("rptr_cli")
     s = scenes.grid(nx=60, nz=40, with_emitters=True)
     rng = np.random.default_rng(5)
     for m in s.materials:
@@ -630,7 +551,7 @@ def test_cli_renders_a_vks_file_like_the_python_host(tmp_path):
     """.vks -> C++ reader -> C++ emitter preparation -> backend, no Python in between: the validation image equals the one the Python
     host renders from the same file, bit for bit"""
     from realtimepathtracingresearchframework_amd import backend, vks
-    exe = _build_cli(tmp_path)
+    exe = build_host_tool("rptr_cli")
     src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "vks", "alpha_v4.vks")
     W, H = 96, 64
     r = subprocess.run([exe, src, "--img", str(W), str(H), "--pfm", "--validation", str(tmp_path / "v"), "--validation-spp", "3"], capture_output=True, text=True)
@@ -652,7 +573,7 @@ def test_cpp_vks_reader_wide_ids_indices_and_lods(tmp_path):
     """the C++ reader on a file with 16-bit material ids, index buffers and a LoD group: same flat scene as the Python reader, for the base
     level and for --remove-first-lods 1"""
     from realtimepathtracingresearchframework_amd import vks
-    exe = _build_cli(tmp_path)
+    exe = build_host_tool("rptr_cli")
     s = scenes.alpha_test()
     pm = next(i for i, p in enumerate(s.pmeshes) if p.tri_material_ids is not None)
     n = len(s.pmeshes[pm].tri_material_ids)
@@ -674,7 +595,7 @@ def test_vks_loader_params_dynamic_keywords_and_instance_pruning(tmp_path):
     dynamic (subtly dynamic with small_deformation, not at all with ignore_animation), instance_pruning_probability drops the instances
     whose halton2(index) lies below it (scene.cpp:658-706,734-749); same flat scene from Python and C++"""
     from realtimepathtracingresearchframework_amd import vks, abi
-    exe = _build_cli(tmp_path)
+    exe = build_host_tool("rptr_cli")
     s = scenes.two_level_test()
     path = str(tmp_path / "f.vks")
     names = vks.write_vks(path, s)
@@ -706,7 +627,7 @@ def test_cli_argument_table_follows_the_reference(tmp_path):
     """cmdline.cpp:226-259,296-494: old single-dash arguments and --benchmark-file are refused with a pointer to their successors,
     profiling automation options need --profiling, -h / --help print the usage, --profiling-frames / --frame are the old spellings of
     --profiling-fps / --keyframe (parsed; --describe shows the keyframe)"""
-    exe = _build_cli(tmp_path)
+    exe = build_host_tool("rptr_cli")
     s = scenes.cornell32()
     path = str(tmp_path / "c.rpsc")
     s.dump(path)
@@ -735,7 +656,7 @@ def test_cli_argument_table_follows_the_reference(tmp_path):
 def test_cli_data_capture_toggles_and_keyframes(tmp_path):
     """--data-capture over two keyframes with --data-capture-no-aovs --data-capture-normal-depth: rgba + normal_depth per keyframe, nothing
     else (cmdline.cpp:432-452, app_state.cpp:499-531); a profiling run without keyframes ends after its first frame (imstate.cpp:890-898)"""
-    exe = _build_cli(tmp_path)
+    exe = build_host_tool("rptr_cli")
     s = scenes.cornell32()
     path = str(tmp_path / "c.rpsc")
     s.dump(path)
@@ -755,12 +676,6 @@ def test_cli_data_capture_toggles_and_keyframes(tmp_path):
 
 
 # ---------------------------------------------------------------- rptr_compare (util/compare_exr.cpp)
-def _build_compare(tmp_path):
-    exe = str(tmp_path / "rptr_compare")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", os.path.join(HOST, "rptr_compare.cpp"), "-o", exe, "-lz"])
-    return exe
-
-
 def write_exr_py(path, planes, half=False, compression=0):
     """a scan-line OpenEXR file written independently of host/write_image.hpp: `planes` = {channel name: (h, w) array}, channels stored in
     alphabetical order as FLOAT or HALF, compression NONE (0), RLE (1), ZIPS (2) or ZIP (3) with OpenEXR's byte shuffle + delta predictor"""
@@ -822,7 +737,7 @@ def test_compare_tool_follows_compare_exr(tmp_path):
     """util/compare_exr.cpp:51-97: per value |ref - cmp| / ref (|cmp| where ref is 0), above 1e-6 anywhere = not the same, exit code -1,
     the error of every value in <CMP>_err.exr; EXR files with NONE / RLE / ZIPS / ZIP compression, FLOAT and HALF channels; PFM; compressions without
     a decoder here (PXR24 ...) refused by name"""
-    exe = _build_compare(tmp_path)
+    exe = build_host_tool("rptr_compare", link_library=False, extra=("-lz",))
     rng = np.random.default_rng(3)
     H, W = 37, 29
     base = {n: rng.random((H, W)).astype(np.float32) + 0.25 for n in "RGBA"}
@@ -878,7 +793,7 @@ def test_compare_tool_reads_piz_compressed_validation_images(tmp_path):
     channels with two blocks (32 + 5 lines, odd width: the 16-bit wavelet), HALF channels in three blocks (the 14-bit wavelet), a constant
     image (runs); any further <name>.exr + <name>.f32 pair dropped there (e.g. written by a build of the reference) is checked too."""
     import glob
-    exe = _build_compare(tmp_path)
+    exe = build_host_tool("rptr_compare", link_library=False, extra=("-lz",))
     gold = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "piz")
     names = sorted(glob.glob(os.path.join(gold, "*.exr")))
     assert len(names) >= 3
@@ -916,7 +831,7 @@ def test_compare_tool_refuses_corrupt_piz_streams_without_crashing(tmp_path):
     block whose Huffman table / bitmap / code stream has flipped bytes, a block length that points beyond the file: the tool must end with
     its error exit code (255: unreadable or different), never with a signal, never hang"""
     import glob
-    exe = _build_compare(tmp_path)
+    exe = build_host_tool("rptr_compare", link_library=False, extra=("-lz",))
     gold = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "piz")
     rng = np.random.default_rng(7)
     n_runs = 0
@@ -944,7 +859,7 @@ def test_compare_tool_refuses_corrupt_piz_streams_without_crashing(tmp_path):
 def test_validation_images_through_the_compare_tool(tmp_path):
     """the reference's regression workflow end to end: two --validation runs of the same configuration compare equal (exit 0), a run with
     another sample count does not"""
-    exe, cmp = _build_cli(tmp_path), _build_compare(tmp_path)
+    exe, cmp = build_host_tool("rptr_cli"), build_host_tool("rptr_compare", link_library=False, extra=("-lz",))
     s = scenes.cornell32()
     path = str(tmp_path / "c.rpsc")
     s.dump(path)
@@ -960,7 +875,7 @@ def test_cpp_vks_reader_keeps_mip_levels(tmp_path):
     """a .vks scene whose textures carry mip levels: the C++ reader's flat scene (levels back to back, RptrTextureDesc.mip_levels) equals the
     Python reader's byte for byte, and the dump reads back with the levels in place"""
     from realtimepathtracingresearchframework_amd import vks
-    exe = _build_cli(tmp_path)
+    exe = build_host_tool("rptr_cli")
     s = scenes.textured_test()
     for t in s.textures:
         lv, cur = [], np.asarray(t.rgba)
@@ -1038,7 +953,7 @@ def test_cli_refits_the_sky_for_the_sun_settings_of_an_ini(tmp_path):
     the scene file's sky is kept and a note says why."""
     from common import gpu_render
     from realtimepathtracingresearchframework_amd import backend, sky_fit
-    exe = _build_cli(tmp_path)
+    exe = build_host_tool("rptr_cli")
     s = scenes.grid(40, 20, with_emitters=True)
     path = str(tmp_path / "g.rpsc")
     s.dump(path)
@@ -1084,17 +999,17 @@ def test_cli_refits_the_sky_for_the_sun_settings_of_an_ini(tmp_path):
 def test_synthetic_sky_tables_parse_like_the_real_layout(tmp_path):
     """(CPU) the stand-in headers go through the same parsers (C++ and Python) and give the same fit in both"""
     import ctypes as C
-    from test_sky_fit import as_words, build_shim
+    from host_tools import build_sky_shim, sky_words
     from realtimepathtracingresearchframework_amd import sky_fit
     write_synthetic_sky_data(tmp_path)
     t = sky_fit.SkyTables(str(tmp_path))
     assert t.has_sun and [len(v) for v in t.rgb] == [1080] * 3 and [len(v) for v in t.solar] == [1800] * 11 and len(t.cie) == 285
-    L = build_shim(tmp_path)
+    L = build_sky_shim(tmp_path)
     err = C.create_string_buffer(512)
     for d, turb, al, lights in (((0.3, 0.8, 0.5), 3.0, (0.2, 0.2, 0.2), 0), ((0.8, 0.25, 0.3), 6.5, (0.4, 0.3, 0.1), 4), ((0.0, -1.0, 0.0), 10.0, (1.0, 0.0, 0.5), 0)):
         got = abi.SceneParams()
         assert L.shim_fit(str(tmp_path).encode(), (C.c_float * 3)(*d), C.c_float(turb), (C.c_float * 3)(*al), lights, C.byref(got), err, 512) == 0, err.value
-        assert np.array_equal(as_words(got), as_words(sky_fit.fit_sky(t, d, turb, al, lights)))
+        assert np.array_equal(sky_words(got), sky_words(sky_fit.fit_sky(t, d, turb, al, lights)))
 
 
 # ---------------------------------------------------------------- several scene files per run, --deduplicate-scene (SURVEY 8f rank 1 / 2 remainder)
@@ -1109,7 +1024,7 @@ def test_cli_appends_further_scene_files_and_deduplicates(tmp_path):
     """`<scene_file> [<scene_file>...]` (librender/scene.cpp:50-69): the files' meshes / parameterized meshes / instances / materials /
     textures are appended with shifted indices, the emitters binned over the whole scene; --deduplicate-scene (Scene::deduplicate +
     garbage_collect, :142-148) merges equal meshes, materials and textures and drops what nothing refers to any more. No GPU needed."""
-    exe = _build_cli(tmp_path)
+    exe = build_host_tool("rptr_cli")
     a, b = scenes.textured_test(), scenes.grid(20, 10, with_emitters=True)
     pa, pb = str(tmp_path / "a.rpsc"), str(tmp_path / "b.rpsc")
     a.dump(pa)
@@ -1142,7 +1057,7 @@ def test_cli_renders_several_scene_files_like_the_merged_scene(tmp_path):
     """the image of `a.rpsc b.rpsc` = the image of the Python host's merged scene (Scene.append), bit for bit, and the same with
     --deduplicate-scene on a scene that holds the same meshes twice (textures and their handles survive the re-indexing)"""
     from common import gpu_render
-    exe = _build_cli(tmp_path)
+    exe = build_host_tool("rptr_cli")
     a, b = scenes.textured_test(), scenes.grid(20, 10, with_emitters=True)
     pa, pb = str(tmp_path / "a.rpsc"), str(tmp_path / "b.rpsc")
     a.dump(pa)
@@ -1181,7 +1096,7 @@ def test_cli_profiling_reproduces_the_benchmarks_schedule(tmp_path):
     import json
     import re
     import sys
-    exe = _build_cli(tmp_path)
+    exe = build_host_tool("rptr_cli")
     s = scenes.grid_1m()
     path = str(tmp_path / "grid1m.rpsc")
     s.dump(path)
@@ -1241,7 +1156,7 @@ def _partitioned_scene():
 def test_cli_merges_partition_instances(tmp_path):
     """--merge-partition-instances (SceneLoaderParams::PerFile::merge_partition_instances, librender/scene.cpp:757-797): consecutive instances
     with one transform become one instance whose mesh lists all their geometries; same triangles, fewer instances. No GPU needed."""
-    exe = _build_cli(tmp_path)
+    exe = build_host_tool("rptr_cli")
     s = _partitioned_scene()
     path = str(tmp_path / "p.rpsc")
     s.dump(path)
@@ -1259,7 +1174,7 @@ def test_cli_merges_partition_instances(tmp_path):
 @pytest.mark.gpu
 def test_merged_partition_instances_render_the_same_image(tmp_path):
     from common import gpu_render
-    exe = _build_cli(tmp_path)
+    exe = build_host_tool("rptr_cli")
     s = _partitioned_scene()
     path = str(tmp_path / "p.rpsc")
     s.dump(path)

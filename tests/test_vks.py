@@ -14,60 +14,20 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from common import float_bits
 from realtimepathtracingresearchframework_amd import abi, scenes, vks
+from vks_checks import REF_LIB, compare_with_dump, ref_reader, same_streams
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
-REF_LIB = os.path.join(ROOT, "oracle", "_ref", "libvkr_ref.so")
 REF_DUMPS = os.path.join(GOLD, "vks", "ref_reader_dumps.json")
-
-
-def _bits(x):
-    return np.ascontiguousarray(np.asarray(x, np.float32)).view(np.uint32)
-
-
-def _compare_with_dump(path, ref):
-    v = vks.read_vks_header(path)
-    for key in ("version", "flags", "headerSize", "dataOffset", "numMaterials", "numTriangles", "numMeshes", "numInstances", "numLodGroups",
-                "numFrames", "numStaticTransforms", "numAnimatedTransforms"):
-        assert v[key] == ref[key], key
-    if v["version"] >= 4:
-        assert v["animationOffset"] == ref["animationOffset"]
-    assert len(v["meshes"]) == len(ref["meshes"])
-    for m, r in zip(v["meshes"], ref["meshes"]):
-        assert _bits(m["vertexScale"]).tolist() == r["vertexScale"] and _bits(m["vertexOffset"]).tolist() == r["vertexOffset"]
-        for key in ("name", "flags", "numSegments", "materialIdBufferBase", "numMaterialsInRange", "numTriangles", "lodGroup", "vertexBufferOffset",
-                    "normalUvBufferOffset", "materialIdBufferOffset", "materialIdSize", "indexBufferOffset", "segmentNumTriangles",
-                    "segmentMaterialBaseOffsets"):
-            assert m[key] == r[key], key
-    assert [(i["name"], i["meshId"], i["transformIndex"], i["flags"]) for i in v["instances"]] == [
-        (i["name"], i["meshId"], i["transformIndex"], i["flags"]) for i in ref["instances"]]
-    assert [(g["numLevelsOfDetail"], g["meshIds"]) for g in v["lodGroups"]] == [(g["numLevelsOfDetail"], g["meshIds"]) for g in ref["lodGroups"]]
-    assert v["materialNames"] == [m["name"] for m in ref["materials"]]
-    tdir = vks.texture_dir(path)
-    for name, r in zip(v["materialNames"], ref["materials"]):
-        m = vks._load_material_files(tdir, name)
-        for key in ("emissionIntensity", "specularTransmission", "iorEta", "iorK", "translucency"):
-            assert int(_bits(m[key]).reshape(-1)[0]) == r[key], (name, key)
-        assert _bits(m["emitterBaseColor"]).tolist() == r["emitterBaseColor"]
-        for mine, theirs in (("texBaseColor", "texBaseColor"), ("texNormal", "texNormal"), ("texSpecular", "texSpecular")):
-            assert (m[mine] is None) == (r[theirs] is None), (name, mine)
-            if m[mine] is not None:
-                assert m[mine][0].shape[:2] == (r[theirs]["height"], r[theirs]["width"]) and m[mine][1] == r[theirs]["format"]
-                assert 1 + len(m[mine][2]) == r[theirs]["numMipLevels"] and r[theirs]["dataOffset"] == 32 + 24 * r[theirs]["numMipLevels"], (name, mine)
-    # the transform table as the reference dequantises it
-    assert len(ref["transforms"]) == v["numStaticTransforms"]
-    for k, r in enumerate(ref["transforms"]):
-        mine = vks.dequantize_transform(v["transforms"][24 * k:24 * k + 24])
-        assert _bits(mine).reshape(-1).tolist() == r, "transform %d" % k
-    return v
 
 
 @pytest.mark.parametrize("version", [3, 4])
 def test_reader_reproduces_the_reference_readers_dump(version):
     path = os.path.join(GOLD, "vks", "alpha_v%d.vks" % version)
     ref = json.load(open(path[:-4] + ".ref.json"))
-    v = _compare_with_dump(path, ref)
+    v = compare_with_dump(path, ref)
     assert v["version"] == version and v["numMeshes"] == 6 and v["numInstances"] == 7
 
 
@@ -84,8 +44,8 @@ def test_quantization_matches_the_reference_vectors():
     mine = np.zeros((len(q), 3), np.float32)
     O.lib().orc_dequantize_positions(q.ctypes.data_as(C.c_void_p), len(q), scale.ctypes.data_as(C.c_void_p), offset.ctypes.data_as(C.c_void_p),
                                      mine.ctypes.data_as(C.c_void_p))
-    assert np.array_equal(_bits(-mine[:, 0]), _bits(ref[:, 0]))
-    assert np.array_equal(_bits(mine[:, 2]), _bits(ref[:, 1])) and np.array_equal(_bits(mine[:, 1]), _bits(ref[:, 2]))
+    assert np.array_equal(float_bits(-mine[:, 0]), float_bits(ref[:, 0]))
+    assert np.array_equal(float_bits(mine[:, 2]), float_bits(ref[:, 1])) and np.array_equal(float_bits(mine[:, 1]), float_bits(ref[:, 2]))
     assert np.array_equal(scenes.dequantize_positions(q, scale, offset), mine)
     nq = np.array(g["normal_uv_q"], np.uint64)
     rn = np.array(g["normal_out"], np.uint32).view(np.float32).reshape(-1, 3)
@@ -97,11 +57,11 @@ def test_quantization_matches_the_reference_vectors():
     ln = np.linalg.norm(flipped, axis=1, keepdims=True)
     ok = ln[:, 0] > 0
     assert ok.sum() > 200 and np.allclose(nrm[ok], (flipped / np.where(ln > 0, ln, 1))[ok], atol=2e-7)
-    assert np.array_equal(_bits(uv[:, 0]), _bits(ruv[:, 0]))
+    assert np.array_equal(float_bits(uv[:, 0]), float_bits(ruv[:, 0]))
     for m_in, packed, out in zip(g["transform_in"], g["transform_packed"], g["transform_out"]):
         m = np.array(m_in, np.uint32).view(np.float32).reshape(4, 3)
         assert list(vks.quantize_transform(m)) == packed
-        assert _bits(vks.dequantize_transform(bytes(packed))).reshape(-1).tolist() == out
+        assert float_bits(vks.dequantize_transform(bytes(packed))).reshape(-1).tolist() == out
     # identity, pure translations, half turns, mirrors, extreme scales, a zero matrix: the packed bytes and the round trip of the
     # reference's vkr_quantize_transform / vkr_dequantize_transform
     assert len(g["special_transform_in"]) >= 16
@@ -109,7 +69,7 @@ def test_quantization_matches_the_reference_vectors():
         m = np.array(m_in, np.uint32).view(np.float32).reshape(4, 3)
         with np.errstate(all="ignore"):
             got = list(vks.quantize_transform(m))
-            back = _bits(vks.dequantize_transform(bytes(packed))).reshape(-1).tolist()
+            back = float_bits(vks.dequantize_transform(bytes(packed))).reshape(-1).tolist()
         assert got == packed, (m.tolist(), got, packed)
         want = np.array(out, np.uint32).view(np.float32)
         have = np.array(back, np.uint32).view(np.float32)
@@ -155,22 +115,6 @@ def test_block_encoders_round_trip():
     assert np.abs(d3[..., 3]).max() <= 8 and np.abs(d3[..., :3]).max() <= 40
 
 
-def _same_streams(a, b):
-    assert len(a.pmeshes) == len(b.pmeshes)
-    for pa, pb in zip(a.pmeshes, b.pmeshes):
-        ma, mb = a.meshes[pa.mesh], b.meshes[pb.mesh]
-        assert ma.num_geometries == mb.num_geometries
-        assert np.array_equal(pa.material_offsets, pb.material_offsets)
-        assert (pa.tri_material_ids is None) == (pb.tri_material_ids is None)
-        if pa.tri_material_ids is not None:
-            assert np.array_equal(pa.tri_material_ids, pb.tri_material_ids)
-        for j in range(ma.num_geometries):
-            ga, gb = a.geometries[ma.first_geometry + j], b.geometries[mb.first_geometry + j]
-            assert np.array_equal(ga.qpos, gb.qpos) and np.array_equal(_bits(ga.scaling), _bits(gb.scaling)) and np.array_equal(_bits(ga.offset), _bits(gb.offset))
-            if ga.qnrm_uv is not None and ga.has_normals and ga.has_uvs:
-                assert np.array_equal(ga.qnrm_uv, gb.qnrm_uv)
-
-
 @pytest.mark.parametrize("name", ["alpha_test", "textured_test", "cornell32", "two_level_test"])
 @pytest.mark.parametrize("version", [3, 4])
 def test_write_then_read_keeps_the_scene(tmp_path, name, version):
@@ -178,7 +122,7 @@ def test_write_then_read_keeps_the_scene(tmp_path, name, version):
     path = str(tmp_path / (name + ".vks"))
     vks.write_vks(path, s, version=version)
     r = vks.read_vks(path)
-    _same_streams(s, r)
+    same_streams(s, r)
     assert len(r.instances) == len(s.instances)
     for ia, ib in zip(s.instances, r.instances):
         assert ia.pmesh == ib.pmesh
@@ -226,8 +170,8 @@ def test_lod_groups_instance_the_base_level_only(tmp_path):
     kept = [i for i in s.instances if i.pmesh != 1]
     assert len(r.instances) == len(kept) and all(a.pmesh == b.pmesh for a, b in zip(r.instances, kept))
     ref = _reference_dump(path, "lod_groups", tmp_path)
-    _compare_with_dump(path, ref)
-    assert [g["detailReduction"] for g in ref["lodGroups"]][1] == _bits([0.0, 0.5]).tolist()
+    compare_with_dump(path, ref)
+    assert [g["detailReduction"] for g in ref["lodGroups"]][1] == float_bits([0.0, 0.5]).tolist()
     with pytest.raises(vks.VksError):
         vks.write_vks(str(tmp_path / "lod3.vks"), s, version=3, lod_groups=[[(0, 0.0), (1, 0.5)]])
 
@@ -273,7 +217,7 @@ def test_sixteen_bit_material_ids_and_index_buffers(tmp_path):
     vks.write_vks(plain, s)
     q = vks.read_vks(plain)
     assert all(np.array_equal(a.qpos, b.qpos) for a, b in zip(r.geometries, q.geometries)) and len(r.instances) == len(q.instances)
-    _compare_with_dump(path, _reference_dump(path, "wide_ids", tmp_path))
+    compare_with_dump(path, _reference_dump(path, "wide_ids", tmp_path))
 
 
 def test_unrepresentable_scenes_are_refused(tmp_path):
@@ -306,12 +250,6 @@ def test_reader_errors(tmp_path):
 
 
 # ---------------------------------------------------------------- against the reference's reader (live where oracle/_ref was built)
-def _ref():
-    lib = C.CDLL(REF_LIB)
-    lib.ref_vkr_dump.argtypes = [C.c_char_p, C.c_char_p]
-    return lib
-
-
 def tree_digest(path):
     """sha256 over a written .vks file and its texture directory: a stored dump belongs to exactly these bytes"""
     h = hashlib.sha256(open(path, "rb").read())
@@ -324,7 +262,7 @@ def tree_digest(path):
 
 def live_dump(path, out):
     """the reference reader's dump of `path` (None when it refuses the file); textureDir as its base name, as the stored dumps hold it"""
-    if _ref().ref_vkr_dump(path.encode(), out.encode()) != 0:
+    if ref_reader().ref_vkr_dump(path.encode(), out.encode()) != 0:
         return None
     d = json.load(open(out))
     d["textureDir"] = os.path.basename(d["textureDir"].rstrip("/"))
@@ -347,7 +285,7 @@ def test_written_files_are_read_identically_by_the_reference(tmp_path, name, ver
     s = getattr(scenes, name)()
     path = str(tmp_path / (name + ".vks"))
     vks.write_vks(path, s, version=version)
-    _compare_with_dump(path, _reference_dump(path, "%s_v%d" % (name, version), tmp_path))
+    compare_with_dump(path, _reference_dump(path, "%s_v%d" % (name, version), tmp_path))
 
 
 def reject_cases():
@@ -364,7 +302,7 @@ def test_reference_and_reader_reject_the_same_files(tmp_path):
         p = str(tmp_path / "t.vks")
         open(p, "wb").write(data)
         if os.path.isfile(REF_LIB):
-            assert (_ref().ref_vkr_dump(p.encode(), str(tmp_path / "d.json").encode()) == 0) == accepted[tag], tag
+            assert (ref_reader().ref_vkr_dump(p.encode(), str(tmp_path / "d.json").encode()) == 0) == accepted[tag], tag
         try:
             vks.read_vks_header(p)
             mine_ok = True
@@ -429,7 +367,7 @@ def test_mip_mapped_vkt_files_are_read_by_the_reference(tmp_path):
     path = str(tmp_path / "m.vks")
     vks.write_vks(path, mip_mapped_scene())
     ref = _reference_dump(path, "mip_mapped", tmp_path)
-    _compare_with_dump(path, ref)
+    compare_with_dump(path, ref)
     levels = [m["texBaseColor"]["numMipLevels"] for m in ref["materials"] if m["texBaseColor"]]
     assert max(levels) >= 4
     tdir = vks.texture_dir(path)
