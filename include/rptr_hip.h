@@ -436,8 +436,10 @@ int rptr_hip_bvh_rebuild_count(const rptr_hip_t *h, uint64_t *out_rebuilds);
  * Frames in flight: a scene with a RPTR_MESH_INSTANCES_MOVE (or dynamic) mesh gives every frame context its own tree and instance
  * records, so a refit never waits -- per context a copy of the node array (88 bytes per node, top level and bottom-level trees are one
  * array) and of the instance records; triangles and shading records are shared unless a mesh deforms --; in any other scene rptr_hip_refit waits for the frames in flight first, as it always did.
- * Limits: the motion AOV stays motion_vector = 0 for moved objects (rigid-motion vectors need the previous transform next to the 128-byte
- * record): under reprojection_mode = 2 a moved object ghosts until its history is rejected. rptr_hip_traversal_preset keeps what set_scene
+ * Limits: a frame writes its motion AOV with motion_vector = 0 for moved objects, as the reference does; rptr_hip_track_object_motion +
+ * rptr_hip_object_motion ("object motion" below) rewrite it after the frame for the consumers that run after it (rptr_hip_denoise_temporal,
+ * rptr_hip_taa_upscale). reprojection_mode = 2 and option "taa" resolve inside the frame, before that pass can run: there a moved object
+ * still ghosts until its history is rejected. rptr_hip_traversal_preset keeps what set_scene
  * chose. The top level's refit after a rebuild runs in one block up to 8192 records; that break-even was estimated, not measured. */
 #define RPTR_TLAS_REBUILD 0
 #define RPTR_TLAS_REFIT 1
@@ -731,6 +733,38 @@ typedef struct RptrTaaUpscaleParams { /* 16 bytes */
 void rptr_hip_taa_upscale_defaults(RptrTaaUpscaleParams *out);
 int rptr_hip_taa_upscale(rptr_hip_t *h, const RptrTaaUpscaleParams *p /* NULL = defaults */);
 int rptr_hip_readback_upscaled_u8(rptr_hip_t *h, unsigned char *rgba, size_t n_bytes);
+
+/* ---- object motion: a pass over a finished frame that rewrites the motion half of its motion + jitter AOV image where objects moved.
+ * A frame projects the SAME world point through the previous and the current view (motion_vector = 0, as the reference): the AOV follows
+ * the camera, not rptr_hip_update_instances / rptr_hip_update_vertices. rptr_hip_object_motion(h), called after the frame and before
+ * its consumers (update_* -> refit -> render -> object_motion -> denoise_temporal / taa_upscale), replaces the .xy half of a texel with
+ *   project(view_ref, x_prev) / max(w, 0) - project(view, x_cur) / max(w, 0)        (the frame's own formula when x_prev == x_cur)
+ * where x_cur is the hit of the pixel's REPRESENTATIVE RAY and x_prev is where that surface point was in the previous frame: for a rigid
+ * instance object_to_world_prev * (world_to_object_cur * x_cur); for a geometry whose positions were updated, the hit's barycentrics on
+ * the triangle's previous positions, through the previous object_to_world. The representative ray is the frame's primary ray with the
+ * pixel-filter draw replaced by its mean: through ((x + .5) / W, (y + .5) / H), plus half the frame's screen jitter under
+ * enable_raster_taa, from the position of the frame's last camera, pinhole even with aperture_radius > 0. Under enable_raster_taa it is
+ * exactly the ray whose hit the frame wrote into the AOV images; otherwise a ray through the same pixel. It is traced as ray queries are:
+ * opaque geometry (alpha-tested cut-outs count as surfaces), interval (0, inf).
+ * Only pixels whose hit lies on an instance whose object_to_world differs bitwise from the previous frame's, or on a geometry whose
+ * positions were updated, are written: one 4-byte store of the .xy word. The jitter half, misses and hits on unmoved surfaces keep their
+ * bits; the pass computes from the hit, so a second call stores the same bytes. It touches no other image, no frame_id / frame_offset,
+ * no statistics; a host that never calls it launches what it always launched.
+ * rptr_hip_track_object_motion(h, enable): after set_scene (a new set_scene drops it). Keeps the previous frame's state: 96 bytes per
+ * instance and 36 bytes per triangle of the dynamic meshes, copied on the backend's stream by the first update_* call after a frame's
+ * submission (transforms) and the first update_vertices* of a geometry in that interval (positions). "The state a frame sees" is what the
+ * last rptr_hip_refit before its submission applied; the pass compares the last submitted frame N with frame N-1 (both submitted while
+ * the tracking was on). Nothing staged between them, no frame N-1, or a launch sequence of several frames as the last submission
+ * (objects cannot move inside one): the call succeeds, launches nothing and writes nothing.
+ * The pass waits for the frames in flight, then runs on the backend's stream, asynchronously. rptr_hip_get_option(h,
+ * "object_motion_pixels") (read-only; waits for the stream): the pixels the last call rewrote.
+ * RPTR_E_INVALID: NULL handle; before set_scene; tracking not switched on; before initialize or before a frame has finished, and whatever
+ * else the denoiser refuses about the finished frame; no frame submitted since the tracking was switched on; updates staged and not yet
+ * refitted, or staged after frame N's submission (the tables no longer hold what frame N saw: call the pass before the next update_*);
+ * frame N or N-1 was submitted while staged updates awaited a refit. RPTR_E_UNSUPPORTED: option "aovs" = 0; world_size > 1.
+ * Limits: reprojection_mode = 2 and option "taa" resolve inside the frame and never see the rewritten image; lights' bins do not move. */
+int rptr_hip_track_object_motion(rptr_hip_t *h, int enable);
+int rptr_hip_object_motion(rptr_hip_t *h);
 
 /* ---- multi-GPU: this rank's rows, packed top-to-bottom, for the RCCL gather.
  * rptr_hip_tile_rows writes up to `cap` (first_row,num_rows) pairs for `rank`

@@ -307,6 +307,7 @@ EXPORTED_SYMBOLS = [
     "rptr_hip_denoise_defaults", "rptr_hip_denoise", "rptr_hip_readback_denoised_f32", "rptr_hip_readback_denoised_u8",
     "rptr_hip_denoise_temporal_defaults", "rptr_hip_denoise_temporal", "rptr_hip_readback_denoise_history_f32",
     "rptr_hip_taa_upscale_defaults", "rptr_hip_taa_upscale", "rptr_hip_readback_upscaled_u8",
+    "rptr_hip_track_object_motion", "rptr_hip_object_motion",
     "rptr_hip_tile_rows", "rptr_hip_local_pixel_count", "rptr_hip_copy_tile_to_device", "rptr_hip_trace", "rptr_hip_trace_device", "rptr_hip_enable_ray_queries", "rptr_hip_render_ray_queries", "rptr_hip_trace_radiance", "rptr_hip_trace_radiance_device", "rptr_hip_render_radiance_queries", "rptr_hip_trace_surface", "rptr_hip_trace_surface_device", "rptr_hip_occlusion_defaults", "rptr_hip_trace_occlusion", "rptr_hip_trace_occlusion_device", "rptr_hip_set_light_sampling_variant", "rptr_hip_trace_counted",
     "rptr_hip_export_bvh", "rptr_hip_build_bvh_host", "rptr_hip_stats",
     "rptr_hip_comm_get_unique_id", "rptr_hip_comm_init_rank", "rptr_hip_comm_init_all", "rptr_hip_comm_destroy", "rptr_hip_comm_transport", "rptr_hip_comm_ipc_export", "rptr_hip_comm_ipc_init", "rptr_hip_gather", "rptr_hip_gather_all", "rptr_hip_gather_batch", "rptr_hip_gather_all_batch", "rptr_hip_readback_gathered_frame_f32",

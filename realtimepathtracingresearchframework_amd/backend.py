@@ -113,6 +113,8 @@ def load_library(path=None):
     L.rptr_hip_taa_upscale_defaults.restype = None
     L.rptr_hip_taa_upscale.argtypes = [vp, C.POINTER(abi.TaaUpscaleParams)]
     L.rptr_hip_readback_upscaled_u8.argtypes = [vp, vp, C.c_size_t]
+    L.rptr_hip_track_object_motion.argtypes = [vp, i32]
+    L.rptr_hip_object_motion.argtypes = [vp]
     L.rptr_hip_tile_rows.argtypes = [vp, i32, vp, i32]
     L.rptr_hip_local_pixel_count.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.rptr_hip_copy_tile_to_device.argtypes = [vp, vp, C.c_size_t]
@@ -482,6 +484,19 @@ class RenderHip:
         out = np.zeros((2 * hgt, 2 * w, c), np.uint8)
         self._check(self._L.rptr_hip_readback_upscaled_u8(self._h, out.ctypes.data_as(C.c_void_p), out.size))
         return out
+
+    # ---- object motion (include/rptr_hip.h rptr_hip_object_motion; csrc/object_motion.h)
+    def track_object_motion(self, enable=True):
+        """Keeps the state the previous frame saw (instance transforms, positions of dynamic meshes) so that object_motion() can tell
+        what moved. After set_scene; a new set_scene drops it."""
+        self._check(self._L.rptr_hip_track_object_motion(self._h, 1 if enable else 0))
+
+    def object_motion(self):
+        """Rewrites the .xy half of the last submitted frame's motion + jitter AOV texels where its objects moved since the frame before
+        (call order per frame: update_* -> refit -> render -> object_motion -> denoise_temporal / taa_upscale). Returns the number of
+        pixels rewritten (waits for the pass)."""
+        self._check(self._L.rptr_hip_object_motion(self._h))
+        return self.get_option("object_motion_pixels")
 
     # ---- ray queries (RQ_CLOSEST)
     def enable_ray_queries(self, max_queries=512 * 512, max_queries_per_pixel=0):

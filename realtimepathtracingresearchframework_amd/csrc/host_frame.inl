@@ -653,6 +653,14 @@ static int render_batch_impl(rptr_hip_t *h, const RptrCamera *camera, bool per_f
     }
     c.launches_extend = launched.extend;
     c.launches_connect = launched.connect;
+    if (h->om.enabled) { // object motion: the frame constants stay with the context, the interval of staged updates ends
+        c.last_frame = f;
+        c.last_submission = ++h->om.submissions;
+        h->om.dirty[1] = h->om.dirty[0];
+        h->om.dirty[0] = h->om.unrefitted;
+        h->om.staged_since_submission = false;
+        h->om.last_frames = n_frames;
+    }
     return close_submission(h, c, spp, n_frames, reset_rest, realtime, frame_id_before, out_tickets);
 }
 } // extern "C++"

@@ -369,3 +369,99 @@ int rptr_hip_trace_occlusion_device(rptr_hip_t *h, const RptrRenderRayQuery *dev
     if ((rc = begin_query_run(h))) return rc;
     return on_callers_stream(h, hip_stream, [&](hipStream_t st) { return occlusion_queries_on(h, device_queries, n, p, device_out_bits, st); });
 }
+
+// ---- object motion (object_motion.h): the tracking of the previous frame's state, and the pass over the last submitted frame's
+// motion + jitter AOV image. The pass is a query run over the master set -- after the checks below that set holds what the frame saw.
+int rptr_hip_track_object_motion(rptr_hip_t *h, int enable) {
+    const char *who = "rptr_hip_track_object_motion";
+    if (!h) return fail(nullptr, RPTR_E_INVALID, "NULL handle");
+    if (!h->have_scene) return fail(h, RPTR_E_INVALID, "%s before set_scene", who);
+    if (h->world > 1) return fail(h, RPTR_E_UNSUPPORTED, "%s needs world_size 1", who);
+    auto &om = h->om;
+    if (!enable) { // (the buffers stay until the next set_scene: switching it on again allocates nothing)
+        om.enabled = false;
+        return RPTR_OK;
+    }
+    if (om.enabled) return RPTR_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc;
+    if (!om.d_rewritten) {
+        std::vector<void *> *const A = &h->scene_allocs;
+        const size_t ng = h->master.dynpos.size();
+        if ((rc = dev_alloc(h, &om.prev_inst_xf, (size_t)24 * h->num_instances, A))) return rc;
+        om.prev_pos.assign(ng, nullptr);
+        for (size_t g = 0; g < ng; ++g)
+            if (h->master.dynpos[g] && (rc = dev_alloc(h, &om.prev_pos[g], (size_t)h->geom_tris[g] * 9, A))) return rc;
+        std::vector<const float *> table(om.prev_pos.begin(), om.prev_pos.end());
+        if ((rc = dev_upload(h, &om.d_prev_pos, table.size(), table.data(), hipMemcpyHostToDevice, A))) return rc;
+        if ((rc = dev_upload(h, &om.d_record_geom, h->record_geometry.size(), h->record_geometry.data(), hipMemcpyHostToDevice, A))) return rc;
+        if ((rc = dev_alloc(h, &om.d_geom_changed, ng, A))) return rc;
+        if ((rc = dev_alloc(h, &om.d_rewritten, 1, A))) return rc;
+        om.geom_marked.assign(ng, 0);
+    }
+    om.submissions = 0;
+    om.snapshot = om.counted = om.staged_since_submission = om.dirty[0] = om.dirty[1] = false;
+    om.last_frames = 1;
+    for (FrameCtx &c : h->ctx) c.last_submission = 0;
+    om.enabled = true;
+    return RPTR_OK;
+}
+
+int rptr_hip_object_motion(rptr_hip_t *h) {
+    const char *who = "rptr_hip_object_motion";
+    if (!h) return fail(nullptr, RPTR_E_INVALID, "NULL handle");
+    if (!h->have_scene) return fail(h, RPTR_E_INVALID, "%s before set_scene", who);
+    auto &om = h->om;
+    if (!om.enabled) return fail(h, RPTR_E_INVALID, "%s: the previous frame's state is not tracked (rptr_hip_track_object_motion after set_scene)", who);
+    if (h->world > 1) return fail(h, RPTR_E_UNSUPPORTED, "%s needs world_size 1", who);
+    if (h->width != 0 && !h->aovs) return fail(h, RPTR_E_UNSUPPORTED, "%s rewrites the motion + jitter AOV image: option \"aovs\" is 0", who);
+    if (om.unrefitted && om.staged_since_submission)
+        return fail(h, RPTR_E_INVALID, "%s: updates are staged and not refitted: the tables no longer hold what the last frame saw (call it before the next "
+                                       "update_instances / update_vertices)", who);
+    if (om.staged_since_submission)
+        return fail(h, RPTR_E_INVALID, "%s: updates were staged after the last frame's submission: the tables no longer hold what that frame saw (call it "
+                                       "before the next update_instances / update_vertices)", who);
+    if (om.dirty[0] || om.dirty[1])
+        return fail(h, RPTR_E_INVALID, "%s: the last frame or the one before it was submitted while staged updates awaited rptr_hip_refit: what it saw is "
+                                       "not what was staged", who);
+    // frames in flight are waited for, oldest first: the frame waited for last is the one submitted last
+    for (;;) {
+        FrameCtx *first = nullptr;
+        for (FrameCtx &c : h->ctx)
+            if (c.pending && (!first || c.ticket < first->ticket)) first = &c;
+        if (!first) break;
+        const int rc = finish_frame(h, *first, nullptr);
+        if (rc) return rc;
+    }
+    int rc;
+    if ((rc = check_finished_frame_with_aovs(h, who, "call it", "the motion + jitter AOV image", false))) return rc;
+    const FrameCtx &ac = h->ctx[(size_t)h->aov_ctx];
+    if (om.submissions == 0 || ac.last_submission != om.submissions)
+        return fail(h, RPTR_E_INVALID, "%s: no frame has been submitted since the tracking was switched on", who);
+    om.counted = false;
+    // nothing moved: a launch sequence of several frames (objects cannot move inside one), nothing staged between the previous frame and
+    // this one, or no previous frame since the tracking was switched on
+    if (om.last_frames > 1 || !om.snapshot || om.snapshot_of < 1 || om.snapshot_of + 1 != om.submissions) return RPTR_OK;
+    if ((rc = begin_query_run(h)) || (rc = surface_scratch(h, h->npix_padded))) return rc;
+    const RpFrame &f = ac.last_frame;
+    const RpScene &sc = h->master.dscene;
+    RpObjectMotionTables tb;
+    tb.inst_xf = h->master.inst_xf;
+    tb.prev_inst_xf = om.prev_inst_xf;
+    tb.record_geom = om.d_record_geom;
+    tb.geom_changed = om.d_geom_changed;
+    tb.prev_pos = om.d_prev_pos;
+    tb.num_instances = h->num_instances;
+    tb.any_geom_changed = std::find(om.geom_marked.begin(), om.geom_marked.end(), (char)1) != om.geom_marked.end() ? 1u : 0u;
+    RpRawHit *raw = static_cast<RpRawHit *>(h->sq_raw);
+    hipStream_t st = h->stream;
+    HIP_TRY(h, hipMemsetAsync(om.d_rewritten, 0, sizeof(uint32_t), st));
+    uint32_t *cursor = borrowed_cursor(h, st);
+    rp_pick(sc.single_instance != 0, [&](auto S) {
+        hipLaunchKernelGGL((rp_k_trace_pixels<decltype(S)::value>), dim3(h->persistent_blocks), dim3(RP_TRAVERSE_BLOCK), 0, st, sc, f, raw, cursor, h->ctx[0].gstack);
+    });
+    hipLaunchKernelGGL(rp_k_object_motion, dim3(((unsigned)h->npix_padded + 255u) / 256u), dim3(256), 0, st, sc, f, tb, (const RpRawHit *)raw, om.d_rewritten);
+    HIP_TRY(h, hipGetLastError());
+    om.counted = true;
+    return RPTR_OK;
+}

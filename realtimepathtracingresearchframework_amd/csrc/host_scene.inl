@@ -505,6 +505,8 @@ int rptr_hip_set_scene(rptr_hip_t *h, const RptrSceneDesc *s) {
     if ((rc = scene_upload_vertex_streams(h, s, d_qpos, d_qnu))) return rc;
     SceneTables T;
     if ((rc = scene_geometry_records(h, s, d_qpos, d_qnu, T))) return rc;
+    h->record_geometry = T.geom_index;
+    h->om = decltype(h->om)(); // (object-motion tracking belongs to a scene: its buffers went with scene_allocs above)
     RptrBaseMaterial *d_mats = nullptr;
     RptrTriLightData *d_lights = nullptr;
     if ((rc = dev_upload(h, &d_mats, s->num_materials, s->materials, hipMemcpyHostToDevice, &h->scene_allocs))) return rc;
@@ -586,6 +588,31 @@ int rptr_hip_set_scene(rptr_hip_t *h, const RptrSceneDesc *s) {
     return RPTR_OK;
 }
 
+// ---- object motion (object_motion.h, rptr_hip_track_object_motion): what an update does for the tracking BEFORE it stages anything, on
+// the backend's stream. The first update after a submission keeps the staged transform table -- what the last submitted frame saw, as
+// long as every update was refitted before that frame (rptr_hip_object_motion refuses otherwise) -- and clears the changed marks; the
+// first update of a geometry's positions in that interval keeps those. geometry < 0: an instance update.
+static int object_motion_before_update(rptr_hip *h, int geometry) {
+    auto &om = h->om;
+    if (!om.enabled) return RPTR_OK;
+    if (!om.staged_since_submission) {
+        if (h->num_instances)
+            HIP_TRY(h, hipMemcpyAsync(om.prev_inst_xf, h->master.inst_xf, (size_t)96 * h->num_instances, hipMemcpyDeviceToDevice, h->stream));
+        if (!om.geom_marked.empty()) HIP_TRY(h, hipMemsetAsync(om.d_geom_changed, 0, om.geom_marked.size() * sizeof(uint32_t), h->stream));
+        std::fill(om.geom_marked.begin(), om.geom_marked.end(), 0);
+        om.snapshot = true;
+        om.snapshot_of = om.submissions;
+        om.staged_since_submission = true;
+    }
+    if (geometry >= 0 && !om.geom_marked[(size_t)geometry]) {
+        HIP_TRY(h, hipMemcpyAsync(om.prev_pos[(size_t)geometry], h->master.dynpos[(size_t)geometry], (size_t)h->geom_tris[(size_t)geometry] * 9 * sizeof(float),
+                                  hipMemcpyDeviceToDevice, h->stream));
+        HIP_TRY(h, hipMemsetD32Async((hipDeviceptr_t)(om.d_geom_changed + geometry), 1, 1, h->stream));
+        om.geom_marked[(size_t)geometry] = 1;
+    }
+    return RPTR_OK;
+}
+
 static int update_vertices_common(rptr_hip_t *h, uint32_t geometry, const float *xyz, uint32_t num_vertices, bool device_src) {
     if (!h || !xyz) return fail(h, RPTR_E_INVALID, "NULL argument");
     if (!h->have_scene) return fail(h, RPTR_E_INVALID, "update_vertices before set_scene");
@@ -598,11 +625,16 @@ static int update_vertices_common(rptr_hip_t *h, uint32_t geometry, const float 
     if (num_vertices != 3u * h->geom_tris[geometry])
         return fail(h, RPTR_E_INVALID, "geometry %u has %u unrolled vertices, got %u", geometry, 3u * h->geom_tris[geometry], num_vertices);
     HIP_TRY(h, hipSetDevice(h->device));
+    {
+        const int rc0 = object_motion_before_update(h, (int)geometry);
+        if (rc0) return rc0;
+    }
     HIP_TRY(h, hipMemcpyAsync(h->master.dynpos[geometry], xyz, (size_t)num_vertices * 12, device_src ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
                               h->stream));
     if (!device_src) HIP_TRY(h, hipStreamSynchronize(h->stream)); // the host array is only borrowed for the call
     h->master.mesh_dirty[h->geom_mesh[geometry]] = 1;
     h->vertex_updates++;
+    h->om.unrefitted = true; // (kept whether the tracking is on or not: it may be switched on between an update and its refit)
     return RPTR_OK;
 }
 int rptr_hip_update_vertices(rptr_hip_t *h, uint32_t geometry, const float *xyz, uint32_t num_vertices) {
@@ -631,10 +663,9 @@ static int update_instances_common(rptr_hip_t *h, uint32_t first, uint32_t count
                                                "(register rptr_hip_set_light_sources first)", i);
     }
     HIP_TRY(h, hipSetDevice(h->device));
-    if (device_src)
-        hipLaunchKernelGGL(rp_k_stage_instance_transforms, dim3(grid_for(h, count)), dim3(256), 0, h->stream, xf12, first, count, h->master.inst_xf, h->d_inst_rejected);
-    else {
-        std::vector<float> rows((size_t)24 * count);
+    std::vector<float> rows; // host source: the table rows, checked before anything is queued
+    if (!device_src) {
+        rows.resize((size_t)24 * count);
         for (uint32_t i = 0; i < count; ++i) {
             const float *m = xf12 + 12ull * i;
             float *row = &rows[(size_t)24 * i];
@@ -644,12 +675,21 @@ static int update_instances_common(rptr_hip_t *h, uint32_t first, uint32_t count
             for (int k = 0; k < 24; ++k) ok = ok && std::isfinite(row[k]); // (det == 0: 1 / det is infinite)
             if (!ok) return fail(h, RPTR_E_INVALID, "transform %u (instance %u) is not finite or singular", i, first + i);
         }
+    }
+    {
+        const int rc0 = object_motion_before_update(h, -1);
+        if (rc0) return rc0;
+    }
+    if (device_src)
+        hipLaunchKernelGGL(rp_k_stage_instance_transforms, dim3(grid_for(h, count)), dim3(256), 0, h->stream, xf12, first, count, h->master.inst_xf, h->d_inst_rejected);
+    else {
         HIP_TRY(h, hipMemcpyAsync(h->master.inst_xf + 24ull * first, rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream)); // (pageable staging: the copy must be over before `rows` goes)
     }
     HIP_TRY(h, hipGetLastError());
     h->inst_version++;
     h->vertex_updates++; // (one counter for everything a refit has to pick up: rptr_hip_refit with frame contexts that own their sets)
+    h->om.unrefitted = true;
     return RPTR_OK;
 }
 int rptr_hip_update_instances(rptr_hip_t *h, uint32_t first_instance, uint32_t count, const float *transforms12) {
@@ -973,6 +1013,7 @@ int rptr_hip_refit(rptr_hip_t *h) {
         int rc0 = drain(h);
         if (rc0) return rc0;
     }
+    h->om.unrefitted = false; // (object motion: what was staged reaches the next frame)
     // ---- the BVH policy: which dynamic meshes get a new tree instead of a refit (librender/render_params.glsl.h:61,90-93)
     {
         bool changed = false;

@@ -105,6 +105,10 @@ struct FrameCtx {
     int launches_extend = 0, launches_connect = 0, spp_after = 0;
     int tail_from = 0; // the bounce at which this context's last frame handed over to the tail kernel (= max depth: no tail)
     size_t gstack_threads = 0;    // threads the stack scratch is sized for
+    // object motion (object_motion.h): the constants of the last submission on this context -- the views its AOV images were written with,
+    // its last camera, what its screen jitter follows from -- and which submission of the handle that was (rptr_hip::ObjectMotion::submissions)
+    RpFrame last_frame;
+    uint64_t last_submission = 0;
     // multi-GPU gather (host_comm.h): the image this context produced is being sent; its next frame waits for that on the device
     hipEvent_t ev_gather = nullptr;
     bool gather_pending = false;
@@ -402,6 +406,30 @@ struct rptr_hip {
         bool have = false;                  // img[cur] holds a call's output: the next call's history, what the read-back returns
     } up;
     uint64_t finished_serial = 0;           // frames waited for since initialize: the read-backs' frame changes with each
+    // object motion (object_motion.h, rptr_hip_track_object_motion / rptr_hip_object_motion): the state the PREVIOUS frame saw, kept while
+    // tracking is on. The first update_instances* / update_vertices* after a submission copies the staged transform table into
+    // prev_inst_xf and clears the changed marks; the first update_vertices* of a geometry in that interval copies its positions into
+    // prev_pos[g] and marks it -- all on the backend's stream, in front of the staging write. Device buffers live in scene_allocs:
+    // set_scene frees them and drops the tracking.
+    struct ObjectMotion {
+        bool enabled = false;
+        float *prev_inst_xf = nullptr;
+        std::vector<float *> prev_pos;      // per global geometry, beside master.dynpos
+        const float **d_prev_pos = nullptr; // ... the device table of them
+        uint32_t *d_record_geom = nullptr;  // per geometry record: its global geometry
+        uint32_t *d_geom_changed = nullptr; // per global geometry
+        uint32_t *d_rewritten = nullptr;    // pixels the last call rewrote (option "object_motion_pixels")
+        bool counted = false;               // ... d_rewritten holds the last call's count (false: that call launched nothing, the count is 0)
+        std::vector<char> geom_marked;      // host mirror of d_geom_changed for the current interval
+        uint64_t submissions = 0;           // launch sequences submitted since tracking was enabled
+        bool snapshot = false;              // prev_* describe the state submission `snapshot_of` saw
+        uint64_t snapshot_of = 0;
+        bool staged_since_submission = false; // an update was staged after the last submission
+        bool unrefitted = false;              // an update was staged and rptr_hip_refit has not run since
+        bool dirty[2] = {false, false};       // the last / the one-before-last submission was made while `unrefitted`
+        int last_frames = 1;                  // frames of the last launch sequence
+    } om;
+    std::vector<uint32_t> record_geometry;  // per geometry record (parameterized mesh, geometry): the global geometry (set_scene)
     size_t path_capacity = 0;
     // persistent traversal grids (traversal_grid below): [0] first / [1] later closest-hit, shadow rays [2] two-level / [3] one instance record
     int resident_per_cu[4] = {0, 0, 0, 0}; // blocks per CU of each kernel that fit at once (its occupancy, at most 8)

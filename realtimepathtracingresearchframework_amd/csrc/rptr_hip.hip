@@ -15,6 +15,7 @@
 #include "denoise_temporal.h"
 #include "surface_query.h"
 #include "occlusion_query.h"
+#include "object_motion.h"
 #include "launch.h"
 #include "lbvh.h"
 #include "tlas_build.h"
@@ -311,6 +312,9 @@ int rptr_hip_initialize(rptr_hip_t *h, int fb_width, int fb_height) {
     h->dt = decltype(h->dt)(); // (the temporal denoiser's history: allocated by the first rptr_hip_denoise_temporal, freed with the rest above)
     h->up = decltype(h->up)(); // (the upscaler's images: allocated by the first rptr_hip_taa_upscale, freed with the rest above)
     h->finished_serial = 0;
+    h->om.submissions = 0; // (object motion: no frame of the new size has been submitted; the tracking itself belongs to the scene and stays)
+    h->om.snapshot = h->om.counted = h->om.dirty[0] = h->om.dirty[1] = false;
+    for (FrameCtx &c : h->ctx) c.last_submission = 0;
     h->rt = decltype(h->rt)(); // (mode-2 images: allocated by the first frame that needs them, freed with the rest above)
     h->aov_ctx = 0;
     h->output_overwritten = h->aov_overwritten = false;

@@ -248,6 +248,9 @@ public:
         ranks_[0]->upscale_every_frame(on);
     }
     size_t readback_upscaled(size_t buffer_size, unsigned char *buffer) { return ranks_[0]->readback_upscaled(buffer_size, buffer); }
+    // object motion works on one GPU's whole frame as well (rptr_hip_object_motion refuses world_size > 1)
+    void track_object_motion(bool enable = true) { ranks_[0]->track_object_motion(enable); }
+    int64_t object_motion() { return ranks_[0]->object_motion(); }
     size_t readback_aov(RenderHip::AOVBufferIndex aov, size_t buffer_size, uint16_t *buffer) {
         size_t n = 0;
         for (auto &r : ranks_) n = r->readback_aov(aov, buffer_size, buffer);

@@ -371,6 +371,17 @@ public:
         flush_pipeline();
         check(rptr_hip_taa_upscale(h_, &p));
     }
+    // Object motion (include/rptr_hip.h rptr_hip_object_motion): track_object_motion after set_scene; object_motion after the frame that
+    // followed update_* + refit and before denoise_temporal / taa_upscale -- everything in flight is finished first. Returns the pixels
+    // whose motion vector was rewritten (waits for the pass).
+    void track_object_motion(bool enable = true) { check(rptr_hip_track_object_motion(h_, enable ? 1 : 0)); }
+    int64_t object_motion() {
+        flush_pipeline();
+        check(rptr_hip_object_motion(h_));
+        int64_t n = 0;
+        check(rptr_hip_get_option(h_, "object_motion_pixels", &n));
+        return n;
+    }
     // ... or with every frame of the reference's loop (begin_frame / draw_frame with or without a command stream), issued when the frame
     // it belongs to has been collected -- begin_frame's wait for the swap index it reuses, flush_pipeline, the synchronous draw_frame --
     // with reset_history = that frame's reset_accumulation. Frames collected through wait(ticket) are the host's to upscale.

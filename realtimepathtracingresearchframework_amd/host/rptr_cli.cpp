@@ -67,6 +67,11 @@ static int g_denoise_iterations = 0;
 // are the upscaled ones, at twice --img; the history restarts with the frames that restart the accumulation (the first one, a new
 // keyframe, moved geometry, a moved camera unless the history is reprojected). The float images stay the frame's own. Not with --denoise.
 static bool g_taa_upscale = false;
+// --object-motion (this host's): plays the animated transforms of a .vks file (numFrames > 1) -- frame k of the run gets the file's frame
+// k mod numFrames through update_instances + refit -- and runs rptr_hip_object_motion after every frame, in front of --denoise-temporal /
+// --taa-upscale (profiling mode, one frame at a time) or of the captured images (--data-capture: one capture per frame of the file).
+// Refused with anything else: without a consumer or a capture nothing reads the rewritten motion image.
+static bool g_object_motion = false;
 // --denoise-temporal <iterations> (this host's): every frame goes through rptr_hip_denoise_temporal as it is collected (the library's
 // defaults and that many passes; one frame per launch sequence), the history restarting with the frames that restart the accumulation,
 // and the images written are the denoised ones. Not with --denoise, --taa-upscale or several devices.
@@ -216,6 +221,7 @@ int main(int argc, char **argv) {
         else if (a == "--denoise") { need(1); g_denoise_iterations = std::atoi(argv[++i]); if (g_denoise_iterations < 1 || g_denoise_iterations > 5) { std::fprintf(stderr, "--denoise takes 1..5 iterations\n"); return 2; } }
         else if (a == "--denoise-temporal") { need(1); g_denoise_temporal_iterations = std::atoi(argv[++i]); if (g_denoise_temporal_iterations < 1 || g_denoise_temporal_iterations > 5) { std::fprintf(stderr, "--denoise-temporal takes 1..5 iterations\n"); return 2; } }
         else if (a == "--taa-upscale") g_taa_upscale = true;
+        else if (a == "--object-motion") g_object_motion = true;
         else if (a == "--img") { need(2); width = std::atoi(argv[++i]); height = std::atoi(argv[++i]); }
         else if (a == "--eye") { vec3(eye); got_eye = true; }
         else if (a == "--center") { vec3(center); got_center = true; }
@@ -382,10 +388,26 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "--taa-upscale needs one device (rptr_hip_taa_upscale refuses world_size > 1)\n");
         return 2;
     }
+    if (g_object_motion) {
+        const size_t n = scene_path.size();
+        const char *why = nullptr;
+        if (devices.size() > 1) why = "needs one device (rptr_hip_object_motion refuses world_size > 1)";
+        else if (validation) why = "needs --data-capture or --profiling: a validation run accumulates one still scene";
+        else if (!data_capture && !g_taa_upscale && g_denoise_temporal_iterations == 0)
+            why = "needs --denoise-temporal, --taa-upscale or --data-capture: nothing else reads the rewritten motion image";
+        else if (n < 4 || scene_path.compare(n - 4, 4, ".vks") != 0 || !g_more_scenes.empty() || g_load.ignore_animation)
+            why = "plays the animated transforms of ONE .vks file (not with --ignore-animation)";
+        else if (data_capture && !keyframes.empty()) why = "captures one image set per frame of the file: not with --keyframe";
+        else if (wave_amp != 0.f || freeze_frame) why = "cannot be combined with --animate-wave or --freeze-frame";
+        if (why) {
+            std::fprintf(stderr, "--object-motion %s\n", why);
+            return 2;
+        }
+    }
     if (want_help) scene_path.clear(); // prints the usage
     if (scene_path.empty() || (int)validation + (int)profiling + (int)data_capture != 1 || batch_spp < 1 || width < 1 || height < 1 || (profiling && profiling_frames < 1)) {
         std::fprintf(stderr, "usage: rptr_hip <scene.rpsc> (--validation <prefix> [--validation-spp n] | --profiling <csv prefix> [--profiling-fps f] "
-                             "[--profiling-img <prefix>] [--keyframe [len:]file.ini ...] [--profiling-count n] [--synchronous] [--fly-through] [--frames-in-flight n [--frames-per-launch b]] [--animate-wave a k]) [--img w h] [--denoise iterations | --denoise-temporal iterations | --taa-upscale] [--eye x y z] [--center x y z] "
+                             "[--profiling-img <prefix>] [--keyframe [len:]file.ini ...] [--profiling-count n] [--synchronous] [--fly-through] [--frames-in-flight n [--frames-per-launch b]] [--animate-wave a k]) [--img w h] [--denoise iterations | --denoise-temporal iterations | --taa-upscale] [--object-motion] [--eye x y z] [--center x y z] "
                              "[--up x y z] [--fov deg] [--variant gltf|diffuse] [--batch-spp k] [--every-frame] [--exr|--pfm|--png] [--config file.ini ...] [--sky-data <dir of the Hosek-Wilkie data headers>]\n"
                              "       rptr_hip <scene.rpsc> --data-capture <prefix> [--data-capture-spp n] [--data-capture-no-rgba] [--data-capture-no-aovs] "
                              "[--data-capture-albedo-roughness] [--data-capture-normal-depth] [--data-capture-motion] [--keyframe ...]   (EXR images per keyframe)\n"
@@ -475,6 +497,36 @@ int main(int argc, char **argv) {
                 }
             }
         }
+        // --object-motion: the file's transform table stays open; play(k) stages the transforms of the file's frame k mod numFrames that
+        // differ from the ones staged last (static instances -- which may be baked into the flattened tree -- are never named) and refits
+        rptr::vks::Header anim;
+        std::vector<float> anim_xf;
+        if (g_object_motion) {
+            anim = rptr::vks::read_header(scene_path);
+            if (anim.numFrames < 2 || anim.numAnimatedTransforms == 0) {
+                std::fprintf(stderr, "--object-motion: %s has no animated transforms (numFrames %llu)\n", scene_path.c_str(), (unsigned long long)anim.numFrames);
+                return 2;
+            }
+            anim_xf = rptr::vks::frame_transforms(anim, g_load.frame, g_load.instance_pruning_probability);
+            if (anim_xf.size() != 12 * scene.instances.size()) throw std::runtime_error("--object-motion: the file's instances are not the loaded scene's");
+            backend.track_object_motion();
+        }
+        auto play = [&](uint64_t k) {
+            const std::vector<float> xf = rptr::vks::frame_transforms(anim, k % anim.numFrames, g_load.instance_pruning_probability);
+            const size_t n = xf.size() / 12;
+            for (size_t i = 0; i < n;) {
+                if (!std::memcmp(&xf[12 * i], &anim_xf[12 * i], 48)) {
+                    ++i;
+                    continue;
+                }
+                size_t j = i + 1;
+                while (j < n && std::memcmp(&xf[12 * j], &anim_xf[12 * j], 48)) ++j;
+                backend.update_instances((uint32_t)i, (uint32_t)(j - i), &xf[12 * i]);
+                i = j;
+            }
+            anim_xf = xf;
+            backend.refit();
+        };
         base.params.batch_spp = batch_spp;
         backend.set_params(base.params, base.lighting);
         backend.update_config(scene.scene_params);
@@ -587,8 +639,13 @@ int main(int argc, char **argv) {
             // of every keyframe (one without --keyframe) are stored as <prefix>_%04d_{rgba,albedo_roughness,normal_depth,motion_jitter}.exr;
             // --data-capture-fps only paces the reference's animation clock between captures (a keyframe here is captured once)
             (void)capture_fps;
-            const size_t n_keys = std::max<size_t>(1, frames.size());
+            // --object-motion: one capture per frame of the file's animation instead, the motion image rewritten before it is stored
+            const size_t n_keys = g_object_motion ? (size_t)anim.numFrames : std::max<size_t>(1, frames.size());
             for (size_t k = 0; k < n_keys; ++k) {
+                if (g_object_motion) {
+                    if (k) play(g_load.frame + k);
+                    cfg.reset_accumulation = true;
+                }
                 if (!frames.empty()) {
                     rptr::HostConfig st = frames[k];
                     st.params.batch_spp = batch_spp;
@@ -603,10 +660,12 @@ int main(int argc, char **argv) {
                 }
                 int accumulated = 0;
                 while (accumulated < capture_spp) {
-                    const rptr::RenderStats st = backend.render(cfg);
+                    // (--object-motion: the capture's samples in ONE submission -- the pass compares the last two submissions)
+                    const rptr::RenderStats st = g_object_motion ? backend.render(cfg, capture_spp) : backend.render(cfg);
                     cfg.reset_accumulation = false;
                     accumulated = st.spp;
                 }
+                if (g_object_motion) std::printf("object motion: frame %zu, %lld pixels rewritten\n", k + 1, (long long)backend.object_motion());
                 char idx[16];
                 std::snprintf(idx, sizeof(idx), "_%04d", (int)k + 1);
                 const std::string pf = capture_prefix + idx;
@@ -698,7 +757,7 @@ int main(int argc, char **argv) {
                         p.reset = true;
                     }
                 }
-                if (!rest.empty()) p.reset = true; // the geometry moves: the accumulation starts over
+                if (!rest.empty() || g_object_motion) p.reset = true; // the geometry moves: the accumulation starts over
                 p.camera = cam;
                 if (fly_through) { // a moved camera restarts the accumulation (the application resets when the view changes) ...
                     p.camera = fly_camera(frame);
@@ -738,7 +797,7 @@ int main(int argc, char **argv) {
         // frames of one keyframe, every frame with its own view (rptr_hip_render_batch_cameras_async), n sequences in flight -- the schedule
         // bench.py times (the library asks the HIP runtime for a hardware queue per frame context itself: csrc/rptr_hip.hip
         // ensure_hw_queues). One CSV row per frame as it is collected; render_time_ms is the frame's share of its sequence.
-        if (frames_in_flight > 1 && rest.empty() && !freeze_frame) {
+        if (frames_in_flight > 1 && rest.empty() && !freeze_frame && !g_object_motion) {
             frames_per_launch = std::min(frames_per_launch, std::max(1, 16 / std::max(1, batch_spp)));
             // reprojection_mode 2 folds each frame into the one before it: one frame per launch sequence (include/rptr_hip.h)
             bool realtime = base.params.reprojection_mode == 2;
@@ -805,9 +864,10 @@ int main(int argc, char **argv) {
         // ---- the reference's loop (app.cpp:453-469): begin_frame / draw_frame / end_frame per frame, with the display's command stream (two
         // frames in flight, statistics two frames late) or, --synchronous, without one
         rptr::CommandStream display_stream;
-        backend.upscale_every_frame(g_taa_upscale); // (issued as each frame is collected: render_group.hpp frame)
-        backend.denoise_temporal_every_frame(g_denoise_temporal_iterations > 0, denoise_temporal_params());
-        rptr::CommandStream *const cmd_stream = synchronous ? nullptr : &display_stream;
+        // (--object-motion: the pass goes between a frame and its consumer, so the loop below renders one frame at a time and issues both)
+        backend.upscale_every_frame(g_taa_upscale && !g_object_motion); // (issued as each frame is collected: render_group.hpp frame)
+        backend.denoise_temporal_every_frame(g_denoise_temporal_iterations > 0 && !g_object_motion, denoise_temporal_params());
+        rptr::CommandStream *const cmd_stream = synchronous || g_object_motion ? nullptr : &display_stream;
         if (!rest.empty() || fly_through) { // (a short warm-up when the run is a measurement: the adaptive tail hand-over settles in two frames)
             apply_key(plan[0].key);
             for (int w = 0; w < 4; ++w) {
@@ -829,7 +889,13 @@ int main(int argc, char **argv) {
                 backend.update_vertices(scene.meshes[0].first_geometry, cur.data(), (uint32_t)(cur.size() / 3));
                 backend.refit();
             }
+            if (g_object_motion && frame) play(g_load.frame + (uint64_t)frame); // the file's next frame: new transforms, refit
             const rptr::RenderStats st = backend.frame(cmd_stream, config_of(fp));
+            if (g_object_motion) {
+                backend.object_motion();
+                if (g_taa_upscale) backend.taa_upscale(frame == 0);
+                if (g_denoise_temporal_iterations > 0) denoise_temporal(backend, frame == 0);
+            }
             gpu_ms += st.render_time;
             const auto now = std::chrono::steady_clock::now();
             const double app_ms = std::chrono::duration<double, std::milli>(now - last).count();
