@@ -122,8 +122,12 @@ RP_DEV V3 rp_xform_dir(const float4 r0, const float4 r1, const float4 r2, V3 d) 
 // machine; when RP_REFILL_MIN or more lanes have finished their ray, the idle
 // lanes take the next pool entries (ballot + mbcnt rank, no atomics), so short
 // rays do not leave lanes idle while the longest ray of the wave finishes.
+// A finished ray's result stays in its lane's registers until that refill: the idle lanes hand their results in together, right before
+// they take new entries, so Done is issued once per refill at refill_min or more lanes and not in every loop iteration at the few lanes
+// whose ray happened to end in it. The wave's last rays are retired by the refill block's final pass, the one that ends the loop.
 //   Load(i, o, d, tmin, tmax)  fetches queue entry i; false = the entry names no ray, nothing is traced or consumed for it
-//   Done(i, hit)               consumes the result of entry i
+//   Done(i, hit)               consumes the result of entry i: once per ray, some time after the ray's last step and before the lane's
+//                              next Load; the lanes of a wave that call it together are those retired by one refill
 //   Alpha(i, inst_idx, inst_id, geom, prim, u, v) -> true = ignore this candidate (ALPHA only: the reference's
 //                              any-hit test of alpha-tested materials, pt_megakernel.glsl:153-212); called for the
 //                              hits of triangles flagged RPTR_BVH_TRI_ALPHA that would otherwise be accepted
@@ -282,6 +286,17 @@ RP_DEV void rp_wave_trace(const RpScene &sc, const uint32_t n, uint32_t *cursor,
         const unsigned long long idle_mask = __ballot(idle);
         const uint32_t nidle = (uint32_t)__popcll(idle_mask);
         if (nidle >= refill_min) {
+            // retire: the idle lanes that still hold a result are the ones whose ray ended since the last refill; they hand it in here,
+            // together, not one by one in the iteration in which each of them happened to finish. First thing in the block, because
+            //   - load() below overwrites what done() reads (my_i, best, the caller's per-lane state), and
+            //   - the loop's only exit is the break below: it is taken with all 64 lanes idle, so the wave's last rays are retired
+            //     just above it. Nothing else in this function leaves the loop.
+            // A lane that finishes while fewer than refill_min lanes are idle (an empty pool, stragglers still walking) waits with its
+            // result until the count is reached -- 64 at the latest, when the stragglers end. `active` makes it exactly once per ray.
+            if (active && idle) {
+                done(my_i, best);
+                active = false;
+            }
             if (pool_next >= pool_end && more) {
                 uint32_t base = 0;
                 if (lane == 0) base = atomicAdd(cursor, fetch); // the cursor counts entries handed out behind the static pools
@@ -585,12 +600,9 @@ RP_DEV void rp_wave_trace(const RpScene &sc, const uint32_t n, uint32_t *cursor,
                 if (!SINGLE && cur == RP_SENTINEL) leave_instance();
             }
         }
-        if (active && cur == RP_EXIT) {
-            done(my_i, best);
-            active = false;
-        }
+        // (a lane whose ray just ended keeps its result in registers until the wave's next refill retires it)
 #ifdef RP_PROF
-        if (lane == 0) atomicAdd(&rp_prof[4], (unsigned long long)(wall_clock64() - prof_t2)); // leaf+done time (100 MHz ticks)
+        if (lane == 0) atomicAdd(&rp_prof[4], (unsigned long long)(wall_clock64() - prof_t2)); // leaf time (100 MHz ticks); done() is in the refill section
 #endif
     }
 #undef RP_SP_LEVEL

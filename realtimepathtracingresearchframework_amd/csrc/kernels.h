@@ -353,16 +353,14 @@ RP_DEV void rp_connect_body(const RpScene &sc, const RpFrame &f, const RpPathSta
         tmax = d.w;
         return true;
     };
+    // (runs at the wave's refill for all the rays that ended since the last one, dtraverse.h: one test, then the loads of all those lanes
+    // in flight together -- the id, then both rows of the path -- and one wait before the adds)
     auto done = [&](uint32_t i, const RpHitRec &h) {
-        if (h.inst_idx < 0) { // visible: NEE contribution arrives (nee.glsl:76-84)
-            const uint32_t p = ids[i];
-            const float4 c = sq.contrib[p];
-            float4 il = ps.illum[p];
-            il.x += c.x;
-            il.y += c.y;
-            il.z += c.z;
-            ps.illum[p] = il;
-        }
+        if (h.inst_idx >= 0) return; // occluded: nothing arrives
+        const uint32_t p = ids[i];   // visible: NEE contribution arrives (nee.glsl:76-84)
+        const float4 c = sq.contrib[p];
+        const float4 il = ps.illum[p];
+        ps.illum[p] = make_float4(il.x + c.x, il.y + c.y, il.z + c.z, il.w);
     };
     rp_wave_trace<true, COUNT, RP_NODE_MIN_ANY, RP_REFILL_MIN_ANY, ALPHA, SINGLE, LOCAL, LDSTOP, EXTLDS>(sc, n, cursor, gstack, load, done, alpha, n_nodes, n_tris,
                                                                                                         ext_stack);

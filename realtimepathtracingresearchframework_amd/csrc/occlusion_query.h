@@ -11,7 +11,7 @@
 // (lanes refill from later pools while others still walk), and the bits of skipped queries and those behind n belong to the caller: a
 // blind store of the word is not possible. Pools are multiples of 64 consecutive queries, so a word is only ever written by one wave --
 // the atomics order nothing between waves, they merge bits that arrive at different times into one word.
-//   1 (the default: measured, profiles/occlusion_queries_notes.md)  the lanes that finish in the same step are grouped by word with
+//   1 (the default: measured, profiles/occlusion_queries_notes.md)  the lanes that one refill retires (dtraverse.h) are grouped by word with
 //     ballots and the group's first lane issues one OR (the hits) and one AND (the misses) for the word, or a plain store when the
 //     group is the whole word. The bits of a group come from two
 //     ballots when every lane of the group holds the query whose bit index is its own lane index modulo 32 (a wave that refills all its
@@ -51,7 +51,7 @@ __global__ __launch_bounds__(RP_TRAVERSE_BLOCK, (ALPHA ? RP_QUERY_ALPHA_EXTEND_W
         else
             (void)__hip_atomic_fetch_and(word, ~bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #else
-        // (the lanes that finished in this step are the active ones: the ballots see nobody else)
+        // (the lanes retired by this refill are the active ones: the ballots see nobody else)
         const uint32_t w = i >> 5, key = (i & 31u) | (hit ? 32u : 0u);
         const uint32_t lane = rp_lane_id();
         unsigned long long todo = __ballot(!skip);
