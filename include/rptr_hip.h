@@ -734,6 +734,57 @@ void rptr_hip_taa_upscale_defaults(RptrTaaUpscaleParams *out);
 int rptr_hip_taa_upscale(rptr_hip_t *h, const RptrTaaUpscaleParams *p /* NULL = defaults */);
 int rptr_hip_readback_upscaled_u8(rptr_hip_t *h, unsigned char *rgba, size_t n_bytes);
 
+/* ---- auto-exposure: a metered display pass, the step from scene-referred radiance to a display image (stands where the reference's
+ * application runs its "uber post" step, RenderProcessingStep::UberPost, whose source is not shipped; process_samples.comp exposes and
+ * tone-maps only "if we don't have the uber post pass"). A call meters the last finished frame's accumulation image (source 0) or the
+ * denoiser's float image (source 1: the result of whichever denoise call ran last) with a log-luminance histogram -- 256 bins, eight
+ * per octave from 2^-16 up -- takes the mean log luminance between two percentiles, maps it to `key`, moves an exposure value ev
+ * towards that target at speed_up / speed_down per second, and writes an RGBA8 image of its own: colour x 2^(exposure + ev), an optional
+ * colour balance in LMS space, the tone map and sRGB of the denoiser's RGBA8 image. The ev lives on the device: no host round trip.
+ * csrc/auto_exposure.h states every operation, tests/auto_exposure_ref.py restates it in numpy, and histogram, state and image equal
+ * that restatement bit for bit. INTEGRATION.md "Auto-exposure" lists what a host can rely on.
+ * The call is explicit and additive, like rptr_hip_denoise, with the same source frame (the frame waited for last): it never touches the
+ * accumulation image, the RGBA8 frame, the AOV images, the denoiser's images and history, the upscaler's history, frame_id /
+ * frame_offset or the statistics; a frame rendered after it is bit-identical to one rendered without it, and a host that never calls
+ * it launches what it always launched. The call is asynchronous on the backend's stream; its buffers (4 bytes per pixel, 2 KB of
+ * histogram and state) are allocated by the first call and freed by rptr_hip_initialize / rptr_hip_destroy, which also forget the ev.
+ * mode 0 (manual): nothing is metered, the state is untouched, ev counts as 0 -- the image is the source through exposure, balance and
+ * tone map. With source 1, gains of 1 and tone_mapping_mode = early_tone_mapping_mode it equals rptr_hip_readback_denoised_u8 byte for
+ * byte. With output_channel != 0 the image is a copy of the frame's RGBA8 (an AOV view), nothing is metered and the state is untouched.
+ * Defaults: speed_up 1, speed_down 3 per second. A falling EV is a brightening scene, and eyes adapt to brightening within a second or
+ * so and to darkening far more slowly: the two rates keep that 3 : 1 order of the common eye-adaptation defaults.
+ * rptr_hip_readback_exposed_u8: the image of the last call, W x H x 4 bytes; rptr_hip_readback_exposure_state: what the last mode-1 call
+ * left. Both wait for the call.
+ * RPTR_E_INVALID: NULL handle; a field outside the range its comment states, or not finite; reserved != 0; before initialize or before a
+ * frame has finished, and whatever else rptr_hip_denoise refuses about the finished frame; source 1 when
+ * rptr_hip_readback_denoised_f32 would be refused (no denoise call, or stale); a read-back of the image before any call since
+ * initialize, after a later frame finished, or into fewer than 4 W H bytes; a state read-back (or NULL out) before any mode-1 call since
+ * initialize. RPTR_E_UNSUPPORTED: option "aovs" = 0 with source 1 (source 0 needs no AOV image); world_size > 1;
+ * render_upscale_factor 2. */
+typedef struct RptrAutoExposureParams { /* 64 bytes */
+    int32_t source;            /* 0: the frame's accumulation image; 1: the denoiser's float image (whichever denoise call ran last) */
+    int32_t mode;              /* 1: meter and adapt; 0: manual -- nothing is metered, the state is untouched, ev counts as 0 */
+    int32_t reset_history;     /* 1: no adaptation, ev jumps to this call's target */
+    int32_t tone_mapping_mode; /* -1, 0: none; 1: neutral; 2: fast -- the values of early_tone_mapping_mode */
+    float key;                 /* > 0; the luminance the metered mean is mapped to (0.18) */
+    float low_percentile;      /* [0, 1) (0.5) */
+    float high_percentile;     /* (low, 1] (0.95) */
+    float min_ev, max_ev;      /* min <= max, finite (-8, 8) */
+    float speed_up, speed_down;/* >= 0, per second: the rate when the target EV is above / below the current one (1, 3) */
+    float dt;                  /* >= 0, seconds since the previous call; 0: jump to the target */
+    float white_balance[3];    /* > 0, gains on L, M, S (1, 1, 1) */
+    int32_t reserved;          /* must be 0 */
+} RptrAutoExposureParams;
+void rptr_hip_auto_exposure_defaults(RptrAutoExposureParams *out);
+int rptr_hip_auto_exposure(rptr_hip_t *h, const RptrAutoExposureParams *p /* NULL = defaults */);
+int rptr_hip_readback_exposed_u8(rptr_hip_t *h, unsigned char *rgba, size_t n_bytes);
+typedef struct RptrExposureState { /* 32 + 1024 bytes */
+    float ev, target_ev, mean_log2, scale; /* scale = what the display kernel multiplied by */
+    uint32_t counted, black, ignored, calls;
+    uint32_t histogram[256];
+} RptrExposureState;
+int rptr_hip_readback_exposure_state(rptr_hip_t *h, RptrExposureState *out);
+
 /* ---- object motion: a pass over a finished frame that rewrites the motion half of its motion + jitter AOV image where objects moved.
  * A frame projects the SAME world point through the previous and the current view (motion_vector = 0, as the reference): the AOV follows
  * the camera, not rptr_hip_update_instances / rptr_hip_update_vertices. rptr_hip_object_motion(h), called after the frame and before

@@ -262,6 +262,17 @@ class TaaUpscaleParams(C.Structure):  # include/rptr_hip.h RptrTaaUpscaleParams
     _fields_ = [("factor", C.c_int32), ("reset_history", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
+class AutoExposureParams(C.Structure):  # include/rptr_hip.h RptrAutoExposureParams
+    _fields_ = [("source", C.c_int32), ("mode", C.c_int32), ("reset_history", C.c_int32), ("tone_mapping_mode", C.c_int32),
+                ("key", C.c_float), ("low_percentile", C.c_float), ("high_percentile", C.c_float), ("min_ev", C.c_float), ("max_ev", C.c_float),
+                ("speed_up", C.c_float), ("speed_down", C.c_float), ("dt", C.c_float), ("white_balance", C.c_float * 3), ("reserved", C.c_int32)]
+
+
+class ExposureState(C.Structure):  # include/rptr_hip.h RptrExposureState
+    _fields_ = [("ev", C.c_float), ("target_ev", C.c_float), ("mean_log2", C.c_float), ("scale", C.c_float),
+                ("counted", C.c_uint32), ("black", C.c_uint32), ("ignored", C.c_uint32), ("calls", C.c_uint32), ("histogram", C.c_uint32 * 256)]
+
+
 class OcclusionParams(C.Structure):  # include/rptr_hip.h RptrOcclusionParams
     _fields_ = [("flags", C.c_uint32), ("alpha_cutoff", C.c_float), ("reserved", C.c_uint32 * 2)]
 
@@ -283,6 +294,8 @@ SURFACE_HIT_DTYPE = _surface_hit_dtype()  # numpy structured dtype of SurfaceHit
 assert C.sizeof(SurfaceHit) == 96 and SURFACE_HIT_DTYPE.itemsize == 96
 assert C.sizeof(OcclusionParams) == 16
 assert C.sizeof(TaaUpscaleParams) == 16
+assert C.sizeof(AutoExposureParams) == 64
+assert C.sizeof(ExposureState) == 32 + 1024
 assert C.sizeof(LightSource) == 48
 assert C.sizeof(DenoiseParams) == 32
 assert C.sizeof(DenoiseTemporalParams) == 64
@@ -307,6 +320,7 @@ EXPORTED_SYMBOLS = [
     "rptr_hip_denoise_defaults", "rptr_hip_denoise", "rptr_hip_readback_denoised_f32", "rptr_hip_readback_denoised_u8",
     "rptr_hip_denoise_temporal_defaults", "rptr_hip_denoise_temporal", "rptr_hip_readback_denoise_history_f32",
     "rptr_hip_taa_upscale_defaults", "rptr_hip_taa_upscale", "rptr_hip_readback_upscaled_u8",
+    "rptr_hip_auto_exposure_defaults", "rptr_hip_auto_exposure", "rptr_hip_readback_exposed_u8", "rptr_hip_readback_exposure_state",
     "rptr_hip_track_object_motion", "rptr_hip_object_motion",
     "rptr_hip_tile_rows", "rptr_hip_local_pixel_count", "rptr_hip_copy_tile_to_device", "rptr_hip_trace", "rptr_hip_trace_device", "rptr_hip_enable_ray_queries", "rptr_hip_render_ray_queries", "rptr_hip_trace_radiance", "rptr_hip_trace_radiance_device", "rptr_hip_render_radiance_queries", "rptr_hip_trace_surface", "rptr_hip_trace_surface_device", "rptr_hip_occlusion_defaults", "rptr_hip_trace_occlusion", "rptr_hip_trace_occlusion_device", "rptr_hip_set_light_sampling_variant", "rptr_hip_trace_counted",
     "rptr_hip_export_bvh", "rptr_hip_build_bvh_host", "rptr_hip_stats",

@@ -113,6 +113,11 @@ def load_library(path=None):
     L.rptr_hip_taa_upscale_defaults.restype = None
     L.rptr_hip_taa_upscale.argtypes = [vp, C.POINTER(abi.TaaUpscaleParams)]
     L.rptr_hip_readback_upscaled_u8.argtypes = [vp, vp, C.c_size_t]
+    L.rptr_hip_auto_exposure_defaults.argtypes = [C.POINTER(abi.AutoExposureParams)]
+    L.rptr_hip_auto_exposure_defaults.restype = None
+    L.rptr_hip_auto_exposure.argtypes = [vp, C.POINTER(abi.AutoExposureParams)]
+    L.rptr_hip_readback_exposed_u8.argtypes = [vp, vp, C.c_size_t]
+    L.rptr_hip_readback_exposure_state.argtypes = [vp, C.POINTER(abi.ExposureState)]
     L.rptr_hip_track_object_motion.argtypes = [vp, i32]
     L.rptr_hip_object_motion.argtypes = [vp]
     L.rptr_hip_tile_rows.argtypes = [vp, i32, vp, i32]
@@ -484,6 +489,42 @@ class RenderHip:
         out = np.zeros((2 * hgt, 2 * w, c), np.uint8)
         self._check(self._L.rptr_hip_readback_upscaled_u8(self._h, out.ctypes.data_as(C.c_void_p), out.size))
         return out
+
+    # ---- auto-exposure (include/rptr_hip.h rptr_hip_auto_exposure; csrc/auto_exposure.h)
+    def auto_exposure(self, params=None, **fields):
+        """Meters the frame the read-backs return (the frame waited for last; source = 1: the denoised image of that frame), adapts the
+        exposure value on the device and writes a display-ready RGBA8 image of its own; asynchronous on the backend's stream. params: an
+        abi.AutoExposureParams, or None for the library's defaults; keyword arguments override single fields (white_balance: three
+        gains). Pass reset_history = 1 for a frame the adaptation should not carry over to, and dt = the seconds since the previous
+        call (0: jump to the target). self.params.exposure, as it is now, is added to the metered value. Returns the parameters used."""
+        p = abi.AutoExposureParams()
+        if params is None:
+            self._L.rptr_hip_auto_exposure_defaults(C.byref(p))
+        else:
+            C.memmove(C.byref(p), C.byref(params), C.sizeof(p))
+        for k, v in fields.items():
+            if k not in dict(abi.AutoExposureParams._fields_) or k == "reserved":
+                raise TypeError("auto_exposure: unknown parameter %r" % k)
+            if k == "white_balance":
+                p.white_balance[:] = [float(g) for g in v]
+            else:
+                setattr(p, k, v)
+        self._push_params()
+        self._check(self._L.rptr_hip_auto_exposure(self._h, C.byref(p)))
+        return p
+
+    def readback_exposed(self):
+        """the RGBA8 image of the last auto_exposure() as an (H, W, 4) uint8 array"""
+        w, hgt, c = self.get_framebuffer_size()
+        out = np.zeros((hgt, w, c), np.uint8)
+        self._check(self._L.rptr_hip_readback_exposed_u8(self._h, out.ctypes.data_as(C.c_void_p), out.size))
+        return out
+
+    def readback_exposure_state(self):
+        """what the last metering auto_exposure() (mode = 1) left: an abi.ExposureState"""
+        st = abi.ExposureState()
+        self._check(self._L.rptr_hip_readback_exposure_state(self._h, C.byref(st)))
+        return st
 
     # ---- object motion (include/rptr_hip.h rptr_hip_object_motion; csrc/object_motion.h)
     def track_object_motion(self, enable=True):

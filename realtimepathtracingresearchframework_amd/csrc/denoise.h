@@ -248,13 +248,13 @@ __global__ __launch_bounds__(256) void rp_k_denoise_pass(RpDenoiseArgs a, const 
 RP_DEV float rp_dn_srgb(float x) {
     return (x <= 0.0031308f) ? 12.92f * x : 1.055f * float(pow(double(fmaxf(fabsf(x), 1.192092896e-07f)), double(1.f / 2.4f))) - 0.055f;
 }
-RP_DEV float4 rp_dn_display(const RpDenoiseArgs &a, float4 o) {
-    float x = o.x * a.exposure_scale, y = o.y * a.exposure_scale, z = o.z * a.exposure_scale;
-    if (a.tone_mapping_mode == 2) {
+// ... from the exposed colour on: the tone map and sRGB (auto_exposure.h ends with the same two steps)
+RP_DEV float4 rp_dn_tone_map_srgb(int tone_mapping_mode, float x, float y, float z, float w) {
+    if (tone_mapping_mode == 2) {
         x = x / (1.0f + x);
         y = y / (1.0f + y);
         z = z / (1.0f + z);
-    } else if (a.tone_mapping_mode == 1) {
+    } else if (tone_mapping_mode == 1) {
         const float L = fmaxf(fmaxf(x, y), fmaxf(z, 1.0f));
         const float g = float(log2(double(L)));
         const float k = ((0.1f * g) * (1.0f - 0.8f) + 1.0f * 0.8f) / L;
@@ -262,7 +262,10 @@ RP_DEV float4 rp_dn_display(const RpDenoiseArgs &a, float4 o) {
         y = y * k;
         z = z * k;
     }
-    return make_float4(rp_dn_srgb(x), rp_dn_srgb(y), rp_dn_srgb(z), o.w);
+    return make_float4(rp_dn_srgb(x), rp_dn_srgb(y), rp_dn_srgb(z), w);
+}
+RP_DEV float4 rp_dn_display(const RpDenoiseArgs &a, float4 o) {
+    return rp_dn_tone_map_srgb(a.tone_mapping_mode, o.x * a.exposure_scale, o.y * a.exposure_scale, o.z * a.exposure_scale, o.w);
 }
 
 // One thread per pixel: remodulate, store both images

@@ -247,13 +247,13 @@ int rptr_hip_readback_aov(rptr_hip_t *h, int aov_index, uint16_t *rgba16f, size_
 
 // ---- what the calls that work on the last finished frame and its AOV images (the denoiser, the temporal upscaler) ask of the handle:
 // one device, the AOV images on, a frame finished, its images not being overwritten by a frame in flight, and the AOV images those of
-// the frame waited for last. `who`: the entry point; `verb`: what the host is told to do earlier; `reads`: the AOV images it needs;
-// at_render_resolution: the call's images have the render resolution, so render_upscale_factor 2 is refused
+// the frame waited for last. `who`: the entry point; `verb`: what the host is told to do earlier; `reads`: the AOV images it needs
+// (NULL: none, option "aovs" may be 0); at_render_resolution: the call's images have the render resolution, so render_upscale_factor 2 is refused
 extern "C++" {
 static int check_finished_frame_with_aovs(rptr_hip *h, const char *who, const char *verb, const char *reads, bool at_render_resolution) {
     if (h->world > 1) return fail(h, RPTR_E_UNSUPPORTED, "%s needs world_size 1: the taps of a stripe's pixels lie in other ranks' rows", who);
     if (h->width == 0) return fail(h, RPTR_E_INVALID, "%s before initialize", who);
-    if (!h->aovs) return fail(h, RPTR_E_UNSUPPORTED, "%s reads %s: option \"aovs\" is 0", who, reads);
+    if (reads && !h->aovs) return fail(h, RPTR_E_UNSUPPORTED, "%s reads %s: option \"aovs\" is 0", who, reads);
     if (at_render_resolution && h->params.render_upscale_factor == 2)
         return fail(h, RPTR_E_UNSUPPORTED, "%s needs render_upscale_factor 1 (its RGBA8 image has the render resolution)", who);
     if (h->finished_serial == 0) return fail(h, RPTR_E_INVALID, "%s before a frame has finished (render, or wait for a ticket, first)", who);
@@ -514,6 +514,122 @@ int rptr_hip_readback_upscaled_u8(rptr_hip_t *h, unsigned char *rgba, size_t n_b
     if (n_bytes < need) return fail(h, RPTR_E_INVALID, "read-back buffer too small for the upscaled image: %zu < %zu bytes", n_bytes, need);
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipMemcpyAsync(rgba, h->up.img[h->up.cur], need, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return RPTR_OK;
+}
+
+// ---- auto-exposure (auto_exposure.h): meter the last finished frame or the denoiser's image, adapt the ev on the device, expose
+void rptr_hip_auto_exposure_defaults(RptrAutoExposureParams *out) {
+    if (!out) return;
+    memset(out, 0, sizeof(*out));
+    out->mode = 1;
+    out->tone_mapping_mode = -1;
+    out->key = 0.18f;
+    out->low_percentile = 0.5f;
+    out->high_percentile = 0.95f;
+    out->min_ev = -8.0f;
+    out->max_ev = 8.0f;
+    out->speed_up = 1.0f;
+    out->speed_down = 3.0f;
+    out->white_balance[0] = out->white_balance[1] = out->white_balance[2] = 1.0f;
+}
+
+int rptr_hip_auto_exposure(rptr_hip_t *h, const RptrAutoExposureParams *p) {
+    const char *who = "rptr_hip_auto_exposure";
+    if (!h) return fail(nullptr, RPTR_E_INVALID, "NULL handle");
+    RptrAutoExposureParams defaults;
+    rptr_hip_auto_exposure_defaults(&defaults);
+    if (!p) p = &defaults;
+    if (p->source != 0 && p->source != 1) return fail(h, RPTR_E_INVALID, "%s: source = %d (0: the frame, 1: the denoised image)", who, p->source);
+    if (p->mode != 0 && p->mode != 1) return fail(h, RPTR_E_INVALID, "%s: mode = %d (0: manual, 1: meter and adapt)", who, p->mode);
+    if (p->reset_history != 0 && p->reset_history != 1) return fail(h, RPTR_E_INVALID, "%s: reset_history must be 0 or 1", who);
+    if (p->tone_mapping_mode < -1 || p->tone_mapping_mode > 2) return fail(h, RPTR_E_INVALID, "%s: tone_mapping_mode = %d is outside [-1, 2]", who, p->tone_mapping_mode);
+    if (!(p->key > 0.0f) || !std::isfinite(p->key)) return fail(h, RPTR_E_INVALID, "%s: key must be finite and > 0 (is %g)", who, (double)p->key);
+    if (!(p->low_percentile >= 0.0f && p->low_percentile < 1.0f) || !(p->high_percentile > p->low_percentile && p->high_percentile <= 1.0f))
+        return fail(h, RPTR_E_INVALID, "%s: the percentiles must satisfy 0 <= low < high <= 1 (are %g, %g)", who, (double)p->low_percentile, (double)p->high_percentile);
+    if (!std::isfinite(p->min_ev) || !std::isfinite(p->max_ev) || !(p->min_ev <= p->max_ev))
+        return fail(h, RPTR_E_INVALID, "%s: min_ev and max_ev must be finite, min_ev <= max_ev (are %g, %g)", who, (double)p->min_ev, (double)p->max_ev);
+    if (!(p->speed_up >= 0.0f) || !std::isfinite(p->speed_up) || !(p->speed_down >= 0.0f) || !std::isfinite(p->speed_down))
+        return fail(h, RPTR_E_INVALID, "%s: speed_up and speed_down must be finite and >= 0 (are %g, %g)", who, (double)p->speed_up, (double)p->speed_down);
+    if (!(p->dt >= 0.0f) || !std::isfinite(p->dt)) return fail(h, RPTR_E_INVALID, "%s: dt must be finite and >= 0 (is %g)", who, (double)p->dt);
+    for (float g : p->white_balance)
+        if (!(g > 0.0f) || !std::isfinite(g)) return fail(h, RPTR_E_INVALID, "%s: white_balance gains must be finite and > 0", who);
+    if (p->reserved) return fail(h, RPTR_E_INVALID, "%s: RptrAutoExposureParams.reserved must be 0", who);
+    int rc;
+    if ((rc = check_finished_frame_with_aovs(h, who, "expose", p->source == 1 ? "the denoised image, made from the AOV images" : nullptr, true))) return rc;
+    if (p->source == 1 && (rc = check_denoised(h))) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t npix = (size_t)h->width * (size_t)h->height;
+    if (!h->ae.out_u8) {
+        if ((rc = dev_alloc(h, &h->ae.hist, RP_AE_WORDS, nullptr)) || (rc = dev_alloc(h, &h->ae.state, 1, nullptr)) || (rc = dev_alloc(h, &h->ae.out_u8, npix, nullptr))) {
+            h->ae = decltype(h->ae)(); // (what was allocated stays on the handle's list and is freed with it)
+            return rc;
+        }
+        HIP_TRY(h, hipMemsetAsync(h->ae.hist, 0, RP_AE_WORDS * sizeof(uint32_t), h->stream));
+        HIP_TRY(h, hipMemsetAsync(h->ae.state, 0, sizeof(RptrExposureState), h->stream));
+    }
+    const float4 *accum = nullptr;
+    const uchar4 *fb = nullptr;
+    if ((rc = last_finished_image(h, &accum, &fb))) return rc; // (world_size 1: an image is the whole frame, npix pixels)
+    const RpLaunch one{dim3(1), h->stream, nullptr, nullptr};
+    const RpLaunch per_pixel{dim3((unsigned)grid_for(h, npix)), h->stream, nullptr, nullptr};
+    if (h->params.output_channel != 0) { // an AOV view: the frame's RGBA8 as it is (the denoiser's rule)
+        HIP_TRY(h, hipMemcpyAsync(h->ae.out_u8, fb, npix * sizeof(uchar4), hipMemcpyDeviceToDevice, h->stream));
+        h->ae.serial = h->finished_serial;
+        return RPTR_OK;
+    }
+    RpExposeArgs x;
+    memset(&x, 0, sizeof(x));
+    x.src = p->source == 1 ? h->dn.out_f32 : accum;
+    x.fb = fb;
+    x.out = h->ae.out_u8;
+    x.npix = npix;
+    x.tone_mapping_mode = p->tone_mapping_mode;
+    x.balance = (p->white_balance[0] != 1.0f || p->white_balance[1] != 1.0f || p->white_balance[2] != 1.0f) ? 1 : 0;
+    for (int k = 0; k < 3; ++k) x.gains[k] = p->white_balance[k];
+    if (p->mode == 1) {
+        RpMeterReduceArgs m;
+        memset(&m, 0, sizeof(m));
+        m.hist = h->ae.hist;
+        m.state = h->ae.state;
+        for (int s = 0; s < 8; ++s) m.T[s] = std::log2(1.0 + ((double)s + 0.5) / 8.0);
+        m.log2_key = std::log2((double)p->key);
+        m.k_up = 1.0 - std::exp(-(double)p->dt * (double)p->speed_up);
+        m.k_down = 1.0 - std::exp(-(double)p->dt * (double)p->speed_down);
+        m.low_percentile = p->low_percentile;
+        m.high_percentile = p->high_percentile;
+        m.min_ev = p->min_ev;
+        m.max_ev = p->max_ev;
+        m.exposure = h->params.exposure;
+        m.have_state = h->ae.have_state ? 1 : 0;
+        m.reset_history = p->reset_history;
+        m.jump = p->dt == 0.0f ? 1 : 0;
+        // (four blocks per CU: at most 1024 x 256 global adds on 256 CUs, whatever the image size)
+        rp_launch_kernel(RpLaunch{dim3((unsigned)grid_for(h, npix, 4)), h->stream, nullptr, nullptr}, rp_k_meter<false>, 256u, x.src, npix, h->ae.hist);
+        rp_launch_kernel(one, rp_k_meter_reduce, 256u, m);
+        h->ae.have_state = true;
+        x.state = h->ae.state;
+    } else
+        x.scale = (float)std::exp2((double)(h->params.exposure + 0.0f));
+    rp_launch_kernel(per_pixel, rp_k_expose, 256u, x);
+    HIP_TRY(h, hipGetLastError());
+    h->ae.serial = h->finished_serial;
+    return RPTR_OK;
+}
+
+int rptr_hip_readback_exposed_u8(rptr_hip_t *h, unsigned char *rgba, size_t n_bytes) {
+    if (!h || !rgba) return fail(h, RPTR_E_INVALID, "NULL argument");
+    if (!h->ae.out_u8 || h->ae.serial == 0) return fail(h, RPTR_E_INVALID, "no exposed image: call rptr_hip_auto_exposure first");
+    if (h->ae.serial != h->finished_serial)
+        return fail(h, RPTR_E_INVALID, "the exposed image is stale: a later frame has finished since rptr_hip_auto_exposure ran; call it again for that frame");
+    return readback_rows<uchar4>(h, h->ae.out_u8, reinterpret_cast<uchar4 *>(rgba), n_bytes / 4);
+}
+
+int rptr_hip_readback_exposure_state(rptr_hip_t *h, RptrExposureState *out) {
+    if (!h || !out) return fail(h, RPTR_E_INVALID, "NULL argument");
+    if (!h->ae.have_state) return fail(h, RPTR_E_INVALID, "no exposure state: call rptr_hip_auto_exposure with mode 1 first");
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipMemcpyAsync(out, h->ae.state, sizeof(*out), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return RPTR_OK;
 }

@@ -405,7 +405,16 @@ struct rptr_hip {
         int cur = 0;
         bool have = false;                  // img[cur] holds a call's output: the next call's history, what the read-back returns
     } up;
-    uint64_t finished_serial = 0;           // frames waited for since initialize: the read-backs' frame changes with each
+    // auto-exposure (auto_exposure.h, rptr_hip_auto_exposure): the working histogram, the state and the exposed RGBA8 image, made by the
+    // first call and freed with the other frame-sized buffers
+    struct AutoExposure {
+        uint32_t *hist = nullptr;           // RP_AE_WORDS words, zero between calls (the reduce kernel clears what it has copied)
+        RptrExposureState *state = nullptr;
+        uchar4 *out_u8 = nullptr;
+        uint64_t serial = 0;                // finished_serial of the frame the image was made from (0: none)
+        bool have_state = false;            // a mode-1 call has run since initialize: `state` holds an ev
+    } ae;
+    uint64_t finished_serial = 0;          // frames waited for since initialize: the read-backs' frame changes with each
     // object motion (object_motion.h, rptr_hip_track_object_motion / rptr_hip_object_motion): the state the PREVIOUS frame saw, kept while
     // tracking is on. The first update_instances* / update_vertices* after a submission copies the staged transform table into
     // prev_inst_xf and clears the changed marks; the first update_vertices* of a geometry in that interval copies its positions into

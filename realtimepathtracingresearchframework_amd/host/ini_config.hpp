@@ -123,6 +123,9 @@ struct HostConfig {
     bool bvh_policy_set = false; // a file named one of the two
     float bump_scale = 0.f; // 0: not set
     bool sun_changed = false;
+    // auto-exposure (Tonemapping: "auto exposure", "exposure key", "white balance"); -1 / NAN = not named by any file so far
+    int auto_exposure = -1;
+    float exposure_key = NAN, white_balance[3] = {NAN, NAN, NAN};
     // the Sun header of the scene state (libapp/scene_state.h:79-96); NAN = not named by any file so far
     float sun_height = NAN, sun_angle = NAN, turbidity = NAN, albedo[3] = {NAN, NAN, NAN};
     std::vector<std::string> notes;
@@ -174,6 +177,9 @@ inline void apply_ini_object(const IniObject &o, HostConfig &c) {
     }
     if (const IniObject *t = o.child("Tonemapping")) {
         t->get("exposure", &c.params.exposure, 1);
+        t->get("auto exposure", &c.auto_exposure); // this host's three keys: rptr_hip_auto_exposure (bin/rptr_hip --auto-exposure)
+        t->get("exposure key", &c.exposure_key, 1);
+        t->get("white balance", c.white_balance, 3);
         if (const IniObject *op = t->child("operator")) { // COMPATIBILITY_TONEMAPPING_OPERATOR_NAMES + TONEMAPPING_MODES_NAMES (postprocess/tonemapping.h)
             const std::string s = op->selected();
             if (s.find("NEUTRAL") != std::string::npos || s.find("LOG") != std::string::npos) c.params.early_tone_mapping_mode = 1;

@@ -91,6 +91,14 @@ public:
         if (size() > 1 || !cmd_stream) {
             const RenderStats s = render(config);
             if (denoise_temporal_every_frame_) denoise_temporal(config.reset_accumulation);
+            if (auto_exposure_every_frame_) { // (render() collects through tickets: the call is this loop's to issue, as the two around it)
+                RptrAutoExposureParams p = auto_exposure_params_;
+                p.reset_history = config.reset_accumulation ? 1 : 0;
+                p.dt = have_time_ && config.time > last_time_ ? float(config.time - last_time_) : 0.0f;
+                auto_exposure(p);
+            }
+            last_time_ = config.time;
+            have_time_ = true;
             if (upscale_every_frame_) taa_upscale(config.reset_accumulation);
             return s;
         }
@@ -235,6 +243,18 @@ public:
         ranks_[0]->denoise_temporal_every_frame(on, p);
     }
     size_t readback_denoise_history(size_t buffer_size, float *buffer) { return ranks_[0]->readback_denoise_history(buffer_size, buffer); }
+    // auto-exposure meters one GPU's whole frame as well (rptr_hip_auto_exposure refuses world_size > 1)
+    void auto_exposure(const RptrAutoExposureParams &p) { ranks_[0]->auto_exposure(p); }
+    // with every frame of frame(), as upscale_every_frame below (RenderHip issues it in both of its loops); for one device only
+    void auto_exposure_every_frame(bool on, const RptrAutoExposureParams &p = RenderHip::auto_exposure_defaults()) {
+        if (on && size() > 1) throw std::runtime_error("auto_exposure_every_frame needs one device (rptr_hip_auto_exposure refuses world_size > 1)");
+        auto_exposure_every_frame_ = on;
+        auto_exposure_params_ = p;
+        ranks_[0]->auto_exposure_every_frame(on, p);
+    }
+    size_t readback_exposed(size_t buffer_size, unsigned char *buffer) { return ranks_[0]->readback_exposed(buffer_size, buffer); }
+    RptrExposureState readback_exposure_state(bool newest = true) { return ranks_[0]->readback_exposure_state(newest); }
+    bool exposure_state_ready() const { return ranks_[0]->exposure_state_ready(); }
     // temporal 2x upscaling works on one GPU's whole frame as well (rptr_hip_taa_upscale refuses world_size > 1)
     void taa_upscale(const RptrTaaUpscaleParams &p) { ranks_[0]->taa_upscale(p); }
     void taa_upscale(bool reset_history) {
@@ -278,6 +298,10 @@ private:
     bool upscale_every_frame_ = false;
     bool denoise_temporal_every_frame_ = false;
     RptrDenoiseTemporalParams denoise_temporal_params_ = RenderHip::denoise_temporal_defaults();
+    bool auto_exposure_every_frame_ = false;
+    RptrAutoExposureParams auto_exposure_params_ = RenderHip::auto_exposure_defaults();
+    double last_time_ = 0.0; // RenderConfiguration::time of the previous synchronous frame(): the next one's time step
+    bool have_time_ = false;
 };
 
 } // namespace rptr

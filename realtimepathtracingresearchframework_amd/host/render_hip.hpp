@@ -180,6 +180,7 @@ public:
         check(rptr_hip_render_async(h_, &cam, variant_, batch_spp(0), reset_accumulation ? 1 : 0, 0, &ticket_[swap_index_]));
         pending_[swap_index_] = true;
         slot_reset_[swap_index_] = reset_accumulation;
+        slot_dt_[swap_index_] = frame_dt_;
         asynchronous_ = true;
         count_frame(batch_spp(0));
     }
@@ -195,6 +196,9 @@ public:
         reset_accumulation = config.reset_accumulation;
         freeze_frame = config.freeze_frame;
         configure_for(config.active_variant);
+        frame_dt_ = have_time_ && config.time > last_time_ ? float(config.time - last_time_) : 0.0f; // (auto_exposure_every_frame)
+        last_time_ = config.time;
+        have_time_ = true;
     }
     void draw_frame(int spp = 0) { // synchronous
         flush_pipeline();
@@ -202,7 +206,7 @@ public:
         const RptrCamera cam = abi_camera();
         check(rptr_hip_render(h_, &cam, variant_, batch_spp(spp), reset_accumulation ? 1 : 0, 0, &last_));
         ++stats_serial_;
-        frame_collected(reset_accumulation);
+        frame_collected(reset_accumulation, frame_dt_);
         count_frame(batch_spp(spp));
         asynchronous_ = false;
     }
@@ -371,6 +375,46 @@ public:
         flush_pipeline();
         check(rptr_hip_taa_upscale(h_, &p));
     }
+    // Auto-exposure (include/rptr_hip.h rptr_hip_auto_exposure): the frame the read-backs return -- everything in flight is finished first
+    // -- or its denoised image (p.source = 1) is metered, the exposure value adapts on the device, and a display-ready RGBA8 image of its
+    // own is written; nothing else is touched. Asynchronous on the backend's stream. `params.exposure`, as it is now, is added to the
+    // metered value.
+    static RptrAutoExposureParams auto_exposure_defaults() {
+        RptrAutoExposureParams p;
+        rptr_hip_auto_exposure_defaults(&p);
+        return p;
+    }
+    void auto_exposure(const RptrAutoExposureParams &p) {
+        flush_pipeline();
+        push_state();
+        check(rptr_hip_auto_exposure(h_, &p));
+        if (p.mode == 1) ++exposure_calls_;
+    }
+    // ... or with every frame of the reference's loop, as upscale_every_frame below (after that frame's temporal denoise when both are on:
+    // p.source = 1 then meters its result), with `p`, reset_history = that frame's reset_accumulation and dt = the frame's time step,
+    // RenderConfiguration::time minus the previous frame's (0, a jump to the target, for the first frame and for a clock that stands)
+    void auto_exposure_every_frame(bool on, const RptrAutoExposureParams &p = auto_exposure_defaults()) {
+        auto_exposure_every_frame_ = on;
+        auto_exposure_params_ = p;
+    }
+    size_t readback_exposed(size_t buffer_size, unsigned char *buffer) { // sRGB RGBA8
+        uint32_t whc[3];
+        get_framebuffer_size(whc);
+        const size_t need = size_t(whc[0]) * whc[1] * 4;
+        if (buffer_size < need) return 0;
+        if (auto_exposure_every_frame_) flush_pipeline(); // (the frames in flight are collected, and exposed, first)
+        check(rptr_hip_readback_exposed_u8(h_, buffer, buffer_size));
+        return need;
+    }
+    // newest = false: what the call of the frame collected last left -- under a command stream that frame is frame_stats_delay frames
+    // behind, like stats(); nothing in flight is waited for (exposure_state_ready(): such a call has run)
+    RptrExposureState readback_exposure_state(bool newest = true) {
+        if (auto_exposure_every_frame_ && newest) flush_pipeline();
+        RptrExposureState st;
+        check(rptr_hip_readback_exposure_state(h_, &st));
+        return st;
+    }
+    bool exposure_state_ready() const { return exposure_calls_ > 0; }
     // Object motion (include/rptr_hip.h rptr_hip_object_motion): track_object_motion after set_scene; object_motion after the frame that
     // followed update_* + refit and before denoise_temporal / taa_upscale -- everything in flight is finished first. Returns the pixels
     // whose motion vector was rewritten (waits for the pass).
@@ -524,15 +568,23 @@ private:
         const int rc = rptr_hip_wait(h_, ticket_[i], &last_);
         if (rc == RPTR_OK) {
             ++stats_serial_;
-            frame_collected(slot_reset_[i]);
+            frame_collected(slot_reset_[i], slot_dt_[i]);
         }
         if (rc != RPTR_OK && !(rc == RPTR_E_INVALID && std::string(rptr_hip_last_error(h_)).find("not in flight") != std::string::npos)) check(rc);
     }
-    void frame_collected(bool restarted) { // upscale_every_frame, denoise_temporal_every_frame: the call that belongs to the frame just collected
+    // upscale_every_frame, denoise_temporal_every_frame, auto_exposure_every_frame: the calls that belong to the frame just collected
+    void frame_collected(bool restarted, float dt) {
         if (denoise_temporal_every_frame_) {
             RptrDenoiseTemporalParams p = denoise_temporal_params_;
             p.reset_history = restarted ? 1 : 0;
             check(rptr_hip_denoise_temporal(h_, &p));
+        }
+        if (auto_exposure_every_frame_) {
+            RptrAutoExposureParams p = auto_exposure_params_;
+            p.reset_history = restarted ? 1 : 0;
+            p.dt = dt;
+            check(rptr_hip_auto_exposure(h_, &p));
+            if (p.mode == 1) ++exposure_calls_;
         }
         if (!upscale_every_frame_) return;
         RptrTaaUpscaleParams p = taa_upscale_defaults();
@@ -573,6 +625,13 @@ private:
     bool upscale_every_frame_ = false;
     bool denoise_temporal_every_frame_ = false;
     RptrDenoiseTemporalParams denoise_temporal_params_{};
+    bool auto_exposure_every_frame_ = false;
+    RptrAutoExposureParams auto_exposure_params_{};
+    uint64_t exposure_calls_ = 0; // metering calls issued through this object (exposure_state_ready)
+    float slot_dt_[MAX_SWAP_BUFFERS] = {0.f, 0.f}; // the time step of the frame submitted on each swap index ...
+    float frame_dt_ = 0.f;                          // ... and of the frame begin_frame saw last: its RenderConfiguration::time minus the previous one's
+    double last_time_ = 0.0;
+    bool have_time_ = false;
     bool asynchronous_ = false;
     uint32_t frame_id_ = 0;
     uint64_t stats_serial_ = 0;

@@ -1,7 +1,7 @@
 // rptr_cli.cpp -- the reference's headless run modes through the C ABI (binary: bin/rptr_hip):
 //
 //   <scene> = the reference's .vks file (textures in <name>_textures/) or the flat dump scenes.py writes (.rpsc)
-//   rptr_hip <scene> --validation <prefix> [--validation-spp n] [--img w h] [--pfm] [--denoise iterations | --denoise-temporal iterations | --taa-upscale]
+//   rptr_hip <scene> --validation <prefix> [--validation-spp n] [--img w h] [--pfm] [--denoise iterations | --denoise-temporal iterations | --taa-upscale] [--auto-exposure]
 //   rptr_hip <scene.rpsc> --profiling <csv prefix> [--profiling-fps f] [--profiling-img <prefix>] [--profiling-frames n]
 //            [--animate-wave amplitude kx] [--synchronous] [--fly-through] [--frames-in-flight n [--frames-per-launch b]]
 //   common:  [--eye x y z] [--center x y z] [--up x y z] [--fov deg] [--variant gltf|diffuse|gltf-transmission] [--batch-spp k] [--every-frame]
@@ -86,8 +86,32 @@ static void denoise_temporal(rptr::RenderGroup &backend, bool reset_history) {
     p.reset_history = reset_history ? 1 : 0;
     backend.denoise_temporal(p);
 }
+// --auto-exposure (this host's; .ini: Tonemapping "auto exposure" = 1, "exposure key", "white balance"): every frame -- in a validation run
+// every image written -- goes through rptr_hip_auto_exposure as it is collected, after --denoise / --denoise-temporal (whose image it then
+// meters: source 1), with the configuration's tone mapping operator, dt = the animation time step and the history restarted with the
+// accumulation; the RGBA8 images written (--png) are the exposed ones, the float images stay what they were, and the frame log on stdout
+// gets a line "auto-exposure: frame n ev e target t" per frame. Not with --taa-upscale (the upscaler reads the frame's own RGBA8) or
+// several devices.
+static bool g_auto_exposure = false;
+static RptrAutoExposureParams g_auto_exposure_params;
+static const char *auto_exposure_refusal(size_t n_devices) {
+    if (!g_auto_exposure) return nullptr;
+    if (g_taa_upscale) return "--auto-exposure and --taa-upscale cannot be combined: the upscaler reads the frame's own RGBA8 image, not the exposed one\n";
+    if (n_devices > 1) return "--auto-exposure needs one device (rptr_hip_auto_exposure refuses world_size > 1)\n";
+    return nullptr;
+}
+static void print_exposure(const RptrExposureState &st, int frame) {
+    std::printf("auto-exposure: frame %d ev %.6f target %.6f\n", frame, st.ev, st.target_ev);
+}
+static void auto_exposure(rptr::RenderGroup &backend, bool reset_history, float dt, int frame) {
+    RptrAutoExposureParams p = g_auto_exposure_params;
+    p.reset_history = reset_history ? 1 : 0;
+    p.dt = dt;
+    backend.auto_exposure(p);
+    print_exposure(backend.readback_exposure_state(), frame);
+}
 static void save_image(rptr::RenderGroup &backend, OutputFormat format, const std::string &prefix, int number, const std::string &suffix, int width, int height,
-                       std::vector<float> &img) {
+                       std::vector<float> &img, bool expose_now = false) {
     char name[32];
     std::snprintf(name, sizeof(name), "_%04d", number);
     const std::string base = prefix + name + suffix;
@@ -98,7 +122,14 @@ static void save_image(rptr::RenderGroup &backend, OutputFormat format, const st
         backend.denoise(dp);
     }
     const bool denoised = g_denoise_iterations > 0 || g_denoise_temporal_iterations > 0;
-    if (format == FORMAT_PNG && g_taa_upscale) {
+    // (expose_now: a validation run's still image, metered as it is written -- no adaptation; with --denoise the denoised image exists
+    // only from here on, so the frame loops leave the call to this function as well)
+    if (g_auto_exposure && (expose_now || g_denoise_iterations > 0)) auto_exposure(backend, true, 0.f, number);
+    if (format == FORMAT_PNG && g_auto_exposure) {
+        std::vector<unsigned char> rgba8((size_t)width * height * 4);
+        if (backend.readback_exposed(rgba8.size(), rgba8.data()) != rgba8.size()) throw std::runtime_error("read-back failed");
+        ok = rptr::write_png(base, (unsigned)width, (unsigned)height, 4, rgba8.data());
+    } else if (format == FORMAT_PNG && g_taa_upscale) {
         std::vector<unsigned char> rgba8((size_t)width * height * 16);
         if (backend.readback_upscaled(rgba8.size(), rgba8.data()) != rgba8.size()) throw std::runtime_error("read-back failed");
         ok = rptr::write_png(base, 2u * (unsigned)width, 2u * (unsigned)height, 4, rgba8.data());
@@ -221,6 +252,7 @@ int main(int argc, char **argv) {
         else if (a == "--denoise") { need(1); g_denoise_iterations = std::atoi(argv[++i]); if (g_denoise_iterations < 1 || g_denoise_iterations > 5) { std::fprintf(stderr, "--denoise takes 1..5 iterations\n"); return 2; } }
         else if (a == "--denoise-temporal") { need(1); g_denoise_temporal_iterations = std::atoi(argv[++i]); if (g_denoise_temporal_iterations < 1 || g_denoise_temporal_iterations > 5) { std::fprintf(stderr, "--denoise-temporal takes 1..5 iterations\n"); return 2; } }
         else if (a == "--taa-upscale") g_taa_upscale = true;
+        else if (a == "--auto-exposure") g_auto_exposure = true;
         else if (a == "--object-motion") g_object_motion = true;
         else if (a == "--img") { need(2); width = std::atoi(argv[++i]); height = std::atoi(argv[++i]); }
         else if (a == "--eye") { vec3(eye); got_eye = true; }
@@ -388,6 +420,10 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "--taa-upscale needs one device (rptr_hip_taa_upscale refuses world_size > 1)\n");
         return 2;
     }
+    if (const char *why = auto_exposure_refusal(devices.size())) {
+        std::fputs(why, stderr);
+        return 2;
+    }
     if (g_object_motion) {
         const size_t n = scene_path.size();
         const char *why = nullptr;
@@ -407,7 +443,7 @@ int main(int argc, char **argv) {
     if (want_help) scene_path.clear(); // prints the usage
     if (scene_path.empty() || (int)validation + (int)profiling + (int)data_capture != 1 || batch_spp < 1 || width < 1 || height < 1 || (profiling && profiling_frames < 1)) {
         std::fprintf(stderr, "usage: rptr_hip <scene.rpsc> (--validation <prefix> [--validation-spp n] | --profiling <csv prefix> [--profiling-fps f] "
-                             "[--profiling-img <prefix>] [--keyframe [len:]file.ini ...] [--profiling-count n] [--synchronous] [--fly-through] [--frames-in-flight n [--frames-per-launch b]] [--animate-wave a k]) [--img w h] [--denoise iterations | --denoise-temporal iterations | --taa-upscale] [--object-motion] [--eye x y z] [--center x y z] "
+                             "[--profiling-img <prefix>] [--keyframe [len:]file.ini ...] [--profiling-count n] [--synchronous] [--fly-through] [--frames-in-flight n [--frames-per-launch b]] [--animate-wave a k]) [--img w h] [--denoise iterations | --denoise-temporal iterations | --taa-upscale] [--auto-exposure] [--object-motion] [--eye x y z] [--center x y z] "
                              "[--up x y z] [--fov deg] [--variant gltf|diffuse] [--batch-spp k] [--every-frame] [--exr|--pfm|--png] [--config file.ini ...] [--sky-data <dir of the Hosek-Wilkie data headers>]\n"
                              "       rptr_hip <scene.rpsc> --data-capture <prefix> [--data-capture-spp n] [--data-capture-no-rgba] [--data-capture-no-aovs] "
                              "[--data-capture-albedo-roughness] [--data-capture-normal-depth] [--data-capture-motion] [--keyframe ...]   (EXR images per keyframe)\n"
@@ -477,6 +513,18 @@ int main(int argc, char **argv) {
         if (!got_batch_spp) batch_spp = std::max(1, base.params.batch_spp);
         if (!got_variant && base.variant >= 0) variant = base.variant;
         if (upscale >= 1) base.params.render_upscale_factor = upscale;
+        if (base.auto_exposure >= 0) g_auto_exposure = g_auto_exposure || base.auto_exposure != 0; // (.ini "auto exposure": the flag's equal)
+        if (const char *why = auto_exposure_refusal(devices.size())) {
+            std::fputs(why, stderr);
+            return 2;
+        }
+        g_auto_exposure_params = rptr::RenderHip::auto_exposure_defaults();
+        g_auto_exposure_params.source = g_denoise_iterations > 0 || g_denoise_temporal_iterations > 0 ? 1 : 0;
+        g_auto_exposure_params.tone_mapping_mode = base.params.early_tone_mapping_mode;
+        if (!std::isnan(base.exposure_key)) g_auto_exposure_params.key = base.exposure_key;
+        for (int k = 0; k < 3; ++k)
+            if (!std::isnan(base.white_balance[k])) g_auto_exposure_params.white_balance[k] = base.white_balance[k];
+        const bool expose_frames = g_auto_exposure && g_denoise_iterations == 0; // (--denoise runs when an image is written: save_image exposes there)
         if (frames_in_flight == 1) synchronous = true; // (one frame context: nothing to overlap)
         // frame contexts: the reference's two swap buffers; what --frames-in-flight asks for; four for a queued --validation accumulation
         // (its launch sequences are independent of the display: the deeper queue is what fills the GPU)
@@ -598,7 +646,7 @@ int main(int argc, char **argv) {
                         gpu_ms += st.render_time;
                         if (accumulated >= target_spp || every_frame) {
                             const auto w0 = std::chrono::steady_clock::now();
-                            save_image(backend, format, validation_prefix, accumulated, "", width, height, img);
+                            save_image(backend, format, validation_prefix, accumulated, "", width, height, img, true);
                             image_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
                         }
                     }
@@ -621,7 +669,7 @@ int main(int argc, char **argv) {
                 gpu_ms += st.render_time;
                 if (accumulated >= target_spp || every_frame) {
                     const auto w0 = std::chrono::steady_clock::now();
-                    save_image(backend, format, validation_prefix, accumulated, "", width, height, img);
+                    save_image(backend, format, validation_prefix, accumulated, "", width, height, img, true);
                     image_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
                 }
             }
@@ -802,7 +850,7 @@ int main(int argc, char **argv) {
             // reprojection_mode 2 folds each frame into the one before it: one frame per launch sequence (include/rptr_hip.h)
             bool realtime = base.params.reprojection_mode == 2;
             for (const rptr::HostConfig &st : frames) realtime = realtime || st.params.reprojection_mode == 2;
-            if (realtime || g_taa_upscale || g_denoise_temporal_iterations > 0) frames_per_launch = 1; // (the upscaler and the temporal denoiser read the AOV images, which are those of a sequence's last frame)
+            if (realtime || g_taa_upscale || g_denoise_temporal_iterations > 0 || expose_frames) frames_per_launch = 1; // (auto-exposure meters the last frame of a sequence only; (the upscaler and the temporal denoiser read the AOV images, which are those of a sequence's last frame)
             struct Pending {
                 rptr::RenderGroup::Sequence q;
                 int first;
@@ -830,6 +878,7 @@ int main(int argc, char **argv) {
                     const rptr::RenderStats st = backend.collect_frame(p.q, k);
                     if (g_taa_upscale) backend.taa_upscale(fp.reset);
                     if (g_denoise_temporal_iterations > 0) denoise_temporal(backend, fp.reset);
+                    if (expose_frames) auto_exposure(backend, fp.reset, p.first + k ? dt : 0.f, p.first + k + 1);
                     gpu_ms += st.render_time;
                     const auto now = std::chrono::steady_clock::now();
                     std::fprintf(csv, "%d,%d,%d,%g,%g\n", ++collected, fp.keyframe_no, fp.accumulated, st.render_time, std::chrono::duration<double, std::milli>(now - last).count());
@@ -867,6 +916,7 @@ int main(int argc, char **argv) {
         // (--object-motion: the pass goes between a frame and its consumer, so the loop below renders one frame at a time and issues both)
         backend.upscale_every_frame(g_taa_upscale && !g_object_motion); // (issued as each frame is collected: render_group.hpp frame)
         backend.denoise_temporal_every_frame(g_denoise_temporal_iterations > 0 && !g_object_motion, denoise_temporal_params());
+        backend.auto_exposure_every_frame(expose_frames && !g_object_motion, g_auto_exposure_params); // (dt: the step of RenderConfiguration::time)
         rptr::CommandStream *const cmd_stream = synchronous || g_object_motion ? nullptr : &display_stream;
         if (!rest.empty() || fly_through) { // (a short warm-up when the run is a measurement: the adaptive tail hand-over settles in two frames)
             apply_key(plan[0].key);
@@ -895,7 +945,10 @@ int main(int argc, char **argv) {
                 backend.object_motion();
                 if (g_taa_upscale) backend.taa_upscale(frame == 0);
                 if (g_denoise_temporal_iterations > 0) denoise_temporal(backend, frame == 0);
-            }
+                if (expose_frames) auto_exposure(backend, frame == 0, frame ? dt : 0.f, frame + 1);
+            } else if (expose_frames && backend.exposure_state_ready())
+                // (a synchronous frame's own call; under the command stream the call of the frame collected last, two frames back, like `st`)
+                print_exposure(backend.readback_exposure_state(false), cmd_stream ? std::max(1, frame + 1 - (int)rptr::RenderHip::MAX_SWAP_BUFFERS) : frame + 1);
             gpu_ms += st.render_time;
             const auto now = std::chrono::steady_clock::now();
             const double app_ms = std::chrono::duration<double, std::milli>(now - last).count();
