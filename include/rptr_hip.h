@@ -479,6 +479,56 @@ typedef struct RptrLightSource { /* 48 bytes, one per entry of RptrSceneDesc.lig
 int rptr_hip_set_light_sources(rptr_hip_t *h, const RptrLightSource *sources, uint32_t count);
 int rptr_hip_readback_lights(rptr_hip_t *h, RptrTriLightData *out, uint32_t count);
 
+/* ---- skinned meshes: bones in, float positions and shading normals out on the device. The reference animates "with a compute shader
+ * that writes the float vertex buffer" (render_vulkan.cpp:2834-2840) and ships the buffer, not the shader; this is that piece
+ * (csrc/skin.h rp_k_skin): linear blend skinning with at most FOUR influences per vertex. The host sends 48 bytes per bone instead of 36
+ * bytes per triangle, and the shading normals of the deformed mesh follow, which rptr_hip_update_vertices cannot make them do (it leaves
+ * the oct-encoded vertex normals set_scene uploaded where they are).
+ * rptr_hip_set_skin(h, geometry, vertices, num_vertices): after set_scene, on a geometry of a mesh flagged RPTR_MESH_DYNAMIC /
+ * _SUBTLY_DYNAMIC. One RptrSkinVertex per UNROLLED vertex (three per triangle, the order of rptr_hip_update_vertices: a vertex shared
+ * by several triangles is skinned once per corner), num_vertices == 3 * triangles. Binds the geometry: its REST POSE is its float
+ * positions at the time of the call (a device copy), its rest normals are the normal halves of its qnrm_uv words as uploaded
+ * (dequantize.glsl:23-41). Checked on the host before anything is queued: RPTR_E_INVALID for a NULL handle, a call before set_scene, a
+ * geometry that is not dynamic, num_vertices != 3 * triangles, a bone index >= RPTR_MAX_BONES, weights that do not sum to 65535 -- the
+ * message names the first offending vertex. (NULL, 0) unbinds: positions and normals stay as last written. A new set_scene drops every
+ * binding and resets the bone table to identity. The call waits for the frames in flight.
+ * rptr_hip_update_bones[_device](h, first_bone, count, transforms12): `count` row-major 3x4 matrices (the layout of
+ * RptrInstanceDesc.transform) that map the mesh's rest object space to its posed object space, staged into rows [first_bone,
+ * first_bone + count) of the handle's bone table: RPTR_MAX_BONES rows, identity after set_scene. The host form refuses a bad range, NULL
+ * and a matrix that is not finite (RPTR_E_INVALID, nothing staged). The _device form reads DEVICE memory, ordered on the backend's
+ * stream, no host synchronisation; it cannot report a bad matrix (see "rejected vertices").
+ * rptr_hip_skin(h): for every bound geometry, one kernel on the backend's stream that writes the master copy's float positions and, for
+ * a geometry with normals, its skinned normal words; then exactly what rptr_hip_update_vertices_device does per geometry. The host calls
+ * rptr_hip_refit afterwards as always: refit or device rebuild, the scene copy of every frame context, registered light sources
+ * (rptr_hip_set_light_sources: lights follow ONLY with registered sources, as for update_vertices) and object motion follow without
+ * knowing that anything changed; the refit also writes the skinned normal words into the shading records (csrc/skin.h
+ * rp_k_refit_normals -- launched only for meshes that have a skinned geometry with normals; the qnrm_uv stream itself, its uv halves and
+ * the alpha test that reads them are untouched). No kernel of a frame changes. Nothing bound: RPTR_E_INVALID.
+ * Arithmetic: binary32 throughout, every product and sum rounded on its own (no contraction), IEEE division.
+ *   w_k     = float(weight[k]) / 65535.0f
+ *   B[r][c] = ((w0 M0[r][c] + w1 M1[r][c]) + w2 M2[r][c]) + w3 M3[r][c]                 (a zero weight's bone is still read)
+ *   p'[r]   = (B[r][0] x + B[r][1] y) + (B[r][2] z + B[r][3])                           (the placement rule of the moving lights)
+ *   n'[r]   = (C[r][0] nx + C[r][1] ny) + C[r][2] nz, C the cofactor matrix of A = the 3x3 part of B: rows cross(A1, A2), cross(A2, A0),
+ *             cross(A0, A1); n' is negated when det = A0 . C0 = (x x' + y y') + z z' is negative (a mirroring bone)
+ *   word    = quantize_normal(n') (librender/quantize.h:21-35; it divides by the L1 norm: nothing is normalised first)
+ * Identity bones reproduce the rest pose ONLY TO ROUNDING: the weights are rounded quotients, and so is their sum.
+ * Rejected vertices: a vertex whose skinned position is not finite keeps the position and the normal it had and is counted:
+ * rptr_hip_get_option(h, "skin_vertices_rejected") (read-only, since set_scene; reading it waits for the backend's stream). A normal
+ * that is not finite or all zero keeps its previous word.
+ * rptr_hip_readback_skinned: the master copy's current positions (3 floats per vertex) and normal words (one uint32 per vertex: the
+ * normal half of a qnrm_uv word) of a bound geometry, after pending work; either pointer may be NULL. normal_words on a geometry without normals:
+ * RPTR_E_INVALID. world_size > 1: every rank holds the whole scene, call on each. */
+#define RPTR_MAX_BONES 4096
+typedef struct RptrSkinVertex { /* 16 bytes, one per UNROLLED vertex: 3 per triangle, the order of rptr_hip_update_vertices */
+    uint16_t bone[4];           /* rows of the handle's bone table, < RPTR_MAX_BONES */
+    uint16_t weight[4];         /* unorm16, the four must sum to 65535; a zero weight's bone is still read */
+} RptrSkinVertex;
+int rptr_hip_set_skin(rptr_hip_t *h, uint32_t geometry, const RptrSkinVertex *vertices, uint32_t num_vertices);
+int rptr_hip_update_bones(rptr_hip_t *h, uint32_t first_bone, uint32_t count, const float *transforms12);
+int rptr_hip_update_bones_device(rptr_hip_t *h, uint32_t first_bone, uint32_t count, const float *device_transforms12);
+int rptr_hip_skin(rptr_hip_t *h);
+int rptr_hip_readback_skinned(rptr_hip_t *h, uint32_t geometry, float *xyz, uint32_t *normal_words, uint32_t num_vertices);
+
 /* ---- RenderBackend::params / lighting_params / update_config
  * (render_backend.h:69-76, render_vulkan.cpp:2943-2959) */
 int rptr_hip_set_params(rptr_hip_t *h, const RptrRenderParams *params,

@@ -249,6 +249,13 @@ class LightSource(C.Structure):  # include/rptr_hip.h RptrLightSource: where one
                 ("triangle", C.c_uint32)]
 
 
+MAX_BONES = 4096  # RPTR_MAX_BONES
+
+
+class SkinVertex(C.Structure):  # include/rptr_hip.h RptrSkinVertex: the influences of one unrolled vertex
+    _fields_ = [("bone", C.c_uint16 * 4), ("weight", C.c_uint16 * 4)]
+
+
 class SurfaceHit(C.Structure):  # include/rptr_hip.h RptrSurfaceHit: six 16-byte rows per surface query
     _fields_ = [("position", C.c_float * 3), ("t", C.c_float),
                 ("geo_normal", C.c_float * 3), ("instance_geometry", C.c_int32),
@@ -297,6 +304,7 @@ assert C.sizeof(TaaUpscaleParams) == 16
 assert C.sizeof(AutoExposureParams) == 64
 assert C.sizeof(ExposureState) == 32 + 1024
 assert C.sizeof(LightSource) == 48
+assert C.sizeof(SkinVertex) == 16
 assert C.sizeof(DenoiseParams) == 32
 assert C.sizeof(DenoiseTemporalParams) == 64
 assert C.sizeof(BaseMaterial) == 80
@@ -316,7 +324,8 @@ COMM_IPC_BYTES = 256  # RPTR_COMM_IPC_BYTES
 EXPORTED_SYMBOLS = [
     "rptr_hip_create", "rptr_hip_abi_version", "rptr_hip_build_id", "rptr_hip_bvh_build_info", "rptr_hip_traversal_preset", "rptr_hip_destroy", "rptr_hip_last_error", "rptr_hip_name", "rptr_hip_set_stream",
     "rptr_hip_initialize", "rptr_hip_set_scene", "rptr_hip_update_vertices", "rptr_hip_update_vertices_device", "rptr_hip_refit", "rptr_hip_set_params",
-    "rptr_hip_render", "rptr_hip_render_async", "rptr_hip_render_batch_async", "rptr_hip_render_batch_cameras_async", "rptr_hip_wait", "rptr_hip_set_stage_timing", "rptr_hip_set_freeze_frame", "rptr_hip_set_option", "rptr_hip_get_option", "rptr_hip_option_count", "rptr_hip_option_name", "rptr_hip_set_rng_variant", "rptr_hip_set_bvh_policy", "rptr_hip_bvh_rebuild_count", "rptr_hip_update_instances", "rptr_hip_update_instances_device", "rptr_hip_set_tlas_policy", "rptr_hip_tlas_rebuild_count", "rptr_hip_set_light_sources", "rptr_hip_readback_lights", "rptr_hip_get_framebuffer_size", "rptr_hip_readback_f32", "rptr_hip_readback_u8", "rptr_hip_readback_aov",
+    "rptr_hip_render", "rptr_hip_render_async", "rptr_hip_render_batch_async", "rptr_hip_render_batch_cameras_async", "rptr_hip_wait", "rptr_hip_set_stage_timing", "rptr_hip_set_freeze_frame", "rptr_hip_set_option", "rptr_hip_get_option", "rptr_hip_option_count", "rptr_hip_option_name", "rptr_hip_set_rng_variant", "rptr_hip_set_bvh_policy", "rptr_hip_bvh_rebuild_count", "rptr_hip_update_instances", "rptr_hip_update_instances_device", "rptr_hip_set_tlas_policy", "rptr_hip_tlas_rebuild_count", "rptr_hip_set_light_sources", "rptr_hip_readback_lights",
+    "rptr_hip_set_skin", "rptr_hip_update_bones", "rptr_hip_update_bones_device", "rptr_hip_skin", "rptr_hip_readback_skinned", "rptr_hip_get_framebuffer_size", "rptr_hip_readback_f32", "rptr_hip_readback_u8", "rptr_hip_readback_aov",
     "rptr_hip_denoise_defaults", "rptr_hip_denoise", "rptr_hip_readback_denoised_f32", "rptr_hip_readback_denoised_u8",
     "rptr_hip_denoise_temporal_defaults", "rptr_hip_denoise_temporal", "rptr_hip_readback_denoise_history_f32",
     "rptr_hip_taa_upscale_defaults", "rptr_hip_taa_upscale", "rptr_hip_readback_upscaled_u8",

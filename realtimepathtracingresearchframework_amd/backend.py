@@ -94,6 +94,11 @@ def load_library(path=None):
     L.rptr_hip_tlas_rebuild_count.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.rptr_hip_set_light_sources.argtypes = [vp, vp, C.c_uint32]
     L.rptr_hip_readback_lights.argtypes = [vp, vp, C.c_uint32]
+    L.rptr_hip_set_skin.argtypes = [vp, C.c_uint32, vp, C.c_uint32]
+    L.rptr_hip_update_bones.argtypes = [vp, C.c_uint32, C.c_uint32, vp]
+    L.rptr_hip_update_bones_device.argtypes = [vp, C.c_uint32, C.c_uint32, vp]
+    L.rptr_hip_skin.argtypes = [vp]
+    L.rptr_hip_readback_skinned.argtypes = [vp, C.c_uint32, vp, vp, C.c_uint32]
     L.rptr_hip_bvh_build_info.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.rptr_hip_traversal_preset.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.rptr_hip_get_framebuffer_size.argtypes = [vp, C.POINTER(C.c_uint32)]
@@ -260,6 +265,7 @@ class RenderHip:
         desc = scene.desc()
         self._check(self._L.rptr_hip_set_scene(self._h, C.byref(desc)))
         self._num_lights = int(desc.num_lights)
+        self._geometries = [(int(g.num_tris), bool(g.has_normals and g.qnrm_uv is not None)) for g in scene.geometries]  # (readback_skinned)
         self.update_config(scene)
 
     def update_config(self, scene_or_params):
@@ -754,6 +760,42 @@ class RenderHip:
         out = np.zeros((n, 4, 3), dtype=np.float32)
         self._check(self._L.rptr_hip_readback_lights(self._h, out.ctypes.data_as(C.c_void_p), n))
         return out
+
+    # ---- skinned meshes (rptr_hip_set_skin / update_bones / skin): bones in, positions and shading normals out on the device
+    def set_skin(self, geometry, bones=None, weights=None):
+        """Bind one geometry of a dynamic mesh: bones and weights are (n, 4) uint16, one row per UNROLLED vertex (n = 3 * triangles);
+        a row's weights are unorm16 and sum to 65535. The rest pose is the geometry's positions now. bones=None unbinds."""
+        if bones is None:
+            self._check(self._L.rptr_hip_set_skin(self._h, int(geometry), None, 0))
+            return
+        rec = np.concatenate([np.ascontiguousarray(bones, dtype=np.uint16).reshape(-1, 4), np.ascontiguousarray(weights, dtype=np.uint16).reshape(-1, 4)], axis=1)
+        rec = np.ascontiguousarray(rec)  # RptrSkinVertex: bone[4], weight[4]
+        self._check(self._L.rptr_hip_set_skin(self._h, int(geometry), rec.ctypes.data_as(C.c_void_p) if len(rec) else None, len(rec)))
+
+    def update_bones(self, first, transforms: np.ndarray):
+        """Stage bone matrices [first, first + k): transforms is (k, 3, 4) or (k, 12) float32, row-major 3x4, rest object space to posed
+        object space. The next skin() reads them."""
+        t = np.ascontiguousarray(transforms, dtype=np.float32).reshape(-1, 12)
+        self._check(self._L.rptr_hip_update_bones(self._h, int(first), t.shape[0], t.ctypes.data_as(C.c_void_p)))
+
+    def update_bones_device(self, first, device_ptr, count):
+        """same from a device buffer (12 float32 per bone) written on the backend's stream."""
+        self._check(self._L.rptr_hip_update_bones_device(self._h, int(first), int(count), C.c_void_p(device_ptr)))
+
+    def skin(self):
+        """Skin every bound geometry on the device; refit() afterwards, as after update_vertices."""
+        self._check(self._L.rptr_hip_skin(self._h))
+
+    def readback_skinned(self, geometry, num_vertices=None):
+        """(xyz (n, 3) float32, normal words (n,) uint32 or None for a geometry without normals) of a bound geometry, after pending work."""
+        geoms = getattr(self, "_geometries", [])
+        tris, has_normals = geoms[int(geometry)] if 0 <= int(geometry) < len(geoms) else (0, False)
+        n = 3 * tris if num_vertices is None else int(num_vertices)
+        xyz = np.zeros((n, 3), dtype=np.float32)
+        words = np.zeros(n, dtype=np.uint32) if has_normals else None
+        self._check(self._L.rptr_hip_readback_skinned(self._h, int(geometry), xyz.ctypes.data_as(C.c_void_p),
+                                                      words.ctypes.data_as(C.c_void_p) if has_normals else None, n))
+        return xyz, words
 
     def set_rng_variant(self, rng_variant, table=None):
         """RenderBackendOptions::rng_variant (render_params.glsl.h:34-37,76) + the table upload of the point set's render extension

@@ -87,6 +87,16 @@ int rptr_hip_get_option(const rptr_hip_t *h, const char *key, int64_t *out_value
         *out_value = (int64_t)n;
         return RPTR_OK;
     }
+    if (h && key && out_value && !strcmp(key, "skin_vertices_rejected")) { // (read-only: vertices rptr_hip_skin left alone because their new position
+        uint32_t n = 0;                                                    // was not finite, since set_scene; waits for the backend's stream)
+        if (h->have_scene && h->skin.d_rejected) {
+            if (hipSetDevice(h->device) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess ||
+                hipMemcpy(&n, h->skin.d_rejected, sizeof(n), hipMemcpyDeviceToHost) != hipSuccess)
+                return fail(nullptr, RPTR_E_HIP, "reading the counter failed");
+        }
+        *out_value = (int64_t)n;
+        return RPTR_OK;
+    }
     if (h && key && out_value && !strcmp(key, "object_motion_pixels")) { // (read-only: pixels the last rptr_hip_object_motion rewrote; waits for the
         uint32_t n = 0;                                                  // backend's stream)
         if (h->have_scene && h->om.d_rewritten && h->om.counted) {

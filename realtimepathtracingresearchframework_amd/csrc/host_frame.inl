@@ -474,6 +474,10 @@ static int follow_master_scene(rptr_hip_t *h, FrameCtx &c, SceneCopy &scn) {
             if (scn.dynpos[gi])
                 HIP_TRY(h, hipMemcpyAsync(scn.dynpos[gi], h->master.dynpos[gi], (size_t)h->geom_tris[gi] * 9 * sizeof(float), hipMemcpyDeviceToDevice,
                                           h->stream));
+        for (size_t gi = 0; gi < scn.dynnrm.size(); ++gi) // ... with the skinned normal words of the geometries that have them (skin.h)
+            if (scn.dynnrm[gi])
+                HIP_TRY(h, hipMemcpyAsync(scn.dynnrm[gi], h->master.dynnrm[gi], (size_t)h->geom_tris[gi] * 3 * sizeof(uint32_t), hipMemcpyDeviceToDevice,
+                                          h->stream));
         if (scn.inst_version != h->inst_version && h->num_instances) // ... and so do the staged instance transforms (rptr_hip_update_instances)
             HIP_TRY(h, hipMemcpyAsync(scn.inst_xf, h->master.inst_xf, (size_t)96 * h->num_instances, hipMemcpyDeviceToDevice, h->stream));
     }

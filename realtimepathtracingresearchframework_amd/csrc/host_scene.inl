@@ -427,6 +427,8 @@ static int scene_copy_build(rptr_hip *h, const RptrSceneDesc *s, const SceneTabl
     sc.dynpos.assign(s->num_geometries, nullptr);
     sc.mesh_dirty.assign(s->num_meshes, 0);
     sc.mesh_dyn.assign(s->num_meshes, nullptr);
+    sc.dynnrm.assign(s->num_geometries, nullptr); // (skinned normal words: made by rptr_hip_set_skin)
+    sc.mesh_nrm.assign(s->num_meshes, nullptr);
     for (uint32_t m = 0; m < s->num_meshes; ++m) {
         const RptrMeshDesc &mesh = s->meshes[m];
         if (!(mesh.dynamic & kMeshDeforms)) continue;
@@ -556,6 +558,17 @@ int rptr_hip_set_scene(rptr_hip_t *h, const RptrSceneDesc *s) {
     }
     if ((rc = dev_alloc(h, &h->d_inst_rejected, 1, &h->scene_allocs))) return rc;
     HIP_TRY(h, hipMemset(h->d_inst_rejected, 0, sizeof(uint32_t)));
+    // ---- skinned meshes: no binding survives a new scene, the bone table is identity again
+    {
+        h->skin = decltype(h->skin)();
+        h->skin.geom_qnu = d_qnu;
+        h->skin.geom_normals.assign(s->num_geometries, 0);
+        for (uint32_t g = 0; g < s->num_geometries; ++g) h->skin.geom_normals[g] = s->geometries[g].has_normals && d_qnu[g] ? 1 : 0;
+        h->skin.bound.assign(s->num_geometries, 0);
+        h->skin.records.assign(s->num_geometries, nullptr);
+        h->skin.rest_pos.assign(s->num_geometries, nullptr);
+        h->skin.rest_nrm.assign(s->num_geometries, nullptr); // (the table itself is made by the first call that needs it: skin_bone_table)
+    }
     // ---- refit tables, then the master copy
     if ((rc = scene_refit_tables(h, T))) return rc;
     h->rebuild_epoch.assign(h->meshes.size(), 0);
@@ -726,6 +739,15 @@ static int build_shade_records(rptr_hip *h, SceneCopy &sc, int only_mesh, hipStr
     }
     HIP_TRY(h, hipGetLastError());
     return RPTR_OK;
+}
+
+// skinned meshes (skin.h): the skinned normal words of mesh m go into its shading records. A mesh none of whose geometries was ever bound
+// (or has normals) launches nothing.
+static void refit_mesh_normals(rptr_hip *h, SceneCopy &sc, size_t m, hipStream_t st) {
+    const MeshRt &mr = h->meshes[m];
+    if (m >= sc.mesh_nrm.size() || !sc.mesh_nrm[m] || mr.tri_count <= 0) return;
+    hipLaunchKernelGGL(rp_k_refit_normals, dim3(grid_for(h, (size_t)mr.tri_count)), dim3(256), 0, st, sc.tris, sc.shade, (uint32_t)mr.tri_base, (uint32_t)mr.tri_count,
+                       sc.mesh_nrm[m]);
 }
 
 // the depth levels of dynamic mesh m of one scene copy, deepest first: a launch per deep level, the shallow ones (at most 4^5 + ... + 1
@@ -962,12 +984,14 @@ static bool refit_scene_copy(rptr_hip *h, SceneCopy &sc, bool all_dynamic, hipSt
         if (mr.tri_count)
             hipLaunchKernelGGL(rp_k_refit_tris, dim3(grid_for(h, (size_t)mr.tri_count)), dim3(256), 0, st, sc.tris, sc.tri_box, sc.shade, (uint32_t)mr.tri_base,
                                (uint32_t)mr.tri_count, sc.mesh_dyn[m]);
+        refit_mesh_normals(h, sc, m, st);
         sc.mesh_dirty[m] = 0;
         if (sc.built_epoch[m] != h->rebuild_epoch[m]) {
             const int rc = lbvh_rebuild(h, sc, m, st, with_top);
             if (rc == RPTR_OK) {
                 sc.built_epoch[m] = h->rebuild_epoch[m];
                 (void)build_shade_records(h, sc, (int)m, st); // the rebuild reordered the mesh's triangles: its shading records follow
+                refit_mesh_normals(h, sc, m, st);             // ... and they read the rest normals again: the skinned ones go back in
             } else {
                 if (err && *err == RPTR_OK) *err = rc;
                 refit_mesh_levels(h, sc, m, st, with_top);
@@ -1168,5 +1192,157 @@ int rptr_hip_readback_lights(rptr_hip_t *h, RptrTriLightData *out, uint32_t coun
     }
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     if (count) HIP_TRY(h, hipMemcpy(out, h->master.dscene.lights, (size_t)count * sizeof(RptrTriLightData), hipMemcpyDeviceToHost));
+    return RPTR_OK;
+}
+
+// ---- skinned meshes (include/rptr_hip.h "skinned meshes", skin.h)
+// the bone table (identity) and the counter of rejected vertices, made by the first set_skin / update_bones after a set_scene: a scene
+// that is never skinned allocates what it always did
+static int skin_bone_table(rptr_hip *h) {
+    int rc;
+    auto &sk = h->skin;
+    if (!sk.d_bones) {
+        std::vector<float> identity((size_t)12 * RPTR_MAX_BONES, 0.0f);
+        for (size_t b = 0; b < RPTR_MAX_BONES; ++b) identity[12 * b] = identity[12 * b + 5] = identity[12 * b + 10] = 1.0f;
+        if ((rc = dev_upload(h, &sk.d_bones, identity.size(), identity.data(), hipMemcpyHostToDevice, &h->scene_allocs))) return rc;
+    }
+    if (!sk.d_rejected) {
+        if ((rc = dev_alloc(h, &sk.d_rejected, 1, &h->scene_allocs))) return rc;
+        HIP_TRY(h, hipMemset(sk.d_rejected, 0, sizeof(uint32_t)));
+    }
+    return RPTR_OK;
+}
+// one scene copy's skinned normal words of `geometry` (made once, starting from the rest normals) and the table of its mesh
+static int skin_copy_normals(rptr_hip *h, SceneCopy &sc, uint32_t geometry) {
+    int rc;
+    const size_t n = (size_t)h->geom_tris[geometry] * 3;
+    if (!sc.dynnrm[geometry]) {
+        uint32_t *d = nullptr;
+        if ((rc = dev_upload(h, &d, n, h->skin.rest_nrm[geometry], hipMemcpyDeviceToDevice, &h->scene_allocs))) return rc;
+        sc.dynnrm[geometry] = d;
+    }
+    const int m = h->geom_mesh[geometry];
+    std::vector<const uint32_t *> table;
+    for (size_t g = 0; g < h->geom_mesh.size(); ++g)
+        if (h->geom_mesh[g] == m) table.push_back(sc.dynnrm[g]); // (a mesh's geometries are consecutive: the table's order is the mesh's)
+    if (!sc.mesh_nrm[(size_t)m]) return dev_upload(h, &sc.mesh_nrm[(size_t)m], table.size(), table.data(), hipMemcpyHostToDevice, &h->scene_allocs);
+    HIP_TRY(h, hipMemcpy(sc.mesh_nrm[(size_t)m], table.data(), table.size() * sizeof(table[0]), hipMemcpyHostToDevice));
+    return RPTR_OK;
+}
+int rptr_hip_set_skin(rptr_hip_t *h, uint32_t geometry, const RptrSkinVertex *vertices, uint32_t num_vertices) {
+    if (!h) return fail(nullptr, RPTR_E_INVALID, "NULL handle");
+    if (!h->have_scene) return fail(h, RPTR_E_INVALID, "set_skin before set_scene");
+    if (geometry >= h->master.dynpos.size() || !h->master.dynpos[geometry])
+        return fail(h, RPTR_E_INVALID, "geometry %u does not belong to a dynamic mesh (RptrMeshDesc.dynamic)", geometry);
+    if ((vertices == nullptr) != (num_vertices == 0)) return fail(h, RPTR_E_INVALID, "vertices and num_vertices must both be given, or NULL and 0 to unbind");
+    const uint32_t n = 3u * h->geom_tris[geometry];
+    if (vertices) {
+        if (num_vertices != n) return fail(h, RPTR_E_INVALID, "geometry %u has %u unrolled vertices, got %u", geometry, n, num_vertices);
+        for (uint32_t v = 0; v < n; ++v) {
+            uint32_t sum = 0;
+            for (int k = 0; k < 4; ++k) {
+                if (vertices[v].bone[k] >= RPTR_MAX_BONES)
+                    return fail(h, RPTR_E_INVALID, "skin vertex %u: bone %u (influence %d) is outside the table of %d bones", v, (unsigned)vertices[v].bone[k], k, RPTR_MAX_BONES);
+                sum += vertices[v].weight[k];
+            }
+            if (sum != 65535u) return fail(h, RPTR_E_INVALID, "skin vertex %u: its weights sum to %u, not 65535", v, sum);
+        }
+    }
+    // ---- checked: from here on the scene copies change, so nothing of the handle may still be rendering from them
+    HIP_TRY(h, hipSetDevice(h->device));
+    {
+        int rc0 = drain(h);
+        if (rc0) return rc0;
+    }
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    auto &sk = h->skin;
+    if (!vertices) { // unbind: positions and normals stay as last written
+        sk.bound[geometry] = 0;
+        return RPTR_OK;
+    }
+    int rc;
+    sk.bound[geometry] = 0;
+    if ((rc = skin_bone_table(h))) return rc;
+    if (!sk.records[geometry] && (rc = dev_alloc(h, &sk.records[geometry], n, &h->scene_allocs))) return rc;
+    if (!sk.rest_pos[geometry] && (rc = dev_alloc(h, &sk.rest_pos[geometry], (size_t)n * 3, &h->scene_allocs))) return rc;
+    HIP_TRY(h, hipMemcpy(sk.records[geometry], vertices, (size_t)n * sizeof(RptrSkinVertex), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(sk.rest_pos[geometry], h->master.dynpos[geometry], (size_t)n * 12, hipMemcpyDeviceToDevice));
+    if (sk.geom_normals[geometry]) {
+        if (!sk.rest_nrm[geometry]) {
+            if ((rc = dev_alloc(h, &sk.rest_nrm[geometry], n, &h->scene_allocs))) return rc;
+            if (n) hipLaunchKernelGGL(rp_k_skin_rest_normals, dim3(grid_for(h, n)), dim3(256), 0, h->stream, sk.geom_qnu[geometry], sk.rest_nrm[geometry], n);
+            HIP_TRY(h, hipGetLastError());
+            HIP_TRY(h, hipStreamSynchronize(h->stream));
+        }
+        if ((rc = skin_copy_normals(h, h->master, geometry))) return rc;
+        for (SceneCopy &sc : h->ctx_scene)
+            if ((rc = skin_copy_normals(h, sc, geometry))) return rc;
+    }
+    sk.bound[geometry] = 1;
+    return RPTR_OK;
+}
+static int update_bones_common(rptr_hip_t *h, uint32_t first, uint32_t count, const float *xf12, bool device_src) {
+    if (!h) return fail(nullptr, RPTR_E_INVALID, "NULL handle");
+    if (!h->have_scene) return fail(h, RPTR_E_INVALID, "update_bones before set_scene");
+    if ((uint64_t)first + count > RPTR_MAX_BONES) return fail(h, RPTR_E_INVALID, "bones [%u, +%u) are outside the table of %d bones", first, count, RPTR_MAX_BONES);
+    if (count == 0) return RPTR_OK;
+    if (!xf12) return fail(h, RPTR_E_INVALID, "NULL transforms");
+    if (!device_src)
+        for (uint32_t i = 0; i < count; ++i)
+            for (int k = 0; k < 12; ++k)
+                if (!std::isfinite(xf12[12ull * i + k])) return fail(h, RPTR_E_INVALID, "transform %u (bone %u) is not finite", i, first + i);
+    HIP_TRY(h, hipSetDevice(h->device));
+    {
+        const int rc0 = skin_bone_table(h);
+        if (rc0) return rc0;
+    }
+    HIP_TRY(h, hipMemcpyAsync(h->skin.d_bones + 12ull * first, xf12, (size_t)count * 48, device_src ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+    if (!device_src) HIP_TRY(h, hipStreamSynchronize(h->stream)); // the host array is only borrowed for the call
+    return RPTR_OK;
+}
+int rptr_hip_update_bones(rptr_hip_t *h, uint32_t first_bone, uint32_t count, const float *transforms12) {
+    return update_bones_common(h, first_bone, count, transforms12, false);
+}
+int rptr_hip_update_bones_device(rptr_hip_t *h, uint32_t first_bone, uint32_t count, const float *device_transforms12) {
+    return update_bones_common(h, first_bone, count, device_transforms12, true);
+}
+// every bound geometry's positions (and normal words) from its rest pose and the bone table, on the backend's stream; then what
+// rptr_hip_update_vertices_device does per geometry
+int rptr_hip_skin(rptr_hip_t *h) {
+    if (!h) return fail(nullptr, RPTR_E_INVALID, "NULL handle");
+    if (!h->have_scene) return fail(h, RPTR_E_INVALID, "skin before set_scene");
+    auto &sk = h->skin;
+    if (std::find(sk.bound.begin(), sk.bound.end(), (char)1) == sk.bound.end()) return fail(h, RPTR_E_INVALID, "skin: no geometry is bound (rptr_hip_set_skin)");
+    if (h->ctx_scene.empty()) { // frames in flight read the master vertex buffer and tree
+        int rc0 = drain(h);
+        if (rc0) return rc0;
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    for (size_t g = 0; g < sk.bound.size(); ++g) {
+        if (!sk.bound[g]) continue;
+        const int rc0 = object_motion_before_update(h, (int)g);
+        if (rc0) return rc0;
+        const uint32_t n = 3u * h->geom_tris[g];
+        if (n)
+            hipLaunchKernelGGL(rp_k_skin, dim3(grid_for(h, n)), dim3(256), 0, h->stream, reinterpret_cast<const uint4 *>(sk.records[g]), sk.rest_pos[g], sk.rest_nrm[g],
+                               reinterpret_cast<const float4 *>(sk.d_bones), n, h->master.dynpos[g], h->master.dynnrm[g], sk.d_rejected);
+        HIP_TRY(h, hipGetLastError());
+        h->master.mesh_dirty[(size_t)h->geom_mesh[g]] = 1;
+        h->vertex_updates++;
+        h->om.unrefitted = true;
+    }
+    return RPTR_OK;
+}
+int rptr_hip_readback_skinned(rptr_hip_t *h, uint32_t geometry, float *xyz, uint32_t *normal_words, uint32_t num_vertices) {
+    if (!h) return fail(nullptr, RPTR_E_INVALID, "NULL handle");
+    if (!h->have_scene) return fail(h, RPTR_E_INVALID, "readback_skinned before set_scene");
+    if (geometry >= h->skin.bound.size() || !h->skin.bound[geometry]) return fail(h, RPTR_E_INVALID, "geometry %u has no skin (rptr_hip_set_skin)", geometry);
+    if (num_vertices != 3u * h->geom_tris[geometry])
+        return fail(h, RPTR_E_INVALID, "geometry %u has %u unrolled vertices, got %u", geometry, 3u * h->geom_tris[geometry], num_vertices);
+    if (normal_words && !h->master.dynnrm[geometry]) return fail(h, RPTR_E_INVALID, "geometry %u has no normals", geometry);
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (xyz && num_vertices) HIP_TRY(h, hipMemcpy(xyz, h->master.dynpos[geometry], (size_t)num_vertices * 12, hipMemcpyDeviceToHost));
+    if (normal_words && num_vertices) HIP_TRY(h, hipMemcpy(normal_words, h->master.dynnrm[geometry], (size_t)num_vertices * 4, hipMemcpyDeviceToHost));
     return RPTR_OK;
 }

@@ -35,6 +35,10 @@ struct SceneCopy {
     float *node_box = nullptr, *tri_box = nullptr, *inst_box = nullptr;
     std::vector<float *> dynpos;            // per global geometry: float positions (9 per triangle) or NULL
     std::vector<const float **> mesh_dyn;   // per mesh: device table of its geometries' dynpos pointers
+    // skinned meshes (skin.h): per global geometry the skinned normal words (3 per triangle; NULL until rptr_hip_set_skin binds a geometry
+    // that has normals), per mesh the device table of its geometries' arrays (NULL: no geometry of the mesh has one -- nothing is launched)
+    std::vector<uint32_t *> dynnrm;
+    std::vector<const uint32_t **> mesh_nrm;
     std::vector<char> mesh_dirty;           // 0 clean, 1 new vertices, 2 dynamic but triangle bounds never written
     uint64_t version = 0;                   // rptr_hip.refit_version this copy reflects
     // refit of the dynamic bottom-level trees by depth levels (lbvh.h): the node list (every mesh's nodes in its own slice, deepest
@@ -338,6 +342,17 @@ struct rptr_hip {
     std::vector<float> scene_xf;                 // ... the 12 floats per instance set_scene received: what a registration is checked against
     std::vector<int> inst_mesh;                  // per scene instance: its mesh
     std::vector<char> mesh_has_lights;           // per mesh: a registered source names one of its geometries
+    // skinned meshes (rptr_hip_set_skin / update_bones / skin, skin.h). Device buffers live in scene_allocs: set_scene drops every binding.
+    struct Skin {
+        float *d_bones = nullptr;                  // RPTR_MAX_BONES rows of 12 floats, identity when the first set_skin / update_bones of a scene makes it
+        uint32_t *d_rejected = nullptr;            // vertices rp_k_skin left alone since set_scene (option "skin_vertices_rejected")
+        std::vector<const uint64_t *> geom_qnu;    // per global geometry: the device copy of its qnrm_uv stream (NULL: none)
+        std::vector<char> geom_normals;            // per global geometry: it has normals
+        std::vector<char> bound;                   // per global geometry: rptr_hip_skin writes it
+        std::vector<RptrSkinVertex *> records;     // per global geometry: the skin records (made by the first binding, reused by later ones)
+        std::vector<float *> rest_pos;             // ... the rest pose: the float positions at the time of the binding
+        std::vector<uint32_t *> rest_nrm;          // ... the rest normal words as uploaded (NULL: the geometry has no normals)
+    } skin;
 
     // device buffers (frame sized)
     std::vector<FrameCtx> ctx;      // frames in flight (RptrCreateInfo.frames_in_flight, at least 1)

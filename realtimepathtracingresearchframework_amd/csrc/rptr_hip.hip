@@ -20,6 +20,7 @@
 #include "launch.h"
 #include "lbvh.h"
 #include "tlas_build.h"
+#include "skin.h"
 #include "ploc.h"
 #include <hip/hip_ext.h>
 

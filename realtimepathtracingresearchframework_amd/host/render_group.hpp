@@ -70,6 +70,22 @@ public:
         for (auto &r : ranks_) r->set_light_sources(sources);
     }
     std::vector<RptrTriLightData> readback_lights(uint32_t num_lights) { return ranks_[0]->readback_lights(num_lights); } // (the ranks' buffers are equal)
+    void set_skin(uint32_t geometry, const std::vector<RptrSkinVertex> &vertices) { // every GPU holds the whole scene: every rank is bound
+        for (auto &r : ranks_) r->set_skin(geometry, vertices);
+    }
+    void update_bones(uint32_t first, uint32_t count, const float *transforms12) {
+        for (auto &r : ranks_) r->update_bones(first, count, transforms12);
+    }
+    // (device memory belongs to one GPU: rank k reads device_transforms12[k])
+    void update_bones_device(uint32_t first, uint32_t count, const std::vector<const float *> &device_transforms12) {
+        for (size_t k = 0; k < ranks_.size(); ++k) ranks_[k]->update_bones_device(first, count, device_transforms12.at(k));
+    }
+    void skin() {
+        for (auto &r : ranks_) r->skin();
+    }
+    std::vector<float> readback_skinned(uint32_t geometry, uint32_t num_vertices, std::vector<uint32_t> *normal_words = nullptr) { // (the ranks' buffers are equal)
+        return ranks_[0]->readback_skinned(geometry, num_vertices, normal_words);
+    }
     void set_rng_variant(int rng_variant, const std::vector<uint32_t> &table = {}) {
         for (auto &r : ranks_) r->set_rng_variant(rng_variant, table);
     }

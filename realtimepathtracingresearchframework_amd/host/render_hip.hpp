@@ -137,6 +137,25 @@ public:
         check(rptr_hip_readback_lights(h_, out.data(), num_lights));
         return out;
     }
+    // skinned meshes: one RptrSkinVertex per unrolled vertex binds a geometry of a dynamic mesh (its rest pose: the positions it has now;
+    // an empty vector unbinds); bone matrices are row-major 3x4, rest to posed object space; skin() writes positions and shading normals
+    // of every bound geometry on the device, refit() follows as after update_vertices
+    void set_skin(uint32_t geometry, const std::vector<RptrSkinVertex> &vertices) {
+        flush_pipeline();
+        check(rptr_hip_set_skin(h_, geometry, vertices.empty() ? nullptr : vertices.data(), (uint32_t)vertices.size()));
+    }
+    void update_bones(uint32_t first, uint32_t count, const float *transforms12) { check(rptr_hip_update_bones(h_, first, count, transforms12)); }
+    void update_bones_device(uint32_t first, uint32_t count, const float *device_transforms12) {
+        check(rptr_hip_update_bones_device(h_, first, count, device_transforms12));
+    }
+    void skin() { check(rptr_hip_skin(h_)); }
+    // the master copy's positions (3 floats per vertex) and, when `normal_words` is given, normal words of a bound geometry
+    std::vector<float> readback_skinned(uint32_t geometry, uint32_t num_vertices, std::vector<uint32_t> *normal_words = nullptr) {
+        std::vector<float> xyz((size_t)num_vertices * 3);
+        if (normal_words) normal_words->assign(num_vertices, 0u);
+        check(rptr_hip_readback_skinned(h_, geometry, xyz.data(), normal_words ? normal_words->data() : nullptr, num_vertices));
+        return xyz;
+    }
     // RenderBackendOptions (render_params.glsl.h:56-93): the point set with the table its render extension uploads, and the BVH policy
     void set_rng_variant(int rng_variant, const std::vector<uint32_t> &table = {}) {
         check(rptr_hip_set_rng_variant(h_, rng_variant, table.empty() ? nullptr : table.data(), table.size() * sizeof(uint32_t)));

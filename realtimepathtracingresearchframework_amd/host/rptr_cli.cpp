@@ -34,6 +34,11 @@
 //  * --animate-wave a k (profiling mode, scenes whose mesh 0 is dynamic): y = y0 + a sin(k x + 2 pi t) on geometry 0 before
 //    every frame, followed by rptr_hip_refit -- SURVEY 8d C5 (the reference animates with a compute shader,
 //    render_vulkan.cpp:2834-2840; per-frame BLAS update + TLAS refit :1323-1354).
+//  * --skin <file> --bones <file> (profiling and data-capture mode, scenes whose mesh 0 is dynamic): the skin file holds raw
+//    RptrSkinVertex records (16 bytes per unrolled vertex) for geometry first_geometry of mesh 0, the bones file two uint32 (frames,
+//    bones) and frames x bones x 12 float32. Frame k of the run stages the bones of frame k mod frames, skins on the device
+//    (rptr_hip_skin) and refits before it renders; positions AND shading normals follow. One flag without the other, --animate-wave
+//    beside them, a mesh 0 that is not dynamic or a file of the wrong size: exit code 2 before a device is touched.
 //  * data-capture mode (--data-capture <prefix> [--data-capture-spp n] [--data-capture-no-rgba] [--data-capture-no-aovs]
 //    [--data-capture-albedo-roughness|-normal-depth|-motion]) stores the accumulation buffer and the chosen AOV images of every
 //    keyframe as <prefix>_%04d_{rgba,albedo_roughness,normal_depth,motion_jitter}.exr (libapp/app_state.cpp:499-531).
@@ -213,6 +218,7 @@ int main(int argc, char **argv) {
     bool freeze_frame = false, got_batch_spp = false, got_variant = false;
     int rng_variant = -1, force_bvh_rebuild = -1, rebuild_triangle_budget = -1; // -1: as the configuration files say
     std::string bn_table_path, dump_scene_path, sky_data;
+    std::string skin_path, bones_path; // --skin / --bones: a skinned mesh 0 (rptr_hip_set_skin / update_bones / skin)
     bool got_frames_per_launch = false;
     int upscale = 0, stripe_rows = 8, frames_in_flight = 0, frames_per_launch = 1; // frames_in_flight 0: the reference's loop (two swap buffers)
     bool synchronous = false, fly_through = false;
@@ -249,6 +255,8 @@ int main(int argc, char **argv) {
         else if (a == "--fly-through") fly_through = true;   // (this host's: bench.py's camera path)
         else if (a == "--profiling-count") { need(1); profiling_frames = std::atoi(argv[++i]); have_profiling_options = true; } // (this host's: frames of a run without keyframes)
         else if (a == "--animate-wave") { need(2); wave_amp = (float)std::atof(argv[++i]); wave_k = (float)std::atof(argv[++i]); }
+        else if (a == "--skin") { need(1); skin_path = argv[++i]; }
+        else if (a == "--bones") { need(1); bones_path = argv[++i]; }
         else if (a == "--denoise") { need(1); g_denoise_iterations = std::atoi(argv[++i]); if (g_denoise_iterations < 1 || g_denoise_iterations > 5) { std::fprintf(stderr, "--denoise takes 1..5 iterations\n"); return 2; } }
         else if (a == "--denoise-temporal") { need(1); g_denoise_temporal_iterations = std::atoi(argv[++i]); if (g_denoise_temporal_iterations < 1 || g_denoise_temporal_iterations > 5) { std::fprintf(stderr, "--denoise-temporal takes 1..5 iterations\n"); return 2; } }
         else if (a == "--taa-upscale") g_taa_upscale = true;
@@ -440,6 +448,16 @@ int main(int argc, char **argv) {
             return 2;
         }
     }
+    if (!skin_path.empty() || !bones_path.empty()) {
+        const char *why = nullptr;
+        if (skin_path.empty() || bones_path.empty()) why = "go together: the influences of mesh 0's vertices and the bone matrices of every frame";
+        else if (wave_amp != 0.f) why = "cannot be combined with --animate-wave: both write the vertices of mesh 0";
+        else if (validation) why = "need --profiling or --data-capture: a validation run accumulates one still scene";
+        if (why) {
+            std::fprintf(stderr, "--skin and --bones %s\n", why);
+            return 2;
+        }
+    }
     if (want_help) scene_path.clear(); // prints the usage
     if (scene_path.empty() || (int)validation + (int)profiling + (int)data_capture != 1 || batch_spp < 1 || width < 1 || height < 1 || (profiling && profiling_frames < 1)) {
         std::fprintf(stderr, "usage: rptr_hip <scene.rpsc> (--validation <prefix> [--validation-spp n] | --profiling <csv prefix> [--profiling-fps f] "
@@ -525,6 +543,49 @@ int main(int argc, char **argv) {
         for (int k = 0; k < 3; ++k)
             if (!std::isnan(base.white_balance[k])) g_auto_exposure_params.white_balance[k] = base.white_balance[k];
         const bool expose_frames = g_auto_exposure && g_denoise_iterations == 0; // (--denoise runs when an image is written: save_image exposes there)
+        // --skin <file>: raw RptrSkinVertex records of geometry first_geometry of mesh 0; --bones <file>: two uint32 (frames, bones), then
+        // frames x bones x 12 float32. Both are checked against the scene before a device is touched.
+        const bool skinned = !skin_path.empty();
+        std::vector<RptrSkinVertex> skin_records;
+        std::vector<float> bone_frames;
+        uint32_t n_bone_frames = 0, n_bones = 0;
+        if (skinned) {
+            auto slurp = [](const std::string &path, std::vector<char> &out) {
+                FILE *f = std::fopen(path.c_str(), "rb");
+                if (!f) return false;
+                std::fseek(f, 0, SEEK_END);
+                const long n = std::ftell(f);
+                std::fseek(f, 0, SEEK_SET);
+                out.resize(n > 0 ? (size_t)n : 0);
+                const bool ok = out.empty() || std::fread(out.data(), 1, out.size(), f) == out.size();
+                std::fclose(f);
+                return ok;
+            };
+            if (scene.meshes.empty() || !(scene.meshes[0].dynamic & (RPTR_MESH_DYNAMIC | RPTR_MESH_SUBTLY_DYNAMIC))) {
+                std::fprintf(stderr, "--skin needs a scene whose mesh 0 is dynamic\n");
+                return 2;
+            }
+            const size_t n_vertices = (size_t)scene.geometries[scene.meshes[0].first_geometry].num_tris * 3;
+            std::vector<char> raw;
+            if (!slurp(skin_path, raw) || raw.size() != n_vertices * sizeof(RptrSkinVertex)) {
+                std::fprintf(stderr, "--skin %s: %zu bytes, geometry %u has %zu unrolled vertices of %zu bytes each\n", skin_path.c_str(), raw.size(),
+                             scene.meshes[0].first_geometry, n_vertices, sizeof(RptrSkinVertex));
+                return 2;
+            }
+            skin_records.resize(n_vertices);
+            if (!raw.empty()) std::memcpy(skin_records.data(), raw.data(), raw.size());
+            if (slurp(bones_path, raw) && raw.size() >= 8) {
+                std::memcpy(&n_bone_frames, raw.data(), 4);
+                std::memcpy(&n_bones, raw.data() + 4, 4);
+            }
+            if (n_bone_frames < 1 || n_bones < 1 || n_bones > RPTR_MAX_BONES || raw.size() != 8 + (size_t)n_bone_frames * n_bones * 48) {
+                std::fprintf(stderr, "--bones %s: %zu bytes do not hold a header of two uint32 (frames %u, bones %u of at most %d) and frames x bones x 12 float32\n",
+                             bones_path.c_str(), raw.size(), n_bone_frames, n_bones, RPTR_MAX_BONES);
+                return 2;
+            }
+            bone_frames.resize((size_t)n_bone_frames * n_bones * 12);
+            std::memcpy(bone_frames.data(), raw.data() + 8, bone_frames.size() * sizeof(float));
+        }
         if (frames_in_flight == 1) synchronous = true; // (one frame context: nothing to overlap)
         // frame contexts: the reference's two swap buffers; what --frames-in-flight asks for; four for a queued --validation accumulation
         // (its launch sequences are independent of the display: the deeper queue is what fills the GPU)
@@ -545,6 +606,14 @@ int main(int argc, char **argv) {
                 }
             }
         }
+        // --skin / --bones: mesh 0's first geometry is bound at its rest pose; pose(k) stages the bones of the file's frame k mod frames,
+        // skins and refits (positions, shading normals and -- with registered sources -- lights follow)
+        if (skinned) backend.set_skin(scene.meshes[0].first_geometry, skin_records);
+        auto pose = [&](uint64_t k) {
+            backend.update_bones(0, n_bones, &bone_frames[(size_t)(k % n_bone_frames) * n_bones * 12]);
+            backend.skin();
+            backend.refit();
+        };
         // --object-motion: the file's transform table stays open; play(k) stages the transforms of the file's frame k mod numFrames that
         // differ from the ones staged last (static instances -- which may be baked into the flattened tree -- are never named) and refits
         rptr::vks::Header anim;
@@ -688,10 +757,15 @@ int main(int argc, char **argv) {
             // --data-capture-fps only paces the reference's animation clock between captures (a keyframe here is captured once)
             (void)capture_fps;
             // --object-motion: one capture per frame of the file's animation instead, the motion image rewritten before it is stored
-            const size_t n_keys = g_object_motion ? (size_t)anim.numFrames : std::max<size_t>(1, frames.size());
+            // --skin / --bones without keyframes: one capture per frame of the bones file, each at its pose
+            const size_t n_keys = g_object_motion ? (size_t)anim.numFrames : skinned && frames.empty() ? (size_t)n_bone_frames : std::max<size_t>(1, frames.size());
             for (size_t k = 0; k < n_keys; ++k) {
                 if (g_object_motion) {
                     if (k) play(g_load.frame + k);
+                    cfg.reset_accumulation = true;
+                }
+                if (skinned) {
+                    pose(k);
                     cfg.reset_accumulation = true;
                 }
                 if (!frames.empty()) {
@@ -805,7 +879,7 @@ int main(int argc, char **argv) {
                         p.reset = true;
                     }
                 }
-                if (!rest.empty() || g_object_motion) p.reset = true; // the geometry moves: the accumulation starts over
+                if (!rest.empty() || g_object_motion || skinned) p.reset = true; // the geometry moves: the accumulation starts over
                 p.camera = cam;
                 if (fly_through) { // a moved camera restarts the accumulation (the application resets when the view changes) ...
                     p.camera = fly_camera(frame);
@@ -845,7 +919,7 @@ int main(int argc, char **argv) {
         // frames of one keyframe, every frame with its own view (rptr_hip_render_batch_cameras_async), n sequences in flight -- the schedule
         // bench.py times (the library asks the HIP runtime for a hardware queue per frame context itself: csrc/rptr_hip.hip
         // ensure_hw_queues). One CSV row per frame as it is collected; render_time_ms is the frame's share of its sequence.
-        if (frames_in_flight > 1 && rest.empty() && !freeze_frame && !g_object_motion) {
+        if (frames_in_flight > 1 && rest.empty() && !skinned && !freeze_frame && !g_object_motion) {
             frames_per_launch = std::min(frames_per_launch, std::max(1, 16 / std::max(1, batch_spp)));
             // reprojection_mode 2 folds each frame into the one before it: one frame per launch sequence (include/rptr_hip.h)
             bool realtime = base.params.reprojection_mode == 2;
@@ -939,6 +1013,7 @@ int main(int argc, char **argv) {
                 backend.update_vertices(scene.meshes[0].first_geometry, cur.data(), (uint32_t)(cur.size() / 3));
                 backend.refit();
             }
+            if (skinned) pose((uint64_t)frame); // the bones of this frame: skin, refit, and the accumulation starts over
             if (g_object_motion && frame) play(g_load.frame + (uint64_t)frame); // the file's next frame: new transforms, refit
             const rptr::RenderStats st = backend.frame(cmd_stream, config_of(fp));
             if (g_object_motion) {
