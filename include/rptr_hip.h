@@ -529,6 +529,63 @@ int rptr_hip_update_bones_device(rptr_hip_t *h, uint32_t first_bone, uint32_t co
 int rptr_hip_skin(rptr_hip_t *h);
 int rptr_hip_readback_skinned(rptr_hip_t *h, uint32_t geometry, float *xyz, uint32_t *normal_words, uint32_t num_vertices);
 
+/* ---- morph targets (blend shapes): weights in, float positions and shading normals out on the device (csrc/morph.h rp_k_morph). The
+ * other half of character animation: faces, corrective shapes, cloth and fluid caches played back as "keyframe minus rest" with a weight,
+ * every glTF `targets` / `weights` pair. The morph stage sits IN FRONT of the skinner: it runs alone where a geometry has no skin, and
+ * with a skin the morphed rest pose goes through exactly the operations of rp_k_skin. It shares the skinner's rest pose, output arrays,
+ * rejection rule and everything downstream; no kernel of a frame or of the refit changes, and a scene that binds nothing launches and
+ * allocates what it did.
+ * rptr_hip_set_morph_targets(h, geometry, targets, num_targets): after set_scene, on a geometry of a mesh flagged RPTR_MESH_DYNAMIC /
+ * _SUBTLY_DYNAMIC. Targets are SPARSE: a target lists only the vertices it moves and may have zero deltas; `vertex` is an UNROLLED
+ * vertex (three per triangle, the order of rptr_hip_update_vertices: a vertex shared by several triangles has one delta per corner, the
+ * convention of RptrSkinVertex). Checked on the host before anything is queued: RPTR_E_INVALID, nothing changed and a message that names
+ * the first offending target and delta, for a NULL handle, a call before set_scene, a geometry that is not dynamic, num_targets >
+ * RPTR_MAX_MORPH_TARGETS, a vertex >= 3 * triangles, a vertex that appears twice within one target, a delta component that is not
+ * finite, a non-zero _pad, deltas == NULL with num_deltas != 0, and a total number of deltas that does not fit 32 bits. The library
+ * transposes the targets once into a per-vertex list sorted by target (csrc/morph.h). (NULL, 0) unbinds: positions and normals stay as
+ * last written. A new set_scene drops every binding. The call waits for the frames in flight. The weights of a newly bound geometry are
+ * all zero.
+ * Rest pose: ONE per geometry, shared by both deformers. A binding call (set_skin or set_morph_targets) captures it -- a device copy of
+ * the float positions, and the normal halves of the uploaded qnrm_uv words -- only when the geometry has neither a skin nor morph targets
+ * at that moment; on a geometry that already has the other deformer bound it reuses the captured one. (rptr_hip_set_skin on a geometry
+ * without morph targets behaves as it always did: it captures.)
+ * rptr_hip_update_morph_weights[_device](h, geometry, first_target, count, weights): `count` floats into rows [first_target,
+ * first_target + count) of that geometry's weight table, on the backend's stream. The host form refuses a range beyond the geometry's
+ * num_targets, NULL with count > 0, a geometry without targets and a weight that is not finite (RPTR_E_INVALID, nothing staged). The
+ * _device form reads DEVICE memory, ordered on the backend's stream, and cannot see its values (see "rejected vertices"). Negative
+ * weights and weights above 1 are legal.
+ * rptr_hip_skin(h) stays the one call that runs the deformers: for every geometry that has a skin, morph targets or both it launches one
+ * kernel (a skin without morph targets: rp_k_skin, exactly as before), then does what it always did. "Nothing bound" (RPTR_E_INVALID)
+ * means neither deformer. rptr_hip_readback_skinned accepts a geometry bound by either.
+ * Arithmetic: binary32, every product and sum rounded on its own. For vertex i, its entries are the deltas of all targets that name it,
+ * in ASCENDING TARGET INDEX:
+ *   p = rest_pos[i];  n = dequantize_normal(rest_word[i])                          (geometries with normals)
+ *   for each entry (t, dpos, dnrm):  w = weight[t];  w == 0.0f: the entry is skipped
+ *       p[c] = p[c] + w * dpos[c];   n[c] = n[c] + w * dnrm[c]                     (c = 0, 1, 2)
+ *   no skin: p' = p, q = n; when no entry was applied the normal word written is rest_word[i] itself (no re-quantisation)
+ *   skin:    B, p' = place(B, p), q = cof(A) n with the sign rule: the operations of "skinned meshes" on the morphed p and n
+ *   word = quantize_normal(q) unless q is not finite or all zero (the previous word stays)
+ * Without a skin, all-zero weights reproduce the rest pose BIT FOR BIT, positions and words; with a skin and zero weights the result is
+ * bit for bit what rp_k_skin writes. The kernel always reads the rest pose, never its own output.
+ * Rejected vertices: a vertex whose final position is not finite (a NaN weight from a device table) keeps its position and normal and is
+ * counted in the existing read-only option "skin_vertices_rejected".
+ * Lights follow only with registered sources, and bins are not re-equalised after non-rigid change (see "moving lights"). */
+#define RPTR_MAX_MORPH_TARGETS 1024 /* per geometry */
+typedef struct RptrMorphDelta { /* 32 bytes */
+    uint32_t vertex;            /* UNROLLED vertex (3 per triangle, the order of rptr_hip_update_vertices) */
+    float dpos[3];              /* added to the rest position, object space */
+    float dnrm[3];              /* added to the rest normal (ignored for a geometry without normals) */
+    uint32_t _pad;              /* zero */
+} RptrMorphDelta;
+typedef struct RptrMorphTargetDesc {
+    const RptrMorphDelta *deltas;
+    uint32_t num_deltas;
+    uint32_t _pad;
+} RptrMorphTargetDesc;
+int rptr_hip_set_morph_targets(rptr_hip_t *h, uint32_t geometry, const RptrMorphTargetDesc *targets, uint32_t num_targets);
+int rptr_hip_update_morph_weights(rptr_hip_t *h, uint32_t geometry, uint32_t first_target, uint32_t count, const float *weights);
+int rptr_hip_update_morph_weights_device(rptr_hip_t *h, uint32_t geometry, uint32_t first_target, uint32_t count, const float *device_weights);
+
 /* ---- RenderBackend::params / lighting_params / update_config
  * (render_backend.h:69-76, render_vulkan.cpp:2943-2959) */
 int rptr_hip_set_params(rptr_hip_t *h, const RptrRenderParams *params,

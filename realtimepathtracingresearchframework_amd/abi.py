@@ -256,6 +256,20 @@ class SkinVertex(C.Structure):  # include/rptr_hip.h RptrSkinVertex: the influen
     _fields_ = [("bone", C.c_uint16 * 4), ("weight", C.c_uint16 * 4)]
 
 
+MAX_MORPH_TARGETS = 1024  # RPTR_MAX_MORPH_TARGETS (per geometry)
+
+
+class MorphDelta(C.Structure):  # include/rptr_hip.h RptrMorphDelta: what one target adds to one unrolled vertex
+    _fields_ = [("vertex", C.c_uint32), ("dpos", C.c_float * 3), ("dnrm", C.c_float * 3), ("_pad", C.c_uint32)]
+
+
+class MorphTargetDesc(C.Structure):  # include/rptr_hip.h RptrMorphTargetDesc: one sparse target
+    _fields_ = [("deltas", C.POINTER(MorphDelta)), ("num_deltas", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+MORPH_DELTA_DTYPE = [("vertex", "<u4"), ("dpos", "<f4", (3,)), ("dnrm", "<f4", (3,)), ("_pad", "<u4")]  # RptrMorphDelta as a numpy record
+
+
 class SurfaceHit(C.Structure):  # include/rptr_hip.h RptrSurfaceHit: six 16-byte rows per surface query
     _fields_ = [("position", C.c_float * 3), ("t", C.c_float),
                 ("geo_normal", C.c_float * 3), ("instance_geometry", C.c_int32),
@@ -305,6 +319,8 @@ assert C.sizeof(AutoExposureParams) == 64
 assert C.sizeof(ExposureState) == 32 + 1024
 assert C.sizeof(LightSource) == 48
 assert C.sizeof(SkinVertex) == 16
+assert C.sizeof(MorphDelta) == 32
+assert C.sizeof(MorphTargetDesc) == 16
 assert C.sizeof(DenoiseParams) == 32
 assert C.sizeof(DenoiseTemporalParams) == 64
 assert C.sizeof(BaseMaterial) == 80
@@ -325,7 +341,8 @@ EXPORTED_SYMBOLS = [
     "rptr_hip_create", "rptr_hip_abi_version", "rptr_hip_build_id", "rptr_hip_bvh_build_info", "rptr_hip_traversal_preset", "rptr_hip_destroy", "rptr_hip_last_error", "rptr_hip_name", "rptr_hip_set_stream",
     "rptr_hip_initialize", "rptr_hip_set_scene", "rptr_hip_update_vertices", "rptr_hip_update_vertices_device", "rptr_hip_refit", "rptr_hip_set_params",
     "rptr_hip_render", "rptr_hip_render_async", "rptr_hip_render_batch_async", "rptr_hip_render_batch_cameras_async", "rptr_hip_wait", "rptr_hip_set_stage_timing", "rptr_hip_set_freeze_frame", "rptr_hip_set_option", "rptr_hip_get_option", "rptr_hip_option_count", "rptr_hip_option_name", "rptr_hip_set_rng_variant", "rptr_hip_set_bvh_policy", "rptr_hip_bvh_rebuild_count", "rptr_hip_update_instances", "rptr_hip_update_instances_device", "rptr_hip_set_tlas_policy", "rptr_hip_tlas_rebuild_count", "rptr_hip_set_light_sources", "rptr_hip_readback_lights",
-    "rptr_hip_set_skin", "rptr_hip_update_bones", "rptr_hip_update_bones_device", "rptr_hip_skin", "rptr_hip_readback_skinned", "rptr_hip_get_framebuffer_size", "rptr_hip_readback_f32", "rptr_hip_readback_u8", "rptr_hip_readback_aov",
+    "rptr_hip_set_skin", "rptr_hip_update_bones", "rptr_hip_update_bones_device", "rptr_hip_skin", "rptr_hip_readback_skinned",
+    "rptr_hip_set_morph_targets", "rptr_hip_update_morph_weights", "rptr_hip_update_morph_weights_device", "rptr_hip_get_framebuffer_size", "rptr_hip_readback_f32", "rptr_hip_readback_u8", "rptr_hip_readback_aov",
     "rptr_hip_denoise_defaults", "rptr_hip_denoise", "rptr_hip_readback_denoised_f32", "rptr_hip_readback_denoised_u8",
     "rptr_hip_denoise_temporal_defaults", "rptr_hip_denoise_temporal", "rptr_hip_readback_denoise_history_f32",
     "rptr_hip_taa_upscale_defaults", "rptr_hip_taa_upscale", "rptr_hip_readback_upscaled_u8",

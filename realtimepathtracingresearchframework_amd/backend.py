@@ -99,6 +99,9 @@ def load_library(path=None):
     L.rptr_hip_update_bones_device.argtypes = [vp, C.c_uint32, C.c_uint32, vp]
     L.rptr_hip_skin.argtypes = [vp]
     L.rptr_hip_readback_skinned.argtypes = [vp, C.c_uint32, vp, vp, C.c_uint32]
+    L.rptr_hip_set_morph_targets.argtypes = [vp, C.c_uint32, vp, C.c_uint32]
+    L.rptr_hip_update_morph_weights.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]
+    L.rptr_hip_update_morph_weights_device.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]
     L.rptr_hip_bvh_build_info.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.rptr_hip_traversal_preset.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.rptr_hip_get_framebuffer_size.argtypes = [vp, C.POINTER(C.c_uint32)]
@@ -796,6 +799,46 @@ class RenderHip:
         self._check(self._L.rptr_hip_readback_skinned(self._h, int(geometry), xyz.ctypes.data_as(C.c_void_p),
                                                       words.ctypes.data_as(C.c_void_p) if has_normals else None, n))
         return xyz, words
+
+    # ---- morph targets (rptr_hip_set_morph_targets / update_morph_weights): the stage in front of the skinner; skin() runs both
+    @staticmethod
+    def morph_deltas(vertex, dpos, dnrm=None):
+        """one target as a numpy array of RptrMorphDelta records (abi.MORPH_DELTA_DTYPE)"""
+        vertex = np.ascontiguousarray(vertex, dtype=np.uint32).reshape(-1)
+        rec = np.zeros(len(vertex), dtype=abi.MORPH_DELTA_DTYPE)
+        rec["vertex"] = vertex
+        rec["dpos"] = np.asarray(dpos, dtype=np.float32).reshape(-1, 3)
+        if dnrm is not None:
+            rec["dnrm"] = np.asarray(dnrm, dtype=np.float32).reshape(-1, 3)
+        return rec
+
+    def set_morph_targets(self, geometry, targets=None):
+        """Bind one geometry of a dynamic mesh: targets is a list of (vertex uint32[k], dpos float32[k, 3], dnrm float32[k, 3] or None),
+        sparse -- a target lists the UNROLLED vertices it moves, each at most once, and may be empty. The weights start at zero. The rest
+        pose is the geometry's positions now, or the one its skin captured. targets=None unbinds."""
+        if targets is None:
+            self._check(self._L.rptr_hip_set_morph_targets(self._h, int(geometry), None, 0))
+            return
+        recs = [self.morph_deltas(*t) for t in targets]  # (kept alive until the call returns)
+        descs = (abi.MorphTargetDesc * max(len(recs), 1))()
+        for d, rec in zip(descs, recs):
+            d.deltas = C.cast(rec.ctypes.data, C.POINTER(abi.MorphDelta)) if len(rec) else None
+            d.num_deltas = len(rec)
+        self._check(self._L.rptr_hip_set_morph_targets(self._h, int(geometry), descs if recs else None, len(recs)))
+
+    def update_morph_weights(self, geometry, first_target, weights):
+        """Stage the weights of targets [first_target, first_target + k) of one geometry: a numpy array (checked: finite), or a torch
+        device tensor of float32 written on the backend's stream (not checked: see "skin_vertices_rejected"). The next skin() reads them."""
+        if hasattr(weights, "data_ptr") and getattr(weights, "is_cuda", False):
+            assert str(weights.dtype) == "torch.float32" and weights.is_contiguous()
+            self.update_morph_weights_device(geometry, first_target, weights.data_ptr(), weights.numel())
+            return
+        w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+        self._check(self._L.rptr_hip_update_morph_weights(self._h, int(geometry), int(first_target), len(w), w.ctypes.data_as(C.c_void_p) if len(w) else None))
+
+    def update_morph_weights_device(self, geometry, first_target, device_ptr, count):
+        """same from a device buffer of float32 written on the backend's stream."""
+        self._check(self._L.rptr_hip_update_morph_weights_device(self._h, int(geometry), int(first_target), int(count), C.c_void_p(device_ptr)))
 
     def set_rng_variant(self, rng_variant, table=None):
         """RenderBackendOptions::rng_variant (render_params.glsl.h:34-37,76) + the table upload of the point set's render extension

@@ -568,6 +568,14 @@ int rptr_hip_set_scene(rptr_hip_t *h, const RptrSceneDesc *s) {
         h->skin.records.assign(s->num_geometries, nullptr);
         h->skin.rest_pos.assign(s->num_geometries, nullptr);
         h->skin.rest_nrm.assign(s->num_geometries, nullptr); // (the table itself is made by the first call that needs it: skin_bone_table)
+        h->morph = decltype(h->morph)(); // morph targets (morph.h): host vectors only; the device arrays are made by set_morph_targets
+        h->morph.bound.assign(s->num_geometries, 0);
+        h->morph.num_targets.assign(s->num_geometries, 0);
+        h->morph.offsets.assign(s->num_geometries, nullptr);
+        h->morph.entries.assign(s->num_geometries, nullptr);
+        h->morph.weights.assign(s->num_geometries, nullptr);
+        h->morph.cap_entries.assign(s->num_geometries, 0);
+        h->morph.cap_weights.assign(s->num_geometries, 0);
     }
     // ---- refit tables, then the master copy
     if ((rc = scene_refit_tables(h, T))) return rc;
@@ -1198,6 +1206,15 @@ int rptr_hip_readback_lights(rptr_hip_t *h, RptrTriLightData *out, uint32_t coun
 // ---- skinned meshes (include/rptr_hip.h "skinned meshes", skin.h)
 // the bone table (identity) and the counter of rejected vertices, made by the first set_skin / update_bones after a set_scene: a scene
 // that is never skinned allocates what it always did
+static int skin_rejected_counter(rptr_hip *h) { // (a geometry with morph targets and no skin needs only this)
+    auto &sk = h->skin;
+    if (!sk.d_rejected) {
+        const int rc = dev_alloc(h, &sk.d_rejected, 1, &h->scene_allocs);
+        if (rc) return rc;
+        HIP_TRY(h, hipMemset(sk.d_rejected, 0, sizeof(uint32_t)));
+    }
+    return RPTR_OK;
+}
 static int skin_bone_table(rptr_hip *h) {
     int rc;
     auto &sk = h->skin;
@@ -1206,9 +1223,31 @@ static int skin_bone_table(rptr_hip *h) {
         for (size_t b = 0; b < RPTR_MAX_BONES; ++b) identity[12 * b] = identity[12 * b + 5] = identity[12 * b + 10] = 1.0f;
         if ((rc = dev_upload(h, &sk.d_bones, identity.size(), identity.data(), hipMemcpyHostToDevice, &h->scene_allocs))) return rc;
     }
-    if (!sk.d_rejected) {
-        if ((rc = dev_alloc(h, &sk.d_rejected, 1, &h->scene_allocs))) return rc;
-        HIP_TRY(h, hipMemset(sk.d_rejected, 0, sizeof(uint32_t)));
+    return skin_rejected_counter(h);
+}
+// the rest pose of `geometry`, shared by the skinner and the morph stage: a device copy of its float positions now (`capture`; a binding
+// call on a geometry that already has the other deformer bound keeps the one it has), the normal halves of its qnrm_uv words as uploaded,
+// and -- for a geometry with normals -- the output array of normal words in the master and in every frame context's scene copy
+static int skin_copy_normals(rptr_hip *h, SceneCopy &sc, uint32_t geometry);
+static int skin_rest_pose(rptr_hip *h, uint32_t geometry, bool capture) {
+    int rc;
+    auto &sk = h->skin;
+    const uint32_t n = 3u * h->geom_tris[geometry];
+    if (!sk.rest_pos[geometry]) {
+        if ((rc = dev_alloc(h, &sk.rest_pos[geometry], (size_t)n * 3, &h->scene_allocs))) return rc;
+        capture = true;
+    }
+    if (capture) HIP_TRY(h, hipMemcpy(sk.rest_pos[geometry], h->master.dynpos[geometry], (size_t)n * 12, hipMemcpyDeviceToDevice));
+    if (sk.geom_normals[geometry]) {
+        if (!sk.rest_nrm[geometry]) {
+            if ((rc = dev_alloc(h, &sk.rest_nrm[geometry], n, &h->scene_allocs))) return rc;
+            if (n) hipLaunchKernelGGL(rp_k_skin_rest_normals, dim3(grid_for(h, n)), dim3(256), 0, h->stream, sk.geom_qnu[geometry], sk.rest_nrm[geometry], n);
+            HIP_TRY(h, hipGetLastError());
+            HIP_TRY(h, hipStreamSynchronize(h->stream));
+        }
+        if ((rc = skin_copy_normals(h, h->master, geometry))) return rc;
+        for (SceneCopy &sc : h->ctx_scene)
+            if ((rc = skin_copy_normals(h, sc, geometry))) return rc;
     }
     return RPTR_OK;
 }
@@ -1264,20 +1303,8 @@ int rptr_hip_set_skin(rptr_hip_t *h, uint32_t geometry, const RptrSkinVertex *ve
     sk.bound[geometry] = 0;
     if ((rc = skin_bone_table(h))) return rc;
     if (!sk.records[geometry] && (rc = dev_alloc(h, &sk.records[geometry], n, &h->scene_allocs))) return rc;
-    if (!sk.rest_pos[geometry] && (rc = dev_alloc(h, &sk.rest_pos[geometry], (size_t)n * 3, &h->scene_allocs))) return rc;
     HIP_TRY(h, hipMemcpy(sk.records[geometry], vertices, (size_t)n * sizeof(RptrSkinVertex), hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemcpy(sk.rest_pos[geometry], h->master.dynpos[geometry], (size_t)n * 12, hipMemcpyDeviceToDevice));
-    if (sk.geom_normals[geometry]) {
-        if (!sk.rest_nrm[geometry]) {
-            if ((rc = dev_alloc(h, &sk.rest_nrm[geometry], n, &h->scene_allocs))) return rc;
-            if (n) hipLaunchKernelGGL(rp_k_skin_rest_normals, dim3(grid_for(h, n)), dim3(256), 0, h->stream, sk.geom_qnu[geometry], sk.rest_nrm[geometry], n);
-            HIP_TRY(h, hipGetLastError());
-            HIP_TRY(h, hipStreamSynchronize(h->stream));
-        }
-        if ((rc = skin_copy_normals(h, h->master, geometry))) return rc;
-        for (SceneCopy &sc : h->ctx_scene)
-            if ((rc = skin_copy_normals(h, sc, geometry))) return rc;
-    }
+    if ((rc = skin_rest_pose(h, geometry, !h->morph.bound[geometry]))) return rc; // (morph targets bound: their rest pose is this one's too)
     sk.bound[geometry] = 1;
     return RPTR_OK;
 }
@@ -1312,20 +1339,36 @@ int rptr_hip_skin(rptr_hip_t *h) {
     if (!h) return fail(nullptr, RPTR_E_INVALID, "NULL handle");
     if (!h->have_scene) return fail(h, RPTR_E_INVALID, "skin before set_scene");
     auto &sk = h->skin;
-    if (std::find(sk.bound.begin(), sk.bound.end(), (char)1) == sk.bound.end()) return fail(h, RPTR_E_INVALID, "skin: no geometry is bound (rptr_hip_set_skin)");
+    auto &mo = h->morph;
+    if (std::find(sk.bound.begin(), sk.bound.end(), (char)1) == sk.bound.end() && std::find(mo.bound.begin(), mo.bound.end(), (char)1) == mo.bound.end())
+        return fail(h, RPTR_E_INVALID, "skin: no geometry is bound (rptr_hip_set_skin, rptr_hip_set_morph_targets)");
     if (h->ctx_scene.empty()) { // frames in flight read the master vertex buffer and tree
         int rc0 = drain(h);
         if (rc0) return rc0;
     }
     HIP_TRY(h, hipSetDevice(h->device));
     for (size_t g = 0; g < sk.bound.size(); ++g) {
-        if (!sk.bound[g]) continue;
+        if (!sk.bound[g] && !mo.bound[g]) continue;
         const int rc0 = object_motion_before_update(h, (int)g);
         if (rc0) return rc0;
         const uint32_t n = 3u * h->geom_tris[g];
-        if (n)
+        if (n && !mo.bound[g])
             hipLaunchKernelGGL(rp_k_skin, dim3(grid_for(h, n)), dim3(256), 0, h->stream, reinterpret_cast<const uint4 *>(sk.records[g]), sk.rest_pos[g], sk.rest_nrm[g],
                                reinterpret_cast<const float4 *>(sk.d_bones), n, h->master.dynpos[g], h->master.dynnrm[g], sk.d_rejected);
+        else if (n) { // morph targets, alone or in front of the skin (morph.h)
+            const bool skinned = sk.bound[g] != 0, normals = sk.geom_normals[g] != 0;
+            const dim3 grid(grid_for(h, n)), block(256);
+            const uint4 *rec = skinned ? reinterpret_cast<const uint4 *>(sk.records[g]) : nullptr;
+            const float4 *bones = skinned ? reinterpret_cast<const float4 *>(sk.d_bones) : nullptr;
+#define RP_MORPH_LAUNCH(S, N)                                                                                                                          \
+    hipLaunchKernelGGL((rp_k_morph<S, N>), grid, block, 0, h->stream, (const uint32_t *)mo.offsets[g], (const float4 *)mo.entries[g], (const float *)mo.weights[g], rec, \
+                       (const float *)sk.rest_pos[g], (const uint32_t *)sk.rest_nrm[g], bones, n, h->master.dynpos[g], h->master.dynnrm[g], sk.d_rejected)
+            if (skinned && normals) RP_MORPH_LAUNCH(true, true);
+            else if (skinned) RP_MORPH_LAUNCH(true, false);
+            else if (normals) RP_MORPH_LAUNCH(false, true);
+            else RP_MORPH_LAUNCH(false, false);
+#undef RP_MORPH_LAUNCH
+        }
         HIP_TRY(h, hipGetLastError());
         h->master.mesh_dirty[(size_t)h->geom_mesh[g]] = 1;
         h->vertex_updates++;
@@ -1336,7 +1379,8 @@ int rptr_hip_skin(rptr_hip_t *h) {
 int rptr_hip_readback_skinned(rptr_hip_t *h, uint32_t geometry, float *xyz, uint32_t *normal_words, uint32_t num_vertices) {
     if (!h) return fail(nullptr, RPTR_E_INVALID, "NULL handle");
     if (!h->have_scene) return fail(h, RPTR_E_INVALID, "readback_skinned before set_scene");
-    if (geometry >= h->skin.bound.size() || !h->skin.bound[geometry]) return fail(h, RPTR_E_INVALID, "geometry %u has no skin (rptr_hip_set_skin)", geometry);
+    if (geometry >= h->skin.bound.size() || (!h->skin.bound[geometry] && !h->morph.bound[geometry]))
+        return fail(h, RPTR_E_INVALID, "geometry %u has no skin (rptr_hip_set_skin) and no morph targets (rptr_hip_set_morph_targets)", geometry);
     if (num_vertices != 3u * h->geom_tris[geometry])
         return fail(h, RPTR_E_INVALID, "geometry %u has %u unrolled vertices, got %u", geometry, 3u * h->geom_tris[geometry], num_vertices);
     if (normal_words && !h->master.dynnrm[geometry]) return fail(h, RPTR_E_INVALID, "geometry %u has no normals", geometry);
@@ -1345,4 +1389,110 @@ int rptr_hip_readback_skinned(rptr_hip_t *h, uint32_t geometry, float *xyz, uint
     if (xyz && num_vertices) HIP_TRY(h, hipMemcpy(xyz, h->master.dynpos[geometry], (size_t)num_vertices * 12, hipMemcpyDeviceToHost));
     if (normal_words && num_vertices) HIP_TRY(h, hipMemcpy(normal_words, h->master.dynnrm[geometry], (size_t)num_vertices * 4, hipMemcpyDeviceToHost));
     return RPTR_OK;
+}
+
+// ---- morph targets (include/rptr_hip.h "morph targets", morph.h)
+int rptr_hip_set_morph_targets(rptr_hip_t *h, uint32_t geometry, const RptrMorphTargetDesc *targets, uint32_t num_targets) {
+    if (!h) return fail(nullptr, RPTR_E_INVALID, "NULL handle");
+    if (!h->have_scene) return fail(h, RPTR_E_INVALID, "set_morph_targets before set_scene");
+    if (geometry >= h->master.dynpos.size() || !h->master.dynpos[geometry])
+        return fail(h, RPTR_E_INVALID, "geometry %u does not belong to a dynamic mesh (RptrMeshDesc.dynamic)", geometry);
+    if ((targets == nullptr) != (num_targets == 0)) return fail(h, RPTR_E_INVALID, "targets and num_targets must both be given, or NULL and 0 to unbind");
+    if (num_targets > RPTR_MAX_MORPH_TARGETS)
+        return fail(h, RPTR_E_INVALID, "%u morph targets, a geometry takes at most %d (RPTR_MAX_MORPH_TARGETS)", num_targets, RPTR_MAX_MORPH_TARGETS);
+    const uint32_t n = 3u * h->geom_tris[geometry];
+    auto &sk = h->skin;
+    auto &mo = h->morph;
+    const bool normals = sk.geom_normals[geometry] != 0;
+    // ---- the host's checks and the transposition: per vertex its entries in ascending target order (a counting sort over the targets in order)
+    std::vector<uint32_t> offsets((size_t)n + 1, 0);
+    std::vector<float> entries;
+    if (targets) {
+        uint64_t total = 0;
+        std::vector<uint32_t> seen_in(n, UINT32_MAX); // the last target that named the vertex
+        for (uint32_t t = 0; t < num_targets; ++t) {
+            const RptrMorphTargetDesc &T = targets[t];
+            if (!T.deltas && T.num_deltas) return fail(h, RPTR_E_INVALID, "morph target %u: NULL deltas with num_deltas %u", t, T.num_deltas);
+            if (T._pad) return fail(h, RPTR_E_INVALID, "morph target %u: _pad of its descriptor is not zero", t);
+            for (uint32_t d = 0; d < T.num_deltas; ++d) {
+                const RptrMorphDelta &D = T.deltas[d];
+                if (D.vertex >= n) return fail(h, RPTR_E_INVALID, "morph target %u, delta %u: vertex %u, geometry %u has %u unrolled vertices", t, d, D.vertex, geometry, n);
+                if (seen_in[D.vertex] == t) return fail(h, RPTR_E_INVALID, "morph target %u, delta %u: vertex %u appears twice in the target", t, d, D.vertex);
+                seen_in[D.vertex] = t;
+                for (int c = 0; c < 3; ++c)
+                    if (!std::isfinite(D.dpos[c]) || !std::isfinite(D.dnrm[c])) return fail(h, RPTR_E_INVALID, "morph target %u, delta %u: a component is not finite", t, d);
+                if (D._pad) return fail(h, RPTR_E_INVALID, "morph target %u, delta %u: _pad is not zero", t, d);
+                offsets[(size_t)D.vertex + 1]++;
+            }
+            total += T.num_deltas;
+        }
+        if (total > UINT32_MAX) return fail(h, RPTR_E_INVALID, "%llu morph deltas: the entries of a geometry must fit 32 bits", (unsigned long long)total);
+        for (uint32_t v = 0; v < n; ++v) offsets[(size_t)v + 1] += offsets[v];
+        const size_t per = normals ? 8 : 4; // floats per entry
+        entries.assign((size_t)total * per, 0.0f);
+        std::vector<uint32_t> cursor(offsets.begin(), offsets.end() - 1);
+        for (uint32_t t = 0; t < num_targets; ++t)
+            for (uint32_t d = 0; d < targets[t].num_deltas; ++d) {
+                const RptrMorphDelta &D = targets[t].deltas[d];
+                float *e = entries.data() + (size_t)cursor[D.vertex]++ * per;
+                e[0] = D.dpos[0], e[1] = D.dpos[1], e[2] = D.dpos[2];
+                std::memcpy(e + 3, &t, sizeof(t)); // the target index as bits
+                if (normals) e[4] = D.dnrm[0], e[5] = D.dnrm[1], e[6] = D.dnrm[2];
+            }
+    }
+    // ---- checked: from here on the scene copies change, so nothing of the handle may still be rendering from them
+    HIP_TRY(h, hipSetDevice(h->device));
+    {
+        int rc0 = drain(h);
+        if (rc0) return rc0;
+    }
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (!targets) { // unbind: positions and normals stay as last written
+        mo.bound[geometry] = 0;
+        return RPTR_OK;
+    }
+    int rc;
+    const bool capture = !sk.bound[geometry] && !mo.bound[geometry]; // (either deformer bound: the rest pose is the one it captured)
+    mo.bound[geometry] = 0;
+    if ((rc = skin_rejected_counter(h))) return rc;
+    if (!mo.offsets[geometry] && (rc = dev_alloc(h, &mo.offsets[geometry], (size_t)n + 1, &h->scene_allocs))) return rc;
+    const size_t n_entries = entries.size() / 4; // float4s
+    if (!mo.entries[geometry] || mo.cap_entries[geometry] < n_entries) {
+        if ((rc = dev_alloc(h, &mo.entries[geometry], n_entries, &h->scene_allocs))) return rc;
+        mo.cap_entries[geometry] = n_entries;
+    }
+    if (!mo.weights[geometry] || mo.cap_weights[geometry] < num_targets) {
+        if ((rc = dev_alloc(h, &mo.weights[geometry], num_targets, &h->scene_allocs))) return rc;
+        mo.cap_weights[geometry] = num_targets;
+    }
+    HIP_TRY(h, hipMemcpy(mo.offsets[geometry], offsets.data(), offsets.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (n_entries) HIP_TRY(h, hipMemcpy(mo.entries[geometry], entries.data(), entries.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemset(mo.weights[geometry], 0, (size_t)num_targets * sizeof(float)));
+    if ((rc = skin_rest_pose(h, geometry, capture))) return rc;
+    mo.num_targets[geometry] = num_targets;
+    mo.bound[geometry] = 1;
+    return RPTR_OK;
+}
+static int update_morph_weights_common(rptr_hip_t *h, uint32_t geometry, uint32_t first, uint32_t count, const float *weights, bool device_src) {
+    if (!h) return fail(nullptr, RPTR_E_INVALID, "NULL handle");
+    if (!h->have_scene) return fail(h, RPTR_E_INVALID, "update_morph_weights before set_scene");
+    auto &mo = h->morph;
+    if (geometry >= mo.bound.size() || !mo.bound[geometry]) return fail(h, RPTR_E_INVALID, "geometry %u has no morph targets (rptr_hip_set_morph_targets)", geometry);
+    if ((uint64_t)first + count > mo.num_targets[geometry])
+        return fail(h, RPTR_E_INVALID, "morph weights [%u, +%u) are outside the %u targets of geometry %u", first, count, mo.num_targets[geometry], geometry);
+    if (count == 0) return RPTR_OK;
+    if (!weights) return fail(h, RPTR_E_INVALID, "NULL weights");
+    if (!device_src)
+        for (uint32_t i = 0; i < count; ++i)
+            if (!std::isfinite(weights[i])) return fail(h, RPTR_E_INVALID, "morph weight %u (target %u) is not finite", i, first + i);
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipMemcpyAsync(mo.weights[geometry] + first, weights, (size_t)count * sizeof(float), device_src ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+    if (!device_src) HIP_TRY(h, hipStreamSynchronize(h->stream)); // the host array is only borrowed for the call
+    return RPTR_OK;
+}
+int rptr_hip_update_morph_weights(rptr_hip_t *h, uint32_t geometry, uint32_t first_target, uint32_t count, const float *weights) {
+    return update_morph_weights_common(h, geometry, first_target, count, weights, false);
+}
+int rptr_hip_update_morph_weights_device(rptr_hip_t *h, uint32_t geometry, uint32_t first_target, uint32_t count, const float *device_weights) {
+    return update_morph_weights_common(h, geometry, first_target, count, device_weights, true);
 }

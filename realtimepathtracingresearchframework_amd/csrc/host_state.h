@@ -353,6 +353,16 @@ struct rptr_hip {
         std::vector<float *> rest_pos;             // ... the rest pose: the float positions at the time of the binding
         std::vector<uint32_t *> rest_nrm;          // ... the rest normal words as uploaded (NULL: the geometry has no normals)
     } skin;
+    // morph targets (rptr_hip_set_morph_targets / update_morph_weights, morph.h): the stage in front of the skinner. It shares skin.rest_pos /
+    // rest_nrm / d_rejected and the output arrays; everything here is made by the first rptr_hip_set_morph_targets of a geometry (scene_allocs).
+    struct Morph {
+        std::vector<char> bound;                   // per global geometry: rptr_hip_skin morphs it
+        std::vector<uint32_t> num_targets;         // ... rows of its weight table
+        std::vector<uint32_t *> offsets;           // ... per-vertex CSR: 3 * triangles + 1 offsets into `entries`
+        std::vector<float4 *> entries;             // ... sorted by (vertex, target): one float4 per entry, two for a geometry with normals
+        std::vector<float *> weights;              // ... one float per target, zero after a binding
+        std::vector<size_t> cap_entries, cap_weights; // ... what the arrays hold room for (a later binding that fits reuses them)
+    } morph;
 
     // device buffers (frame sized)
     std::vector<FrameCtx> ctx;      // frames in flight (RptrCreateInfo.frames_in_flight, at least 1)

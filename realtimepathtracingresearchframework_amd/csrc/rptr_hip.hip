@@ -21,6 +21,7 @@
 #include "lbvh.h"
 #include "tlas_build.h"
 #include "skin.h"
+#include "morph.h"
 #include "ploc.h"
 #include <hip/hip_ext.h>
 

@@ -42,6 +42,34 @@ __global__ __launch_bounds__(256) void rp_k_skin_rest_normals(const uint64_t *qn
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) out[i] = uint32_t(qnrm_uv[i]);
 }
 
+// The steps of rp_k_skin as functions: rp_k_morph (morph.h) performs exactly these operations on a morphed rest pose.
+// blended matrix of one skin record, B[4 r + c]
+RP_DEV void rp_skin_blend(const uint4 s, const float4 *bones, float *B) {
+    const uint32_t bone[4] = {s.x & 0xFFFFu, s.x >> 16, s.y & 0xFFFFu, s.y >> 16};
+    const uint32_t wq[4] = {s.z & 0xFFFFu, s.z >> 16, s.w & 0xFFFFu, s.w >> 16};
+    for (int k = 0; k < 4; ++k) {
+        const float w = float(wq[k]) / 65535.0f;
+        const float4 *m = bones + 3ull * min(bone[k], uint32_t(RPTR_MAX_BONES - 1)); // (set_skin checked the index: the clamp only guards the table)
+        for (int r = 0; r < 3; ++r) {
+            const float4 row = m[r];
+            const float t[4] = {w * row.x, w * row.y, w * row.z, w * row.w};
+            for (int c = 0; c < 4; ++c) B[4 * r + c] = k == 0 ? t[c] : B[4 * r + c] + t[c];
+        }
+    }
+}
+// cof(A) n, A the 3x3 part of B, negated under a mirroring blend
+RP_DEV V3 rp_skin_normal(const float *B, const V3 n) {
+    const V3 A0 = v3(B[0], B[1], B[2]), A1 = v3(B[4], B[5], B[6]), A2 = v3(B[8], B[9], B[10]);
+    const V3 C0 = cross3(A1, A2), C1 = cross3(A2, A0), C2 = cross3(A0, A1);
+    V3 q = v3(dot3(C0, n), dot3(C1, n), dot3(C2, n));
+    if (dot3(A0, C0) < 0.0f) q = -q;
+    return q;
+}
+// a normal the quantiser can take: finite and not all zero (otherwise the previous word stays)
+RP_DEV bool rp_skin_normal_usable(const V3 q) {
+    return isfinite(q.x) && isfinite(q.y) && isfinite(q.z) && !(q.x == 0.0f && q.y == 0.0f && q.z == 0.0f);
+}
+
 // One lane per unrolled vertex. Loads: 16 bytes of skin record, 12 of rest position, 4 of rest normal word, and three float4 per bone
 // (lanes of a wave share few bones: cache hits); stores: 12 + 4 bytes. rest_nrm / out_nrm NULL: a geometry without normals.
 // A vertex whose new position is not finite keeps position and normal and is counted in *rejected; a normal that is not finite or all
@@ -49,19 +77,8 @@ __global__ __launch_bounds__(256) void rp_k_skin_rest_normals(const uint64_t *qn
 __global__ __launch_bounds__(256) void rp_k_skin(const uint4 *skin, const float *rest_pos, const uint32_t *rest_nrm, const float4 *bones, uint32_t n, float *out_pos,
                                                  uint32_t *out_nrm, uint32_t *rejected) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        const uint4 s = skin[i];
-        const uint32_t bone[4] = {s.x & 0xFFFFu, s.x >> 16, s.y & 0xFFFFu, s.y >> 16};
-        const uint32_t wq[4] = {s.z & 0xFFFFu, s.z >> 16, s.w & 0xFFFFu, s.w >> 16};
         float B[12];
-        for (int k = 0; k < 4; ++k) {
-            const float w = float(wq[k]) / 65535.0f;
-            const float4 *m = bones + 3ull * min(bone[k], uint32_t(RPTR_MAX_BONES - 1)); // (set_skin checked the index: the clamp only guards the table)
-            for (int r = 0; r < 3; ++r) {
-                const float4 row = m[r];
-                const float t[4] = {w * row.x, w * row.y, w * row.z, w * row.w};
-                for (int c = 0; c < 4; ++c) B[4 * r + c] = k == 0 ? t[c] : B[4 * r + c] + t[c];
-            }
-        }
+        rp_skin_blend(skin[i], bones, B);
         const float x = rest_pos[3ull * i], y = rest_pos[3ull * i + 1], z = rest_pos[3ull * i + 2];
         float p[3];
         for (int r = 0; r < 3; ++r) p[r] = rp_place_coord(B + 4 * r, x, y, z);
@@ -71,12 +88,8 @@ __global__ __launch_bounds__(256) void rp_k_skin(const uint4 *skin, const float 
         }
         out_pos[3ull * i] = p[0], out_pos[3ull * i + 1] = p[1], out_pos[3ull * i + 2] = p[2];
         if (!out_nrm) continue;
-        const V3 n = rp_dequantize_normal(rest_nrm[i]);
-        const V3 A0 = v3(B[0], B[1], B[2]), A1 = v3(B[4], B[5], B[6]), A2 = v3(B[8], B[9], B[10]);
-        const V3 C0 = cross3(A1, A2), C1 = cross3(A2, A0), C2 = cross3(A0, A1);
-        V3 q = v3(dot3(C0, n), dot3(C1, n), dot3(C2, n));
-        if (dot3(A0, C0) < 0.0f) q = -q;
-        if (!(isfinite(q.x) && isfinite(q.y) && isfinite(q.z)) || (q.x == 0.0f && q.y == 0.0f && q.z == 0.0f)) continue;
+        const V3 q = rp_skin_normal(B, rp_dequantize_normal(rest_nrm[i]));
+        if (!rp_skin_normal_usable(q)) continue;
         out_nrm[i] = rp_quantize_normal(q);
     }
 }

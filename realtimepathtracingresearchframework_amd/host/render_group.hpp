@@ -83,6 +83,16 @@ public:
     void skin() {
         for (auto &r : ranks_) r->skin();
     }
+    void set_morph_targets(uint32_t geometry, const std::vector<std::vector<RptrMorphDelta>> &targets) { // every rank is bound
+        for (auto &r : ranks_) r->set_morph_targets(geometry, targets);
+    }
+    void update_morph_weights(uint32_t geometry, uint32_t first_target, uint32_t count, const float *weights) {
+        for (auto &r : ranks_) r->update_morph_weights(geometry, first_target, count, weights);
+    }
+    // (device memory belongs to one GPU: rank k reads device_weights[k])
+    void update_morph_weights_device(uint32_t geometry, uint32_t first_target, uint32_t count, const std::vector<const float *> &device_weights) {
+        for (size_t k = 0; k < ranks_.size(); ++k) ranks_[k]->update_morph_weights_device(geometry, first_target, count, device_weights.at(k));
+    }
     std::vector<float> readback_skinned(uint32_t geometry, uint32_t num_vertices, std::vector<uint32_t> *normal_words = nullptr) { // (the ranks' buffers are equal)
         return ranks_[0]->readback_skinned(geometry, num_vertices, normal_words);
     }

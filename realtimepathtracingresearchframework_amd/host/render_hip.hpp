@@ -148,6 +148,20 @@ public:
     void update_bones_device(uint32_t first, uint32_t count, const float *device_transforms12) {
         check(rptr_hip_update_bones_device(h_, first, count, device_transforms12));
     }
+    // morph targets: the stage in front of the skinner. One vector of RptrMorphDelta per target (sparse: the unrolled vertices the target
+    // moves, each at most once; a target may be empty); the weights start at zero; no targets at all unbinds. skin() runs both deformers.
+    void set_morph_targets(uint32_t geometry, const std::vector<std::vector<RptrMorphDelta>> &targets) {
+        flush_pipeline();
+        std::vector<RptrMorphTargetDesc> descs(targets.size());
+        for (size_t t = 0; t < targets.size(); ++t) descs[t] = RptrMorphTargetDesc{targets[t].empty() ? nullptr : targets[t].data(), (uint32_t)targets[t].size(), 0u};
+        check(rptr_hip_set_morph_targets(h_, geometry, descs.empty() ? nullptr : descs.data(), (uint32_t)descs.size()));
+    }
+    void update_morph_weights(uint32_t geometry, uint32_t first_target, uint32_t count, const float *weights) {
+        check(rptr_hip_update_morph_weights(h_, geometry, first_target, count, weights));
+    }
+    void update_morph_weights_device(uint32_t geometry, uint32_t first_target, uint32_t count, const float *device_weights) {
+        check(rptr_hip_update_morph_weights_device(h_, geometry, first_target, count, device_weights));
+    }
     void skin() { check(rptr_hip_skin(h_)); }
     // the master copy's positions (3 floats per vertex) and, when `normal_words` is given, normal words of a bound geometry
     std::vector<float> readback_skinned(uint32_t geometry, uint32_t num_vertices, std::vector<uint32_t> *normal_words = nullptr) {

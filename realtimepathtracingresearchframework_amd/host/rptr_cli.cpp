@@ -39,6 +39,11 @@
 //    bones) and frames x bones x 12 float32. Frame k of the run stages the bones of frame k mod frames, skins on the device
 //    (rptr_hip_skin) and refits before it renders; positions AND shading normals follow. One flag without the other, --animate-wave
 //    beside them, a mesh 0 that is not dynamic or a file of the wrong size: exit code 2 before a device is touched.
+//  * --morph <file> --morph-weights <file> (the same modes, alone or together with --skin --bones): the morph file holds uint32 targets,
+//    then per target uint32 deltas and that many 32-byte RptrMorphDelta records, for geometry first_geometry of mesh 0; the weights file
+//    two uint32 (frames, targets) and frames x targets float32. Frame k stages the weights of frame k mod frames, then skins (the morph
+//    stage runs in front of the skin) and refits. One flag without the other, a size mismatch, a target count that differs between the
+//    two files or a static mesh 0: exit code 2 before a device is touched.
 //  * data-capture mode (--data-capture <prefix> [--data-capture-spp n] [--data-capture-no-rgba] [--data-capture-no-aovs]
 //    [--data-capture-albedo-roughness|-normal-depth|-motion]) stores the accumulation buffer and the chosen AOV images of every
 //    keyframe as <prefix>_%04d_{rgba,albedo_roughness,normal_depth,motion_jitter}.exr (libapp/app_state.cpp:499-531).
@@ -219,6 +224,7 @@ int main(int argc, char **argv) {
     int rng_variant = -1, force_bvh_rebuild = -1, rebuild_triangle_budget = -1; // -1: as the configuration files say
     std::string bn_table_path, dump_scene_path, sky_data;
     std::string skin_path, bones_path; // --skin / --bones: a skinned mesh 0 (rptr_hip_set_skin / update_bones / skin)
+    std::string morph_path, morph_weights_path; // --morph / --morph-weights: morph targets on mesh 0 (rptr_hip_set_morph_targets / update_morph_weights)
     bool got_frames_per_launch = false;
     int upscale = 0, stripe_rows = 8, frames_in_flight = 0, frames_per_launch = 1; // frames_in_flight 0: the reference's loop (two swap buffers)
     bool synchronous = false, fly_through = false;
@@ -257,6 +263,8 @@ int main(int argc, char **argv) {
         else if (a == "--animate-wave") { need(2); wave_amp = (float)std::atof(argv[++i]); wave_k = (float)std::atof(argv[++i]); }
         else if (a == "--skin") { need(1); skin_path = argv[++i]; }
         else if (a == "--bones") { need(1); bones_path = argv[++i]; }
+        else if (a == "--morph") { need(1); morph_path = argv[++i]; }
+        else if (a == "--morph-weights") { need(1); morph_weights_path = argv[++i]; }
         else if (a == "--denoise") { need(1); g_denoise_iterations = std::atoi(argv[++i]); if (g_denoise_iterations < 1 || g_denoise_iterations > 5) { std::fprintf(stderr, "--denoise takes 1..5 iterations\n"); return 2; } }
         else if (a == "--denoise-temporal") { need(1); g_denoise_temporal_iterations = std::atoi(argv[++i]); if (g_denoise_temporal_iterations < 1 || g_denoise_temporal_iterations > 5) { std::fprintf(stderr, "--denoise-temporal takes 1..5 iterations\n"); return 2; } }
         else if (a == "--taa-upscale") g_taa_upscale = true;
@@ -458,6 +466,16 @@ int main(int argc, char **argv) {
             return 2;
         }
     }
+    if (!morph_path.empty() || !morph_weights_path.empty()) {
+        const char *why = nullptr;
+        if (morph_path.empty() || morph_weights_path.empty()) why = "go together: the targets of mesh 0's vertices and the weights of every frame";
+        else if (wave_amp != 0.f) why = "cannot be combined with --animate-wave: both write the vertices of mesh 0";
+        else if (validation) why = "need --profiling or --data-capture: a validation run accumulates one still scene";
+        if (why) {
+            std::fprintf(stderr, "--morph and --morph-weights %s\n", why);
+            return 2;
+        }
+    }
     if (want_help) scene_path.clear(); // prints the usage
     if (scene_path.empty() || (int)validation + (int)profiling + (int)data_capture != 1 || batch_spp < 1 || width < 1 || height < 1 || (profiling && profiling_frames < 1)) {
         std::fprintf(stderr, "usage: rptr_hip <scene.rpsc> (--validation <prefix> [--validation-spp n] | --profiling <csv prefix> [--profiling-fps f] "
@@ -549,18 +567,18 @@ int main(int argc, char **argv) {
         std::vector<RptrSkinVertex> skin_records;
         std::vector<float> bone_frames;
         uint32_t n_bone_frames = 0, n_bones = 0;
+        auto slurp = [](const std::string &path, std::vector<char> &out) {
+            FILE *f = std::fopen(path.c_str(), "rb");
+            if (!f) return false;
+            std::fseek(f, 0, SEEK_END);
+            const long n = std::ftell(f);
+            std::fseek(f, 0, SEEK_SET);
+            out.resize(n > 0 ? (size_t)n : 0);
+            const bool ok = out.empty() || std::fread(out.data(), 1, out.size(), f) == out.size();
+            std::fclose(f);
+            return ok;
+        };
         if (skinned) {
-            auto slurp = [](const std::string &path, std::vector<char> &out) {
-                FILE *f = std::fopen(path.c_str(), "rb");
-                if (!f) return false;
-                std::fseek(f, 0, SEEK_END);
-                const long n = std::ftell(f);
-                std::fseek(f, 0, SEEK_SET);
-                out.resize(n > 0 ? (size_t)n : 0);
-                const bool ok = out.empty() || std::fread(out.data(), 1, out.size(), f) == out.size();
-                std::fclose(f);
-                return ok;
-            };
             if (scene.meshes.empty() || !(scene.meshes[0].dynamic & (RPTR_MESH_DYNAMIC | RPTR_MESH_SUBTLY_DYNAMIC))) {
                 std::fprintf(stderr, "--skin needs a scene whose mesh 0 is dynamic\n");
                 return 2;
@@ -586,6 +604,61 @@ int main(int argc, char **argv) {
             bone_frames.resize((size_t)n_bone_frames * n_bones * 12);
             std::memcpy(bone_frames.data(), raw.data() + 8, bone_frames.size() * sizeof(float));
         }
+        // --morph <file>: uint32 targets, then per target uint32 deltas and that many RptrMorphDelta records, for the same geometry;
+        // --morph-weights <file>: two uint32 (frames, targets), then frames x targets float32. Checked like the two above.
+        const bool morphed = !morph_path.empty();
+        const bool deformed = skinned || morphed; // mesh 0 is posed before every frame
+        std::vector<std::vector<RptrMorphDelta>> morph_targets;
+        std::vector<float> morph_weight_frames;
+        uint32_t n_weight_frames = 0, n_morph_targets = 0;
+        if (morphed) {
+            if (scene.meshes.empty() || !(scene.meshes[0].dynamic & (RPTR_MESH_DYNAMIC | RPTR_MESH_SUBTLY_DYNAMIC))) {
+                std::fprintf(stderr, "--morph needs a scene whose mesh 0 is dynamic\n");
+                return 2;
+            }
+            const size_t n_vertices = (size_t)scene.geometries[scene.meshes[0].first_geometry].num_tris * 3;
+            std::vector<char> raw;
+            uint32_t file_targets = 0;
+            bool ok = slurp(morph_path, raw) && raw.size() >= 4;
+            size_t at = 4;
+            if (ok) std::memcpy(&file_targets, raw.data(), 4);
+            ok = ok && file_targets >= 1 && file_targets <= RPTR_MAX_MORPH_TARGETS;
+            for (uint32_t t = 0; ok && t < file_targets; ++t) {
+                uint32_t deltas = 0;
+                ok = raw.size() - at >= 4;
+                if (!ok) break;
+                std::memcpy(&deltas, raw.data() + at, 4);
+                at += 4;
+                ok = (raw.size() - at) / sizeof(RptrMorphDelta) >= deltas;
+                if (!ok) break;
+                morph_targets.emplace_back(deltas);
+                if (deltas) std::memcpy(morph_targets.back().data(), raw.data() + at, (size_t)deltas * sizeof(RptrMorphDelta));
+                at += (size_t)deltas * sizeof(RptrMorphDelta);
+                for (const RptrMorphDelta &d : morph_targets.back()) ok = ok && d.vertex < n_vertices;
+            }
+            if (!ok || at != raw.size()) {
+                std::fprintf(stderr, "--morph %s: %zu bytes do not hold uint32 targets (%u of at most %d) and per target uint32 deltas and that many %zu-byte records "
+                                     "that name the %zu unrolled vertices of geometry %u\n",
+                             morph_path.c_str(), raw.size(), file_targets, RPTR_MAX_MORPH_TARGETS, sizeof(RptrMorphDelta), n_vertices, scene.meshes[0].first_geometry);
+                return 2;
+            }
+            if (slurp(morph_weights_path, raw) && raw.size() >= 8) {
+                std::memcpy(&n_weight_frames, raw.data(), 4);
+                std::memcpy(&n_morph_targets, raw.data() + 4, 4);
+            }
+            if (n_weight_frames < 1 || n_morph_targets < 1 || n_morph_targets > RPTR_MAX_MORPH_TARGETS || raw.size() != 8 + (size_t)n_weight_frames * n_morph_targets * 4) {
+                std::fprintf(stderr, "--morph-weights %s: %zu bytes do not hold a header of two uint32 (frames %u, targets %u of at most %d) and frames x targets float32\n",
+                             morph_weights_path.c_str(), raw.size(), n_weight_frames, n_morph_targets, RPTR_MAX_MORPH_TARGETS);
+                return 2;
+            }
+            if (n_morph_targets != file_targets) {
+                std::fprintf(stderr, "--morph-weights %s holds weights for %u targets, --morph %s holds %u targets\n", morph_weights_path.c_str(), n_morph_targets,
+                             morph_path.c_str(), file_targets);
+                return 2;
+            }
+            morph_weight_frames.resize((size_t)n_weight_frames * n_morph_targets);
+            std::memcpy(morph_weight_frames.data(), raw.data() + 8, morph_weight_frames.size() * sizeof(float));
+        }
         if (frames_in_flight == 1) synchronous = true; // (one frame context: nothing to overlap)
         // frame contexts: the reference's two swap buffers; what --frames-in-flight asks for; four for a queued --validation accumulation
         // (its launch sequences are independent of the display: the deeper queue is what fills the GPU)
@@ -608,9 +681,13 @@ int main(int argc, char **argv) {
         }
         // --skin / --bones: mesh 0's first geometry is bound at its rest pose; pose(k) stages the bones of the file's frame k mod frames,
         // skins and refits (positions, shading normals and -- with registered sources -- lights follow)
+        // --morph / --morph-weights: the same geometry gets its targets; pose(k) stages the weights of the file's frame k mod frames first
+        // (the morph stage runs in front of the skin, from the one rest pose the two share)
         if (skinned) backend.set_skin(scene.meshes[0].first_geometry, skin_records);
+        if (morphed) backend.set_morph_targets(scene.meshes[0].first_geometry, morph_targets);
         auto pose = [&](uint64_t k) {
-            backend.update_bones(0, n_bones, &bone_frames[(size_t)(k % n_bone_frames) * n_bones * 12]);
+            if (skinned) backend.update_bones(0, n_bones, &bone_frames[(size_t)(k % n_bone_frames) * n_bones * 12]);
+            if (morphed) backend.update_morph_weights(scene.meshes[0].first_geometry, 0, n_morph_targets, &morph_weight_frames[(size_t)(k % n_weight_frames) * n_morph_targets]);
             backend.skin();
             backend.refit();
         };
@@ -758,13 +835,13 @@ int main(int argc, char **argv) {
             (void)capture_fps;
             // --object-motion: one capture per frame of the file's animation instead, the motion image rewritten before it is stored
             // --skin / --bones without keyframes: one capture per frame of the bones file, each at its pose
-            const size_t n_keys = g_object_motion ? (size_t)anim.numFrames : skinned && frames.empty() ? (size_t)n_bone_frames : std::max<size_t>(1, frames.size());
+            const size_t n_keys = g_object_motion ? (size_t)anim.numFrames : deformed && frames.empty() ? (size_t)(skinned ? n_bone_frames : n_weight_frames) : std::max<size_t>(1, frames.size());
             for (size_t k = 0; k < n_keys; ++k) {
                 if (g_object_motion) {
                     if (k) play(g_load.frame + k);
                     cfg.reset_accumulation = true;
                 }
-                if (skinned) {
+                if (deformed) {
                     pose(k);
                     cfg.reset_accumulation = true;
                 }
@@ -879,7 +956,7 @@ int main(int argc, char **argv) {
                         p.reset = true;
                     }
                 }
-                if (!rest.empty() || g_object_motion || skinned) p.reset = true; // the geometry moves: the accumulation starts over
+                if (!rest.empty() || g_object_motion || deformed) p.reset = true; // the geometry moves: the accumulation starts over
                 p.camera = cam;
                 if (fly_through) { // a moved camera restarts the accumulation (the application resets when the view changes) ...
                     p.camera = fly_camera(frame);
@@ -919,7 +996,7 @@ int main(int argc, char **argv) {
         // frames of one keyframe, every frame with its own view (rptr_hip_render_batch_cameras_async), n sequences in flight -- the schedule
         // bench.py times (the library asks the HIP runtime for a hardware queue per frame context itself: csrc/rptr_hip.hip
         // ensure_hw_queues). One CSV row per frame as it is collected; render_time_ms is the frame's share of its sequence.
-        if (frames_in_flight > 1 && rest.empty() && !skinned && !freeze_frame && !g_object_motion) {
+        if (frames_in_flight > 1 && rest.empty() && !deformed && !freeze_frame && !g_object_motion) {
             frames_per_launch = std::min(frames_per_launch, std::max(1, 16 / std::max(1, batch_spp)));
             // reprojection_mode 2 folds each frame into the one before it: one frame per launch sequence (include/rptr_hip.h)
             bool realtime = base.params.reprojection_mode == 2;
@@ -1013,7 +1090,7 @@ int main(int argc, char **argv) {
                 backend.update_vertices(scene.meshes[0].first_geometry, cur.data(), (uint32_t)(cur.size() / 3));
                 backend.refit();
             }
-            if (skinned) pose((uint64_t)frame); // the bones of this frame: skin, refit, and the accumulation starts over
+            if (deformed) pose((uint64_t)frame); // the bones and morph weights of this frame: skin, refit, and the accumulation starts over
             if (g_object_motion && frame) play(g_load.frame + (uint64_t)frame); // the file's next frame: new transforms, refit
             const rptr::RenderStats st = backend.frame(cmd_stream, config_of(fp));
             if (g_object_motion) {

@@ -1,0 +1,495 @@
+"""Morph targets on the GPU (csrc/morph.h; rptr_hip_set_morph_targets / update_morph_weights / skin / readback_skinned) against
+tests/morph_ref.py.
+
+Every comparison is exact: the kernel and the restatement perform the same IEEE binary32 operations in the same order (the library is built
+without contraction; a vertex's entries are summed in ascending target index on both sides), and everything behind the deformers -- refit,
+device rebuild, frames, queries, lights, object motion -- is compared between a renderer that was given targets and weights and one that
+was given the same shape as finished vertices and normals, byte for byte.
+
+The scene, the chain rig and the observation helpers are those of tests/test_gpu_skin.py: scenes.grid(7, 5) as a dynamic mesh with normals
+(210 unrolled vertices: no launch is full) and a second dynamic mesh of 12 loose triangles without normals. The grid gets 301 targets:
+target 0 dense, target 1 a patch of 20 vertices, target 2 the last vertex alone (the end of the offsets array is read), target 300 (an
+index above 255) a patch that overlaps target 1, all others empty -- vertices with 1, 2 and 3 entries. The loose mesh gets two sparse
+targets without normal deltas that leave some vertices with no entry at all. Weight sets: all zero, one-hot, and a mixed set with a
+negative weight and one above 1. Frames are 48 x 32."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import morph_ref as MR
+import skin_ref as S
+import test_gpu_skin as TS
+from common import config, float_bits, read_frame, renderer, same_images
+from realtimepathtracingresearchframework_amd import abi, backend, scenes
+
+pytestmark = pytest.mark.gpu
+
+W, H = TS.W, TS.H
+N_TARGETS = 301
+f32 = np.float32
+
+
+# ------------------------------------------------------------------ targets, weight sets, reference shapes
+def _nearest(P, point, k, exclude=()):
+    d = np.linalg.norm(P.astype(np.float64) - np.asarray(point, np.float64), axis=1)
+    d[list(exclude)] = np.inf
+    return np.argsort(d, kind="stable")[:k].astype(np.uint32)
+
+
+def _grid_targets(scene, n_targets=N_TARGETS, patch=20, seed=5):
+    """target 0 dense, 1 a patch, 2 the last vertex, n_targets - 1 (if there are more than three) a patch overlapping target 1; all others
+    empty; deltas listed in random order"""
+    P, _ = TS._rest(scene, 0)
+    n = len(P)
+    rng = np.random.default_rng(seed)
+    lo, hi = P.min(axis=0), P.max(axis=0)
+    size = float((hi - lo).max())
+    c1 = lo + (hi - lo) * np.array([0.3, 0.5, 0.4])
+    p1 = _nearest(P, c1, patch, exclude=[n - 1])
+    # the second patch: half of the first one's vertices and as many others near it
+    p2 = np.concatenate([p1[::2], _nearest(P, c1, 2 * patch, exclude=[n - 1] + p1.tolist())[:patch - len(p1[::2])]]).astype(np.uint32)
+    verts = {0: rng.permutation(n).astype(np.uint32), 1: rng.permutation(p1), 2: np.array([n - 1], np.uint32)}
+    if n_targets > 3:
+        verts[n_targets - 1] = rng.permutation(p2)
+    out = []
+    for t in range(n_targets):
+        v = verts.get(t, np.zeros(0, np.uint32))
+        out.append((v, (rng.uniform(-0.04, 0.04, (len(v), 3)) * size).astype(f32), rng.uniform(-0.8, 0.8, (len(v), 3)).astype(f32)))
+    counts = np.bincount(np.concatenate([t[0] for t in out]).astype(np.int64), minlength=n)
+    assert set(counts.tolist()) == ({1, 2, 3} if n_targets > 3 else {1, 2}) and counts[n - 1] == 2
+    return out
+
+
+def _loose_targets(scene, seed=6):
+    P, _ = TS._rest(scene, 1)
+    n = len(P)
+    rng = np.random.default_rng(seed)
+    va, vb = np.arange(0, n, 2, dtype=np.uint32), np.arange(0, n, 3, dtype=np.uint32)
+    out = [(rng.permutation(v), rng.uniform(-2, 2, (len(v), 3)).astype(f32), None) for v in (va, vb)]
+    counts = np.bincount(np.concatenate([va, vb]).astype(np.int64), minlength=n)
+    assert {0, 1, 2} == set(counts.tolist())
+    return out
+
+
+def _weights(kind, n_targets=N_TARGETS):
+    """per geometry the weight table of one set"""
+    w0, w1 = np.zeros(n_targets, f32), np.zeros(2, f32)
+    if kind == "one-hot":
+        w0[1], w1[0] = 1.0, 1.0
+    elif kind == "mixed":
+        w0[0], w0[1], w0[2], w0[n_targets - 1] = 0.6, -0.8, 1.0, 1.7
+        w1[:] = (-0.5, 1.3)
+    elif kind == "other":
+        w0[0], w0[1], w0[n_targets - 1] = -0.3, 0.45, 0.9
+        w1[:] = (0.7, 0.0)
+    else:
+        assert kind == "zero"
+    return [w0, w1]
+
+
+class Shape:
+    """the reference's result for one weight set (and bone table): per geometry positions and normal words, never changed afterwards.
+    It has the attributes test_gpu_skin's helpers read from a Pose."""
+
+    def __init__(self, scene, targets, weights, skin0=None):
+        self.weights = weights
+        self.M = None if skin0 is None else skin0[2]
+        self.pos, self.words = [], []
+        for g in range(2):
+            P, words = TS._rest(scene, g)
+            p, w, rejected = MR.morph(P, words, targets[g], weights[g], skin=skin0 if g == 0 else None)
+            assert not rejected.any()
+            p.setflags(write=False)
+            self.pos.append(p)
+            self.words.append(w)
+
+
+def _bind(r, targets, geometries=(0, 1)):
+    for g in geometries:
+        r.set_morph_targets(g, targets[g])
+
+
+def _shape_with_weights(r, weights, geometries=(0, 1), M=None):
+    for g in geometries:
+        r.update_morph_weights(g, 0, weights[g])
+    if M is not None:
+        r.update_bones(0, M[:5])
+        r.update_bones(TS.GROUP_BONE, M[TS.GROUP_BONE:TS.GROUP_BONE + 1])
+    r.skin()
+    r.refit()
+
+
+def _assert_readback(r, shape, geometries=(0, 1)):
+    for g in geometries:
+        xyz, words = r.readback_skinned(g)
+        assert np.array_equal(float_bits(xyz), float_bits(shape.pos[g])), "positions of geometry %d" % g
+        if shape.words[g] is None:
+            assert words is None
+        else:
+            bad = np.nonzero(words != shape.words[g])[0]
+            assert len(bad) == 0, "normal words of geometry %d differ at %s" % (g, bad[:8])
+
+
+@pytest.fixture(scope="module")
+def setup():
+    scene = TS._scene()
+    targets = [_grid_targets(scene), _loose_targets(scene)]
+    shapes = {kind: Shape(scene, targets, _weights(kind)) for kind in ("zero", "one-hot", "mixed", "other")}
+    return scene, targets, shapes
+
+
+# ------------------------------------------------------------------ 1. the kernel against the restatement
+def test_readback_equals_the_reference(setup):
+    scene, targets, shapes = setup
+    r = renderer(scene, W, H)
+    _bind(r, targets)
+    for kind in ("mixed", "zero", "one-hot", "zero"):
+        _shape_with_weights(r, shapes[kind].weights)
+        _assert_readback(r, shapes[kind])
+        if kind == "zero":                                              # the rest arrays themselves, positions and words
+            for g in range(2):
+                P, words = TS._rest(scene, g)
+                xyz, got = r.readback_skinned(g)
+                assert np.array_equal(float_bits(xyz), float_bits(P)) and (words is None or np.array_equal(got, words))
+    rest_words = TS._rest(scene, 0)[1]
+    assert not np.array_equal(shapes["mixed"].words[0], rest_words) and not np.array_equal(float_bits(shapes["one-hot"].pos[1]), float_bits(TS._rest(scene, 1)[0]))
+    assert r.get_option("skin_vertices_rejected") == 0
+    r.close()
+
+
+def test_readback_equals_the_reference_over_many_blocks():
+    scene = TS._scene(120, 90)
+    targets = [_grid_targets(scene, n_targets=3, patch=5000), _loose_targets(scene)]
+    assert len(targets[0][0][0]) == 64800
+    w = [np.array([0.6, -0.8, 1.7], f32), np.array([-0.5, 1.3], f32)]
+    shape = Shape(scene, targets, w)
+    r = renderer(scene, W, H)
+    _bind(r, targets)
+    _shape_with_weights(r, w)
+    _assert_readback(r, shape)
+    r.close()
+
+
+# ------------------------------------------------------------------ 2. morph and skin together, in either binding order
+@pytest.fixture(scope="module")
+def rigged(setup):
+    scene, targets, shapes = setup
+    rig = TS._rig(scene)
+    M = TS._bones(31)
+    skin0 = (rig[0][0], rig[0][1], M)
+    return rig, M, {kind: Shape(scene, targets, _weights(kind), skin0=skin0) for kind in ("zero", "mixed")}
+
+
+def test_morph_in_front_of_a_skin(setup, rigged):
+    scene, targets, shapes = setup
+    rig, M, skinned = rigged
+    r = renderer(scene, W, H)
+    r.set_skin(0, *rig[0])
+    _bind(r, targets)
+    _shape_with_weights(r, skinned["mixed"].weights, M=M)
+    _assert_readback(r, skinned["mixed"])
+    assert not np.array_equal(float_bits(skinned["mixed"].pos[0]), float_bits(skinned["zero"].pos[0]))
+    _shape_with_weights(r, skinned["zero"].weights, M=M)
+    _assert_readback(r, skinned["zero"])
+    P, words = TS._rest(scene, 0)                                       # zero weights: bit for bit what rp_k_skin writes
+    pos, w, _ = S.skin(P, words, rig[0][0], rig[0][1], M)
+    xyz, got = r.readback_skinned(0)
+    assert np.array_equal(float_bits(xyz), float_bits(pos)) and np.array_equal(got, w)
+    # ... and after the targets are gone the geometry is skinned by rp_k_skin itself, from the same rest pose
+    r.set_morph_targets(0, None)
+    r.skin()
+    xyz, got = r.readback_skinned(0)
+    assert np.array_equal(float_bits(xyz), float_bits(pos)) and np.array_equal(got, w)
+    r.close()
+
+
+def test_the_binding_order_does_not_recapture_the_rest_pose(setup, rigged):
+    """targets first, a shape applied, THEN the skin: the skin's rest pose is the one the targets captured, not the morphed positions"""
+    scene, targets, shapes = setup
+    rig, M, skinned = rigged
+    a = renderer(scene, W, H)
+    a.set_skin(0, *rig[0])
+    _bind(a, targets)
+    _shape_with_weights(a, skinned["mixed"].weights, M=M)
+    b = renderer(scene, W, H)
+    _bind(b, targets)
+    _shape_with_weights(b, shapes["other"].weights)
+    _assert_readback(b, shapes["other"])
+    b.set_skin(0, *rig[0])
+    _shape_with_weights(b, skinned["mixed"].weights, M=M)
+    for r in (a, b):
+        _assert_readback(r, skinned["mixed"])
+    # the other way round: a skin with a pose applied, then NEW targets on the bound geometry
+    a.set_morph_targets(0, targets[0])
+    _shape_with_weights(a, skinned["zero"].weights, M=M)
+    _assert_readback(a, skinned["zero"])
+    a.close()
+    b.close()
+
+
+# ------------------------------------------------------------------ 3. skin() + refit is the same shape by the old road
+@pytest.mark.parametrize("rebuild", [False, True])
+@pytest.mark.parametrize("emissive", [False, True])
+def test_morph_and_refit_equal_finished_vertices_and_normals(emissive, rebuild):
+    """renderer A gets the rest scene, targets and weights; B a scene whose geometry carries the reference's normal words, and the
+    reference's positions through update_vertices; C the rest scene and the positions only. A == B byte for byte; A's normal image
+    differs from C's: the normals moved."""
+    scene = TS._scene(emissive=emissive)
+    targets = [_grid_targets(scene), _loose_targets(scene)]
+    shape = Shape(scene, targets, _weights("mixed"))
+    cam = TS._looking_at(scene, shape)
+    q = TS._queries(cam, shape)
+    a, b, c = renderer(scene, W, H), renderer(TS._with_normal_words(scene, shape.words[0]), W, H), renderer(scene, W, H)
+    for r in (a, b, c):
+        if emissive:
+            r.set_light_sources(scene)
+        if rebuild:
+            r.set_bvh_policy(force_bvh_rebuild=True)
+    _bind(a, targets)
+    _shape_with_weights(a, shape.weights)
+    TS._pose_with_vertices(b, shape)
+    TS._pose_with_vertices(c, shape)
+    oa, ob, oc = (TS._observe(r, scene, cam, q) for r in (a, b, c))
+    n_hit = int((oa[0][:, 0] >= 0).sum())
+    print("emissive %d rebuild %d: %d of %d query rays hit" % (emissive, rebuild, n_hit, len(q)))
+    assert n_hit > len(q) // 2
+    assert TS._same_observations(oa, ob)
+    assert np.array_equal(float_bits(oa[0]), float_bits(oc[0]))                        # the same surface ...
+    assert not np.array_equal(oa[2][3].view(np.uint16), oc[2][3].view(np.uint16))      # ... under other shading normals (normal + depth AOV)
+    assert oa[1]["normal"].tobytes() != oc[1]["normal"].tobytes()
+    if rebuild:
+        assert a.bvh_rebuild_count() >= 1 and a.bvh_rebuild_count() == b.bvh_rebuild_count()
+    if emissive:
+        la, lb = a.readback_lights(), b.readback_lights()
+        assert np.array_equal(float_bits(la), float_bits(lb)) and not np.array_equal(float_bits(la), float_bits(scene.lights))
+    for r in (a, b, c):
+        r.close()
+
+
+def test_frames_in_flight_equal_one_at_a_time(setup):
+    scene, targets, shapes = setup
+    order = [shapes[k] for k in ("mixed", "one-hot", "other")]
+    cam = TS._looking_at(scene, order[0])
+
+    def run(fif):
+        r = renderer(scene, W, H, frames_in_flight=fif)
+        _bind(r, targets)
+        images, queue = [], []
+
+        def collect():
+            r.wait(queue.pop(0))
+            images.append(read_frame(r, W, H))
+        for shape in order:
+            _shape_with_weights(r, shape.weights)
+            queue.append(r.render_async(config(scene, abi.VARIANT_GLTF, reset=True, camera=cam), spp=2))
+            if len(queue) >= fif:
+                collect()
+        while queue:
+            collect()
+        _assert_readback(r, order[-1])
+        r.close()
+        return images
+
+    ref, got = run(1), run(2)
+    for x, y in zip(ref, got):
+        assert same_images(x, y)
+    assert not same_images(ref[0], ref[1])
+
+
+# ------------------------------------------------------------------ 4. object motion
+def test_object_motion_follows_a_morphed_mesh(setup):
+    scene, targets, shapes = setup
+    order = [shapes["one-hot"], shapes["mixed"]]
+    cam = TS._looking_at(scene, order[1])
+
+    def run(morphed):
+        r = renderer(scene, W, H)
+        if morphed:
+            _bind(r, targets)
+        r.track_object_motion()
+        for shape in order:
+            if morphed:
+                _shape_with_weights(r, shape.weights)
+            else:
+                TS._pose_with_vertices(r, shape)
+            r.render(config(scene, abi.VARIANT_SIMPLE, reset=True, camera=cam), spp=1)
+        n = r.object_motion()
+        motion = read_frame(r, W, H)[4]
+        r.close()
+        return n, motion
+
+    (na, ma), (nb, mb) = run(True), run(False)
+    print("object motion: %d pixels rewritten" % na)
+    assert na == nb and na > 20
+    assert np.array_equal(ma.view(np.uint16), mb.view(np.uint16))
+
+
+# ------------------------------------------------------------------ 5. repeated shapes
+def test_ten_alternating_weight_sets_end_where_one_does(setup):
+    """the kernel reads the rest pose, never its own output"""
+    scene, targets, shapes = setup
+    r = renderer(scene, W, H)
+    _bind(r, targets)
+    for k in range(10):
+        _shape_with_weights(r, shapes[("mixed", "other")[k % 2]].weights)
+    _assert_readback(r, shapes["other"])
+    r.close()
+
+
+# ------------------------------------------------------------------ 6. the error convention
+def _raw_bind(r, geometry, records, num_deltas=None, desc_pad=None):
+    """rptr_hip_set_morph_targets with records (and descriptor fields) exactly as given"""
+    descs = (abi.MorphTargetDesc * max(len(records), 1))()
+    for k, rec in enumerate(records):
+        descs[k].deltas = C.cast(rec.ctypes.data, C.POINTER(abi.MorphDelta)) if rec is not None and len(rec) else None
+        descs[k].num_deltas = (0 if rec is None else len(rec)) if num_deltas is None else num_deltas[k]
+        descs[k]._pad = 0 if desc_pad is None else desc_pad[k]
+    r._check(r._L.rptr_hip_set_morph_targets(r._h, geometry, descs, len(records)))
+
+
+def test_refusals(setup):
+    scene, targets, shapes = setup
+    L = backend.load_library()
+    vp = C.c_void_p
+    small = [backend.RenderHip.morph_deltas(*t) for t in targets[0][:3]]
+    one = (abi.MorphTargetDesc * 1)()
+    w3 = np.zeros(3, f32)
+    assert L.rptr_hip_set_morph_targets(None, 0, one, 1) == abi.RPTR_E_INVALID
+    assert L.rptr_hip_update_morph_weights(None, 0, 0, 3, w3.ctypes.data_as(vp)) == abi.RPTR_E_INVALID
+    assert L.rptr_hip_update_morph_weights_device(None, 0, 0, 0, None) == abi.RPTR_E_INVALID
+    r = backend.RenderHip()
+    r.initialize(W, H)
+    state = {"shape": None}
+
+    def refused(call, *text):
+        with pytest.raises(backend.BackendError) as e:
+            call()
+        assert e.value.code == abi.RPTR_E_INVALID, str(e.value)
+        for t in text:
+            assert t in str(e.value), str(e.value)
+        if state["shape"] is not None:                                  # a refused call changed nothing
+            _assert_readback(r, state["shape"])
+
+    refused(lambda: r.set_morph_targets(0, targets[0]), "before set_scene")
+    refused(lambda: r.update_morph_weights(0, 0, w3), "before set_scene")
+    r.set_scene(scenes.grid(7, 5))                                      # a static mesh
+    refused(lambda: r.set_morph_targets(0, targets[0]), "dynamic")
+    r.set_scene(scene)
+    refused(r.skin, "no geometry is bound")
+    refused(lambda: r.readback_skinned(0), "no morph targets")
+    refused(lambda: r.update_morph_weights(0, 0, w3), "no morph targets")
+    refused(lambda: r.set_morph_targets(2, targets[0]), "dynamic")      # no such geometry
+    empty = (np.zeros(0, np.uint32), np.zeros((0, 3), f32), None)
+    refused(lambda: r.set_morph_targets(0, [empty] * (abi.MAX_MORPH_TARGETS + 1)), "1025", "1024")
+
+    def bad_records(field, index, value, target=1, delta=3):
+        recs = [x.copy() for x in small]
+        if index is None:
+            recs[target][field][delta] = value
+        else:
+            recs[target][field][delta, index] = value
+        return recs
+
+    def refusals_of_a_binding():
+        refused(lambda: _raw_bind(r, 0, bad_records("vertex", None, 210)), "target 1, delta 3", "vertex 210")
+        twice = bad_records("vertex", None, int(small[1]["vertex"][0]))
+        refused(lambda: _raw_bind(r, 0, twice), "target 1, delta 3", "twice")
+        refused(lambda: _raw_bind(r, 0, bad_records("dpos", 2, np.inf)), "target 1, delta 3", "not finite")
+        refused(lambda: _raw_bind(r, 0, bad_records("dnrm", 0, np.nan, target=0, delta=7)), "target 0, delta 7", "not finite")
+        refused(lambda: _raw_bind(r, 0, bad_records("_pad", None, 9)), "target 1, delta 3", "_pad")
+        refused(lambda: _raw_bind(r, 0, small, desc_pad=[0, 0, 4]), "target 2", "_pad")
+        refused(lambda: _raw_bind(r, 0, [small[0], None, small[2]], num_deltas=[len(small[0]), 5, 1]), "target 1", "NULL deltas")
+        assert L.rptr_hip_set_morph_targets(r._h, 0, None, 3) == abi.RPTR_E_INVALID and L.rptr_hip_set_morph_targets(r._h, 0, one, 0) == abi.RPTR_E_INVALID
+
+    refusals_of_a_binding()
+    refused(r.skin, "no geometry is bound")                             # none of the refused calls bound anything
+    _bind(r, targets)
+    _shape_with_weights(r, shapes["mixed"].weights)
+    state["shape"] = shapes["mixed"]
+    refusals_of_a_binding()                                             # ... nor do they disturb a geometry that is bound
+    # weights: a range beyond the targets, NULL, a geometry without targets, a weight that is not finite -- nothing is staged
+    refused(lambda: r.update_morph_weights(0, N_TARGETS - 2, w3), "301")
+    refused(lambda: r._check(L.rptr_hip_update_morph_weights(r._h, 0, 0, 3, None)), "NULL")
+    refused(lambda: r._check(L.rptr_hip_update_morph_weights_device(r._h, 0, N_TARGETS, 1, None)), "301")
+    bad = shapes["other"].weights[0].copy()
+    bad[N_TARGETS - 1] = np.inf
+    refused(lambda: r.update_morph_weights(0, 0, bad), "target 300", "not finite")
+    r.update_morph_weights(0, N_TARGETS - 1, shapes["mixed"].weights[0][-1:])   # the last row is a row
+    r.update_morph_weights(0, N_TARGETS, np.zeros(0, f32))                      # ... and an empty range at the end is a range
+    r.skin()
+    r.refit()
+    _assert_readback(r, shapes["mixed"])                                # the table is what it was
+    refused(lambda: r.readback_skinned(0, num_vertices=209), "210")
+    # unbinding: the geometry stays as last written and is no longer morphed
+    r.set_morph_targets(1, None)
+    _shape_with_weights(r, shapes["other"].weights, geometries=(0,))
+    state["shape"] = None
+    _assert_readback(r, shapes["other"], geometries=(0,))
+    refused(lambda: r.readback_skinned(1), "no morph targets")
+    refused(lambda: r.update_morph_weights(1, 0, shapes["other"].weights[1]), "no morph targets")
+    r.set_morph_targets(0, None)
+    refused(r.skin, "no geometry is bound")
+    # a new set_scene: no binding; a new binding starts from zero weights
+    _bind(r, targets)
+    r.set_scene(scene)
+    refused(r.skin, "no geometry is bound")
+    _bind(r, targets)
+    r.skin()
+    r.refit()
+    _assert_readback(r, shapes["zero"])
+    r.close()
+
+
+# ------------------------------------------------------------------ 7. rejected vertices
+def test_a_nan_weight_from_the_device_leaves_its_vertices_alone(setup):
+    """read-backs only: the poisoned state is never refitted, traced or rendered, and finite weights are applied before the handle closes"""
+    import torch
+    scene, targets, shapes = setup
+    r = renderer(scene, W, H)
+    _bind(r, targets)
+    first = shapes["one-hot"]
+    for g in range(2):
+        r.update_morph_weights(g, 0, first.weights[g])
+    r.skin()
+    _assert_readback(r, first)
+    w = shapes["mixed"].weights[0].copy()
+    w[1] = np.nan
+    buf = torch.from_numpy(w).cuda()
+    torch.cuda.synchronize()
+    r.update_morph_weights(0, 0, buf)                                   # (a device tensor: the library cannot see the values)
+    r.update_morph_weights(1, 0, shapes["mixed"].weights[1])
+    r.skin()
+    P, words = TS._rest(scene, 0)
+    pos, ww, rejected = MR.morph(P, words, targets[0], w, prev_pos=first.pos[0], prev_words=first.words[0])
+    named = np.zeros(len(P), bool)
+    named[targets[0][1][0]] = True
+    assert np.array_equal(rejected, named) and rejected.sum() == 20
+    xyz, gw = r.readback_skinned(0)
+    assert np.array_equal(float_bits(xyz), float_bits(pos)) and np.array_equal(gw, ww)
+    assert np.array_equal(float_bits(xyz[rejected]), float_bits(first.pos[0][rejected])) and np.array_equal(gw[rejected], first.words[0][rejected])
+    assert not np.array_equal(float_bits(xyz[~rejected]), float_bits(first.pos[0][~rejected]))
+    _assert_readback(r, shapes["mixed"], geometries=(1,))
+    assert r.get_option("skin_vertices_rejected") == 20
+    _shape_with_weights(r, shapes["mixed"].weights)
+    _assert_readback(r, shapes["mixed"])
+    assert r.get_option("skin_vertices_rejected") == 20
+    r.close()
+
+
+# ------------------------------------------------------------------ 8. a mesh without targets
+def test_a_mesh_without_targets_behaves_as_before(setup):
+    """mesh 0 never gets targets and gets its vertices through update_vertices, on a handle that morphs the OTHER mesh and on one that
+    never heard of morph targets: the same frames, byte for byte"""
+    scene, targets, shapes = setup
+    shape = shapes["mixed"]
+    cam = TS._looking_at(scene, shape)
+    q = TS._queries(cam, shape)
+    a, b = renderer(scene, W, H), renderer(scene, W, H)
+    _bind(a, targets, geometries=(1,))
+    a.update_vertices(0, shape.pos[0])
+    _shape_with_weights(a, shape.weights, geometries=(1,))
+    TS._pose_with_vertices(b, shape)
+    assert TS._same_observations(TS._observe(a, scene, cam, q), TS._observe(b, scene, cam, q))
+    a.close()
+    b.close()
