@@ -282,6 +282,7 @@ static inline bool raytrace_test_visibility(const Frame &f, float geometry_scale
 static inline float eval_direct_sun_light_pdf(const Frame &f) { return f.sp.sun_radiance[3] * sample_sun_dir_pdf(f.sp.sun_cos_angle); }
 
 static inline int binned_lights_bin_count(const Frame &f) { // pt_megakernel.glsl:103
+    if (f.sc->num_lights == 0) return 1; // a scene without lights: one (empty) bin, never chosen (render_impl hands sun weight 1 then)
     return (f.sc->num_lights + (f.lc.bin_size - 1)) / f.lc.bin_size;
 }
 // rendering/mc/lights_linear.glsl:129-137
@@ -319,7 +320,9 @@ static vec3 compute_sky_illum(const Frame &f, vec3 ray_dir, float prev_bsdf_pdf)
 
 // rendering/mc/lights_linear.glsl:19-127 (BINNED_LIGHTS_BIN_MAX_SIZE = 16, solid angle sampling)
 static vec3 sample_tri_lights(const Frame &f, const vec3 hit_p, const vec3 hit_n, vec2 dir_sample, vec2 sel_sample, vec3 &light_dir,
-                              float &light_dist, float &pdf, float &mis_wpdf) {
+                              float &light_dist, float &pdf, float &mis_wpdf, int *probe_bin = nullptr, float *probe_contributions = nullptr) {
+    // probe_bin / probe_contributions (orc_tri_light_bins): the chosen bin [begin, end), the light the selection ends on, and the
+    // RPTR_BINNED_LIGHTS_BIN_MAX_SIZE contributions (0 behind the bin's end)
     const RptrTriLightData *lights = f.sc->lights.data();
     int num_lights = f.sc->num_lights;
     const int BIN = f.lc.bin_size;
@@ -363,6 +366,9 @@ static vec3 sample_tri_lights(const Frame &f, const vec3 hit_p, const vec3 hit_n
         t += p;
         if (sel_sample.y < t) break;
     }
+    if (probe_bin) probe_bin[0] = BIN * bin_id, probe_bin[1] = bin_end, probe_bin[2] = light_id;
+    if (probe_contributions)
+        for (int i = 0; i < RPTR_BINNED_LIGHTS_BIN_MAX_SIZE; ++i) probe_contributions[i] = BIN * bin_id + i < bin_end ? light_contributions[i] : 0.0f;
     sel_p *= p;
     // note: the reference may leave light_id == bin_end here (one past the
     // bin) when rounding keeps sel_sample.y >= t; the light buffer is padded
@@ -883,6 +889,9 @@ static int render_impl(void *p, const OrcRenderArgs *a, float *accum, OrcRenderS
     f.rp = a->params;
     f.sp = a->scene_params;
     f.lc = a->lighting;
+    // a scene without lights sends every NEE sample to the sun whatever weight it is handed (vulkan/render_sky.cpp:67-70 hands w = 1 when
+    // light_count == 0): sample_tri_lights never runs on an empty table
+    if (s->num_lights == 0) f.sp.sun_radiance[3] = 1.0f;
 #ifdef ORC_BASELINE
     f.count = false;
 #else
@@ -1176,6 +1185,29 @@ void orc_sample_tri_lights(void *p, const RptrLightSamplingConfig *cfg, const fl
         dir3[3 * i] = ld.x; dir3[3 * i + 1] = ld.y; dir3[3 * i + 2] = ld.z;
         dist[i] = d; pdf[i] = pd; mis_wpdf[i] = mw;
     }
+}
+// orc_sample_tri_lights, plus what the selection went through: bins3 = (bin_begin, bin_end, the light the selection ended on) and the 16
+// contributions of the bin per shading point. -1 for a scene without lights or a bin size outside 1 .. RPTR_BINNED_LIGHTS_BIN_MAX_SIZE
+// (there is no bin to choose: the walk would index in front of the table), nothing written then.
+int orc_tri_light_bins(void *p, const RptrLightSamplingConfig *cfg, const float *p3, const float *n3, const float *u4, int n,
+                        float *radiance_over_pdf3, float *dir3, float *dist, float *pdf, float *mis_wpdf, int32_t *bins3, float *contributions16) {
+    Scene *s = (Scene *)p;
+    if (s->num_lights < 1 || cfg->bin_size < 1 || cfg->bin_size > RPTR_BINNED_LIGHTS_BIN_MAX_SIZE) return -1;
+    Frame f;
+    f.sc = s;
+    f.lc = *cfg;
+    for (int i = 0; i < n; ++i) {
+        vec3 ld;
+        float d = 0, pd = 0, mw = 0;
+        int bin[3];
+        vec3 L = sample_tri_lights(f, vec3(p3[3 * i], p3[3 * i + 1], p3[3 * i + 2]), vec3(n3[3 * i], n3[3 * i + 1], n3[3 * i + 2]),
+                                   vec2(u4[4 * i], u4[4 * i + 1]), vec2(u4[4 * i + 2], u4[4 * i + 3]), ld, d, pd, mw, bin, contributions16 + 16 * i);
+        radiance_over_pdf3[3 * i] = L.x; radiance_over_pdf3[3 * i + 1] = L.y; radiance_over_pdf3[3 * i + 2] = L.z;
+        dir3[3 * i] = ld.x; dir3[3 * i + 1] = ld.y; dir3[3 * i + 2] = ld.z;
+        dist[i] = d; pdf[i] = pd; mis_wpdf[i] = mw;
+        bins3[3 * i] = bin[0]; bins3[3 * i + 1] = bin[1]; bins3[3 * i + 2] = bin[2];
+    }
+    return 0;
 }
 // sample_direct_light (nee.glsl:32-90) for n shading points over one glTF material: interaction = (p, gn, n; v_x / v_y from ortho_basis(n)),
 // scene parameters from sp (sun direction / cone / radiance + sun weight), the scene's light table with cfg's bins; the visibility query traces

@@ -420,10 +420,12 @@ static void fill_frame_constants(rptr_hip_t *h, FrameCtx &c, const RptrCamera *c
     f.div_stripe_rows = rp_make_div((uint32_t)h->stripe_rows);
     f.div_width = rp_make_div((uint32_t)h->width);
     f.num_bins = (h->num_lights + (h->lighting.bin_size - 1)) / h->lighting.bin_size;
-    if (h->lights_disabled) { // LIGHT_SAMPLING_VARIANT_NONE (rendering/mc/nee.glsl:12-14): every NEE sample goes to the sun
+    if (h->lights_disabled || h->num_lights == 0) { // LIGHT_SAMPLING_VARIANT_NONE (rendering/mc/nee.glsl:12-14): every NEE sample goes to the sun
         // the adapter hands sun_radiance.w = 1 with this variant (vulkan/render_sky.cpp:67-70: light_count is 0 without the binned-lights
         // extension); emitters that are HIT keep their full weight: pdf of picking them = (1 - 1) / (bins x solid angle) with a bin count
-        // that must not be zero for that product to be 0 rather than NaN
+        // that must not be zero for that product to be 0 rather than NaN.
+        // A scene without lights gets the same rule whatever sun weight scene_params carries (the same file hands w = 1 when light_count
+        // == 0): with a weight below 1 the light-sampling kernels would choose bin -1 of 0 and read in front of the light table
         f.num_bins = std::max(f.num_bins, 1);
         f.sp.sun_radiance[3] = 1.0f;
     }

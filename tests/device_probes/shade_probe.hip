@@ -165,6 +165,79 @@ __global__ void k_tri_light(const float *v9, const float *u2, int n, float *out9
     o[0] = omega, o[1] = tan_half, o[2] = tp.x, o[3] = tp.y, o[4] = tp.z, o[5] = dir.x, o[6] = dir.y, o[7] = dir.z;
     o[8] = rp_frcp(omega);
 }
+// ---- binned light selection (orc_tri_light_bins' layout): the bin, the straight loop of 16 contributions, the selection among them
+__global__ void k_tri_lights(RpScene sc, RpFrame f, const float *p3, const float *n3, const float *u4, int n, float *radiance_over_pdf3, float *dir3,
+                             float *dist, float *pdf, float *mis_wpdf, int32_t *bins2, float *contributions16) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const V3 hp = ldv(p3, i), hn = ldv(n3, i);
+    const RpLightBin bin = rp_choose_light_bin(sc, f, u4[4 * i + 2]);
+    float c[RPTR_BINNED_LIGHTS_BIN_MAX_SIZE];
+    for (int k = 0; k < RPTR_BINNED_LIGHTS_BIN_MAX_SIZE; ++k) c[k] = rp_tri_light_contribution(sc, bin.bin_begin + k, bin.bin_end, hp, hn);
+    V3 light_dir = v3s(0.0f);
+    float light_dist = 0.0f, pp = 0.0f, mw = 0.0f;
+    const V3 L = rp_finish_tri_light_sample(sc, f, bin, [&](int k) { return c[k]; }, hp, v2(u4[4 * i], u4[4 * i + 1]), u4[4 * i + 3], light_dir,
+                                            light_dist, pp, mw);
+    stv(radiance_over_pdf3, i, L);
+    stv(dir3, i, light_dir);
+    dist[i] = light_dist, pdf[i] = pp, mis_wpdf[i] = mw;
+    bins2[2 * i] = bin.bin_begin, bins2[2 * i + 1] = bin.bin_end;
+    for (int k = 0; k < RPTR_BINNED_LIGHTS_BIN_MAX_SIZE; ++k) contributions16[16 * i + k] = c[k];
+}
+// ---- point sets: rp_rng_open<TABLE>, then rp_draw1<TABLE> at the absolute dimensions dims[0..n_single) in order, then rp_draw2<TABLE> at
+// dims[n_single], dims[n_single + 2], ... (a pair fills two columns: the host checks that dims[k + 1] == dims[k] + 1 there); 6 words per
+// query: width, sample_index, frame_offset, frame_id, px, py
+template <bool TABLE>
+__global__ void k_pointset(RpFrame f, const uint32_t *q6, int n, const uint32_t *dims, int n_single, int n_dims, float *draws, uint32_t *index) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t *q = q6 + 6 * i;
+    f.width = int32_t(q[0]);
+    RpSlotFrame sf;
+    sf.frame = 0u, sf.sample_index = q[1], sf.frame_offset = q[2], sf.frame_id = q[3];
+    RpRng r = rp_rng_open<TABLE>(f, sf, q[4], q[5]);
+    index[i] = r.index;
+    float *out = draws + (size_t)i * n_dims;
+    for (int k = 0; k < n_single; ++k) out[k] = rp_draw1<TABLE>(f, r, dims[k]);
+    for (int k = n_single; k + 1 < n_dims; k += 2) {
+        const V2 v = rp_draw2<TABLE>(f, r, dims[k]);
+        out[k] = v.x, out[k + 1] = v.y;
+    }
+}
+// out3: rp_randf, then rp_rand2 from the same state; after2: the state behind each
+__global__ void k_randf(const uint32_t *states, int n, float *out3, uint32_t *after2) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    uint32_t s = states[i], s2 = states[i];
+    out3[3 * i] = rp_randf(s);
+    const V2 v = rp_rand2(s2);
+    out3[3 * i + 1] = v.x, out3[3 * i + 2] = v.y;
+    after2[2 * i] = s, after2[2 * i + 1] = s2;
+}
+// ---- slot and index arithmetic
+__global__ void k_div(const uint32_t *nn, const RpDivU32 *d, int n, uint32_t *q) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) q[i] = rp_div(nn[i], d[i]);
+}
+// local3: (lx, ly, the pixel exists) of every slot; slot_of / global_row: of every pixel (lx, ly) of pix2
+__global__ void k_slots(RpFrame f, const uint32_t *slots, int n_slots, int32_t *local3, const int32_t *pix2, int n_pix, uint32_t *slot_of, int32_t *global_row) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_slots) {
+        int lx = 0, ly = 0;
+        const bool valid = rp_slot_to_local(f, slots[i], lx, ly);
+        local3[3 * i] = lx, local3[3 * i + 1] = ly, local3[3 * i + 2] = valid ? 1 : 0;
+    }
+    if (i < n_pix) {
+        slot_of[i] = rp_local_to_slot(f, pix2[2 * i], pix2[2 * i + 1]);
+        global_row[i] = rp_local_row_to_global(f, pix2[2 * i + 1]);
+    }
+}
+__global__ void k_slot_frame(RpFrame f, const uint32_t *sslots, int n, uint32_t *out4) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const RpSlotFrame sf = rp_slot_frame(f, sslots[i]);
+    out4[4 * i] = sf.frame, out4[4 * i + 1] = sf.sample_index, out4[4 * i + 2] = sf.frame_offset, out4[4 * i + 3] = sf.frame_id;
+}
 // ---- sun and MIS
 __global__ void k_sun(V3 sun_dir, float cos_radius, const float *u2, int n, float *dirs3, float *pdf) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -286,6 +359,173 @@ int sp_tri_light(const float *v9, const float *u2, int n, float *out9) {
     k_tri_light<<<blocks(n), kBlock>>>(dv, du, n, dout);
     if (launched("k_tri_light")) return 1;
     return copy_out(out9, dout, 9 * n);
+}
+// The light table as the library uploads it (host_scene.inl): num_lights records followed by RPTR_BINNED_LIGHTS_BIN_MAX_SIZE + 1 zeroed ones.
+// A selection that falls through its bin reads record bin_end <= num_lights, a bin's contributions records below bin_end: refused are an
+// empty table, a bin size outside 1 .. RPTR_BINNED_LIGHTS_BIN_MAX_SIZE and a bin sample u4[2] outside [0, 1] (the bin index would leave the table).
+int sp_tri_lights(const RptrTriLightData *lights, int num_lights, const RptrLightSamplingConfig *cfg, const float *p3, const float *n3, const float *u4,
+                  int n, float *radiance_over_pdf3, float *dir3, float *dist, float *pdf, float *mis_wpdf, int32_t *bins2, float *contributions16) {
+    if (!lights || !cfg || num_lights < 1 || cfg->bin_size < 1 || cfg->bin_size > RPTR_BINNED_LIGHTS_BIN_MAX_SIZE || n < 0) {
+        fprintf(stderr, "shade_probe: sp_tri_lights: %d lights in bins of %d\n", num_lights, cfg ? cfg->bin_size : 0);
+        return 2;
+    }
+    for (int i = 0; i < n; ++i)
+        if (!(u4[4 * i + 2] >= 0.0f && u4[4 * i + 2] <= 1.0f)) {
+            fprintf(stderr, "shade_probe: sp_tri_lights: bin sample %d is %g\n", i, (double)u4[4 * i + 2]);
+            return 2;
+        }
+    const size_t padded = (size_t)num_lights + RPTR_BINNED_LIGHTS_BIN_MAX_SIZE + 1;
+    Buffers b;
+    RptrTriLightData *dl;
+    const float *dp, *dn, *du;
+    float *dL, *dd, *dt, *dq, *dm, *dc;
+    int32_t *db;
+    if (b.alloc(dl, padded) || b.in(dp, p3, 3 * (size_t)n) || b.in(dn, n3, 3 * (size_t)n) || b.in(du, u4, 4 * (size_t)n) || b.alloc(dL, 3 * (size_t)n) ||
+        b.alloc(dd, 3 * (size_t)n) || b.alloc(dt, n) || b.alloc(dq, n) || b.alloc(dm, n) || b.alloc(db, 2 * (size_t)n) || b.alloc(dc, 16 * (size_t)n))
+        return 1;
+    SP_TRY(hipMemset(dl, 0, padded * sizeof(RptrTriLightData)));
+    SP_TRY(hipMemcpy(dl, lights, (size_t)num_lights * sizeof(RptrTriLightData), hipMemcpyHostToDevice));
+    RpScene sc{};
+    sc.lights = dl;
+    sc.num_lights = num_lights;
+    RpFrame f;
+    memset(&f, 0, sizeof f);
+    f.lc = *cfg;
+    f.num_bins = (num_lights + (cfg->bin_size - 1)) / cfg->bin_size; // host_frame.inl fill_frame_constants
+    k_tri_lights<<<blocks(n), kBlock>>>(sc, f, dp, dn, du, n, dL, dd, dt, dq, dm, db, dc);
+    if (launched("k_tri_lights")) return 1;
+    return copy_out(radiance_over_pdf3, dL, 3 * (size_t)n) || copy_out(dir3, dd, 3 * (size_t)n) || copy_out(dist, dt, n) || copy_out(pdf, dq, n) ||
+           copy_out(mis_wpdf, dm, n) || copy_out(bins2, db, 2 * (size_t)n) || copy_out(contributions16, dc, 16 * (size_t)n);
+}
+// table / table_words: the point set's whole table as rptr_hip_set_rng_variant takes it (every index the draws form lies inside it), NULL / 0
+// with the uniform generator; table_code: the rp_rng_open<TABLE> / rp_draw1<TABLE> instantiation (0 serves the uniform generator only)
+// dims[0..n_single) are drawn one by one, the rest in pairs (d, d + 1) through rp_draw2
+int sp_pointset(int rng_variant, int table_code, const uint32_t *table, size_t table_words, const uint32_t *q6, int n, const uint32_t *dims, int n_single,
+                int n_dims, float *draws, uint32_t *index) {
+    size_t need = 0;
+    if (rng_variant == RPTR_RNG_VARIANT_BN) need = size_t(RP_BN_SAMPLES) * RP_BN_DIMS + size_t(RP_BN_TILE) * RP_BN_TILE * RP_BN_SCR_DIMS;
+    else if (rng_variant == RPTR_RNG_VARIANT_SOBOL || rng_variant == RPTR_RNG_VARIANT_Z_SBL) need = size_t(RP_SOBOL_DIMS) * RP_SOBOL_BITS + size_t(RP_SOBOL_TILE) * RP_SOBOL_TILE;
+    else if (rng_variant != RPTR_RNG_VARIANT_UNIFORM) return 2;
+    bool pairs_ok = n_single >= 0 && n_single <= n_dims && (n_dims - n_single) % 2 == 0;
+    for (int k = n_single; pairs_ok && k + 1 < n_dims; k += 2) pairs_ok = dims[k + 1] == dims[k] + 1u;
+    if ((need && (!table || table_words < need)) || (need && !table_code) || n < 0 || n_dims < 0 || !pairs_ok) {
+        fprintf(stderr, "shade_probe: sp_pointset: point set %d with %zu table words, TABLE = %d\n", rng_variant, table_words, table_code);
+        return 2;
+    }
+    Buffers b;
+    const uint32_t *dtab = nullptr, *dq, *ddims;
+    float *ddraws;
+    uint32_t *dindex;
+    if ((need && b.in(dtab, table, need)) || b.in(dq, q6, 6 * (size_t)n) || b.in(ddims, dims, n_dims) || b.alloc(ddraws, (size_t)n * n_dims) || b.alloc(dindex, n))
+        return 1;
+    RpFrame f;
+    memset(&f, 0, sizeof f);
+    f.rng_variant = rng_variant;
+    f.rng_table = dtab;
+    if (table_code)
+        k_pointset<true><<<blocks(n), kBlock>>>(f, dq, n, ddims, n_single, n_dims, ddraws, dindex);
+    else
+        k_pointset<false><<<blocks(n), kBlock>>>(f, dq, n, ddims, n_single, n_dims, ddraws, dindex);
+    if (launched("k_pointset")) return 1;
+    return copy_out(draws, ddraws, (size_t)n * n_dims) || copy_out(index, dindex, n);
+}
+int sp_randf(const uint32_t *states, int n, float *out3, uint32_t *after2) {
+    Buffers b;
+    const uint32_t *ds;
+    float *dout;
+    uint32_t *da;
+    if (b.in(ds, states, n) || b.alloc(dout, 3 * (size_t)n) || b.alloc(da, 2 * (size_t)n)) return 1;
+    k_randf<<<blocks(n), kBlock>>>(ds, n, dout, da);
+    if (launched("k_randf")) return 1;
+    return copy_out(out3, dout, 3 * (size_t)n) || copy_out(after2, da, 2 * (size_t)n);
+}
+// q[i] = rp_div(n[i], rp_make_div(d[i])), the divisor records made by the header's own host function; d >= 1
+int sp_div(const uint32_t *nn, const uint32_t *d, int n, uint32_t *q) {
+    std::vector<RpDivU32> divs((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        if (d[i] < 1u) return 2;
+        divs[(size_t)i] = rp_make_div(d[i]);
+    }
+    Buffers b;
+    const uint32_t *dn;
+    const RpDivU32 *dd;
+    uint32_t *dq;
+    if (b.in(dn, nn, n) || b.in(dd, divs.data(), n) || b.alloc(dq, n)) return 1;
+    k_div<<<blocks(n), kBlock>>>(dn, dd, n, dq);
+    if (launched("k_div")) return 1;
+    return copy_out(q, dq, n);
+}
+namespace {
+struct SpGeometry {
+    int32_t width, height, rank, world, stripe_rows;
+};
+// the tile mapping of a frame as rptr_hip_initialize (rptr_hip.hip) and fill_frame_constants (host_frame.inl) set it. A COPY of those
+// host lines (local_row_count of host_state.h, tiles_x / tiles_y / npix_padded), made to feed the device functions a frame of the
+// product's shape: what sp_slot_geometry hands back, and what the tests compare with their own statement, is this copy, not the product's
+// host code (that is exercised by every rendered frame).
+bool slot_geometry(const SpGeometry &g, RpFrame &f) {
+    memset(&f, 0, sizeof f);
+    if (g.width < 1 || g.height < 1 || g.world < 1 || g.rank < 0 || g.rank >= g.world || g.stripe_rows < 1) return false;
+    f.width = g.width;
+    f.height = g.height;
+    f.rank = g.rank;
+    f.world = g.world;
+    f.stripe_rows = g.stripe_rows;
+    const int n_stripes = (g.height + g.stripe_rows - 1) / g.stripe_rows; // host_state.h local_row_count
+    for (int s = g.rank; s < n_stripes; s += g.world) f.local_rows += g.stripe_rows < g.height - s * g.stripe_rows ? g.stripe_rows : g.height - s * g.stripe_rows;
+    f.tiles_x = ((g.width + 7) / 8 + RP_TILE_BLOCK - 1) / RP_TILE_BLOCK * RP_TILE_BLOCK;
+    f.tiles_y = (((f.local_rows > 1 ? f.local_rows : 1) + 7) / 8 + RP_TILE_BLOCK - 1) / RP_TILE_BLOCK * RP_TILE_BLOCK;
+    f.npix_padded = f.tiles_x * f.tiles_y * 64;
+    f.div_npix_padded = rp_make_div((uint32_t)f.npix_padded);
+    f.div_tiles_x = rp_make_div((uint32_t)(f.tiles_x / RP_TILE_BLOCK));
+    f.div_stripe_rows = rp_make_div((uint32_t)f.stripe_rows);
+    f.div_width = rp_make_div((uint32_t)f.width);
+    return true;
+}
+} // namespace
+// out4: local_rows, tiles_x, tiles_y, npix_padded
+int sp_slot_geometry(const SpGeometry *g, int32_t *out4) {
+    RpFrame f;
+    if (!g || !slot_geometry(*g, f)) return 2;
+    out4[0] = f.local_rows, out4[1] = f.tiles_x, out4[2] = f.tiles_y, out4[3] = f.npix_padded;
+    return 0;
+}
+int sp_slots(const SpGeometry *g, const uint32_t *slots, int n_slots, int32_t *local3, const int32_t *pix2, int n_pix, uint32_t *slot_of, int32_t *global_row) {
+    RpFrame f;
+    if (!g || !slot_geometry(*g, f) || n_slots < 0 || n_pix < 0) return 2;
+    Buffers b;
+    const uint32_t *ds;
+    const int32_t *dp;
+    int32_t *dl, *dg;
+    uint32_t *dso;
+    if (b.in(ds, slots, n_slots) || b.in(dp, pix2, 2 * (size_t)n_pix) || b.alloc(dl, 3 * (size_t)n_slots) || b.alloc(dso, n_pix) || b.alloc(dg, n_pix)) return 1;
+    const int n = n_slots > n_pix ? n_slots : n_pix;
+    if (n == 0) return 0;
+    k_slots<<<blocks(n), kBlock>>>(f, ds, n_slots, dl, dp, n_pix, dso, dg);
+    if (launched("k_slots")) return 1;
+    return copy_out(local3, dl, 3 * (size_t)n_slots) || copy_out(slot_of, dso, n_pix) || copy_out(global_row, dg, n_pix);
+}
+// out4: (frame, sample_index, frame_offset, frame_id) of every sample slot of a launch sequence of batch_frames frames of frame_spp slots
+int sp_slot_frame(int batch_frames, int frame_spp, int batch_reset, uint32_t frame_offset, uint32_t sample_base, uint32_t frame_id, const uint32_t *sslots,
+                  int n, uint32_t *out4) {
+    if (batch_frames < 1 || frame_spp < 1 || n < 0) return 2;
+    RpFrame f;
+    memset(&f, 0, sizeof f);
+    f.frame_offset = frame_offset; // host_frame.inl fill_frame_constants
+    f.sample_base = sample_base;
+    f.frame_id = frame_id;
+    f.batch_frames = batch_frames;
+    f.frame_spp = frame_spp;
+    f.batch_spp = batch_frames * frame_spp;
+    f.batch_reset = batch_reset ? 1 : 0;
+    f.div_frame_spp = rp_make_div((uint32_t)frame_spp);
+    Buffers b;
+    const uint32_t *ds;
+    uint32_t *dout;
+    if (b.in(ds, sslots, n) || b.alloc(dout, 4 * (size_t)n)) return 1;
+    k_slot_frame<<<blocks(n), kBlock>>>(f, ds, n, dout);
+    if (launched("k_slot_frame")) return 1;
+    return copy_out(out4, dout, 4 * (size_t)n);
 }
 int sp_sample_sun(const float sun_dir[3], float cos_radius, const float *u2, int n, float *dirs3, float *pdf) {
     Buffers b;

@@ -180,3 +180,226 @@ def oct_words(seed=7, n_random=4096):
         e += [(0x8000 + k) | ((0x8000 + 0x7FFF - k) << 16), (0x8000 - k) | ((0x8000 + (0x7FFF - k)) << 16)]
     r = rng.integers(0, 2 ** 32, n_random, dtype=np.uint64)
     return np.concatenate([np.array(e, np.uint64), r])
+
+
+# ---------------------------------------------------------------- binned light selection
+LIGHT_TABLE_SIZES = (1, 15, 16, 17, 33, 40)
+LIGHT_BIN_SIZES = (1, 7, 16)
+SEL_Y_CLEARANCE = 2.0 ** -12   # random sel.y values keep this distance from every running sum of their bin
+ZERO_RADIANCE_LIGHT, ZERO_AREA_LIGHTS = 7, (5, 21)
+
+
+def light_table(n, seed=20):
+    """(n, 4, 3) float32 records (v0, v1, v2, radiance): triangles of at least 0.1 square units around y = 3, four of five turned to face the
+    receivers below them; light 0 lies in the plane y = 3 exactly; every radiance differs (light ZERO_RADIANCE_LIGHT has none, lights
+    ZERO_AREA_LIGHTS no area)"""
+    rng = np.random.default_rng(seed + n)
+    c = np.stack([rng.uniform(-2, 2, n), rng.uniform(2.5, 3.5, n), rng.uniform(-2, 2, n)], axis=1)
+    v = np.zeros((n, 3, 3))
+    for k in range(n):   # no slivers: at least 0.1 square units (a light of 1e-4 sr makes the direction sample ill conditioned, see light_queries)
+        while np.linalg.norm(np.cross(v[k, 1] - v[k, 0], v[k, 2] - v[k, 0])) < 0.2:
+            v[k] = c[k] + rng.normal(size=(3, 3)) * rng.uniform(0.3, 0.7)
+    v[0, :, 1] = 3.0
+    seen_from_origin = np.sum(np.cross(v[:, 0], v[:, 1]) * v[:, 2], axis=1) < 0
+    turn = ~seen_from_origin & (np.arange(n) % 5 != 4)
+    turn |= seen_from_origin & (np.arange(n) % 5 == 4) & (np.arange(n) > 0)
+    v[turn] = v[turn][:, [0, 2, 1]]
+    for k in ZERO_AREA_LIGHTS:
+        if k < n:
+            v[k, 2] = v[k, 1]
+    rad = np.stack([1.0 + np.arange(n), 2.0 + 0.5 * np.arange(n), 0.5 + 0.25 * np.arange(n)], axis=1)
+    if ZERO_RADIANCE_LIGHT < n:
+        rad[ZERO_RADIANCE_LIGHT] = 0.0
+    return np.ascontiguousarray(np.concatenate([v, rad[:, None, :]], axis=1), F32)
+
+
+def light_receivers(table, seed=21):
+    """(p, n, kind): receivers below the lights with normals in the upper hemisphere ("random"), then the edges -- above every light with the
+    normal up ("dark": every contribution is MIN_IRRADIANCE), in light 0's plane ("plane"), on light 0's first vertex ("vertex"), 1e4
+    units away ("far") and 1e-3 units in front of a light ("near")"""
+    rng = np.random.default_rng(seed + len(table))
+    m = 24
+    p = np.stack([rng.uniform(-2, 2, m), rng.uniform(-1, 1, m), rng.uniform(-2, 2, m)], axis=1)
+    n = rng.normal(size=(m, 3))
+    n[:, 1] = np.abs(n[:, 1]) + 0.2
+    kinds = ["random"] * m
+    t = np.asarray(table, np.float64)
+    up = np.array([0.0, 1.0, 0.0])
+    extra = [([0.3, 100.0, -0.2], up, "dark"), ([50.0, 60.0, 10.0], [0.1, 1.0, 0.0], "dark"),
+             ([t[0, 0, 0] + 2.0, 3.0, t[0, 0, 2] + 1.5], up, "plane"), ([0.25, 3.0, -0.5], [0.0, -1.0, 0.0], "plane"),
+             (t[0, 0], up, "vertex"), (t[-1, 2], [0.0, -1.0, 0.0], "vertex"),
+             ([6000.0, -8000.0, 0.0], [-0.6, 0.8, 0.0], "far"), ([0.0, -1e4, 0.0], up, "far")]
+    for k in sorted({0, len(t) // 2, len(t) - 1}):
+        centre = t[k, :3].mean(axis=0)
+        nrm = np.cross(t[k, 1] - t[k, 0], t[k, 2] - t[k, 0])
+        if np.linalg.norm(nrm) > 0:
+            nrm = nrm / np.linalg.norm(nrm)
+            extra.append((centre + 1e-3 * nrm, -nrm, "near"))   # (front: (a x b) . c < 0 seen from the side the normal points to)
+    p = np.concatenate([p, np.array([e[0] for e in extra], np.float64)])
+    n = np.concatenate([n, np.array([e[1] for e in extra], np.float64)])
+    return np.ascontiguousarray(p, F32), _unit(n), kinds + [e[2] for e in extra]
+
+
+def light_queries(table, bin_size, n_random=4096, seed=22):
+    """(p, n, u4 = (dir sample, sel.x, sel.y), boundary (sel.y is one of the chosen edge values), kind of receiver).
+    Bin edges: the bin sample takes 0, every k / bins and the number below it, 1 - 2^-24 and 1 (rp_randf gives it, nee renormalises it to
+    it), each with sel.y = 0 and a random sel.y over three receivers; the first and the last bin (sel.x = 0 and 1) also meet sel.y =
+    1 - 2^-24 and 1, which walk through their bin. Those four queries sit ON a decision boundary of the running sum (a build with other
+    roundings may end one light earlier or later); the random block is large enough that four are less than 0.1 % of a case.
+    Edge receivers: every one of them with two random samples and with sel.y = 0 in the first and the last bin.
+    Then random samples over the random receivers.
+    The edge receivers are few on purpose. The direction sample of a light of 1e-4 sr and less (the far receivers, the dark ones, a
+    receiver 1e-3 units in front of a light whose neighbours it sees edge on) is ill conditioned: one ulp of the sample moves the
+    ORACLE's direction by hundreds of ulps of 1, so a device whose cosf differs in its last bit leaves any fixed bound there. The device
+    test holds the direction to a fixed bound on all but 0.1 % of the queries; tests/test_light_selection_cpu.py shows on the oracle
+    alone that the cases leave that rule to the code (fewer than 1 % of the queries move by more than the bound under such an ulp)."""
+    rng = np.random.default_rng(seed + 100 * len(table) + bin_size)
+    bins = (len(table) + bin_size - 1) // bin_size
+    rp, rn, kinds = light_receivers(table)
+    ordinary = [i for i, k in enumerate(kinds) if k == "random"]
+    special = [i for i, k in enumerate(kinds) if k != "random"]
+    xs = [F32(0.0), ULP_DN(1.0), F32(1.0)]
+    for k in range(1, bins + 1):
+        e = F32(F32(k) / F32(bins))
+        xs += [e, ULP_DN(e)]
+    xs = np.unique(np.array(xs, F32))
+    sel, boundary, who = [], [], []
+    i = 0
+    for x in xs:
+        for rep in range(3):
+            ys = [F32(0.0), None] + ([ULP_DN(1.0), F32(1.0)] if rep == 0 and x in (F32(0.0), F32(1.0)) else [])
+            for y in ys:
+                sel.append((x, rng.random() if y is None else y))
+                boundary.append(y is not None)
+                who.append(ordinary[i % len(ordinary)])
+                i += 1
+    for r in special:
+        for (x, y) in [(rng.random(), None)] * 2 + [(F32(0.0), F32(0.0)), (F32(1.0), F32(0.0))]:
+            sel.append((x, rng.random() if y is None else y))
+            boundary.append(y is not None)
+            who.append(r)
+    for k in range(n_random):
+        sel.append((rng.random(), rng.random()))
+        boundary.append(False)
+        who.append(ordinary[k % len(ordinary)])
+    who = np.array(who)
+    u4 = np.zeros((len(sel), 4), F32)
+    u4[:, :2] = rng.random((len(sel), 2))
+    u4[:4, :2] = [[0, 0], [1 - 2 ** -24, 1 - 2 ** -24], [0.5, 0.0], [0.0, 1 - 2 ** -24]]
+    u4[:, 2:] = np.array(sel, F32)
+    return np.ascontiguousarray(rp[who]), np.ascontiguousarray(rn[who]), u4, np.array(boundary), [kinds[w] for w in who]
+
+
+def oracle_tri_light_bins(table, bin_size, p, n, u4):
+    """orc_tri_light_bins over a scene whose light table is `table` -> dict of the outputs"""
+    import ctypes as C
+    import oracle_lib as O
+    s = scenes.cornell32()
+    s.lights = np.ascontiguousarray(table, F32)
+    osc = O.OracleScene(s)
+    cfg = abi.LightSamplingConfig(0.0, int(bin_size), 15.0, 0.0)
+    N = len(p)
+    out = dict(L=np.zeros((N, 3), F32), dir=np.zeros((N, 3), F32), dist=np.zeros(N, F32), pdf=np.zeros(N, F32), mis=np.zeros(N, F32),
+               bins=np.zeros((N, 3), np.int32), contrib=np.zeros((N, 16), F32))
+    fn = O.lib().orc_tri_light_bins
+    fn.argtypes, fn.restype = None, C.c_int
+    rc = fn(C.c_void_p(osc.h), C.byref(cfg), O._p(p), O._p(n), O._p(u4), N, *[O._p(out[k]) for k in ("L", "dir", "dist", "pdf", "mis", "bins", "contrib")])
+    assert rc == 0, "orc_tri_light_bins refused %d lights in bins of %d" % (len(table), bin_size)
+    osc.close()
+    return out
+
+
+_LIGHT_CASES = {}
+
+
+def light_case(num_lights, bin_size):
+    """one table, its queries and the oracle's results for them (computed once, shared, never written to). The random sel.y values are
+    moved SEL_Y_CLEARANCE away from the running sums of their bin (formed from the oracle's contributions, which do not depend on sel.y),
+    so that only the chosen edge values sit at a decision boundary."""
+    import shade_ref64 as R
+    key = (num_lights, bin_size)
+    if key not in _LIGHT_CASES:
+        table = light_table(num_lights)
+        p, n, u4, boundary, kinds = light_queries(table, bin_size)
+        first = oracle_tri_light_bins(table, bin_size, p, n, u4)
+        count = first["bins"][:, 1] - first["bins"][:, 0]
+        _, _, sums = R.light_select(first["contrib"], count, u4[:, 3], np.float32)
+        for _ in range(8):
+            with np.errstate(invalid="ignore"):
+                d = np.abs(sums - u4[:, 3:4].astype(np.float64))
+            near = ~boundary & (np.nan_to_num(d, nan=1.0).min(axis=1) < SEL_Y_CLEARANCE)
+            if not near.any():
+                break
+            u4[near, 3] = (u4[near, 3] + F32(4 * SEL_Y_CLEARANCE)) % F32(1.0)
+        assert not near.any()
+        u4 = np.ascontiguousarray(u4)
+        ref = oracle_tri_light_bins(table, bin_size, p, n, u4)
+        assert np.array_equal(ref["contrib"].view(np.uint32), first["contrib"].view(np.uint32))
+        for a in (table, p, n, u4, boundary, *ref.values()):
+            a.setflags(write=False)
+        _LIGHT_CASES[key] = dict(table=table, bin_size=bin_size, p=p, n=n, u4=u4, boundary=boundary, kinds=np.array(kinds), ref=ref)
+    return _LIGHT_CASES[key]
+
+
+# ---------------------------------------------------------------- point sets
+POINTSET_PIXELS = ((0, 0), (255, 255), (256, 0), (300, 200), (3839, 2159), (7679, 4319))
+POINTSET_WIDTHS = (200, 256, 1920, 3840, 7680)
+POINTSET_SAMPLES = (0, 1, 1023, 65535, 65536, 2 ** 24)
+POINTSET_FRAMES = (0, 77, 0xFFFFFFF0)
+
+
+def pointset_dims():
+    """absolute dimensions: the camera's, every bounce's eight (rp_bounce_dim(b) = 6 + 8 b, b <= MAX_PATH_DEPTH), the last Sobol' dimension and
+    beyond it (the mask), dimensions whose blue-noise pixel offset d / 8 reaches 128 and beyond; 16387, 32773 and 65535: the first whose
+    blue-noise dimension (d mod 8) + 8 (d div 1024) leaves the first 128 of the 256 stored ones, and two that the mask of 255 wraps; then
+    the pairs (d, d + 1) of POINTSET_PAIRS, which the device draws through rp_draw2 (x first: the oracle draws them one by one)"""
+    d = list(range(6))
+    for b in range(abi.MAX_PATH_DEPTH + 1):
+        d += [6 + 8 * b + k for k in range(8)]
+    d += [1023, 1024, 1025, 2047, 8191, 16387, 32773, 65535]
+    for first in POINTSET_PAIRS:
+        d += [first, first + 1]
+    return np.array(d, np.uint32)
+
+
+POINTSET_PAIRS = (0, 4, 6 + 8 * 9 + 2, 1023, 8191)   # first dimensions of pairs (d, d + 1): the device draws these through rp_draw2
+
+
+def pointset_singles():
+    """how many of pointset_dims() are single draws (rp_draw1); the rest are the pairs of POINTSET_PAIRS"""
+    return len(pointset_dims()) - 2 * len(POINTSET_PAIRS)
+
+
+def pointset_queries():
+    """(N, 6) uint32: width, sample_index, frame_offset, frame_id, px, py -- every pixel at every width (a pixel beyond the width is the
+    same integer arithmetic), every sample index with frame_offset = frame_id = 0 and with the large frame constants, every pair of frame constants
+    at sample index 1"""
+    q = []
+    for w in POINTSET_WIDTHS:
+        for (px, py) in POINTSET_PIXELS:
+            for si in POINTSET_SAMPLES:
+                q.append((w, si, 0, 0, px, py))
+                q.append((w, si, 0xFFFFFFF0, 77, px, py))
+            for fo in POINTSET_FRAMES:
+                for fi in POINTSET_FRAMES:
+                    q.append((w, 1, fo, fi, px, py))
+    return np.unique(np.array(q, np.uint32), axis=0)
+
+
+LCG_A, LCG_C = 1664525, 1013904223
+
+
+def randf_states(n_random=4096, seed=23):
+    """generator states: 0, the largest state whose float is below 1 (0xFFFFFF7F), the smallest that rounds to 1.0f (0xFFFFFF80), 0xFFFFFFFF,
+    the states from which the generator steps ONTO those four (so that rp_randf returns their floats), random ones"""
+    edges = [0, 0xFFFFFF7F, 0xFFFFFF80, 0xFFFFFFFF]
+    inv = pow(LCG_A, -1, 2 ** 32)
+    before = [((e - LCG_C) * inv) % 2 ** 32 for e in edges]
+    r = np.random.default_rng(seed).integers(0, 2 ** 32, n_random, dtype=np.uint64)
+    return np.concatenate([np.array(edges + before, np.uint64), r]).astype(np.uint32)
+
+
+def randf_ref(states):
+    """rendering/pointsets/lcg_rng.glsl:15-26 on Python integers -> (next state, float(next state) * 2^-32 rounded to binary32 once)"""
+    nxt = (np.asarray(states, np.uint64) * np.uint64(LCG_A) + np.uint64(LCG_C)) % np.uint64(2 ** 32)
+    return nxt.astype(np.uint32), (nxt.astype(np.uint32).astype(F32) * F32(2.0 ** -32)).astype(F32)

@@ -136,6 +136,108 @@ def tri_solid_angle(v9):
     return 2.0 * np.arctan2(num, den)
 
 
+# ---------------------------------------------------------------- binned light selection, rendering/mc/lights_linear.glsl:19-127
+MIN_IRRADIANCE = 6.2e-4 * 0.001
+BIN_MAX = 16  # BINNED_LIGHTS_BIN_MAX_SIZE
+
+
+def pad_lights(lights):
+    """(L, 4, 3) float64 records (v0, v1, v2, radiance) followed by BIN_MAX + 1 zeroed ones, as the light buffer is padded"""
+    lights = np.asarray(lights, np.float64).reshape(-1, 4, 3)
+    return np.concatenate([lights, np.zeros((BIN_MAX + 1, 4, 3))])
+
+
+def light_bin(num_lights, bin_size, sel_x):
+    """:21-36 (bin_begin, bin_end, number of bins). The bin is an integer outcome of ONE binary32 product, sel_x * float(bins), so that
+    product is formed in binary32 here as well; everything after it is integer arithmetic"""
+    bins = (num_lights + bin_size - 1) // bin_size
+    x = np.asarray(sel_x, F32) * F32(bins)
+    b = np.minimum(np.floor(x.astype(np.float64)).astype(np.int64), bins - 1)
+    return b * bin_size, np.minimum(bin_size * (b + 1), num_lights), bins
+
+
+def light_contributions(lights, begin, end, p, n):
+    """:41-66 -> (contributions (N, BIN_MAX), 0 behind the bin's end; decided (N, BIN_MAX): the facing tests of that light have a margin
+    of 1e-5 of the vectors' lengths, so that a binary32 evaluation takes the same branch). The solid angle is the exact one
+    (tri_solid_angle), which the shader approximates within 2 * FAST_ATAN_MAX_ABS_ERROR"""
+    L = pad_lights(lights)
+    p, n = np.asarray(p, np.float64), np.asarray(n, np.float64)
+    idx = np.asarray(begin)[:, None] + np.arange(BIN_MAX)[None, :]
+    inside = idx < np.asarray(end)[:, None]
+    rec = L[np.minimum(idx, len(L) - 1)]                       # (N, BIN_MAX, 4, 3)
+    v = rec[:, :, :3, :] - p[:, None, None, :]
+    a, b, c = v[:, :, 0], v[:, :, 1], v[:, :, 2]
+    triple = _dot(np.cross(a, b), c)
+    la, lb, lc = (np.linalg.norm(x, axis=-1) for x in (a, b, c))
+    dn = np.stack([_dot(x, n[:, None, :]) for x in (a, b, c)], axis=-1)
+    front = triple < 0.0
+    above = (dn > 0.0).any(axis=-1)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        omega = tri_solid_angle(v.reshape(-1, 9)).reshape(idx.shape)
+    contrib = np.where(front & above, _lum(rec[:, :, 3]) * omega, 0.0) + MIN_IRRADIANCE
+    eps = 1e-5
+    decided = (np.abs(triple) > eps * la * lb * lc) & (np.abs(dn) > eps * np.stack([la, lb, lc], axis=-1) * np.linalg.norm(n, axis=-1)[:, None, None]).all(axis=-1)
+    return np.where(inside, contrib, 0.0), decided & inside
+
+
+def light_select(contributions, count, sel_y, dtype=np.float64):
+    """:68-100 the selection among the first `count` contributions -> (offset of the light the loop ends on -- count when sel_y stays
+    at or above the last running sum of a bin shorter than BIN_MAX: the light BEHIND the bin --, its share p of the total, the running
+    sums (N, BIN_MAX), NaN behind the end of the walk). dtype = numpy.float32 performs the shader's own binary32 operations in its order (+ and
+    / only: exactly rounded in numpy as on the device), numpy.float64 states the rule."""
+    c = np.asarray(contributions).astype(dtype)
+    count = np.asarray(count)
+    y = np.asarray(sel_y).astype(dtype)
+    N = len(c)
+    total = np.zeros(N, dtype)
+    for i in range(BIN_MAX):
+        total = np.where(i < count, total + c[:, i], total).astype(dtype)
+    p, t = np.zeros(N, dtype), np.zeros(N, dtype)
+    chosen, done = np.zeros(N, np.int64), np.zeros(N, bool)
+    sums = np.full((N, BIN_MAX), np.nan)
+    for i in range(BIN_MAX):
+        live = ~done
+        chosen = np.where(live, i, chosen)
+        act = live & (i < count)
+        done |= live & ~act
+        with np.errstate(invalid="ignore", divide="ignore"):
+            pi = (c[:, i] / total).astype(dtype)
+        p = np.where(act, pi, p).astype(dtype)
+        t = np.where(act, t + pi, t).astype(dtype)
+        sums[:, i] = np.where(act, t, np.nan)
+        done |= act & (y < t)
+    return chosen, p, sums
+
+
+def name_light(table, radiance_over_pdf, pdf):
+    """the record whose radiance is nearest to radiance_over_pdf * pdf among the table and the zeroed record behind it (every light of a
+    test table has its own radiance; the light without radiance and the zeroed record share theirs: compare radiances, not indices)"""
+    rad = pad_lights(table)[:len(table) + 1, 3]
+    with np.errstate(invalid="ignore", over="ignore"):
+        got = np.asarray(radiance_over_pdf, np.float64) * np.asarray(pdf, np.float64)[:, None]
+        d = np.abs(np.nan_to_num(got, nan=1e300, posinf=1e300, neginf=-1e300)[:, None, :] - rad[None, :, :]).max(axis=2)
+    return np.argmin(d, axis=1)
+
+
+# the oracle's light_dist / mis_wpdf over the float64 band at its own direction, in the rounding units of light_dist_wpdf_excess (a
+# worst-case envelope of the formula's own roundings: tens of ulps of the result on a typical query, see there), every query of
+# tests/shade_cases.py light_case: measured on the CPU by tests/test_light_selection_cpu.py, which holds the oracle to them. In plain
+# ulps of the result the same excess reaches 158 / 228 on the oracle, on single queries whose direction grazes the light's plane: there
+# the rounding of the dot products' terms decides, which the envelope accounts for and a band over input ulps does not.
+ORACLE_DIST_EXCESS = 0.18   # measured 0.179
+ORACLE_WPDF_EXCESS = 0.16   # measured 0.157
+
+
+def light_dist_wpdf(l0, l1, l2, p, light_dir, num_bins):
+    """:112-124 the distance to the light's plane along light_dir and the area pdf turned solid-angle pdf, over the bins"""
+    l0, l1, l2, p, d = (np.asarray(x, np.float64) for x in (l0, l1, l2, p, light_dir))
+    e_n = np.cross(l1 - l0, l2 - l0)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        den = _dot(d, e_n)
+        dist = _dot(l0 - p, e_n) / den
+        return dist, 2.0 * dist * dist / np.abs(den) / num_bins
+
+
 def sun_dir_pdf(cos_radius):  # rendering/lights/sun.glsl:17-20
     with np.errstate(divide="ignore"):
         return 1.0 / (2.0 * np.pi * (1.0 - np.asarray(cos_radius, np.float64)))
@@ -273,6 +375,60 @@ def band(fn, arrays, count=8, seed=0):
         with np.errstate(invalid="ignore"):
             lo, hi = np.fmin(lo, w), np.fmax(hi, w)
     return lo, hi
+
+
+def light_dist_wpdf_rounding(l0, l1, l2, p, light_dir, num_bins):
+    """what the binary32 roundings INSIDE light_dist_wpdf amount to, absolutely, for (light_dist, mis_wpdf): every product of the two dot
+    products with e_n and of e_n's own components is rounded to half an ulp of ITSELF, so where a sum of them cancels (a direction that
+    grazes the light's plane, a receiver close to it) the result carries 2^-24 of the sum of their magnitudes however small it is. First
+    order: err(e_n) per component, err(num) and err(den) from the magnitudes, err(dist) = err(num) / |den| + |num| err(den) / den^2,
+    err(wpdf) = wpdf (2 err(dist) / |dist| + err(den) / |den|). The band over input ulps does not see this; band_excess takes it as the
+    floor of its unit."""
+    l0, l1, l2, p, d = (np.asarray(x, np.float64) for x in (l0, l1, l2, p, light_dir))
+    eps = 2.0 ** -24
+    u, v, a = l1 - l0, l2 - l0, l0 - p
+    e_n = np.cross(u, v)
+    au, av = np.abs(u), np.abs(v)
+    # (the differences u, v, a are rounded too: an eps of the operands each)
+    du, dv = eps * (np.abs(l1) + np.abs(l0)), eps * (np.abs(l2) + np.abs(l0))
+    da = eps * (np.abs(l0) + np.abs(p))
+    mag = np.stack([au[:, 1] * av[:, 2] + au[:, 2] * av[:, 1], au[:, 2] * av[:, 0] + au[:, 0] * av[:, 2], au[:, 0] * av[:, 1] + au[:, 1] * av[:, 0]], axis=1)
+    cross_abs = lambda x, y: np.stack([x[:, 1] * y[:, 2] + x[:, 2] * y[:, 1], x[:, 2] * y[:, 0] + x[:, 0] * y[:, 2], x[:, 0] * y[:, 1] + x[:, 1] * y[:, 0]], axis=1)  # noqa: E731
+    err_en = 2 * eps * mag + cross_abs(du, av) + cross_abs(au, dv)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        num, den = _dot(a, e_n), _dot(d, e_n)
+        err_num = 2 * eps * _dot(np.abs(a), np.abs(e_n)) + _dot(np.abs(a), err_en) + _dot(da, np.abs(e_n))
+        err_den = 2 * eps * _dot(np.abs(d), np.abs(e_n)) + _dot(np.abs(d), err_en)
+        dist = num / den
+        err_dist = err_num / np.abs(den) + np.abs(num) * err_den / (den * den)
+        w = 2.0 * dist * dist / np.abs(den) / num_bins
+        err_w = w * (2.0 * err_dist / np.abs(dist) + err_den / np.abs(den))
+    return np.nan_to_num(err_dist, nan=0.0, posinf=0.0), np.nan_to_num(err_w, nan=0.0, posinf=0.0)
+
+
+def light_dist_wpdf_excess(table, num_bins, p, light_id, light_dir, dist, mis_wpdf, extra_ulps=(0.0, 0.0)):
+    """the band excess of a binary32 light_dist and mis_wpdf over light_dist_wpdf at the light `light_id` of each query and at the
+    binary32 light_dir handed in (the evaluation's OWN direction: what is held is the arithmetic behind the direction sample)
+    -> (light_dist, mis_wpdf in ROUNDING UNITS, light_dist, mis_wpdf in plain ulps of the result).
+    A rounding unit is light_dist_wpdf_rounding's worst-case envelope of the formula's own roundings, or an ulp of the result where that
+    is larger -- which it practically never is: the envelope charges a full 2^-24 per operation on sums of magnitudes and is 33 .. 46 ulps
+    of the result at the median for light_dist (83 .. 117 for mis_wpdf), hundreds to thousands on 1 % of the queries, up to 37 000 / 85 000
+    on grazing ones; on no query of the cases is it below one ulp. 0.18 units thus reads: 18 % of a pessimistic envelope, 6 .. 8 ulps of
+    light_dist on a typical query.
+    extra_ulps: REAL ulps of the result by which the band is widened before the excess is taken (a build that divides through a 1-ulp
+    reciprocal: one per division; not multiplied by the envelope). The plain-ulp figures are reported without it.
+    Queries whose band is not finite (a direction of NaN, the zeroed light behind the table) measure 0."""
+    rec = pad_lights(table)[np.asarray(light_id)].astype(np.float32)
+    args = [np.ascontiguousarray(rec[:, k]) for k in range(3)] + [np.asarray(p, np.float32), np.asarray(light_dir, np.float32)]
+    floors = light_dist_wpdf_rounding(*args, num_bins)
+    units, plain = [], []
+    for k, got in ((0, dist), (1, mis_wpdf)):
+        lo, hi = band(lambda a, b, c, q, d: light_dist_wpdf(a, b, c, q, d, num_bins)[k], args)
+        plain.append(band_excess(got, lo, hi))
+        with np.errstate(invalid="ignore"):
+            w = extra_ulps[k] * ulp32(np.maximum(np.abs(lo), np.abs(hi)))
+        units.append(band_excess(got, lo - w, hi + w, floor=floors[k]))
+    return units[0], units[1], plain[0], plain[1]
 
 
 def band_excess(got, lo, hi, floor=0.0):

@@ -103,6 +103,68 @@ def test_image_parity_vs_oracle(small_scenes, name, variant, W, H, spp):
     assert st.spp == spp
 
 
+def five_light_cornell():
+    """cornell32 with its light table replaced by five triangles under the ceiling, every one with its own radiance"""
+    s = scenes.cornell32()
+    y = 0.99
+    lights = []
+    for k, (cx, cz, r) in enumerate(((-0.5, -0.5, 0.2), (0.5, -0.5, 0.15), (0.0, 0.0, 0.25), (-0.5, 0.5, 0.1), (0.5, 0.5, 0.3))):
+        lights.append([[cx - r, y, cz - r], [cx + r, y, cz - r], [cx + r, y, cz + r], [4.0 + 3 * k, 12.0 - 2 * k, 2.0 + k * k]])
+    s.lights = np.array(lights, np.float32)
+    return s
+
+
+@pytest.mark.parametrize("bin_size", [1, 2, 16])
+def test_image_parity_vs_oracle_over_light_bin_sizes(bin_size):
+    """five lights in bins of 1 (five bins), 2 (the last bin holds one light: a wrong last bin moves a third of the light samples) and 16
+    (one partial bin), through the kernels: LightSamplingConfig.bin_size reaches rp_choose_light_bin and the frame's bin count"""
+    s = five_light_cornell()
+    W, H, spp = 96, 64, 2
+    cfg = abi.LightSamplingConfig.default()
+    cfg.bin_size = bin_size
+    img, st, _ = gpu_render(s, W, H, spp, abi.VARIANT_GLTF, lighting=cfg)
+    osc = O.OracleScene(s)
+    ref, ost = osc.render(W, H, spp, variant=abi.VARIANT_GLTF, lighting=cfg)
+    rmse, same_nan_mask, maxabs = image_error(img, ref)
+    print("bins of %d: rmse vs oracle %.3e, largest difference %.3e" % (bin_size, rmse, maxabs))
+    assert same_nan_mask
+    assert rmse < RMSE_TOL, (rmse, maxabs)
+    assert np.array_equal(np.nan_to_num(img[..., 3]), np.nan_to_num(ref[..., 3]))
+    assert abs(int(st.raw.rays_closest) - int(ost.rays_closest)) <= max(4, 1e-3 * ost.rays_closest)
+    assert abs(int(st.raw.rays_shadow) - int(ost.rays_shadow)) <= max(4, 1e-3 * ost.rays_shadow)
+    assert st.spp == spp
+    if bin_size != 16:   # the bin size is no dead parameter: the frame differs from the one of a single bin by far more than the tolerance
+        other, _ = osc.render(W, H, spp, variant=abi.VARIANT_GLTF)
+        assert image_error(ref, other)[0] > 10 * RMSE_TOL
+
+
+def test_scene_without_lights_ignores_the_sun_weight():
+    """A scene without lights sends every NEE sample to the sun, whatever sun weight its scene parameters carry (the reference hands w = 1
+    when light_count == 0): sun_radiance[3] = 0.5 gives the bits of 1.0. (Before this rule a weight below 1 ran the light-sampling
+    kernels over an empty table: bin -1 of 0.)"""
+    s = scenes.cornell32()
+    s.lights = np.zeros((0, 4, 3), np.float32)
+    W, H, spp = 64, 48, 2
+    imgs = []
+    for w in (1.0, 0.5):
+        sp = s.scene_params()
+        sp.sun_radiance[3] = w
+        r = backend.RenderHip()
+        r.initialize(W, H)
+        r.set_scene(s)
+        r.update_config(sp)
+        img, st, _ = gpu_render(s, W, H, spp, abi.VARIANT_GLTF, renderer=r)
+        imgs.append(img)
+        r.close()
+    assert np.array_equal(imgs[0].view(np.uint32), imgs[1].view(np.uint32))
+    sp = s.scene_params()
+    sp.sun_radiance[3] = 0.5
+    ref, _ = O.OracleScene(s).render(W, H, spp, variant=abi.VARIANT_GLTF, scene_params=sp)
+    rmse, same_nan_mask, maxabs = image_error(imgs[1], ref)
+    print("no lights, sun weight 0.5: rmse vs oracle %.3e" % rmse)
+    assert same_nan_mask and rmse < RMSE_TOL, (rmse, maxabs)
+
+
 def test_progressive_accumulation_matches_one_shot(small_scenes):
     """N frames of 1 spp (reference: batch_spp = 1 + running mean) == one call with N spp, bit for bit."""
     s = small_scenes["cornell"]

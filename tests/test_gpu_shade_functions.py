@@ -15,9 +15,17 @@ Function classes, IEEE build against the oracle:
       rp_skymodel_radiance, rp_linear_to_srgb, rp_texture_grad (log2f picks the level)
   discrete outcomes (the lobe a sample takes, the levels a lookup blends) follow from those values: a sample whose direction differs
   by more than the bound took another branch; at most 0.1 % may (inputs at a decision boundary).
+
+Three more classes of the same header have files of their own, over the same probes and helpers (tests/shade_probes.py):
+  binned light selection (tests/test_gpu_light_selection.py): rp_choose_light_bin, rp_tri_light_contribution, rp_finish_tri_light_sample,
+      rp_load_light -- bin, contributions, pdf and radiance_over_pdf bit for bit, the chosen light on every query, light_dir within ULP_LIBM,
+      light_dist / mis_wpdf against float64 at the device's own direction
+  point sets (tests/test_gpu_pointset_functions.py): rp_rng_seed, rp_randf / rp_rand2, rp_part1by1, rp_morton_shuffled,
+      rp_sobol_shift_invert, rp_rng_open<TABLE>, rp_draw_table, rp_draw1 / rp_draw2 -- draws and index bit for bit, in both builds
+  slot and index arithmetic (tests/test_gpu_slot_arithmetic.py): rp_div with rp_make_div, rp_slot_frame, rp_slot_to_local, rp_local_to_slot,
+      rp_local_row_to_global -- equal to an integer restatement (tests/slot_ref.py)
 """
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
@@ -25,82 +33,19 @@ import pytest
 import oracle_lib as O
 import shade_cases as S
 import shade_ref64 as R
-import device_probes as DP
 from common import rel_excess
+from shade_probes import EXCEPTIONS, SAMPLE_PDF_REL, ULP_LIBM, bits_equal, call, dir_ulps, line, nonfinite, ulps
 from oracle_lib import _p
 from realtimepathtracingresearchframework_amd import abi
 
 pytestmark = pytest.mark.gpu
 
-ULP_LIBM = 64          # sample directions / sky / sRGB / anisotropic lookups: device libm vs glibc, amplified through the formulas
-SAMPLE_PDF_REL = 1e-3  # sampled pdf / MIS pdf against the oracle's at the same inputs
 UNEXPLAINED = 6        # samples that differ without a decision boundary within ULP_LIBM of the oracle's samples (measured 3)
-EXCEPTIONS = 1e-3      # share of samples allowed to take another branch (their oracle value lies at a decision boundary)
 # fast_math against float64: v_rcp / v_sqrt / v_rsq are 1-ulp instructions; their error is amplified exactly where the band rule
 # amplifies an input ulp, so the same rule with a wider margin
 FAST_GLTF_REL_MAX, FAST_GLTF_REL_TAIL = 2e-3, 4e-5   # measured: 1.15e-3 max, like IEEE
 IEEE_GLTF_REL_MAX, IEEE_GLTF_REL_TAIL = 2e-3, 2e-5   # tests/test_shade_ref64.py (the IEEE build equals the oracle bit for bit)
 TEXTURE_ULPS = {0: 16, 1: 64}
-
-
-_LIBS = {}
-
-
-def probes(fast):
-    if fast not in _LIBS:
-        d = os.environ.get("RPTR_SHADE_PROBE_DIR")
-        if d:
-            path = DP.lib_paths(d)[fast]
-        else:
-            if DP.needs_build():
-                DP.build()
-            path = DP.lib_paths()[fast]
-        L = C.CDLL(path)
-        for name in ("sp_gltf_sample", "sp_gltf_eval", "sp_gltf_t_sample", "sp_gltf_t_eval", "sp_simple", "sp_tri_light", "sp_sample_sun", "sp_sun_pdf",
-                     "sp_nee_mis", "sp_sky_radiance", "sp_hit_attributes", "sp_dequantize", "sp_footprint", "sp_texture", "sp_linear_to_srgb", "sp_half4"):
-            getattr(L, name).restype = C.c_int
-        L.sp_sample_sun.argtypes = [C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        L.sp_texture.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
-        assert L.sp_fast_math() == fast
-        _LIBS[fast] = L
-    return _LIBS[fast]
-
-
-def call(fast, name, *args):
-    rc = getattr(probes(fast), name)(*args)
-    assert rc == 0, "%s returned %d" % (name, rc)
-
-
-def bits_equal(a, b):
-    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
-    return (a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))
-
-
-def ulps(a, b):
-    """distance in binary32 ulps (monotone integer map; NaN == NaN: 0, NaN vs number: huge)"""
-    def key(x):
-        i = np.asarray(x, np.float32).view(np.int32).astype(np.int64)
-        return np.where(i < 0, -(i & 0x7FFFFFFF), i)
-    d = np.abs(key(a) - key(b)).astype(np.float64)
-    na, nb = np.isnan(np.asarray(a, np.float32)), np.isnan(np.asarray(b, np.float32))
-    return np.where(na & nb, 0.0, np.where(na | nb, 2.0 ** 40, d))
-
-
-def dir_ulps(a, b):
-    """the distance of two unit vectors in ulps of 1 (2^-24; NaN == NaN: 0)"""
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    d = np.abs(a - b).max(axis=-1) / 2.0 ** -24
-    nan_a, nan_b = np.isnan(a).any(axis=-1), np.isnan(b).any(axis=-1)
-    return np.where(nan_a & nan_b, 0.0, np.where(nan_a | nan_b, 2.0 ** 40, d))
-
-
-def line(name, build, ulp_max, rel, nonfinite):
-    print("%-40s %-5s max ulp vs oracle %-12s max rel vs float64 %-10s non-finite %d" % (
-        name, build, "-" if ulp_max is None else "%d" % ulp_max, "-" if rel is None else "%.2e" % rel, nonfinite))
-
-
-def nonfinite(*a):
-    return int(sum((~np.isfinite(np.asarray(x, np.float32))).sum() for x in a))
 
 
 def gltf_eval(fast, m, n, wo, wi, t=False):
