@@ -483,7 +483,7 @@ int rptr_hip_readback_lights(rptr_hip_t *h, RptrTriLightData *out, uint32_t coun
  * that writes the float vertex buffer" (render_vulkan.cpp:2834-2840) and ships the buffer, not the shader; this is that piece
  * (csrc/skin.h rp_k_skin): linear blend skinning with at most FOUR influences per vertex. The host sends 48 bytes per bone instead of 36
  * bytes per triangle, and the shading normals of the deformed mesh follow, which rptr_hip_update_vertices cannot make them do (it leaves
- * the oct-encoded vertex normals set_scene uploaded where they are).
+ * the oct-encoded vertex normals set_scene uploaded where they are; "recomputed normals" below is the remedy on that road).
  * rptr_hip_set_skin(h, geometry, vertices, num_vertices): after set_scene, on a geometry of a mesh flagged RPTR_MESH_DYNAMIC /
  * _SUBTLY_DYNAMIC. One RptrSkinVertex per UNROLLED vertex (three per triangle, the order of rptr_hip_update_vertices: a vertex shared
  * by several triangles is skinned once per corner), num_vertices == 3 * triangles. Binds the geometry: its REST POSE is its float
@@ -585,6 +585,47 @@ typedef struct RptrMorphTargetDesc {
 int rptr_hip_set_morph_targets(rptr_hip_t *h, uint32_t geometry, const RptrMorphTargetDesc *targets, uint32_t num_targets);
 int rptr_hip_update_morph_weights(rptr_hip_t *h, uint32_t geometry, uint32_t first_target, uint32_t count, const float *weights);
 int rptr_hip_update_morph_weights_device(rptr_hip_t *h, uint32_t geometry, uint32_t first_target, uint32_t count, const float *device_weights);
+
+/* ---- recomputed normals: float positions in, shading normals out on the device (csrc/normals.h rp_k_face_normals, rp_k_group_normals).
+ * rptr_hip_update_vertices[_device] replaces positions and leaves the normal words set_scene uploaded where they are: a cloth, fluid or
+ * soft-body solver that writes the vertex buffer on the device is lit as if it were at rest. Morph targets without normal deltas leave
+ * the same hole. This is the remedy: area-weighted smooth normals made from the positions as they are now, written into the array of
+ * normal words the deformers write; the refit carries them on as it carries theirs. No kernel of a frame, of the refit, of rp_k_skin or
+ * of rp_k_morph changes, and a scene that binds nothing launches and allocates what it did.
+ * rptr_hip_set_normal_groups(h, geometry, group, num_vertices, flags): after set_scene, on a geometry of a mesh flagged RPTR_MESH_DYNAMIC
+ * / _SUBTLY_DYNAMIC that has normals. Vertices are unrolled, so the library cannot know which corners are one smooth vertex: `group`
+ * holds one value per UNROLLED vertex (three per triangle, the order of rptr_hip_update_vertices), num_vertices == 3 * triangles.
+ * Corners with the same value share one normal -- a host passes the index buffer of the indexed mesh it unrolled (or welds with
+ * host/normal_groups.hpp / scenes.normal_groups); RPTR_NORMAL_GROUP_FLAT gives a corner its own triangle's face normal. Values are
+ * arbitrary 32-bit labels: the library renumbers them densely and transposes them once, on the host, into a per-group list of member
+ * corners in ASCENDING UNROLLED VERTEX INDEX. The geometry's array of normal words is made if it has none (in the master and in every
+ * frame context's scene copy, starting from the uploaded words). RPTR_E_INVALID, nothing changed and a message that names the offender,
+ * for a NULL handle, a call before set_scene, a geometry that is not dynamic, a geometry without normals, num_vertices != 3 * triangles
+ * and unknown flag bits. (NULL, 0, 0) unbinds: the normals stay as last written. A new set_scene drops every binding. The call waits
+ * for the frames in flight.
+ * rptr_hip_recompute_normals(h): for every bound geometry, two kernels on the backend's stream that read the master copy's CURRENT
+ * float positions -- whatever update_vertices[_device] or rptr_hip_skin last wrote, ordered behind them on the stream -- and write its
+ * normal words; then exactly what rptr_hip_update_vertices_device does per geometry, so the next rptr_hip_refit carries the words into
+ * the shading records of every scene copy (refit or device rebuild, frames in flight, registered lights, object motion). Host order:
+ * update_vertices* and / or rptr_hip_skin, then rptr_hip_recompute_normals, then rptr_hip_refit. On a geometry that also has a skin or
+ * morph targets the recomputed words replace what rptr_hip_skin wrote: this is how morph targets without dnrm get correct normals.
+ * Nothing bound: RPTR_E_INVALID. rptr_hip_readback_skinned accepts a geometry bound only by normal groups. world_size > 1: every rank
+ * holds the whole scene, call on each.
+ * Arithmetic: binary32, every product, difference and sum rounded on its own (no contraction), as for "skinned meshes".
+ *   triangle t, corners p0 p1 p2 = positions[3t .. 3t+2]:
+ *     e1 = p1 - p0,  e2 = p2 - p0
+ *     f  = ( e1.y*e2.z - e1.z*e2.y,  e1.z*e2.x - e1.x*e2.z,  e1.x*e2.y - e1.y*e2.x )      (area-weighted, never normalised)
+ *   corner i in group g with members c_0 < c_1 < ... :   n = f(c_0 / 3);  n = n + f(c_k / 3) for k = 1, 2, ...     (left to right)
+ *   corner i with RPTR_NORMAL_GROUP_FLAT:                n = f(i / 3)
+ *   RPTR_NORMALS_FLIP: n = -n
+ *   word = quantize_normal(n), unless n is not finite or all zero: the corner keeps its previous word
+ * Weighting is by AREA only; angle weighting is out of scope. A triangle that has two corners in one group contributes once per corner
+ * (the rule above, not a special case). A zero-area triangle contributes zeros; a group made only of such triangles, a NaN or infinite
+ * position and an overflowing product all fall under "keeps its previous word". Nothing is counted. */
+#define RPTR_NORMAL_GROUP_FLAT 0xFFFFFFFFu
+#define RPTR_NORMALS_FLIP 1u   /* the mesh is wound the other way: negate every recomputed normal */
+int rptr_hip_set_normal_groups(rptr_hip_t *h, uint32_t geometry, const uint32_t *group, uint32_t num_vertices, uint32_t flags);
+int rptr_hip_recompute_normals(rptr_hip_t *h);
 
 /* ---- RenderBackend::params / lighting_params / update_config
  * (render_backend.h:69-76, render_vulkan.cpp:2943-2959) */

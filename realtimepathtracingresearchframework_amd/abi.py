@@ -270,6 +270,10 @@ class MorphTargetDesc(C.Structure):  # include/rptr_hip.h RptrMorphTargetDesc: o
 MORPH_DELTA_DTYPE = [("vertex", "<u4"), ("dpos", "<f4", (3,)), ("dnrm", "<f4", (3,)), ("_pad", "<u4")]  # RptrMorphDelta as a numpy record
 
 
+NORMAL_GROUP_FLAT = 0xFFFFFFFF  # RPTR_NORMAL_GROUP_FLAT: the corner gets its own triangle's face normal
+NORMALS_FLIP = 1                # RPTR_NORMALS_FLIP
+
+
 class SurfaceHit(C.Structure):  # include/rptr_hip.h RptrSurfaceHit: six 16-byte rows per surface query
     _fields_ = [("position", C.c_float * 3), ("t", C.c_float),
                 ("geo_normal", C.c_float * 3), ("instance_geometry", C.c_int32),
@@ -342,7 +346,8 @@ EXPORTED_SYMBOLS = [
     "rptr_hip_initialize", "rptr_hip_set_scene", "rptr_hip_update_vertices", "rptr_hip_update_vertices_device", "rptr_hip_refit", "rptr_hip_set_params",
     "rptr_hip_render", "rptr_hip_render_async", "rptr_hip_render_batch_async", "rptr_hip_render_batch_cameras_async", "rptr_hip_wait", "rptr_hip_set_stage_timing", "rptr_hip_set_freeze_frame", "rptr_hip_set_option", "rptr_hip_get_option", "rptr_hip_option_count", "rptr_hip_option_name", "rptr_hip_set_rng_variant", "rptr_hip_set_bvh_policy", "rptr_hip_bvh_rebuild_count", "rptr_hip_update_instances", "rptr_hip_update_instances_device", "rptr_hip_set_tlas_policy", "rptr_hip_tlas_rebuild_count", "rptr_hip_set_light_sources", "rptr_hip_readback_lights",
     "rptr_hip_set_skin", "rptr_hip_update_bones", "rptr_hip_update_bones_device", "rptr_hip_skin", "rptr_hip_readback_skinned",
-    "rptr_hip_set_morph_targets", "rptr_hip_update_morph_weights", "rptr_hip_update_morph_weights_device", "rptr_hip_get_framebuffer_size", "rptr_hip_readback_f32", "rptr_hip_readback_u8", "rptr_hip_readback_aov",
+    "rptr_hip_set_morph_targets", "rptr_hip_update_morph_weights", "rptr_hip_update_morph_weights_device",
+    "rptr_hip_set_normal_groups", "rptr_hip_recompute_normals", "rptr_hip_get_framebuffer_size", "rptr_hip_readback_f32", "rptr_hip_readback_u8", "rptr_hip_readback_aov",
     "rptr_hip_denoise_defaults", "rptr_hip_denoise", "rptr_hip_readback_denoised_f32", "rptr_hip_readback_denoised_u8",
     "rptr_hip_denoise_temporal_defaults", "rptr_hip_denoise_temporal", "rptr_hip_readback_denoise_history_f32",
     "rptr_hip_taa_upscale_defaults", "rptr_hip_taa_upscale", "rptr_hip_readback_upscaled_u8",

@@ -102,6 +102,8 @@ def load_library(path=None):
     L.rptr_hip_set_morph_targets.argtypes = [vp, C.c_uint32, vp, C.c_uint32]
     L.rptr_hip_update_morph_weights.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]
     L.rptr_hip_update_morph_weights_device.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]
+    L.rptr_hip_set_normal_groups.argtypes = [vp, C.c_uint32, vp, C.c_uint32, C.c_uint32]
+    L.rptr_hip_recompute_normals.argtypes = [vp]
     L.rptr_hip_bvh_build_info.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.rptr_hip_traversal_preset.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.rptr_hip_get_framebuffer_size.argtypes = [vp, C.POINTER(C.c_uint32)]
@@ -790,7 +792,8 @@ class RenderHip:
         self._check(self._L.rptr_hip_skin(self._h))
 
     def readback_skinned(self, geometry, num_vertices=None):
-        """(xyz (n, 3) float32, normal words (n,) uint32 or None for a geometry without normals) of a bound geometry, after pending work."""
+        """(xyz (n, 3) float32, normal words (n,) uint32 or None for a geometry without normals) of a geometry bound by a skin, morph targets
+        or normal groups, after pending work."""
         geoms = getattr(self, "_geometries", [])
         tris, has_normals = geoms[int(geometry)] if 0 <= int(geometry) < len(geoms) else (0, False)
         n = 3 * tris if num_vertices is None else int(num_vertices)
@@ -839,6 +842,23 @@ class RenderHip:
     def update_morph_weights_device(self, geometry, first_target, device_ptr, count):
         """same from a device buffer of float32 written on the backend's stream."""
         self._check(self._L.rptr_hip_update_morph_weights_device(self._h, int(geometry), int(first_target), int(count), C.c_void_p(device_ptr)))
+
+    # ---- recomputed normals (rptr_hip_set_normal_groups / recompute_normals): shading normals from the positions as they are now
+    def set_normal_groups(self, geometry, groups=None, flip=False):
+        """Bind one geometry of a dynamic mesh that has normals: groups is (n,) uint32, one label per UNROLLED vertex (n = 3 * triangles);
+        corners with the same label share one normal (the index buffer of the mesh that was unrolled, or scenes.normal_groups),
+        abi.NORMAL_GROUP_FLAT gives a corner its triangle's face normal. flip: the mesh is wound the other way. groups=None unbinds."""
+        if groups is None:
+            self._check(self._L.rptr_hip_set_normal_groups(self._h, int(geometry), None, 0, 0))
+            return
+        g = np.ascontiguousarray(groups, dtype=np.uint32).reshape(-1)
+        self._check(self._L.rptr_hip_set_normal_groups(self._h, int(geometry), g.ctypes.data_as(C.c_void_p) if len(g) else None, len(g),
+                                                       abi.NORMALS_FLIP if flip else 0))
+
+    def recompute_normals(self):
+        """The normal words of every bound geometry from its current positions, on the device: after update_vertices* / skin(), before
+        refit()."""
+        self._check(self._L.rptr_hip_recompute_normals(self._h))
 
     def set_rng_variant(self, rng_variant, table=None):
         """RenderBackendOptions::rng_variant (render_params.glsl.h:34-37,76) + the table upload of the point set's render extension

@@ -576,6 +576,12 @@ int rptr_hip_set_scene(rptr_hip_t *h, const RptrSceneDesc *s) {
         h->morph.weights.assign(s->num_geometries, nullptr);
         h->morph.cap_entries.assign(s->num_geometries, 0);
         h->morph.cap_weights.assign(s->num_geometries, 0);
+        h->normals = decltype(h->normals)(); // recomputed normals (normals.h): the device arrays are made by set_normal_groups
+        h->normals.bound.assign(s->num_geometries, 0);
+        h->normals.flip.assign(s->num_geometries, 0);
+        h->normals.num_groups.assign(s->num_geometries, 0);
+        h->normals.offsets.assign(s->num_geometries, nullptr);
+        h->normals.members.assign(s->num_geometries, nullptr);
     }
     // ---- refit tables, then the master copy
     if ((rc = scene_refit_tables(h, T))) return rc;
@@ -1229,6 +1235,23 @@ static int skin_bone_table(rptr_hip *h) {
 // call on a geometry that already has the other deformer bound keeps the one it has), the normal halves of its qnrm_uv words as uploaded,
 // and -- for a geometry with normals -- the output array of normal words in the master and in every frame context's scene copy
 static int skin_copy_normals(rptr_hip *h, SceneCopy &sc, uint32_t geometry);
+// the normal half of it, which is all rptr_hip_set_normal_groups needs: the rest normal words and the output arrays of a geometry with normals
+static int skin_rest_normals(rptr_hip *h, uint32_t geometry) {
+    int rc;
+    auto &sk = h->skin;
+    const uint32_t n = 3u * h->geom_tris[geometry];
+    if (!sk.geom_normals[geometry]) return RPTR_OK;
+    if (!sk.rest_nrm[geometry]) {
+        if ((rc = dev_alloc(h, &sk.rest_nrm[geometry], n, &h->scene_allocs))) return rc;
+        if (n) hipLaunchKernelGGL(rp_k_skin_rest_normals, dim3(grid_for(h, n)), dim3(256), 0, h->stream, sk.geom_qnu[geometry], sk.rest_nrm[geometry], n);
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+    }
+    if ((rc = skin_copy_normals(h, h->master, geometry))) return rc;
+    for (SceneCopy &sc : h->ctx_scene)
+        if ((rc = skin_copy_normals(h, sc, geometry))) return rc;
+    return RPTR_OK;
+}
 static int skin_rest_pose(rptr_hip *h, uint32_t geometry, bool capture) {
     int rc;
     auto &sk = h->skin;
@@ -1238,18 +1261,7 @@ static int skin_rest_pose(rptr_hip *h, uint32_t geometry, bool capture) {
         capture = true;
     }
     if (capture) HIP_TRY(h, hipMemcpy(sk.rest_pos[geometry], h->master.dynpos[geometry], (size_t)n * 12, hipMemcpyDeviceToDevice));
-    if (sk.geom_normals[geometry]) {
-        if (!sk.rest_nrm[geometry]) {
-            if ((rc = dev_alloc(h, &sk.rest_nrm[geometry], n, &h->scene_allocs))) return rc;
-            if (n) hipLaunchKernelGGL(rp_k_skin_rest_normals, dim3(grid_for(h, n)), dim3(256), 0, h->stream, sk.geom_qnu[geometry], sk.rest_nrm[geometry], n);
-            HIP_TRY(h, hipGetLastError());
-            HIP_TRY(h, hipStreamSynchronize(h->stream));
-        }
-        if ((rc = skin_copy_normals(h, h->master, geometry))) return rc;
-        for (SceneCopy &sc : h->ctx_scene)
-            if ((rc = skin_copy_normals(h, sc, geometry))) return rc;
-    }
-    return RPTR_OK;
+    return skin_rest_normals(h, geometry);
 }
 // one scene copy's skinned normal words of `geometry` (made once, starting from the rest normals) and the table of its mesh
 static int skin_copy_normals(rptr_hip *h, SceneCopy &sc, uint32_t geometry) {
@@ -1379,8 +1391,9 @@ int rptr_hip_skin(rptr_hip_t *h) {
 int rptr_hip_readback_skinned(rptr_hip_t *h, uint32_t geometry, float *xyz, uint32_t *normal_words, uint32_t num_vertices) {
     if (!h) return fail(nullptr, RPTR_E_INVALID, "NULL handle");
     if (!h->have_scene) return fail(h, RPTR_E_INVALID, "readback_skinned before set_scene");
-    if (geometry >= h->skin.bound.size() || (!h->skin.bound[geometry] && !h->morph.bound[geometry]))
-        return fail(h, RPTR_E_INVALID, "geometry %u has no skin (rptr_hip_set_skin) and no morph targets (rptr_hip_set_morph_targets)", geometry);
+    if (geometry >= h->skin.bound.size() || (!h->skin.bound[geometry] && !h->morph.bound[geometry] && !h->normals.bound[geometry]))
+        return fail(h, RPTR_E_INVALID, "geometry %u has no skin (rptr_hip_set_skin) and no morph targets (rptr_hip_set_morph_targets) and no normal groups "
+                                       "(rptr_hip_set_normal_groups)", geometry);
     if (num_vertices != 3u * h->geom_tris[geometry])
         return fail(h, RPTR_E_INVALID, "geometry %u has %u unrolled vertices, got %u", geometry, 3u * h->geom_tris[geometry], num_vertices);
     if (normal_words && !h->master.dynnrm[geometry]) return fail(h, RPTR_E_INVALID, "geometry %u has no normals", geometry);
@@ -1495,4 +1508,98 @@ int rptr_hip_update_morph_weights(rptr_hip_t *h, uint32_t geometry, uint32_t fir
 }
 int rptr_hip_update_morph_weights_device(rptr_hip_t *h, uint32_t geometry, uint32_t first_target, uint32_t count, const float *device_weights) {
     return update_morph_weights_common(h, geometry, first_target, count, device_weights, true);
+}
+
+// ---- recomputed normals (include/rptr_hip.h "recomputed normals", normals.h)
+int rptr_hip_set_normal_groups(rptr_hip_t *h, uint32_t geometry, const uint32_t *group, uint32_t num_vertices, uint32_t flags) {
+    if (!h) return fail(nullptr, RPTR_E_INVALID, "NULL handle");
+    if (!h->have_scene) return fail(h, RPTR_E_INVALID, "set_normal_groups before set_scene");
+    if (geometry >= h->master.dynpos.size() || !h->master.dynpos[geometry])
+        return fail(h, RPTR_E_INVALID, "geometry %u does not belong to a dynamic mesh (RptrMeshDesc.dynamic)", geometry);
+    if (!h->skin.geom_normals[geometry]) return fail(h, RPTR_E_INVALID, "geometry %u has no normals: there are no normal words to recompute", geometry);
+    if ((group == nullptr) != (num_vertices == 0)) return fail(h, RPTR_E_INVALID, "group and num_vertices must both be given, or NULL and 0 to unbind");
+    if (flags & ~RPTR_NORMALS_FLIP) return fail(h, RPTR_E_INVALID, "unknown flag bits 0x%x (RPTR_NORMALS_FLIP is the only flag)", flags & ~RPTR_NORMALS_FLIP);
+    const uint32_t n = 3u * h->geom_tris[geometry];
+    if (group && num_vertices != n) return fail(h, RPTR_E_INVALID, "geometry %u has %u unrolled vertices, got %u", geometry, n, num_vertices);
+    // ---- the labels renumbered densely by first occurrence (every FLAT corner a group of its own), then transposed: per group its
+    // member corners in ascending order (a counting sort over the corners in order)
+    std::vector<uint32_t> offsets, members;
+    uint32_t num_groups = 0;
+    if (group) {
+        std::vector<uint32_t> dense(n);
+        std::unordered_map<uint32_t, uint32_t> id_of;
+        id_of.reserve(n);
+        for (uint32_t v = 0; v < n; ++v) {
+            if (group[v] == RPTR_NORMAL_GROUP_FLAT) {
+                dense[v] = num_groups++;
+                continue;
+            }
+            const auto it = id_of.emplace(group[v], num_groups);
+            if (it.second) ++num_groups;
+            dense[v] = it.first->second;
+        }
+        offsets.assign((size_t)num_groups + 1, 0);
+        for (uint32_t v = 0; v < n; ++v) offsets[(size_t)dense[v] + 1]++;
+        for (uint32_t g = 0; g < num_groups; ++g) offsets[(size_t)g + 1] += offsets[g];
+        members.resize(n);
+        std::vector<uint32_t> cursor(offsets.begin(), offsets.end() - 1);
+        for (uint32_t v = 0; v < n; ++v) members[cursor[dense[v]]++] = v;
+    }
+    // ---- checked: from here on the scene copies change, so nothing of the handle may still be rendering from them
+    HIP_TRY(h, hipSetDevice(h->device));
+    {
+        int rc0 = drain(h);
+        if (rc0) return rc0;
+    }
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    auto &nm = h->normals;
+    if (!group) { // unbind: the normals stay as last written
+        nm.bound[geometry] = 0;
+        return RPTR_OK;
+    }
+    int rc;
+    nm.bound[geometry] = 0;
+    if (!nm.offsets[geometry] && (rc = dev_alloc(h, &nm.offsets[geometry], (size_t)n + 1, &h->scene_allocs))) return rc; // (at most one group per corner)
+    if (!nm.members[geometry] && (rc = dev_alloc(h, &nm.members[geometry], n, &h->scene_allocs))) return rc;
+    if (!nm.d_face || nm.cap_face < h->geom_tris[geometry]) {
+        if ((rc = dev_alloc(h, &nm.d_face, h->geom_tris[geometry], &h->scene_allocs))) return rc;
+        nm.cap_face = h->geom_tris[geometry];
+    }
+    HIP_TRY(h, hipMemcpy(nm.offsets[geometry], offsets.data(), offsets.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (n) HIP_TRY(h, hipMemcpy(nm.members[geometry], members.data(), members.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if ((rc = skin_rest_normals(h, geometry))) return rc; // dynnrm in every scene copy, from the uploaded words, and the mesh's table
+    nm.num_groups[geometry] = num_groups;
+    nm.flip[geometry] = (flags & RPTR_NORMALS_FLIP) ? 1 : 0;
+    nm.bound[geometry] = 1;
+    return RPTR_OK;
+}
+// every bound geometry's normal words from the master copy's current positions, on the backend's stream; then what
+// rptr_hip_update_vertices_device does per geometry
+int rptr_hip_recompute_normals(rptr_hip_t *h) {
+    if (!h) return fail(nullptr, RPTR_E_INVALID, "NULL handle");
+    if (!h->have_scene) return fail(h, RPTR_E_INVALID, "recompute_normals before set_scene");
+    auto &nm = h->normals;
+    if (std::find(nm.bound.begin(), nm.bound.end(), (char)1) == nm.bound.end())
+        return fail(h, RPTR_E_INVALID, "recompute_normals: no geometry is bound (rptr_hip_set_normal_groups)");
+    if (h->ctx_scene.empty()) { // frames in flight read the master vertex buffer and tree
+        int rc0 = drain(h);
+        if (rc0) return rc0;
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    for (size_t g = 0; g < nm.bound.size(); ++g) {
+        if (!nm.bound[g]) continue;
+        const int rc0 = object_motion_before_update(h, (int)g);
+        if (rc0) return rc0;
+        const uint32_t tris = h->geom_tris[g];
+        if (tris) {
+            hipLaunchKernelGGL(rp_k_face_normals, dim3(grid_for(h, tris)), dim3(256), 0, h->stream, (const float *)h->master.dynpos[g], tris, nm.d_face);
+            hipLaunchKernelGGL(rp_k_group_normals, dim3(grid_for(h, nm.num_groups[g])), dim3(256), 0, h->stream, (const uint32_t *)nm.offsets[g],
+                               (const uint32_t *)nm.members[g], (const float4 *)nm.d_face, nm.num_groups[g], (uint32_t)nm.flip[g], h->master.dynnrm[g]);
+        }
+        HIP_TRY(h, hipGetLastError());
+        h->master.mesh_dirty[(size_t)h->geom_mesh[g]] = 1;
+        h->vertex_updates++;
+        h->om.unrefitted = true;
+    }
+    return RPTR_OK;
 }

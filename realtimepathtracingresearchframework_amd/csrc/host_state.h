@@ -363,6 +363,17 @@ struct rptr_hip {
         std::vector<float *> weights;              // ... one float per target, zero after a binding
         std::vector<size_t> cap_entries, cap_weights; // ... what the arrays hold room for (a later binding that fits reuses them)
     } morph;
+    // recomputed normals (rptr_hip_set_normal_groups / recompute_normals, normals.h): normal words from the current positions. It writes
+    // the output array of the two deformers (master.dynnrm) and needs neither; everything here is made by rptr_hip_set_normal_groups.
+    struct Normals {
+        std::vector<char> bound;                   // per global geometry: rptr_hip_recompute_normals writes its normal words
+        std::vector<char> flip;                    // ... RPTR_NORMALS_FLIP
+        std::vector<uint32_t> num_groups;          // ... dense groups (every FLAT corner is one)
+        std::vector<uint32_t *> offsets;           // ... per-group CSR: room for 3 * triangles + 1 offsets into `members`
+        std::vector<uint32_t *> members;           // ... 3 * triangles corners, sorted by (group, corner)
+        float4 *d_face = nullptr;                  // scratch of rp_k_face_normals: one float4 per triangle of the largest bound geometry
+        size_t cap_face = 0;
+    } normals;
 
     // device buffers (frame sized)
     std::vector<FrameCtx> ctx;      // frames in flight (RptrCreateInfo.frames_in_flight, at least 1)

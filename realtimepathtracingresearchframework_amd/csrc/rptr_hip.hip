@@ -22,6 +22,7 @@
 #include "tlas_build.h"
 #include "skin.h"
 #include "morph.h"
+#include "normals.h"
 #include "ploc.h"
 #include <hip/hip_ext.h>
 
@@ -38,6 +39,7 @@
 #include <functional>
 #include <string>
 #include <type_traits>
+#include <unordered_map>
 #include <vector>
 
 #include "host_state.h"

@@ -93,6 +93,12 @@ public:
     void update_morph_weights_device(uint32_t geometry, uint32_t first_target, uint32_t count, const std::vector<const float *> &device_weights) {
         for (size_t k = 0; k < ranks_.size(); ++k) ranks_[k]->update_morph_weights_device(geometry, first_target, count, device_weights.at(k));
     }
+    void set_normal_groups(uint32_t geometry, const std::vector<uint32_t> &groups, bool flip = false) { // every rank is bound
+        for (auto &r : ranks_) r->set_normal_groups(geometry, groups, flip);
+    }
+    void recompute_normals() {
+        for (auto &r : ranks_) r->recompute_normals();
+    }
     std::vector<float> readback_skinned(uint32_t geometry, uint32_t num_vertices, std::vector<uint32_t> *normal_words = nullptr) { // (the ranks' buffers are equal)
         return ranks_[0]->readback_skinned(geometry, num_vertices, normal_words);
     }

@@ -163,6 +163,14 @@ public:
         check(rptr_hip_update_morph_weights_device(h_, geometry, first_target, count, device_weights));
     }
     void skin() { check(rptr_hip_skin(h_)); }
+    // recomputed normals: one label per UNROLLED vertex (corners with the same label share a normal; RPTR_NORMAL_GROUP_FLAT: the face
+    // normal; host/normal_groups.hpp welds a mesh that has no index buffer); no labels at all unbinds. recompute_normals() goes between
+    // update_vertices* / skin() and refit().
+    void set_normal_groups(uint32_t geometry, const std::vector<uint32_t> &groups, bool flip = false) {
+        flush_pipeline();
+        check(rptr_hip_set_normal_groups(h_, geometry, groups.empty() ? nullptr : groups.data(), (uint32_t)groups.size(), flip && !groups.empty() ? RPTR_NORMALS_FLIP : 0u));
+    }
+    void recompute_normals() { check(rptr_hip_recompute_normals(h_)); }
     // the master copy's positions (3 floats per vertex) and, when `normal_words` is given, normal words of a bound geometry
     std::vector<float> readback_skinned(uint32_t geometry, uint32_t num_vertices, std::vector<uint32_t> *normal_words = nullptr) {
         std::vector<float> xyz((size_t)num_vertices * 3);

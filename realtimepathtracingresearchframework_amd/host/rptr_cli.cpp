@@ -3,7 +3,7 @@
 //   <scene> = the reference's .vks file (textures in <name>_textures/) or the flat dump scenes.py writes (.rpsc)
 //   rptr_hip <scene> --validation <prefix> [--validation-spp n] [--img w h] [--pfm] [--denoise iterations | --denoise-temporal iterations | --taa-upscale] [--auto-exposure]
 //   rptr_hip <scene.rpsc> --profiling <csv prefix> [--profiling-fps f] [--profiling-img <prefix>] [--profiling-frames n]
-//            [--animate-wave amplitude kx] [--synchronous] [--fly-through] [--frames-in-flight n [--frames-per-launch b]]
+//            [--animate-wave amplitude kx] [--recompute-normals] [--synchronous] [--fly-through] [--frames-in-flight n [--frames-per-launch b]]
 //   common:  [--eye x y z] [--center x y z] [--up x y z] [--fov deg] [--variant gltf|diffuse|gltf-transmission] [--batch-spp k] [--every-frame]
 //            [--config file.ini]... [--keyframe [<seconds>:]file.ini]... [--camera n] [--freeze-frame] [--upscale n] [--backend hip]
 //            [--sky-data <dir with the Hosek-Wilkie data headers>]   (Sun settings of the .ini files refit the sky: host/sky_fit.hpp; also RPTR_SKY_DATA)
@@ -44,12 +44,18 @@
 //    two uint32 (frames, targets) and frames x targets float32. Frame k stages the weights of frame k mod frames, then skins (the morph
 //    stage runs in front of the skin) and refits. One flag without the other, a size mismatch, a target count that differs between the
 //    two files or a static mesh 0: exit code 2 before a device is touched.
+//  * --recompute-normals (with --animate-wave, --skin --bones or --morph --morph-weights): the written geometry -- first_geometry of mesh
+//    0, which must have normals -- is welded at its rest pose (host/normal_groups.hpp: corners with bitwise equal positions and equal
+//    normal words are one smooth vertex) and bound with rptr_hip_set_normal_groups; rptr_hip_recompute_normals runs before every refit,
+//    so the shading normals follow the wave (or replace what the skinner wrote: morph targets without normal deltas). Without one of
+//    those flags nothing writes vertices: exit code 2 before a device is touched.
 //  * data-capture mode (--data-capture <prefix> [--data-capture-spp n] [--data-capture-no-rgba] [--data-capture-no-aovs]
 //    [--data-capture-albedo-roughness|-normal-depth|-motion]) stores the accumulation buffer and the chosen AOV images of every
 //    keyframe as <prefix>_%04d_{rgba,albedo_roughness,normal_depth,motion_jitter}.exr (libapp/app_state.cpp:499-531).
 // Images: --exr (default, as in the reference), --pfm, --png (write_image.hpp).
 // The scene comes from a dump file (scene_dump.hpp) instead of a .vks (python -m ...vks converts).
 #include "ini_config.hpp"
+#include "normal_groups.hpp"
 #include "render_group.hpp"
 #include "scene_dump.hpp"
 #include "sky_fit.hpp"
@@ -209,6 +215,19 @@ static rptr::SceneDump load_scene(const std::string &path) {
     return s;
 }
 
+// the float positions of a geometry at rest, 3 per unrolled vertex (librender/dequantize.glsl:8-21): what set_scene puts into a dynamic
+// mesh's vertex buffer
+static std::vector<float> rest_positions(const RptrGeometryDesc &g) {
+    std::vector<float> rest((size_t)g.num_tris * 9);
+    for (size_t v = 0; v < (size_t)g.num_tris * 3; ++v) {
+        const uint64_t w = g.qpos[v];
+        rest[3 * v + 0] = float(uint32_t(w) & 0x1FFFFFu) * g.quantized_scaling[0] + g.quantized_offset[0];
+        rest[3 * v + 1] = float(uint32_t(w >> 21) & 0x1FFFFFu) * g.quantized_scaling[1] + g.quantized_offset[1];
+        rest[3 * v + 2] = float(uint32_t(w >> 42) & 0x1FFFFFu) * g.quantized_scaling[2] + g.quantized_offset[2];
+    }
+    return rest;
+}
+
 int main(int argc, char **argv) {
     std::string scene_path, validation_prefix, csv_prefix, profiling_img_prefix, capture_prefix;
     OutputFormat format = FORMAT_EXR;
@@ -225,6 +244,7 @@ int main(int argc, char **argv) {
     std::string bn_table_path, dump_scene_path, sky_data;
     std::string skin_path, bones_path; // --skin / --bones: a skinned mesh 0 (rptr_hip_set_skin / update_bones / skin)
     std::string morph_path, morph_weights_path; // --morph / --morph-weights: morph targets on mesh 0 (rptr_hip_set_morph_targets / update_morph_weights)
+    bool recompute_normals = false; // --recompute-normals: rptr_hip_set_normal_groups on the written geometry, recompute_normals before every refit
     bool got_frames_per_launch = false;
     int upscale = 0, stripe_rows = 8, frames_in_flight = 0, frames_per_launch = 1; // frames_in_flight 0: the reference's loop (two swap buffers)
     bool synchronous = false, fly_through = false;
@@ -265,6 +285,7 @@ int main(int argc, char **argv) {
         else if (a == "--bones") { need(1); bones_path = argv[++i]; }
         else if (a == "--morph") { need(1); morph_path = argv[++i]; }
         else if (a == "--morph-weights") { need(1); morph_weights_path = argv[++i]; }
+        else if (a == "--recompute-normals") recompute_normals = true;
         else if (a == "--denoise") { need(1); g_denoise_iterations = std::atoi(argv[++i]); if (g_denoise_iterations < 1 || g_denoise_iterations > 5) { std::fprintf(stderr, "--denoise takes 1..5 iterations\n"); return 2; } }
         else if (a == "--denoise-temporal") { need(1); g_denoise_temporal_iterations = std::atoi(argv[++i]); if (g_denoise_temporal_iterations < 1 || g_denoise_temporal_iterations > 5) { std::fprintf(stderr, "--denoise-temporal takes 1..5 iterations\n"); return 2; } }
         else if (a == "--taa-upscale") g_taa_upscale = true;
@@ -476,10 +497,19 @@ int main(int argc, char **argv) {
             return 2;
         }
     }
+    if (recompute_normals) {
+        const char *why = nullptr;
+        if (wave_amp == 0.f && skin_path.empty() && morph_path.empty()) why = "needs --animate-wave, --skin --bones or --morph --morph-weights: nothing else writes the vertices of mesh 0";
+        else if (wave_amp != 0.f && !profiling) why = "with --animate-wave needs --profiling: the wave runs in profiling mode only";
+        if (why) {
+            std::fprintf(stderr, "--recompute-normals %s\n", why);
+            return 2;
+        }
+    }
     if (want_help) scene_path.clear(); // prints the usage
     if (scene_path.empty() || (int)validation + (int)profiling + (int)data_capture != 1 || batch_spp < 1 || width < 1 || height < 1 || (profiling && profiling_frames < 1)) {
         std::fprintf(stderr, "usage: rptr_hip <scene.rpsc> (--validation <prefix> [--validation-spp n] | --profiling <csv prefix> [--profiling-fps f] "
-                             "[--profiling-img <prefix>] [--keyframe [len:]file.ini ...] [--profiling-count n] [--synchronous] [--fly-through] [--frames-in-flight n [--frames-per-launch b]] [--animate-wave a k]) [--img w h] [--denoise iterations | --denoise-temporal iterations | --taa-upscale] [--auto-exposure] [--object-motion] [--eye x y z] [--center x y z] "
+                             "[--profiling-img <prefix>] [--keyframe [len:]file.ini ...] [--profiling-count n] [--synchronous] [--fly-through] [--frames-in-flight n [--frames-per-launch b]] [--animate-wave a k [--recompute-normals]]) [--img w h] [--denoise iterations | --denoise-temporal iterations | --taa-upscale] [--auto-exposure] [--object-motion] [--eye x y z] [--center x y z] "
                              "[--up x y z] [--fov deg] [--variant gltf|diffuse] [--batch-spp k] [--every-frame] [--exr|--pfm|--png] [--config file.ini ...] [--sky-data <dir of the Hosek-Wilkie data headers>]\n"
                              "       rptr_hip <scene.rpsc> --data-capture <prefix> [--data-capture-spp n] [--data-capture-no-rgba] [--data-capture-no-aovs] "
                              "[--data-capture-albedo-roughness] [--data-capture-normal-depth] [--data-capture-motion] [--keyframe ...]   (EXR images per keyframe)\n"
@@ -659,6 +689,24 @@ int main(int argc, char **argv) {
             morph_weight_frames.resize((size_t)n_weight_frames * n_morph_targets);
             std::memcpy(morph_weight_frames.data(), raw.data() + 8, morph_weight_frames.size() * sizeof(float));
         }
+        // --recompute-normals: the written geometry welded at its rest pose (normal_groups.hpp); bound once the scene is set
+        std::vector<uint32_t> normal_group_labels;
+        if (recompute_normals) {
+            if (scene.meshes.empty() || !(scene.meshes[0].dynamic & (RPTR_MESH_DYNAMIC | RPTR_MESH_SUBTLY_DYNAMIC))) {
+                std::fprintf(stderr, "--recompute-normals needs a scene whose mesh 0 is dynamic\n");
+                return 2;
+            }
+            const RptrGeometryDesc &g = scene.geometries[scene.meshes[0].first_geometry];
+            if (!g.has_normals || !g.qnrm_uv) {
+                std::fprintf(stderr, "--recompute-normals needs normals on geometry %u: there are no normal words to recompute\n", scene.meshes[0].first_geometry);
+                return 2;
+            }
+            const size_t n_vertices = (size_t)g.num_tris * 3;
+            const std::vector<float> rest_xyz = rest_positions(g);
+            std::vector<uint32_t> words(n_vertices);
+            for (size_t v = 0; v < n_vertices; ++v) words[v] = uint32_t(g.qnrm_uv[v]);
+            normal_group_labels = rptr::normal_groups(rest_xyz.data(), words.data(), n_vertices);
+        }
         if (frames_in_flight == 1) synchronous = true; // (one frame context: nothing to overlap)
         // frame contexts: the reference's two swap buffers; what --frames-in-flight asks for; four for a queued --validation accumulation
         // (its launch sequences are independent of the display: the deeper queue is what fills the GPU)
@@ -685,10 +733,13 @@ int main(int argc, char **argv) {
         // (the morph stage runs in front of the skin, from the one rest pose the two share)
         if (skinned) backend.set_skin(scene.meshes[0].first_geometry, skin_records);
         if (morphed) backend.set_morph_targets(scene.meshes[0].first_geometry, morph_targets);
+        // --recompute-normals: the same geometry's corners in their welded groups; the normals are recomputed in front of every refit
+        if (recompute_normals) backend.set_normal_groups(scene.meshes[0].first_geometry, normal_group_labels);
         auto pose = [&](uint64_t k) {
             if (skinned) backend.update_bones(0, n_bones, &bone_frames[(size_t)(k % n_bone_frames) * n_bones * 12]);
             if (morphed) backend.update_morph_weights(scene.meshes[0].first_geometry, 0, n_morph_targets, &morph_weight_frames[(size_t)(k % n_weight_frames) * n_morph_targets]);
             backend.skin();
+            if (recompute_normals) backend.recompute_normals();
             backend.refit();
         };
         // --object-motion: the file's transform table stays open; play(k) stages the transforms of the file's frame k mod numFrames that
@@ -881,14 +932,7 @@ int main(int argc, char **argv) {
         std::vector<float> rest, cur; // --animate-wave: float positions of geometry 0 at rest
         if (wave_amp != 0.f) {
             if (scene.meshes.empty() || !scene.meshes[0].dynamic) throw std::runtime_error("--animate-wave needs a scene whose mesh 0 is dynamic");
-            const RptrGeometryDesc &g = scene.geometries[scene.meshes[0].first_geometry];
-            rest.resize((size_t)g.num_tris * 9);
-            for (size_t v = 0; v < (size_t)g.num_tris * 3; ++v) { // librender/dequantize.glsl:8-21
-                const uint64_t w = g.qpos[v];
-                rest[3 * v + 0] = float(uint32_t(w) & 0x1FFFFFu) * g.quantized_scaling[0] + g.quantized_offset[0];
-                rest[3 * v + 1] = float(uint32_t(w >> 21) & 0x1FFFFFu) * g.quantized_scaling[1] + g.quantized_offset[1];
-                rest[3 * v + 2] = float(uint32_t(w >> 42) & 0x1FFFFFu) * g.quantized_scaling[2] + g.quantized_offset[2];
-            }
+            rest = rest_positions(scene.geometries[scene.meshes[0].first_geometry]);
             cur = rest;
         }
         const std::string csv_path = csv_prefix + ".csv";
@@ -1088,6 +1132,7 @@ int main(int argc, char **argv) {
                 const float phase = 6.283185307179586f * (float)fp.time;
                 for (size_t v = 0; v < rest.size() / 3; ++v) cur[3 * v + 1] = rest[3 * v + 1] + wave_amp * std::sin(wave_k * rest[3 * v] + phase);
                 backend.update_vertices(scene.meshes[0].first_geometry, cur.data(), (uint32_t)(cur.size() / 3));
+                if (recompute_normals) backend.recompute_normals();
                 backend.refit();
             }
             if (deformed) pose((uint64_t)frame); // the bones and morph weights of this frame: skin, refit, and the accumulation starts over

@@ -71,6 +71,19 @@ def quantize_normals(n):
     return ux | (uy << np.uint32(16))
 
 
+def normal_groups(positions, normal_words):
+    """Weld unrolled vertices for rptr_hip_set_normal_groups: corners whose rest positions are BITWISE equal and whose uploaded normal
+    words are equal become one group, so smooth vertices weld and hard edges stay hard. positions (n, 3) float32, normal_words (n,)
+    uint32 -> (n,) uint32, groups numbered by first occurrence (host/normal_groups.hpp gives the same array)."""
+    key = np.empty((len(normal_words), 4), np.uint32)
+    key[:, :3] = np.ascontiguousarray(positions, dtype=f32).reshape(-1, 3).view(np.uint32)
+    key[:, 3] = np.asarray(normal_words, np.uint32)
+    _, first, inverse = np.unique(key, axis=0, return_index=True, return_inverse=True)
+    rank = np.empty(len(first), np.uint32)
+    rank[np.argsort(first, kind="stable")] = np.arange(len(first), dtype=np.uint32)  # sorted-key id -> order of first occurrence
+    return rank[np.asarray(inverse).reshape(-1)]
+
+
 def quantize_uvs(uv):
     """quantize.h:38-42 with safety_offset = 0 -> (n,) uint32."""
     uv = np.asarray(uv, dtype=f32)
