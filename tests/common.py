@@ -20,6 +20,14 @@ def renderer(scene, W, H, **kw):
     return r
 
 
+def one_grid_elements(per_cu=8):
+    """how many elements one launch of a grid-stride kernel covers before any lane takes a second trip: csrc/host_state.h grid_for caps
+    the grid at per_cu * num_cus blocks of 256, and num_cus is the device's multiProcessorCount (rptr_hip.hip). Tests that mean to
+    cross the cap size their shapes from this value."""
+    import torch
+    return torch.cuda.get_device_properties(0).multi_processor_count * per_cu * 256
+
+
 def config(scene, variant=abi.VARIANT_GLTF, reset=True, camera=None, freeze_frame=False):
     return backend.RenderConfiguration(camera or scene.camera_params(), active_variant=variant, reset_accumulation=reset, freeze_frame=freeze_frame)
 

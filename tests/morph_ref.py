@@ -94,6 +94,93 @@ def morph(rest_pos, rest_words, targets, weights, skin=None, prev_pos=None, prev
     return pos, words.astype(np.uint32), rejected
 
 
+# ---- runs of entries across rp_k_morph's four-entry fetch (RP_MORPH_CHUNK): the fixture of tests/test_gpu_morph.py section 9, and the
+# reorderings tests/test_morph_cpu.py uses to show that the fixture can see an order error
+RUN_LENGTHS = (0, 1, 2, 3, 4, 5, 7, 8, 9, 12, 13)   # under a chunk, a full chunk, one and two chunks with every remainder, three chunks + 1
+LONG_RUN = 40                                       # ten trips
+
+
+def grid_rest_pose(nx=7, nz=5):
+    """(positions, normal words) of geometry 0 of scenes.grid(nx, nz, deform_t=0.0) as set_scene uploads them"""
+    geo = scenes.grid(nx, nz, deform_t=0.0).geometries[0]
+    return scenes.dequantize_positions(geo.qpos, geo.scaling, geo.offset), (np.asarray(geo.qnrm_uv, np.uint64) & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+
+
+def run_targets(P, n_targets=1024, seed=11):
+    """n_targets sparse targets over the vertices P such that vertex v has RUN_LENGTHS[v % 11] entries and the middle vertex LONG_RUN, on
+    target indices drawn from all of 0 .. n_targets - 1 (the last one is used). Every delta component is uniform(-1, 1) * 2^uniform(-6, 6),
+    positions times 1/64 of the mesh's extent: partial sums of very different magnitude, so the order of a run's sum shows in its bits."""
+    P = np.asarray(P, f32).reshape(-1, 3)
+    n = len(P)
+    rng = np.random.default_rng(seed)
+    size = float((P.max(axis=0) - P.min(axis=0)).max())
+    count = np.array([RUN_LENGTHS[v % len(RUN_LENGTHS)] for v in range(n)], np.int64)
+    count[n // 2] = LONG_RUN
+    listed = [[] for _ in range(n_targets)]
+    for v in rng.permutation(n).tolist():                           # (a target lists its vertices in random order)
+        if v == n // 2:
+            ts = np.concatenate([rng.choice(n_targets - 1, LONG_RUN - 1, replace=False), [n_targets - 1]])
+        else:
+            ts = rng.choice(n_targets, count[v], replace=False)
+        for t in ts.tolist():
+            listed[t].append(v)
+    out = []
+    for t in range(n_targets):
+        v = np.array(listed[t], np.uint32)
+        mag = lambda: rng.uniform(-1, 1, (len(v), 3)) * 2.0 ** rng.uniform(-6, 6, (len(v), 3))
+        out.append((v, (mag() * (size / 64)).astype(f32), (mag() / 8).astype(f32)))
+    counts = np.bincount(np.concatenate([t[0] for t in out]).astype(np.int64), minlength=n)
+    assert set(counts.tolist()) == set(RUN_LENGTHS) | {LONG_RUN} and (counts == LONG_RUN).sum() == 1 and len(out[n_targets - 1][0]) > 0
+    return out
+
+
+def run_weight_sets(targets, n, seed=12):
+    """-> {name: (weights (len(targets),) float32, the vertex the set is about or None)}: uniform(-1.5, 1.5), none zero ("mixed"), and
+    the same with the special cases of the entry loop put on the boundaries of its four-entry trips:
+      first-four-zero  entries 0-3 of a vertex of 5 entries have weight 0, entry 4 has not: `applied` is set in the second trip only
+      entry-3-zero     only entry 3 of a vertex of 9 entries: the last lane of a full first trip is skipped
+      entry-4-zero     only entry 4 of a vertex of 13 entries: the first lane of the second trip is skipped
+      zero             every weight
+      nan              a NaN on an entry of the second trip (positions 4-7) of a vertex, on a target no other vertex is listed in"""
+    offsets, target, _, _ = transpose(targets, n)
+    count = np.diff(offsets)
+    uses = np.bincount(target, minlength=len(targets))
+    rng = np.random.default_rng(seed)
+    base = rng.uniform(-1.5, 1.5, len(targets)).astype(f32)
+    assert (base != 0).all()
+    entries = lambda v: target[offsets[v]:offsets[v + 1]]
+    sets = {"mixed": (base, None), "zero": (np.zeros(len(targets), f32), None)}
+    for name, length, zeroed in (("first-four-zero", 5, [0, 1, 2, 3]), ("entry-3-zero", 9, [3]), ("entry-4-zero", 13, [4])):
+        v = int(np.nonzero(count == length)[0][0])
+        w = base.copy()
+        w[entries(v)[zeroed]] = 0
+        z = w[entries(v)] == 0
+        assert np.array_equal(np.nonzero(z)[0], zeroed), name
+        sets[name] = (w, v)
+    lone = [(v, k) for v in np.nonzero(count > 4)[0].tolist() for k in range(4, min(int(count[v]), 8)) if uses[entries(v)[k]] == 1]
+    assert lone
+    v, k = lone[0]
+    w = base.copy()
+    w[entries(v)[k]] = np.nan
+    sets["nan"] = (w, v)
+    return sets
+
+
+def reordered(transposed, kind):
+    """transpose()'s arrays with every vertex's entries "reversed", or with its entries 4 ... in front of its entries 0-3 ("trips-swapped"):
+    what a kernel would sum that walked a run backwards, or took its trips in the wrong order"""
+    offsets, target, dpos, dnrm = transposed
+    perm = np.arange(len(target))
+    for v in range(len(offsets) - 1):
+        a, b = int(offsets[v]), int(offsets[v + 1])
+        if kind == "reversed":
+            perm[a:b] = np.arange(a, b)[::-1]
+        else:
+            assert kind == "trips-swapped"
+            perm[a:b] = np.concatenate([np.arange(min(a + 4, b), b), np.arange(a, min(a + 4, b))])
+    return offsets, target[perm], dpos[perm], dnrm[perm]
+
+
 # ---- the files bin/rptr_hip --morph / --morph-weights reads (host/rptr_cli.cpp)
 def morph_file(targets):
     """the file bin/rptr_hip --morph reads: uint32 targets, then per target uint32 deltas and that many RptrMorphDelta records"""

@@ -11,8 +11,14 @@ The scene, the chain rig and the observation helpers are those of tests/test_gpu
 target 0 dense, target 1 a patch of 20 vertices, target 2 the last vertex alone (the end of the offsets array is read), target 300 (an
 index above 255) a patch that overlaps target 1, all others empty -- vertices with 1, 2 and 3 entries. The loose mesh gets two sparse
 targets without normal deltas that leave some vertices with no entry at all. Weight sets: all zero, one-hot, and a mixed set with a
-negative weight and one above 1. Frames are 48 x 32."""
+negative weight and one above 1. Frames are 48 x 32.
+
+Those shapes never take rp_k_morph's entry loop (four entries fetched per trip) round a second time. Section 9 does: runs of 0 to 13
+entries and one of 40 on target indices up to 1023, through all four instantiations of the kernel, with zero and NaN weights placed on
+the boundaries of the trips (morph_ref.run_targets, run_weight_sets)."""
+import copy
 import ctypes as C
+import dataclasses
 
 import numpy as np
 import pytest
@@ -493,3 +499,85 @@ def test_a_mesh_without_targets_behaves_as_before(setup):
     assert TS._same_observations(TS._observe(a, scene, cam, q), TS._observe(b, scene, cam, q))
     a.close()
     b.close()
+
+
+# ------------------------------------------------------------------ 9. runs of entries across the four-entry fetch
+def _without_normals(scene):
+    """the scene whose geometry 0 has no normals (its uv halves stay): rp_k_morph<*, false>"""
+    s = copy.copy(scene)
+    s.geometries = [dataclasses.replace(scene.geometries[0], has_normals=False)] + list(scene.geometries[1:])
+    return s
+
+
+@pytest.fixture(scope="module")
+def runs():
+    """the grid's 210 vertices with runs of 0, 1, 2, 3, 4, 5, 7, 8, 9, 12, 13 entries and one of 40, on 1024 targets (morph_ref.run_targets;
+    tests/test_morph_cpu.py shows that an order error changes the bits of this fixture), and the weight sets of morph_ref.run_weight_sets"""
+    scene = TS._scene()
+    P, words = TS._rest(scene, 0)
+    assert np.array_equal(float_bits(P), float_bits(MR.grid_rest_pose()[0])) and np.array_equal(words, MR.grid_rest_pose()[1])
+    targets = MR.run_targets(P)
+    counts = np.bincount(np.concatenate([t[0] for t in targets]).astype(np.int64), minlength=len(P))
+    assert set(counts.tolist()) == {0, 1, 2, 3, 4, 5, 7, 8, 9, 12, 13, 40} and (counts == 40).sum() == 1
+    assert len(targets) == abi.MAX_MORPH_TARGETS and len(targets[-1][0]) > 0
+    sets = MR.run_weight_sets(targets, len(P))
+    assert all((sets[k][0] != 0).all() for k in ("mixed", "nan"))
+    return scene, P, words, targets, MR.transpose(targets, len(P)), sets, TS._rig(scene)[0], TS._bones(31)
+
+
+@pytest.mark.parametrize("skinned", [False, True], ids=["alone", "skinned"])
+@pytest.mark.parametrize("normals", [True, False], ids=["normals", "positions-only"])
+def test_runs_across_the_four_entry_fetch(runs, normals, skinned):
+    """all four instantiations of rp_k_morph against the restatement, bit for bit: positions, normal words and the rejected count, for
+    every weight set; the NaN comes last and from a device tensor (read-backs only, finite weights before the handle closes)"""
+    import torch
+    scene, P, rest_words, targets, tr, sets, rig, M = runs
+    words = rest_words if normals else None
+    skin0 = (rig[0], rig[1], M) if skinned else None
+    r = renderer(scene if normals else _without_normals(scene), W, H)
+    if skinned:
+        r.set_skin(0, *rig)
+        r.update_bones(0, M[:5])
+        r.update_bones(TS.GROUP_BONE, M[TS.GROUP_BONE:TS.GROUP_BONE + 1])
+    r.set_morph_targets(0, targets)
+
+    def check(name, w, prev=(None, None), refit=True):
+        r.update_morph_weights(0, 0, w)
+        r.skin()
+        if refit:
+            r.refit()
+        pos, ww, rejected = MR.morph(P, words, targets, w.cpu().numpy() if hasattr(w, "cpu") else w, skin=skin0, prev_pos=prev[0], prev_words=prev[1], transposed=tr)
+        xyz, got = r.readback_skinned(0)
+        bad = np.nonzero((float_bits(xyz) != float_bits(pos)).any(axis=1))[0]
+        assert len(bad) == 0, "%s: positions differ at vertices %s" % (name, bad[:8])
+        if normals:
+            bad = np.nonzero(got != ww)[0]
+            assert len(bad) == 0, "%s: normal words differ at vertices %s" % (name, bad[:8])
+        else:
+            assert got is None
+        return pos, ww, rejected
+
+    mixed = check("mixed", sets["mixed"][0])
+    assert not mixed[2].any()
+    for name in ("first-four-zero", "entry-3-zero", "entry-4-zero"):
+        w, v = sets[name]
+        pos, ww, rejected = check(name, w)
+        assert not rejected.any() and not np.array_equal(float_bits(pos[v]), float_bits(mixed[0][v]))
+        if name == "first-four-zero" and normals and not skinned:       # applied in the second trip only: re-quantised, not the rest word
+            assert ww[v] != rest_words[v]
+    pos, ww, _ = check("zero", sets["zero"][0])
+    rest = S.skin(P, words, rig[0], rig[1], M) if skinned else (P, words)
+    assert np.array_equal(float_bits(pos), float_bits(rest[0])) and (not normals or np.array_equal(ww, rest[1]))
+    assert r.get_option("skin_vertices_rejected") == 0
+    first = check("mixed again", sets["mixed"][0])
+    w, v = sets["nan"]
+    buf = torch.from_numpy(w).cuda()
+    torch.cuda.synchronize()
+    pos, ww, rejected = check("nan", buf, prev=first[:2], refit=False)
+    assert rejected.sum() == 1 and rejected[v] and np.array_equal(float_bits(pos[v]), float_bits(first[0][v]))
+    others = ~rejected & (np.diff(tr[0]) > 0)
+    assert (float_bits(pos[others]) == float_bits(first[0][others])).all()      # the same finite weights: its neighbours are what they were
+    assert r.get_option("skin_vertices_rejected") == 1
+    check("mixed after the nan", sets["mixed"][0])
+    assert r.get_option("skin_vertices_rejected") == 1
+    r.close()

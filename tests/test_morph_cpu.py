@@ -126,6 +126,46 @@ def test_the_order_of_a_targets_deltas_changes_nothing():
         assert (np.diff(target[offsets[i]:offsets[i + 1]]) > 0).all()
 
 
+def test_the_run_fixture_can_see_an_order_error():
+    """the fixture of tests/test_gpu_morph.py section 9 (runs of 0 ... 13 and 40 entries on a four-entry fetch): the restatement with
+    every vertex's entries applied in reverse, and with its entries 4 ... applied before its entries 0-3, gives other position bits for
+    at least half of the vertices that have five entries or more -- a kernel that walked a run or its trips in another order could not
+    pass the bit-for-bit comparison. Vertices of up to four entries are one trip: the swap leaves them alone."""
+    P, words = MR.grid_rest_pose()
+    n = len(P)
+    targets = MR.run_targets(P)
+    assert len(targets) == abi.MAX_MORPH_TARGETS and n == 210
+    sets = MR.run_weight_sets(targets, n)
+    w = sets["mixed"][0]
+    tr = MR.transpose(targets, n)
+    count = np.diff(tr[0])
+    want = MR.morph(P, words, targets, w, transposed=tr)
+    assert not want[2].any()
+    long = count >= 5
+    assert long.sum() > 100
+    for kind in ("reversed", "trips-swapped"):
+        got = MR.morph(P, words, targets, w, transposed=MR.reordered(tr, kind))
+        changed = (_bits(got[0]) != _bits(want[0])).any(axis=1)
+        print("%s: position bits change for %.3f of the vertices with five entries or more" % (kind, changed[long].mean()))
+        assert changed[long].mean() >= 0.5, (kind, changed[long].mean())
+        if kind == "trips-swapped":
+            assert not changed[count <= 4].any()
+    # the weight sets say what they claim, and the special cases leave their mark on the reference: a word that is re-quantised,
+    # one rejected vertex
+    offsets, target = tr[0], tr[1]
+    for name, zeroed in (("first-four-zero", [0, 1, 2, 3]), ("entry-3-zero", [3]), ("entry-4-zero", [4])):
+        wk, v = sets[name]
+        assert count[v] >= 5 and np.array_equal(np.nonzero(wk[target[offsets[v]:offsets[v + 1]]] == 0)[0], zeroed)
+    wk, v = sets["first-four-zero"]
+    got = MR.morph(P, words, targets, wk, transposed=tr)
+    assert got[1][v] != words[v] and not np.array_equal(_bits(got[0][v]), _bits(P[v]))
+    wk, v = sets["nan"]
+    rejected = MR.morph(P, words, targets, wk, transposed=tr)[2]
+    assert rejected.sum() == 1 and rejected[v]
+    k = int(np.nonzero(np.isnan(wk[target[offsets[v]:offsets[v + 1]]]))[0][0])
+    assert 4 <= k < 8
+
+
 def test_abi_records():
     assert C.sizeof(abi.MorphDelta) == 32 and np.dtype(abi.MORPH_DELTA_DTYPE).itemsize == 32
     assert C.sizeof(abi.MorphTargetDesc) == 16 and abi.MAX_MORPH_TARGETS == 1024
