@@ -259,7 +259,8 @@ typedef struct RptrInstanceDesc {
  * parameters (rendering/rt/material_textures.glsl:37-75 with USE_MIPMAPPING, librender/render_params.glsl.h:8), textureLod(uv, bounce)
  * for normal maps (pt_megakernel.glsl:642-648), level 0 for the any-hit alpha test (:205).
  * mip_levels: 0 or 1 = level 0 only; n = rgba8 holds levels 0..n-1 back to back, level l being max(1, width >> l) x max(1, height >> l)
- * texels (what a .vkt file holds; none is generated: vulkan/resource_utils.cpp:34-100 uploads the levels of the file).
+ * texels (what a .vkt file holds; set_scene generates none: vulkan/resource_utils.cpp:34-100 uploads the levels of the file. "dynamic textures"
+ * below makes the chain on the device).
  * srgb != 0: the colour channels are sRGB-encoded (VK_FORMAT_R8G8B8A8_SRGB), alpha is linear. A float material parameter
  * with its sign bit set is a texture handle (rendering/bsdfs/texture_channel_mask.h): bits 0..28 = index into
  * RptrSceneDesc.textures, bits 29..30 = channel for scalar parameters. */
@@ -626,6 +627,54 @@ int rptr_hip_update_morph_weights_device(rptr_hip_t *h, uint32_t geometry, uint3
 #define RPTR_NORMALS_FLIP 1u   /* the mesh is wound the other way: negate every recomputed normal */
 int rptr_hip_set_normal_groups(rptr_hip_t *h, uint32_t geometry, const uint32_t *group, uint32_t num_vertices, uint32_t flags);
 int rptr_hip_recompute_normals(rptr_hip_t *h);
+
+/* ---- dynamic textures: new texels in, mip chain generated on the device (csrc/texture_mips.h rp_k_mip_level).
+ * set_scene uploads every RptrTextureDesc once, and the sampler filters the levels the host supplied; until here nothing could write a
+ * texel again (a video or procedural texture, a paint tool, a light-map baker needed a fresh set_scene and with it every BVH), and a
+ * host with plain RGBA8 images had level 0 only. No frame kernel changes; a scene that never calls these functions allocates and
+ * launches what it did. (RPTR_HIP_ABI_VERSION stays 5: new entry points, no layout changes.)
+ * rptr_hip_update_texture(h, texture, rgba8, n_bytes, flags): after set_scene. rgba8 is LEVEL 0 ONLY, row 0 first, and n_bytes must be
+ * 4 * width * height of the texture as set_scene received it: size and the srgb flag never change. With RPTR_TEXTURE_GENERATE_MIPS the
+ * levels 1 .. full - 1 are made on the device from the new level 0 and the texture has the full chain down to 1 x 1; without it the
+ * texture becomes level 0 only (rptr_hip_texture_levels says 1): a stale level is never sampled. (NULL, 0, RPTR_TEXTURE_GENERATE_MIPS)
+ * keeps level 0 and generates the chain -- the call of a host that has no mip levels. The _device form reads DEVICE memory, ordered on
+ * the backend's stream, without a host synchronisation behind the copy.
+ * Storage: the first call that needs more room than set_scene allocated gets ONE allocation for the full chain; level 0 is copied
+ * across on the device and the old block is released. Later calls reuse it: repeated updates neither allocate nor leak.
+ * Ordering: textures are shared by every scene copy, so the call waits for the frames in flight (as rptr_hip_set_skin does), then
+ * works on the backend's stream: the copy, one launch per level, and last the texture's record, patched in place. Every frame and every
+ * query run submitted afterwards, on any frame context or caller's stream, is queued behind that stream's work and sees the new texels;
+ * frames submitted before show the old ones. Double-buffered textures that would avoid the wait are out of scope.
+ * RPTR_E_INVALID, nothing changed and a message that names the offender: a NULL handle; a call before set_scene; texture >=
+ * num_textures; n_bytes other than 4 * width * height; unknown flag bits; NULL texels without the flag or with n_bytes != 0.
+ * RPTR_E_UNSUPPORTED: a texture that any material with emission_intensity > 0 reads, through a textured parameter or its normal map
+ * (decided once, in set_scene): RptrSceneDesc.lights carry radiance the host prepared from that texture, and next-event estimation would
+ * silently disagree with what paths see -- the precedent of "moving lights". Alpha-tested textures are allowed (the test reads level
+ * 0). world_size > 1: every rank holds the whole scene, call on each.
+ * rptr_hip_readback_texture(h, texture, level, rgba8, n_bytes): one level as the device holds it, behind whatever was queued on the
+ * backend's stream; n_bytes == 4 * that level's texels. A level beyond the current levels: RPTR_E_INVALID. rptr_hip_texture_levels: the
+ * levels a sampler may read now. rptr_hip_srgb_decode_table (host only, no handle): the 256-entry table rp_srgb_decode_lut makes and
+ * set_scene uploads, so that a host can restate the filter.
+ * The filter -- the reference generates no mip levels, so this rule is the definition. Level l + 1 is made from the QUANTISED level l; a
+ * source of h x w texels gives max(1, h >> 1) x max(1, w >> 1). Taps per axis of source size n at destination coordinate x, as
+ * (source index, integer weight):
+ *     n == 1                   (0, 1)                                          total 1
+ *     n even                   (2x, 1), (2x + 1, 1)                            total 2
+ *     n odd >= 3, m = n >> 1   (2x, m - x), (2x + 1, m), (2x + 2, x + 1)       total n   (the exact-area box: nothing dropped, nothing shifts)
+ * Per channel, in binary32, every product, sum and quotient rounded on its own, IEEE division, no contraction (as "skinned meshes"):
+ *     f(c) = srgb_decode_table[c] for the colour channels of an sRGB texture; float(c) for alpha and every channel of a linear texture
+ *     acc = 0; for ty in row order, tx in column order: acc = acc + float(wx * wy) * f(texel[ty][tx])      (the integer product converted once)
+ *     mean = acc / float(totx * toty)                                                                      (the integer product converted once)
+ *     linear code: min(255, int(mean + 0.5f))
+ *     sRGB code: the number of k in 1..255 with mean >= T[k], T[k] = (table[k - 1] + table[k]) * 0.5f
+ * The thresholds are built on the host from the same table; the device evaluates no transcendental function, and the result is bit for
+ * bit what tests/texture_mips_ref.py and scenes.generate_mips compute in numpy. On even sizes the linear path is (a + b + c + d + 2) >> 2. */
+#define RPTR_TEXTURE_GENERATE_MIPS 1u
+int rptr_hip_update_texture(rptr_hip_t *h, uint32_t texture, const uint8_t *rgba8, size_t n_bytes, uint32_t flags);
+int rptr_hip_update_texture_device(rptr_hip_t *h, uint32_t texture, const uint8_t *device_rgba8, size_t n_bytes, uint32_t flags);
+int rptr_hip_readback_texture(rptr_hip_t *h, uint32_t texture, uint32_t level, uint8_t *rgba8, size_t n_bytes);
+int rptr_hip_texture_levels(const rptr_hip_t *h, uint32_t texture, uint32_t *out_levels);
+void rptr_hip_srgb_decode_table(float out256[256]); /* host only: the table rp_srgb_decode_lut makes and set_scene uploads */
 
 /* ---- RenderBackend::params / lighting_params / update_config
  * (render_backend.h:69-76, render_vulkan.cpp:2943-2959) */

@@ -272,6 +272,7 @@ MORPH_DELTA_DTYPE = [("vertex", "<u4"), ("dpos", "<f4", (3,)), ("dnrm", "<f4", (
 
 NORMAL_GROUP_FLAT = 0xFFFFFFFF  # RPTR_NORMAL_GROUP_FLAT: the corner gets its own triangle's face normal
 NORMALS_FLIP = 1                # RPTR_NORMALS_FLIP
+TEXTURE_GENERATE_MIPS = 1       # RPTR_TEXTURE_GENERATE_MIPS
 
 
 class SurfaceHit(C.Structure):  # include/rptr_hip.h RptrSurfaceHit: six 16-byte rows per surface query
@@ -347,7 +348,9 @@ EXPORTED_SYMBOLS = [
     "rptr_hip_render", "rptr_hip_render_async", "rptr_hip_render_batch_async", "rptr_hip_render_batch_cameras_async", "rptr_hip_wait", "rptr_hip_set_stage_timing", "rptr_hip_set_freeze_frame", "rptr_hip_set_option", "rptr_hip_get_option", "rptr_hip_option_count", "rptr_hip_option_name", "rptr_hip_set_rng_variant", "rptr_hip_set_bvh_policy", "rptr_hip_bvh_rebuild_count", "rptr_hip_update_instances", "rptr_hip_update_instances_device", "rptr_hip_set_tlas_policy", "rptr_hip_tlas_rebuild_count", "rptr_hip_set_light_sources", "rptr_hip_readback_lights",
     "rptr_hip_set_skin", "rptr_hip_update_bones", "rptr_hip_update_bones_device", "rptr_hip_skin", "rptr_hip_readback_skinned",
     "rptr_hip_set_morph_targets", "rptr_hip_update_morph_weights", "rptr_hip_update_morph_weights_device",
-    "rptr_hip_set_normal_groups", "rptr_hip_recompute_normals", "rptr_hip_get_framebuffer_size", "rptr_hip_readback_f32", "rptr_hip_readback_u8", "rptr_hip_readback_aov",
+    "rptr_hip_set_normal_groups", "rptr_hip_recompute_normals",
+    "rptr_hip_update_texture", "rptr_hip_update_texture_device", "rptr_hip_readback_texture", "rptr_hip_texture_levels", "rptr_hip_srgb_decode_table",
+    "rptr_hip_get_framebuffer_size", "rptr_hip_readback_f32", "rptr_hip_readback_u8", "rptr_hip_readback_aov",
     "rptr_hip_denoise_defaults", "rptr_hip_denoise", "rptr_hip_readback_denoised_f32", "rptr_hip_readback_denoised_u8",
     "rptr_hip_denoise_temporal_defaults", "rptr_hip_denoise_temporal", "rptr_hip_readback_denoise_history_f32",
     "rptr_hip_taa_upscale_defaults", "rptr_hip_taa_upscale", "rptr_hip_readback_upscaled_u8",

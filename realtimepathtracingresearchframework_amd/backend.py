@@ -104,6 +104,12 @@ def load_library(path=None):
     L.rptr_hip_update_morph_weights_device.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]
     L.rptr_hip_set_normal_groups.argtypes = [vp, C.c_uint32, vp, C.c_uint32, C.c_uint32]
     L.rptr_hip_recompute_normals.argtypes = [vp]
+    L.rptr_hip_update_texture.argtypes = [vp, C.c_uint32, vp, C.c_size_t, C.c_uint32]
+    L.rptr_hip_update_texture_device.argtypes = [vp, C.c_uint32, vp, C.c_size_t, C.c_uint32]
+    L.rptr_hip_readback_texture.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.c_size_t]
+    L.rptr_hip_texture_levels.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32)]
+    L.rptr_hip_srgb_decode_table.argtypes = [C.POINTER(C.c_float)]
+    L.rptr_hip_srgb_decode_table.restype = None
     L.rptr_hip_bvh_build_info.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.rptr_hip_traversal_preset.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.rptr_hip_get_framebuffer_size.argtypes = [vp, C.POINTER(C.c_uint32)]
@@ -159,6 +165,13 @@ def load_library(path=None):
         getattr(L, name)  # AttributeError if the library lacks a declared symbol
     _lib = L
     return L
+
+
+def srgb_decode_table():
+    """(256,) float32: the sRGB decode table set_scene uploads (rptr_hip_srgb_decode_table; no GPU needed). scenes.generate_mips takes it."""
+    out = np.zeros(256, dtype=np.float32)
+    load_library().rptr_hip_srgb_decode_table(out.ctypes.data_as(C.POINTER(C.c_float)))
+    return out
 
 
 def build_bvh_host(scene):
@@ -271,6 +284,7 @@ class RenderHip:
         self._check(self._L.rptr_hip_set_scene(self._h, C.byref(desc)))
         self._num_lights = int(desc.num_lights)
         self._geometries = [(int(g.num_tris), bool(g.has_normals and g.qnrm_uv is not None)) for g in scene.geometries]  # (readback_skinned)
+        self._textures = [tuple(int(v) for v in np.asarray(t.rgba).shape[:2]) for t in scene.textures]  # (height, width): readback_texture
         self.update_config(scene)
 
     def update_config(self, scene_or_params):
@@ -859,6 +873,37 @@ class RenderHip:
         """The normal words of every bound geometry from its current positions, on the device: after update_vertices* / skin(), before
         refit()."""
         self._check(self._L.rptr_hip_recompute_normals(self._h))
+
+    # ---- dynamic textures (rptr_hip_update_texture / readback_texture / texture_levels): new texels in, mip chain made on the device
+    def update_texture(self, index, rgba=None, generate_mips=True):
+        """New level-0 texels for texture `index` of the scene: rgba is (height, width, 4) uint8 of the size set_scene received, as a
+        numpy array or a CUDA / HIP torch uint8 tensor written on the backend's stream (the _device form: no host synchronisation).
+        generate_mips: the full chain down to 1 x 1 is made on the device (scenes.generate_mips states the filter); without it the
+        texture becomes level 0 only. rgba=None keeps level 0 and generates the chain. Waits for the frames in flight; every frame and
+        query submitted afterwards sees the new texels. A texture an emissive material reads is refused (BackendError, UNSUPPORTED)."""
+        flags = abi.TEXTURE_GENERATE_MIPS if generate_mips else 0
+        if rgba is None:
+            self._check(self._L.rptr_hip_update_texture(self._h, int(index), None, 0, flags))
+        elif hasattr(rgba, "data_ptr") and getattr(rgba, "is_cuda", False):
+            assert str(rgba.dtype) == "torch.uint8" and rgba.is_contiguous()
+            self._check(self._L.rptr_hip_update_texture_device(self._h, int(index), C.c_void_p(rgba.data_ptr()), rgba.numel(), flags))
+        else:
+            a = np.ascontiguousarray(rgba, dtype=np.uint8)
+            self._check(self._L.rptr_hip_update_texture(self._h, int(index), a.ctypes.data_as(C.c_void_p) if a.size else None, a.size, flags))
+
+    def texture_levels(self, index):
+        """the levels of texture `index` a sampler may read now"""
+        n = C.c_uint32(0)
+        self._check(self._L.rptr_hip_texture_levels(self._h, int(index), C.byref(n)))
+        return int(n.value)
+
+    def readback_texture(self, index, level=0):
+        """(max(1, height >> level), max(1, width >> level), 4) uint8: one level of texture `index` as the device holds it, after pending work"""
+        tex = getattr(self, "_textures", [])
+        h, w = tex[int(index)] if 0 <= int(index) < len(tex) else (0, 0)
+        out = np.zeros((max(1, h >> int(level)) if h else 0, max(1, w >> int(level)) if w else 0, 4), np.uint8)
+        self._check(self._L.rptr_hip_readback_texture(self._h, int(index), int(level), out.ctypes.data_as(C.c_void_p) if out.size else None, out.size))
+        return out
 
     def set_rng_variant(self, rng_variant, table=None):
         """RenderBackendOptions::rng_variant (render_params.glsl.h:34-37,76) + the table upload of the point set's render extension

@@ -51,8 +51,23 @@ static int scene_upload_textures(rptr_hip *h, const RptrSceneDesc *s, RpTexture 
     if ((h->uses_textures || h->uses_alpha) && h->path_capacity)
         for (FrameCtx &c : h->ctx)
             if (!c.ps.footprint && (rc = dev_alloc(h, &c.ps.footprint, h->path_capacity, nullptr))) return rc;
+    h->tex = decltype(h->tex)(); // dynamic textures (texture_mips.h): the host's copy of the records, and which textures an emissive material reads
+    h->tex.cap_texels.assign(s->num_textures, 0);
+    h->tex.emissive.assign(s->num_textures, 0);
+    for (uint32_t m = 0; m < s->num_materials; ++m) { // (scene_validate checked every index)
+        const RptrBaseMaterial &mat = s->materials[m];
+        if (!(mat.emission_intensity > 0.0f)) continue;
+        if (mat.normal_map != -1) h->tex.emissive[(size_t)mat.normal_map] = 1;
+        const float vals[5] = {mat.base_color[0], mat.roughness, mat.specular, mat.metallic, mat.ior};
+        for (float v : vals) {
+            uint32_t u;
+            memcpy(&u, &v, 4);
+            if (u & RPTR_TEXTURED_PARAM_MASK) h->tex.emissive[RPTR_TEXTURE_ID(u)] = 1;
+        }
+    }
     {
-        std::vector<RpTexture> tex(s->num_textures);
+        std::vector<RpTexture> &tex = h->tex.records;
+        tex.assign(s->num_textures, RpTexture{});
         for (uint32_t t = 0; t < s->num_textures; ++t) {
             const RptrTextureDesc &td = s->textures[t];
             uchar4 *dt = nullptr;
@@ -65,8 +80,10 @@ static int scene_upload_textures(rptr_hip *h, const RptrSceneDesc *s, RpTexture 
             tex[t].height = (int)td.height;
             tex[t].srgb = td.srgb ? 1 : 0;
             tex[t].levels = (int)levels;
+            h->tex.cap_texels[t] = n;
         }
         if ((rc = dev_upload(h, &d_textures, tex.size(), tex.data(), hipMemcpyHostToDevice, &h->scene_allocs))) return rc;
+        h->tex.d_records = d_textures;
         float lut[256];
         rp_srgb_decode_lut(lut);
         if ((rc = dev_upload(h, &d_srgb_lut, 256, lut, hipMemcpyHostToDevice, &h->scene_allocs))) return rc;
@@ -1601,5 +1618,134 @@ int rptr_hip_recompute_normals(rptr_hip_t *h) {
         h->vertex_updates++;
         h->om.unrefitted = true;
     }
+    return RPTR_OK;
+}
+
+// ---- dynamic textures (include/rptr_hip.h "dynamic textures", texture_mips.h)
+void rptr_hip_srgb_decode_table(float out256[256]) {
+    if (out256) rp_srgb_decode_lut(out256);
+}
+// levels of the full chain of a w x h texture, down to 1 x 1
+static uint32_t texture_full_levels(uint32_t w, uint32_t hh) {
+    uint32_t full = 1;
+    for (; w > 1 || hh > 1; w = std::max(1u, w / 2), hh = std::max(1u, hh / 2)) ++full;
+    return full;
+}
+// texels in front of `level` in a texture's storage (the levels lie back to back); lw x lh: that level's size
+static size_t texture_level_offset(uint32_t w, uint32_t hh, uint32_t level, uint32_t *lw, uint32_t *lh) {
+    size_t at = 0;
+    for (uint32_t l = 0; l < level; ++l, w = std::max(1u, w / 2), hh = std::max(1u, hh / 2)) at += (size_t)w * hh;
+    *lw = w, *lh = hh;
+    return at;
+}
+// what every call checks first: the handle, the scene, the index
+static int texture_call_checks(const rptr_hip *ch, const char *what, uint32_t texture) {
+    rptr_hip *h = const_cast<rptr_hip *>(ch); // (fail only writes the message)
+    if (!h) return fail(nullptr, RPTR_E_INVALID, "NULL handle");
+    if (!h->have_scene) return fail(h, RPTR_E_INVALID, "%s before set_scene", what);
+    if (texture >= h->tex.records.size()) return fail(h, RPTR_E_INVALID, "%s: texture %u is not a texture of this scene (%zu textures)", what, texture, h->tex.records.size());
+    return RPTR_OK;
+}
+static int update_texture_common(rptr_hip_t *h, uint32_t texture, const uint8_t *rgba8, size_t n_bytes, uint32_t flags, bool device_src) {
+    int rc;
+    if ((rc = texture_call_checks(h, "update_texture", texture))) return rc;
+    if (flags & ~RPTR_TEXTURE_GENERATE_MIPS)
+        return fail(h, RPTR_E_INVALID, "update_texture: unknown flag bits 0x%x (RPTR_TEXTURE_GENERATE_MIPS is the only flag)", flags & ~RPTR_TEXTURE_GENERATE_MIPS);
+    const bool generate = (flags & RPTR_TEXTURE_GENERATE_MIPS) != 0;
+    RpTexture rec = h->tex.records[texture];
+    const uint32_t w = (uint32_t)rec.width, hh = (uint32_t)rec.height;
+    const size_t texels0 = (size_t)w * hh;
+    if (!rgba8 && (n_bytes != 0 || !generate))
+        return fail(h, RPTR_E_INVALID, "update_texture: texture %u: NULL texels keep level 0, which only (NULL, 0, RPTR_TEXTURE_GENERATE_MIPS) asks for", texture);
+    if (rgba8 && n_bytes != 4 * texels0)
+        return fail(h, RPTR_E_INVALID, "update_texture: texture %u is %u x %u: level 0 has %zu bytes, got %zu", texture, w, hh, 4 * texels0, n_bytes);
+    if (h->tex.emissive[texture])
+        return fail(h, RPTR_E_UNSUPPORTED, "update_texture: texture %u is read by a material with emission_intensity > 0: RptrSceneDesc.lights carry the radiance the "
+                                           "host prepared from it, and next-event estimation would disagree with what paths see", texture);
+    // ---- checked: every scene copy reads these texels, so nothing of the handle may still be rendering
+    HIP_TRY(h, hipSetDevice(h->device));
+    if ((rc = drain(h))) return rc;
+    const uint32_t full = texture_full_levels(w, hh);
+    if (generate && rec.srgb && !h->tex.d_thresholds) {
+        float lut[256], thr[256];
+        rp_srgb_decode_lut(lut);
+        rp_srgb_thresholds(lut, thr);
+        if ((rc = dev_upload(h, &h->tex.d_thresholds, 256, thr, hipMemcpyHostToDevice, &h->scene_allocs))) return rc;
+    }
+    uint32_t lw, lh;
+    const size_t need = generate ? texture_level_offset(w, hh, full, &lw, &lh) : texels0;
+    if (need > h->tex.cap_texels[texture]) { // the first call that needs more room than set_scene allocated: one allocation for the full chain
+        uchar4 *bigger = nullptr, *old = const_cast<uchar4 *>(rec.texels);
+        if ((rc = dev_alloc(h, &bigger, need, &h->scene_allocs))) return rc;
+        HIP_TRY(h, hipMemcpyAsync(bigger, old, texels0 * sizeof(uchar4), hipMemcpyDeviceToDevice, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream)); // (and whatever was queued in front of it: nothing reads the old block any more)
+        (void)hipFree(old);
+        h->scene_allocs.erase(std::remove(h->scene_allocs.begin(), h->scene_allocs.end(), (void *)old), h->scene_allocs.end());
+        h->bytes_scene -= std::min(h->bytes_scene, std::max<size_t>(h->tex.cap_texels[texture], 1) * sizeof(uchar4));
+        h->bytes_allocated = h->bytes_scene + h->bytes_frame;
+        rec.texels = bigger;
+        rec.levels = 1; // (only level 0 was carried over)
+        h->tex.cap_texels[texture] = need;
+        h->tex.records[texture] = rec;
+        hipLaunchKernelGGL(rp_k_set_texture_record, dim3(1), dim3(64), 0, h->stream, h->tex.d_records + texture, rec); // the old block is gone: at once
+        HIP_TRY(h, hipGetLastError());
+    }
+    uchar4 *level0 = const_cast<uchar4 *>(rec.texels);
+    if (rgba8) {
+        HIP_TRY(h, hipMemcpyAsync(level0, rgba8, n_bytes, device_src ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+        if (!device_src) HIP_TRY(h, hipStreamSynchronize(h->stream)); // the host array is only borrowed for the call
+    }
+    if (generate) { // level l + 1 from the quantised level l: one launch per level, in stream order
+        uchar4 *src = level0;
+        for (uint32_t l = 0, sw = w, sh = hh; l + 1 < full; ++l) {
+            uchar4 *dst = src + (size_t)sw * sh;
+            const uint32_t dw = std::max(1u, sw / 2), dh = std::max(1u, sh / 2);
+            const bool pair = (sw & 1u) == 0 && ((uintptr_t)src & 7u) == 0;
+            const dim3 grid(grid_for(h, (size_t)dw * dh));
+            if (pair)
+                hipLaunchKernelGGL(rp_k_mip_level<true>, grid, dim3(256), 0, h->stream, (const uchar4 *)src, dst, sw, sh, (uint32_t)rec.srgb, h->master.dscene.srgb_lut,
+                                   (const float *)h->tex.d_thresholds);
+            else
+                hipLaunchKernelGGL(rp_k_mip_level<false>, grid, dim3(256), 0, h->stream, (const uchar4 *)src, dst, sw, sh, (uint32_t)rec.srgb, h->master.dscene.srgb_lut,
+                                   (const float *)h->tex.d_thresholds);
+            src = dst, sw = dw, sh = dh;
+        }
+    }
+    // the record every scene copy reads, patched in place behind the texels: without the flag the texture is level 0 only, so no stale level
+    // is ever sampled. Frames submitted from here on wait for the backend's stream (follow_master_scene), query runs are queued behind it
+    // (on_callers_stream).
+    rec.levels = generate ? (int)full : 1;
+    hipLaunchKernelGGL(rp_k_set_texture_record, dim3(1), dim3(64), 0, h->stream, h->tex.d_records + texture, rec);
+    HIP_TRY(h, hipGetLastError());
+    h->tex.records[texture] = rec;
+    return RPTR_OK;
+}
+int rptr_hip_update_texture(rptr_hip_t *h, uint32_t texture, const uint8_t *rgba8, size_t n_bytes, uint32_t flags) {
+    return update_texture_common(h, texture, rgba8, n_bytes, flags, false);
+}
+int rptr_hip_update_texture_device(rptr_hip_t *h, uint32_t texture, const uint8_t *device_rgba8, size_t n_bytes, uint32_t flags) {
+    return update_texture_common(h, texture, device_rgba8, n_bytes, flags, true);
+}
+int rptr_hip_texture_levels(const rptr_hip_t *h, uint32_t texture, uint32_t *out_levels) {
+    int rc;
+    if ((rc = texture_call_checks(h, "texture_levels", texture))) return rc;
+    if (!out_levels) return fail(const_cast<rptr_hip *>(h), RPTR_E_INVALID, "NULL argument");
+    *out_levels = (uint32_t)h->tex.records[texture].levels;
+    return RPTR_OK;
+}
+// one level as the device holds it, behind whatever was queued on the backend's stream
+int rptr_hip_readback_texture(rptr_hip_t *h, uint32_t texture, uint32_t level, uint8_t *rgba8, size_t n_bytes) {
+    int rc;
+    if ((rc = texture_call_checks(h, "readback_texture", texture))) return rc;
+    const RpTexture &rec = h->tex.records[texture];
+    if (level >= (uint32_t)rec.levels) return fail(h, RPTR_E_INVALID, "readback_texture: texture %u has %d levels, level %u is not one of them", texture, rec.levels, level);
+    uint32_t lw, lh;
+    const size_t at = texture_level_offset((uint32_t)rec.width, (uint32_t)rec.height, level, &lw, &lh);
+    if (!rgba8 || n_bytes != 4 * (size_t)lw * lh)
+        return fail(h, RPTR_E_INVALID, "readback_texture: level %u of texture %u is %u x %u: %zu bytes, got %zu%s", level, texture, lw, lh, 4 * (size_t)lw * lh, n_bytes,
+                    rgba8 ? "" : " and a NULL array");
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipMemcpyAsync(rgba8, rec.texels + at, n_bytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
     return RPTR_OK;
 }

@@ -374,6 +374,15 @@ struct rptr_hip {
         float4 *d_face = nullptr;                  // scratch of rp_k_face_normals: one float4 per triangle of the largest bound geometry
         size_t cap_face = 0;
     } normals;
+    // dynamic textures (rptr_hip_update_texture / readback_texture, texture_mips.h): the host's copy of the records in dscene.textures,
+    // which the calls patch in place -- every scene copy reads that one array. set_scene fills everything but d_thresholds.
+    struct Textures {
+        RpTexture *d_records = nullptr;            // dscene.textures, writable
+        std::vector<RpTexture> records;            // ... as the device holds them (records[t].levels: the levels a sampler may read)
+        std::vector<size_t> cap_texels;            // per texture: texels its allocation has room for (set_scene: the levels it received)
+        std::vector<char> emissive;                // per texture: a material with emission_intensity > 0 reads it (updates are refused)
+        float *d_thresholds = nullptr;             // rp_srgb_thresholds, made by the first call that generates a chain
+    } tex;
 
     // device buffers (frame sized)
     std::vector<FrameCtx> ctx;      // frames in flight (RptrCreateInfo.frames_in_flight, at least 1)

@@ -23,6 +23,7 @@
 #include "skin.h"
 #include "morph.h"
 #include "normals.h"
+#include "texture_mips.h"
 #include "ploc.h"
 #include <hip/hip_ext.h>
 

@@ -99,6 +99,16 @@ public:
     void recompute_normals() {
         for (auto &r : ranks_) r->recompute_normals();
     }
+    // dynamic textures: every GPU holds the whole scene, so every rank is updated (false: refused as emissive, on every rank alike)
+    bool update_texture(uint32_t texture, const uint8_t *rgba8, size_t n_bytes, bool generate_mips = true) {
+        bool done = true;
+        for (auto &r : ranks_) done = r->update_texture(texture, rgba8, n_bytes, generate_mips) && done;
+        return done;
+    }
+    uint32_t texture_levels(uint32_t texture) const { return ranks_[0]->texture_levels(texture); } // (the ranks' textures are equal)
+    std::vector<uint8_t> readback_texture(uint32_t texture, uint32_t level, uint32_t width, uint32_t height) {
+        return ranks_[0]->readback_texture(texture, level, width, height);
+    }
     std::vector<float> readback_skinned(uint32_t geometry, uint32_t num_vertices, std::vector<uint32_t> *normal_words = nullptr) { // (the ranks' buffers are equal)
         return ranks_[0]->readback_skinned(geometry, num_vertices, normal_words);
     }

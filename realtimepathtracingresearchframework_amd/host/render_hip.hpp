@@ -171,6 +171,35 @@ public:
         check(rptr_hip_set_normal_groups(h_, geometry, groups.empty() ? nullptr : groups.data(), (uint32_t)groups.size(), flip && !groups.empty() ? RPTR_NORMALS_FLIP : 0u));
     }
     void recompute_normals() { check(rptr_hip_recompute_normals(h_)); }
+    // dynamic textures: new level-0 texels (n_bytes == 4 * width * height as set_scene received them; nullptr, 0 keeps level 0), and with
+    // generate_mips the full chain made on the device. Returns false, nothing changed, for a texture an emissive material reads
+    // (RPTR_E_UNSUPPORTED: the scene's lights were made from it); every other refusal throws. Waits for the frames in flight.
+    bool update_texture(uint32_t texture, const uint8_t *rgba8, size_t n_bytes, bool generate_mips = true) {
+        flush_pipeline();
+        const int rc = rptr_hip_update_texture(h_, texture, rgba8, n_bytes, generate_mips ? RPTR_TEXTURE_GENERATE_MIPS : 0u);
+        if (rc == RPTR_E_UNSUPPORTED) return false;
+        check(rc);
+        return true;
+    }
+    bool update_texture_device(uint32_t texture, const uint8_t *device_rgba8, size_t n_bytes, bool generate_mips = true) { // (ordered on the backend's stream)
+        flush_pipeline();
+        const int rc = rptr_hip_update_texture_device(h_, texture, device_rgba8, n_bytes, generate_mips ? RPTR_TEXTURE_GENERATE_MIPS : 0u);
+        if (rc == RPTR_E_UNSUPPORTED) return false;
+        check(rc);
+        return true;
+    }
+    uint32_t texture_levels(uint32_t texture) const {
+        uint32_t n = 0;
+        check(rptr_hip_texture_levels(h_, texture, &n));
+        return n;
+    }
+    // one level of a texture whose level 0 is width x height: max(1, width >> level) x max(1, height >> level) RGBA8 texels, row 0 first
+    std::vector<uint8_t> readback_texture(uint32_t texture, uint32_t level, uint32_t width, uint32_t height) {
+        const uint32_t w = level < 32 && (width >> level) ? width >> level : 1u, h = level < 32 && (height >> level) ? height >> level : 1u;
+        std::vector<uint8_t> out((size_t)4 * w * h);
+        check(rptr_hip_readback_texture(h_, texture, level, out.data(), out.size()));
+        return out;
+    }
     // the master copy's positions (3 floats per vertex) and, when `normal_words` is given, normal words of a bound geometry
     std::vector<float> readback_skinned(uint32_t geometry, uint32_t num_vertices, std::vector<uint32_t> *normal_words = nullptr) {
         std::vector<float> xyz((size_t)num_vertices * 3);

@@ -4,7 +4,7 @@
 //   rptr_hip <scene> --validation <prefix> [--validation-spp n] [--img w h] [--pfm] [--denoise iterations | --denoise-temporal iterations | --taa-upscale] [--auto-exposure]
 //   rptr_hip <scene.rpsc> --profiling <csv prefix> [--profiling-fps f] [--profiling-img <prefix>] [--profiling-frames n]
 //            [--animate-wave amplitude kx] [--recompute-normals] [--synchronous] [--fly-through] [--frames-in-flight n [--frames-per-launch b]]
-//   common:  [--eye x y z] [--center x y z] [--up x y z] [--fov deg] [--variant gltf|diffuse|gltf-transmission] [--batch-spp k] [--every-frame]
+//   common:  [--eye x y z] [--center x y z] [--up x y z] [--fov deg] [--variant gltf|diffuse|gltf-transmission] [--batch-spp k] [--every-frame] [--generate-mips]
 //            [--config file.ini]... [--keyframe [<seconds>:]file.ini]... [--camera n] [--freeze-frame] [--upscale n] [--backend hip]
 //            [--sky-data <dir with the Hosek-Wilkie data headers>]   (Sun settings of the .ini files refit the sky: host/sky_fit.hpp; also RPTR_SKY_DATA)
 //            [--rng-variant uniform|bn|sobol|z-sobol] [--bn-table bn_tables.h|BNData.u32] [--force-bvh-rebuild] [--rebuild-triangle-budget n]
@@ -49,6 +49,10 @@
 //    normal words are one smooth vertex) and bound with rptr_hip_set_normal_groups; rptr_hip_recompute_normals runs before every refit,
 //    so the shading normals follow the wave (or replace what the skinner wrote: morph targets without normal deltas). Without one of
 //    those flags nothing writes vertices: exit code 2 before a device is touched.
+//  * --generate-mips: after set_scene, every texture that came with level 0 only gets its full mip chain on the device
+//    (rptr_hip_update_texture(t, NULL, 0, RPTR_TEXTURE_GENERATE_MIPS): include/rptr_hip.h "dynamic textures"). One line per such texture on
+//    stdout: "generate-mips: texture t w x h -> n levels", or "generate-mips: texture t w x h skipped (emissive)" for a texture a material
+//    with emission_intensity > 0 reads (the scene's lights were made from it: the library refuses).
 //  * data-capture mode (--data-capture <prefix> [--data-capture-spp n] [--data-capture-no-rgba] [--data-capture-no-aovs]
 //    [--data-capture-albedo-roughness|-normal-depth|-motion]) stores the accumulation buffer and the chosen AOV images of every
 //    keyframe as <prefix>_%04d_{rgba,albedo_roughness,normal_depth,motion_jitter}.exr (libapp/app_state.cpp:499-531).
@@ -244,6 +248,7 @@ int main(int argc, char **argv) {
     std::string bn_table_path, dump_scene_path, sky_data;
     std::string skin_path, bones_path; // --skin / --bones: a skinned mesh 0 (rptr_hip_set_skin / update_bones / skin)
     std::string morph_path, morph_weights_path; // --morph / --morph-weights: morph targets on mesh 0 (rptr_hip_set_morph_targets / update_morph_weights)
+    bool generate_mips = false;     // --generate-mips: the full mip chain, made on the device, for every texture that has level 0 only
     bool recompute_normals = false; // --recompute-normals: rptr_hip_set_normal_groups on the written geometry, recompute_normals before every refit
     bool got_frames_per_launch = false;
     int upscale = 0, stripe_rows = 8, frames_in_flight = 0, frames_per_launch = 1; // frames_in_flight 0: the reference's loop (two swap buffers)
@@ -286,6 +291,7 @@ int main(int argc, char **argv) {
         else if (a == "--morph") { need(1); morph_path = argv[++i]; }
         else if (a == "--morph-weights") { need(1); morph_weights_path = argv[++i]; }
         else if (a == "--recompute-normals") recompute_normals = true;
+        else if (a == "--generate-mips") generate_mips = true;
         else if (a == "--denoise") { need(1); g_denoise_iterations = std::atoi(argv[++i]); if (g_denoise_iterations < 1 || g_denoise_iterations > 5) { std::fprintf(stderr, "--denoise takes 1..5 iterations\n"); return 2; } }
         else if (a == "--denoise-temporal") { need(1); g_denoise_temporal_iterations = std::atoi(argv[++i]); if (g_denoise_temporal_iterations < 1 || g_denoise_temporal_iterations > 5) { std::fprintf(stderr, "--denoise-temporal takes 1..5 iterations\n"); return 2; } }
         else if (a == "--taa-upscale") g_taa_upscale = true;
@@ -509,7 +515,7 @@ int main(int argc, char **argv) {
     if (want_help) scene_path.clear(); // prints the usage
     if (scene_path.empty() || (int)validation + (int)profiling + (int)data_capture != 1 || batch_spp < 1 || width < 1 || height < 1 || (profiling && profiling_frames < 1)) {
         std::fprintf(stderr, "usage: rptr_hip <scene.rpsc> (--validation <prefix> [--validation-spp n] | --profiling <csv prefix> [--profiling-fps f] "
-                             "[--profiling-img <prefix>] [--keyframe [len:]file.ini ...] [--profiling-count n] [--synchronous] [--fly-through] [--frames-in-flight n [--frames-per-launch b]] [--animate-wave a k [--recompute-normals]]) [--img w h] [--denoise iterations | --denoise-temporal iterations | --taa-upscale] [--auto-exposure] [--object-motion] [--eye x y z] [--center x y z] "
+                             "[--profiling-img <prefix>] [--keyframe [len:]file.ini ...] [--profiling-count n] [--synchronous] [--fly-through] [--frames-in-flight n [--frames-per-launch b]] [--animate-wave a k [--recompute-normals]]) [--img w h] [--denoise iterations | --denoise-temporal iterations | --taa-upscale] [--auto-exposure] [--object-motion] [--generate-mips] [--eye x y z] [--center x y z] "
                              "[--up x y z] [--fov deg] [--variant gltf|diffuse] [--batch-spp k] [--every-frame] [--exr|--pfm|--png] [--config file.ini ...] [--sky-data <dir of the Hosek-Wilkie data headers>]\n"
                              "       rptr_hip <scene.rpsc> --data-capture <prefix> [--data-capture-spp n] [--data-capture-no-rgba] [--data-capture-no-aovs] "
                              "[--data-capture-albedo-roughness] [--data-capture-normal-depth] [--data-capture-motion] [--keyframe ...]   (EXR images per keyframe)\n"
@@ -727,6 +733,16 @@ int main(int argc, char **argv) {
                 }
             }
         }
+        // --generate-mips: the chains of the textures that came without one, made on the device before the first frame
+        if (generate_mips)
+            for (uint32_t t = 0; t < (uint32_t)scene.textures.size(); ++t) {
+                const RptrTextureDesc &td = scene.textures[t];
+                if (td.mip_levels > 1u) continue;
+                if (backend.update_texture(t, nullptr, 0, true))
+                    std::printf("generate-mips: texture %u %u x %u -> %u levels\n", t, td.width, td.height, backend.texture_levels(t));
+                else
+                    std::printf("generate-mips: texture %u %u x %u skipped (emissive)\n", t, td.width, td.height);
+            }
         // --skin / --bones: mesh 0's first geometry is bound at its rest pose; pose(k) stages the bones of the file's frame k mod frames,
         // skins and refits (positions, shading normals and -- with registered sources -- lights follow)
         // --morph / --morph-weights: the same geometry gets its targets; pose(k) stages the weights of the file's frame k mod frames first

@@ -135,11 +135,61 @@ class SceneConfig:  # librender/render_params.glsl.h:157-162
     albedo: tuple = (0.2, 0.2, 0.2)
 
 
+def _mip_axis(f, axis):
+    """the taps of include/rptr_hip.h "dynamic textures" along one axis of a float32 image, as strided views: [(view, integer weights
+    per destination coordinate)], and the total of the weights"""
+    n = f.shape[axis]
+    m = n >> 1
+
+    def cut(first, count):
+        sl = [slice(None)] * f.ndim
+        sl[axis] = slice(first, first + 2 * count - 1, 2)
+        return f[tuple(sl)]
+    if n == 1:
+        return [(f, np.ones(1, np.int64))], 1
+    if n % 2 == 0:
+        return [(cut(0, m), np.ones(m, np.int64)), (cut(1, m), np.ones(m, np.int64))], 2
+    x = np.arange(m, dtype=np.int64)
+    return [(cut(0, m), m - x), (cut(1, m), np.full(m, m, np.int64)), (cut(2, m), x + 1)], n
+
+
+def generate_mips(rgba, srgb, table):
+    """The mip chain rptr_hip_update_texture(.., RPTR_TEXTURE_GENERATE_MIPS) makes on the device, bit for bit (include/rptr_hip.h
+    "dynamic textures" states the rule): rgba (height, width, 4) uint8, table (256,) float32 = backend.srgb_decode_table()
+    -> [level 1, ..., the 1 x 1 level]."""
+    table = np.ascontiguousarray(table, dtype=f32).reshape(256)
+    thresholds = (table[:-1] + table[1:]) * f32(0.5)                      # T[1..255]
+    cur = np.ascontiguousarray(rgba, dtype=np.uint8)
+    out = []
+    while cur.shape[0] > 1 or cur.shape[1] > 1:
+        f = cur.astype(f32)
+        if srgb:
+            f[..., :3] = table[cur[..., :3]]
+        acc = None
+        rows, toty = _mip_axis(f, 0)
+        for frow, wy in rows:                                              # row order, then column order
+            cols, totx = _mip_axis(frow, 1)
+            for tap, wx in cols:
+                term = (wy[:, None] * wx[None, :]).astype(f32)[..., None] * tap
+                acc = term if acc is None else acc + term                  # (0 + x == x)
+        mean = acc / f32(totx * toty)
+        code = np.minimum((mean + f32(0.5)).astype(np.int32), 255)
+        if srgb:
+            code[..., :3] = np.searchsorted(thresholds, mean[..., :3], side="right")  # how many T[k] <= mean
+        cur = code.astype(np.uint8)
+        out.append(cur)
+    return out
+
+
 @dataclass
 class Texture:
     rgba: np.ndarray  # (height, width, 4) uint8, row 0 first
     srgb: bool = False
     mips: Optional[list] = None  # levels 1..n-1, level l being (max(1, height >> l), max(1, width >> l), 4) uint8; None: level 0 only
+
+    def with_generated_mips(self, table):
+        """a copy whose `mips` are the full chain generate_mips makes from `rgba`"""
+        return Texture(rgba=self.rgba, srgb=self.srgb, mips=generate_mips(self.rgba, self.srgb, table) or None)
 
     def levels(self):
         """all levels, level 0 first, shapes checked"""
