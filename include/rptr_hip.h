@@ -982,6 +982,53 @@ typedef struct RptrExposureState { /* 32 + 1024 bytes */
 } RptrExposureState;
 int rptr_hip_readback_exposure_state(rptr_hip_t *h, RptrExposureState *out);
 
+/* ---- bloom: a glare pass between exposure and the display image. After exposure a light can be 10 or 10 000 times display white, and the
+ * tone map clips all of them to the same patch; glare around it is the one cue of intensity an 8-bit image has. A call takes the part of
+ * the EXPOSED linear image above `threshold` (soft knee, at most `clamp` per source texel: a firefly of 1e6 spreads no wider than an honest
+ * highlight), filters it down a pyramid of L levels (each half the size, rounded up), adds the levels back up with `scatter` per step, and
+ * writes an RGBA8 image of its own: exposed colour + gain x the upsampled pyramid, then auto-exposure's balance, tone map and sRGB. The
+ * exposure scale is auto-exposure's: exposure_mode 1 reads the `scale` the last mode-1 rptr_hip_auto_exposure call left in the device
+ * state ON THE DEVICE (call order per frame: rptr_hip_auto_exposure -> rptr_hip_bloom -> present; no host round trip), exposure_mode 0 is
+ * its manual rule. csrc/bloom.h states every operation, tests/bloom_ref.py restates it in numpy, and every pyramid level and the image
+ * equal that restatement bit for bit. INTEGRATION.md "Bloom" lists what a host can rely on.
+ * Source frame, stream and asynchrony, refusals about the finished frame, and the output_channel != 0 rule (the image is a copy of the
+ * frame's RGBA8, no pyramid is made, rptr_hip_bloom_levels gives 0) are rptr_hip_auto_exposure's. The call never touches the accumulation
+ * image, the RGBA8 frame, the AOV images, the denoisers' images and histories, the upscaler's history, the exposure state, the exposed
+ * image, frame_id / frame_offset or the statistics; a frame rendered after it is bit-identical to one rendered without it, and a host that
+ * never calls it launches what it always launched. Its buffers (4 bytes per pixel for the image, two pyramids of about 16/3 bytes per
+ * pixel each) are allocated by the first call and freed by rptr_hip_initialize / rptr_hip_destroy.
+ * With intensity 0 the image equals rptr_hip_readback_exposed_u8 of the auto-exposure call with the corresponding mode and parameters.
+ * The defaults are conventional starting values of real-time pipelines, not measurements of anything: tune them per scene.
+ * rptr_hip_readback_bloomed_u8: the image of the last call, W x H x 4 bytes. rptr_hip_bloom_levels: L of the last call.
+ * rptr_hip_readback_bloom_level_f32: level 1 .. L of the down pyramid d (which 0) or the up pyramid u (which 1) of the last call, w_l x h_l
+ * float4 texels with w = 0 (w_0 x h_0 = W x H, w_l = (w_(l-1) + 1) / 2): for tests and for tuning. All three wait for the call.
+ * RPTR_E_INVALID: NULL handle; a field outside the range its comment states, or not finite; reserved != 0; exposure_mode 1 when no mode-1
+ * rptr_hip_auto_exposure call has run since initialize; whatever rptr_hip_auto_exposure refuses about the finished frame and the
+ * denoised image; a read-back before any call since initialize, after a later frame finished, of a level outside 1 .. L, or into a
+ * buffer that is too small. RPTR_E_UNSUPPORTED: as rptr_hip_auto_exposure (option "aovs" = 0 with source 1; world_size > 1;
+ * render_upscale_factor 2). */
+#define RPTR_BLOOM_MAX_LEVELS 12
+typedef struct RptrBloomParams { /* 64 bytes */
+    int32_t source;            /* 0: the frame's accumulation image; 1: the denoiser's float image -- as RptrAutoExposureParams.source */
+    int32_t exposure_mode;     /* 0: scale = float(exp2(double(RptrRenderParams.exposure))), host-evaluated (auto-exposure's manual rule);
+                                  1: the `scale` the last mode-1 rptr_hip_auto_exposure call left in the device state, read on the device */
+    int32_t tone_mapping_mode; /* as RptrAutoExposureParams (-1) */
+    int32_t levels;            /* 0: auto (the largest L <= 8 whose level is at least 2 texels on both axes); 1 .. RPTR_BLOOM_MAX_LEVELS: asked
+                                  for, clamped to what the frame size allows */
+    float threshold;           /* >= 0, display-linear units: 1 = display white before the tone map (1.0) */
+    float knee;                /* >= 0, half-width of the soft threshold (0.5) */
+    float clamp;               /* > 0: the most one source texel may contribute, the firefly bound (16) */
+    float intensity;           /* >= 0 (0.2); 0: the image is auto-exposure's */
+    float scatter;             /* [0, 1]: how much of each coarser level reaches the next finer one (0.7) */
+    float white_balance[3];    /* as RptrAutoExposureParams (1, 1, 1) */
+    int32_t reserved[4];       /* must be 0 */
+} RptrBloomParams;
+void rptr_hip_bloom_defaults(RptrBloomParams *out);
+int rptr_hip_bloom(rptr_hip_t *h, const RptrBloomParams *p /* NULL = defaults */);
+int rptr_hip_readback_bloomed_u8(rptr_hip_t *h, unsigned char *rgba, size_t n_bytes);
+int rptr_hip_bloom_levels(const rptr_hip_t *h, uint32_t *out_levels);
+int rptr_hip_readback_bloom_level_f32(rptr_hip_t *h, int which /* 0: d, 1: u */, uint32_t level /* 1 .. L */, float *rgba, size_t n_floats);
+
 /* ---- object motion: a pass over a finished frame that rewrites the motion half of its motion + jitter AOV image where objects moved.
  * A frame projects the SAME world point through the previous and the current view (motion_vector = 0, as the reference): the AOV follows
  * the camera, not rptr_hip_update_instances / rptr_hip_update_vertices. rptr_hip_object_motion(h), called after the frame and before

@@ -299,6 +299,15 @@ class ExposureState(C.Structure):  # include/rptr_hip.h RptrExposureState
                 ("counted", C.c_uint32), ("black", C.c_uint32), ("ignored", C.c_uint32), ("calls", C.c_uint32), ("histogram", C.c_uint32 * 256)]
 
 
+class BloomParams(C.Structure):  # include/rptr_hip.h RptrBloomParams
+    _fields_ = [("source", C.c_int32), ("exposure_mode", C.c_int32), ("tone_mapping_mode", C.c_int32), ("levels", C.c_int32),
+                ("threshold", C.c_float), ("knee", C.c_float), ("clamp", C.c_float), ("intensity", C.c_float), ("scatter", C.c_float),
+                ("white_balance", C.c_float * 3), ("reserved", C.c_int32 * 4)]
+
+
+BLOOM_MAX_LEVELS = 12  # RPTR_BLOOM_MAX_LEVELS
+
+
 class OcclusionParams(C.Structure):  # include/rptr_hip.h RptrOcclusionParams
     _fields_ = [("flags", C.c_uint32), ("alpha_cutoff", C.c_float), ("reserved", C.c_uint32 * 2)]
 
@@ -322,6 +331,7 @@ assert C.sizeof(OcclusionParams) == 16
 assert C.sizeof(TaaUpscaleParams) == 16
 assert C.sizeof(AutoExposureParams) == 64
 assert C.sizeof(ExposureState) == 32 + 1024
+assert C.sizeof(BloomParams) == 64
 assert C.sizeof(LightSource) == 48
 assert C.sizeof(SkinVertex) == 16
 assert C.sizeof(MorphDelta) == 32
@@ -355,6 +365,7 @@ EXPORTED_SYMBOLS = [
     "rptr_hip_denoise_temporal_defaults", "rptr_hip_denoise_temporal", "rptr_hip_readback_denoise_history_f32",
     "rptr_hip_taa_upscale_defaults", "rptr_hip_taa_upscale", "rptr_hip_readback_upscaled_u8",
     "rptr_hip_auto_exposure_defaults", "rptr_hip_auto_exposure", "rptr_hip_readback_exposed_u8", "rptr_hip_readback_exposure_state",
+    "rptr_hip_bloom_defaults", "rptr_hip_bloom", "rptr_hip_readback_bloomed_u8", "rptr_hip_bloom_levels", "rptr_hip_readback_bloom_level_f32",
     "rptr_hip_track_object_motion", "rptr_hip_object_motion",
     "rptr_hip_tile_rows", "rptr_hip_local_pixel_count", "rptr_hip_copy_tile_to_device", "rptr_hip_trace", "rptr_hip_trace_device", "rptr_hip_enable_ray_queries", "rptr_hip_render_ray_queries", "rptr_hip_trace_radiance", "rptr_hip_trace_radiance_device", "rptr_hip_render_radiance_queries", "rptr_hip_trace_surface", "rptr_hip_trace_surface_device", "rptr_hip_occlusion_defaults", "rptr_hip_trace_occlusion", "rptr_hip_trace_occlusion_device", "rptr_hip_set_light_sampling_variant", "rptr_hip_trace_counted",
     "rptr_hip_export_bvh", "rptr_hip_build_bvh_host", "rptr_hip_stats",

@@ -134,6 +134,12 @@ def load_library(path=None):
     L.rptr_hip_auto_exposure.argtypes = [vp, C.POINTER(abi.AutoExposureParams)]
     L.rptr_hip_readback_exposed_u8.argtypes = [vp, vp, C.c_size_t]
     L.rptr_hip_readback_exposure_state.argtypes = [vp, C.POINTER(abi.ExposureState)]
+    L.rptr_hip_bloom_defaults.argtypes = [C.POINTER(abi.BloomParams)]
+    L.rptr_hip_bloom_defaults.restype = None
+    L.rptr_hip_bloom.argtypes = [vp, C.POINTER(abi.BloomParams)]
+    L.rptr_hip_readback_bloomed_u8.argtypes = [vp, vp, C.c_size_t]
+    L.rptr_hip_bloom_levels.argtypes = [vp, C.POINTER(C.c_uint32)]
+    L.rptr_hip_readback_bloom_level_f32.argtypes = [vp, C.c_int, C.c_uint32, vp, C.c_size_t]
     L.rptr_hip_track_object_motion.argtypes = [vp, i32]
     L.rptr_hip_object_motion.argtypes = [vp]
     L.rptr_hip_tile_rows.argtypes = [vp, i32, vp, i32]
@@ -550,6 +556,51 @@ class RenderHip:
         st = abi.ExposureState()
         self._check(self._L.rptr_hip_readback_exposure_state(self._h, C.byref(st)))
         return st
+
+    # ---- bloom (include/rptr_hip.h rptr_hip_bloom; csrc/bloom.h)
+    def bloom(self, params=None, **fields):
+        """Adds glare to the frame the read-backs return: what the exposed image holds above `threshold` goes down a pyramid, back up,
+        and is added in front of the tone map, into an RGBA8 image of its own; asynchronous on the backend's stream. params: an
+        abi.BloomParams, or None for the library's defaults; keyword arguments override single fields (white_balance: three gains).
+        exposure_mode = 1 uses the scale the last metering auto_exposure() left on the device (call order: auto_exposure -> bloom ->
+        present); 0 uses self.params.exposure as it is now. Returns the parameters used."""
+        p = abi.BloomParams()
+        if params is None:
+            self._L.rptr_hip_bloom_defaults(C.byref(p))
+        else:
+            C.memmove(C.byref(p), C.byref(params), C.sizeof(p))
+        for k, v in fields.items():
+            if k not in dict(abi.BloomParams._fields_) or k == "reserved":
+                raise TypeError("bloom: unknown parameter %r" % k)
+            if k == "white_balance":
+                p.white_balance[:] = [float(g) for g in v]
+            else:
+                setattr(p, k, v)
+        self._push_params()
+        self._check(self._L.rptr_hip_bloom(self._h, C.byref(p)))
+        return p
+
+    def readback_bloomed(self):
+        """the RGBA8 image of the last bloom() as an (H, W, 4) uint8 array"""
+        w, hgt, c = self.get_framebuffer_size()
+        out = np.zeros((hgt, w, c), np.uint8)
+        self._check(self._L.rptr_hip_readback_bloomed_u8(self._h, out.ctypes.data_as(C.c_void_p), out.size))
+        return out
+
+    def bloom_levels(self):
+        """L of the last bloom() (0: it copied an AOV view)"""
+        n = C.c_uint32(0)
+        self._check(self._L.rptr_hip_bloom_levels(self._h, C.byref(n)))
+        return int(n.value)
+
+    def bloom_level(self, which, level):
+        """level 1 .. L of the last bloom()'s down pyramid d (which = 0) or up pyramid u (which = 1): an (h_l, w_l, 4) float32 array"""
+        w, hgt, _ = self.get_framebuffer_size()
+        for _ in range(int(level)):
+            w, hgt = (w + 1) // 2, (hgt + 1) // 2
+        out = np.zeros((max(hgt, 1), max(w, 1), 4), np.float32)
+        self._check(self._L.rptr_hip_readback_bloom_level_f32(self._h, int(which), int(level), out.ctypes.data_as(C.c_void_p), out.size))
+        return out
 
     # ---- object motion (include/rptr_hip.h rptr_hip_object_motion; csrc/object_motion.h)
     def track_object_motion(self, enable=True):

@@ -180,6 +180,19 @@ __global__ __launch_bounds__(256) void rp_k_meter_reduce(RpMeterReduceArgs a) {
 
 RP_DEV float rp_ae_row(float m0, float m1, float m2, float x0, float x1, float x2) { return (m0 * x0 + m1 * x1) + m2 * x2; }
 
+// The display rule from the exposed colour (x, y, z) on: balance, tone map, sRGB, RGBA8 (bloom.h's composite ends with the same steps)
+RP_DEV uchar4 rp_ae_display(const RpExposeArgs &a, float x, float y, float z, float w) {
+    if (a.balance) {
+        const float l = rp_ae_row(3.90405e-1f, 5.49941e-1f, 8.92632e-3f, x, y, z) * a.gains[0];
+        const float m = rp_ae_row(7.08416e-2f, 9.63172e-1f, 1.35775e-3f, x, y, z) * a.gains[1];
+        const float s = rp_ae_row(2.31082e-2f, 1.28021e-1f, 9.36245e-1f, x, y, z) * a.gains[2];
+        x = rp_ae_row(2.85847e+0f, -1.62879e+0f, -2.48910e-2f, l, m, s);
+        y = rp_ae_row(-2.10182e-1f, 1.15820e+0f, 3.24281e-4f, l, m, s);
+        z = rp_ae_row(-4.18120e-2f, -1.18169e-1f, 1.06867e+0f, l, m, s);
+    }
+    return rp_rgba8(rp_dn_tone_map_srgb(a.tone_mapping_mode, x, y, z, w));
+}
+
 // One thread per pixel, the shape of rp_k_denoise_finish
 __global__ __launch_bounds__(256) void rp_k_expose(RpExposeArgs a) {
     const float scale = a.state ? a.state->scale : a.scale;
@@ -187,18 +200,7 @@ __global__ __launch_bounds__(256) void rp_k_expose(RpExposeArgs a) {
         const float4 c = a.src[i];
         uchar4 shown = a.fb[i];
         const float w = fminf(c.w, 1.0f);
-        if (w >= 0.0f) {
-            float x = c.x * scale, y = c.y * scale, z = c.z * scale;
-            if (a.balance) {
-                const float l = rp_ae_row(3.90405e-1f, 5.49941e-1f, 8.92632e-3f, x, y, z) * a.gains[0];
-                const float m = rp_ae_row(7.08416e-2f, 9.63172e-1f, 1.35775e-3f, x, y, z) * a.gains[1];
-                const float s = rp_ae_row(2.31082e-2f, 1.28021e-1f, 9.36245e-1f, x, y, z) * a.gains[2];
-                x = rp_ae_row(2.85847e+0f, -1.62879e+0f, -2.48910e-2f, l, m, s);
-                y = rp_ae_row(-2.10182e-1f, 1.15820e+0f, 3.24281e-4f, l, m, s);
-                z = rp_ae_row(-4.18120e-2f, -1.18169e-1f, 1.06867e+0f, l, m, s);
-            }
-            shown = rp_rgba8(rp_dn_tone_map_srgb(a.tone_mapping_mode, x, y, z, w));
-        }
+        if (w >= 0.0f) shown = rp_ae_display(a, c.x * scale, c.y * scale, c.z * scale, w);
         a.out[i] = shown;
     }
 }

@@ -544,16 +544,59 @@ void rptr_hip_auto_exposure_defaults(RptrAutoExposureParams *out) {
     out->white_balance[0] = out->white_balance[1] = out->white_balance[2] = 1.0f;
 }
 
+// What the display passes (auto-exposure, bloom) share: the checks of the fields both parameter structs have, ...
+extern "C++" {
+static int check_display_fields(rptr_hip *h, const char *who, int source, int tone_mapping_mode, const float white_balance[3]) {
+    if (source != 0 && source != 1) return fail(h, RPTR_E_INVALID, "%s: source = %d (0: the frame, 1: the denoised image)", who, source);
+    if (tone_mapping_mode < -1 || tone_mapping_mode > 2) return fail(h, RPTR_E_INVALID, "%s: tone_mapping_mode = %d is outside [-1, 2]", who, tone_mapping_mode);
+    for (int k = 0; k < 3; ++k)
+        if (!(white_balance[k] > 0.0f) || !std::isfinite(white_balance[k])) return fail(h, RPTR_E_INVALID, "%s: white_balance gains must be finite and > 0", who);
+    return RPTR_OK;
+}
+// ... what they ask of the finished frame (and of the denoised image, source 1); selects the device, ...
+static int check_display_frame(rptr_hip *h, const char *who, int source) {
+    int rc;
+    if ((rc = check_finished_frame_with_aovs(h, who, "expose", source == 1 ? "the denoised image, made from the AOV images" : nullptr, true))) return rc;
+    if (source == 1 && (rc = check_denoised(h))) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    return RPTR_OK;
+}
+// ... and the display kernel's arguments for the last finished frame, all but the scale. *copied: output_channel != 0, an AOV view -- `out`
+// has been given the frame's RGBA8 as it is (the denoiser's rule) and there is nothing to launch.
+static int display_args(rptr_hip *h, int source, int tone_mapping_mode, const float white_balance[3], uchar4 *out, RpExposeArgs &x, bool *copied) {
+    int rc;
+    const size_t npix = (size_t)h->width * (size_t)h->height;
+    const float4 *accum = nullptr;
+    const uchar4 *fb = nullptr;
+    if ((rc = last_finished_image(h, &accum, &fb))) return rc; // (world_size 1: an image is the whole frame, npix pixels)
+    *copied = h->params.output_channel != 0;
+    if (*copied) {
+        HIP_TRY(h, hipMemcpyAsync(out, fb, npix * sizeof(uchar4), hipMemcpyDeviceToDevice, h->stream));
+        return RPTR_OK;
+    }
+    memset(&x, 0, sizeof(x));
+    x.src = source == 1 ? h->dn.out_f32 : accum;
+    x.fb = fb;
+    x.out = out;
+    x.npix = npix;
+    x.tone_mapping_mode = tone_mapping_mode;
+    x.balance = (white_balance[0] != 1.0f || white_balance[1] != 1.0f || white_balance[2] != 1.0f) ? 1 : 0;
+    for (int k = 0; k < 3; ++k) x.gains[k] = white_balance[k];
+    return RPTR_OK;
+}
+static float manual_exposure_scale(const rptr_hip *h) { return (float)std::exp2((double)(h->params.exposure + 0.0f)); }
+}
+
 int rptr_hip_auto_exposure(rptr_hip_t *h, const RptrAutoExposureParams *p) {
     const char *who = "rptr_hip_auto_exposure";
     if (!h) return fail(nullptr, RPTR_E_INVALID, "NULL handle");
     RptrAutoExposureParams defaults;
     rptr_hip_auto_exposure_defaults(&defaults);
     if (!p) p = &defaults;
-    if (p->source != 0 && p->source != 1) return fail(h, RPTR_E_INVALID, "%s: source = %d (0: the frame, 1: the denoised image)", who, p->source);
+    int rc;
+    if ((rc = check_display_fields(h, who, p->source, p->tone_mapping_mode, p->white_balance))) return rc;
     if (p->mode != 0 && p->mode != 1) return fail(h, RPTR_E_INVALID, "%s: mode = %d (0: manual, 1: meter and adapt)", who, p->mode);
     if (p->reset_history != 0 && p->reset_history != 1) return fail(h, RPTR_E_INVALID, "%s: reset_history must be 0 or 1", who);
-    if (p->tone_mapping_mode < -1 || p->tone_mapping_mode > 2) return fail(h, RPTR_E_INVALID, "%s: tone_mapping_mode = %d is outside [-1, 2]", who, p->tone_mapping_mode);
     if (!(p->key > 0.0f) || !std::isfinite(p->key)) return fail(h, RPTR_E_INVALID, "%s: key must be finite and > 0 (is %g)", who, (double)p->key);
     if (!(p->low_percentile >= 0.0f && p->low_percentile < 1.0f) || !(p->high_percentile > p->low_percentile && p->high_percentile <= 1.0f))
         return fail(h, RPTR_E_INVALID, "%s: the percentiles must satisfy 0 <= low < high <= 1 (are %g, %g)", who, (double)p->low_percentile, (double)p->high_percentile);
@@ -562,13 +605,8 @@ int rptr_hip_auto_exposure(rptr_hip_t *h, const RptrAutoExposureParams *p) {
     if (!(p->speed_up >= 0.0f) || !std::isfinite(p->speed_up) || !(p->speed_down >= 0.0f) || !std::isfinite(p->speed_down))
         return fail(h, RPTR_E_INVALID, "%s: speed_up and speed_down must be finite and >= 0 (are %g, %g)", who, (double)p->speed_up, (double)p->speed_down);
     if (!(p->dt >= 0.0f) || !std::isfinite(p->dt)) return fail(h, RPTR_E_INVALID, "%s: dt must be finite and >= 0 (is %g)", who, (double)p->dt);
-    for (float g : p->white_balance)
-        if (!(g > 0.0f) || !std::isfinite(g)) return fail(h, RPTR_E_INVALID, "%s: white_balance gains must be finite and > 0", who);
     if (p->reserved) return fail(h, RPTR_E_INVALID, "%s: RptrAutoExposureParams.reserved must be 0", who);
-    int rc;
-    if ((rc = check_finished_frame_with_aovs(h, who, "expose", p->source == 1 ? "the denoised image, made from the AOV images" : nullptr, true))) return rc;
-    if (p->source == 1 && (rc = check_denoised(h))) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
+    if ((rc = check_display_frame(h, who, p->source))) return rc;
     const size_t npix = (size_t)h->width * (size_t)h->height;
     if (!h->ae.out_u8) {
         if ((rc = dev_alloc(h, &h->ae.hist, RP_AE_WORDS, nullptr)) || (rc = dev_alloc(h, &h->ae.state, 1, nullptr)) || (rc = dev_alloc(h, &h->ae.out_u8, npix, nullptr))) {
@@ -578,25 +616,15 @@ int rptr_hip_auto_exposure(rptr_hip_t *h, const RptrAutoExposureParams *p) {
         HIP_TRY(h, hipMemsetAsync(h->ae.hist, 0, RP_AE_WORDS * sizeof(uint32_t), h->stream));
         HIP_TRY(h, hipMemsetAsync(h->ae.state, 0, sizeof(RptrExposureState), h->stream));
     }
-    const float4 *accum = nullptr;
-    const uchar4 *fb = nullptr;
-    if ((rc = last_finished_image(h, &accum, &fb))) return rc; // (world_size 1: an image is the whole frame, npix pixels)
-    const RpLaunch one{dim3(1), h->stream, nullptr, nullptr};
-    const RpLaunch per_pixel{dim3((unsigned)grid_for(h, npix)), h->stream, nullptr, nullptr};
-    if (h->params.output_channel != 0) { // an AOV view: the frame's RGBA8 as it is (the denoiser's rule)
-        HIP_TRY(h, hipMemcpyAsync(h->ae.out_u8, fb, npix * sizeof(uchar4), hipMemcpyDeviceToDevice, h->stream));
+    RpExposeArgs x;
+    bool copied = false;
+    if ((rc = display_args(h, p->source, p->tone_mapping_mode, p->white_balance, h->ae.out_u8, x, &copied))) return rc;
+    if (copied) {
         h->ae.serial = h->finished_serial;
         return RPTR_OK;
     }
-    RpExposeArgs x;
-    memset(&x, 0, sizeof(x));
-    x.src = p->source == 1 ? h->dn.out_f32 : accum;
-    x.fb = fb;
-    x.out = h->ae.out_u8;
-    x.npix = npix;
-    x.tone_mapping_mode = p->tone_mapping_mode;
-    x.balance = (p->white_balance[0] != 1.0f || p->white_balance[1] != 1.0f || p->white_balance[2] != 1.0f) ? 1 : 0;
-    for (int k = 0; k < 3; ++k) x.gains[k] = p->white_balance[k];
+    const RpLaunch one{dim3(1), h->stream, nullptr, nullptr};
+    const RpLaunch per_pixel{dim3((unsigned)grid_for(h, npix)), h->stream, nullptr, nullptr};
     if (p->mode == 1) {
         RpMeterReduceArgs m;
         memset(&m, 0, sizeof(m));
@@ -620,7 +648,7 @@ int rptr_hip_auto_exposure(rptr_hip_t *h, const RptrAutoExposureParams *p) {
         h->ae.have_state = true;
         x.state = h->ae.state;
     } else
-        x.scale = (float)std::exp2((double)(h->params.exposure + 0.0f));
+        x.scale = manual_exposure_scale(h);
     rp_launch_kernel(per_pixel, rp_k_expose, 256u, x);
     HIP_TRY(h, hipGetLastError());
     h->ae.serial = h->finished_serial;
@@ -640,6 +668,115 @@ int rptr_hip_readback_exposure_state(rptr_hip_t *h, RptrExposureState *out) {
     if (!h->ae.have_state) return fail(h, RPTR_E_INVALID, "no exposure state: call rptr_hip_auto_exposure with mode 1 first");
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipMemcpyAsync(out, h->ae.state, sizeof(*out), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return RPTR_OK;
+}
+
+// ---- bloom (bloom.h): the part of the exposed image above a threshold down a pyramid, back up, and added in front of the tone map
+void rptr_hip_bloom_defaults(RptrBloomParams *out) {
+    if (!out) return;
+    memset(out, 0, sizeof(*out));
+    out->tone_mapping_mode = -1;
+    out->threshold = 1.0f;
+    out->knee = 0.5f;
+    out->clamp = 16.0f;
+    out->intensity = 0.2f;
+    out->scatter = 0.7f;
+    out->white_balance[0] = out->white_balance[1] = out->white_balance[2] = 1.0f;
+}
+
+int rptr_hip_bloom(rptr_hip_t *h, const RptrBloomParams *p) {
+    const char *who = "rptr_hip_bloom";
+    if (!h) return fail(nullptr, RPTR_E_INVALID, "NULL handle");
+    RptrBloomParams defaults;
+    rptr_hip_bloom_defaults(&defaults);
+    if (!p) p = &defaults;
+    int rc;
+    if ((rc = check_display_fields(h, who, p->source, p->tone_mapping_mode, p->white_balance))) return rc;
+    if (p->exposure_mode != 0 && p->exposure_mode != 1) return fail(h, RPTR_E_INVALID, "%s: exposure_mode = %d (0: manual, 1: the metered state)", who, p->exposure_mode);
+    if (p->levels < 0 || p->levels > RPTR_BLOOM_MAX_LEVELS) return fail(h, RPTR_E_INVALID, "%s: levels = %d is outside [0, %d]", who, p->levels, RPTR_BLOOM_MAX_LEVELS);
+    if (!(p->threshold >= 0.0f) || !std::isfinite(p->threshold) || !(p->knee >= 0.0f) || !std::isfinite(p->knee))
+        return fail(h, RPTR_E_INVALID, "%s: threshold and knee must be finite and >= 0 (are %g, %g)", who, (double)p->threshold, (double)p->knee);
+    if (!(p->clamp > 0.0f) || !std::isfinite(p->clamp)) return fail(h, RPTR_E_INVALID, "%s: clamp must be finite and > 0 (is %g)", who, (double)p->clamp);
+    if (!(p->intensity >= 0.0f) || !std::isfinite(p->intensity)) return fail(h, RPTR_E_INVALID, "%s: intensity must be finite and >= 0 (is %g)", who, (double)p->intensity);
+    if (!(p->scatter >= 0.0f && p->scatter <= 1.0f)) return fail(h, RPTR_E_INVALID, "%s: scatter = %g is outside [0, 1]", who, (double)p->scatter);
+    for (int r : p->reserved)
+        if (r) return fail(h, RPTR_E_INVALID, "%s: RptrBloomParams.reserved must be 0", who);
+    if (p->exposure_mode == 1 && !h->ae.have_state)
+        return fail(h, RPTR_E_INVALID, "%s: exposure_mode 1 reads the exposure state: call rptr_hip_auto_exposure with mode 1 first", who);
+    if ((rc = check_display_frame(h, who, p->source))) return rc;
+    const size_t npix = (size_t)h->width * (size_t)h->height;
+    if (!h->bl.out_u8) {
+        const RpBloomPyramid all = rp_bloom_pyramid((uint32_t)h->width, (uint32_t)h->height, RP_BLOOM_MAX_LEVELS);
+        const size_t texels = all.off[all.L + 1];
+        if ((rc = dev_alloc(h, &h->bl.d, texels, nullptr)) || (rc = dev_alloc(h, &h->bl.u, texels, nullptr)) || (rc = dev_alloc(h, &h->bl.out_u8, npix, nullptr))) {
+            h->bl = decltype(h->bl)(); // (what was allocated stays on the handle's list and is freed with it)
+            return rc;
+        }
+    }
+    RpBloomRun r;
+    memset(&r, 0, sizeof(r));
+    bool copied = false;
+    if ((rc = display_args(h, p->source, p->tone_mapping_mode, p->white_balance, h->bl.out_u8, r.comp.x, &copied))) return rc;
+    h->bl.levels = 0;
+    h->bl.asked = p->levels;
+    if (!copied) {
+        const bool metered = p->exposure_mode == 1;
+        const float scale = metered ? 0.0f : manual_exposure_scale(h);
+        r.pyr = rp_bloom_pyramid((uint32_t)h->width, (uint32_t)h->height, p->levels);
+        r.pf = rp_bloom_prefilter_args(metered ? h->ae.state : nullptr, scale, p->threshold, p->knee, p->clamp);
+        r.comp.x.state = metered ? h->ae.state : nullptr;
+        r.comp.x.scale = scale;
+        r.comp.W = h->width;
+        r.comp.H = h->height;
+        r.comp.gain = rp_bloom_gain(p->intensity, p->scatter, r.pyr.L);
+        r.comp.add = p->intensity != 0.0f ? 1 : 0;
+        r.d = h->bl.d;
+        r.u = h->bl.u;
+        r.scatter = p->scatter;
+        r.max_blocks = (unsigned)h->num_cus * 8u;
+        r.stages = 7;
+        rp_bloom_enqueue<RP_BLOOM_SHIP_TILE != 0, RP_BLOOM_SHIP_TAIL != 0>(r, h->stream); // (which forms, and why: profiles/bloom_notes.md)
+        HIP_TRY(h, hipGetLastError());
+        h->bl.levels = r.pyr.L;
+    }
+    h->bl.serial = h->finished_serial;
+    return RPTR_OK;
+}
+
+extern "C++" {
+static int check_bloomed(rptr_hip *h) {
+    if (!h->bl.out_u8 || h->bl.serial == 0) return fail(h, RPTR_E_INVALID, "no bloomed image: call rptr_hip_bloom first");
+    if (h->bl.serial != h->finished_serial)
+        return fail(h, RPTR_E_INVALID, "the bloomed image is stale: a later frame has finished since rptr_hip_bloom ran; call it again for that frame");
+    return RPTR_OK;
+}
+}
+int rptr_hip_readback_bloomed_u8(rptr_hip_t *h, unsigned char *rgba, size_t n_bytes) {
+    if (!h || !rgba) return fail(h, RPTR_E_INVALID, "NULL argument");
+    const int rc = check_bloomed(h);
+    return rc ? rc : readback_rows<uchar4>(h, h->bl.out_u8, reinterpret_cast<uchar4 *>(rgba), n_bytes / 4);
+}
+
+int rptr_hip_bloom_levels(const rptr_hip_t *h, uint32_t *out_levels) {
+    if (!h || !out_levels) return fail(nullptr, RPTR_E_INVALID, "NULL argument");
+    if (!h->bl.out_u8 || h->bl.serial == 0) return fail(nullptr, RPTR_E_INVALID, "no bloomed image: call rptr_hip_bloom first");
+    *out_levels = (uint32_t)h->bl.levels;
+    return RPTR_OK;
+}
+
+int rptr_hip_readback_bloom_level_f32(rptr_hip_t *h, int which, uint32_t level, float *rgba, size_t n_floats) {
+    if (!h || !rgba) return fail(h, RPTR_E_INVALID, "NULL argument");
+    int rc;
+    if ((rc = check_bloomed(h))) return rc;
+    if (which != 0 && which != 1) return fail(h, RPTR_E_INVALID, "rptr_hip_readback_bloom_level_f32: which = %d (0: the down pyramid d, 1: the up pyramid u)", which);
+    if (level < 1 || level > (uint32_t)h->bl.levels)
+        return fail(h, RPTR_E_INVALID, "rptr_hip_readback_bloom_level_f32: level %u is outside 1 .. %d, the levels of the last call", level, h->bl.levels);
+    const RpBloomPyramid pyr = rp_bloom_pyramid((uint32_t)h->width, (uint32_t)h->height, h->bl.asked);
+    const size_t texels = (size_t)pyr.w[level] * pyr.h[level];
+    if (n_floats / 4 < texels) return fail(h, RPTR_E_INVALID, "read-back buffer too small for level %u: %zu < %zu floats", level, n_floats, 4 * texels);
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipMemcpyAsync(rgba, (which ? h->bl.u : h->bl.d) + pyr.off[level], texels * sizeof(float4), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return RPTR_OK;
 }

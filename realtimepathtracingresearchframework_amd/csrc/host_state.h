@@ -459,7 +459,16 @@ struct rptr_hip {
         uint64_t serial = 0;                // finished_serial of the frame the image was made from (0: none)
         bool have_state = false;            // a mode-1 call has run since initialize: `state` holds an ev
     } ae;
-    uint64_t finished_serial = 0;          // frames waited for since initialize: the read-backs' frame changes with each
+    // bloom (bloom.h, rptr_hip_bloom): the two pyramids (levels 1 .. min(L_max, 12) of the frame size, back to back) and the bloomed RGBA8
+    // image, made by the first call and freed with the other frame-sized buffers
+    struct Bloom {
+        float4 *d = nullptr, *u = nullptr;
+        uchar4 *out_u8 = nullptr;
+        uint64_t serial = 0;                // finished_serial of the frame the image was made from (0: none)
+        int levels = 0;                     // L of the last call (0: it copied an AOV view)
+        int asked = 0;                      // ... and the RptrBloomParams.levels that gave it
+    } bl;
+    uint64_t finished_serial = 0;         // frames waited for since initialize: the read-backs' frame changes with each
     // object motion (object_motion.h, rptr_hip_track_object_motion / rptr_hip_object_motion): the state the PREVIOUS frame saw, kept while
     // tracking is on. The first update_instances* / update_vertices* after a submission copies the staged transform table into
     // prev_inst_xf and clears the changed marks; the first update_vertices* of a geometry in that interval copies its positions into

@@ -14,6 +14,7 @@
 #include "denoise.h"
 #include "denoise_temporal.h"
 #include "auto_exposure.h"
+#include "bloom.h"
 #include "surface_query.h"
 #include "occlusion_query.h"
 #include "object_motion.h"
@@ -318,6 +319,7 @@ int rptr_hip_initialize(rptr_hip_t *h, int fb_width, int fb_height) {
     h->dt = decltype(h->dt)(); // (the temporal denoiser's history: allocated by the first rptr_hip_denoise_temporal, freed with the rest above)
     h->up = decltype(h->up)(); // (the upscaler's images: allocated by the first rptr_hip_taa_upscale, freed with the rest above)
     h->ae = decltype(h->ae)(); // (auto-exposure's buffers and state: allocated by the first rptr_hip_auto_exposure, freed with the rest above)
+    h->bl = decltype(h->bl)(); // (bloom's pyramids and image: allocated by the first rptr_hip_bloom, freed with the rest above)
     h->finished_serial = 0;
     h->om.submissions = 0; // (object motion: no frame of the new size has been submitted; the tracking itself belongs to the scene and stays)
     h->om.snapshot = h->om.counted = h->om.dirty[0] = h->om.dirty[1] = false;

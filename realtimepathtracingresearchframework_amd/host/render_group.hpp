@@ -297,6 +297,9 @@ public:
     size_t readback_exposed(size_t buffer_size, unsigned char *buffer) { return ranks_[0]->readback_exposed(buffer_size, buffer); }
     RptrExposureState readback_exposure_state(bool newest = true) { return ranks_[0]->readback_exposure_state(newest); }
     bool exposure_state_ready() const { return ranks_[0]->exposure_state_ready(); }
+    // bloom works on one GPU's whole frame as well (rptr_hip_bloom refuses world_size > 1)
+    void bloom(const RptrBloomParams &p) { ranks_[0]->bloom(p); }
+    size_t readback_bloomed(size_t buffer_size, unsigned char *buffer) { return ranks_[0]->readback_bloomed(buffer_size, buffer); }
     // temporal 2x upscaling works on one GPU's whole frame as well (rptr_hip_taa_upscale refuses world_size > 1)
     void taa_upscale(const RptrTaaUpscaleParams &p) { ranks_[0]->taa_upscale(p); }
     void taa_upscale(bool reset_history) {

@@ -18,6 +18,7 @@ namespace rptr {
 static_assert(sizeof(RptrOcclusionParams) == 16, "RptrOcclusionParams: flags, alpha_cutoff, two reserved words (include/rptr_hip.h)");
 static_assert(sizeof(RptrDenoiseTemporalParams) == 64, "RptrDenoiseTemporalParams: ten parameters and six reserved words (include/rptr_hip.h)");
 static_assert(sizeof(RptrTaaUpscaleParams) == 16, "RptrTaaUpscaleParams: factor, reset_history, two reserved words (include/rptr_hip.h)");
+static_assert(sizeof(RptrBloomParams) == 64, "RptrBloomParams: four switches, five parameters, three gains, four reserved words (include/rptr_hip.h)");
 static_assert(sizeof(RptrSurfaceHit) == 96, "RptrSurfaceHit: six 16-byte rows per surface query (include/rptr_hip.h)");
 
 struct RenderStats { // librender/render_backend.h:15-24
@@ -485,6 +486,33 @@ public:
         return st;
     }
     bool exposure_state_ready() const { return exposure_calls_ > 0; }
+    // Bloom (include/rptr_hip.h rptr_hip_bloom): glare for the frame the read-backs return -- everything in flight is finished first -- or
+    // its denoised image (p.source = 1), into an RGBA8 image of its own; nothing else is touched. Asynchronous on the backend's stream.
+    // p.exposure_mode = 1 uses the scale the last metering auto_exposure() left on the device (call order: auto_exposure, bloom, present);
+    // 0 uses `params.exposure` as it is now.
+    static RptrBloomParams bloom_defaults() {
+        RptrBloomParams p;
+        rptr_hip_bloom_defaults(&p);
+        return p;
+    }
+    void bloom(const RptrBloomParams &p) {
+        flush_pipeline();
+        push_state();
+        check(rptr_hip_bloom(h_, &p));
+    }
+    size_t readback_bloomed(size_t buffer_size, unsigned char *buffer) { // sRGB RGBA8
+        uint32_t whc[3];
+        get_framebuffer_size(whc);
+        const size_t need = size_t(whc[0]) * whc[1] * 4;
+        if (buffer_size < need) return 0;
+        check(rptr_hip_readback_bloomed_u8(h_, buffer, buffer_size));
+        return need;
+    }
+    uint32_t bloom_levels() {
+        uint32_t n = 0;
+        check(rptr_hip_bloom_levels(h_, &n));
+        return n;
+    }
     // Object motion (include/rptr_hip.h rptr_hip_object_motion): track_object_motion after set_scene; object_motion after the frame that
     // followed update_* + refit and before denoise_temporal / taa_upscale -- everything in flight is finished first. Returns the pixels
     // whose motion vector was rewritten (waits for the pass).

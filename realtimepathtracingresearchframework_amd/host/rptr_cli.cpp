@@ -1,7 +1,7 @@
 // rptr_cli.cpp -- the reference's headless run modes through the C ABI (binary: bin/rptr_hip):
 //
 //   <scene> = the reference's .vks file (textures in <name>_textures/) or the flat dump scenes.py writes (.rpsc)
-//   rptr_hip <scene> --validation <prefix> [--validation-spp n] [--img w h] [--pfm] [--denoise iterations | --denoise-temporal iterations | --taa-upscale] [--auto-exposure]
+//   rptr_hip <scene> --validation <prefix> [--validation-spp n] [--img w h] [--pfm] [--denoise iterations | --denoise-temporal iterations | --taa-upscale] [--auto-exposure] [--bloom intensity]
 //   rptr_hip <scene.rpsc> --profiling <csv prefix> [--profiling-fps f] [--profiling-img <prefix>] [--profiling-frames n]
 //            [--animate-wave amplitude kx] [--recompute-normals] [--synchronous] [--fly-through] [--frames-in-flight n [--frames-per-launch b]]
 //   common:  [--eye x y z] [--center x y z] [--up x y z] [--fov deg] [--variant gltf|diffuse|gltf-transmission] [--batch-spp k] [--every-frame] [--generate-mips]
@@ -130,6 +130,19 @@ static void auto_exposure(rptr::RenderGroup &backend, bool reset_history, float 
     backend.auto_exposure(p);
     print_exposure(backend.readback_exposure_state(), frame);
 }
+// --bloom <intensity> (this host's): every RGBA8 image written (--png) goes through rptr_hip_bloom with the library's defaults and that
+// intensity, behind --denoise / --denoise-temporal (source 1) and --auto-exposure, whose metered scale it then reads on the device
+// (exposure_mode 1) and whose white balance it shares; without --auto-exposure the configuration's exposure counts (exposure_mode 0). The
+// tone mapping operator is the configuration's. Not with --taa-upscale or several devices.
+static bool g_bloom = false;
+static RptrBloomParams g_bloom_params;
+static float g_bloom_intensity = 0.f;
+static const char *bloom_refusal(size_t n_devices) {
+    if (!g_bloom) return nullptr;
+    if (g_taa_upscale) return "--bloom and --taa-upscale cannot be combined: bloom works on the frame at render resolution\n";
+    if (n_devices > 1) return "--bloom needs one device (rptr_hip_bloom refuses world_size > 1)\n";
+    return nullptr;
+}
 static void save_image(rptr::RenderGroup &backend, OutputFormat format, const std::string &prefix, int number, const std::string &suffix, int width, int height,
                        std::vector<float> &img, bool expose_now = false) {
     char name[32];
@@ -145,7 +158,12 @@ static void save_image(rptr::RenderGroup &backend, OutputFormat format, const st
     // (expose_now: a validation run's still image, metered as it is written -- no adaptation; with --denoise the denoised image exists
     // only from here on, so the frame loops leave the call to this function as well)
     if (g_auto_exposure && (expose_now || g_denoise_iterations > 0)) auto_exposure(backend, true, 0.f, number);
-    if (format == FORMAT_PNG && g_auto_exposure) {
+    if (format == FORMAT_PNG && g_bloom) { // (behind the exposure call above, or the frame loop's: the state it reads is that frame's)
+        std::vector<unsigned char> rgba8((size_t)width * height * 4);
+        backend.bloom(g_bloom_params);
+        if (backend.readback_bloomed(rgba8.size(), rgba8.data()) != rgba8.size()) throw std::runtime_error("read-back failed");
+        ok = rptr::write_png(base, (unsigned)width, (unsigned)height, 4, rgba8.data());
+    } else if (format == FORMAT_PNG && g_auto_exposure) {
         std::vector<unsigned char> rgba8((size_t)width * height * 4);
         if (backend.readback_exposed(rgba8.size(), rgba8.data()) != rgba8.size()) throw std::runtime_error("read-back failed");
         ok = rptr::write_png(base, (unsigned)width, (unsigned)height, 4, rgba8.data());
@@ -296,6 +314,7 @@ int main(int argc, char **argv) {
         else if (a == "--denoise-temporal") { need(1); g_denoise_temporal_iterations = std::atoi(argv[++i]); if (g_denoise_temporal_iterations < 1 || g_denoise_temporal_iterations > 5) { std::fprintf(stderr, "--denoise-temporal takes 1..5 iterations\n"); return 2; } }
         else if (a == "--taa-upscale") g_taa_upscale = true;
         else if (a == "--auto-exposure") g_auto_exposure = true;
+        else if (a == "--bloom") { need(1); g_bloom = true; g_bloom_intensity = (float)std::atof(argv[++i]); if (!(g_bloom_intensity >= 0.f) || !std::isfinite(g_bloom_intensity)) { std::fprintf(stderr, "--bloom takes an intensity >= 0\n"); return 2; } }
         else if (a == "--object-motion") g_object_motion = true;
         else if (a == "--img") { need(2); width = std::atoi(argv[++i]); height = std::atoi(argv[++i]); }
         else if (a == "--eye") { vec3(eye); got_eye = true; }
@@ -467,6 +486,10 @@ int main(int argc, char **argv) {
         std::fputs(why, stderr);
         return 2;
     }
+    if (const char *why = bloom_refusal(devices.size())) {
+        std::fputs(why, stderr);
+        return 2;
+    }
     if (g_object_motion) {
         const size_t n = scene_path.size();
         const char *why = nullptr;
@@ -515,7 +538,7 @@ int main(int argc, char **argv) {
     if (want_help) scene_path.clear(); // prints the usage
     if (scene_path.empty() || (int)validation + (int)profiling + (int)data_capture != 1 || batch_spp < 1 || width < 1 || height < 1 || (profiling && profiling_frames < 1)) {
         std::fprintf(stderr, "usage: rptr_hip <scene.rpsc> (--validation <prefix> [--validation-spp n] | --profiling <csv prefix> [--profiling-fps f] "
-                             "[--profiling-img <prefix>] [--keyframe [len:]file.ini ...] [--profiling-count n] [--synchronous] [--fly-through] [--frames-in-flight n [--frames-per-launch b]] [--animate-wave a k [--recompute-normals]]) [--img w h] [--denoise iterations | --denoise-temporal iterations | --taa-upscale] [--auto-exposure] [--object-motion] [--generate-mips] [--eye x y z] [--center x y z] "
+                             "[--profiling-img <prefix>] [--keyframe [len:]file.ini ...] [--profiling-count n] [--synchronous] [--fly-through] [--frames-in-flight n [--frames-per-launch b]] [--animate-wave a k [--recompute-normals]]) [--img w h] [--denoise iterations | --denoise-temporal iterations | --taa-upscale] [--auto-exposure] [--bloom intensity] [--object-motion] [--generate-mips] [--eye x y z] [--center x y z] "
                              "[--up x y z] [--fov deg] [--variant gltf|diffuse] [--batch-spp k] [--every-frame] [--exr|--pfm|--png] [--config file.ini ...] [--sky-data <dir of the Hosek-Wilkie data headers>]\n"
                              "       rptr_hip <scene.rpsc> --data-capture <prefix> [--data-capture-spp n] [--data-capture-no-rgba] [--data-capture-no-aovs] "
                              "[--data-capture-albedo-roughness] [--data-capture-normal-depth] [--data-capture-motion] [--keyframe ...]   (EXR images per keyframe)\n"
@@ -596,6 +619,12 @@ int main(int argc, char **argv) {
         if (!std::isnan(base.exposure_key)) g_auto_exposure_params.key = base.exposure_key;
         for (int k = 0; k < 3; ++k)
             if (!std::isnan(base.white_balance[k])) g_auto_exposure_params.white_balance[k] = base.white_balance[k];
+        g_bloom_params = rptr::RenderHip::bloom_defaults();
+        g_bloom_params.source = g_auto_exposure_params.source;
+        g_bloom_params.exposure_mode = g_auto_exposure ? 1 : 0;
+        g_bloom_params.tone_mapping_mode = g_auto_exposure_params.tone_mapping_mode;
+        g_bloom_params.intensity = g_bloom_intensity;
+        for (int k = 0; k < 3; ++k) g_bloom_params.white_balance[k] = g_auto_exposure_params.white_balance[k];
         const bool expose_frames = g_auto_exposure && g_denoise_iterations == 0; // (--denoise runs when an image is written: save_image exposes there)
         // --skin <file>: raw RptrSkinVertex records of geometry first_geometry of mesh 0; --bones <file>: two uint32 (frames, bones), then
         // frames x bones x 12 float32. Both are checked against the scene before a device is touched.
