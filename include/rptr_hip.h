@@ -1259,6 +1259,85 @@ int rptr_hip_trace_occlusion(rptr_hip_t *h, const RptrRenderRayQuery *queries, i
                              uint32_t *out_bits);
 int rptr_hip_trace_occlusion_device(rptr_hip_t *h, const RptrRenderRayQuery *device_queries /* NULL: the buffer of rptr_hip_enable_ray_queries */,
                                     int n, const RptrOcclusionParams *params, uint32_t *device_out_bits, void *hip_stream);
+/* ---- irradiance probes: positions in, second-order spherical-harmonics coefficients of the incident radiance out
+ * The step from rays to a probe (a DDGI-style grid, a light-probe baker, irradiance for particles and volumetrics): a ray-generation
+ * kernel, a radiance-query run and a projection kernel, with nothing but 144 bytes per probe leaving the device. No reference counterpart.
+ * The arithmetic is binary32, every product and sum rounded on its own (no contraction), IEEE division; tests/probes_ref.py restates it.
+ *   Directions  rptr_hip_probe_directions(K, out): the spherical Fibonacci set, on the host in double, each component rounded to float
+ *               once: g = (sqrt 5 - 1) / 2, z = 1 - (2k + 1) / K, phi = 2 pi frac(k g), r = sqrt(max(0, 1 - z z)), d_k = (r cos phi,
+ *               r sin phi, z). The device evaluates no transcendental function: the table is uploaded once per K and kept in the handle.
+ *   Rays        ray q = p K + k of a run: origin = the probe's position, dir[r] = (R[r][0] x + R[r][1] y) + R[r][2] z of d_k = (x, y, z)
+ *               with R = `rotation` (row-major), NOT renormalised (queries use dir as given), t_max from the params, mode_or_data = 0.
+ *               A probe with a coordinate that is not finite is skipped: its K records get mode_or_data = -1 (origin, dir and t_max are
+ *               written as for any probe), its 36 coefficients keep every byte, nothing is traced or counted for it.
+ *   Runs        the probes are processed in runs of max(1, floor(R / K)) whole probes, R = max_run_rays or 1 << 22; ray p_local K + k is
+ *               query q of the run's radiance queries (rptr_hip_trace_radiance rule 1), so a probe's random numbers depend on its index
+ *               within its run, and a call over exactly the probes of one run gives that run's bits.
+ *   Samples     the run's samples have random-number indices sample_index ... sample_index + samples_per_ray - 1, and frame_id
+ *               likewise, as radiance queries pin it; the fold counts from 0: a ray's value is the running mean (rule 2) of THIS run's
+ *               samples alone, whatever sample_index is -- a fresh estimate per call, as per-frame rotated ray sets need.
+ *   Values      a ray whose float4 has a component that is not finite contributes (0, 0, 0, 0). clamp > 0 and m = max(r, g, b) > clamp:
+ *               rgb = rgb (clamp / m); alpha is never scaled.
+ *   Basis       from the rotated float direction (x, y, z), in this order: Y0 = 0.282095f, Y1 = 0.488603f y, Y2 = 0.488603f z,
+ *               Y3 = 0.488603f x, Y4 = 1.092548f (x y), Y5 = 1.092548f (y z), Y6 = 0.315392f (3 (z z) - 1), Y7 = 1.092548f (x z),
+ *               Y8 = 0.546274f (x x - y y).
+ *   Sum         one 64-lane wavefront per probe: lane l starts from +0 and takes k = l, l + 64, ... in ascending order, per step
+ *               acc[i][ch] = acc[i][ch] + v[ch] Y_i; then acc = acc + xor-shuffle(acc, off) for off = 32, 16, 8, 4, 2, 1 (IEEE addition
+ *               commutes: every lane ends with the same bits); c_new = acc w, w = float(4 pi / K) from double.
+ *   Blend       blend == 1: a plain store (garbage or NaN in the buffer never survives); otherwise c = c + (c_new - c) blend.
+ *   Layout      coeffs[p][i][ch]: 36 floats, 144 bytes per probe, channels r, g, b, alpha. Alpha is 1 where the first ray hit a surface, so
+ *               its coefficients are the SH visibility of geometry against the sky.
+ * rptr_hip_probe_defaults: K 128, one sample per ray, sample_index 0, identity rotation, blend 1, clamp 0, t_max 1e20, everything else 0.
+ * rptr_hip_probe_directions: host only, no handle; K outside 1 .. RPTR_PROBE_MAX_RAYS or out3K == NULL: RPTR_E_INVALID.
+ * The two stages are public on purpose, on DEVICE buffers, asynchronously on `hip_stream` (NULL: the backend's stream; a caller's stream
+ * is ordered as for rptr_hip_trace_device). They need a handle and neither a scene nor a frame size, wait for nothing and touch nothing
+ * a frame owns:
+ *   rptr_hip_probe_rays_device     n_probes K records of 32 bytes (n_probes K < 2^31), for any query kind: closest hits for DDGI
+ *                                  visibility, occlusion for AO.
+ *   rptr_hip_probe_project_device  any n_probes K float4 -> coefficients. It reads 16 bytes per ray and recomputes the directions from
+ *                                  the table, not the records. device_positions3 exists only so that the stage skips the probes the ray
+ *                                  stage skipped; NULL: none is skipped.
+ * rptr_hip_trace_probes: host arrays, synchronous; coeffs36 is read as well as written (skipped probes, blend < 1); out_stats (may be NULL)
+ * gets rays_closest / rays_shadow / hits_shaded of the call, spp = samples_per_ray, times 0.
+ * rptr_hip_trace_probes_device: DEVICE buffers, asynchronously on `hip_stream`, ordered as rptr_hip_trace_device.
+ * Both are rays -> radiance run -> projection per run, in scratch the handle owns: 48 bytes per ray of a run (record + value), grown to
+ * the largest run seen and freed by rptr_hip_destroy; a host that never calls them allocates nothing. `camera` and `variant` mean what
+ * they mean for radiance queries (the camera only supplies the texture-footprint axes). Ordering and isolation are those of
+ * rptr_hip_trace_radiance: the frames in flight are waited for; the accumulation, frame and AOV images, frame_id / frame_offset, the
+ * histories, the denoised images and rptr_hip_stats are left alone; the scene copy is the one rptr_hip_trace traces. world_size > 1:
+ * RPTR_E_UNSUPPORTED.
+ * rptr_hip_readback_probe_rays (diagnostic, synchronous): the first n_rays ray values of the LAST run of the last rptr_hip_trace_probes
+ * [_device], as the radiance run left them (before the sanitising and the clamp); the rays of a skipped probe read 0. More than that
+ * run had, or no run yet: RPTR_E_INVALID.
+ * RPTR_E_INVALID, checked before the device is touched, with a message that names the offender: NULL handle; NULL position or coefficient
+ * (record, value) buffer with n_probes > 0; a whole call before set_scene / initialize; rays_per_probe outside 1 .. RPTR_PROBE_MAX_RAYS;
+ * samples_per_ray < 1; sample_index < 0 or sample_index + samples_per_ray > INT32_MAX; flags or reserved != 0; blend outside (0, 1] or
+ * not finite; clamp negative or not finite; t_max not > 0; a rotation that is not finite or whose R R^T (in double) differs from the
+ * identity by more than 1e-3 in any entry. params NULL = the defaults. n_probes == 0 succeeds and touches nothing. */
+#define RPTR_PROBE_MAX_RAYS 4096u
+typedef struct RptrProbeParams { /* 80 bytes */
+    uint32_t rays_per_probe;  /* K, 1 .. RPTR_PROBE_MAX_RAYS; default 128 */
+    uint32_t samples_per_ray; /* m >= 1; default 1 */
+    int32_t sample_index;     /* >= 0: random-number sample index of the run's first sample; default 0 */
+    uint32_t flags;           /* must be 0 */
+    float rotation[9];        /* row-major 3x3 applied to the direction set; default identity */
+    float blend;              /* weight of the new coefficients, (0, 1]; default 1 = replace */
+    float clamp;              /* 0 = none; > 0, finite: a ray's rgb is scaled so that its largest component is <= clamp */
+    float t_max;              /* > 0; default 1e20f */
+    uint32_t max_run_rays;    /* 0 = 1 << 22 */
+    uint32_t reserved[3];     /* must be 0 */
+} RptrProbeParams;
+void rptr_hip_probe_defaults(RptrProbeParams *out);
+int rptr_hip_probe_directions(uint32_t K, float *out3K);
+int rptr_hip_probe_rays_device(rptr_hip_t *h, const float *device_positions3, uint32_t n_probes, const RptrProbeParams *params /* NULL = defaults */,
+                               RptrRenderRayQuery *device_queries, void *hip_stream);
+int rptr_hip_probe_project_device(rptr_hip_t *h, const float *device_values4, uint32_t n_probes, const float *device_positions3 /* may be NULL */,
+                                  const RptrProbeParams *params, float *device_coeffs36, void *hip_stream);
+int rptr_hip_trace_probes(rptr_hip_t *h, const float *positions3, uint32_t n_probes, const RptrCamera *camera, int variant,
+                          const RptrProbeParams *params, float *coeffs36, RptrStats *out_stats);
+int rptr_hip_trace_probes_device(rptr_hip_t *h, const float *device_positions3, uint32_t n_probes, const RptrCamera *camera, int variant,
+                                 const RptrProbeParams *params, float *device_coeffs36, void *hip_stream);
+int rptr_hip_readback_probe_rays(rptr_hip_t *h, float *out4, size_t n_rays);
 /* RenderBackendOptions::light_sampling_variant (rendering/mc/light_sampling.h:11-20, rendering/mc/nee.glsl:12-14): 0 =
  * LIGHT_SAMPLING_VARIANT_NONE disables next-event estimation towards the emissive triangles (every NEE sample goes to the sun; emitters
  * that a path HITS still contribute, at full weight), 1 = LIGHT_SAMPLING_VARIANT_RIS (the default: binned RIS). The image is that of

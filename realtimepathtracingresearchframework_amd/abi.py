@@ -315,6 +315,15 @@ class OcclusionParams(C.Structure):  # include/rptr_hip.h RptrOcclusionParams
 OCCLUSION_ALPHA_CUTOUT = 1  # RPTR_OCCLUSION_ALPHA_CUTOUT
 
 
+class ProbeParams(C.Structure):  # include/rptr_hip.h RptrProbeParams
+    _fields_ = [("rays_per_probe", C.c_uint32), ("samples_per_ray", C.c_uint32), ("sample_index", C.c_int32), ("flags", C.c_uint32),
+                ("rotation", C.c_float * 9), ("blend", C.c_float), ("clamp", C.c_float), ("t_max", C.c_float), ("max_run_rays", C.c_uint32),
+                ("reserved", C.c_uint32 * 3)]
+
+
+PROBE_MAX_RAYS = 4096  # RPTR_PROBE_MAX_RAYS
+
+
 def _surface_hit_dtype():
     import numpy as np
     kinds = {C.c_float: np.float32, C.c_int32: np.int32}
@@ -328,6 +337,7 @@ SURFACE_HIT_DTYPE = _surface_hit_dtype()  # numpy structured dtype of SurfaceHit
 
 assert C.sizeof(SurfaceHit) == 96 and SURFACE_HIT_DTYPE.itemsize == 96
 assert C.sizeof(OcclusionParams) == 16
+assert C.sizeof(ProbeParams) == 80
 assert C.sizeof(TaaUpscaleParams) == 16
 assert C.sizeof(AutoExposureParams) == 64
 assert C.sizeof(ExposureState) == 32 + 1024
@@ -367,7 +377,9 @@ EXPORTED_SYMBOLS = [
     "rptr_hip_auto_exposure_defaults", "rptr_hip_auto_exposure", "rptr_hip_readback_exposed_u8", "rptr_hip_readback_exposure_state",
     "rptr_hip_bloom_defaults", "rptr_hip_bloom", "rptr_hip_readback_bloomed_u8", "rptr_hip_bloom_levels", "rptr_hip_readback_bloom_level_f32",
     "rptr_hip_track_object_motion", "rptr_hip_object_motion",
-    "rptr_hip_tile_rows", "rptr_hip_local_pixel_count", "rptr_hip_copy_tile_to_device", "rptr_hip_trace", "rptr_hip_trace_device", "rptr_hip_enable_ray_queries", "rptr_hip_render_ray_queries", "rptr_hip_trace_radiance", "rptr_hip_trace_radiance_device", "rptr_hip_render_radiance_queries", "rptr_hip_trace_surface", "rptr_hip_trace_surface_device", "rptr_hip_occlusion_defaults", "rptr_hip_trace_occlusion", "rptr_hip_trace_occlusion_device", "rptr_hip_set_light_sampling_variant", "rptr_hip_trace_counted",
+    "rptr_hip_tile_rows", "rptr_hip_local_pixel_count", "rptr_hip_copy_tile_to_device", "rptr_hip_trace", "rptr_hip_trace_device", "rptr_hip_enable_ray_queries", "rptr_hip_render_ray_queries", "rptr_hip_trace_radiance", "rptr_hip_trace_radiance_device", "rptr_hip_render_radiance_queries", "rptr_hip_trace_surface", "rptr_hip_trace_surface_device", "rptr_hip_occlusion_defaults", "rptr_hip_trace_occlusion", "rptr_hip_trace_occlusion_device",
+    "rptr_hip_probe_defaults", "rptr_hip_probe_directions", "rptr_hip_probe_rays_device", "rptr_hip_probe_project_device", "rptr_hip_trace_probes", "rptr_hip_trace_probes_device", "rptr_hip_readback_probe_rays",
+    "rptr_hip_set_light_sampling_variant", "rptr_hip_trace_counted",
     "rptr_hip_export_bvh", "rptr_hip_build_bvh_host", "rptr_hip_stats",
     "rptr_hip_comm_get_unique_id", "rptr_hip_comm_init_rank", "rptr_hip_comm_init_all", "rptr_hip_comm_destroy", "rptr_hip_comm_transport", "rptr_hip_comm_ipc_export", "rptr_hip_comm_ipc_init", "rptr_hip_gather", "rptr_hip_gather_all", "rptr_hip_gather_batch", "rptr_hip_gather_all_batch", "rptr_hip_readback_gathered_frame_f32",
     "rptr_hip_gathered_frame", "rptr_hip_readback_gathered_f32", "rptr_hip_comm_stats",

@@ -79,6 +79,14 @@ def load_library(path=None):
     L.rptr_hip_occlusion_defaults.restype = None
     L.rptr_hip_trace_occlusion.argtypes = [vp, vp, i32, C.POINTER(abi.OcclusionParams), vp]
     L.rptr_hip_trace_occlusion_device.argtypes = [vp, vp, i32, C.POINTER(abi.OcclusionParams), vp, vp]
+    L.rptr_hip_probe_defaults.argtypes = [C.POINTER(abi.ProbeParams)]
+    L.rptr_hip_probe_defaults.restype = None
+    L.rptr_hip_probe_directions.argtypes = [C.c_uint32, vp]
+    L.rptr_hip_probe_rays_device.argtypes = [vp, vp, C.c_uint32, C.POINTER(abi.ProbeParams), vp, vp]
+    L.rptr_hip_probe_project_device.argtypes = [vp, vp, C.c_uint32, vp, C.POINTER(abi.ProbeParams), vp, vp]
+    L.rptr_hip_trace_probes.argtypes = [vp, vp, C.c_uint32, C.POINTER(abi.Camera), i32, C.POINTER(abi.ProbeParams), vp, C.POINTER(abi.Stats)]
+    L.rptr_hip_trace_probes_device.argtypes = [vp, vp, C.c_uint32, C.POINTER(abi.Camera), i32, C.POINTER(abi.ProbeParams), vp, vp]
+    L.rptr_hip_readback_probe_rays.argtypes = [vp, vp, C.c_size_t]
     L.rptr_hip_set_light_sampling_variant.argtypes = [vp, i32]
     L.rptr_hip_set_freeze_frame.argtypes = [vp, i32]
     L.rptr_hip_set_option.argtypes = [vp, C.c_char_p, C.c_int64]
@@ -747,6 +755,65 @@ class RenderHip:
         p = self._occlusion_params(alpha_cutoff)
         self._check(self._L.rptr_hip_trace_occlusion_device(self._h, C.c_void_p(device_queries or 0), int(num_queries), C.byref(p), C.c_void_p(device_bits or 0),
                                                             C.c_void_p(stream or 0)))
+
+    # ---- irradiance probes: SH coefficients of the incident radiance at points (include/rptr_hip.h rptr_hip_trace_probes; probes.py)
+    @staticmethod
+    def probe_params(**fields):
+        """abi.ProbeParams: the library's defaults with `fields` set (rays_per_probe, samples_per_ray, sample_index, rotation -- nine
+        floats or a 3 x 3 array, row-major --, blend, clamp, t_max, max_run_rays; flags and reserved for the refusal tests)"""
+        p = abi.ProbeParams()
+        load_library().rptr_hip_probe_defaults(C.byref(p))
+        for name, value in fields.items():
+            if name not in dict(abi.ProbeParams._fields_):
+                raise TypeError("probe_params: unknown field %r" % name)
+            if name in ("rotation", "reserved"):
+                flat = np.asarray(value).reshape(-1)
+                getattr(p, name)[:] = [float(v) if name == "rotation" else int(v) for v in flat]
+            else:
+                setattr(p, name, value)
+        return p
+
+    def trace_probes(self, positions: np.ndarray, camera, variant=abi.VARIANT_GLTF, coeffs: np.ndarray = None, **fields) -> np.ndarray:
+        """positions: (n, 3) float32; camera: abi.Camera (its image-plane axes size the texture footprint); fields: probe_params().
+        Returns (n, 9, 4) float32: coeffs[p][i][ch], the L2 SH coefficients of the radiance arriving at probe p (channels r, g, b and
+        alpha = visibility of geometry), written into `coeffs` when given (read too: probes with a coordinate that is not finite keep
+        theirs, and blend < 1 blends into them). The frame in progress is left alone; the call's ray counts: radiance_query_stats()."""
+        pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+        n = len(pos)
+        coeffs = self._result_rows(coeffs, n, np.float32, (9, 4), "trace_probes", "a C-contiguous float32 array of n x 9 x 4")
+        p = self.probe_params(**fields)
+        self._push_params()
+        st = abi.Stats()
+        self._check(self._L.rptr_hip_trace_probes(self._h, pos.ctypes.data_as(C.c_void_p), n, C.byref(camera), int(variant), C.byref(p),
+                                                  coeffs.ctypes.data_as(C.c_void_p), C.byref(st)))
+        self._query_stats = st
+        return coeffs
+
+    def trace_probes_device(self, device_positions, n_probes, camera, device_coeffs, variant=abi.VARIANT_GLTF, stream=None, **fields):
+        """the same over DEVICE buffers (3 floats and 36 floats per probe), asynchronously on `stream` (None = the backend's)"""
+        p = self.probe_params(**fields)
+        self._push_params()
+        self._check(self._L.rptr_hip_trace_probes_device(self._h, C.c_void_p(device_positions or 0), int(n_probes), C.byref(camera), int(variant), C.byref(p),
+                                                         C.c_void_p(device_coeffs or 0), C.c_void_p(stream or 0)))
+
+    def probe_rays_device(self, device_positions, n_probes, device_queries, stream=None, **fields):
+        """the ray stage alone: n_probes x rays_per_probe RenderRayQuery records into device_queries, for any query kind"""
+        p = self.probe_params(**fields)
+        self._check(self._L.rptr_hip_probe_rays_device(self._h, C.c_void_p(device_positions or 0), int(n_probes), C.byref(p), C.c_void_p(device_queries or 0),
+                                                       C.c_void_p(stream or 0)))
+
+    def probe_project_device(self, device_values, n_probes, device_coeffs, device_positions=None, stream=None, **fields):
+        """the projection stage alone: n_probes x rays_per_probe float4 values -> 36 floats per probe; device_positions (optional): the
+        probes with a coordinate that is not finite keep their coefficients"""
+        p = self.probe_params(**fields)
+        self._check(self._L.rptr_hip_probe_project_device(self._h, C.c_void_p(device_values or 0), int(n_probes), C.c_void_p(device_positions or 0), C.byref(p),
+                                                          C.c_void_p(device_coeffs or 0), C.c_void_p(stream or 0)))
+
+    def readback_probe_rays(self, n_rays) -> np.ndarray:
+        """diagnostic: (n_rays, 4) float32, the ray values of the last run of the last trace_probes[_device] as the radiance run left them"""
+        out = np.zeros((int(n_rays), 4), np.float32)
+        self._check(self._L.rptr_hip_readback_probe_rays(self._h, out.ctypes.data_as(C.c_void_p), int(n_rays)))
+        return out
 
     def set_light_sampling_variant(self, variant):
         """RenderBackendOptions::light_sampling_variant: 0 = NONE (no NEE towards emissive triangles), 1 = RIS (default)"""

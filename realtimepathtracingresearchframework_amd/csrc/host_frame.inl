@@ -683,8 +683,9 @@ extern "C++" {
 // first_sample + s (frame_id seeds the alpha test of shadow rays and the blue-noise point set) -- one call of k samples and k calls of one
 // give the same bits.
 // totals != NULL: the ray counters of every batch are added to it (the host waits for each batch); NULL: nothing is waited for.
+// fresh (a probe run, host_queries.inl): the fold into `dr` counts from 0 instead of first_sample -- the mean of this run's samples alone.
 static int radiance_queries_on(rptr_hip_t *h, const RptrRenderRayQuery *dq, int n, const RptrCamera *camera, int variant, int spp, int first_sample, float4 *dr,
-                               hipStream_t st, RpCounters *totals) {
+                               hipStream_t st, RpCounters *totals, bool fresh = false) {
     if (n == 0) return RPTR_OK;
     FrameCtx &c = h->ctx[0];
     RpFrame f;
@@ -695,7 +696,7 @@ static int radiance_queries_on(rptr_hip_t *h, const RptrRenderRayQuery *dq, int 
     f.world = 1;
     f.stripe_rows = slice_rows;
     f.div_stripe_rows = rp_make_div((uint32_t)slice_rows);
-    const RpQueries rq = {dq, (uint32_t)n, 0u};
+    const RpQueries rq = {dq, (uint32_t)n, fresh ? RP_QUERIES_FRESH | (uint32_t)first_sample : 0u};
     PathRun run = {};
     run.c = &c;
     run.scene = &h->master.dscene;

@@ -1,8 +1,9 @@
 // host_queries.inl -- ray queries, four kinds behind ten entry points: closest hits (rptr_hip_trace, _trace_counted, _trace_device,
 // _render_ray_queries), path-traced radiance (rptr_hip_trace_radiance, _trace_radiance_device, _render_radiance_queries; the run itself is
 // host_frame.inl radiance_queries_on), surface records (rptr_hip_trace_surface, _trace_surface_device) and occlusion bits
-// (rptr_hip_trace_occlusion, _trace_occlusion_device). What the kinds share stands here once: the run preamble, the borrowed pool cursor,
-// the staging of host arrays, the budget of the backend's own buffers, the checks.
+// (rptr_hip_trace_occlusion, _trace_occlusion_device); and the irradiance probes built on the radiance kind (probes.h:
+// rptr_hip_trace_probes, _trace_probes_device, their two stages). What the kinds share stands here once: the run preamble, the borrowed
+// pool cursor, the staging of host arrays, the budget of the backend's own buffers, the checks.
 // Part of the ONE translation unit rptr_hip.hip (included there after host_access.inl).
 extern "C++" {
 // A query run borrows context 0 and nothing a frame owns: the traversals take its stack scratch and, as their pool cursor, its
@@ -368,6 +369,226 @@ int rptr_hip_trace_occlusion_device(rptr_hip_t *h, const RptrRenderRayQuery *dev
     }
     if ((rc = begin_query_run(h))) return rc;
     return on_callers_stream(h, hip_stream, [&](hipStream_t st) { return occlusion_queries_on(h, device_queries, n, p, device_out_bits, st); });
+}
+
+// ---- irradiance probes (probes.h): per run of whole probes the ray kernel, a radiance-query run with the fresh fold, the projection.
+void rptr_hip_probe_defaults(RptrProbeParams *out) {
+    if (!out) return;
+    memset(out, 0, sizeof(*out));
+    out->rays_per_probe = 128u;
+    out->samples_per_ray = 1u;
+    out->rotation[0] = out->rotation[4] = out->rotation[8] = 1.0f;
+    out->blend = 1.0f;
+    out->t_max = 1e20f;
+}
+
+int rptr_hip_probe_directions(uint32_t K, float *out3K) {
+    if (K < 1u || K > RPTR_PROBE_MAX_RAYS) return fail(nullptr, RPTR_E_INVALID, "probe directions: K = %u is outside 1 .. %u", K, RPTR_PROBE_MAX_RAYS);
+    if (!out3K) return fail(nullptr, RPTR_E_INVALID, "probe directions: NULL output");
+    const double g = (std::sqrt(5.0) - 1.0) / 2.0, two_pi = 2.0 * 3.14159265358979323846;
+    for (uint32_t k = 0; k < K; ++k) {
+        const double z = 1.0 - (2.0 * (double)k + 1.0) / (double)K;
+        const double kg = (double)k * g;
+        const double phi = two_pi * (kg - std::floor(kg));
+        const double r = std::sqrt(std::max(0.0, 1.0 - z * z));
+        out3K[3 * k] = (float)(r * std::cos(phi));
+        out3K[3 * k + 1] = (float)(r * std::sin(phi));
+        out3K[3 * k + 2] = (float)z;
+    }
+    return RPTR_OK;
+}
+
+extern "C++" {
+static RptrProbeParams probe_params_or_defaults(const RptrProbeParams *params) {
+    RptrProbeParams p;
+    rptr_hip_probe_defaults(&p);
+    return params ? *params : p;
+}
+// the params alone: they need neither a handle nor a device. `p` is never NULL here (the entry points pass the defaults)
+static int check_probe_params(rptr_hip_t *h, const RptrProbeParams &p) {
+    const char *kind = "probes";
+    if (p.rays_per_probe < 1u || p.rays_per_probe > RPTR_PROBE_MAX_RAYS)
+        return fail(h, RPTR_E_INVALID, "%s: rays_per_probe = %u is outside 1 .. %u", kind, p.rays_per_probe, RPTR_PROBE_MAX_RAYS);
+    if (p.samples_per_ray < 1u) return fail(h, RPTR_E_INVALID, "%s: samples_per_ray must be >= 1", kind);
+    if (p.sample_index < 0) return fail(h, RPTR_E_INVALID, "%s: sample_index must be >= 0", kind);
+    if ((unsigned long long)p.sample_index + p.samples_per_ray > 0x7fffffffull) return fail(h, RPTR_E_INVALID, "%s: sample_index + samples_per_ray overflows", kind);
+    if (p.flags != 0u) return fail(h, RPTR_E_INVALID, "%s: unknown flag bits 0x%x", kind, p.flags);
+    if (p.reserved[0] != 0u || p.reserved[1] != 0u || p.reserved[2] != 0u) return fail(h, RPTR_E_INVALID, "%s: reserved words must be 0", kind);
+    if (!(std::isfinite(p.blend) && p.blend > 0.0f && p.blend <= 1.0f)) return fail(h, RPTR_E_INVALID, "%s: blend must be finite and in (0, 1]", kind);
+    if (!(std::isfinite(p.clamp) && p.clamp >= 0.0f)) return fail(h, RPTR_E_INVALID, "%s: clamp must be finite and >= 0", kind);
+    if (!(p.t_max > 0.0f)) return fail(h, RPTR_E_INVALID, "%s: t_max must be > 0", kind);
+    for (int i = 0; i < 9; ++i)
+        if (!std::isfinite(p.rotation[i])) return fail(h, RPTR_E_INVALID, "%s: rotation[%d] is not finite", kind, i);
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) {
+            double dot = 0.0;
+            for (int k = 0; k < 3; ++k) dot += (double)p.rotation[3 * r + k] * (double)p.rotation[3 * c + k];
+            if (!(std::fabs(dot - (r == c ? 1.0 : 0.0)) <= 1e-3))
+                return fail(h, RPTR_E_INVALID, "%s: rotation is not orthonormal: (R R^T)[%d][%d] = %g", kind, r, c, dot);
+        }
+    return RPTR_OK;
+}
+static RpProbeConst probe_constants(const RptrProbeParams &p) {
+    RpProbeConst c;
+    memcpy(c.rot, p.rotation, sizeof(c.rot));
+    c.t_max = p.t_max;
+    c.clamp = p.clamp;
+    c.blend = p.blend;
+    c.weight = (float)(4.0 * 3.14159265358979323846 / (double)p.rays_per_probe);
+    c.K = p.rays_per_probe;
+    return c;
+}
+// the direction table of K on the device: computed and uploaded when K changes, kept otherwise
+static int probe_table(rptr_hip_t *h, uint32_t K) {
+    if (h->pb_dirs && h->pb_dirs_K == K) return RPTR_OK;
+    HIP_TRY(h, hipStreamSynchronize(h->stream)); // (an earlier run -- on a caller's stream too: the backend's is ordered behind it -- may still read the old table)
+    if (!h->pb_dirs && hipMalloc((void **)&h->pb_dirs, (size_t)RPTR_PROBE_MAX_RAYS * 3 * sizeof(float)) != hipSuccess) {
+        h->pb_dirs = nullptr;
+        return fail(h, RPTR_E_NOMEM, "hipMalloc of the probe direction table failed");
+    }
+    std::vector<float> table((size_t)K * 3);
+    const int rc = rptr_hip_probe_directions(K, table.data());
+    if (rc) return rc;
+    h->pb_dirs_K = 0;
+    HIP_TRY(h, hipMemcpy(h->pb_dirs, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice));
+    h->pb_dirs_K = K;
+    return RPTR_OK;
+}
+// 48 bytes per ray: the records of `rays` rays, then their values; holds the largest run seen
+static int probe_scratch(rptr_hip_t *h, size_t rays) {
+    if (rays <= h->pb_capacity) return RPTR_OK;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (h->pb_scratch) (void)hipFree(h->pb_scratch);
+    h->pb_scratch = nullptr;
+    h->pb_capacity = 0;
+    h->pb_last_rays = 0;
+    if (hipMalloc(&h->pb_scratch, rays * 48) != hipSuccess) {
+        h->pb_scratch = nullptr;
+        return fail(h, RPTR_E_NOMEM, "hipMalloc of the probe scratch (%zu rays) failed", rays);
+    }
+    h->pb_capacity = rays;
+    return RPTR_OK;
+}
+static int probe_rays_on(rptr_hip_t *h, const float *dpos, uint32_t n_probes, const RpProbeConst &c, RptrRenderRayQuery *dq, hipStream_t st) {
+    const uint32_t n_rays = n_probes * c.K;
+    hipLaunchKernelGGL(rp_k_probe_rays, dim3((unsigned)grid_for(h, n_rays)), dim3(256), 0, st, dpos, n_rays, c, (const float *)h->pb_dirs, reinterpret_cast<float4 *>(dq));
+    HIP_TRY(h, hipGetLastError());
+    return RPTR_OK;
+}
+static int probe_project_on(rptr_hip_t *h, const float4 *dvalues, uint32_t n_probes, const float *dpos, const RpProbeConst &c, float *dcoeffs, hipStream_t st) {
+    // one wave per probe, four to a block
+    hipLaunchKernelGGL(rp_k_probe_project, dim3((unsigned)grid_for(h, (size_t)n_probes * 64)), dim3(256), 0, st, dvalues, dpos, n_probes, c, (const float *)h->pb_dirs,
+                       reinterpret_cast<float4 *>(dcoeffs));
+    HIP_TRY(h, hipGetLastError());
+    return RPTR_OK;
+}
+static int check_probe_stage(rptr_hip_t *h, const char *stage, uint32_t n_probes, const RptrProbeParams &p, const char *missing_buffer) {
+    int rc = check_probe_params(h, p);
+    if (rc) return rc;
+    if (n_probes > 0 && missing_buffer) return fail(h, RPTR_E_INVALID, "probes: %s: %s", stage, missing_buffer);
+    if ((unsigned long long)n_probes * p.rays_per_probe > 0x7fffffffull)
+        return fail(h, RPTR_E_INVALID, "probes: %s: %u probes x %u rays exceed 2^31 - 1 rays", stage, n_probes, p.rays_per_probe);
+    if (!h) return fail(nullptr, RPTR_E_INVALID, "NULL handle");
+    return RPTR_OK;
+}
+static uint32_t probes_per_run(const RptrProbeParams &p) {
+    const uint32_t R = p.max_run_rays ? p.max_run_rays : (1u << 22);
+    return std::max(1u, R / p.rays_per_probe);
+}
+static int check_probe_arguments(rptr_hip_t *h, const void *positions, uint32_t n_probes, const RptrCamera *camera, int variant, const RptrProbeParams &p,
+                                 const void *coeffs) {
+    const int rc = check_probe_params(h, p); // (the arguments come first: they need neither a handle nor a device; the handle: check_camera_queries)
+    if (rc) return rc;
+    if (n_probes > 0x7fffffffu) return fail(h, RPTR_E_INVALID, "probes: n_probes = %u is too large", n_probes);
+    return check_camera_queries(h, "probes", (int)n_probes, camera, variant, n_probes > 0 && (!positions || !coeffs) ? "NULL position or coefficient buffer" : nullptr);
+}
+// queues every run of the call on `st` for DEVICE buffers; the scratch holds a run
+static int probes_on(rptr_hip_t *h, const float *dpos, uint32_t n_probes, const RptrCamera *camera, int variant, const RptrProbeParams &p, float *dcoeffs, hipStream_t st,
+                     RpCounters *totals) {
+    const RpProbeConst c = probe_constants(p);
+    const uint32_t per_run = probes_per_run(p);
+    RptrRenderRayQuery *records = static_cast<RptrRenderRayQuery *>(h->pb_scratch);
+    float4 *values = reinterpret_cast<float4 *>(static_cast<char *>(h->pb_scratch) + h->pb_capacity * 32);
+    for (uint32_t p0 = 0; p0 < n_probes; p0 += per_run) {
+        const uint32_t np = std::min(per_run, n_probes - p0);
+        const int n_rays = (int)(np * c.K);
+        int rc = probe_rays_on(h, dpos + 3ull * p0, np, c, records, st);
+        if (rc) return rc;
+        HIP_TRY(h, hipMemsetAsync(values, 0, (size_t)n_rays * sizeof(float4), st)); // (the rays of skipped probes read 0)
+        if ((rc = radiance_queries_on(h, records, n_rays, camera, variant, (int)p.samples_per_ray, p.sample_index, values, st, totals, true))) return rc;
+        if ((rc = probe_project_on(h, values, np, dpos + 3ull * p0, c, dcoeffs + 36ull * p0, st))) return rc;
+        h->pb_last_rays = (size_t)n_rays;
+    }
+    return RPTR_OK;
+}
+static size_t probe_run_rays(uint32_t n_probes, const RptrProbeParams &p) { return (size_t)std::min(n_probes, probes_per_run(p)) * p.rays_per_probe; }
+} // extern "C++"
+
+int rptr_hip_probe_rays_device(rptr_hip_t *h, const float *device_positions3, uint32_t n_probes, const RptrProbeParams *params, RptrRenderRayQuery *device_queries,
+                               void *hip_stream) {
+    const RptrProbeParams p = probe_params_or_defaults(params);
+    int rc = check_probe_stage(h, "ray stage", n_probes, p, !device_positions3 || !device_queries ? "NULL position or record buffer" : nullptr);
+    if (rc || n_probes == 0) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    if ((rc = probe_table(h, p.rays_per_probe))) return rc;
+    return on_callers_stream(h, hip_stream, [&](hipStream_t st) { return probe_rays_on(h, device_positions3, n_probes, probe_constants(p), device_queries, st); });
+}
+
+int rptr_hip_probe_project_device(rptr_hip_t *h, const float *device_values4, uint32_t n_probes, const float *device_positions3, const RptrProbeParams *params,
+                                  float *device_coeffs36, void *hip_stream) {
+    const RptrProbeParams p = probe_params_or_defaults(params);
+    int rc = check_probe_stage(h, "projection stage", n_probes, p, !device_values4 || !device_coeffs36 ? "NULL value or coefficient buffer" : nullptr);
+    if (rc || n_probes == 0) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    if ((rc = probe_table(h, p.rays_per_probe))) return rc;
+    return on_callers_stream(h, hip_stream, [&](hipStream_t st) {
+        return probe_project_on(h, reinterpret_cast<const float4 *>(device_values4), n_probes, device_positions3, probe_constants(p), device_coeffs36, st);
+    });
+}
+
+int rptr_hip_trace_probes(rptr_hip_t *h, const float *positions3, uint32_t n_probes, const RptrCamera *camera, int variant, const RptrProbeParams *params, float *coeffs36,
+                          RptrStats *out_stats) {
+    const RptrProbeParams p = probe_params_or_defaults(params);
+    int rc = check_probe_arguments(h, positions3, n_probes, camera, variant, p, coeffs36);
+    if (rc || n_probes == 0) return rc;
+    if ((rc = begin_query_run(h)) || (rc = probe_table(h, p.rays_per_probe)) || (rc = probe_scratch(h, probe_run_rays(n_probes, p)))) return rc;
+    if (out_stats) memset(out_stats, 0, sizeof(*out_stats));
+    RpCounters tot;
+    memset(&tot, 0, sizeof(tot));
+    HostSpan spans[2] = {{const_cast<float *>(positions3), (size_t)n_probes * 3 * sizeof(float), SPAN_UP, nullptr},
+                         {coeffs36, (size_t)n_probes * 36 * sizeof(float), SPAN_UP | SPAN_DOWN, nullptr}}; // (up: skipped probes, blend < 1)
+    rc = run_on_host_arrays(h, "probe kernels", spans, 2, [&](hipStream_t st, const HostSpan *s) {
+        return probes_on(h, (const float *)s[0].dev, n_probes, camera, variant, p, (float *)s[1].dev, st, &tot);
+    });
+    if (!rc && out_stats) {
+        out_stats->rays_closest = tot.rays_closest;
+        out_stats->rays_shadow = tot.rays_shadow;
+        out_stats->hits_shaded = tot.hits_shaded;
+        out_stats->spp = (int)p.samples_per_ray;
+        out_stats->device_bytes_allocated = h->bytes_allocated;
+    }
+    return rc;
+}
+
+int rptr_hip_trace_probes_device(rptr_hip_t *h, const float *device_positions3, uint32_t n_probes, const RptrCamera *camera, int variant, const RptrProbeParams *params,
+                                 float *device_coeffs36, void *hip_stream) {
+    const RptrProbeParams p = probe_params_or_defaults(params);
+    int rc = check_probe_arguments(h, device_positions3, n_probes, camera, variant, p, device_coeffs36);
+    if (rc || n_probes == 0) return rc;
+    if ((rc = begin_query_run(h)) || (rc = probe_table(h, p.rays_per_probe)) || (rc = probe_scratch(h, probe_run_rays(n_probes, p)))) return rc;
+    return on_callers_stream(h, hip_stream, [&](hipStream_t st) { return probes_on(h, device_positions3, n_probes, camera, variant, p, device_coeffs36, st, nullptr); });
+}
+
+int rptr_hip_readback_probe_rays(rptr_hip_t *h, float *out4, size_t n_rays) {
+    if (!h) return fail(nullptr, RPTR_E_INVALID, "NULL handle");
+    if (!out4 && n_rays > 0) return fail(h, RPTR_E_INVALID, "readback_probe_rays: NULL output");
+    if (!h->pb_scratch || h->pb_last_rays == 0) return fail(h, RPTR_E_INVALID, "readback_probe_rays: no probe run yet");
+    if (n_rays > h->pb_last_rays) return fail(h, RPTR_E_INVALID, "readback_probe_rays: %zu rays asked for, the last run had %zu", n_rays, h->pb_last_rays);
+    if (n_rays == 0) return RPTR_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, hipMemcpy(out4, static_cast<char *>(h->pb_scratch) + h->pb_capacity * 32, n_rays * sizeof(float4), hipMemcpyDeviceToHost));
+    return RPTR_OK;
 }
 
 // ---- object motion (object_motion.h): the tracking of the previous frame's state, and the pass over the last submitted frame's

@@ -406,6 +406,14 @@ struct rptr_hip {
     // rptr_hip_initialize / rptr_hip_destroy
     void *sq_raw = nullptr;
     size_t sq_capacity = 0;
+    // irradiance probes (probes.h): the direction table of the last K (12 bytes per direction, room for RPTR_PROBE_MAX_RAYS), and the
+    // scratch of rptr_hip_trace_probes -- per ray of a run a 32-byte query record, then a 16-byte value; grows to the largest run seen.
+    // Nothing is allocated before the first probe call; freed by rptr_hip_destroy
+    float *pb_dirs = nullptr;
+    uint32_t pb_dirs_K = 0;
+    void *pb_scratch = nullptr;
+    size_t pb_capacity = 0;  // rays
+    size_t pb_last_rays = 0; // rays of the last run of rptr_hip_trace_probes[_device] (rptr_hip_readback_probe_rays)
     bool lights_disabled = false;   // light_sampling_variant == LIGHT_SAMPLING_VARIANT_NONE: no area-light NEE (rptr_hip_set_light_sampling_variant)
     bool aovs = true;               // the reference writes its AOV images with every frame (ENABLE_AOV_BUFFERS, render_vulkan.cpp:2083-2086)
     RptrCamera prev_camera;         // the previous frame's view (VP_reference)

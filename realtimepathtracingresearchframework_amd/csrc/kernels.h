@@ -194,8 +194,10 @@ RP_DEV bool rp_primary_ray(const RpFrame &f, uint32_t p, RpRng &rng, V3 &dir, V3
 struct RpQueries {
     const RptrRenderRayQuery *records; // origin.xyz, mode_or_data | dir.xyz, t_max
     uint32_t n;
-    uint32_t _pad;
+    uint32_t flags; // 0: the fold of rp_k_resolve_queries counts from sample_index. RP_QUERIES_FRESH | first sample index of the run: it counts
+                    // from 0 (probes.h; kernels_misc.h rp_k_resolve_queries is the one reader)
 };
+#define RP_QUERIES_FRESH 0x80000000u
 // the query of path p; false: the slot names none (tile padding, or behind the last query)
 RP_DEV bool rp_query_of_path(const RpFrame &f, const RpQueries &rq, uint32_t p, uint32_t &q, uint32_t &sslot, int &lx, int &gy) {
     sslot = rp_div(p, f.div_npix_padded);

@@ -134,6 +134,8 @@ __global__ __launch_bounds__(256) void rp_k_resolve(RpFrame f, RpPathState ps, f
 //   - its layers (samples of one dispatch) read and write the same slot without order ("todo: atomic support required?"). Here the
 //     samples of a query are folded by one thread.
 //   - records with mode_or_data < 0 keep their slot (the convention of rp_k_trace; the megakernel does not read the field).
+// rq.flags & RP_QUERIES_FRESH (a probe run, probes.h): the low 31 bits hold the run's first sample index, and the fold counts from it -- the
+// result is the running mean of this run's samples alone, whatever indices their random numbers have. flags == 0: as above, bit for bit.
 __global__ __launch_bounds__(256) void rp_k_resolve_queries(RpFrame f, RpPathState ps, RpQueries rq, float4 *results) {
     const uint32_t first = uint32_t(rp_local_row_to_global(f, 0)) * uint32_t(f.width); // the slice's rows are consecutive rows of the virtual image
     const uint32_t count = uint32_t(f.width) * uint32_t(f.local_rows);
@@ -143,12 +145,13 @@ __global__ __launch_bounds__(256) void rp_k_resolve_queries(RpFrame f, RpPathSta
         if (rq.records[q].mode_or_data < 0) continue;
         const int ly = int(rp_div(i, f.div_width)), lx = int(i) - ly * f.width;
         const uint32_t slot = rp_local_to_slot(f, lx, ly);
+        const uint32_t fold_base = f.sample_base - ((rq.flags & RP_QUERIES_FRESH) ? (rq.flags & ~RP_QUERIES_FRESH) : 0u);
         float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (f.sample_base > 0u) acc = results[q];
+        if (fold_base > 0u) acc = results[q];
         for (int s = 0; s < f.batch_spp; ++s) {
             const float4 il = ps.illum[size_t(s) * size_t(f.npix_padded) + slot];
             const float4 c = make_float4(il.x, il.y, il.z, __float_as_int(il.w) == 0 ? 0.0f : 1.0f); // pt_megakernel.glsl:736
-            const uint32_t sample_index = f.sample_base + uint32_t(s);
+            const uint32_t sample_index = fold_base + uint32_t(s);
             if (sample_index == 0)
                 acc = c;
             else {

@@ -17,6 +17,7 @@
 #include "bloom.h"
 #include "surface_query.h"
 #include "occlusion_query.h"
+#include "probes.h"
 #include "object_motion.h"
 #include "launch.h"
 #include "lbvh.h"
@@ -210,6 +211,8 @@ void rptr_hip_destroy(rptr_hip_t *h) {
     if (h->rq_queries) (void)hipFree(h->rq_queries);
     if (h->rq_results) (void)hipFree(h->rq_results);
     if (h->sq_raw) (void)hipFree(h->sq_raw);
+    if (h->pb_dirs) (void)hipFree(h->pb_dirs);
+    if (h->pb_scratch) (void)hipFree(h->pb_scratch);
     delete h;
 }
 

@@ -16,6 +16,7 @@
 namespace rptr {
 
 static_assert(sizeof(RptrOcclusionParams) == 16, "RptrOcclusionParams: flags, alpha_cutoff, two reserved words (include/rptr_hip.h)");
+static_assert(sizeof(RptrProbeParams) == 80, "RptrProbeParams: four words, the rotation, blend / clamp / t_max, max_run_rays, three reserved words (include/rptr_hip.h)");
 static_assert(sizeof(RptrDenoiseTemporalParams) == 64, "RptrDenoiseTemporalParams: ten parameters and six reserved words (include/rptr_hip.h)");
 static_assert(sizeof(RptrTaaUpscaleParams) == 16, "RptrTaaUpscaleParams: factor, reset_history, two reserved words (include/rptr_hip.h)");
 static_assert(sizeof(RptrBloomParams) == 64, "RptrBloomParams: four switches, five parameters, three gains, four reserved words (include/rptr_hip.h)");
@@ -621,6 +622,26 @@ public:
         if (num_queries < 0) return false;
         const RptrOcclusionParams p = occlusion_params(alpha_cutoff);
         check(rptr_hip_trace_occlusion(h_, queries, num_queries, &p, bits));
+        return true;
+    }
+    // Irradiance probes (include/rptr_hip.h rptr_hip_trace_probes): 3 floats of position per probe in, 36 floats out -- coeffs[p][i][ch], the
+    // L2 SH coefficients of the radiance arriving at the probe, channels r, g, b and alpha (visibility of geometry). params: nullptr = the
+    // defaults of rptr_hip_probe_defaults; a per-frame loop sets rotation, sample_index and blend. `camera` supplies the image-plane axes of
+    // the texture footprint, render_params become the handle's. Over DEVICE buffers of the caller's, asynchronously on `hip_stream`
+    // (nullptr: the backend's) ...
+    bool trace_probes(const float *device_positions3, uint32_t num_probes, const RptrRenderParams &render_params, int variant_idx, const RenderCameraParams &camera,
+                      const RptrProbeParams *params, float *device_coeffs36, void *hip_stream) {
+        check(rptr_hip_set_params(h_, &render_params, nullptr, nullptr));
+        const RptrCamera cam = to_abi(camera);
+        check(rptr_hip_trace_probes_device(h_, device_positions3, num_probes, &cam, variant_idx, params, device_coeffs36, hip_stream));
+        return true;
+    }
+    // ... and over HOST arrays, synchronously (coeffs36 is read as well as written: skipped probes keep theirs, blend < 1 blends into them)
+    bool trace_probes(const float *positions3, uint32_t num_probes, const RptrRenderParams &render_params, int variant_idx, const RenderCameraParams &camera,
+                      const RptrProbeParams *params, float *coeffs36) {
+        check(rptr_hip_set_params(h_, &render_params, nullptr, nullptr));
+        const RptrCamera cam = to_abi(camera);
+        check(rptr_hip_trace_probes(h_, positions3, num_probes, &cam, variant_idx, params, coeffs36, nullptr));
         return true;
     }
     // convenience over HOST arrays (tests, tools): rptr_hip_trace uploads, traces, reads back
